@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
 """Headline benchmark of the hot path (driver contract: see the task statement / DESIGN.md §Measurement).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps of the headline workload and prints the line; `--dump-outputs DIR` also
+writes the last timed step's outputs (dump_outputs()).  Everything else below -- the single-step distribution, the
+all-reduce alone, the roofline, the extra keys and the CPU baselines -- runs only with `--full`.
 
 A "step" = one fused training step (q_sample -> denoiser fwd -> eps-MSE -> bwd -> [RCCL grad all-reduce] ->
 fused optimizer) over one batch of synthetic motion windows already resident in HBM.  Headline workload = the
 largest single-GPU training configuration of BASELINE.json: configs[2], the 4-layer d_model = 512 transformer denoiser at
 T = 50, D = 300, bf16 storage / fp32 accumulate, per-GPU batch 256; at N > 1 the same model data-parallel = configs[3]
 (weak scaling: global batch 256 N).  The MLP denoiser (configs[1]), the DDIM loop (configs[4]) and the reference-shape
-regression step (configs[0]) ride as extra keys; a compact `summary` object comes LAST in the line, so a truncated tail
-still carries every headline figure.  Rank 0 prints ONE JSON line.
+regression step (configs[0]) ride as extra keys (`--full`); a compact `summary` object comes LAST in the line, so a
+truncated tail still carries every headline figure.  Rank 0 prints ONE JSON line.
 """
 import argparse
 import json
@@ -467,9 +471,37 @@ def algorithmic_bytes_per_step(kind, T, D, B, nparams):
     return B * per_window + 7 * 4 * nparams
 
 
-def train_leg(workload, a, dev, world, rank, steps, warmup, sync, with_roofline=True):
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(trainer, out_dir):
+    """--dump-outputs: what the timed path hands its caller after its last step -- that step's loss, every parameter as the
+    optimizer left it, and the optimizer's state under torch.optim's names -- one float32 `<name>.npy` per array.  Should
+    the files exceed DUMP_MAX_BYTES (the transformer denoiser's 13.3 M parameters + RMSprop state: 106 MB), every array is
+    cut down to the same fraction of its elements at fixed positions (seed 0, flattened, ascending)."""
+    import numpy as np
+    arrays = {"loss": trainer.result[:1]}
+    for name, (off, n) in trainer.layout.items():
+        shape = trainer._params[name].shape
+        arrays["param." + name] = trainer.flat[off:off + n].view(shape)
+        for key, buf in zip(trainer.TORCH_STATE_KEYS[trainer.opt_type], (trainer.s1, trainer.s2)):
+            arrays[f"opt.{key}.{name}"] = buf[off:off + n].view(shape)
+    total = sum(4 * v.numel() for v in arrays.values())
+    frac = min(1.0, (DUMP_MAX_BYTES - 256 * len(arrays)) / total)       # 256 bytes per file: room for the .npy header
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        v = v.detach().float().cpu()
+        if frac < 1.0:
+            k = max(1, int(v.numel() * frac))
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), v.numpy())
+
+
+def train_leg(workload, a, dev, world, rank, steps, warmup, sync, with_roofline=True, full=True, dump_dir=None):
     """one training workload: W warm-up steps, EXACTLY K timed steps between barriers + synchronisations, max over
-    ranks; then the single-step distribution and (rank 0) the per-launch roofline table."""
+    ranks; then (rank 0, `dump_dir`) the outputs of the last timed step, and with `full` the single-step distribution,
+    the all-reduce alone and (rank 0) the per-launch roofline table."""
     from inferbiomechanics_amd.engine import HipTrainer
     kind, T, D, B = WORKLOADS[workload]
     dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
@@ -503,22 +535,25 @@ def train_leg(workload, a, dev, world, rank, steps, warmup, sync, with_roofline=
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.cpu())
     loss = trainer.loss_value()
+    if dump_dir is not None and rank == 0:
+        dump_outputs(trainer, dump_dir)
 
     # distribution of single-step times (median, p10 / p90): one event per step on the caller's stream,
     # read back after the run -- no host synchronisation inside it
     rehearsal = os.environ.get("IB_BENCH_REHEARSAL") == "1"      # one GPU, gloo: every all-reduce goes through the host
     nq = 6 if rehearsal else max(20, min(steps, 400))
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(nq + 1)]
-    evs[0].record()
-    for i in range(nq):
-        trainer.step(batches[i % len(batches)])
-        evs[i + 1].record()
-    sync()
-    dts = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(nq))
-    pct = lambda q: round(dts[min(nq - 1, int(q * nq))], 4)
+    if full:
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(nq + 1)]
+        evs[0].record()
+        for i in range(nq):
+            trainer.step(batches[i % len(batches)])
+            evs[i + 1].record()
+        sync()
+        dts = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(nq))
+        pct = lambda q: round(dts[min(nq - 1, int(q * nq))], 4)
 
     xg = None
-    if world > 1 and trainer.ddp:
+    if full and world > 1 and trainer.ddp:
         # the gradient all-reduce alone (same buffer, same communicator): bus bandwidth against the xGMI peak
         g = trainer.grad
         for _ in range(3):
@@ -547,7 +582,6 @@ def train_leg(workload, a, dev, world, rank, steps, warmup, sync, with_roofline=
         hbm = algorithmic_bytes_per_step(kind, T, D, B, nparams) * world / (el / steps) / 1e9
         out = {"workload": f"{workload}_D{D}_B{B}_{a.dtype}", "value": round(value, 1), "unit": "windows/s",
                "ms_per_step": round(el / steps * 1e3, 4), "steps": steps, "warmup": warmup,
-               "step_ms": {"p10": pct(0.10), "median": pct(0.50), "p90": pct(0.90), "samples": nq},
                "final_loss": round(loss, 6), "train_tflops": round(tfl, 2),
                "captures_in_timed_region": trainer.captures - cap0,
                "config": {"per_gpu_batch": B, "global_batch": B * world, "window": T, "feat": D, "optimizer": a.opt_type,
@@ -561,6 +595,8 @@ def train_leg(workload, a, dev, world, rank, steps, warmup, sync, with_roofline=
                "step_fractions": {"mfma": round(tfl / world / PEAK_TFLOPS[a.dtype], 4),
                                   "hbm": round(hbm / world / PEAK_HBM_GBS, 4),
                                   "xgmi": None if xg is None else xg["frac"]}}
+        if full:
+            out["step_ms"] = {"p10": pct(0.10), "median": pct(0.50), "p90": pct(0.90), "samples": nq}
         if xg is not None:
             out["xgmi"] = xg
         if rec is not None:
@@ -679,6 +715,12 @@ def main():
                          "graph (about 15 us); 13 MiB = one transformer layer of the T=50 denoiser")
     ap.add_argument("--overlap-comm", default="auto", choices=["auto", "on", "off"],
                     help="data-parallel policy: all-reduce buckets during the backward (on) or once after it (off)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: single-step distribution, all-reduce alone, "
+                         "roofline, MLP denoiser, CPU baselines, CLI path, DDIM, reference-shape regression (the --no-* "
+                         "options pick among them); without it the run times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's last timed step's outputs (loss, parameters, optimizer state) as DIR/<name>.npy")
     a = ap.parse_args()
 
     # stdout carries exactly ONE line (the JSON): libraries that print banners to fd 1 (RCCL prints its version there
@@ -742,11 +784,12 @@ def main():
 
     kind, T, D, B = WORKLOADS[a.workload]
     dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
-    main_leg = train_leg(a.workload, a, dev, world, rank, a.steps, a.warmup, sync, with_roofline=not a.no_roofline)
+    main_leg = train_leg(a.workload, a, dev, world, rank, a.steps, a.warmup, sync, with_roofline=a.full and not a.no_roofline,
+                         full=a.full, dump_dir=a.dump_outputs)
     # BASELINE configs[1]: the token-wise MLP denoiser at T = 50, its own step count (0.13 ms steps); every rank takes part
     # (under data parallelism the step holds the all-reduces)
     mlp_leg = None
-    if kind != "mlp" and not a.no_mlp:
+    if a.full and kind != "mlp" and not a.no_mlp:
         mlp_leg = train_leg("mlp_denoiser_T50", a, dev, world, rank, 8 if rehearsal else 2000, 2 if rehearsal else 200, sync,
                             with_roofline=not a.no_roofline)
     variant = None
@@ -799,7 +842,7 @@ def main():
                                "processes")
             line["graph_collectives_variant"] = variant
             summary["other_collectives_form_ms"] = variant.get("ms_per_step", variant.get("error", variant.get("skipped")))
-        if not a.no_cpu_baseline and world == 1:            # rank 0 at N=1 only (the other ranks wait at the barrier)
+        if a.full and not a.no_cpu_baseline and world == 1:  # rank 0 at N=1 only (the other ranks wait at the barrier)
             line["cpu_baseline"] = cpu_baseline(kind, T, D, B, dev)
             ml = line["cpu_baseline"]["matched_loss"]
             summary["cpu_baseline"] = {"windows_per_s": line["cpu_baseline"]["value"], "cores": line["cpu_baseline"]["cores"],
@@ -823,13 +866,13 @@ def main():
                     summary["mlp_T50"]["cli_path_windows_per_s"] = cp["windows_per_s"]
             mlp_leg.pop("step_breakdown", None)             # the per-launch tables live in profiles/ (keeps the line short)
             line["mlp_T50"] = mlp_leg
-        if not a.no_ddim:
+        if a.full and not a.no_ddim:
             legs = [ddim_leg(dev, dtype, B=b) for b in (1, 16, 256)]          # B in {1, 16, 256}
             line["ddim"] = legs[1]                                            # B = 16: the quoted figure
             line["ddim_batches"] = [legs[0], legs[2]]
             summary["ddim_T200_steps_per_s"] = {f"B{b}": lg["steps_per_sec"] for b, lg in zip((1, 16, 256), legs)}
             summary["ddim_T200_mfma_frac"] = {f"B{b}": lg["roofline"]["frac"] for b, lg in zip((1, 16, 256), legs)}
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             # BASELINE.json configs[0]: the reference's own CPU-runnable case (plumbing; launch-latency bound on the GPU)
             line["regression_ref_shape"] = {
                 "workload": "FeedForwardBaseline([512,512], sigmoid) 1470->300, fp32, RMSprop 1e-4, reference loss "

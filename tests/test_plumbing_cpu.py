@@ -262,6 +262,39 @@ def test_bench_self_launch_relays_the_ranks_return_code():
     assert "needs a GPU" in r.stderr
 
 
+def test_bench_dump_outputs_layout_and_size_cap(dry, tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the loss, every parameter and the optimizer's state as float32 .npy files; whole arrays
+    while they fit, a fixed sample of every array when the files would pass the cap (the headline transformer + RMSprop)"""
+    import numpy as np
+    import bench
+    from inferbiomechanics_amd.engine import HipTrainer
+    m = bench.build_model("mlp", 50, 300, torch.bfloat16, torch.device("cpu"))
+    tr = HipTrainer(m, "diffusion", "adam", 1e-4, use_graph=False)
+    tr.result[0] = 0.25
+    tr.s1.copy_(torch.arange(tr.s1.numel(), dtype=torch.float32))
+    bench.dump_outputs(tr, str(tmp_path / "whole"))
+    names = [k for k, _ in m.named_parameters()]
+    assert sorted(os.listdir(tmp_path / "whole")) == sorted(["loss.npy"] + [f"{p}.{k}.npy" for k in names for p in (
+        "param", "opt.exp_avg", "opt.exp_avg_sq")])
+    assert np.load(tmp_path / "whole" / "loss.npy").tolist() == [0.25]
+    for k, v in m.named_parameters():
+        a = np.load(tmp_path / "whole" / f"param.{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, v.detach().float().numpy())
+    cap = 200_000
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", cap)
+    for d in ("a", "b"):
+        bench.dump_outputs(tr, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "whole"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= cap
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.size >= 1 and np.array_equal(a, b)                       # the same positions every run
+    k, off = names[0], tr.layout[names[0]][0]
+    s = np.load(tmp_path / "a" / f"opt.exp_avg.{k}.npy") - off            # s1 holds its own flat index
+    assert np.all(np.diff(s) > 0) and s[0] >= 0 and s[-1] < tr.layout[k][1]
+
+
 def test_mask_seed_mixes_torch_seed_rank_and_layer(monkeypatch):
     """plans.mask_seed: torch.manual_seed selects the dropout stream, data-parallel ranks and stacked transformer layers
     draw different masks (the reference's nn.Dropout draws independently per module and per process)"""

@@ -329,7 +329,7 @@ def test_bench_data_parallel_launch_sequence_on_one_rank():
         if ddp:
             env.update(IB_DDP_SELFTEST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547", RANK="0", WORLD_SIZE="1",
                        LOCAL_RANK="0")
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "40", "--warmup", "4",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "40", "--warmup", "4", "--full",
                             "--no-cpu-baseline", "--no-ddim"], capture_output=True, text=True, env=env, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -369,7 +369,7 @@ def test_bench_two_rank_control_flow_rehearsal():
     for k in ("IB_DDP_SELFTEST", "RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3",
-                        "--no-ddim", "--no-cpu-baseline", "--batches", "16"],
+                        "--full", "--no-ddim", "--no-cpu-baseline", "--batches", "16"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -381,6 +381,44 @@ def test_bench_two_rank_control_flow_rehearsal():
     assert "configs[3]" in o["config"]["workload"]
     assert o["mlp_T50"]["config"]["parallelism"] == "dp2" and o["mlp_T50"]["config"]["grad_buckets"] == 1
     assert list(o)[-1] == "summary"
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: the headline leg only (no extra keys), K
+    timed steps, and the last timed step's outputs written; two runs with the same arguments dump the same bits (every
+    reduction has a fixed order) and the dumped loss is the line's final_loss"""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("IB_DDP_SELFTEST", "RANK", "WORLD_SIZE", "LOCAL_RANK", "IB_GRAPH_COLLECTIVES"):
+        env.pop(k, None)
+    outs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3",
+                            "--batches", "8", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[:500]
+        outs.append(json.loads(lines[0]))
+    o = outs[0]
+    assert o["metric"] == "motion-windows/sec training (+ DDIM steps/sec)" and o["unit"] == "windows/s"
+    assert o["higher_is_better"] is True and o["dtype"] == "bf16" and o["steps"] == 12 and o["warmup"] == 3
+    assert o["ms_per_step"] > 0 and abs(o["value"] - 256 * 1e3 / o["ms_per_step"]) <= 1e-3 * o["value"]
+    assert not {"step_ms", "roofline", "mlp_T50", "ddim", "cpu_baseline", "regression_ref_shape"} & set(o)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "loss.npy" in files
+    assert any(f.startswith("param.") for f in files) and any(f.startswith("opt.square_avg.") for f in files)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10 ** 6
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), f
+    assert round(float(np.load(tmp_path / "a" / "loss.npy")[0]), 6) == o["final_loss"] == outs[1]["final_loss"]
 
 
 def test_nested_branch_fork_is_refused():
