@@ -1,7 +1,11 @@
 """Kernel-level parity: every C-ABI entry point against float64 restatements (oracle / plain math)
 on seeded inputs.  Tolerances: fp32 mode <= 1e-3 relative (north_star; in practice ~1e-6), bf16 mode
-<= 3e-2 relative to the tensor's max magnitude (bf16 storage has 8 significant bits).  Index / table
-ops (gathers, schedule tables) are bit-exact.  GPU only."""
+<= 3e-2 relative to the tensor's max magnitude (bf16 storage has 8 significant bits).  The GEMM tests
+(linear fwd / dgrad, the small-M tiles) also bound every element on its own (close_gemm): one bf16
+rounding of the result, 2^-8 |e|, plus fp32 accumulation, K 2^-23 (|x| @ |w|^T), with e the float64
+product of the stored (rounded) operands -- a bias or tile lost on a single column fails there even when
+it hides under 3e-2 of the maximum.  Index / table ops (gathers, schedule tables) are bit-exact.
+GPU only."""
 import math
 
 import numpy as np
@@ -42,6 +46,20 @@ def close(actual, expected, rtol, what=""):
     assert err <= rtol * ref, f"{what}: max err {err:.3e} > {rtol:.1e} * {ref:.3e}"
 
 
+def close_gemm(actual, expected, x, w, what, act_scale=1.0):
+    """elementwise: |a - e| <= 2^-8 |e| + K 2^-23 act_scale (|x| @ |w|^T)  (x [M, K], w [N, K]; K = reduction length).
+    act_scale: bound on |act'| for an activation or activation-derivative epilogue"""
+    a = actual.detach().to("cpu", torch.float64)
+    e = expected.detach().to("cpu", torch.float64)
+    assert a.shape == e.shape, (what, a.shape, e.shape)
+    assert torch.isfinite(a).all(), f"{what}: non-finite values"
+    xa, wa = x.detach().to("cpu", torch.float64).abs(), w.detach().to("cpu", torch.float64).abs()
+    bound = 2.0 ** -8 * e.abs() + xa.shape[1] * 2.0 ** -23 * act_scale * (xa @ wa.T)
+    bad = (a - e).abs() > bound
+    assert not bad.any(), f"{what}: {int(bad.sum())} elements out of bound, first at {bad.nonzero()[0].tolist()}: " \
+                          f"{a[tuple(bad.nonzero()[0])].item()} vs {e[tuple(bad.nonzero()[0])].item()}"
+
+
 def test_tr16_transposing_read_layout(hip):
     """ds_read_b64_tr_b16 must deliver in[8*(lane/16)+q][lane%16] as element q (what gemm.hip assumes)."""
     img = torch.arange(64 * 16, dtype=torch.int16).reshape(64, 16)
@@ -69,6 +87,7 @@ def test_linear_fwd(hip, dtype, M, N, K):
     hip.linear_fwd(x.to(DEV), w.to(DEV), b.to(DEV), y)
     exp = x.double() @ w.double().T + b.double()
     close(y, exp, TIGHT[dtype], "linear_fwd")
+    close_gemm(y, exp, x, w, "linear_fwd")
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -89,6 +108,8 @@ def test_linear_fwd_epilogue(hip, dtype, act):
     zz = (zz.reshape(B, T, N) + e.double()[:, None, :] + pm.double()[None, :, :]).reshape(M, N)
     close(z, zz, TIGHT[dtype], "pre-activation")
     close(y, R.act(act, zz), TIGHT[dtype], "activation " + act)
+    close_gemm(z, zz, x, w, "pre-activation")
+    close_gemm(y, R.act(act, zz), x, w, "activation " + act, act_scale=1.1)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -107,19 +128,20 @@ def test_linear_dgrad(hip, dtype, M, N, K, act):
     dx = torch.empty(M, K, dtype=dtype, device=DEV)
     hip.linear_dgrad(dz.to(DEV), w.to(DEV), dx, act_below=act, aux=aux.to(DEV) if act != "none" else None,
                      addend=add.to(DEV))
-    exp = dz.double() @ w.double()
     a = aux.double()
+    fac = torch.ones_like(a)
     if act == "relu":
-        exp = exp * (a > 0)
+        fac = (a > 0).double()
     elif act == "tanh":
-        exp = exp * (1 - a * a)
+        fac = 1 - a * a
     elif act == "sigmoid":
-        exp = exp * a * (1 - a)
+        fac = a * (1 - a)
     elif act == "silu":
         s = torch.sigmoid(a)
-        exp = exp * (s * (1 + a * (1 - s)))
-    exp = exp + add.double()
+        fac = s * (1 + a * (1 - s))
+    exp = (dz.double() @ w.double()) * fac + add.double()
     close(dx, exp, TIGHT[dtype], "dgrad")
+    close_gemm(dx, exp, dz, w.T, "dgrad", act_scale=fac.abs().max().item())
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -585,8 +607,10 @@ def test_small_m_forward_and_dgrad_tiles(hip, M, N, K, act):
     y = torch.full((M, N), 7.0, dtype=bf, device=DEV)
     hip.linear_fwd(x, w, b, y, act=act)
     close(y, R.act(act, x.double() @ w.double().T + b.double()), TIGHT[bf], "small-M forward")
+    close_gemm(y, R.act(act, x.double() @ w.double().T + b.double()), x, w, "small-M forward", act_scale=1.1)
     hip.linear_fwd(x, w, None, y)
     close(y, x.double() @ w.double().T, TIGHT[bf], "small-M forward, no bias")
+    close_gemm(y, x.double() @ w.double().T, x, w, "small-M forward, no bias")
     # dgrad: dx[M, Kout] = (dz[M, Nred] w[Nred, Kout]) * act'(aux); output columns % 16 == 0 for the small tiles
     Kout = (K + 15) // 16 * 16
     dz = rnd((M, N), 4, 1.0, bf).to(DEV)
@@ -599,6 +623,7 @@ def test_small_m_forward_and_dgrad_tiles(hip, M, N, K, act):
     a = aux.double()
     fac = {"none": torch.ones_like(a), "sigmoid": a * (1 - a), "elu": torch.where(a > 0, torch.ones_like(a), a + 1)}[act]
     close(dx, (dz.double() @ w2.double()) * fac, TIGHT[bf], "small-M dgrad")
+    close_gemm(dx, (dz.double() @ w2.double()) * fac, dz, w2.T, "small-M dgrad", act_scale=fac.abs().max().item())
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 512, 1470), (64, 300, 512), (1000, 72, 200), (1, 512, 512), (300, 30, 256)])
@@ -686,6 +711,7 @@ def test_small_m_kernels_seeded_shape_sweep(hip):
         y = torch.full((M, N), 7.0, dtype=bf, device=DEV)
         hip.linear_fwd(x, w, b, y, act="relu")
         close(y, torch.relu(x.double() @ w.double().T + b.double()), TIGHT[bf], f"fwd {M}x{N}x{K}")
+        close_gemm(y, torch.relu(x.double() @ w.double().T + b.double()), x, w, f"fwd {M}x{N}x{K}")
         # weight + bias gradient over the M rows
         dz = rnd((M, N), 160 + case, 1.0, bf).to(DEV)
         dw = torch.full((N, K), 7.0, dtype=torch.float32, device=DEV)
@@ -699,6 +725,7 @@ def test_small_m_kernels_seeded_shape_sweep(hip):
         dx = torch.full((M, Kc), 7.0, dtype=bf, device=DEV)
         hip.linear_dgrad(dz, w2, dx)
         close(dx, dz.double() @ w2.double(), TIGHT[bf], f"dgrad {M}x{N}x{Kc}")
+        close_gemm(dx, dz.double() @ w2.double(), dz, w2.T, f"dgrad {M}x{N}x{Kc}")
 
 
 @pytest.mark.parametrize("M,N,K", [(50, 512, 30), (50, 30, 512), (512, 30, 50), (1, 1, 1), (7, 3, 64), (3, 5, 63), (200, 30, 1000)])
