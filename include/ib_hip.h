@@ -396,6 +396,21 @@ int ib_q_sample(const void* x0, const void* eps, const int64_t* t, const float* 
 int ib_ddim_step(void* x, const void* eps, const float* coef, const int64_t* timesteps,
                  int64_t num_steps, int32_t step, const int32_t* step_dev, int64_t* t_out, int64_t B,
                  int64_t n, int dtype, ib_stream_t stream);
+/* Masked (inpainting) DDIM update over the sampler state x [B, T, ld] (row pitch ld >= D; eps, x0, z the same layout and
+ * dtype), with one uint8 mask [T, ld] for the whole batch.  s = *step_dev (or `step` if step_dev NULL), clamped like
+ * ib_ddim_step:
+ *   mask == 0 (free):     x <- coef[s][0] * x + coef[s][1] * eps             (bit-identical to ib_ddim_step on x, eps)
+ *   mask != 0 (observed): x <- obs_coef[s+1][0] * x0 + obs_coef[s+1][1] * z  (obs_coef fp32 [num_steps + 1, 2])
+ * and t_out[b] = timesteps[s+1] (0 after the last step) as ib_ddim_step writes it.  Loads only the operands a vector of 8
+ * elements needs.  Pad columns must be 0 in the mask (they then stay 0 if x and eps are 0 there). */
+int ib_ddim_cond_step(void* x, const void* eps, const void* x0, const void* z, const uint8_t* mask,
+                      const float* coef, const float* obs_coef, const int64_t* timesteps, int64_t num_steps,
+                      int32_t step, const int32_t* step_dev, int64_t* t_out, int64_t B, int64_t T, int64_t D,
+                      int64_t ld, int dtype, ib_stream_t stream);
+/* The start state of the masked loop: observed elements x <- obs_coef[0][0] * x0 + obs_coef[0][1] * z, free ones untouched
+ * (they hold the drawn noise z).  Same layout rules as ib_ddim_cond_step. */
+int ib_ddim_cond_init(void* x, const void* x0, const void* z, const uint8_t* mask, const float* obs_coef,
+                      int64_t B, int64_t T, int64_t D, int64_t ld, int dtype, ib_stream_t stream);
 /* The diffusion batch made on the device (csrc/noise.hip; replaces host torch.randint / torch.randn + H2D copies in the
  * training loop, cli/train.py -- the reference has no diffusion path).  For window b < B:
  *   x0_out[b, :per] = table[idx[b], :per]           (table NULL: x0 untouched; row_pitch % 8 == 0, row_pitch >= per)

@@ -11,8 +11,9 @@ import os
 import torch
 from torch.utils.data import DataLoader
 
+from ..data.AddBiomechanicsDataset import MotionWindowView, SyntheticWindowDataset
 from ..loss.RegressionLossEvaluator import RegressionLossEvaluator
-from ._common import add_additive_flags, add_component_flags, dtype_of, open_dataset, pick_device
+from ._common import add_additive_flags, add_component_flags, dtype_of, is_diffusion, open_dataset, pick_device
 from .abstract_command import AbstractCommand
 
 
@@ -37,6 +38,12 @@ class AnalyzeCommand(AbstractCommand):
         add_component_flags(p, train_defaults=False)
         add_additive_flags(p)
         p.add_argument('--max-windows', type=int, default=0, help='Stop each split after this many windows (0 = all).')
+        p.add_argument('--sample-steps', type=int, default=100,
+                       help='[diffusion models] DDIM steps of the masked sampler that infers the label columns.')
+        p.add_argument('--sample-seed', type=int, default=0,
+                       help='[diffusion models] seed of the start noise (window i of a split draws from (seed, i)).')
+        p.add_argument('--sample-batch', type=int, default=1,
+                       help='[diffusion models] windows per sampler call; still one CSV row per window.')
 
     def run(self, args: argparse.Namespace):
         if 'command' in args and args.command != 'analyze':
@@ -45,6 +52,8 @@ class AnalyzeCommand(AbstractCommand):
         os.makedirs(checkpoint_dir, exist_ok=True)
         device = pick_device(args)
         geometry = self.ensure_geometry(args.geometry_folder)
+        if is_diffusion(args.model_type):
+            return self.run_diffusion(args, checkpoint_dir, device, geometry)
         model = None
         for split, csv_name in (('dev', 'dev_analysis.csv'), ('train', 'train_analysis.csv')):
             logging.info(f'## Loading {split} dataset:')
@@ -80,6 +89,72 @@ class AnalyzeCommand(AbstractCommand):
             print(f'Final {split} results:')
             evaluator.print_report(log_to_wandb=False)
         return True
+
+    def run_diffusion(self, args: argparse.Namespace, checkpoint_dir: str, device, geometry) -> bool:
+        """the diffusion denoisers: the label columns of every window are inferred by the masked DDIM sampler
+        (models/DiffusionLabelPredictor.py) from the observed input columns, then evaluated, written and reported exactly
+        as the regression models' outputs are"""
+        from ..models.DiffusionLabelPredictor import DiffusionLabelPredictor
+        if args.sample_batch < 1 or args.sample_steps < 1:
+            raise SystemExit("--sample-batch and --sample-steps must be >= 1")
+        predictor = None
+        for split, csv_name in (('dev', 'dev_analysis.csv'), ('train', 'train_analysis.csv')):
+            logging.info(f'## Loading {split} dataset:')
+            view = self.diffusion_view(args, split, geometry)
+            dataset = view.dataset
+            if predictor is None:
+                model = self.diffusion_model(args, view, device)
+                self.load_latest_checkpoint(model, checkpoint_dir=checkpoint_dir)
+                model.eval()
+                predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
+                                                    output_data_format=args.output_data_format)
+            evaluator = RegressionLossEvaluator(dataset=dataset, split=split, device=device)
+            loader = DataLoader(dataset, batch_size=args.sample_batch, shuffle=False, num_workers=args.data_loading_workers)
+            compute_report = bool(getattr(dataset, 'skeletons', None))
+            n = len(dataset)
+            if args.max_windows:
+                n = min(n, args.max_windows)
+            i = 0
+            with torch.no_grad(), open(os.path.join(checkpoint_dir, csv_name), 'a') as f:
+                writer = None
+                for inputs, labels, subj, trial in loader:
+                    outputs = predictor(inputs, labels, draw=i)
+                    for b in range(min(len(subj), n - i)):
+                        one = lambda d: {k: v[b:b + 1] for k, v in d.items()}
+                        evaluator(one(inputs), one(outputs), one(labels), subj[b:b + 1], trial[b:b + 1], args,
+                                  compute_report=compute_report)
+                        stats = {"sub_name": window_subject(dataset, subj[b:b + 1]),
+                                 "trial_name": window_trial(dataset, subj[b:b + 1], trial[b:b + 1])}
+                        writer = writer or csv.DictWriter(f, fieldnames=stats.keys())
+                        writer.writerow(stats)
+                        i += 1
+                        if i % 100 == 0 or i == n:
+                            logging.info(f'  - Batch {i}/{n}')
+                        if i % 1000 == 0 or i == n:
+                            evaluator.print_report(args, reset=False, log_to_wandb=not args.no_wandb)
+                    if i >= n:
+                        break
+            print(f'Final {split} results:')
+            evaluator.print_report(log_to_wandb=False)
+        return True
+
+    def diffusion_view(self, args: argparse.Namespace, split: str, geometry) -> MotionWindowView:
+        """the split as denoiser windows that carry labels: seeded synthetic regression windows (the seeds of
+        open_dataset) or the .b3d windows, both through MotionWindowView"""
+        if args.synthetic_windows > 0:
+            seed = {'train': 0, 'dev': 1, 'test': 2}.get(split, 3)
+            return MotionWindowView(SyntheticWindowDataset(args.synthetic_windows, args.history_len, args.stride,
+                                                           output_data_format=args.output_data_format, seed=seed))
+        return open_dataset(args, split, args.history_len, args.stride, args.output_data_format, geometry)
+
+    def diffusion_model(self, args: argparse.Namespace, view: MotionWindowView, device):
+        """the denoiser as `train` builds it (cli/train.py): feat_dim = the window row's width, window = F frames"""
+        window = args.history_len // args.stride if args.stride > 1 else args.history_len
+        return self.get_model(view.num_dofs, view.num_contact_bodies, args.model_type, history_len=args.history_len,
+                              stride=args.stride, hidden_dims=args.hidden_dims, activation=args.activation,
+                              batchnorm=False, dropout=False, dropout_prob=0.0, root_history_len=10,
+                              output_data_format=args.output_data_format, device=device,
+                              compute_dtype=dtype_of(args), feat_dim=view.feat, window=window).to(device)
 
 
 def window_subject(dataset, subj) -> str:

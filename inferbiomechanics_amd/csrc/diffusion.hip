@@ -79,6 +79,19 @@ __global__ void q_sample_kernel(const T* __restrict__ x0, const T* __restrict__ 
   }
 }
 
+// One element k of the DDIM update x' = cx * x + ce * eps of a vector of V, with its fp32 roundings spelled out.
+// ddim_step_kernel and the free elements of ddim_cond_step_kernel both go through it, so the masked update is bit-identical
+// to the unmasked one however the compiler would contract the bare expression in either kernel.  The forms are those that
+// expression compiled to for gfx950: one lone element sums two rounded products; fp32 x 8 fuses cx * x into the rounded
+// ce * eps; bf16 x 8 alternates which of the two products is rounded first (the pairing of the packed fp32 operations).
+template <typename T, int V>
+__device__ __forceinline__ float ddim_mix(int k, float cx, float a, float ce, float e) {
+#pragma clang fp contract(off)
+  if constexpr (V == 1) return cx * a + ce * e;
+  else if constexpr (sizeof(T) == 4) return __builtin_fmaf(cx, a, ce * e);
+  else return (k & 1) ? __builtin_fmaf(cx, a, ce * e) : __builtin_fmaf(ce, e, cx * a);
+}
+
 template <typename T, int V>
 __global__ void ddim_step_kernel(T* __restrict__ x, const T* __restrict__ eps, const float* __restrict__ coef,
                                  const int64_t* __restrict__ timesteps, int64_t num_steps, int step,
@@ -92,10 +105,79 @@ __global__ void ddim_step_kernel(T* __restrict__ x, const T* __restrict__ eps, c
     ldv<T, V>(x + i * V, a);
     ldv<T, V>(eps + i * V, e);
 #pragma unroll
-    for (int k = 0; k < V; ++k) o[k] = cx * a[k] + ce * e[k];
+    for (int k = 0; k < V; ++k) o[k] = ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
     stv<T, V>(x + i * V, o);
   }
   if (t_out && blockIdx.x == 0) {
+    const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
+    for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
+  }
+}
+
+// masked (inpainting) DDIM update over the sampler state x [B, T, ld] with one mask [T, ld] for the whole batch: a free
+// element (mask 0) takes the update of ddim_step_kernel (ddim_mix: the same fp32 roundings), an observed one
+// the forward-noised observation at the next noise level, obs_coef[s+1] = (sqrt ab_prev(s), sqrt(1 - ab_prev(s))) times
+// (x0, z) -- (1, 0) after the last step, so the loop ends on x0 itself.  INIT: the start state, observed elements <-
+// obs_coef[0] (x0, z), free ones keep the drawn noise.  V = 8 reads the mask 8 bytes at a time and loads only what the
+// vector needs: x / eps when one of its elements is free, x0 / z when one is observed.  mix8: ib_ddim_step would take its
+// 8-wide kernel on these buffers, so the element-wise kernel (a window of T * ld % 8 != 0) rounds as that one does.
+template <typename T, int V, bool INIT>
+__global__ void ddim_cond_step_kernel(T* __restrict__ x, const T* __restrict__ eps, const T* __restrict__ x0,
+                                      const T* __restrict__ z, const uint8_t* __restrict__ mask,
+                                      const float* __restrict__ coef, const float* __restrict__ obs_coef,
+                                      const int64_t* __restrict__ timesteps, int64_t num_steps, int step,
+                                      const int32_t* __restrict__ step_dev, int64_t* __restrict__ t_out, int64_t B,
+                                      int64_t per, int64_t n, int mix8) {
+  int s = 0;
+  float cx = 0.f, ce = 0.f, ox, oz;
+  if constexpr (INIT) {
+    ox = obs_coef[0]; oz = obs_coef[1];
+  } else {
+    s = step_dev ? *step_dev : step;
+    s = s < 0 ? 0 : (s >= num_steps ? (int)num_steps - 1 : s);
+    cx = coef[2 * s]; ce = coef[2 * s + 1];
+    ox = obs_coef[2 * (s + 1)]; oz = obs_coef[2 * (s + 1) + 1];
+  }
+  constexpr unsigned ALL = (1u << V) - 1;
+  const int64_t nv = n / V;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e0 = i * V, m0 = e0 % per;          // per % V == 0: a vector never straddles two windows
+    unsigned bits;
+    if constexpr (V == 1) {
+      bits = mask[m0] != 0;
+    } else {
+      const uint64_t mv = *reinterpret_cast<const uint64_t*>(mask + m0);
+      bits = 0;
+#pragma unroll
+      for (int k = 0; k < V; ++k) bits |= (((mv >> (8 * k)) & 0xff) != 0 ? 1u : 0u) << k;
+    }
+    if (INIT && bits == 0) continue;                  // all free: the drawn noise stays
+    float o[V];
+    if (bits != ALL) {
+      float a[V];
+      ldv<T, V>(x + e0, a);
+      if constexpr (INIT) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) o[k] = a[k];
+      } else {
+        float e[V];
+        ldv<T, V>(eps + e0, e);
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+          o[k] = (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a[k], ce, e[k]) : ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
+      }
+    }
+    if (bits != 0) {
+      float a[V], b[V];
+      ldv<T, V>(x0 + e0, a);
+      ldv<T, V>(z + e0, b);
+#pragma unroll
+      for (int k = 0; k < V; ++k)
+        if ((bits >> k) & 1u) o[k] = ox * a[k] + oz * b[k];
+    }
+    stv<T, V>(x + e0, o);
+  }
+  if (!INIT && t_out && blockIdx.x == 0) {
     const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
     for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
   }
@@ -161,6 +243,55 @@ extern "C" int ib_ddim_step(void* x, const void* eps, const float* coef, const i
     if (v8) hipLaunchKernelGGL((ddim_step_kernel<bf16_t, 8>), dim3(grid), dim3(256), 0, s, (bf16_t*)x, (const bf16_t*)eps, coef, timesteps, num_steps, step, step_dev, t_out, B, n);
     else hipLaunchKernelGGL((ddim_step_kernel<bf16_t, 1>), dim3(grid), dim3(256), 0, s, (bf16_t*)x, (const bf16_t*)eps, coef, timesteps, num_steps, step, step_dev, t_out, B, n);
   } else return IB_E_DTYPE;
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+extern "C" int ib_ddim_cond_step(void* x, const void* eps, const void* x0, const void* z, const uint8_t* mask,
+                                 const float* coef, const float* obs_coef, const int64_t* timesteps, int64_t num_steps,
+                                 int32_t step, const int32_t* step_dev, int64_t* t_out, int64_t B, int64_t T, int64_t D,
+                                 int64_t ld, int dtype, ib_stream_t stream) {
+  if (!x || !eps || !x0 || !z || !mask || !coef || !obs_coef || num_steps <= 0) return IB_E_ARG;
+  if (B <= 0 || T <= 0 || D <= 0 || ld < D) return IB_E_ARG;
+  if (t_out && !timesteps) return IB_E_ARG;
+  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
+  const int64_t per = T * ld, n = B * per;
+  const bool mix8 = (n % 8 == 0) && al16(x) && al16(eps);          // ib_ddim_step's choice of its 8-wide kernel
+  const bool v8 = mix8 && (per % 8 == 0) && al16(x0) && al16(z) && (reinterpret_cast<uintptr_t>(mask) % 8) == 0;
+  const int grid = ib_grid_1d(n / (v8 ? 8 : 1), 256);
+  hipStream_t s = ib_s(stream);
+#define IB_COND_STEP(TY, V)                                                                                                   \
+  hipLaunchKernelGGL((ddim_cond_step_kernel<TY, V, false>), dim3(grid), dim3(256), 0, s, (TY*)x, (const TY*)eps,             \
+                     (const TY*)x0, (const TY*)z, mask, coef, obs_coef, timesteps, num_steps, step, step_dev, t_out, B, per, n, \
+                     (int)mix8)
+  if (dtype == IB_F32) {
+    if (v8) IB_COND_STEP(float, 8); else IB_COND_STEP(float, 1);
+  } else if (dtype == IB_BF16) {
+    if (v8) IB_COND_STEP(bf16_t, 8); else IB_COND_STEP(bf16_t, 1);
+  } else return IB_E_DTYPE;
+#undef IB_COND_STEP
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+extern "C" int ib_ddim_cond_init(void* x, const void* x0, const void* z, const uint8_t* mask, const float* obs_coef,
+                                 int64_t B, int64_t T, int64_t D, int64_t ld, int dtype, ib_stream_t stream) {
+  if (!x || !x0 || !z || !mask || !obs_coef || B <= 0 || T <= 0 || D <= 0 || ld < D) return IB_E_ARG;
+  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
+  const int64_t per = T * ld, n = B * per;
+  const bool v8 = (per % 8 == 0) && al16(x) && al16(x0) && al16(z) && (reinterpret_cast<uintptr_t>(mask) % 8) == 0;
+  const int grid = ib_grid_1d(n / (v8 ? 8 : 1), 256);
+  hipStream_t s = ib_s(stream);
+#define IB_COND_INIT(TY, V)                                                                                                   \
+  hipLaunchKernelGGL((ddim_cond_step_kernel<TY, V, true>), dim3(grid), dim3(256), 0, s, (TY*)x, (const TY*)nullptr,          \
+                     (const TY*)x0, (const TY*)z, mask, (const float*)nullptr, obs_coef, (const int64_t*)nullptr, (int64_t)1, 0, \
+                     (const int32_t*)nullptr, (int64_t*)nullptr, B, per, n, 0)
+  if (dtype == IB_F32) {
+    if (v8) IB_COND_INIT(float, 8); else IB_COND_INIT(float, 1);
+  } else if (dtype == IB_BF16) {
+    if (v8) IB_COND_INIT(bf16_t, 8); else IB_COND_INIT(bf16_t, 1);
+  } else return IB_E_DTYPE;
+#undef IB_COND_INIT
   IB_CHECK_LAUNCH();
   return IB_OK;
 }

@@ -29,11 +29,24 @@ class DDIMSampler:
             B, T, Dp = x.shape
             D = self._D
             plan.forward(x.view(B * T, Dp)[:, :D], t_vec, tabs.temb, P, out=eps_buf.view(B * T, Dp)[:, :D], BT=(B, T))
-            hip.ddim_step(x, eps_buf, tabs.ddim_coef, tabs.ddim_t, step_dev=ctr, t_out=t_vec)
+            self._update(x, eps_buf, ctr, t_vec, tabs)
         else:
             eps = plan.forward(x, t_vec, tabs.temb, P)
-            hip.ddim_step(x, eps, tabs.ddim_coef, tabs.ddim_t, step_dev=ctr, t_out=t_vec)
+            self._update(x, eps, ctr, t_vec, tabs)
         hip.counter_add(ctr, 1)
+
+    def _update(self, x, eps, ctr, t_vec, tabs):
+        hip.ddim_step(x, eps, tabs.ddim_coef, tabs.ddim_t, step_dev=ctr, t_out=t_vec)
+
+    def _extra_buffers(self, B, T, D, Dp, dev, dtype):
+        """more device buffers that live as long as the captured step (a subclass's)"""
+        return {}
+
+    def _extra_sig(self, tabs) -> tuple:
+        return ()
+
+    def _begin(self, x, tabs):
+        """runs once x holds the start draw, before the first step (a subclass's start state)"""
 
     @torch.no_grad()
     def sample(self, x_T: torch.Tensor, steps: Optional[int] = None) -> torch.Tensor:
@@ -57,12 +70,16 @@ class DDIMSampler:
                      steps: Optional[int] = None) -> torch.Tensor:
         """x_T ~ N(0,1) drawn ON the device (csrc/noise.hip: Philox keyed by (seed, draw); `seed` defaults to torch's) and
         denoised to x_0 -- no host random numbers, no H2D copy of the start state."""
+        return self.sample(self.draw_start(batch, window, feat, seed, draw), steps)
+
+    def draw_start(self, batch: int, window: int, feat: int, seed: Optional[int] = None, draw: int = 0) -> torch.Tensor:
+        """the start state x_T ~ N(0,1) of sample_noise, [batch, window, feat] in the compute dtype on the model's device"""
         m = self.model
         dev = next(m.parameters()).device
         x_T = torch.empty((batch, window, feat), dtype=m.compute_dtype, device=dev)
         seed = int(torch.initial_seed()) if seed is None else int(seed)
         hip.diffusion_draw(seed, step=int(draw), stream_id=0x40000000, eps=x_T)
-        return self.sample(x_T, steps)
+        return x_T
 
     def _sample(self, x_T: torch.Tensor, steps: Optional[int] = None) -> torch.Tensor:
         m = self.model
@@ -81,7 +98,7 @@ class DDIMSampler:
         plan = m._get_plan(dev)
         B, T, D = x_T.shape
         Dp = plan.infer_pitch(D) if (hasattr(plan, "infer_pitch") and m.compute_dtype == torch.bfloat16) else D
-        sig = sig + (Dp,)
+        sig = sig + (Dp,) + self._extra_sig(tabs)
         if sig != self._sig:
             self._sig, self._graph = sig, None
             self._bufs = {"x": torch.zeros((B, T, Dp), dtype=m.compute_dtype, device=dev),
@@ -89,9 +106,11 @@ class DDIMSampler:
                           "ctr": torch.zeros(1, dtype=torch.int32, device=dev)}
             if Dp != D:
                 self._bufs["eps"] = torch.zeros((B, T, Dp), dtype=m.compute_dtype, device=dev)
+            self._bufs.update(self._extra_buffers(B, T, D, Dp, dev, m.compute_dtype))
         self._D = D
         x, t_vec, ctr = self._bufs["x"], self._bufs["t"], self._bufs["ctr"]
         x[:, :, :D].copy_(x_T.to(device=dev, dtype=m.compute_dtype))
+        self._begin(x, tabs)
         ctr.zero_()
         hip.fill_i64(t_vec, int(tabs.ddim_t[0]))
         P = m.param_source()
@@ -122,3 +141,64 @@ class DDIMSampler:
             else:
                 self._step_launches(x, t_vec, ctr, tabs, P)
         return x[:, :, :self._D].clone()
+
+
+class ConditionalDDIMSampler(DDIMSampler):
+    """DDIM (eta = 0) inpainting with an unconditional denoiser (replacement method): the elements a mask marks as observed
+    are pinned, at every step, to the observation forward-noised to that step's noise level with the fixed start draw z,
+    sqrt(ab) x0 + sqrt(1 - ab) z -- with eta = 0 that is exactly the DDIM trajectory of the observation, so the loop stays
+    deterministic and its last step (to alpha_bar = 1) returns the observation itself.  The free elements follow the DDIM
+    update.  Same captured single-step graph as DDIMSampler; only the update launch differs (ib_ddim_cond_step, the same
+    launch count per step).  The observation, the draw and the mask live in sampler-owned device buffers that the capture
+    reads, so a new batch of the same shape is copied in and the captured step replayed."""
+
+    def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True):
+        super().__init__(model, num_sample_steps, use_graph)
+        self._cond = None
+
+    @torch.no_grad()
+    def sample(self, x_T: torch.Tensor, observed: torch.Tensor, mask: torch.Tensor,
+               steps: Optional[int] = None) -> torch.Tensor:
+        """x_T [B,T,D] ~ N(0,1) (the draw z), observed [B,T,D], mask [T,D] bool (True = observed) -> x_0, which equals the
+        observation (in the compute dtype) wherever mask is True.  `steps` truncates the loop as in DDIMSampler."""
+        B, T, D = x_T.shape
+        if tuple(observed.shape) != (B, T, D):
+            raise ValueError(f"observed must be {(B, T, D)} like x_T, got {tuple(observed.shape)}")
+        if tuple(mask.shape) != (T, D) or mask.dtype != torch.bool:
+            raise ValueError(f"mask must be a [T, D] = {(T, D)} bool tensor, got {tuple(mask.shape)} {mask.dtype}")
+        self._cond = (observed, mask)
+        try:
+            return super().sample(x_T, steps)
+        finally:
+            self._cond = None
+
+    @torch.no_grad()
+    def sample_noise(self, batch: int, window: int, feat: int, observed: torch.Tensor, mask: torch.Tensor,
+                     seed: Optional[int] = None, draw: int = 0, steps: Optional[int] = None) -> torch.Tensor:
+        """as DDIMSampler.sample_noise: z = x_T drawn on the device from (seed, draw)"""
+        return self.sample(self.draw_start(batch, window, feat, seed, draw), observed, mask, steps)
+
+    def _extra_sig(self, tabs) -> tuple:
+        return (tabs.obs_coef.data_ptr(),)
+
+    def _extra_buffers(self, B, T, D, Dp, dev, dtype):
+        # pitched like the state, pad columns 0 (the mask's pad columns are free, so they stay 0 in x)
+        return {"x0": torch.zeros((B, T, Dp), dtype=dtype, device=dev),
+                "z": torch.zeros((B, T, Dp), dtype=dtype, device=dev),
+                "mask": torch.zeros((T, Dp), dtype=torch.uint8, device=dev)}
+
+    def _begin(self, x, tabs):
+        if self._cond is None:
+            raise RuntimeError("ConditionalDDIMSampler: call sample(x_T, observed, mask)")
+        observed, mask = self._cond
+        D = self._D
+        x0, z, m = self._bufs["x0"], self._bufs["z"], self._bufs["mask"]
+        x0[:, :, :D].copy_(observed.to(device=x0.device, dtype=x0.dtype))
+        m[:, :D].copy_(mask.to(device=m.device, dtype=torch.uint8))
+        z.copy_(x)
+        hip.ddim_cond_init(x, x0, z, m, tabs.obs_coef, D=D)
+
+    def _update(self, x, eps, ctr, t_vec, tabs):
+        b = self._bufs
+        hip.ddim_cond_step(x, eps, b["x0"], b["z"], b["mask"], tabs.ddim_coef, tabs.obs_coef, tabs.ddim_t, step_dev=ctr,
+                           t_out=t_vec, D=self._D)

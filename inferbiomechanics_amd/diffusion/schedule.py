@@ -40,6 +40,17 @@ def ddim_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100) 
     return torch.stack(rows)
 
 
+def observation_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100) -> torch.Tensor:
+    """[S + 1, 2] float64 (c_x0, c_z) of the masked (inpainting) loop: an observed element is x0 forward-noised with the
+    fixed draw z to the loop's noise level, c_x0 x0 + c_z z.  Row 0 = (sqrt ab[t_0], sqrt(1 - ab[t_0])) is the start state;
+    row s + 1 = (sqrt ab_prev(s), sqrt(1 - ab_prev(s))) is the level after step s, so the last row is exactly (1, 0)."""
+    ab = alphas_cumprod(num_train_steps)
+    ts = ddim_timesteps(num_train_steps, num_sample_steps).tolist()
+    levels = [ab[ts[0]]] + [ab[ts[i + 1]] if i + 1 < len(ts) else torch.tensor(1.0, dtype=torch.float64)
+                            for i in range(len(ts))]
+    return torch.stack([torch.stack([torch.sqrt(a), torch.sqrt(1 - a)]) for a in levels])
+
+
 def timestep_embedding_table(num_steps: int, dim: int, max_period: float = 10000.0) -> torch.Tensor:
     """[num_steps, dim] float64: row t = [sin(t w), cos(t w)]."""
     half = dim // 2
@@ -66,6 +77,7 @@ class DiffusionTables:
         dev = self.sqrt_ab.device
         self.ddim_t = ddim_timesteps(self.num_train_steps, num_sample_steps).to(dev)
         self.ddim_coef = ddim_coefficients(self.num_train_steps, num_sample_steps).to(torch.float32).to(dev).contiguous()
+        self.obs_coef = observation_coefficients(self.num_train_steps, num_sample_steps).to(torch.float32).to(dev).contiguous()
 
     def host_tables(self) -> Dict[str, torch.Tensor]:
         return {"sqrt_ab": self.sqrt_ab.cpu(), "sqrt_1mab": self.sqrt_1mab.cpu(), "temb": self.temb.cpu(),

@@ -156,6 +156,9 @@ _SIGS = {
     "ib_sum_partials": (_c.c_int, [_vp, _i64, _f32, _vp, _vp]),
     "ib_q_sample": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
     "ib_ddim_step": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _c.c_int, _vp]),
+    "ib_ddim_cond_step": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i64, _i64,
+                                     _c.c_int, _vp]),
+    "ib_ddim_cond_init": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
     "ib_counter_add": (_c.c_int, [_vp, _i32, _vp]),
     "ib_batchnorm_fwd": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _f32, _f32, _c.c_int,
                                     _c.c_int, _vp]),
@@ -2130,6 +2133,64 @@ def ddim_step(x, eps, coef, timesteps, step=0, step_dev=None, t_out=None):
             raise HipError("t_out must be int64 [B]")
     _check(lib().ib_ddim_step(_ptr(x), _ptr(eps), _ptr(coef), _ptr(timesteps), S, int(step), _ptr(step_dev),
                               _ptr(t_out), B, x.numel(), dtype_code(dt), stream_ptr()), "ib_ddim_step")
+    return x
+
+
+def _cond_operands(what, x, x0, z, mask, obs_coef, D):
+    """shared checks of ddim_cond_step / ddim_cond_init -> (B, T, D, ld)"""
+    dt = x.dtype
+    _req(x, "x", dt, 3)
+    if not x.is_contiguous():
+        raise HipError(f"{what}: x must be a contiguous [B, T, ld] state")
+    B, T, ld = x.shape
+    D = ld if D is None else int(D)
+    if D <= 0 or D > ld:
+        raise HipError(f"{what}: D = {D} must be in 1 .. ld = {ld}")
+    for name, t in (("x0", x0), ("z", z)):
+        _req(t, name, dt)
+        if t.shape != x.shape or not t.is_contiguous():
+            raise HipError(f"{what}: {name} must be contiguous {tuple(x.shape)} {dt}, like x")
+    _req(mask, "mask", torch.uint8, 2)
+    if tuple(mask.shape) != (T, ld) or not mask.is_contiguous():
+        raise HipError(f"{what}: mask must be contiguous uint8 [T, ld] = [{T}, {ld}], got {tuple(mask.shape)}")
+    _req(obs_coef, "obs_coef", torch.float32, 2)
+    if obs_coef.shape[1] != 2 or not obs_coef.is_contiguous():
+        raise HipError(f"{what}: obs_coef must be contiguous [S + 1, 2] fp32")
+    return B, T, D, ld
+
+
+def ddim_cond_step(x, eps, x0, z, mask, coef, obs_coef, timesteps, step=0, step_dev=None, t_out=None, D=None):
+    """masked DDIM update in place over the state x [B, T, ld] (csrc/diffusion.hip): elements with mask [T, ld] == 0 take the
+    ddim_step update from eps, the others obs_coef[s + 1] (x0, z); t_out / step_dev as in ddim_step.  D (default ld): the
+    feature columns in front of the row pitch."""
+    B, T, D, ld = _cond_operands("ddim_cond_step", x, x0, z, mask, obs_coef, D)
+    _req(eps, "eps", x.dtype)
+    if eps.shape != x.shape or not eps.is_contiguous():
+        raise HipError("ddim_cond_step: eps must be contiguous with the shape of x")
+    _req(coef, "coef", torch.float32, 2)
+    _req(timesteps, "timesteps", torch.int64, 1)
+    S = coef.shape[0]
+    if coef.shape[1] != 2 or timesteps.numel() != S or not coef.is_contiguous():
+        raise HipError("coef must be [S,2] fp32, timesteps [S] int64")
+    if obs_coef.shape[0] != S + 1:
+        raise HipError(f"ddim_cond_step: obs_coef must have S + 1 = {S + 1} rows, got {obs_coef.shape[0]}")
+    if t_out is not None:
+        _req(t_out, "t_out", torch.int64, 1)
+        if t_out.numel() != B:
+            raise HipError("t_out must be int64 [B]")
+    if step_dev is not None:
+        _req(step_dev, "step_dev", torch.int32)
+    _check(lib().ib_ddim_cond_step(_ptr(x), _ptr(eps), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef),
+                                   _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out), B, T, D, ld,
+                                   dtype_code(x.dtype), stream_ptr()), "ib_ddim_cond_step")
+    return x
+
+
+def ddim_cond_init(x, x0, z, mask, obs_coef, D=None):
+    """start state of the masked loop in place: x = obs_coef[0] (x0, z) where mask != 0; elsewhere x is left as drawn"""
+    B, T, D, ld = _cond_operands("ddim_cond_init", x, x0, z, mask, obs_coef, D)
+    _check(lib().ib_ddim_cond_init(_ptr(x), _ptr(x0), _ptr(z), _ptr(mask), _ptr(obs_coef), B, T, D, ld,
+                                   dtype_code(x.dtype), stream_ptr()), "ib_ddim_cond_init")
     return x
 
 
