@@ -139,6 +139,32 @@ __device__ __forceinline__ void ff_out_piece(const unsigned char* img, bf16_t* g
   *reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(g + (int64_t)row * ldg) + pc * 16) = v;
 }
 
+// a value the optimiser must recompute instead of reuse: keeps an address computed in one phase (a row offset of the
+// panel's input rows, a lane's epilogue offset) from being kept alive -- in VGPRs or scratch -- across the GEMM phases
+// until a later phase that would compute the same value
+__device__ __forceinline__ int ff_fresh(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+// this lane's first column inside a 512-wide GEMM output (wave w owns columns 64 w .., lane group g = lane / 16 the four
+// columns 4 g .. of every 16-column tile), recomputed at every use: kept as one value it stayed live from the first
+// epilogue to the last and was spilled at the register plan's peak (the attention backward)
+__device__ __forceinline__ int ff_colb() {
+  const int t = ff_fresh(threadIdx.x);
+  return (t & (FF_THREADS - 64)) | 4 * ((t >> 4) & 3);
+}
+
+// The kernel's by-value parameter block read where it is used: the block sits at the start of the kernarg segment, and a
+// field read through this view is loaded (s_load, scalar cache) at the phase that needs it.  Read as a by-value argument,
+// every field is loaded at kernel entry and then held in SGPRs for the whole launch -- 28 pointers, which spilled into
+// VGPR lanes and pushed the VGPR plan past its 256-register budget.
+template <class P>
+using ff_karg_t = const __attribute__((address_space(4))) P;
+template <class P>
+__device__ __forceinline__ ff_karg_t<P>& ff_kargs() {
+  return *(ff_karg_t<P>*)__builtin_amdgcn_kernarg_segment_ptr();
+}
+
 // ---- row-wise passes: wave w owns rows w, w + 8, ... of the panel, a lane 8 consecutive columns of the row (one row per
 // wave-instruction); the row sums are DPP-only (ff_row_sum).  Two rows at a time, stage by stage.
 
@@ -275,20 +301,22 @@ __device__ __forceinline__ void ff_colsum_out(const float* cr, float* partial, i
   partial[((int64_t)q0 * gridDim.x + blockIdx.x) * FF_D + tid] = s0;
   partial[((int64_t)(q0 + 1) * gridDim.x + blockIdx.x) * FF_D + tid] = s1;
 }
-// 64 rows x 64 pieces of 16 bytes from HBM rows into an image (rows beyond the panel = copies of its last row: finite)
-__device__ __forceinline__ void ff_panel_in(const bf16_t* g, unsigned char* img, int nrows, int tid) {
-  uint4 xr[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
+// 64 rows x 64 pieces of 16 bytes from HBM rows into an image (rows beyond the panel = copies of its last row: finite).
+// Eight NAMED registers, every piece requested before the first is stored (as a local array the pieces went through scratch).
+__device__ __forceinline__ uint4 ff_panel_piece(const bf16_t* g, int64_t ldg, int nrows, int idx) {
+  const int row = min(idx >> 6, nrows - 1), pc = idx & 63;
+  return *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(g + (int64_t)row * ldg) + pc * 16);
+}
+__device__ __forceinline__ void ff_panel_in(const bf16_t* g, unsigned char* img, int nrows, int tid, int64_t ldg = FF_D) {
+  const uint4 x0 = ff_panel_piece(g, ldg, nrows, tid + 0 * FF_THREADS), x1 = ff_panel_piece(g, ldg, nrows, tid + 1 * FF_THREADS);
+  const uint4 x2 = ff_panel_piece(g, ldg, nrows, tid + 2 * FF_THREADS), x3 = ff_panel_piece(g, ldg, nrows, tid + 3 * FF_THREADS);
+  const uint4 x4 = ff_panel_piece(g, ldg, nrows, tid + 4 * FF_THREADS), x5 = ff_panel_piece(g, ldg, nrows, tid + 5 * FF_THREADS);
+  const uint4 x6 = ff_panel_piece(g, ldg, nrows, tid + 6 * FF_THREADS), x7 = ff_panel_piece(g, ldg, nrows, tid + 7 * FF_THREADS);
+  auto put = [&](int j, const uint4& v) {
     const int idx = tid + j * FF_THREADS;
-    const int row = min(idx >> 6, nrows - 1), pc = idx & 63;
-    xr[j] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(g + (int64_t)row * FF_D) + pc * 16);
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int idx = tid + j * FF_THREADS;
-    *reinterpret_cast<uint4*>(img + (idx >> 6) * FF_RS + (idx & 63) * 16) = xr[j];
-  }
+    *reinterpret_cast<uint4*>(img + (idx >> 6) * FF_RS + (idx & 63) * 16) = v;
+  };
+  put(0, x0); put(1, x1); put(2, x2); put(3, x3); put(4, x4); put(5, x5); put(6, x6); put(7, x7);
 }
 __device__ __forceinline__ void ff_panel_out(const unsigned char* img, bf16_t* g, int nrows, int tid) {
 #pragma unroll

@@ -57,7 +57,8 @@ struct FfnFwdParams {
 // INFER: the frozen-weight forward (DDIM sampler at batches beyond the row-panel kernels of linln_panel.hip): nothing is saved
 // for a backward -- no f1 / s1 / s2 / x1 rows, no statistics, no ReLU bits leave the workgroup
 template <bool OUT, bool QKV, bool ATT, bool INFER = false>
-__global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams p) {
+__global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams) {
+  ff_karg_t<FfnFwdParams>& p = ff_kargs<FfnFwdParams>();
   static_assert(!ATT || QKV, "the attention rides behind the QKV tail");
   static_assert(!INFER || (OUT && !ATT), "the frozen-weight form: attention epilogue, no attention tail");
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * FF_BUF];
@@ -297,10 +298,10 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams 
       __syncthreads();                   // image H = the attention output of all eight heads
       bf16_t* ag = p.attn_next + (int64_t)r0 * FF_D;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) ff_out_piece(imgH, ag, FF_D, nrows, tid + j * FF_THREADS);
+      for (int j = 0; j < 8; ++j) ff_out_piece(imgH, ag, FF_D, nrows, ff_fresh(tid + j * FF_THREADS));
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) ff_out_piece(imgX, qg + 2 * FF_CHUNK, 3 * FF_D, nrows, tid + j * FF_THREADS);
+    for (int j = 0; j < 8; ++j) ff_out_piece(imgX, qg + 2 * FF_CHUNK, 3 * FF_D, nrows, ff_fresh(tid + j * FF_THREADS));
     FF_STAMP(9 + 4 * p.nchunk);
   }
 }

@@ -35,19 +35,7 @@ struct FfnBwdParams {
 __device__ __forceinline__ void ff_qkv_dgrad(const bf16_t* addend, const bf16_t* dq, const bf16_t* wqkvtp, unsigned char* imgZ,
                                              unsigned char* imgD, int nrows, int tid, int wave_s, int l16, int colb) {
   ff_panel_in(addend, imgZ, nrows, tid);
-  {
-    uint4 xr[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int idx = tid + j * FF_THREADS;
-      xr[j] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(dq + (int64_t)min(idx >> 6, nrows - 1) * (3 * FF_D)) + (idx & 63) * 16);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int idx = tid + j * FF_THREADS;
-      *reinterpret_cast<uint4*>(imgD + (idx >> 6) * FF_RS + (idx & 63) * 16) = xr[j];
-    }
-  }
+  ff_panel_in(dq, imgD, nrows, tid, 3 * FF_D);
   __syncthreads();
   f32x4_t accd[4][FF_NT];
   ff_zero(accd);
@@ -99,7 +87,8 @@ __device__ __forceinline__ void ff_qkv_dgrad(const bf16_t* addend, const bf16_t*
 }
 
 template <bool OUT, bool QKVH, bool ATT>
-__global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams p) {
+__global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams) {
+  ff_karg_t<FfnBwdParams>& p = ff_kargs<FfnBwdParams>();
   static_assert(!ATT || OUT, "the attention backward rides behind the out-projection's dgrad");
   __shared__ float attL[ATT ? FF_WAVES : 1][64], attD[ATT ? FF_WAVES : 1][64];   // per head: the rows' lse, D = sum_key P dP
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * FF_BUF];
@@ -111,12 +100,11 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams 
   const int g = lane >> 4, l16 = lane & 15;
   const int r0 = blockIdx.x * p.P;
   const int nrows = min(p.P, p.M - r0);
-  const int colb = wave * 16 * FF_NT + 4 * g;
   FF_STAMP(0);
   if constexpr (QKVH) {
     // ---- dy = dqkv_next . Wqkv_next + ds1_next (the NEXT layer's in-projection dgrad + its residual addend) -> image Z
     ff_qkv_dgrad(p.ds1_next + (int64_t)r0 * FF_D, p.dqkv_next + (int64_t)r0 * (3 * FF_D), p.wqkvtp, imgZ, imgD, nrows, tid,
-                 wave_s, l16, colb);
+                 wave_s, l16, ff_colb());
   }
   // ---- LayerNorm2 backward, row-wise: dz2 rows -> image Z (+ HBM); its dgamma | dbeta through image D's storage
   {
@@ -141,6 +129,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams 
     };
     ff_gemm<FF_RING_BA>(p.w2tp + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgZ, ff_lane(), acca, sideA);
     __syncthreads();                     // every wave is past the previous chunk's second GEMM: image D may be rewritten
+    const int cb = ff_colb();
 #pragma unroll
     for (int u = 0; u < FF_NT; ++u) {
 #pragma unroll
@@ -152,7 +141,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams 
           const bool on = bit < 32 ? ((mk.x >> bit) & 1u) : ((mk.y >> (bit - 32)) & 1u);
           v[r] = on ? acca[mt][u][r] : 0.f;
         }
-        *reinterpret_cast<bf16x4_t*>(imgD + (16 * mt + l16) * FF_RS + (colb + 16 * u) * 2) = ff_pack4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<bf16x4_t*>(imgD + (16 * mt + l16) * FF_RS + (cb + 16 * u) * 2) = ff_pack4(v[0], v[1], v[2], v[3]);
       }
     }
     __syncthreads();                     // image D = dz1 chunk complete
@@ -165,12 +154,13 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams 
   // ---- dx1 = dx + dz2 (the residual path) -> image D
   __syncthreads();
   FF_STAMP(2);
+  const int cb = ff_colb();
 #pragma unroll
   for (int u = 0; u < FF_NT; ++u) {
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
-      const bf16x4_t zv = *reinterpret_cast<const bf16x4_t*>(imgZ + (16 * mt + l16) * FF_RS + (colb + 16 * u) * 2);
-      *reinterpret_cast<bf16x4_t*>(imgD + (16 * mt + l16) * FF_RS + (colb + 16 * u) * 2) =
+      const bf16x4_t zv = *reinterpret_cast<const bf16x4_t*>(imgZ + (16 * mt + l16) * FF_RS + (cb + 16 * u) * 2);
+      *reinterpret_cast<bf16x4_t*>(imgD + (16 * mt + l16) * FF_RS + (cb + 16 * u) * 2) =
           ff_pack4(accx[mt][u][0] + (float)zv[0], accx[mt][u][1] + (float)zv[1], accx[mt][u][2] + (float)zv[2],
                    accx[mt][u][3] + (float)zv[3]);
     }
@@ -196,11 +186,12 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams 
     const bf16_t* qb = ATT ? p.qkv + (int64_t)r0 * (3 * FF_D) + 64 * wave_s + 8 * g : nullptr;
     auto sideo = [&](auto, int) {};
     ff_gemm<FF_RING_BB>(p.wotp, wave_s * FF_NT, imgZ, ff_lane(), acco, sideo);
+    const int cb = ff_colb();
 #pragma unroll
     for (int u = 0; u < FF_NT; ++u) {
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
-        *reinterpret_cast<bf16x4_t*>(imgD + (16 * mt + l16) * FF_RS + (colb + 16 * u) * 2) =
+        *reinterpret_cast<bf16x4_t*>(imgD + (16 * mt + l16) * FF_RS + (cb + 16 * u) * 2) =
             ff_pack4(acco[mt][u][0], acco[mt][u][1], acco[mt][u][2], acco[mt][u][3]);
     }
     if constexpr (!ATT) {
@@ -405,11 +396,12 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams 
         put(0, n0); put(1, n1); put(2, n2); put(3, n3); put(4, n4); put(5, n5); put(6, n6); put(7, n7);
       }
       __syncthreads();                   // image D = ds1 rows
+      const int cb = ff_colb();
 #pragma unroll
       for (int u = 0; u < FF_NT; ++u) {
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
-          bf16x4_t* slot = reinterpret_cast<bf16x4_t*>(imgD + (16 * mt + l16) * FF_RS + (colb + 16 * u) * 2);
+          bf16x4_t* slot = reinterpret_cast<bf16x4_t*>(imgD + (16 * mt + l16) * FF_RS + (cb + 16 * u) * 2);
           const bf16x4_t av = *slot;
           *slot = ff_pack4(accd[mt][u][0] + (float)av[0], accd[mt][u][1] + (float)av[1], accd[mt][u][2] + (float)av[2],
                            accd[mt][u][3] + (float)av[3]);

@@ -1,0 +1,96 @@
+"""Register and scratch budget of every kernel in csrc/ sources: compiles each source with the Makefile's flags plus
+-Rpass-analysis=kernel-resource-usage (device side only, no object kept) and prints, per kernel, VGPRs, AGPRs, SGPRs,
+VGPR / SGPR spills, scratch bytes per lane, occupancy (waves per SIMD) and LDS bytes.  Runs without a GPU.
+Usage: python tools/kernel_resources.py [--filter SUBSTR] [--json] [file.hip ...]     (default: ffn_chain.hip ffn_chain_bwd.hip)"""
+import argparse
+import json
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "inferbiomechanics_amd", "csrc")
+FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]   # csrc/Makefile CXXFLAGS
+KEYS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch",
+        "Occupancy [waves/SIMD]": "occupancy", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill",
+        "LDS Size [bytes/block]": "lds"}
+_REMARK = re.compile(r"remark:\s+(Function Name|[A-Za-z][A-Za-z \[\]/]*?):\s+(\S+)\s+\[-Rpass-analysis")
+
+
+def hipcc():
+    for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
+        if c and os.path.exists(c):
+            return c
+    return None
+
+
+def short_name(mangled):
+    """_ZN12_GLOBAL__N_120ffn_chain_fwd_kernelILb1ELb1ELb1ELb0EEEvNS_12FfnFwdParamsE -> ffn_chain_fwd_kernel<1,1,1,0>
+    (template arguments that are bools or ints; anything else keeps the mangled tail)"""
+    m = re.match(r"_ZN(?:12_GLOBAL__N_1)?(\d+)", mangled)
+    if not m:
+        return mangled
+    n = int(m.group(1))
+    start = m.end()
+    name = mangled[start:start + n]
+    rest = mangled[start + n:]
+    if rest.startswith("I"):
+        args = re.findall(r"L[bij](-?\d+|n\d+)E", rest[: rest.find("EE") + 1] if "EE" in rest else rest)
+        if args:
+            return f"{name}<{','.join(a.replace('n', '-') for a in args)}>"
+    return name
+
+
+def resources(src, extra=()):
+    """[{kernel, mangled, vgpr, agpr, sgpr, vgpr_spill, sgpr_spill, scratch, occupancy, lds}] of one source"""
+    cc = hipcc()
+    if cc is None:
+        raise RuntimeError("hipcc not found")
+    path = src if os.path.isabs(src) else os.path.join(CSRC, src)
+    with tempfile.TemporaryDirectory() as td:
+        cmd = [cc, *FLAGS, *extra, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", path,
+               "-o", os.path.join(td, "dev.o")]
+        r = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"{' '.join(cmd)} failed:\n{r.stderr[-4000:]}")
+    out, cur = [], None
+    for line in r.stderr.splitlines():
+        m = _REMARK.search(line)
+        if not m:
+            continue
+        key, val = m.group(1).strip(), m.group(2)
+        if key == "Function Name":
+            cur = {"source": os.path.basename(path), "kernel": short_name(val), "mangled": val}
+            out.append(cur)
+        elif cur is not None and key in KEYS:
+            cur[KEYS[key]] = int(val) if val.lstrip("-").isdigit() else val
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("sources", nargs="*", default=["ffn_chain.hip", "ffn_chain_bwd.hip"])
+    ap.add_argument("--filter", default="", help="only kernels whose short name contains this")
+    ap.add_argument("--json", action="store_true")
+    ap.add_argument("-D", action="append", default=[], help="extra -D definitions (e.g. -D IB_AB)")
+    a = ap.parse_args()
+    extra = [f"-D{d}" for d in a.D]
+    with ThreadPoolExecutor(max_workers=min(4, len(a.sources))) as ex:
+        rows = [k for ks in ex.map(lambda s: resources(s, extra), a.sources) for k in ks]
+    rows = [k for k in rows if a.filter in k["kernel"]]
+    if a.json:
+        print(json.dumps(rows, indent=1))
+        return 0
+    cols = ("vgpr", "agpr", "sgpr", "vgpr_spill", "sgpr_spill", "scratch", "occupancy", "lds")
+    print(f"{'source':18s} {'kernel':40s} " + " ".join(f"{c:>10s}" for c in cols))
+    for k in rows:
+        print(f"{k['source']:18s} {k['kernel']:40s} " + " ".join(f"{str(k.get(c, '?')):>10s}" for c in cols))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
