@@ -294,6 +294,22 @@ int ib_optim_step_sources(int opt, float* p, const float* g, float* s1, float* s
  * ib_optim_ticket_words() zero-initialised int32 words (a top word + 32 sub-counters, one 128-byte line each: the exit
  * tickets are drawn in two levels so no single address serialises the grid); the kernel leaves it zeroed. */
 int ib_optim_ticket_words(void);
+/* ib_optim_step / ib_optim_step_sources that also advance an exponential moving average of the parameters in the same pass:
+ * for every element the launch updates (not kind-3 ranges), after the update, ema = fma(d, ema, (1 - d) * p_new) in fp32
+ * with d = min(ema_decay, (1 + step) / (10 + step)) if ema_warmup, else ema_decay -- `step` is the number the bias
+ * corrections use (*step_dev + 1 or *step_dev + step), d is computed in double and rounded to fp32 once, so a replayed
+ * graph follows the device counter.  ema_decay = 0 gives ema == p_new and ema_decay = 1 (no warmup) leaves ema unchanged,
+ * bit for bit; p, s1, s2 and the shadow are exactly those of the entry without _ema.  ema: n fp32, 16-byte aligned (like
+ * p); ema == NULL or ema_decay outside [0, 1] -> IB_E_ARG. */
+int ib_optim_step_ema(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
+                      float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16,
+                      float* ema, float ema_decay, int ema_warmup, ib_stream_t stream);
+int ib_optim_step_sources_ema(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
+                              float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16,
+                              int nsrc, const int64_t* start, const int64_t* len, const int32_t* kind,
+                              const void* const* base, const int64_t* stride, const int32_t* count, const float* scale,
+                              const float* loss_col, int64_t loss_ld, int64_t loss_rows, float loss_scale,
+                              float* loss_out, float* ema, float ema_decay, int ema_warmup, ib_stream_t stream);
 
 /* ---- fused token-local half of the post-norm encoder layer (csrc/ffn_chain.hip), bf16, d == 512, ffn a multiple of 512
  * (<= 4096).  Replaces, per layer and direction, the feed-forward sublayer's two nn.Linear GEMMs + residual + nn.LayerNorm

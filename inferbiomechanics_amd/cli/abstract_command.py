@@ -105,7 +105,10 @@ class AbstractCommand:
         raise hip.HipError("get_model(device='cpu'): the HIP path has no CPU fallback and no GPU is visible; "
                            "pass device='gpu' (CLI: --device gpu) on an MI355X box")
 
-    def load_latest_checkpoint(self, model, optimizer=None, checkpoint_dir="../checkpoints"):
+    def load_latest_checkpoint(self, model, optimizer=None, checkpoint_dir="../checkpoints", use_ema=False):
+        """use_ema: load the checkpoint's EMA weights ('ema_state_dict', `train --ema-decay`) into the model instead of
+        'model_state_dict' (a checkpoint without them is an error).  A HipTrainer with an EMA gets the saved EMA back, or
+        starts it from the loaded weights when the checkpoint has none."""
         if not os.path.exists(checkpoint_dir):
             print("Checkpoint directory does not exist!")
             return -1, 0
@@ -118,8 +121,11 @@ class AbstractCommand:
         latest = os.path.join(checkpoint_dir, checkpoints[-1])
         logging.info(f"latest_checkpoint={latest!r}")
         checkpoint = torch.load(latest, map_location='cpu')
+        if use_ema and 'ema_state_dict' not in checkpoint:
+            raise ValueError(f"{latest} holds no EMA weights (it was not written by `train --ema-decay D` with D > 0): "
+                             f"drop --use-ema to load its weights")
         state = {(k[len('module.'):] if k.startswith('module.') else k): v
-                 for k, v in checkpoint['model_state_dict'].items()}
+                 for k, v in checkpoint['ema_state_dict' if use_ema else 'model_state_dict'].items()}
         target = model.module if hasattr(model, 'module') else model
         target.load_state_dict(state)
         osd = checkpoint.get('optimizer_state_dict')
@@ -127,6 +133,12 @@ class AbstractCommand:
             if osd is not None:
                 optimizer.load_optimizer_state_dict(osd)     # its own flat payload, or a torch.optim state dict
             optimizer.refresh_after_param_load()             # always: the parameters changed under the bf16 shadow
+            if getattr(optimizer, 'ema', None) is not None:
+                if 'ema_state_dict' in checkpoint:
+                    optimizer.load_ema_state_dict(checkpoint['ema_state_dict'])
+                else:
+                    optimizer.reset_ema()
+                    logging.info(f"{latest} holds no EMA weights: the EMA starts from the loaded weights")
         elif optimizer is not None and osd is not None:
             if 'layout' in osd and 'state' not in osd:       # written by the fused trainer, loaded under --eager
                 osd = flat_to_torch_optimizer_state(osd, target)

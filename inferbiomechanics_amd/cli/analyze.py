@@ -44,6 +44,8 @@ class AnalyzeCommand(AbstractCommand):
                        help='[diffusion models] seed of the start noise (window i of a split draws from (seed, i)).')
         p.add_argument('--sample-batch', type=int, default=1,
                        help='[diffusion models] windows per sampler call; still one CSV row per window.')
+        p.add_argument('--use-ema', action='store_true', default=False,
+                       help='Evaluate the EMA weights of the checkpoint (`train --ema-decay`) instead of its last weights.')
 
     def run(self, args: argparse.Namespace):
         if 'command' in args and args.command != 'analyze':
@@ -65,7 +67,7 @@ class AnalyzeCommand(AbstractCommand):
                                        dropout_prob=0.0, root_history_len=10,
                                        output_data_format=args.output_data_format, device=device,
                                        compute_dtype=dtype_of(args)).to(device)
-                self.load_latest_checkpoint(model, checkpoint_dir=checkpoint_dir)
+                self.load_latest_checkpoint(model, checkpoint_dir=checkpoint_dir, use_ema=getattr(args, 'use_ema', False))
                 model.eval()
             evaluator = RegressionLossEvaluator(dataset=dataset, split=split, device=device)
             loader = DataLoader(dataset, batch_size=1, shuffle=False, num_workers=args.data_loading_workers)
@@ -104,7 +106,7 @@ class AnalyzeCommand(AbstractCommand):
             dataset = view.dataset
             if predictor is None:
                 model = self.diffusion_model(args, view, device)
-                self.load_latest_checkpoint(model, checkpoint_dir=checkpoint_dir)
+                self.load_latest_checkpoint(model, checkpoint_dir=checkpoint_dir, use_ema=getattr(args, 'use_ema', False))
                 model.eval()
                 predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
                                                     output_data_format=args.output_data_format)

@@ -87,6 +87,12 @@ class TrainCommand(AbstractCommand):
                        help='[diffusion, --window-cache] keep the device-resident loss of every Nth step for the report.')
         p.add_argument('--seed', type=int, default=None,
                        help='torch.manual_seed for this run (initial weights, dropout masks, diffusion noise).')
+        p.add_argument('--ema-decay', type=float, default=0.0,
+                       help='Keep an exponential moving average of the weights with this decay, advanced inside the fused '
+                            'optimizer launches and saved in the checkpoints (0 = off; 0.999-0.9999 are usual). '
+                            '`analyze --use-ema` / `visualize --use-ema` then load it. Not with --eager.')
+        p.add_argument('--no-ema-warmup', action='store_true',
+                       help='Use --ema-decay from the first step (default: min(decay, (1 + step) / (10 + step))).')
 
     # ------------------------------------------------------------------------------------------
     def run(self, args: argparse.Namespace):
@@ -98,6 +104,7 @@ class TrainCommand(AbstractCommand):
         log_to_wandb: bool = not args.no_wandb
         diffusion = is_diffusion(model_type)
 
+        check_ema_args(args)
         if getattr(args, 'seed', None) is not None:
             torch.manual_seed(args.seed)
         geometry = self.ensure_geometry(args.geometry_folder)
@@ -169,7 +176,9 @@ class TrainCommand(AbstractCommand):
             optimizer = make_torch_optimizer(args.opt_type, model.parameters(), args.learning_rate)
         else:
             trainer = HipTrainer(model, "diffusion" if diffusion else "regression", args.opt_type, args.learning_rate,
-                                 args=args, use_graph=not args.no_graph, bucket_mb=args.bucket_mb)
+                                 args=args, use_graph=not args.no_graph, bucket_mb=args.bucket_mb,
+                                 ema_decay=getattr(args, 'ema_decay', 0.0),
+                                 ema_warmup=not getattr(args, 'no_ema_warmup', False))
 
         if getattr(args, 'loss_every', 1) < 1:
             raise SystemExit("--loss-every must be >= 1")
@@ -350,6 +359,15 @@ def save_motion_windows(dataset, path: str, chunk: int = 4096):
     os.replace(tmp, path)
 
 
+def check_ema_args(args: argparse.Namespace):
+    """--ema-decay D: D in [0, 1); the EMA lives in the fused optimizer launches, so --eager (torch.optim) has none"""
+    d = getattr(args, 'ema_decay', 0.0)
+    if not 0.0 <= d < 1.0:
+        raise SystemExit(f"--ema-decay must lie in [0, 1) (0 = off, 0.999-0.9999 are usual), got {d}")
+    if d > 0 and getattr(args, 'eager', False):
+        raise SystemExit("--ema-decay needs the fused trainer: --eager runs torch.optim, which keeps no EMA of the weights")
+
+
 def make_torch_optimizer(opt_type: str, params, lr: float):
     table = {'adagrad': torch.optim.Adagrad, 'adam': torch.optim.Adam, 'sgd': torch.optim.SGD,
              'rmsprop': torch.optim.RMSprop, 'adadelta': torch.optim.Adadelta, 'adamax': torch.optim.Adamax}
@@ -360,11 +378,17 @@ def make_torch_optimizer(opt_type: str, params, lr: float):
 
 
 def save_checkpoint(checkpoint_dir: str, epoch: int, batch: int, model, opt):
-    """file grammar of train.py:271-278; keys are saved WITHOUT DDP's `module.` prefix"""
+    """file grammar of train.py:271-278; keys are saved WITHOUT DDP's `module.` prefix.  A trainer with an EMA adds
+    'ema_state_dict' (the model's state dict over the EMA weights) and 'ema' ({'decay', 'warmup'}); without one the file
+    holds the three reference keys only"""
     os.makedirs(checkpoint_dir, exist_ok=True)
     path = f"{checkpoint_dir}/epoch_{epoch}_batch_{batch}.pt"
     osd = opt.optimizer_state_dict() if hasattr(opt, 'optimizer_state_dict') else opt.state_dict()
-    torch.save({'epoch': epoch,
-                'model_state_dict': {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
-                'optimizer_state_dict': osd}, path)
+    ckpt = {'epoch': epoch,
+            'model_state_dict': {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
+            'optimizer_state_dict': osd}
+    if getattr(opt, 'ema', None) is not None:
+        ckpt['ema_state_dict'] = opt.ema_state_dict()
+        ckpt['ema'] = {'decay': opt.ema_decay, 'warmup': opt.ema_warmup}
+    torch.save(ckpt, path)
     return path

@@ -36,6 +36,8 @@ class VisualizeCommand(AbstractCommand):
         add_component_flags(p, train_defaults=True)
         add_additive_flags(p)
         p.add_argument('--num-frames', type=int, default=8, help='How many windows to evaluate and print.')
+        p.add_argument('--use-ema', action='store_true', default=False,
+                       help='Load the EMA weights of the checkpoint (`train --ema-decay`) instead of its last weights.')
 
     def run(self, args: argparse.Namespace):
         if 'command' in args and args.command != 'visualize':
@@ -55,7 +57,7 @@ class VisualizeCommand(AbstractCommand):
                                dropout_prob=args.dropout_prob, root_history_len=10,
                                output_data_format=args.output_data_format, device=device,
                                compute_dtype=dtype_of(args)).to(device)
-        self.load_latest_checkpoint(model, checkpoint_dir=checkpoint_dir)
+        self.load_latest_checkpoint(model, checkpoint_dir=checkpoint_dir, use_ema=getattr(args, 'use_ema', False))
         model.eval()
         evaluator = RegressionLossEvaluator(dataset=dataset, split='test', device=device)
         if not have_gui:

@@ -2,7 +2,9 @@
 // torch.optim's per-tensor foreach kernels): torch.optim.{SGD,Adam,RMSprop,Adagrad,Adadelta,Adamax}
 // with only lr set, as src/cli/train.py:183-194 constructs them.  The DDP mean (1/world) is folded
 // in as grad_scale; an optional bf16 shadow of the parameters is refreshed in the same pass so the
-// bf16 GEMMs never need a separate cast kernel.
+// bf16 GEMMs never need a separate cast kernel.  With EMA on (optim_kernel<SRC, true>, the *_ema entries) the same pass also
+// advances an exponential moving average of the parameters from the new value it already holds in registers: one more fp32
+// read and write per parameter, no launch of its own, and the decay follows the device step counter under graph replay.
 #include "ib_common.h"
 
 namespace {
@@ -10,6 +12,7 @@ namespace {
 struct OptArgs {
   float* p; const float* g; float* s1; float* s2; bf16_t* shadow;
   int64_t n; float lr; float gscale; int step; int32_t* step_dev; int32_t* ticket; int opt;
+  float* ema; float ema_decay; int ema_warmup;     // read by optim_kernel<SRC, true> only
 };
 
 // Gradient SOURCES (ib_optim_step_sources): ranges of the flat buffer whose gradient is still a set of partial sums when
@@ -65,6 +68,24 @@ __device__ __forceinline__ float opt_update(const OptArgs& a, float p, float g, 
   }
 }
 
+// ema <- d * ema + (1 - d) * p_new as ONE fma over the rounded product: d = 0 gives p_new and d = 1 the old ema, bit for bit
+__device__ __forceinline__ float ema_update(float d, float e, float p) { return __fmaf_rn(d, e, (1.f - d) * p); }
+
+// The EMA reads the new parameters back through a volatile load of what this thread has just stored (an L2 hit), not
+// from the registers of the update: used there, they changed how the compiler vectorised and contracted the update
+// itself (p and s1 of Adam's column-sum ranges came out one rounding apart from the launch without the EMA).  This way
+// the update is the same code in both instantiations, bit for bit.
+__device__ __forceinline__ void ema4(const OptArgs& a, float d, int64_t i, int nvalid) {
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  const f4v p = *reinterpret_cast<const volatile f4v*>(a.p + 4 * i);
+  float4 e = reinterpret_cast<float4*>(a.ema)[i];
+  e.x = ema_update(d, e.x, p.x);
+  if (nvalid >= 2) e.y = ema_update(d, e.y, p.y);
+  if (nvalid >= 3) e.z = ema_update(d, e.z, p.z);
+  if (nvalid >= 4) e.w = ema_update(d, e.w, p.w);
+  reinterpret_cast<float4*>(a.ema)[i] = e;
+}
+
 // slab-backed ranges are summed by whichever thread owns the element; column-sum ranges are left to the dedicated
 // cooperative blocks below (a single thread summing 256 strided rows was a 100-us tail)
 // (the host passes the sources sorted by start).  Two things made this path 40 us of the transformer's 111-us launch
@@ -106,7 +127,8 @@ __device__ __forceinline__ bool source_grad4(const OptSources& S, const float* g
   return true;
 }
 
-__device__ __forceinline__ void apply4(const OptArgs& a, int64_t i, float4 g, float bc1, float bc2s, int nvalid) {
+template <bool EMA>
+__device__ __forceinline__ void apply4(const OptArgs& a, int64_t i, float4 g, float bc1, float bc2s, float d, int nvalid) {
   // nvalid < 4 only at the ragged end of a column-sum range (the remaining lanes belong to alignment padding)
   const bool has1 = a.s1 != nullptr, has2 = a.s2 != nullptr;
   float4 p = reinterpret_cast<float4*>(a.p)[i];
@@ -128,11 +150,14 @@ __device__ __forceinline__ void apply4(const OptArgs& a, int64_t i, float4 g, fl
     o[0] = (bf16_t)p.x; o[1] = (bf16_t)p.y; o[2] = (bf16_t)p.z; o[3] = (bf16_t)p.w;
     reinterpret_cast<bf16x4_t*>(a.shadow)[i] = o;
   }
+  if constexpr (EMA) ema4(a, d, i, nvalid);
 }
 
 // SRC: blocks [0, main_blocks) walk the flat buffer (skipping column-sum ranges); block main_blocks + b owns 64 columns of
 // a column-sum range: 16 float4 columns x 16 row groups, LDS combine in the order of colsum_segments_kernel, update.
-template <bool SRC>
+// EMA: every element this launch updates also updates a.ema (kind-3 ranges leave both untouched); EMA = false is the
+// kernel without it, instruction for instruction.
+template <bool SRC, bool EMA>
 __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int main_blocks) {
   // self-counting mode (ticket != NULL): *step_dev holds the number of COMPLETED steps; every block reads it on
   // entry, and the block that draws the last exit ticket publishes step and resets the ticket -- it exits after
@@ -148,6 +173,10 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int
     bc1 = (float)(1.0 - pow(0.9, (double)step));
     bc2s = (float)sqrt(1.0 - pow(0.999, (double)step));
   }
+  // EMA decay from the same step number (warmup: min(D, (1 + step) / (10 + step))), in double, rounded once
+  float d = 0.f;
+  if constexpr (EMA)
+    d = (float)(a.ema_warmup ? fmin((double)a.ema_decay, (1.0 + step) / (10.0 + step)) : (double)a.ema_decay);
   const int64_t n4 = a.n / 4;
   const bool has1 = a.s1 != nullptr, has2 = a.s2 != nullptr;
   // the column-sum blocks are long dependent chains (256 strided rows each): they take the FIRST physical block ids so
@@ -189,7 +218,7 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int
 #pragma unroll
         for (int k = 1; k < 16; ++k) { const float4 w = red[k][c4]; t.x += w.x; t.y += w.y; t.z += w.z; t.w += w.w; }
         t.x *= r.scale; t.y *= r.scale; t.z *= r.scale; t.w *= r.scale;
-        apply4(a, (r.start + o) >> 2, t, bc1, bc2s, (int)min((int64_t)4, r.len - o));
+        apply4<EMA>(a, (r.start + o) >> 2, t, bc1, bc2s, d, (int)min((int64_t)4, r.len - o));
       }
     }
   } else {
@@ -216,6 +245,7 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int
       o[0] = (bf16_t)p.x; o[1] = (bf16_t)p.y; o[2] = (bf16_t)p.z; o[3] = (bf16_t)p.w;
       reinterpret_cast<bf16x4_t*>(a.shadow)[i] = o;
     }
+    if constexpr (EMA) ema4(a, d, i, 4);
   }
   // tail (n % 4)
   const int64_t t0 = n4 * 4;
@@ -226,6 +256,7 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int
     if (has1) a.s1[i] = s1;
     if (has2) a.s2[i] = s2;
     if (a.shadow) a.shadow[i] = (bf16_t)p;
+    if constexpr (EMA) a.ema[i] = ema_update(d, a.ema[i], *(const volatile float*)(a.p + i));
   }
   }   // main blocks
   if constexpr (SRC) {
@@ -268,34 +299,35 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int
   }
 }
 
-}  // namespace
-
-extern "C" int ib_optim_ticket_words(void) { return OPT_TICKET_LINE * (1 + OPT_TICKET_SUBS); }
-
-extern "C" int ib_optim_step(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
-                             float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16,
-                             ib_stream_t stream) {
+// the two launchers behind the C entries: ema == NULL launches optim_kernel<SRC, false>, the kernel without the EMA
+int optim_plain(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr, float grad_scale, int32_t step,
+                int32_t* step_dev, int32_t* ticket, void* shadow_bf16, float* ema, float ema_decay, int ema_warmup,
+                ib_stream_t stream) {
   if (!p || !g || n <= 0 || opt < IB_OPT_SGD || opt > IB_OPT_ADAMAX) return IB_E_ARG;
   if (ticket && !step_dev) return IB_E_ARG;
   const bool need1 = opt != IB_OPT_SGD;
   const bool need2 = (opt == IB_OPT_ADAM || opt == IB_OPT_ADADELTA || opt == IB_OPT_ADAMAX);
   if ((need1 && !s1) || (need2 && !s2)) return IB_E_ARG;
   auto al16 = [](const void* q) { return !q || (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
-  if (!al16(p) || !al16(g) || !al16(s1) || !al16(s2) || (shadow_bf16 && reinterpret_cast<uintptr_t>(shadow_bf16) % 8))
+  if (!al16(p) || !al16(g) || !al16(s1) || !al16(s2) || !al16(ema) ||
+      (shadow_bf16 && reinterpret_cast<uintptr_t>(shadow_bf16) % 8))
     return IB_E_ARG;
   OptArgs a{p, g, need1 ? s1 : nullptr, need2 ? s2 : nullptr, reinterpret_cast<bf16_t*>(shadow_bf16),
-            n, lr, grad_scale, step, step_dev, ticket, opt};
-  hipLaunchKernelGGL(optim_kernel<false>, dim3(ib_grid_1d(n / 4 + 1, 256)), dim3(256), 0, ib_s(stream), a, OptSources{}, 0);
+            n, lr, grad_scale, step, step_dev, ticket, opt, ema, ema_decay, ema_warmup};
+  const dim3 grid(ib_grid_1d(n / 4 + 1, 256));
+  if (ema)
+    hipLaunchKernelGGL((optim_kernel<false, true>), grid, dim3(256), 0, ib_s(stream), a, OptSources{}, 0);
+  else
+    hipLaunchKernelGGL((optim_kernel<false, false>), grid, dim3(256), 0, ib_s(stream), a, OptSources{}, 0);
   IB_CHECK_LAUNCH();
   return IB_OK;
 }
 
-extern "C" int ib_optim_step_sources(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
-                                     float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket,
-                                     void* shadow_bf16, int nsrc, const int64_t* start, const int64_t* len,
-                                     const int32_t* kind, const void* const* base, const int64_t* stride,
-                                     const int32_t* count, const float* scale, const float* loss_col, int64_t loss_ld,
-                                     int64_t loss_rows, float loss_scale, float* loss_out, ib_stream_t stream) {
+int optim_sources(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr, float grad_scale,
+                  int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16, int nsrc, const int64_t* start,
+                  const int64_t* len, const int32_t* kind, const void* const* base, const int64_t* stride,
+                  const int32_t* count, const float* scale, const float* loss_col, int64_t loss_ld, int64_t loss_rows,
+                  float loss_scale, float* loss_out, float* ema, float ema_decay, int ema_warmup, ib_stream_t stream) {
   if (!p || !g || n <= 0 || opt < IB_OPT_SGD || opt > IB_OPT_ADAMAX) return IB_E_ARG;
   if (ticket && !step_dev) return IB_E_ARG;
   if (nsrc < 0 || nsrc > OPT_MAXSRC || (nsrc > 0 && (!start || !len || !kind || !base || !stride || !count))) return IB_E_ARG;
@@ -304,7 +336,8 @@ extern "C" int ib_optim_step_sources(int opt, float* p, const float* g, float* s
   const bool need2 = (opt == IB_OPT_ADAM || opt == IB_OPT_ADADELTA || opt == IB_OPT_ADAMAX);
   if ((need1 && !s1) || (need2 && !s2)) return IB_E_ARG;
   auto al16 = [](const void* q) { return !q || (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
-  if (!al16(p) || !al16(g) || !al16(s1) || !al16(s2) || (shadow_bf16 && reinterpret_cast<uintptr_t>(shadow_bf16) % 8))
+  if (!al16(p) || !al16(g) || !al16(s1) || !al16(s2) || !al16(ema) ||
+      (shadow_bf16 && reinterpret_cast<uintptr_t>(shadow_bf16) % 8))
     return IB_E_ARG;
   OptSources S{};
   S.n = nsrc;
@@ -329,12 +362,63 @@ extern "C" int ib_optim_step_sources(int opt, float* p, const float* g, float* s
     S.loss_col = loss_col; S.loss_ld = loss_ld; S.loss_rows = (int)loss_rows; S.loss_scale = loss_scale; S.loss_out = loss_out;
   }
   OptArgs a{p, g, need1 ? s1 : nullptr, need2 ? s2 : nullptr, reinterpret_cast<bf16_t*>(shadow_bf16),
-            n, lr, grad_scale, step, step_dev, ticket, opt};
+            n, lr, grad_scale, step, step_dev, ticket, opt, ema, ema_decay, ema_warmup};
   const int main_blocks = ib_grid_1d(n / 4 + 1, 256);
   int cs_blocks = 0;
   for (int j = 0; j < nsrc; ++j)
     if (kind[j] == 2) cs_blocks += (int)((len[j] + 63) / 64);
-  hipLaunchKernelGGL(optim_kernel<true>, dim3(main_blocks + cs_blocks), dim3(256), 0, ib_s(stream), a, S, main_blocks);
+  const dim3 grid(main_blocks + cs_blocks);
+  if (ema)
+    hipLaunchKernelGGL((optim_kernel<true, true>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks);
+  else
+    hipLaunchKernelGGL((optim_kernel<true, false>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks);
   IB_CHECK_LAUNCH();
   return IB_OK;
+}
+
+// the *_ema entries: a 16-byte aligned EMA buffer (like p) and a decay in [0, 1] (NaN fails the comparisons too)
+bool ema_args_ok(const float* ema, float ema_decay) {
+  return ema && reinterpret_cast<uintptr_t>(ema) % 16 == 0 && ema_decay >= 0.f && ema_decay <= 1.f;
+}
+
+}  // namespace
+
+extern "C" int ib_optim_ticket_words(void) { return OPT_TICKET_LINE * (1 + OPT_TICKET_SUBS); }
+
+extern "C" int ib_optim_step(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
+                             float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16,
+                             ib_stream_t stream) {
+  return optim_plain(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nullptr, 0.f, 0, stream);
+}
+
+extern "C" int ib_optim_step_ema(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
+                                 float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16,
+                                 float* ema, float ema_decay, int ema_warmup, ib_stream_t stream) {
+  if (!ema_args_ok(ema, ema_decay)) return IB_E_ARG;
+  return optim_plain(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup,
+                     stream);
+}
+
+extern "C" int ib_optim_step_sources(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
+                                     float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket,
+                                     void* shadow_bf16, int nsrc, const int64_t* start, const int64_t* len,
+                                     const int32_t* kind, const void* const* base, const int64_t* stride,
+                                     const int32_t* count, const float* scale, const float* loss_col, int64_t loss_ld,
+                                     int64_t loss_rows, float loss_scale, float* loss_out, ib_stream_t stream) {
+  return optim_sources(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nsrc, start, len, kind,
+                       base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out, nullptr, 0.f, 0,
+                       stream);
+}
+
+extern "C" int ib_optim_step_sources_ema(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
+                                         float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket,
+                                         void* shadow_bf16, int nsrc, const int64_t* start, const int64_t* len,
+                                         const int32_t* kind, const void* const* base, const int64_t* stride,
+                                         const int32_t* count, const float* scale, const float* loss_col,
+                                         int64_t loss_ld, int64_t loss_rows, float loss_scale, float* loss_out,
+                                         float* ema, float ema_decay, int ema_warmup, ib_stream_t stream) {
+  if (!ema_args_ok(ema, ema_decay)) return IB_E_ARG;
+  return optim_sources(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nsrc, start, len, kind,
+                       base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out, ema, ema_decay,
+                       ema_warmup, stream);
 }

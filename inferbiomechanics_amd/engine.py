@@ -269,9 +269,12 @@ class HipTrainer:
     """
 
     def __init__(self, model: HipModule, task: str, opt_type: str = "rmsprop", lr: float = 1e-4, args=None,
-                 group=None, bucket_mb: float = 13.0, use_graph: bool = True, overlap_comm: Optional[bool] = None):
+                 group=None, bucket_mb: float = 13.0, use_graph: bool = True, overlap_comm: Optional[bool] = None,
+                 ema_decay: float = 0.0, ema_warmup: bool = True):
         if task not in ("diffusion", "regression"):
             raise ValueError(task)
+        if not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
         if opt_type not in hip.OPT:
             raise ValueError("Invalid optimizer type: " + opt_type)          # train.py:195-197
         self.model, self.task, self.opt_type, self.lr = model, task, opt_type, lr
@@ -330,6 +333,10 @@ class HipTrainer:
         ns = hip.OPT_NUM_STATES[opt_type]
         self.s1 = torch.zeros_like(flat) if ns >= 1 else None
         self.s2 = torch.zeros_like(flat) if ns >= 2 else None
+        # EMA of the parameters (ema_decay > 0): advanced by the optimizer launches themselves, each over the range it updates
+        # (csrc/optim.hip, optim_kernel<SRC, true>); starts equal to the broadcast parameters, so identical on every rank
+        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
+        self.ema = flat.clone() if self.ema_decay > 0 else None
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)      # completed steps (device-resident)
         self.ticket = torch.zeros(hip.optim_ticket_words(), dtype=torch.int32, device=dev)   # optimizer exit tickets
         self.steps_done = 0
@@ -564,7 +571,13 @@ class HipTrainer:
         sl = lambda t: None if t is None else t[lo:hi]
         hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr, step=0,
                        step_dev=self.step_dev, ticket=self.ticket, grad_scale=1.0 / self.world,
-                       shadow=sl(m._shadow) if dt == torch.bfloat16 else None, sources=src)
+                       shadow=sl(m._shadow) if dt == torch.bfloat16 else None, sources=src, **self._ema_args(sl))
+
+    def _ema_args(self, sl) -> Dict:
+        """optim_step's EMA arguments for a launch over the slice `sl` selects (none with the EMA off: the entries without it)"""
+        if self.ema is None:
+            return {}
+        return {"ema": sl(self.ema), "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup}
 
     def _last_launch_range(self, done, src):
         """[lo, hi) of the flat buffers for the step's last optimizer launch + the done ranges left inside it"""
@@ -610,7 +623,7 @@ class HipTrainer:
                 w.wait()                             # stream-level on the GPU path: the SIDE stream waits, not the backward
             hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr, step=1,
                            step_dev=self.step_dev, grad_scale=1.0 / self.world,
-                           shadow=sl(m._shadow) if dt == torch.bfloat16 else None)
+                           shadow=sl(m._shadow) if dt == torch.bfloat16 else None, **self._ema_args(sl))
         self._br_opt.run(fn)
 
     def _prefix_range(self, prefix: str) -> Tuple[int, int]:
@@ -636,7 +649,7 @@ class HipTrainer:
         sl = lambda t: None if t is None else t[lo:hi]
         hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr, step=1,
                        step_dev=self.step_dev, grad_scale=1.0 / self.world,
-                       shadow=sl(m._shadow) if dt == torch.bfloat16 else None, sources=sources)
+                       shadow=sl(m._shadow) if dt == torch.bfloat16 else None, sources=sources, **self._ema_args(sl))
         self._early_done.append((lo, hi))
 
     def _stage(self, batch) -> Dict[str, torch.Tensor]:
@@ -1023,6 +1036,38 @@ class HipTrainer:
             steps = max(steps, int(float(st.get("step", 0))))
         self.steps_done = steps
         self.step_dev.fill_(steps)
+
+    # ---- EMA of the parameters ----------------------------------------------------------------------
+    def ema_state_dict(self) -> Dict:
+        """the model's state dict with every parameter replaced by its EMA (same names and shapes; buffers such as BatchNorm
+        running statistics verbatim): what load_state_dict of the model takes to sample from the EMA weights"""
+        if self.ema is None:
+            raise hip.HipError("this trainer keeps no EMA (ema_decay = 0)")
+        out = {}
+        for k, v in self.model.state_dict().items():
+            if k in self.layout:
+                off, n = self.layout[k]
+                v = self.ema[off:off + n].view(self._params[k].shape)
+            out[k] = v.detach().cpu().clone()
+        return out
+
+    def load_ema_state_dict(self, sd: Dict):
+        if self.ema is None:
+            raise hip.HipError("this trainer keeps no EMA (ema_decay = 0)")
+        missing = [k for k in self.layout if k not in sd]
+        if missing:
+            raise hip.HipError(f"EMA state lacks {missing[:4]}{' ...' if len(missing) > 4 else ''}")
+        for k, (off, n) in self.layout.items():
+            v = sd[k]
+            if tuple(v.shape) != tuple(self._params[k].shape):
+                raise hip.HipError(f"EMA state '{k}' has shape {tuple(v.shape)}, the parameter {tuple(self._params[k].shape)}")
+            self.ema[off:off + n].view(self._params[k].shape).copy_(v.to(torch.float32))
+
+    def reset_ema(self):
+        """EMA := the current parameters"""
+        if self.ema is None:
+            raise hip.HipError("this trainer keeps no EMA (ema_decay = 0)")
+        self.ema.copy_(self.flat)
 
     def refresh_after_param_load(self):
         """call after model.load_state_dict(): re-cast the bf16 shadow"""

@@ -102,6 +102,11 @@ _SIGS = {
     "ib_optim_step": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _vp]),
     "ib_optim_step_sources": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _c.c_int, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp]),
+    "ib_optim_step_ema": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _f32, _c.c_int,
+                                     _vp]),
+    "ib_optim_step_sources_ema": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _c.c_int,
+                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _f32,
+                                             _c.c_int, _vp]),
     "ib_im2col_replicate": (_c.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _c.c_int, _c.c_int, _vp]),
     "ib_col2im_replicate": (_c.c_int, [_vp, _i64, _vp, _c.c_int, _vp, _i64, _i64, _i64, _c.c_int, _c.c_int, _vp]),
     "ib_dropout": (_c.c_int, [_vp, _vp, _i64, _f32, _c.c_uint32, _i32, _vp, _c.c_int, _vp]),
@@ -200,6 +205,7 @@ class _DryRunLib:
     def __init__(self, real):
         self._real = real
         self.calls = []
+        self.ema_ranges = []     # per EMA optimizer launch: (ema pointer, n, [(start, len) of its kind-3 ranges])
 
     def __getattr__(self, name):
         res, args = _SIGS[name]
@@ -214,6 +220,13 @@ class _DryRunLib:
                 if v is not None or t not in (_vp,):
                     t.from_param(v) if hasattr(t, "from_param") else None
             self.calls.append(name)
+            if name == "ib_optim_step_ema":
+                self.ema_ranges.append((a[12], int(a[5]), []))
+            elif name == "ib_optim_step_sources_ema":
+                m = int(a[12])
+                rd = lambda p, ct: ctypes.cast(p, ctypes.POINTER(ct))
+                st, ln, kd = rd(a[13], ctypes.c_int64), rd(a[14], ctypes.c_int64), rd(a[15], ctypes.c_int32)
+                self.ema_ranges.append((a[25], int(a[5]), [(st[j], ln[j]) for j in range(m) if kd[j] == 3]))
             return 0
         return call
 
@@ -253,7 +266,7 @@ class _RecordingLib:
     """Records every C-ABI call (name + raw arguments) of one eager step so bench.py can re-issue each distinct
     call back-to-back inside a hipGraph and time it with HIP events (no host launch overhead in the number)."""
 
-    SKIP = ("ib_optim_step", "ib_counter_add")       # mutate state when repeated
+    SKIP = ("ib_optim_step", "ib_optim_step_ema", "ib_counter_add")       # mutate state when repeated
 
     def __init__(self, real):
         self._real = real
@@ -1344,14 +1357,17 @@ def optim_ticket_words() -> int:
 
 
 def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=1.0, shadow=None, ticket=None,
-               sources=None):
+               sources=None, ema=None, ema_decay=0.0, ema_warmup=True):
     """step: the step number of the bias corrections; with `step_dev` the kernel uses `*step_dev + step`, so the default is
     0 there (the device counter alone) and 1 without a device counter.
     sources = (items, part, rows, segs): the gradient of some ranges of g is still partial sums -- items =
     [(slab workspace, nslab, dw view into g)], segs = [(col0, ncols, dst view into g | the loss scalar, dst2, scale)] over
     part[:rows], or 7-tuples (.., part_i, rows_i) that name their own partial matrix (part may then be None).  The optimizer sums them itself (ib_optim_step_sources) instead of a separate ib_step_reduce launch.
     An optional fifth entry lists views into g whose parameters were already updated this step (launches over a slice of
-    the buffers with step_dev, no ticket and step=1: same step number as the self-counting launch that follows)."""
+    the buffers with step_dev, no ticket and step=1: same step number as the self-counting launch that follows).
+    ema: an fp32 buffer like p that the same pass advances, ema = d * ema + (1 - d) * p_new over every element it updates,
+    d = min(ema_decay, (1 + step) / (10 + step)) with ema_warmup, else ema_decay (the *_ema entries); None: the entries
+    without it."""
     if step is None:
         step = 0 if step_dev is not None else 1
     _req(p, "p", torch.float32, 1)
@@ -1368,6 +1384,12 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
         _req(shadow, "shadow", torch.bfloat16, 1)
         if shadow.numel() != n:
             raise HipError("shadow length mismatch")
+    if ema is not None:
+        _req(ema, "ema", torch.float32, 1)
+        if ema.numel() != n or not ema.is_contiguous():
+            raise HipError("ema length mismatch")
+        if not 0.0 <= float(ema_decay) <= 1.0:
+            raise HipError(f"ema_decay must lie in [0, 1], got {ema_decay}")
     if step_dev is not None:
         _req(step_dev, "step_dev", torch.int32)
     if ticket is not None:
@@ -1414,15 +1436,23 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
         A = lambda ct, k: (ct * m)(*[e[k] for e in ent])
         start, ln, kind = A(ctypes.c_int64, 0), A(ctypes.c_int64, 1), A(ctypes.c_int32, 2)
         base, stride, count, scale = A(ctypes.c_void_p, 3), A(ctypes.c_int64, 4), A(ctypes.c_int32, 5), A(ctypes.c_float, 6)
-        _check(lib().ib_optim_step_sources(OPT[opt], _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), n, float(lr), float(grad_scale),
-                                           int(step), _ptr(step_dev), _ptr(ticket), _ptr(shadow), m, cv(start), cv(ln),
-                                           cv(kind), cv(base), cv(stride), cv(count), cv(scale),
-                                           ctypes.c_void_p(loss[0]) if loss else None, ld, int(rows),
-                                           loss[1] if loss else 0.0, _ptr(loss[2]) if loss else None, stream_ptr()),
-               "ib_optim_step_sources")
+        args = (OPT[opt], _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), n, float(lr), float(grad_scale), int(step), _ptr(step_dev),
+                _ptr(ticket), _ptr(shadow), m, cv(start), cv(ln), cv(kind), cv(base), cv(stride), cv(count), cv(scale),
+                ctypes.c_void_p(loss[0]) if loss else None, ld, int(rows), loss[1] if loss else 0.0,
+                _ptr(loss[2]) if loss else None)
+        if ema is None:
+            _check(lib().ib_optim_step_sources(*args, stream_ptr()), "ib_optim_step_sources")
+        else:
+            _check(lib().ib_optim_step_sources_ema(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), stream_ptr()),
+                   "ib_optim_step_sources_ema")
         return
-    _check(lib().ib_optim_step(OPT[opt], _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), n, float(lr), float(grad_scale),
-                               int(step), _ptr(step_dev), _ptr(ticket), _ptr(shadow), stream_ptr()), "ib_optim_step")
+    args = (OPT[opt], _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), n, float(lr), float(grad_scale), int(step), _ptr(step_dev),
+            _ptr(ticket), _ptr(shadow))
+    if ema is None:
+        _check(lib().ib_optim_step(*args, stream_ptr()), "ib_optim_step")
+    else:
+        _check(lib().ib_optim_step_ema(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), stream_ptr()),
+               "ib_optim_step_ema")
 
 
 # --------------------------------------------------------------------------------------------

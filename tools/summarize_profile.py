@@ -37,7 +37,9 @@ ENTRY_OF = [# round 5: the one-window-panel launches with the attention inside (
             ("mlp_chain_kernel", "", "ib_mlp_chain_train"), ("mlp_chain2_kernel", "", "ib_mlp_chain_train"),
             ("time_mlp_bwd_kernel", "", "ib_time_mlp_bwd"), ("layernorm_bwd512_kernel", "", "ib_layernorm_bwd"),
             ("layernorm_fwd512_kernel", "", "ib_layernorm_fwd"), ("gemm_ring_wgrad_multi_kernel", "", "ib_linear_wgrad_slabs_multi"),
-            ("optim_kernel<true>", "", "ib_optim_step_sources"), ("optim_kernelILb1", "", "ib_optim_step_sources"),
+            ("optim_kernel<true, true>", "", "ib_optim_step_sources_ema"), ("optim_kernelILb1ELb1", "", "ib_optim_step_sources_ema"),
+            ("optim_kernel<false, true>", "", "ib_optim_step_ema"), ("optim_kernelILb0ELb1", "", "ib_optim_step_ema"),
+            ("optim_kernel<true", "", "ib_optim_step_sources"), ("optim_kernelILb1", "", "ib_optim_step_sources"),
             ("step_reduce_kernel", "", "ib_step_reduce"), ("time_mlp_fwd_kernel", "", "ib_mlp_chain_prep"),
             ("gemm_ring_kernel", "Lb0ELb0ELi2", "ib_linear_wgrad_slabs"), ("gemm_ring_kernel", "Lb1ELb1ELi0", "ib_linear_fwd"),
             ("gemm_ring_kernel", "Lb1ELb0ELi1", "ib_linear_dgrad"), ("slab_reduce_multi_kernel", "", "ib_slab_reduce_multi"),
