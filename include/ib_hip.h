@@ -427,6 +427,33 @@ int ib_ddim_cond_step(void* x, const void* eps, const void* x0, const void* z, c
  * (they hold the drawn noise z).  Same layout rules as ib_ddim_cond_step. */
 int ib_ddim_cond_init(void* x, const void* x0, const void* z, const uint8_t* mask, const float* obs_coef,
                       int64_t B, int64_t T, int64_t D, int64_t ld, int dtype, ib_stream_t stream);
+/* The stochastic update of the sampling loop (eta > 0), x <- coef[s][0] * x + coef[s][1] * eps + coef[s][2] * z' over the
+ * state x [B, T, ld] (row pitch ld >= D; eps the same layout), coef fp32 [num_steps, 3] = (c_x, c_eps, sigma).  z' ~ N(0, 1)
+ * is generated inside the update (no noise buffer, no extra launch): the normal of element (window b, frame f, column d)
+ * is Box-Muller over the Philox4x32-10 words of counter ((f * D + d) / 4, s, win_id[b], domain 2), key = seed -- word
+ * pair (f * D + d) % 4 / 2, cosine branch for even elements, as ib_diffusion_draw makes its normals.  It depends on (seed,
+ * win_id[b], s, f, d) only: not on b, B, ld or the vector width of the kernel.  win_id: device int64 [B], values < 2^32.
+ * Pad columns d >= D get no noise (0 stays 0).  s, t_out as in ib_ddim_step.  A step with sigma == 0 skips the generator
+ * and equals ib_ddim_step bit for bit. */
+int ib_ddim_step_noise(void* x, const void* eps, const float* coef, const int64_t* timesteps, int64_t num_steps,
+                       int32_t step, const int32_t* step_dev, int64_t* t_out, const int64_t* win_id, uint64_t seed,
+                       int64_t B, int64_t T, int64_t D, int64_t ld, int dtype, ib_stream_t stream);
+/* The masked stochastic update (operands as ib_ddim_cond_step; coef [num_steps, 3] as ib_ddim_step_noise, obs_noise_coef
+ * fp32 [num_steps, 2] = (r, q)):
+ *   mask == 0 (free):     x <- coef[s][0] * x + coef[s][1] * eps + coef[s][2] * z'
+ *   mask != 0 (observed): z <- r * z + q * z' IN PLACE (rounded to dtype), then x <- obs_coef[s+1][0] * x0 + obs_coef[s+1][1] * z
+ * -- the DDIM posterior given the observation; z of free elements is not changed.  A step with sigma == 0 leaves z alone
+ * and equals ib_ddim_cond_step bit for bit. */
+int ib_ddim_cond_step_noise(void* x, const void* eps, const void* x0, void* z, const uint8_t* mask, const float* coef,
+                            const float* obs_coef, const float* obs_noise_coef, const int64_t* timesteps,
+                            int64_t num_steps, int32_t step, const int32_t* step_dev, int64_t* t_out,
+                            const int64_t* win_id, uint64_t seed, int64_t B, int64_t T, int64_t D, int64_t ld, int dtype,
+                            ib_stream_t stream);
+/* Ensemble reduction: x [B, K, n] (dtype) -> mean [B, n] and unbiased standard deviation [B, n], fp32.  Members are added
+ * in the order k = 0 .. K-1 in fp32, mean = sum / K; std = sqrt(sum_k (x_k - mean)^2 / (K - 1)) in the same order; K = 1
+ * gives std = 0. */
+int ib_ensemble_stats(const void* x, float* mean, float* std_out, int64_t B, int64_t K, int64_t n, int dtype,
+                      ib_stream_t stream);
 /* The diffusion batch made on the device (csrc/noise.hip; replaces host torch.randint / torch.randn + H2D copies in the
  * training loop, cli/train.py -- the reference has no diffusion path).  For window b < B:
  *   x0_out[b, :per] = table[idx[b], :per]           (table NULL: x0 untouched; row_pitch % 8 == 0, row_pitch >= per)

@@ -44,6 +44,10 @@ class AnalyzeCommand(AbstractCommand):
                        help='[diffusion models] seed of the start noise (window i of a split draws from (seed, i)).')
         p.add_argument('--sample-batch', type=int, default=1,
                        help='[diffusion models] windows per sampler call; still one CSV row per window.')
+        p.add_argument('--sample-eta', type=float, default=0.0,
+                       help='[diffusion models] eta of the sampler: 0 = deterministic DDIM, 1 = DDPM ancestral sampling.')
+        p.add_argument('--num-samples', type=int, default=1,
+                       help='[diffusion models] posterior samples per window; the mean is evaluated, the spread reported.')
         p.add_argument('--use-ema', action='store_true', default=False,
                        help='Evaluate the EMA weights of the checkpoint (`train --ema-decay`) instead of its last weights.')
 
@@ -99,6 +103,9 @@ class AnalyzeCommand(AbstractCommand):
         from ..models.DiffusionLabelPredictor import DiffusionLabelPredictor
         if args.sample_batch < 1 or args.sample_steps < 1:
             raise SystemExit("--sample-batch and --sample-steps must be >= 1")
+        eta, num_samples = getattr(args, 'sample_eta', 0.0), getattr(args, 'num_samples', 1)
+        if not 0.0 <= eta <= 1.0 or num_samples < 1:
+            raise SystemExit("--sample-eta must be in [0, 1] and --num-samples >= 1")
         predictor = None
         for split, csv_name in (('dev', 'dev_analysis.csv'), ('train', 'train_analysis.csv')):
             logging.info(f'## Loading {split} dataset:')
@@ -109,7 +116,8 @@ class AnalyzeCommand(AbstractCommand):
                 self.load_latest_checkpoint(model, checkpoint_dir=checkpoint_dir, use_ema=getattr(args, 'use_ema', False))
                 model.eval()
                 predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
-                                                    output_data_format=args.output_data_format)
+                                                    output_data_format=args.output_data_format, eta=eta,
+                                                    num_samples=num_samples)
             evaluator = RegressionLossEvaluator(dataset=dataset, split=split, device=device)
             loader = DataLoader(dataset, batch_size=args.sample_batch, shuffle=False, num_workers=args.data_loading_workers)
             compute_report = bool(getattr(dataset, 'skeletons', None))
@@ -117,10 +125,13 @@ class AnalyzeCommand(AbstractCommand):
             if args.max_windows:
                 n = min(n, args.max_windows)
             i = 0
+            spread = EnsembleSpread() if num_samples > 1 else None
             with torch.no_grad(), open(os.path.join(checkpoint_dir, csv_name), 'a') as f:
                 writer = None
                 for inputs, labels, subj, trial in loader:
                     outputs = predictor(inputs, labels, draw=i)
+                    if spread is not None:
+                        spread.add(outputs, predictor.last_std, labels, min(len(subj), n - i))
                     for b in range(min(len(subj), n - i)):
                         one = lambda d: {k: v[b:b + 1] for k, v in d.items()}
                         evaluator(one(inputs), one(outputs), one(labels), subj[b:b + 1], trial[b:b + 1], args,
@@ -138,6 +149,8 @@ class AnalyzeCommand(AbstractCommand):
                         break
             print(f'Final {split} results:')
             evaluator.print_report(log_to_wandb=False)
+            if spread is not None:
+                print(spread.line(split, num_samples))
         return True
 
     def diffusion_view(self, args: argparse.Namespace, split: str, geometry) -> MotionWindowView:
@@ -157,6 +170,28 @@ class AnalyzeCommand(AbstractCommand):
                               batchnorm=False, dropout=False, dropout_prob=0.0, root_history_len=10,
                               output_data_format=args.output_data_format, device=device,
                               compute_dtype=dtype_of(args), feat_dim=view.feat, window=window).to(device)
+
+
+class EnsembleSpread:
+    """per label key, over the windows of a split: the mean of the ensemble's per-element standard deviation and the RMS
+    error of the ensemble mean against the labels (report bookkeeping on the host, in float64)"""
+
+    def __init__(self):
+        self.n = {}
+        self.std_sum = {}
+        self.sq_sum = {}
+
+    def add(self, mean, std, labels, windows: int):
+        for k in mean:
+            m, s, y = (t[:windows].detach().cpu().double() for t in (mean[k], std[k], labels[k]))
+            self.n[k] = self.n.get(k, 0) + m.numel()
+            self.std_sum[k] = self.std_sum.get(k, 0.0) + float(s.sum())
+            self.sq_sum[k] = self.sq_sum.get(k, 0.0) + float(((m - y) ** 2).sum())
+
+    def line(self, split: str, num_samples: int) -> str:
+        parts = [f'{k}: mean std {self.std_sum[k] / self.n[k]:.6g}, RMS err of mean {(self.sq_sum[k] / self.n[k]) ** 0.5:.6g}'
+                 for k in self.n]
+        return f'Ensemble spread ({split}, {num_samples} samples per window): ' + '; '.join(parts)
 
 
 def window_subject(dataset, subj) -> str:

@@ -1,8 +1,9 @@
 // [BUILD-DEFINED] diffusion wrapper kernels (no reference counterpart):
-// DDPM q_sample, DDIM (eta = 0) update, table gathers.  The schedule / coefficient / timestep-embedding
+// DDPM q_sample, DDIM update (eta = 0, and eta > 0 with the noise term drawn inside the update), table gathers.  The schedule / coefficient / timestep-embedding
 // tables are computed in float64 on the host and cast ONCE to fp32 (bit-exactness target of §8c); these
 // kernels only index them, so noise-schedule and timestep indexing stay bit-exact.
 #include "ib_common.h"
+#include "philox.h"
 
 namespace {
 
@@ -183,6 +184,262 @@ __global__ void ddim_cond_step_kernel(T* __restrict__ x, const T* __restrict__ e
   }
 }
 
+// ---- the stochastic update (eta > 0): x' = cx x + ce eps + sigma z', coef rows (cx, ce, sigma), with z' drawn INSIDE the
+// update kernel -- no noise buffer in HBM and no launch beside the update.  The normal of element (window, frame f,
+// column d) at sampling step s is Box-Muller over Philox4x32-10 (philox.h) at counter ((f * D + d) / 4, s, window id,
+// domain 2), key = seed: a function of (seed, window id, s, f, d) alone -- not of the batch position, the batch size, the
+// row pitch or the vector width.  Pad columns (d >= D) get no noise.  A step whose sigma is 0 (every row of an eta = 0
+// table, the last row of any table) skips the generator and is ib_ddim_step / ib_ddim_cond_step bit for bit.
+struct StepNoise {
+  uint32_t k0, k1;                  // the seed
+  const int64_t* win_id;            // [B] window ids (device: a replayed graph serves new batches)
+  int32_t D, ld, per;               // logical columns, row pitch, T * ld
+};
+
+// the normals of the 8 elements from offset m0 (a multiple of 8) of a window's [T, ld] state; bit k of the result: element
+// k is a logical column.  BLK (D % 4 == 0 and rows that start on a multiple of 8, or no pitch): the vector is two whole
+// Philox blocks, each made once or -- in the pad columns -- not at all.  Otherwise an element looks its block up, and
+// neighbours that share a block share the call.
+template <bool BLK>
+__device__ __forceinline__ unsigned step_noise8(const StepNoise& nz, uint32_t s, uint32_t wid, int m0, float (&z)[8]) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) z[k] = 0.f;
+  if constexpr (BLK) {
+    int l = m0;
+    unsigned ok = 0xffu;
+    if (nz.ld != nz.D) {
+      const int f = m0 / nz.ld, c = m0 - f * nz.ld;
+      l = f * nz.D + c;
+      ok = (c + 4 <= nz.D ? 0x0fu : 0u) | (c + 8 <= nz.D ? 0xf0u : 0u);
+    }
+    const uint32_t q = (uint32_t)l >> 2;
+    if (ok & 0x0fu) {
+      const U4 w = philox4x32_10(U4{q, s, wid, kDomainStep}, nz.k0, nz.k1);
+      box_muller(w.x, w.y, z[0], z[1]); box_muller(w.z, w.w, z[2], z[3]);
+    }
+    if (ok & 0xf0u) {
+      const U4 w = philox4x32_10(U4{q + 1u, s, wid, kDomainStep}, nz.k0, nz.k1);
+      box_muller(w.x, w.y, z[4], z[5]); box_muller(w.z, w.w, z[6], z[7]);
+    }
+    return ok;
+  } else {
+    unsigned ok = 0;
+    uint32_t cur = 0xffffffffu;                  // no block has this index: T * D / 4 < 2^29
+    U4 w{};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int mm = m0 + k, f = mm / nz.ld, c = mm - f * nz.ld;
+      if (c < nz.D) {
+        const int l = f * nz.D + c;
+        const uint32_t q = (uint32_t)l >> 2;
+        if (q != cur) { w = philox4x32_10(U4{q, s, wid, kDomainStep}, nz.k0, nz.k1); cur = q; }
+        float za, zb;
+        if ((l & 2) == 0) box_muller(w.x, w.y, za, zb); else box_muller(w.z, w.w, za, zb);
+        z[k] = (l & 1) ? zb : za;
+        ok |= 1u << k;
+      }
+    }
+    return ok;
+  }
+}
+
+// one element at offset m of a window's state: its normal, or 0 in a pad column (ok = false)
+__device__ __forceinline__ float step_noise1(const StepNoise& nz, uint32_t s, uint32_t wid, int m, bool& ok) {
+  const int f = m / nz.ld, c = m - f * nz.ld;
+  ok = c < nz.D;
+  if (!ok) return 0.f;
+  const int l = f * nz.D + c;
+  const U4 w = philox4x32_10(U4{(uint32_t)l >> 2, s, wid, kDomainStep}, nz.k0, nz.k1);
+  float za, zb;
+  if ((l & 2) == 0) box_muller(w.x, w.y, za, zb); else box_muller(w.z, w.w, za, zb);
+  return (l & 1) ? zb : za;
+}
+
+template <int V, bool BLK>
+__device__ __forceinline__ unsigned step_noise(const StepNoise& nz, uint32_t s, int64_t e0, float (&z)[V]) {
+  const int64_t b = e0 / nz.per;
+  const int m0 = (int)(e0 - b * nz.per);
+  const uint32_t wid = (uint32_t)nz.win_id[b];
+  if constexpr (V == 8) return step_noise8<BLK>(nz, s, wid, m0, z);
+  else {
+    bool ok;
+    z[0] = step_noise1(nz, s, wid, m0, ok);
+    return ok ? 1u : 0u;
+  }
+}
+
+// mix8: ib_ddim_step would take its 8-wide kernel on these buffers, so the element-wise kernel rounds as that one does
+// (as ddim_cond_step_kernel does).  The noise term is one more fused multiply-add on the ddim_mix value, in every kernel.
+template <typename T, int V, bool BLK>
+__global__ __launch_bounds__(256) void ddim_step_noise_kernel(T* __restrict__ x, const T* __restrict__ eps,
+                                                              const float* __restrict__ coef,
+                                                              const int64_t* __restrict__ timesteps, int64_t num_steps,
+                                                              int step, const int32_t* __restrict__ step_dev,
+                                                              int64_t* __restrict__ t_out, int64_t B, int64_t n, int mix8,
+                                                              StepNoise nz) {
+  int s = step_dev ? *step_dev : step;
+  s = s < 0 ? 0 : (s >= num_steps ? (int)num_steps - 1 : s);
+  const float cx = coef[3 * s], ce = coef[3 * s + 1], sg = coef[3 * s + 2];
+  const bool noisy = sg != 0.f;                                        // uniform over the launch
+  const int64_t nv = n / V;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e0 = i * V;
+    float a[V], e[V], o[V];
+    ldv<T, V>(x + e0, a);
+    ldv<T, V>(eps + e0, e);
+#pragma unroll
+    for (int k = 0; k < V; ++k)
+      o[k] = (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a[k], ce, e[k]) : ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
+    if (noisy) {
+      float z[V];
+      const unsigned ok = step_noise<V, BLK>(nz, (uint32_t)s, e0, z);
+#pragma unroll
+      for (int k = 0; k < V; ++k)
+        if ((ok >> k) & 1u) o[k] = __builtin_fmaf(sg, z[k], o[k]);
+    }
+    stv<T, V>(x + e0, o);
+  }
+  if (t_out && blockIdx.x == 0) {
+    const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
+    for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
+  }
+}
+
+// the loop of ddim_cond_step_kernel<T, V, false>, statement for statement: a step whose sigma is 0 runs it, so that the
+// observed elements' unpinned expression compiles as it does there.  (A copy, not a shared function: moving that kernel's
+// loop into a function reordered its instructions, and its results must not depend on this file's other kernels.)
+template <typename T, int V>
+__device__ __forceinline__ void ddim_cond_update(T* __restrict__ x, const T* __restrict__ eps, const T* __restrict__ x0,
+                                                 const T* __restrict__ z, const uint8_t* __restrict__ mask, float cx, float ce,
+                                                 float ox, float oz, int64_t per, int64_t n, int mix8) {
+  constexpr unsigned ALL = (1u << V) - 1;
+  const int64_t nv = n / V;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e0 = i * V, m0 = e0 % per;
+    unsigned bits;
+    if constexpr (V == 1) {
+      bits = mask[m0] != 0;
+    } else {
+      const uint64_t mv = *reinterpret_cast<const uint64_t*>(mask + m0);
+      bits = 0;
+#pragma unroll
+      for (int k = 0; k < V; ++k) bits |= (((mv >> (8 * k)) & 0xff) != 0 ? 1u : 0u) << k;
+    }
+    float o[V];
+    if (bits != ALL) {
+      float a[V];
+      ldv<T, V>(x + e0, a);
+      float e[V];
+      ldv<T, V>(eps + e0, e);
+#pragma unroll
+      for (int k = 0; k < V; ++k)
+        o[k] = (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a[k], ce, e[k]) : ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
+    }
+    if (bits != 0) {
+      float a[V], b[V];
+      ldv<T, V>(x0 + e0, a);
+      ldv<T, V>(z + e0, b);
+#pragma unroll
+      for (int k = 0; k < V; ++k)
+        if ((bits >> k) & 1u) o[k] = ox * a[k] + oz * b[k];
+    }
+    stv<T, V>(x + e0, o);
+  }
+}
+
+// masked stochastic update.  Free elements: ddim_mix + sigma z'.  Observed elements follow the DDIM posterior given the
+// observation: their stored noise z (the buffer, in place) becomes e' = r e + q z' (obs_noise row (r, q), r^2 + q^2 = 1),
+// rounded to the state's dtype, and the pinned value is obs_coef[s + 1] (x0, e') over that stored e', so state and buffer
+// stay on x = sqrt(ab) x0 + sqrt(1 - ab) e.  Free elements leave z as it is.
+template <typename T, int V, bool BLK>
+__global__ __launch_bounds__(256) void ddim_cond_step_noise_kernel(T* __restrict__ x, const T* __restrict__ eps,
+                                                                   const T* __restrict__ x0, T* z,
+                                                                   const uint8_t* __restrict__ mask,
+                                                                   const float* __restrict__ coef,
+                                                                   const float* __restrict__ obs_coef,
+                                                                   const float* __restrict__ obs_noise,
+                                                                   const int64_t* __restrict__ timesteps, int64_t num_steps,
+                                                                   int step, const int32_t* __restrict__ step_dev,
+                                                                   int64_t* __restrict__ t_out, int64_t B, int64_t per,
+                                                                   int64_t n, int mix8, StepNoise nz) {
+  int s = step_dev ? *step_dev : step;
+  s = s < 0 ? 0 : (s >= num_steps ? (int)num_steps - 1 : s);
+  const float cx = coef[3 * s], ce = coef[3 * s + 1], sg = coef[3 * s + 2];
+  const float ox = obs_coef[2 * (s + 1)], oz = obs_coef[2 * (s + 1) + 1];
+  if (sg == 0.f) {                                                     // uniform over the launch
+    ddim_cond_update<T, V>(x, eps, x0, z, mask, cx, ce, ox, oz, per, n, mix8);
+  } else {
+    const float r = obs_noise[2 * s], q = obs_noise[2 * s + 1];
+    constexpr unsigned ALL = (1u << V) - 1;
+    const int64_t nv = n / V;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
+      const int64_t e0 = i * V, m0 = e0 % per;
+      unsigned bits;
+      if constexpr (V == 1) {
+        bits = mask[m0] != 0;
+      } else {
+        const uint64_t mv = *reinterpret_cast<const uint64_t*>(mask + m0);
+        bits = 0;
+#pragma unroll
+        for (int k = 0; k < V; ++k) bits |= (((mv >> (8 * k)) & 0xff) != 0 ? 1u : 0u) << k;
+      }
+      float zn[V], o[V];
+      const unsigned ok = step_noise<V, BLK>(nz, (uint32_t)s, e0, zn);
+      if (bits != ALL) {
+        float a[V], e[V];
+        ldv<T, V>(x + e0, a);
+        ldv<T, V>(eps + e0, e);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+          o[k] = (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a[k], ce, e[k]) : ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
+          if ((ok >> k) & 1u) o[k] = __builtin_fmaf(sg, zn[k], o[k]);
+        }
+      }
+      if (bits != 0) {
+        float a[V], b[V];
+        ldv<T, V>(x0 + e0, a);
+        ldv<T, V>(z + e0, b);
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+          if ((bits >> k) & 1u) {
+            b[k] = ib_to_f32(ib_from_f32<T>(__builtin_fmaf(r, b[k], q * zn[k])));
+            o[k] = __builtin_fmaf(ox, a[k], oz * b[k]);
+          }
+        stv<T, V>(z + e0, b);                       // a free element of a mixed vector gets back the value it had
+      }
+      stv<T, V>(x + e0, o);
+    }
+  }
+  if (t_out && blockIdx.x == 0) {
+    const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
+    for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
+  }
+}
+
+// mean and unbiased standard deviation over the K members of an ensemble x [B, K, n], fp32 out.  One lane per (b, j); the
+// members are added in the order k = 0 .. K - 1, then the squared deviations from the rounded mean in the same order
+// (two passes: the second reads what the first left in cache).  K = 1: std = 0.
+template <typename T>
+__global__ __launch_bounds__(256) void ensemble_stats_kernel(const T* __restrict__ x, float* __restrict__ mean,
+                                                             float* __restrict__ sd, int64_t B, int64_t K, int64_t n) {
+#pragma clang fp contract(off)
+  const int64_t total = B * n;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / n, j = i - b * n;
+    const T* p = x + b * K * n + j;
+    float sum = 0.f;
+    for (int64_t k = 0; k < K; ++k) sum += ib_to_f32(p[k * n]);
+    const float m = sum / (float)K;
+    float ss = 0.f;
+    for (int64_t k = 0; k < K; ++k) {
+      const float d = ib_to_f32(p[k * n]) - m;
+      ss = __builtin_fmaf(d, d, ss);
+    }
+    mean[i] = m;
+    sd[i] = K > 1 ? __builtin_sqrtf(ss / (float)(K - 1)) : 0.f;
+  }
+}
+
 __global__ void counter_add_kernel(int32_t* c, int32_t d) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *c += d;
 }
@@ -292,6 +549,91 @@ extern "C" int ib_ddim_cond_init(void* x, const void* x0, const void* z, const u
     if (v8) IB_COND_INIT(bf16_t, 8); else IB_COND_INIT(bf16_t, 1);
   } else return IB_E_DTYPE;
 #undef IB_COND_INIT
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+// shared argument checks and launch geometry of the two stochastic updates
+namespace {
+struct NoiseLaunch { bool v8, blk, mix8; int64_t per, n; StepNoise nz; };
+int noise_launch(NoiseLaunch& L, const void* x, const void* eps, const void* x0, const void* z, const uint8_t* mask,
+                 const int64_t* win_id, uint64_t seed, int64_t B, int64_t T, int64_t D, int64_t ld) {
+  if (!win_id || B <= 0 || T <= 0 || D <= 0 || ld < D) return IB_E_ARG;
+  if (T * ld >= (int64_t)1 << 31) return IB_E_UNSUPPORTED;             // offsets inside a window are 32-bit
+  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
+  L.per = T * ld; L.n = B * L.per;
+  L.mix8 = (L.n % 8 == 0) && al16(x) && al16(eps);                     // ib_ddim_step's choice of its 8-wide kernel
+  L.v8 = L.mix8 && (L.per % 8 == 0) && al16(x0) && al16(z) && (reinterpret_cast<uintptr_t>(mask) % 8) == 0;
+  L.blk = (D % 4 == 0) && (ld == D || ld % 8 == 0);
+  L.nz = StepNoise{(uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), win_id, (int32_t)D, (int32_t)ld, (int32_t)L.per};
+  return IB_OK;
+}
+}  // namespace
+
+extern "C" int ib_ddim_step_noise(void* x, const void* eps, const float* coef, const int64_t* timesteps, int64_t num_steps,
+                                  int32_t step, const int32_t* step_dev, int64_t* t_out, const int64_t* win_id,
+                                  uint64_t seed, int64_t B, int64_t T, int64_t D, int64_t ld, int dtype, ib_stream_t stream) {
+  if (!x || !eps || !coef || num_steps <= 0) return IB_E_ARG;
+  if (t_out && !timesteps) return IB_E_ARG;
+  if (dtype != IB_F32 && dtype != IB_BF16) return IB_E_DTYPE;
+  NoiseLaunch L;
+  if (const int rc = noise_launch(L, x, eps, nullptr, nullptr, nullptr, win_id, seed, B, T, D, ld)) return rc;
+  const int grid = ib_grid_1d(L.n / (L.v8 ? 8 : 1), 256);
+  hipStream_t s = ib_s(stream);
+#define IB_STEP_NOISE(TY, V, BLK)                                                                                             \
+  hipLaunchKernelGGL((ddim_step_noise_kernel<TY, V, BLK>), dim3(grid), dim3(256), 0, s, (TY*)x, (const TY*)eps, coef, timesteps, \
+                     num_steps, step, step_dev, t_out, B, L.n, (int)L.mix8, L.nz)
+#define IB_STEP_NOISE_T(TY)                                                                                                   \
+  do {                                                                                                                        \
+    if (!L.v8) IB_STEP_NOISE(TY, 1, false);                                                                                   \
+    else if (L.blk) IB_STEP_NOISE(TY, 8, true);                                                                               \
+    else IB_STEP_NOISE(TY, 8, false);                                                                                         \
+  } while (0)
+  if (dtype == IB_F32) IB_STEP_NOISE_T(float); else IB_STEP_NOISE_T(bf16_t);
+#undef IB_STEP_NOISE_T
+#undef IB_STEP_NOISE
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+extern "C" int ib_ddim_cond_step_noise(void* x, const void* eps, const void* x0, void* z, const uint8_t* mask,
+                                       const float* coef, const float* obs_coef, const float* obs_noise_coef,
+                                       const int64_t* timesteps, int64_t num_steps, int32_t step, const int32_t* step_dev,
+                                       int64_t* t_out, const int64_t* win_id, uint64_t seed, int64_t B, int64_t T, int64_t D,
+                                       int64_t ld, int dtype, ib_stream_t stream) {
+  if (!x || !eps || !x0 || !z || !mask || !coef || !obs_coef || !obs_noise_coef || num_steps <= 0) return IB_E_ARG;
+  if (t_out && !timesteps) return IB_E_ARG;
+  if (dtype != IB_F32 && dtype != IB_BF16) return IB_E_DTYPE;
+  NoiseLaunch L;
+  if (const int rc = noise_launch(L, x, eps, x0, z, mask, win_id, seed, B, T, D, ld)) return rc;
+  const int grid = ib_grid_1d(L.n / (L.v8 ? 8 : 1), 256);
+  hipStream_t s = ib_s(stream);
+#define IB_COND_NOISE(TY, V, BLK)                                                                                             \
+  hipLaunchKernelGGL((ddim_cond_step_noise_kernel<TY, V, BLK>), dim3(grid), dim3(256), 0, s, (TY*)x, (const TY*)eps,         \
+                     (const TY*)x0, (TY*)z, mask, coef, obs_coef, obs_noise_coef, timesteps, num_steps, step, step_dev, t_out, \
+                     B, L.per, L.n, (int)L.mix8, L.nz)
+#define IB_COND_NOISE_T(TY)                                                                                                   \
+  do {                                                                                                                        \
+    if (!L.v8) IB_COND_NOISE(TY, 1, false);                                                                                   \
+    else if (L.blk) IB_COND_NOISE(TY, 8, true);                                                                               \
+    else IB_COND_NOISE(TY, 8, false);                                                                                         \
+  } while (0)
+  if (dtype == IB_F32) IB_COND_NOISE_T(float); else IB_COND_NOISE_T(bf16_t);
+#undef IB_COND_NOISE_T
+#undef IB_COND_NOISE
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+extern "C" int ib_ensemble_stats(const void* x, float* mean, float* std_out, int64_t B, int64_t K, int64_t n, int dtype,
+                                 ib_stream_t stream) {
+  if (!x || !mean || !std_out || B <= 0 || K <= 0 || n <= 0) return IB_E_ARG;
+  const int grid = ib_grid_1d(B * n, 256);
+  if (dtype == IB_F32)
+    hipLaunchKernelGGL((ensemble_stats_kernel<float>), dim3(grid), dim3(256), 0, ib_s(stream), (const float*)x, mean, std_out, B, K, n);
+  else if (dtype == IB_BF16)
+    hipLaunchKernelGGL((ensemble_stats_kernel<bf16_t>), dim3(grid), dim3(256), 0, ib_s(stream), (const bf16_t*)x, mean, std_out, B, K, n);
+  else return IB_E_DTYPE;
   IB_CHECK_LAUNCH();
   return IB_OK;
 }

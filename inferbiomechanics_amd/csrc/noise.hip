@@ -12,34 +12,9 @@
 // HBM-bound streaming kernel: per element 2 B (bf16) read of x0 + 2 x 2 B written; 8 elements (16 B of bf16) per lane
 // per access, consecutive lanes on consecutive 16-byte pieces.
 #include "ib_common.h"
+#include "philox.h"
 
 namespace {
-
-constexpr uint32_t kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u, kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
-constexpr uint32_t kDomainEps = 0u, kDomainT = 1u;
-
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(kM0, c.x), lo0 = kM0 * c.x;
-    const uint32_t hi1 = __umulhi(kM1, c.z), lo1 = kM1 * c.z;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += kW0; k1 += kW1;
-  }
-  return c;
-}
-
-// (w, w') -> two N(0,1): u1 = (w + 1) / 2^32 in (0, 1], u2 = w' / 2^32 in [0, 1)
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-  // -2 ln u1 = -2 ln2 * log2(u1); u1 from the top 24 bits + 1 so the float conversion is exact and never 0
-  const float u1 = (float)((a >> 8) + 1u) * 0x1.0p-24f;
-  const float u2 = (float)(b >> 8) * 0x1.0p-24f;                  // revolutions: v_sin / v_cos take x / (2 pi)
-  const float r = __builtin_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));
-  z0 = r * __builtin_amdgcn_cosf(u2);
-  z1 = r * __builtin_amdgcn_sinf(u2);
-}
 
 struct Draw {
   const void* table; int64_t table_rows, row_pitch;     // x0 table [rows, row_pitch] (NULL: x0 is not touched)

@@ -1,10 +1,12 @@
-"""[BUILD-DEFINED] DDIM (eta = 0) sampling loop: N denoiser evaluations + updates.
+"""[BUILD-DEFINED] DDIM / DDPM sampling loop: N denoiser evaluations + updates; eta = 0 is the
+deterministic DDIM loop, eta in (0, 1] adds the noise term sigma z' (eta = 1 with as many sampling steps as training steps:
+DDPM ancestral sampling), drawn inside the update kernel from a counter-based generator keyed by (seed, window id, step).
 
 One denoise step = {time-embedding gather, denoiser forward plan, DDIM update, counter++}.  The step index
 lives in DEVICE memory (an int32 counter the update kernel reads), and the update kernel also writes the next
 step's timestep vector, so ONE captured hipGraph of a single step can be replayed for every step of the loop
 with no host involvement between steps (BASELINE config 5)."""
-from typing import Optional
+from typing import Optional, Sequence, Union
 
 import torch
 
@@ -13,8 +15,15 @@ from ..plans import ParamSource
 
 
 class DDIMSampler:
-    def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True):
+    def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True, eta: float = 0.0,
+                 seed: Optional[int] = None):
+        """eta in [0, 1]; seed (default: torch's initial seed) keys the step noise of an eta > 0 loop"""
+        if not 0.0 <= float(eta) <= 1.0:
+            raise ValueError(f"eta must be in [0, 1], got {eta}")
         self.model, self.S = model, num_sample_steps
+        self.eta = float(eta)
+        self.seed = (int(torch.initial_seed()) if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
+        self._win = None
         self.use_graph = use_graph and not hip._dry_run
         self._graph: Optional[hip.Graph] = None
         self._sig = None
@@ -36,7 +45,27 @@ class DDIMSampler:
         hip.counter_add(ctr, 1)
 
     def _update(self, x, eps, ctr, t_vec, tabs):
-        hip.ddim_step(x, eps, tabs.ddim_coef, tabs.ddim_t, step_dev=ctr, t_out=t_vec)
+        if self.eta == 0.0:
+            hip.ddim_step(x, eps, tabs.ddim_coef, tabs.ddim_t, step_dev=ctr, t_out=t_vec)
+        else:
+            hip.ddim_step_noise(x, eps, tabs.ddim_coef_eta, tabs.ddim_t, self._bufs["win"], self.seed, step_dev=ctr,
+                                t_out=t_vec, D=self._D)
+
+    def _noise_sig(self, tabs) -> tuple:
+        """eta and, for a stochastic loop, what its update launch bakes in: the seed and the eta tables' pointers"""
+        if self.eta == 0.0:
+            return (0.0,)
+        return (self.eta, self.seed, tabs.ddim_coef_eta.data_ptr(), tabs.obs_noise_coef.data_ptr())
+
+    def _set_window_ids(self, B: int):
+        """copies the call's window ids (default 0 .. B-1) into the device buffer the captured update reads"""
+        ids = self._win
+        ids = torch.arange(B, dtype=torch.int64) if ids is None else torch.as_tensor(ids, dtype=torch.int64).reshape(-1).cpu()
+        if ids.numel() != B:
+            raise ValueError(f"window_ids must hold one id per window ({B}), got {ids.numel()}")
+        if B and (int(ids.min()) < 0 or int(ids.max()) >= 1 << 32):
+            raise ValueError("window_ids must be in 0 .. 2^32 - 1 (one word of the generator's counter)")
+        self._bufs["win"].copy_(ids)
 
     def _extra_buffers(self, B, T, D, Dp, dev, dtype):
         """more device buffers that live as long as the captured step (a subclass's)"""
@@ -49,8 +78,18 @@ class DDIMSampler:
         """runs once x holds the start draw, before the first step (a subclass's start state)"""
 
     @torch.no_grad()
-    def sample(self, x_T: torch.Tensor, steps: Optional[int] = None) -> torch.Tensor:
-        """x_T [B,T,D] ~ N(0,1) -> x_0.  `steps` (<= num_sample_steps) truncates the loop (benchmarks)."""
+    def sample(self, x_T: torch.Tensor, steps: Optional[int] = None,
+               window_ids: Union[None, Sequence[int], torch.Tensor] = None) -> torch.Tensor:
+        """x_T [B,T,D] ~ N(0,1) -> x_0.  `steps` (<= num_sample_steps) truncates the loop (benchmarks).  window_ids (default
+        0 .. B-1): with eta > 0 the step noise of window b is keyed by (seed, window_ids[b], step), whatever its place in
+        the batch; unused at eta = 0."""
+        self._win = window_ids
+        try:
+            return self._sample_on_stream(x_T, steps)
+        finally:
+            self._win = None
+
+    def _sample_on_stream(self, x_T: torch.Tensor, steps: Optional[int]) -> torch.Tensor:
         if not x_T.is_cuda and not hip._dry_run:
             x_T = x_T.to(next(self.model.parameters()).device)
         if hip._dry_run:
@@ -67,10 +106,10 @@ class DDIMSampler:
 
     @torch.no_grad()
     def sample_noise(self, batch: int, window: int, feat: int, seed: Optional[int] = None, draw: int = 0,
-                     steps: Optional[int] = None) -> torch.Tensor:
+                     steps: Optional[int] = None, window_ids=None) -> torch.Tensor:
         """x_T ~ N(0,1) drawn ON the device (csrc/noise.hip: Philox keyed by (seed, draw); `seed` defaults to torch's) and
         denoised to x_0 -- no host random numbers, no H2D copy of the start state."""
-        return self.sample(self.draw_start(batch, window, feat, seed, draw), steps)
+        return self.sample(self.draw_start(batch, window, feat, seed, draw), steps, window_ids)
 
     def draw_start(self, batch: int, window: int, feat: int, seed: Optional[int] = None, draw: int = 0) -> torch.Tensor:
         """the start state x_T ~ N(0,1) of sample_noise, [batch, window, feat] in the compute dtype on the model's device"""
@@ -87,8 +126,8 @@ class DDIMSampler:
         m.sync_shadow()
         dev = m._flat.device
         tabs = m.tables(dev)
-        if tabs.num_sample_steps != self.S:
-            tabs.set_sampler(self.S)
+        if tabs.num_sample_steps != self.S or (self.eta > 0.0 and getattr(tabs, "eta", 0.0) != self.eta):
+            tabs.set_sampler(self.S, self.eta)
         # the captured step bakes in raw pointers: the model's flat parameter buffer and bf16 shadow (a HipTrainer built
         # after a first sample() re-packs them), the schedule tables (set_sampler() of another sampler re-creates the DDIM
         # tables) -- all of them are part of the signature, so a change re-captures instead of replaying stale pointers
@@ -98,7 +137,7 @@ class DDIMSampler:
         plan = m._get_plan(dev)
         B, T, D = x_T.shape
         Dp = plan.infer_pitch(D) if (hasattr(plan, "infer_pitch") and m.compute_dtype == torch.bfloat16) else D
-        sig = sig + (Dp,) + self._extra_sig(tabs)
+        sig = sig + (Dp,) + self._extra_sig(tabs) + self._noise_sig(tabs)
         if sig != self._sig:
             self._sig, self._graph = sig, None
             self._bufs = {"x": torch.zeros((B, T, Dp), dtype=m.compute_dtype, device=dev),
@@ -107,7 +146,11 @@ class DDIMSampler:
             if Dp != D:
                 self._bufs["eps"] = torch.zeros((B, T, Dp), dtype=m.compute_dtype, device=dev)
             self._bufs.update(self._extra_buffers(B, T, D, Dp, dev, m.compute_dtype))
+            if self.eta > 0.0:
+                self._bufs["win"] = torch.zeros(B, dtype=torch.int64, device=dev)
         self._D = D
+        if self.eta > 0.0:
+            self._set_window_ids(B)
         x, t_vec, ctr = self._bufs["x"], self._bufs["t"], self._bufs["ctr"]
         x[:, :, :D].copy_(x_T.to(device=dev, dtype=m.compute_dtype))
         self._begin(x, tabs)
@@ -144,23 +187,27 @@ class DDIMSampler:
 
 
 class ConditionalDDIMSampler(DDIMSampler):
-    """DDIM (eta = 0) inpainting with an unconditional denoiser (replacement method): the elements a mask marks as observed
+    """DDIM inpainting with an unconditional denoiser (replacement method): the elements a mask marks as observed
     are pinned, at every step, to the observation forward-noised to that step's noise level with the fixed start draw z,
     sqrt(ab) x0 + sqrt(1 - ab) z -- with eta = 0 that is exactly the DDIM trajectory of the observation, so the loop stays
     deterministic and its last step (to alpha_bar = 1) returns the observation itself.  The free elements follow the DDIM
-    update.  Same captured single-step graph as DDIMSampler; only the update launch differs (ib_ddim_cond_step, the same
+    update.  With eta > 0 an observed element follows the DDIM posterior given the observation: its noise, kept in the z
+    buffer, becomes r z + q z' at every step (schedule.observation_noise_coefficients), and the last step still lands on
+    the observation.  Same captured single-step graph as DDIMSampler; only the update launch differs (ib_ddim_cond_step, the same
     launch count per step).  The observation, the draw and the mask live in sampler-owned device buffers that the capture
     reads, so a new batch of the same shape is copied in and the captured step replayed."""
 
-    def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True):
-        super().__init__(model, num_sample_steps, use_graph)
+    def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True, eta: float = 0.0,
+                 seed: Optional[int] = None):
+        super().__init__(model, num_sample_steps, use_graph, eta, seed)
         self._cond = None
 
     @torch.no_grad()
     def sample(self, x_T: torch.Tensor, observed: torch.Tensor, mask: torch.Tensor,
-               steps: Optional[int] = None) -> torch.Tensor:
+               steps: Optional[int] = None, window_ids=None) -> torch.Tensor:
         """x_T [B,T,D] ~ N(0,1) (the draw z), observed [B,T,D], mask [T,D] bool (True = observed) -> x_0, which equals the
-        observation (in the compute dtype) wherever mask is True.  `steps` truncates the loop as in DDIMSampler."""
+        observation (in the compute dtype) wherever mask is True.  `steps` truncates the loop and window_ids key the step
+        noise as in DDIMSampler."""
         B, T, D = x_T.shape
         if tuple(observed.shape) != (B, T, D):
             raise ValueError(f"observed must be {(B, T, D)} like x_T, got {tuple(observed.shape)}")
@@ -168,15 +215,16 @@ class ConditionalDDIMSampler(DDIMSampler):
             raise ValueError(f"mask must be a [T, D] = {(T, D)} bool tensor, got {tuple(mask.shape)} {mask.dtype}")
         self._cond = (observed, mask)
         try:
-            return super().sample(x_T, steps)
+            return super().sample(x_T, steps, window_ids)
         finally:
             self._cond = None
 
     @torch.no_grad()
     def sample_noise(self, batch: int, window: int, feat: int, observed: torch.Tensor, mask: torch.Tensor,
-                     seed: Optional[int] = None, draw: int = 0, steps: Optional[int] = None) -> torch.Tensor:
+                     seed: Optional[int] = None, draw: int = 0, steps: Optional[int] = None,
+                     window_ids=None) -> torch.Tensor:
         """as DDIMSampler.sample_noise: z = x_T drawn on the device from (seed, draw)"""
-        return self.sample(self.draw_start(batch, window, feat, seed, draw), observed, mask, steps)
+        return self.sample(self.draw_start(batch, window, feat, seed, draw), observed, mask, steps, window_ids)
 
     def _extra_sig(self, tabs) -> tuple:
         return (tabs.obs_coef.data_ptr(),)
@@ -200,5 +248,10 @@ class ConditionalDDIMSampler(DDIMSampler):
 
     def _update(self, x, eps, ctr, t_vec, tabs):
         b = self._bufs
-        hip.ddim_cond_step(x, eps, b["x0"], b["z"], b["mask"], tabs.ddim_coef, tabs.obs_coef, tabs.ddim_t, step_dev=ctr,
-                           t_out=t_vec, D=self._D)
+        if self.eta == 0.0:
+            hip.ddim_cond_step(x, eps, b["x0"], b["z"], b["mask"], tabs.ddim_coef, tabs.obs_coef, tabs.ddim_t, step_dev=ctr,
+                               t_out=t_vec, D=self._D)
+        else:
+            hip.ddim_cond_step_noise(x, eps, b["x0"], b["z"], b["mask"], tabs.ddim_coef_eta, tabs.obs_coef,
+                                     tabs.obs_noise_coef, tabs.ddim_t, b["win"], self.seed, step_dev=ctr, t_out=t_vec,
+                                     D=self._D)

@@ -1,7 +1,7 @@
 """[BUILD-DEFINED] DDPM / DDIM schedule tables (no reference counterpart).
 
 Everything is computed in float64 on the host exactly as the oracle does (literature definitions:
-linear beta schedule 1e-4..0.02 over 1000 steps, alpha_bar = cumprod(1-beta); DDIM eta = 0; sinusoidal
+linear beta schedule 1e-4..0.02 over 1000 steps, alpha_bar = cumprod(1-beta); DDIM with eta in [0, 1]; sinusoidal
 embedding [sin(t w_i), cos(t w_i)], w_i = exp(-ln(1e4) i / half)), cast ONCE to fp32 and uploaded; the
 kernels only index the tables, so schedule values and timestep indices are bit-exact.
 """
@@ -51,6 +51,51 @@ def observation_coefficients(num_train_steps: int = 1000, num_sample_steps: int 
     return torch.stack([torch.stack([torch.sqrt(a), torch.sqrt(1 - a)]) for a in levels])
 
 
+def _levels(num_train_steps: int, num_sample_steps: int):
+    """(alpha_bar[t_s], alpha_bar of the next level) per sampling step, float64; the last step goes to alpha_bar = 1"""
+    ab = alphas_cumprod(num_train_steps)
+    ts = ddim_timesteps(num_train_steps, num_sample_steps).tolist()
+    one = torch.tensor(1.0, dtype=torch.float64)
+    return [(ab[t], ab[ts[i + 1]] if i + 1 < len(ts) else one) for i, t in enumerate(ts)]
+
+
+def ddim_sigmas(num_train_steps: int = 1000, num_sample_steps: int = 100, eta: float = 0.0) -> torch.Tensor:
+    """[S] float64: sigma_s = eta sqrt((1 - p) / (1 - a)) sqrt(1 - a / p) (Song et al., DDIM eq. 16); eta = 1 with S = N is
+    the DDPM posterior's standard deviation.  Exactly 0 at eta = 0 and in the last row (p = 1)."""
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"eta must be in [0, 1], got {eta}")
+    return torch.stack([float(eta) * torch.sqrt((1 - p) / (1 - a)) * torch.sqrt(1 - a / p)
+                        for a, p in _levels(num_train_steps, num_sample_steps)])
+
+
+def ddim_coefficients_eta(num_train_steps: int = 1000, num_sample_steps: int = 100, eta: float = 0.0) -> torch.Tensor:
+    """[S, 3] float64 (c_x, c_eps, sigma): x_prev = c_x x_t + c_eps eps + sigma z', z' ~ N(0, I).  c_x does not depend on
+    eta; c_eps = sqrt(1 - p - sigma^2) - sqrt(p) sqrt(1 - a) / sqrt(a).  At eta = 0 the first two columns are
+    ddim_coefficients bit for bit."""
+    sig = ddim_sigmas(num_train_steps, num_sample_steps, eta)
+    rows = []
+    for (a, p), sg in zip(_levels(num_train_steps, num_sample_steps), sig):
+        cx = torch.sqrt(p) / torch.sqrt(a)
+        ce = torch.sqrt(1 - p - sg * sg) - torch.sqrt(p) * torch.sqrt(1 - a) / torch.sqrt(a)
+        rows.append(torch.stack([cx, ce, sg]))
+    return torch.stack(rows)
+
+
+def observation_noise_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100, eta: float = 0.0) -> torch.Tensor:
+    """[S, 2] float64 (r, q): an observed element of the masked loop follows the DDIM posterior given the observation,
+    q_sigma(x_prev | x_t, x0).  With e the element's current noise (x_t = sqrt(a) x0 + sqrt(1 - a) e), the noise of the next
+    level is e' = r e + q z' with r = sqrt(1 - p - sigma^2) / sqrt(1 - p), q = sigma / sqrt(1 - p), r^2 + q^2 = 1.  Exactly
+    (1, 0) at eta = 0 (e stays the start draw); (0, 0) in the last row, where the level is the observation itself."""
+    sig = ddim_sigmas(num_train_steps, num_sample_steps, eta)
+    rows = []
+    for (a, p), sg in zip(_levels(num_train_steps, num_sample_steps), sig):
+        if float(p) == 1.0:
+            rows.append(torch.zeros(2, dtype=torch.float64))
+        else:
+            rows.append(torch.stack([torch.sqrt(1 - p - sg * sg) / torch.sqrt(1 - p), sg / torch.sqrt(1 - p)]))
+    return torch.stack(rows)
+
+
 def timestep_embedding_table(num_steps: int, dim: int, max_period: float = 10000.0) -> torch.Tensor:
     """[num_steps, dim] float64: row t = [sin(t w), cos(t w)]."""
     half = dim // 2
@@ -72,12 +117,20 @@ class DiffusionTables:
         self.set_sampler(num_sample_steps)
         self.device = device
 
-    def set_sampler(self, num_sample_steps: int):
-        self.num_sample_steps = num_sample_steps
+    def set_sampler(self, num_sample_steps: int, eta: float = 0.0):
+        """the sampler's tables for S steps; eta > 0 adds the stochastic loop's (c_x, c_eps, sigma) and (r, q) tables"""
+        if not 0.0 <= float(eta) <= 1.0:
+            raise ValueError(f"eta must be in [0, 1], got {eta}")
+        self.num_sample_steps, self.eta = num_sample_steps, float(eta)
         dev = self.sqrt_ab.device
         self.ddim_t = ddim_timesteps(self.num_train_steps, num_sample_steps).to(dev)
         self.ddim_coef = ddim_coefficients(self.num_train_steps, num_sample_steps).to(torch.float32).to(dev).contiguous()
         self.obs_coef = observation_coefficients(self.num_train_steps, num_sample_steps).to(torch.float32).to(dev).contiguous()
+        self.ddim_coef_eta = self.obs_noise_coef = None
+        if self.eta > 0.0:
+            N = self.num_train_steps
+            self.ddim_coef_eta = ddim_coefficients_eta(N, num_sample_steps, eta).to(torch.float32).to(dev).contiguous()
+            self.obs_noise_coef = observation_noise_coefficients(N, num_sample_steps, eta).to(torch.float32).to(dev).contiguous()
 
     def host_tables(self) -> Dict[str, torch.Tensor]:
         return {"sqrt_ab": self.sqrt_ab.cpu(), "sqrt_1mab": self.sqrt_1mab.cpu(), "temb": self.temb.cpu(),

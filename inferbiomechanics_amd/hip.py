@@ -164,6 +164,11 @@ _SIGS = {
     "ib_ddim_cond_step": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i64, _i64,
                                      _c.c_int, _vp]),
     "ib_ddim_cond_init": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
+    "ib_ddim_step_noise": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _c.c_uint64, _i64, _i64, _i64, _i64,
+                                      _c.c_int, _vp]),
+    "ib_ddim_cond_step_noise": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp,
+                                           _c.c_uint64, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
+    "ib_ensemble_stats": (_c.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _c.c_int, _vp]),
     "ib_counter_add": (_c.c_int, [_vp, _i32, _vp]),
     "ib_batchnorm_fwd": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _f32, _f32, _c.c_int,
                                     _c.c_int, _vp]),
@@ -2222,6 +2227,92 @@ def ddim_cond_init(x, x0, z, mask, obs_coef, D=None):
     _check(lib().ib_ddim_cond_init(_ptr(x), _ptr(x0), _ptr(z), _ptr(mask), _ptr(obs_coef), B, T, D, ld,
                                    dtype_code(x.dtype), stream_ptr()), "ib_ddim_cond_init")
     return x
+
+
+def _noise_operands(what, x, coef, timesteps, win_id, t_out, step_dev, D):
+    """shared checks of the stochastic updates -> (B, T, D, ld, S)"""
+    _req(x, "x", x.dtype, 3)
+    if not x.is_contiguous():
+        raise HipError(f"{what}: x must be a contiguous [B, T, ld] state")
+    B, T, ld = x.shape
+    D = ld if D is None else int(D)
+    if D <= 0 or D > ld:
+        raise HipError(f"{what}: D = {D} must be in 1 .. ld = {ld}")
+    _req(coef, "coef", torch.float32, 2)
+    _req(timesteps, "timesteps", torch.int64, 1)
+    S = coef.shape[0]
+    if coef.shape[1] != 3 or timesteps.numel() != S or not coef.is_contiguous():
+        raise HipError(f"{what}: coef must be [S, 3] fp32 (c_x, c_eps, sigma), timesteps [S] int64")
+    _req(win_id, "win_id", torch.int64, 1)
+    if win_id.numel() != B or not win_id.is_contiguous():
+        raise HipError(f"{what}: win_id must be contiguous int64 [B] = [{B}]")
+    if t_out is not None:
+        _req(t_out, "t_out", torch.int64, 1)
+        if t_out.numel() != B:
+            raise HipError("t_out must be int64 [B]")
+    if step_dev is not None:
+        _req(step_dev, "step_dev", torch.int32)
+    return B, T, D, ld, S
+
+
+def ddim_step_noise(x, eps, coef, timesteps, win_id, seed, step=0, step_dev=None, t_out=None, D=None):
+    """stochastic DDIM / DDPM update in place over the state x [B, T, ld] (csrc/diffusion.hip): coef [S, 3] = (c_x, c_eps,
+    sigma); the noise of window b is keyed by (seed, win_id[b], step, frame, column) and generated inside the kernel.
+    D (default ld): the feature columns in front of the row pitch; pad columns get no noise."""
+    B, T, D, ld, S = _noise_operands("ddim_step_noise", x, coef, timesteps, win_id, t_out, step_dev, D)
+    _req(eps, "eps", x.dtype)
+    if eps.shape != x.shape or not eps.is_contiguous():
+        raise HipError("ddim_step_noise: eps must be contiguous with the shape of x")
+    _check(lib().ib_ddim_step_noise(_ptr(x), _ptr(eps), _ptr(coef), _ptr(timesteps), S, int(step), _ptr(step_dev),
+                                    _ptr(t_out), _ptr(win_id), int(seed) & 0xFFFFFFFFFFFFFFFF, B, T, D, ld,
+                                    dtype_code(x.dtype), stream_ptr()), "ib_ddim_step_noise")
+    return x
+
+
+def ddim_cond_step_noise(x, eps, x0, z, mask, coef, obs_coef, obs_noise_coef, timesteps, win_id, seed, step=0,
+                         step_dev=None, t_out=None, D=None):
+    """masked stochastic update in place: free elements as ddim_step_noise; observed ones update their stored noise z in
+    place (obs_noise_coef [S, 2] = (r, q): z <- r z + q z') and are pinned to obs_coef[s + 1] (x0, z)."""
+    B, T, D, ld = _cond_operands("ddim_cond_step_noise", x, x0, z, mask, obs_coef, D)
+    _noise_operands("ddim_cond_step_noise", x, coef, timesteps, win_id, t_out, step_dev, D)
+    S = coef.shape[0]
+    _req(eps, "eps", x.dtype)
+    if eps.shape != x.shape or not eps.is_contiguous():
+        raise HipError("ddim_cond_step_noise: eps must be contiguous with the shape of x")
+    if obs_coef.shape[0] != S + 1:
+        raise HipError(f"ddim_cond_step_noise: obs_coef must have S + 1 = {S + 1} rows, got {obs_coef.shape[0]}")
+    _req(obs_noise_coef, "obs_noise_coef", torch.float32, 2)
+    if tuple(obs_noise_coef.shape) != (S, 2) or not obs_noise_coef.is_contiguous():
+        raise HipError(f"ddim_cond_step_noise: obs_noise_coef must be contiguous [S, 2] = [{S}, 2] fp32")
+    _check(lib().ib_ddim_cond_step_noise(_ptr(x), _ptr(eps), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef),
+                                         _ptr(obs_noise_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out),
+                                         _ptr(win_id), int(seed) & 0xFFFFFFFFFFFFFFFF, B, T, D, ld, dtype_code(x.dtype),
+                                         stream_ptr()), "ib_ddim_cond_step_noise")
+    return x
+
+
+def ensemble_stats(x, mean=None, std=None):
+    """x [B, K, ...] (fp32 / bf16, contiguous) -> (mean, std) fp32 [B, ...]: the members' mean and unbiased standard
+    deviation, summed in member order (csrc/diffusion.hip); K = 1 gives std = 0."""
+    _req(x, "x")
+    if x.dim() < 3 or not x.is_contiguous():
+        raise HipError("ensemble_stats: x must be contiguous [B, K, ...]")
+    B, K = x.shape[0], x.shape[1]
+    n = x.numel() // (B * K) if B * K else 0
+    if B <= 0 or K <= 0 or n <= 0:
+        raise HipError(f"ensemble_stats: empty ensemble {tuple(x.shape)}")
+    shape = (B,) + tuple(x.shape[2:])
+    outs = []
+    for name, t in (("mean", mean), ("std", std)):
+        if t is None:
+            t = torch.empty(shape, dtype=torch.float32, device=x.device)
+        _req(t, name, torch.float32)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise HipError(f"ensemble_stats: {name} must be contiguous fp32 {shape}")
+        outs.append(t)
+    _check(lib().ib_ensemble_stats(_ptr(x), _ptr(outs[0]), _ptr(outs[1]), B, K, n, dtype_code(x.dtype), stream_ptr()),
+           "ib_ensemble_stats")
+    return outs[0], outs[1]
 
 
 def batchnorm_fwd(x, gamma, beta, running_mean, running_var, num_batches_tracked, y, save_mean, save_rstd, training: bool,

@@ -4,11 +4,13 @@ A window is the denoiser's ``[F, D]`` matrix (``MotionWindowView.matrix``): the 
 30 label channels cop | force | torque | wrench (``LOSS_KEY_ORDER``, widths 6 / 6 / 6 / 12).  The input columns of
 every frame are observed, the label columns are free, and the masked DDIM loop (``ConditionalDDIMSampler``) fills them
 in.  The result is the reference regression models' outputs dict, so the same ``RegressionLossEvaluator``, CSV rows and
-report apply."""
+report apply.  With ``eta > 0`` the loop is stochastic and with ``num_samples = K > 1`` every window is sampled K times:
+the outputs are then the ensemble mean and ``last_std`` the per-element spread (``ib_ensemble_stats``)."""
 from typing import Dict, Optional
 
 import torch
 
+from .. import hip
 from ..data.AddBiomechanicsDataset import INPUT_KEY_ORDER, LOSS_KEY_ORDER, LOSS_KEY_WIDTHS, MotionWindowView
 from ..diffusion.sampler import ConditionalDDIMSampler
 
@@ -27,14 +29,29 @@ def label_mask(frames: int, feat: int) -> torch.Tensor:
 class DiffusionLabelPredictor:
     """``predictor(inputs) -> outputs``: inputs is the reference's batched input dict ``{key: [B, F, c]}``; outputs holds
     the four ``LOSS_KEY_ORDER`` keys as fp32 ``[B, F, C]``.  Window b of a call draws its start noise z from
-    (seed, draw + b), so a window's result does not depend on how windows are batched into calls."""
+    (seed, draw + b), so a window's result does not depend on how windows are batched into calls.  With num_samples = K,
+    window i = draw + b is replicated K times inside the sampler batch (B K rows); member k has window id i K + k for both its
+    start draw and its step noise (eta > 0), the outputs are the members' mean and ``last_std`` their unbiased standard
+    deviation, in the same four-key layout (None on the default eta = 0, K = 1 path, which is the single deterministic
+    trajectory)."""
 
     def __init__(self, model, num_sample_steps: int = 100, seed: int = 0, output_data_format: str = 'all_frames',
-                 use_graph: bool = True):
+                 use_graph: bool = True, eta: float = 0.0, num_samples: int = 1):
         if output_data_format != 'all_frames':
             raise ValueError("DiffusionLabelPredictor: the diffusion models need --output-data-format all_frames")
+        if not 0.0 <= float(eta) <= 1.0:
+            raise ValueError(f"DiffusionLabelPredictor: eta must be in [0, 1], got {eta}")
+        if int(num_samples) != num_samples or num_samples < 1:
+            raise ValueError(f"DiffusionLabelPredictor: num_samples must be an integer >= 1, got {num_samples}")
         self.model, self.seed = model, int(seed)
-        self.sampler = ConditionalDDIMSampler(model, num_sample_steps, use_graph=use_graph)
+        self.eta, self.num_samples = float(eta), int(num_samples)
+        self.last_std: Optional[Dict[str, torch.Tensor]] = None
+        self.sampler = ConditionalDDIMSampler(model, num_sample_steps, use_graph=use_graph, eta=self.eta, seed=self.seed)
+
+    def member_ids(self, draw: int, batch: int):
+        """window ids of the sampler rows of a call: member k of window i = draw + b is i K + k"""
+        K = self.num_samples
+        return [(draw + b) * K + k for b in range(batch) for k in range(K)]
 
     @staticmethod
     def window_matrix(inputs: Dict[str, torch.Tensor]) -> torch.Tensor:
@@ -66,6 +83,15 @@ class DiffusionLabelPredictor:
             raise ValueError(f"a window row has {D} columns but the denoiser was built for feat_dim = {self.model.feat_dim}")
         if getattr(self.model, 'window', F) != F:
             raise ValueError(f"a window has {F} frames but the denoiser was built for window = {self.model.window}")
-        z = torch.cat([self.sampler.draw_start(1, F, D, self.seed, draw + b) for b in range(B)])
-        x = self.sampler.sample(z, obs, label_mask(F, D))
-        return self.split_labels(x)
+        K = self.num_samples
+        if K == 1 and self.eta == 0.0:
+            z = torch.cat([self.sampler.draw_start(1, F, D, self.seed, draw + b) for b in range(B)])
+            x = self.sampler.sample(z, obs, label_mask(F, D))
+            return self.split_labels(x)
+        ids = self.member_ids(draw, B)
+        z = torch.cat([self.sampler.draw_start(1, F, D, self.seed, i) for i in ids])
+        members = obs.unsqueeze(1).expand(B, K, F, D).reshape(B * K, F, D)
+        x = self.sampler.sample(z, members, label_mask(F, D), window_ids=ids)
+        mean, std = hip.ensemble_stats(x.view(B, K, F, D))
+        self.last_std = self.split_labels(std)
+        return self.split_labels(mean)

@@ -30,7 +30,7 @@ def hipcc():
 
 def short_name(mangled):
     """_ZN12_GLOBAL__N_120ffn_chain_fwd_kernelILb1ELb1ELb1ELb0EEEvNS_12FfnFwdParamsE -> ffn_chain_fwd_kernel<1,1,1,0>
-    (template arguments that are bools or ints; anything else keeps the mangled tail)"""
+    (template arguments that are float / bf16 element types, bools or ints; anything else keeps the mangled tail)"""
     m = re.match(r"_ZN(?:12_GLOBAL__N_1)?(\d+)", mangled)
     if not m:
         return mangled
@@ -39,9 +39,14 @@ def short_name(mangled):
     name = mangled[start:start + n]
     rest = mangled[start + n:]
     if rest.startswith("I"):
-        args = re.findall(r"L[bij](-?\d+|n\d+)E", rest[: rest.find("EE") + 1] if "EE" in rest else rest)
-        if args:
-            return f"{name}<{','.join(a.replace('n', '-') for a in args)}>"
+        # leading element types (f = float, DF16b = bf16), then bool / int literals
+        types, body = [], rest[1:]
+        while body.startswith(("f", "DF16b")):
+            types.append("float" if body[0] == "f" else "bf16")
+            body = body[1 if body[0] == "f" else 5:]
+        args = re.findall(r"L[bij](-?\d+|n\d+)E", body[: body.find("EE") + 1] if "EE" in body else body)
+        if types or args:
+            return f"{name}<{','.join(types + [a.replace('n', '-') for a in args])}>"
     return name
 
 
