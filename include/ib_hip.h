@@ -449,6 +449,29 @@ int ib_ddim_cond_step_noise(void* x, const void* eps, const void* x0, void* z, c
                             int64_t num_steps, int32_t step, const int32_t* step_dev, int64_t* t_out,
                             const int64_t* win_id, uint64_t seed, int64_t B, int64_t T, int64_t D, int64_t ld, int dtype,
                             ib_stream_t stream);
+/* The DPM-Solver++(2M) update of the sampling loop (second-order multistep, deterministic), over n = B * (elements per
+ * window) elements of the state, coef fp32 [num_steps, 5] = (A, E, C, hx, he):
+ *   x    <- coef[s][0] * x + coef[s][1] * eps + coef[s][2] * hist      (hist as the previous step left it)
+ *   hist <- coef[s][3] * x + coef[s][4] * eps                          (over the x the step was given: the data prediction)
+ * hist is fp32 [n] whatever dtype is, written by every row and read only by rows with C != 0.  A row with C == 0 (the
+ * first and the last of a table) never reads hist -- it may hold anything -- and leaves in x what ib_ddim_step leaves given
+ * (A, E), bit for bit.  s, t_out and the 8-wide / element-wise choice as in ib_ddim_step (hist must be 16-byte aligned for
+ * the 8-wide form; the element-wise form then rounds as the 8-wide one).  Zero pad columns of x and eps stay 0 in x and
+ * hist. */
+int ib_dpmpp_step(void* x, const void* eps, float* hist, const float* coef, const int64_t* timesteps, int64_t num_steps,
+                  int32_t step, const int32_t* step_dev, int64_t* t_out, int64_t B, int64_t n, int dtype,
+                  ib_stream_t stream);
+/* The masked DPM-Solver++(2M) update (operands and layout as ib_ddim_cond_step, hist fp32 [B, T, ld], coef [num_steps, 5]):
+ *   mask == 0 (free):     the update of ib_dpmpp_step
+ *   mask != 0 (observed): x <- obs_coef[s+1][0] * x0 + obs_coef[s+1][1] * z, the expression of ib_ddim_cond_step, bit for bit
+ *                         (when both entries take the same form, 8-wide or element-wise: a hist that is not 16-byte
+ *                         aligned moves this entry alone to the element-wise form, whose pinned value rounds differently)
+ * What hist holds at observed elements is unspecified; no step reads it there.  A row with C == 0 equals
+ * ib_ddim_cond_step given (A, E) bit for bit. */
+int ib_dpmpp_cond_step(void* x, const void* eps, float* hist, const void* x0, const void* z, const uint8_t* mask,
+                       const float* coef, const float* obs_coef, const int64_t* timesteps, int64_t num_steps,
+                       int32_t step, const int32_t* step_dev, int64_t* t_out, int64_t B, int64_t T, int64_t D, int64_t ld,
+                       int dtype, ib_stream_t stream);
 /* Ensemble reduction: x [B, K, n] (dtype) -> mean [B, n] and unbiased standard deviation [B, n], fp32.  Members are added
  * in the order k = 0 .. K-1 in fp32, mean = sum / K; std = sqrt(sum_k (x_k - mean)^2 / (K - 1)) in the same order; K = 1
  * gives std = 0. */

@@ -48,6 +48,12 @@ class AnalyzeCommand(AbstractCommand):
                        help='[diffusion models] eta of the sampler: 0 = deterministic DDIM, 1 = DDPM ancestral sampling.')
         p.add_argument('--num-samples', type=int, default=1,
                        help='[diffusion models] posterior samples per window; the mean is evaluated, the spread reported.')
+        p.add_argument('--sampler', type=str, default='ddim', choices=['ddim', 'dpmpp2m'],
+                       help='[diffusion models] update of the sampling loop: first-order DDIM, or DPM-Solver++(2M), second '
+                            'order with one denoiser evaluation per step, like DDIM (deterministic: needs --sample-eta 0).')
+        p.add_argument('--sample-spacing', type=str, default='time', choices=['time', 'logsnr'],
+                       help='[diffusion models] sampling grid: uniform in the timestep, or uniform in log-SNR (no need for '
+                            '--sample-steps to divide the training steps; the grid for few-step dpmpp2m sampling).')
         p.add_argument('--use-ema', action='store_true', default=False,
                        help='Evaluate the EMA weights of the checkpoint (`train --ema-decay`) instead of its last weights.')
 
@@ -106,6 +112,9 @@ class AnalyzeCommand(AbstractCommand):
         eta, num_samples = getattr(args, 'sample_eta', 0.0), getattr(args, 'num_samples', 1)
         if not 0.0 <= eta <= 1.0 or num_samples < 1:
             raise SystemExit("--sample-eta must be in [0, 1] and --num-samples >= 1")
+        solver, spacing = getattr(args, 'sampler', 'ddim'), getattr(args, 'sample_spacing', 'time')
+        if solver == 'dpmpp2m' and eta > 0.0:
+            raise SystemExit("--sampler dpmpp2m is deterministic: it needs --sample-eta 0")
         predictor = None
         for split, csv_name in (('dev', 'dev_analysis.csv'), ('train', 'train_analysis.csv')):
             logging.info(f'## Loading {split} dataset:')
@@ -117,7 +126,7 @@ class AnalyzeCommand(AbstractCommand):
                 model.eval()
                 predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
                                                     output_data_format=args.output_data_format, eta=eta,
-                                                    num_samples=num_samples)
+                                                    num_samples=num_samples, solver=solver, spacing=spacing)
             evaluator = RegressionLossEvaluator(dataset=dataset, split=split, device=device)
             loader = DataLoader(dataset, batch_size=args.sample_batch, shuffle=False, num_workers=args.data_loading_workers)
             compute_report = bool(getattr(dataset, 'skeletons', None))

@@ -1,5 +1,5 @@
 // [BUILD-DEFINED] diffusion wrapper kernels (no reference counterpart):
-// DDPM q_sample, DDIM update (eta = 0, and eta > 0 with the noise term drawn inside the update), table gathers.  The schedule / coefficient / timestep-embedding
+// DDPM q_sample, DDIM update (eta = 0, and eta > 0 with the noise term drawn inside the update), the DPM-Solver++(2M) update, table gathers.  The schedule / coefficient / timestep-embedding
 // tables are computed in float64 on the host and cast ONCE to fp32 (bit-exactness target of §8c); these
 // kernels only index them, so noise-schedule and timestep indexing stay bit-exact.
 #include "ib_common.h"
@@ -416,6 +416,139 @@ __global__ __launch_bounds__(256) void ddim_cond_step_noise_kernel(T* __restrict
   }
 }
 
+// ---- DPM-Solver++(2M) update (schedule.dpmpp_coefficients): coef rows (A, E, C, hx, he), x' = A x + E eps + C h_prev, and
+// the history the next step reads is h = hx x + he eps, the data prediction at this step's level.  hist is fp32 whatever
+// the state's dtype: the update takes the difference of two consecutive data predictions, and rounding each to bf16 would
+// be amplified by c = h_i / (2 h_{i-1}).  A x + E eps goes through ddim_mix and C h is one more fused multiply-add on its
+// value (as the noise term of ddim_step_noise_kernel is).  A row with C == 0 (the first and the last of every table: no
+// history yet, and the step to alpha_bar = 1) does not read hist -- the branch is uniform over the launch -- so its state is
+// ib_ddim_step's given (A, E), bit for bit, and an uninitialised history never reaches the state.  Every row writes hist.
+// mix8: as in ddim_cond_step_kernel.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void dpmpp_step_kernel(T* __restrict__ x, const T* __restrict__ eps, float* hist,
+                                                         const float* __restrict__ coef,
+                                                         const int64_t* __restrict__ timesteps, int64_t num_steps, int step,
+                                                         const int32_t* __restrict__ step_dev, int64_t* __restrict__ t_out,
+                                                         int64_t B, int64_t n, int mix8) {
+  int s = step_dev ? *step_dev : step;
+  s = s < 0 ? 0 : (s >= num_steps ? (int)num_steps - 1 : s);
+  const float cx = coef[5 * s], ce = coef[5 * s + 1], ch = coef[5 * s + 2], hx = coef[5 * s + 3], he = coef[5 * s + 4];
+  const bool second = ch != 0.f;                                       // uniform over the launch
+  const int64_t nv = n / V;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e0 = i * V;
+    float a[V], e[V], o[V], h[V];
+    ldv<T, V>(x + e0, a);
+    ldv<T, V>(eps + e0, e);
+#pragma unroll
+    for (int k = 0; k < V; ++k)
+      o[k] = (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a[k], ce, e[k]) : ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
+    if (second) {
+      ldv<float, V>(hist + e0, h);
+#pragma unroll
+      for (int k = 0; k < V; ++k) o[k] = __builtin_fmaf(ch, h[k], o[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) h[k] = __builtin_fmaf(hx, a[k], he * e[k]);
+    stv<float, V>(hist + e0, h);
+    stv<T, V>(x + e0, o);
+  }
+  if (t_out && blockIdx.x == 0) {
+    const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
+    for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
+  }
+}
+
+// the pinned value of a lone observed element as ddim_cond_step_kernel<T, 1, false> compiled it for gfx950: the sum of two
+// rounded products.  (Spelled out: next to the history's arithmetic the bare expression was fused in one instantiation.)
+__device__ __forceinline__ float obs_pin1(float ox, float a, float oz, float b) {
+#pragma clang fp contract(off)
+  return ox * a + oz * b;
+}
+
+// the loop of ddim_cond_step_kernel<T, V, false> with the history added to the vectors that have a free element: the
+// observed elements' pinned expression is that kernel's statement, so that it compiles as it does there (8-wide: checked
+// in the ISA, the same multiply / fused multiply-add pairing per element; element-wise: obs_pin1).  SECOND: the row
+// has C != 0 and reads hist.  What hist holds at an observed element is unspecified (a vector of observed elements only is
+// not touched; in a mixed vector it gets the expression of the free ones) and no step reads it there.
+template <typename T, int V, bool SECOND>
+__device__ __forceinline__ void dpmpp_cond_update(T* __restrict__ x, const T* __restrict__ eps, float* hist,
+                                                  const T* __restrict__ x0, const T* __restrict__ z,
+                                                  const uint8_t* __restrict__ mask, float cx, float ce, float ch, float hx,
+                                                  float he, float ox, float oz, int64_t per, int64_t n, int mix8) {
+  constexpr unsigned ALL = (1u << V) - 1;
+  const int64_t nv = n / V;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e0 = i * V, m0 = e0 % per;
+    unsigned bits;
+    if constexpr (V == 1) {
+      bits = mask[m0] != 0;
+    } else {
+      const uint64_t mv = *reinterpret_cast<const uint64_t*>(mask + m0);
+      bits = 0;
+#pragma unroll
+      for (int k = 0; k < V; ++k) bits |= (((mv >> (8 * k)) & 0xff) != 0 ? 1u : 0u) << k;
+    }
+    float o[V];
+    if (bits != ALL) {
+      float a[V];
+      ldv<T, V>(x + e0, a);
+      float e[V];
+      ldv<T, V>(eps + e0, e);
+#pragma unroll
+      for (int k = 0; k < V; ++k)
+        o[k] = (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a[k], ce, e[k]) : ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
+      float h[V];
+      if constexpr (SECOND) {
+        ldv<float, V>(hist + e0, h);
+#pragma unroll
+        for (int k = 0; k < V; ++k) o[k] = __builtin_fmaf(ch, h[k], o[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < V; ++k) h[k] = __builtin_fmaf(hx, a[k], he * e[k]);
+      stv<float, V>(hist + e0, h);
+    }
+    if (bits != 0) {
+      float a[V], b[V];
+      ldv<T, V>(x0 + e0, a);
+      ldv<T, V>(z + e0, b);
+#pragma unroll
+      for (int k = 0; k < V; ++k)
+        if ((bits >> k) & 1u) {
+          if constexpr (V == 1) o[k] = obs_pin1(ox, a[k], oz, b[k]);
+          else o[k] = ox * a[k] + oz * b[k];
+        }
+    }
+    stv<T, V>(x + e0, o);
+  }
+}
+
+// masked DPM-Solver++(2M) update: free elements as dpmpp_step_kernel, observed ones the pinned value of
+// ddim_cond_step_kernel, obs_coef[s + 1] (x0, z)
+template <typename T, int V>
+__global__ __launch_bounds__(256) void dpmpp_cond_step_kernel(T* __restrict__ x, const T* __restrict__ eps, float* hist,
+                                                              const T* __restrict__ x0, const T* __restrict__ z,
+                                                              const uint8_t* __restrict__ mask,
+                                                              const float* __restrict__ coef,
+                                                              const float* __restrict__ obs_coef,
+                                                              const int64_t* __restrict__ timesteps, int64_t num_steps,
+                                                              int step, const int32_t* __restrict__ step_dev,
+                                                              int64_t* __restrict__ t_out, int64_t B, int64_t per, int64_t n,
+                                                              int mix8) {
+  int s = step_dev ? *step_dev : step;
+  s = s < 0 ? 0 : (s >= num_steps ? (int)num_steps - 1 : s);
+  const float cx = coef[5 * s], ce = coef[5 * s + 1], ch = coef[5 * s + 2], hx = coef[5 * s + 3], he = coef[5 * s + 4];
+  const float ox = obs_coef[2 * (s + 1)], oz = obs_coef[2 * (s + 1) + 1];
+  if (ch == 0.f)                                                       // uniform over the launch
+    dpmpp_cond_update<T, V, false>(x, eps, hist, x0, z, mask, cx, ce, ch, hx, he, ox, oz, per, n, mix8);
+  else
+    dpmpp_cond_update<T, V, true>(x, eps, hist, x0, z, mask, cx, ce, ch, hx, he, ox, oz, per, n, mix8);
+  if (t_out && blockIdx.x == 0) {
+    const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
+    for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
+  }
+}
+
 // mean and unbiased standard deviation over the K members of an ensemble x [B, K, n], fp32 out.  One lane per (b, j); the
 // members are added in the order k = 0 .. K - 1, then the squared deviations from the rounded mean in the same order
 // (two passes: the second reads what the first left in cache).  K = 1: std = 0.
@@ -621,6 +754,58 @@ extern "C" int ib_ddim_cond_step_noise(void* x, const void* eps, const void* x0,
   if (dtype == IB_F32) IB_COND_NOISE_T(float); else IB_COND_NOISE_T(bf16_t);
 #undef IB_COND_NOISE_T
 #undef IB_COND_NOISE
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+extern "C" int ib_dpmpp_step(void* x, const void* eps, float* hist, const float* coef, const int64_t* timesteps,
+                             int64_t num_steps, int32_t step, const int32_t* step_dev, int64_t* t_out, int64_t B, int64_t n,
+                             int dtype, ib_stream_t stream) {
+  if (!x || !eps || !hist || !coef || num_steps <= 0 || n <= 0) return IB_E_ARG;
+  if (t_out && (!timesteps || B <= 0)) return IB_E_ARG;
+  if (dtype != IB_F32 && dtype != IB_BF16) return IB_E_DTYPE;
+  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
+  const bool mix8 = (n % 8 == 0) && al16(x) && al16(eps);          // ib_ddim_step's choice of its 8-wide kernel
+  const bool v8 = mix8 && al16(hist);
+  const int grid = ib_grid_1d(n / (v8 ? 8 : 1), 256);
+  hipStream_t s = ib_s(stream);
+#define IB_DPMPP_STEP(TY, V)                                                                                                  \
+  hipLaunchKernelGGL((dpmpp_step_kernel<TY, V>), dim3(grid), dim3(256), 0, s, (TY*)x, (const TY*)eps, hist, coef, timesteps,  \
+                     num_steps, step, step_dev, t_out, B, n, (int)mix8)
+  if (dtype == IB_F32) {
+    if (v8) IB_DPMPP_STEP(float, 8); else IB_DPMPP_STEP(float, 1);
+  } else {
+    if (v8) IB_DPMPP_STEP(bf16_t, 8); else IB_DPMPP_STEP(bf16_t, 1);
+  }
+#undef IB_DPMPP_STEP
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+extern "C" int ib_dpmpp_cond_step(void* x, const void* eps, float* hist, const void* x0, const void* z, const uint8_t* mask,
+                                  const float* coef, const float* obs_coef, const int64_t* timesteps, int64_t num_steps,
+                                  int32_t step, const int32_t* step_dev, int64_t* t_out, int64_t B, int64_t T, int64_t D,
+                                  int64_t ld, int dtype, ib_stream_t stream) {
+  if (!x || !eps || !hist || !x0 || !z || !mask || !coef || !obs_coef || num_steps <= 0) return IB_E_ARG;
+  if (B <= 0 || T <= 0 || D <= 0 || ld < D) return IB_E_ARG;
+  if (t_out && !timesteps) return IB_E_ARG;
+  if (dtype != IB_F32 && dtype != IB_BF16) return IB_E_DTYPE;
+  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
+  const int64_t per = T * ld, n = B * per;
+  const bool mix8 = (n % 8 == 0) && al16(x) && al16(eps);          // ib_ddim_step's choice of its 8-wide kernel
+  const bool v8 = mix8 && (per % 8 == 0) && al16(hist) && al16(x0) && al16(z) && (reinterpret_cast<uintptr_t>(mask) % 8) == 0;
+  const int grid = ib_grid_1d(n / (v8 ? 8 : 1), 256);
+  hipStream_t s = ib_s(stream);
+#define IB_DPMPP_COND(TY, V)                                                                                                  \
+  hipLaunchKernelGGL((dpmpp_cond_step_kernel<TY, V>), dim3(grid), dim3(256), 0, s, (TY*)x, (const TY*)eps, hist,             \
+                     (const TY*)x0, (const TY*)z, mask, coef, obs_coef, timesteps, num_steps, step, step_dev, t_out, B, per, n, \
+                     (int)mix8)
+  if (dtype == IB_F32) {
+    if (v8) IB_DPMPP_COND(float, 8); else IB_DPMPP_COND(float, 1);
+  } else {
+    if (v8) IB_DPMPP_COND(bf16_t, 8); else IB_DPMPP_COND(bf16_t, 1);
+  }
+#undef IB_DPMPP_COND
   IB_CHECK_LAUNCH();
   return IB_OK;
 }

@@ -1,6 +1,10 @@
 """[BUILD-DEFINED] DDIM / DDPM sampling loop: N denoiser evaluations + updates; eta = 0 is the
 deterministic DDIM loop, eta in (0, 1] adds the noise term sigma z' (eta = 1 with as many sampling steps as training steps:
 DDPM ancestral sampling), drawn inside the update kernel from a counter-based generator keyed by (seed, window id, step).
+solver = 'dpmpp2m' swaps the first-order DDIM update for DPM-Solver++(2M), a second-order multistep update with the same work
+per step (one denoiser evaluation and one update launch; it keeps the previous step's data prediction in an fp32 buffer), and
+spacing = 'logsnr' runs either solver on a grid uniform in log-SNR instead of in t (schedule.sample_timesteps) -- the pair
+that needs far fewer steps for the same accuracy (docs/EXPERIMENTS.md).
 
 One denoise step = {time-embedding gather, denoiser forward plan, DDIM update, counter++}.  The step index
 lives in DEVICE memory (an int32 counter the update kernel reads), and the update kernel also writes the next
@@ -12,16 +16,25 @@ import torch
 
 from .. import hip
 from ..plans import ParamSource
+from .schedule import SOLVERS, SPACINGS
 
 
 class DDIMSampler:
     def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True, eta: float = 0.0,
-                 seed: Optional[int] = None):
-        """eta in [0, 1]; seed (default: torch's initial seed) keys the step noise of an eta > 0 loop"""
+                 seed: Optional[int] = None, solver: str = "ddim", spacing: str = "time"):
+        """eta in [0, 1]; seed (default: torch's initial seed) keys the step noise of an eta > 0 loop; solver 'ddim' or
+        'dpmpp2m' (deterministic: eta = 0 only); spacing 'time' or 'logsnr', the sampling grid"""
         if not 0.0 <= float(eta) <= 1.0:
             raise ValueError(f"eta must be in [0, 1], got {eta}")
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+        if spacing not in SPACINGS:
+            raise ValueError(f"spacing must be one of {SPACINGS}, got {spacing!r}")
+        if solver == "dpmpp2m" and float(eta) > 0.0:
+            raise ValueError("solver 'dpmpp2m' is deterministic: it needs eta = 0")
         self.model, self.S = model, num_sample_steps
         self.eta = float(eta)
+        self.solver, self.spacing = solver, spacing
         self.seed = (int(torch.initial_seed()) if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
         self._win = None
         self.use_graph = use_graph and not hip._dry_run
@@ -45,7 +58,9 @@ class DDIMSampler:
         hip.counter_add(ctr, 1)
 
     def _update(self, x, eps, ctr, t_vec, tabs):
-        if self.eta == 0.0:
+        if self.solver == "dpmpp2m":
+            hip.dpmpp_step(x, eps, self._bufs["hist"], tabs.dpmpp_coef, tabs.ddim_t, step_dev=ctr, t_out=t_vec)
+        elif self.eta == 0.0:
             hip.ddim_step(x, eps, tabs.ddim_coef, tabs.ddim_t, step_dev=ctr, t_out=t_vec)
         else:
             hip.ddim_step_noise(x, eps, tabs.ddim_coef_eta, tabs.ddim_t, self._bufs["win"], self.seed, step_dev=ctr,
@@ -56,6 +71,12 @@ class DDIMSampler:
         if self.eta == 0.0:
             return (0.0,)
         return (self.eta, self.seed, tabs.ddim_coef_eta.data_ptr(), tabs.obs_noise_coef.data_ptr())
+
+    def _solver_sig(self, tabs) -> tuple:
+        """solver and grid, and the table a 'dpmpp2m' update launch bakes in; nothing at the defaults"""
+        if self.solver == "ddim" and self.spacing == "time":
+            return ()
+        return (self.solver, self.spacing, tabs.dpmpp_coef.data_ptr() if self.solver == "dpmpp2m" else 0)
 
     def _set_window_ids(self, B: int):
         """copies the call's window ids (default 0 .. B-1) into the device buffer the captured update reads"""
@@ -126,8 +147,8 @@ class DDIMSampler:
         m.sync_shadow()
         dev = m._flat.device
         tabs = m.tables(dev)
-        if tabs.num_sample_steps != self.S or (self.eta > 0.0 and getattr(tabs, "eta", 0.0) != self.eta):
-            tabs.set_sampler(self.S, self.eta)
+        if not tabs.serves(self.S, self.eta, self.solver, self.spacing):
+            tabs.set_sampler(self.S, self.eta, self.solver, self.spacing)
         # the captured step bakes in raw pointers: the model's flat parameter buffer and bf16 shadow (a HipTrainer built
         # after a first sample() re-packs them), the schedule tables (set_sampler() of another sampler re-creates the DDIM
         # tables) -- all of them are part of the signature, so a change re-captures instead of replaying stale pointers
@@ -137,7 +158,7 @@ class DDIMSampler:
         plan = m._get_plan(dev)
         B, T, D = x_T.shape
         Dp = plan.infer_pitch(D) if (hasattr(plan, "infer_pitch") and m.compute_dtype == torch.bfloat16) else D
-        sig = sig + (Dp,) + self._extra_sig(tabs) + self._noise_sig(tabs)
+        sig = sig + (Dp,) + self._extra_sig(tabs) + self._solver_sig(tabs) + self._noise_sig(tabs)
         if sig != self._sig:
             self._sig, self._graph = sig, None
             self._bufs = {"x": torch.zeros((B, T, Dp), dtype=m.compute_dtype, device=dev),
@@ -148,6 +169,10 @@ class DDIMSampler:
             self._bufs.update(self._extra_buffers(B, T, D, Dp, dev, m.compute_dtype))
             if self.eta > 0.0:
                 self._bufs["win"] = torch.zeros(B, dtype=torch.int64, device=dev)
+            if self.solver == "dpmpp2m":
+                # the previous step's data prediction, fp32 whatever the state's dtype, pitched like the state.  The first
+                # row of the table does not read it, so a new batch needs no reset
+                self._bufs["hist"] = torch.zeros((B, T, Dp), dtype=torch.float32, device=dev)
         self._D = D
         if self.eta > 0.0:
             self._set_window_ids(B)
@@ -193,13 +218,14 @@ class ConditionalDDIMSampler(DDIMSampler):
     deterministic and its last step (to alpha_bar = 1) returns the observation itself.  The free elements follow the DDIM
     update.  With eta > 0 an observed element follows the DDIM posterior given the observation: its noise, kept in the z
     buffer, becomes r z + q z' at every step (schedule.observation_noise_coefficients), and the last step still lands on
-    the observation.  Same captured single-step graph as DDIMSampler; only the update launch differs (ib_ddim_cond_step, the same
+    the observation.  With solver = 'dpmpp2m' the free elements take the DPM-Solver++(2M) update instead and the observed ones
+    the same pinned value (ib_dpmpp_cond_step).  Same captured single-step graph as DDIMSampler; only the update launch differs (ib_ddim_cond_step, the same
     launch count per step).  The observation, the draw and the mask live in sampler-owned device buffers that the capture
     reads, so a new batch of the same shape is copied in and the captured step replayed."""
 
     def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True, eta: float = 0.0,
-                 seed: Optional[int] = None):
-        super().__init__(model, num_sample_steps, use_graph, eta, seed)
+                 seed: Optional[int] = None, solver: str = "ddim", spacing: str = "time"):
+        super().__init__(model, num_sample_steps, use_graph, eta, seed, solver, spacing)
         self._cond = None
 
     @torch.no_grad()
@@ -248,7 +274,10 @@ class ConditionalDDIMSampler(DDIMSampler):
 
     def _update(self, x, eps, ctr, t_vec, tabs):
         b = self._bufs
-        if self.eta == 0.0:
+        if self.solver == "dpmpp2m":
+            hip.dpmpp_cond_step(x, eps, b["hist"], b["x0"], b["z"], b["mask"], tabs.dpmpp_coef, tabs.obs_coef, tabs.ddim_t,
+                                step_dev=ctr, t_out=t_vec, D=self._D)
+        elif self.eta == 0.0:
             hip.ddim_cond_step(x, eps, b["x0"], b["z"], b["mask"], tabs.ddim_coef, tabs.obs_coef, tabs.ddim_t, step_dev=ctr,
                                t_out=t_vec, D=self._D)
         else:

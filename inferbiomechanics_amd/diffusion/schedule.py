@@ -26,10 +26,47 @@ def ddim_timesteps(num_train_steps: int = 1000, num_sample_steps: int = 100) -> 
     return torch.arange(num_sample_steps - 1, -1, -1, dtype=torch.int64) * stride
 
 
-def ddim_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100) -> torch.Tensor:
+def log_snr(num_train_steps: int = 1000) -> torch.Tensor:
+    """[N] float64: lambda_t = 1/2 log(alpha_bar_t / (1 - alpha_bar_t)), the half log-SNR; strictly decreasing in t"""
+    ab = alphas_cumprod(num_train_steps)
+    return 0.5 * torch.log(ab / (1.0 - ab))
+
+
+SPACINGS = ("time", "logsnr")
+SOLVERS = ("ddim", "dpmpp2m")
+
+
+def sample_timesteps(num_train_steps: int = 1000, num_sample_steps: int = 100, spacing: str = "time") -> torch.Tensor:
+    """[S] int64, strictly decreasing: the sampling grid.  'time' is ddim_timesteps (uniform in t, needs S | N).  'logsnr' is
+    uniform in lambda: S targets from lambda_{N-1} to lambda_0, each rounded to the timestep whose lambda is nearest; the
+    linear beta schedule packs much of the lambda range into the last few timesteps, so neighbouring targets can round to
+    one timestep there -- strict decrease is then forced from the clean end, t[S-1] = nearest, t[i] = max(nearest[i],
+    t[i+1] + 1).  Needs no S | N; an S so large that the forcing would pass N - 1 is an error."""
+    if spacing == "time":
+        return ddim_timesteps(num_train_steps, num_sample_steps)
+    if spacing != "logsnr":
+        raise ValueError(f"spacing must be one of {SPACINGS}, got {spacing!r}")
+    N, S = int(num_train_steps), int(num_sample_steps)
+    if S < 1:
+        raise ValueError("num_sample_steps must be at least 1")
+    lam = log_snr(N)
+    targets = torch.linspace(float(lam[N - 1]), float(lam[0]), S, dtype=torch.float64)
+    up = lam.flip(0)                                                       # ascending: up[j] = lambda_{N-1-j}
+    hi = torch.searchsorted(up, targets).clamp(1, N - 1)                   # up[hi - 1] < target <= up[hi]
+    hi = torch.where(targets - up[hi - 1] < up[hi] - targets, hi - 1, hi)  # the nearer neighbour; a tie takes the smaller t
+    nearest = (N - 1 - hi).tolist()
+    ts = list(nearest)
+    for i in range(S - 2, -1, -1):
+        ts[i] = max(nearest[i], ts[i + 1] + 1)
+    if ts[0] > N - 1:
+        raise ValueError(f"no strictly decreasing log-SNR grid of {S} steps fits {N} training steps")
+    return torch.tensor(ts, dtype=torch.int64)
+
+
+def ddim_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100, spacing: str = "time") -> torch.Tensor:
     """[S, 2] float64 (c_x, c_eps): x_prev = c_x x_t + c_eps eps (eta = 0; last step goes to alpha_bar = 1)."""
     ab = alphas_cumprod(num_train_steps)
-    ts = ddim_timesteps(num_train_steps, num_sample_steps).tolist()
+    ts = sample_timesteps(num_train_steps, num_sample_steps, spacing).tolist()
     rows = []
     for i, t in enumerate(ts):
         ab_t = ab[t]
@@ -40,59 +77,96 @@ def ddim_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100) 
     return torch.stack(rows)
 
 
-def observation_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100) -> torch.Tensor:
+def observation_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100, spacing: str = "time") -> torch.Tensor:
     """[S + 1, 2] float64 (c_x0, c_z) of the masked (inpainting) loop: an observed element is x0 forward-noised with the
     fixed draw z to the loop's noise level, c_x0 x0 + c_z z.  Row 0 = (sqrt ab[t_0], sqrt(1 - ab[t_0])) is the start state;
     row s + 1 = (sqrt ab_prev(s), sqrt(1 - ab_prev(s))) is the level after step s, so the last row is exactly (1, 0)."""
     ab = alphas_cumprod(num_train_steps)
-    ts = ddim_timesteps(num_train_steps, num_sample_steps).tolist()
+    ts = sample_timesteps(num_train_steps, num_sample_steps, spacing).tolist()
     levels = [ab[ts[0]]] + [ab[ts[i + 1]] if i + 1 < len(ts) else torch.tensor(1.0, dtype=torch.float64)
                             for i in range(len(ts))]
     return torch.stack([torch.stack([torch.sqrt(a), torch.sqrt(1 - a)]) for a in levels])
 
 
-def _levels(num_train_steps: int, num_sample_steps: int):
+def _levels(num_train_steps: int, num_sample_steps: int, spacing: str = "time"):
     """(alpha_bar[t_s], alpha_bar of the next level) per sampling step, float64; the last step goes to alpha_bar = 1"""
     ab = alphas_cumprod(num_train_steps)
-    ts = ddim_timesteps(num_train_steps, num_sample_steps).tolist()
+    ts = sample_timesteps(num_train_steps, num_sample_steps, spacing).tolist()
     one = torch.tensor(1.0, dtype=torch.float64)
     return [(ab[t], ab[ts[i + 1]] if i + 1 < len(ts) else one) for i, t in enumerate(ts)]
 
 
-def ddim_sigmas(num_train_steps: int = 1000, num_sample_steps: int = 100, eta: float = 0.0) -> torch.Tensor:
+def ddim_sigmas(num_train_steps: int = 1000, num_sample_steps: int = 100, eta: float = 0.0,
+                spacing: str = "time") -> torch.Tensor:
     """[S] float64: sigma_s = eta sqrt((1 - p) / (1 - a)) sqrt(1 - a / p) (Song et al., DDIM eq. 16); eta = 1 with S = N is
     the DDPM posterior's standard deviation.  Exactly 0 at eta = 0 and in the last row (p = 1)."""
     if not 0.0 <= float(eta) <= 1.0:
         raise ValueError(f"eta must be in [0, 1], got {eta}")
     return torch.stack([float(eta) * torch.sqrt((1 - p) / (1 - a)) * torch.sqrt(1 - a / p)
-                        for a, p in _levels(num_train_steps, num_sample_steps)])
+                        for a, p in _levels(num_train_steps, num_sample_steps, spacing)])
 
 
-def ddim_coefficients_eta(num_train_steps: int = 1000, num_sample_steps: int = 100, eta: float = 0.0) -> torch.Tensor:
+def ddim_coefficients_eta(num_train_steps: int = 1000, num_sample_steps: int = 100, eta: float = 0.0,
+                          spacing: str = "time") -> torch.Tensor:
     """[S, 3] float64 (c_x, c_eps, sigma): x_prev = c_x x_t + c_eps eps + sigma z', z' ~ N(0, I).  c_x does not depend on
     eta; c_eps = sqrt(1 - p - sigma^2) - sqrt(p) sqrt(1 - a) / sqrt(a).  At eta = 0 the first two columns are
     ddim_coefficients bit for bit."""
-    sig = ddim_sigmas(num_train_steps, num_sample_steps, eta)
+    sig = ddim_sigmas(num_train_steps, num_sample_steps, eta, spacing)
     rows = []
-    for (a, p), sg in zip(_levels(num_train_steps, num_sample_steps), sig):
+    for (a, p), sg in zip(_levels(num_train_steps, num_sample_steps, spacing), sig):
         cx = torch.sqrt(p) / torch.sqrt(a)
         ce = torch.sqrt(1 - p - sg * sg) - torch.sqrt(p) * torch.sqrt(1 - a) / torch.sqrt(a)
         rows.append(torch.stack([cx, ce, sg]))
     return torch.stack(rows)
 
 
-def observation_noise_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100, eta: float = 0.0) -> torch.Tensor:
+def observation_noise_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100, eta: float = 0.0,
+                                   spacing: str = "time") -> torch.Tensor:
     """[S, 2] float64 (r, q): an observed element of the masked loop follows the DDIM posterior given the observation,
     q_sigma(x_prev | x_t, x0).  With e the element's current noise (x_t = sqrt(a) x0 + sqrt(1 - a) e), the noise of the next
     level is e' = r e + q z' with r = sqrt(1 - p - sigma^2) / sqrt(1 - p), q = sigma / sqrt(1 - p), r^2 + q^2 = 1.  Exactly
     (1, 0) at eta = 0 (e stays the start draw); (0, 0) in the last row, where the level is the observation itself."""
-    sig = ddim_sigmas(num_train_steps, num_sample_steps, eta)
+    sig = ddim_sigmas(num_train_steps, num_sample_steps, eta, spacing)
     rows = []
-    for (a, p), sg in zip(_levels(num_train_steps, num_sample_steps), sig):
+    for (a, p), sg in zip(_levels(num_train_steps, num_sample_steps, spacing), sig):
         if float(p) == 1.0:
             rows.append(torch.zeros(2, dtype=torch.float64))
         else:
             rows.append(torch.stack([torch.sqrt(1 - p - sg * sg) / torch.sqrt(1 - p), sg / torch.sqrt(1 - p)]))
+    return torch.stack(rows)
+
+
+def dpmpp_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100, spacing: str = "time") -> torch.Tensor:
+    """[S, 5] float64 (A, E, C, hx, he) of DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2; data prediction, multistep):
+    x' = A x + E eps + C h_prev, and the history the next step reads is h = hx x + he eps = (x - sigma_s eps) / alpha_s, the
+    data prediction at this step's level (alpha = sqrt(alpha_bar), sigma = sqrt(1 - alpha_bar)).  Step i from level s to
+    level t: h_i = lambda_t - lambda_s, g = alpha_t (1 - exp(-h_i)), c = h_i / (2 h_{i-1}); the solver's
+    x' = (sigma_t / sigma_s) x + g ((1 + c) x0_s - c x0_prev) gives A = sigma_t / sigma_s + g (1 + c) / alpha_s,
+    E = -g (1 + c) sigma_s / alpha_s, C = -g c.  The first row has no history and the last goes to alpha_bar = 1 (h
+    infinite): both are first order, which in this parametrisation is the DDIM update -- their (A, E) are the
+    ddim_coefficients rows of the same grid and C = 0."""
+    ab = alphas_cumprod(num_train_steps)
+    ts = sample_timesteps(num_train_steps, num_sample_steps, spacing).tolist()
+    first = ddim_coefficients(num_train_steps, num_sample_steps, spacing)
+    lam = log_snr(num_train_steps)
+    S = len(ts)
+    zero = torch.tensor(0.0, dtype=torch.float64)
+    rows = []
+    for i, s in enumerate(ts):
+        al_s, sg_s = torch.sqrt(ab[s]), torch.sqrt(1 - ab[s])
+        hx, he = 1.0 / al_s, -sg_s / al_s
+        if i == 0 or i == S - 1:
+            A, E, C = first[i, 0], first[i, 1], zero
+        else:
+            t = ts[i + 1]
+            al_t, sg_t = torch.sqrt(ab[t]), torch.sqrt(1 - ab[t])
+            h = lam[t] - lam[s]
+            c = h / (2.0 * (lam[s] - lam[ts[i - 1]]))
+            g = -al_t * torch.expm1(-h)
+            A = sg_t / sg_s + g * (1 + c) / al_s
+            E = -g * (1 + c) * sg_s / al_s
+            C = -g * c
+        rows.append(torch.stack([A, E, C, hx, he]))
     return torch.stack(rows)
 
 
@@ -117,20 +191,37 @@ class DiffusionTables:
         self.set_sampler(num_sample_steps)
         self.device = device
 
-    def set_sampler(self, num_sample_steps: int, eta: float = 0.0):
-        """the sampler's tables for S steps; eta > 0 adds the stochastic loop's (c_x, c_eps, sigma) and (r, q) tables"""
+    def set_sampler(self, num_sample_steps: int, eta: float = 0.0, solver: str = "ddim", spacing: str = "time"):
+        """the sampler's tables for S steps on the `spacing` grid; eta > 0 adds the stochastic loop's (c_x, c_eps, sigma) and
+        (r, q) tables, solver 'dpmpp2m' the second-order multistep solver's (A, E, C, hx, he) table"""
         if not 0.0 <= float(eta) <= 1.0:
             raise ValueError(f"eta must be in [0, 1], got {eta}")
-        self.num_sample_steps, self.eta = num_sample_steps, float(eta)
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+        if spacing not in SPACINGS:
+            raise ValueError(f"spacing must be one of {SPACINGS}, got {spacing!r}")
+        if solver == "dpmpp2m" and float(eta) > 0.0:
+            raise ValueError("solver 'dpmpp2m' is deterministic: it needs eta = 0")
+        N = self.num_train_steps
         dev = self.sqrt_ab.device
-        self.ddim_t = ddim_timesteps(self.num_train_steps, num_sample_steps).to(dev)
-        self.ddim_coef = ddim_coefficients(self.num_train_steps, num_sample_steps).to(torch.float32).to(dev).contiguous()
-        self.obs_coef = observation_coefficients(self.num_train_steps, num_sample_steps).to(torch.float32).to(dev).contiguous()
-        self.ddim_coef_eta = self.obs_noise_coef = None
+        ddim_t = sample_timesteps(N, num_sample_steps, spacing).to(dev)          # raises before anything is replaced
+        self.num_sample_steps, self.eta, self.solver, self.spacing = num_sample_steps, float(eta), solver, spacing
+        self.ddim_t = ddim_t
+        self.ddim_coef = ddim_coefficients(N, num_sample_steps, spacing).to(torch.float32).to(dev).contiguous()
+        self.obs_coef = observation_coefficients(N, num_sample_steps, spacing).to(torch.float32).to(dev).contiguous()
+        self.ddim_coef_eta = self.obs_noise_coef = self.dpmpp_coef = None
         if self.eta > 0.0:
-            N = self.num_train_steps
-            self.ddim_coef_eta = ddim_coefficients_eta(N, num_sample_steps, eta).to(torch.float32).to(dev).contiguous()
-            self.obs_noise_coef = observation_noise_coefficients(N, num_sample_steps, eta).to(torch.float32).to(dev).contiguous()
+            self.ddim_coef_eta = ddim_coefficients_eta(N, num_sample_steps, eta, spacing).to(torch.float32).to(dev).contiguous()
+            self.obs_noise_coef = observation_noise_coefficients(N, num_sample_steps, eta, spacing).to(torch.float32).to(dev).contiguous()
+        if solver == "dpmpp2m":
+            self.dpmpp_coef = dpmpp_coefficients(N, num_sample_steps, spacing).to(torch.float32).to(dev).contiguous()
+
+    def serves(self, num_sample_steps: int, eta: float = 0.0, solver: str = "ddim", spacing: str = "time") -> bool:
+        """whether the current tables are the ones a loop with these settings reads: the grid (S, spacing) must match; the
+        eta tables only matter to an eta > 0 loop and the solver's table only to 'dpmpp2m'"""
+        return (self.num_sample_steps == num_sample_steps and self.spacing == spacing
+                and (float(eta) == 0.0 or self.eta == float(eta))
+                and (solver != "dpmpp2m" or self.dpmpp_coef is not None))
 
     def host_tables(self) -> Dict[str, torch.Tensor]:
         return {"sqrt_ab": self.sqrt_ab.cpu(), "sqrt_1mab": self.sqrt_1mab.cpu(), "temb": self.temb.cpu(),

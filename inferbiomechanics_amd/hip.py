@@ -168,6 +168,9 @@ _SIGS = {
                                       _c.c_int, _vp]),
     "ib_ddim_cond_step_noise": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp,
                                            _c.c_uint64, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
+    "ib_dpmpp_step": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _c.c_int, _vp]),
+    "ib_dpmpp_cond_step": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i64,
+                                      _i64, _c.c_int, _vp]),
     "ib_ensemble_stats": (_c.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _c.c_int, _vp]),
     "ib_counter_add": (_c.c_int, [_vp, _i32, _vp]),
     "ib_batchnorm_fwd": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _f32, _f32, _c.c_int,
@@ -2288,6 +2291,52 @@ def ddim_cond_step_noise(x, eps, x0, z, mask, coef, obs_coef, obs_noise_coef, ti
                                          _ptr(obs_noise_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out),
                                          _ptr(win_id), int(seed) & 0xFFFFFFFFFFFFFFFF, B, T, D, ld, dtype_code(x.dtype),
                                          stream_ptr()), "ib_ddim_cond_step_noise")
+    return x
+
+
+def _dpmpp_operands(what, x, eps, hist, coef, timesteps, t_out, step_dev):
+    """shared checks of the DPM-Solver++(2M) updates -> S"""
+    _req(eps, "eps", x.dtype)
+    if eps.shape != x.shape or not x.is_contiguous() or not eps.is_contiguous():
+        raise HipError(f"{what}: x/eps must be contiguous with one shape")
+    _req(hist, "hist", torch.float32)
+    if hist.shape != x.shape or not hist.is_contiguous():
+        raise HipError(f"{what}: hist must be contiguous fp32 {tuple(x.shape)}, like x")
+    _req(coef, "coef", torch.float32, 2)
+    _req(timesteps, "timesteps", torch.int64, 1)
+    S = coef.shape[0]
+    if coef.shape[1] != 5 or timesteps.numel() != S or not coef.is_contiguous():
+        raise HipError(f"{what}: coef must be [S, 5] fp32 (A, E, C, hx, he), timesteps [S] int64")
+    if t_out is not None:
+        _req(t_out, "t_out", torch.int64, 1)
+        if t_out.numel() != x.shape[0]:
+            raise HipError("t_out must be int64 [B]")
+    if step_dev is not None:
+        _req(step_dev, "step_dev", torch.int32)
+    return S
+
+
+def dpmpp_step(x, eps, hist, coef, timesteps, step=0, step_dev=None, t_out=None):
+    """DPM-Solver++(2M) update in place (csrc/diffusion.hip): coef [S, 5] = (A, E, C, hx, he), x <- A x + E eps + C hist, then
+    hist <- hx x + he eps over the x it was given (fp32, the shape of x); a row with C == 0 does not read hist and equals
+    ddim_step given (A, E).  t_out / step_dev as in ddim_step."""
+    _req(x, "x", x.dtype)
+    S = _dpmpp_operands("dpmpp_step", x, eps, hist, coef, timesteps, t_out, step_dev)
+    _check(lib().ib_dpmpp_step(_ptr(x), _ptr(eps), _ptr(hist), _ptr(coef), _ptr(timesteps), S, int(step), _ptr(step_dev),
+                               _ptr(t_out), x.shape[0], x.numel(), dtype_code(x.dtype), stream_ptr()), "ib_dpmpp_step")
+    return x
+
+
+def dpmpp_cond_step(x, eps, hist, x0, z, mask, coef, obs_coef, timesteps, step=0, step_dev=None, t_out=None, D=None):
+    """masked DPM-Solver++(2M) update in place over the state x [B, T, ld]: elements with mask [T, ld] == 0 take the
+    dpmpp_step update (hist fp32 [B, T, ld]), the others obs_coef[s + 1] (x0, z) as in ddim_cond_step."""
+    B, T, D, ld = _cond_operands("dpmpp_cond_step", x, x0, z, mask, obs_coef, D)
+    S = _dpmpp_operands("dpmpp_cond_step", x, eps, hist, coef, timesteps, t_out, step_dev)
+    if obs_coef.shape[0] != S + 1:
+        raise HipError(f"dpmpp_cond_step: obs_coef must have S + 1 = {S + 1} rows, got {obs_coef.shape[0]}")
+    _check(lib().ib_dpmpp_cond_step(_ptr(x), _ptr(eps), _ptr(hist), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef),
+                                    _ptr(obs_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out), B, T, D, ld,
+                                    dtype_code(x.dtype), stream_ptr()), "ib_dpmpp_cond_step")
     return x
 
 

@@ -33,10 +33,11 @@ class DiffusionLabelPredictor:
     window i = draw + b is replicated K times inside the sampler batch (B K rows); member k has window id i K + k for both its
     start draw and its step noise (eta > 0), the outputs are the members' mean and ``last_std`` their unbiased standard
     deviation, in the same four-key layout (None on the default eta = 0, K = 1 path, which is the single deterministic
-    trajectory)."""
+    trajectory).  solver / spacing choose the sampler's update and grid (diffusion/sampler.py)."""
 
     def __init__(self, model, num_sample_steps: int = 100, seed: int = 0, output_data_format: str = 'all_frames',
-                 use_graph: bool = True, eta: float = 0.0, num_samples: int = 1):
+                 use_graph: bool = True, eta: float = 0.0, num_samples: int = 1, solver: str = 'ddim',
+                 spacing: str = 'time'):
         if output_data_format != 'all_frames':
             raise ValueError("DiffusionLabelPredictor: the diffusion models need --output-data-format all_frames")
         if not 0.0 <= float(eta) <= 1.0:
@@ -46,7 +47,8 @@ class DiffusionLabelPredictor:
         self.model, self.seed = model, int(seed)
         self.eta, self.num_samples = float(eta), int(num_samples)
         self.last_std: Optional[Dict[str, torch.Tensor]] = None
-        self.sampler = ConditionalDDIMSampler(model, num_sample_steps, use_graph=use_graph, eta=self.eta, seed=self.seed)
+        self.sampler = ConditionalDDIMSampler(model, num_sample_steps, use_graph=use_graph, eta=self.eta, seed=self.seed,
+                                              solver=solver, spacing=spacing)
 
     def member_ids(self, draw: int, batch: int):
         """window ids of the sampler rows of a call: member k of window i = draw + b is i K + k"""
