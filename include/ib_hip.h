@@ -266,6 +266,16 @@ int ib_mse_loss_partial(const void* pred, int64_t ld_pred, const void* target, v
                         void* workspace, size_t workspace_bytes, int64_t rows, int64_t cols, int dtype,
                         ib_stream_t stream);   /* pred / dpred: [rows, cols] with leading dimensions; target contiguous */
 int ib_mse_loss_finalize(const void* workspace, size_t workspace_bytes, float* result, int64_t n, ib_stream_t stream);
+/* the same pair for a denoiser conditioned on the first cond_cols columns of every row (0 <= cond_cols < cols): loss = mean
+ * over the rows x (cols - cond_cols) free elements, dpred = 2 (pred - target) / (rows (cols - cond_cols)) there and exact
+ * 0 on the conditioning columns, written on every launch.  The workspace is that of n = rows * cols.  The finalize takes the
+ * launch's n (the partial count) and the mean's denominator apart: n_launch = rows * cols, n_mean = rows * (cols -
+ * cond_cols).  cond_cols = 0 is ib_mse_loss_partial + ib_mse_loss_finalize bit for bit. */
+int ib_mse_loss_partial_cond(const void* pred, int64_t ld_pred, const void* target, void* dpred, int64_t ld_dpred,
+                             void* workspace, size_t workspace_bytes, int64_t rows, int64_t cols, int64_t cond_cols,
+                             int dtype, ib_stream_t stream);
+int ib_mse_loss_finalize_cond(const void* workspace, size_t workspace_bytes, float* result, int64_t n_launch, int64_t n_mean,
+                              ib_stream_t stream);
 
 /* ---- optimizer step: torch.optim.{SGD,Adam,RMSprop,Adagrad,Adadelta,Adamax}(lr) defaults,
  * src/cli/train.py:183-197,284.  One launch over a FLAT fp32 parameter buffer.  g is multiplied by
@@ -406,6 +416,11 @@ int ib_gather_rows_bwd(const float* dout, const int64_t* idx, float* dtable, int
 int ib_q_sample(const void* x0, const void* eps, const int64_t* t, const float* sqrt_ab,
                 const float* sqrt_1mab, void* x_t, int64_t ld_xt, int64_t B, int64_t T, int64_t D,
                 int64_t table_rows, int dtype, ib_stream_t stream);
+/* q_sample for a denoiser conditioned on the first cond_cols columns of every frame row (0 <= cond_cols < D): those columns
+ * of x_t are x0's, copied without arithmetic; the columns from cond_cols on are what ib_q_sample writes, bit for bit. */
+int ib_q_sample_cond(const void* x0, const void* eps, const int64_t* t, const float* sqrt_ab,
+                     const float* sqrt_1mab, void* x_t, int64_t ld_xt, int64_t B, int64_t T, int64_t D,
+                     int64_t table_rows, int64_t cond_cols, int dtype, ib_stream_t stream);
 /* x <- coef[s][0] * x + coef[s][1] * eps with s = *step_dev (or `step` if step_dev NULL).
  * Also writes t_out[b] = timesteps[s+1] (the NEXT step's timestep, if t_out given) so a captured
  * single-step graph can be replayed; ib_counter_add advances the counter. */

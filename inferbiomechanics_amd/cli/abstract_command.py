@@ -128,6 +128,8 @@ class AbstractCommand:
                  for k, v in checkpoint['ema_state_dict' if use_ema else 'model_state_dict'].items()}
         target = model.module if hasattr(model, 'module') else model
         target.load_state_dict(state)
+        if hasattr(target, 'cond_cols'):                     # denoisers: `train --cond-cols`; older checkpoints have no key
+            target.cond_cols = int(checkpoint.get('cond_cols', 0))
         osd = checkpoint.get('optimizer_state_dict')
         if optimizer is not None and hasattr(optimizer, 'load_optimizer_state_dict'):      # HipTrainer
             if osd is not None:

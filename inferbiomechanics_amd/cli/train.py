@@ -91,6 +91,11 @@ class TrainCommand(AbstractCommand):
                        help='Keep an exponential moving average of the weights with this decay, advanced inside the fused '
                             'optimizer launches and saved in the checkpoints (0 = off; 0.999-0.9999 are usual). '
                             '`analyze --use-ema` / `visualize --use-ema` then load it. Not with --eager.')
+        p.add_argument('--cond-cols', type=int, default=0,
+                       help='[diffusion] Train a denoiser conditioned on the first N columns of every frame: they enter the '
+                            'network clean at every noise level, only the other columns are noised and scored. For label '
+                            'inference N = feat_dim - 30; `analyze` / `visualize` read N from the checkpoint. 0 = '
+                            'unconditional.')
         p.add_argument('--no-ema-warmup', action='store_true',
                        help='Use --ema-decay from the first step (default: min(decay, (1 + step) / (10 + step))).')
 
@@ -105,6 +110,7 @@ class TrainCommand(AbstractCommand):
         diffusion = is_diffusion(model_type)
 
         check_ema_args(args)
+        check_cond_cols(model_type, getattr(args, 'cond_cols', 0))
         if getattr(args, 'seed', None) is not None:
             torch.manual_seed(args.seed)
         geometry = self.ensure_geometry(args.geometry_folder)
@@ -161,8 +167,11 @@ class TrainCommand(AbstractCommand):
             print("No parameters to optimize. Skipping training loop.")
             return False
 
+        cond_cols = getattr(args, 'cond_cols', 0) if diffusion else 0
         if diffusion:
-            train_eval, dev_eval = DiffusionLossEvaluator('train'), DiffusionLossEvaluator(DEV)
+            check_cond_cols(model_type, cond_cols, feat_dim=model.feat_dim)
+            model.cond_cols = cond_cols
+            train_eval, dev_eval = DiffusionLossEvaluator('train', cond_cols), DiffusionLossEvaluator(DEV, cond_cols)
         else:
             train_eval = RegressionLossEvaluator(dataset=train_dataset, split='train', device=device)
             dev_eval = RegressionLossEvaluator(dataset=dev_dataset, split=DEV, device=device)
@@ -178,7 +187,7 @@ class TrainCommand(AbstractCommand):
             trainer = HipTrainer(model, "diffusion" if diffusion else "regression", args.opt_type, args.learning_rate,
                                  args=args, use_graph=not args.no_graph, bucket_mb=args.bucket_mb,
                                  ema_decay=getattr(args, 'ema_decay', 0.0),
-                                 ema_warmup=not getattr(args, 'no_ema_warmup', False))
+                                 ema_warmup=not getattr(args, 'no_ema_warmup', False), cond_cols=cond_cols)
 
         if getattr(args, 'loss_every', 1) < 1:
             raise SystemExit("--loss-every must be >= 1")
@@ -227,6 +236,9 @@ class TrainCommand(AbstractCommand):
 
         epoch_checkpoint, _ = self.load_latest_checkpoint(model, optimizer=trainer if trainer is not None else optimizer,
                                                           checkpoint_dir=checkpoint_dir)
+        if diffusion and model.cond_cols != cond_cols:       # the checkpoint's value: a resumed run keeps training that model
+            raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained with --cond-cols {model.cond_cols}, this run "
+                             f"asks for {cond_cols}: resume with the same value or use another --checkpoint-dir")
         from .. import hip
         noise_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
 
@@ -244,6 +256,13 @@ class TrainCommand(AbstractCommand):
                                num_train_steps=model.num_train_steps)
             return xd, td, ed
 
+        def noise_batch(xd, ed, td, tabs, xt):
+            """x_t of the dev-set evaluation and the --eager loop: conditioning columns clean when --cond-cols N > 0"""
+            if cond_cols:
+                hip.q_sample_cond(xd, ed, td, tabs.sqrt_ab, tabs.sqrt_1mab, xt, cond_cols)
+            else:
+                hip.q_sample(xd, ed, td, tabs.sqrt_ab, tabs.sqrt_1mab, xt)
+
         adopted = False
         prev_stream = None
         for epoch in range(epoch_checkpoint + 1, args.epochs):
@@ -257,7 +276,7 @@ class TrainCommand(AbstractCommand):
                         xd, td, ed = device_batch(batch, 0x80000000 | rank, i)   # the same noise before every epoch
                         tabs = model.tables(device)
                         xt = torch.empty_like(xd)
-                        hip.q_sample(xd, ed, td, tabs.sqrt_ab, tabs.sqrt_1mab, xt)
+                        noise_batch(xd, ed, td, tabs, xt)
                         dev_eval(model(xt, td), ed)
                     else:
                         inputs, labels, subj, trial = batch
@@ -297,7 +316,7 @@ class TrainCommand(AbstractCommand):
                         tabs = model.tables(device)
                         xd, td, ed = device_batch(batch, rank, epoch * n_batches + i)
                         xt = torch.empty_like(xd)
-                        hip.q_sample(xd, ed, td, tabs.sqrt_ab, tabs.sqrt_1mab, xt)
+                        noise_batch(xd, ed, td, tabs, xt)
                         loss = train_eval(ddp_model(xt, td), ed)
                         loss.backward()
                         optimizer.step()
@@ -368,6 +387,16 @@ def check_ema_args(args: argparse.Namespace):
         raise SystemExit("--ema-decay needs the fused trainer: --eager runs torch.optim, which keeps no EMA of the weights")
 
 
+def check_cond_cols(model_type: str, cond_cols: int, feat_dim: int = None):
+    """--cond-cols N: diffusion model types only, N in 0 .. feat_dim - 1 (feat_dim is known once the data set is open)"""
+    if cond_cols and not is_diffusion(model_type):
+        raise SystemExit(f"--cond-cols conditions a diffusion denoiser on its first columns: model type '{model_type}' "
+                         f"has none (diffusion-mlp / diffusion-transformer do)")
+    if cond_cols < 0 or (feat_dim is not None and cond_cols >= feat_dim):
+        hi = "feat_dim - 1" if feat_dim is None else str(feat_dim - 1)
+        raise SystemExit(f"--cond-cols must lie in 0 .. {hi} (at least one column has to stay free), got {cond_cols}")
+
+
 def make_torch_optimizer(opt_type: str, params, lr: float):
     table = {'adagrad': torch.optim.Adagrad, 'adam': torch.optim.Adam, 'sgd': torch.optim.SGD,
              'rmsprop': torch.optim.RMSprop, 'adadelta': torch.optim.Adadelta, 'adamax': torch.optim.Adamax}
@@ -380,13 +409,15 @@ def make_torch_optimizer(opt_type: str, params, lr: float):
 def save_checkpoint(checkpoint_dir: str, epoch: int, batch: int, model, opt):
     """file grammar of train.py:271-278; keys are saved WITHOUT DDP's `module.` prefix.  A trainer with an EMA adds
     'ema_state_dict' (the model's state dict over the EMA weights) and 'ema' ({'decay', 'warmup'}); without one the file
-    holds the three reference keys only"""
+    holds the three reference keys only.  A denoiser trained with --cond-cols N > 0 adds 'cond_cols': N."""
     os.makedirs(checkpoint_dir, exist_ok=True)
     path = f"{checkpoint_dir}/epoch_{epoch}_batch_{batch}.pt"
     osd = opt.optimizer_state_dict() if hasattr(opt, 'optimizer_state_dict') else opt.state_dict()
     ckpt = {'epoch': epoch,
             'model_state_dict': {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
             'optimizer_state_dict': osd}
+    if getattr(model, 'cond_cols', 0):
+        ckpt['cond_cols'] = int(model.cond_cols)
     if getattr(opt, 'ema', None) is not None:
         ckpt['ema_state_dict'] = opt.ema_state_dict()
         ckpt['ema'] = {'decay': opt.ema_decay, 'warmup': opt.ema_warmup}

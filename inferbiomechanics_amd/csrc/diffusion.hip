@@ -2,6 +2,8 @@
 // DDPM q_sample, DDIM update (eta = 0, and eta > 0 with the noise term drawn inside the update), the DPM-Solver++(2M) update, table gathers.  The schedule / coefficient / timestep-embedding
 // tables are computed in float64 on the host and cast ONCE to fp32 (bit-exactness target of §8c); these
 // kernels only index them, so noise-schedule and timestep indexing stay bit-exact.
+#include <type_traits>
+
 #include "ib_common.h"
 #include "philox.h"
 
@@ -46,6 +48,18 @@ __device__ __forceinline__ void stv(T* p, const float (&v)[V]) {
   }
 }
 
+// One element of q_sample, a * x + s * e, with its fp32 roundings spelled out.  q_sample_kernel and the free columns of
+// q_sample_cond_kernel both go through it, so the two agree bit for bit however the compiler would contract the bare
+// expression in either kernel.  The forms are those that expression compiled to in q_sample_kernel<T, V> for gfx950 (its
+// ISA is unchanged by the helper): the lone fp32 element sums two rounded products; every other form fuses a * x into the
+// rounded s * e.
+template <typename T, int V>
+__device__ __forceinline__ float q_mix(float a, float x, float s, float e) {
+#pragma clang fp contract(off)
+  if constexpr (V == 1 && sizeof(T) == 4) return a * x + s * e;
+  else return __builtin_fmaf(a, x, s * e);
+}
+
 // rows = B*T tokens, cols = D features; 4 consecutive columns per thread (8 B bf16 / 16 B fp32).  x_t may have a
 // padded leading dimension (the trainer keeps D = 300 activations at ld = 304 so every row starts 16-byte aligned).
 template <typename T, int V>
@@ -67,15 +81,62 @@ __global__ void q_sample_kernel(const T* __restrict__ x0, const T* __restrict__ 
         for (int j = 0; j < 4; ++j) { x[j] = (float)tx[j]; e[j] = (float)te[j]; }
         bf16x4_t o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (bf16_t)(a * x[j] + s * e[j]);
+        for (int j = 0; j < 4; ++j) o[j] = (bf16_t)q_mix<T, 4>(a, x[j], s, e[j]);
         *reinterpret_cast<bf16x4_t*>(xt + r * ld_xt + c) = o;
       } else {
         const float4 tx = *reinterpret_cast<const float4*>(x0 + r * cols + c), te = *reinterpret_cast<const float4*>(eps + r * cols + c);
         *reinterpret_cast<float4*>(xt + r * ld_xt + c) =
-            make_float4(a * tx.x + s * te.x, a * tx.y + s * te.y, a * tx.z + s * te.z, a * tx.w + s * te.w);
+            make_float4(q_mix<T, 4>(a, tx.x, s, te.x), q_mix<T, 4>(a, tx.y, s, te.y), q_mix<T, 4>(a, tx.z, s, te.z),
+                        q_mix<T, 4>(a, tx.w, s, te.w));
       }
     } else {
-      xt[r * ld_xt + c] = ib_from_f32<T>(a * ib_to_f32(x0[r * cols + c]) + s * ib_to_f32(eps[r * cols + c]));
+      xt[r * ld_xt + c] = ib_from_f32<T>(q_mix<T, 1>(a, ib_to_f32(x0[r * cols + c]), s, ib_to_f32(eps[r * cols + c])));
+    }
+  }
+}
+
+// q_sample for a denoiser conditioned on the first C columns of every row (0 < C < cols): those columns reach x_t as they
+// are (a copy of x0's bits, no arithmetic), the free columns c >= C are q_sample_kernel's.  Same geometry as that kernel.
+// A vector inside the conditioning range moves x0 only (eps is not read); the one vector that straddles C (D = 300,
+// C = 270: columns 268 .. 271) loads both and chooses per element.
+template <typename T, int V>
+__global__ void q_sample_cond_kernel(const T* __restrict__ x0, const T* __restrict__ eps, const int64_t* __restrict__ t,
+                                     const float* __restrict__ sqrt_ab, const float* __restrict__ sqrt_1mab,
+                                     T* __restrict__ xt, int64_t ld_xt, int64_t rows, int64_t rows_per_window, int64_t cols,
+                                     int64_t table_rows, int64_t C) {
+  const int64_t cv = cols / V;
+  const int64_t n = rows * cv;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / cv, c = (i % cv) * V;
+    if constexpr (V == 4) {
+      using VT = typename std::conditional<sizeof(T) == 2, bf16x4_t, float4>::type;
+      const VT tx = *reinterpret_cast<const VT*>(x0 + r * cols + c);
+      if (c + 4 <= C) {                                // conditioning only
+        *reinterpret_cast<VT*>(xt + r * ld_xt + c) = tx;
+        continue;
+      }
+      int64_t k = t[r / rows_per_window];
+      k = k < 0 ? 0 : (k >= table_rows ? table_rows - 1 : k);
+      const float a = sqrt_ab[k], s = sqrt_1mab[k];
+      const VT te = *reinterpret_cast<const VT*>(eps + r * cols + c);
+      if constexpr (sizeof(T) == 2) {
+        bf16x4_t o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (c + j < C) ? tx[j] : (bf16_t)q_mix<T, 4>(a, (float)tx[j], s, (float)te[j]);
+        *reinterpret_cast<bf16x4_t*>(xt + r * ld_xt + c) = o;
+      } else {
+        const float x[4] = {tx.x, tx.y, tx.z, tx.w}, e[4] = {te.x, te.y, te.z, te.w};
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (c + j < C) ? x[j] : q_mix<T, 4>(a, x[j], s, e[j]);
+        *reinterpret_cast<float4*>(xt + r * ld_xt + c) = make_float4(o[0], o[1], o[2], o[3]);
+      }
+    } else {
+      const T x = x0[r * cols + c];
+      if (c < C) { xt[r * ld_xt + c] = x; continue; }
+      int64_t k = t[r / rows_per_window];
+      k = k < 0 ? 0 : (k >= table_rows ? table_rows - 1 : k);
+      xt[r * ld_xt + c] = ib_from_f32<T>(q_mix<T, 1>(sqrt_ab[k], ib_to_f32(x), sqrt_1mab[k], ib_to_f32(eps[r * cols + c])));
     }
   }
 }
@@ -613,6 +674,33 @@ extern "C" int ib_q_sample(const void* x0, const void* eps, const int64_t* t, co
     if (v4) hipLaunchKernelGGL((q_sample_kernel<bf16_t, 4>), dim3(grid), dim3(256), 0, s, (const bf16_t*)x0, (const bf16_t*)eps, t, sqrt_ab, sqrt_1mab, (bf16_t*)x_t, ld_xt, rows, T, D, table_rows);
     else hipLaunchKernelGGL((q_sample_kernel<bf16_t, 1>), dim3(grid), dim3(256), 0, s, (const bf16_t*)x0, (const bf16_t*)eps, t, sqrt_ab, sqrt_1mab, (bf16_t*)x_t, ld_xt, rows, T, D, table_rows);
   } else return IB_E_DTYPE;
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+extern "C" int ib_q_sample_cond(const void* x0, const void* eps, const int64_t* t, const float* sqrt_ab,
+                                const float* sqrt_1mab, void* x_t, int64_t ld_xt, int64_t B, int64_t T, int64_t D,
+                                int64_t table_rows, int64_t cond_cols, int dtype, ib_stream_t stream) {
+  if (cond_cols < 0 || cond_cols >= D) return IB_E_ARG;
+  if (cond_cols == 0)                                  // no conditioning columns: ib_q_sample's own launch
+    return ib_q_sample(x0, eps, t, sqrt_ab, sqrt_1mab, x_t, ld_xt, B, T, D, table_rows, dtype, stream);
+  if (!x0 || !eps || !t || !sqrt_ab || !sqrt_1mab || !x_t || B <= 0 || T <= 0 || D <= 0 || table_rows <= 0 || ld_xt < D)
+    return IB_E_ARG;
+  const int es = dtype == IB_BF16 ? 2 : 4;
+  auto al = [&](const void* q) { return (reinterpret_cast<uintptr_t>(q) % (4 * es)) == 0; };
+  const bool v4 = (D % 4 == 0) && (ld_xt % 4 == 0) && al(x0) && al(eps) && al(x_t);      // ib_q_sample's choice
+  const int64_t rows = B * T;
+  const int grid = ib_grid_1d(rows * D / (v4 ? 4 : 1), 256);
+  hipStream_t s = ib_s(stream);
+#define IB_QS_COND(TY, V)                                                                                                     \
+  hipLaunchKernelGGL((q_sample_cond_kernel<TY, V>), dim3(grid), dim3(256), 0, s, (const TY*)x0, (const TY*)eps, t, sqrt_ab,   \
+                     sqrt_1mab, (TY*)x_t, ld_xt, rows, T, D, table_rows, cond_cols)
+  if (dtype == IB_F32) {
+    if (v4) IB_QS_COND(float, 4); else IB_QS_COND(float, 1);
+  } else if (dtype == IB_BF16) {
+    if (v4) IB_QS_COND(bf16_t, 4); else IB_QS_COND(bf16_t, 1);
+  } else return IB_E_DTYPE;
+#undef IB_QS_COND
   IB_CHECK_LAUNCH();
   return IB_OK;
 }

@@ -258,6 +258,67 @@ __global__ void mse_final_kernel(const float* __restrict__ partial, int nparts, 
   if (threadIdx.x == 0) result[0] = red[0] * inv_n;
 }
 
+// mse_partial_kernel for a denoiser conditioned on the first C columns of every row (0 < C < cols): only the free columns
+// c >= C are scored -- gscale = 2 / (rows (cols - C)) -- and dpred is written as exact 0 on the conditioning columns on
+// every launch (the trainer reuses the buffer and nothing else clears it).  Same geometry and the same fixed order of the
+// sums as that kernel.  A vector inside the conditioning range loads nothing; the one that straddles C chooses per element.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void mse_partial_cond_kernel(const T* __restrict__ pred, int64_t ld_pred,
+                                                               const T* __restrict__ target, T* __restrict__ dpred,
+                                                               int64_t ld_dpred, float* __restrict__ partial, int64_t rows,
+                                                               int64_t cols, int64_t C, float gscale) {
+  __shared__ float red[4];
+  float s = 0.f;
+  const int64_t cv = cols / V;
+  const int64_t n = rows * cv;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / cv, c = (i % cv) * V;
+    float d[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) d[e] = 0.f;
+    if (c + V > C) {                                   // at least one free column
+      float a[V], b[V];
+      if constexpr (V == 4) {
+        if constexpr (sizeof(T) == 2) {
+          const bf16x4_t ta = *reinterpret_cast<const bf16x4_t*>(pred + r * ld_pred + c), tb = *reinterpret_cast<const bf16x4_t*>(target + r * cols + c);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { a[e] = (float)ta[e]; b[e] = (float)tb[e]; }
+        } else {
+          const float4 ta = *reinterpret_cast<const float4*>(pred + r * ld_pred + c), tb = *reinterpret_cast<const float4*>(target + r * cols + c);
+          a[0] = ta.x; a[1] = ta.y; a[2] = ta.z; a[3] = ta.w; b[0] = tb.x; b[1] = tb.y; b[2] = tb.z; b[3] = tb.w;
+        }
+      } else {
+        a[0] = ib_to_f32(pred[r * ld_pred + c]); b[0] = ib_to_f32(target[r * cols + c]);
+      }
+#pragma unroll
+      for (int e = 0; e < V; ++e)
+        if (c + e >= C) {
+          const float q = a[e] - b[e];
+          s = __builtin_fmaf(q, q, s);
+          d[e] = q * gscale;
+        }
+    }
+    if (dpred) {
+      if constexpr (V == 4) {
+        if constexpr (sizeof(T) == 2) {
+          bf16x4_t o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = (bf16_t)d[e];
+          *reinterpret_cast<bf16x4_t*>(dpred + r * ld_dpred + c) = o;
+        } else {
+          *reinterpret_cast<float4*>(dpred + r * ld_dpred + c) = make_float4(d[0], d[1], d[2], d[3]);
+        }
+      } else {
+        dpred[r * ld_dpred + c] = ib_from_f32<T>(d[0]);
+      }
+    }
+  }
+  s = ib_wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 int rl_parts(int64_t rows) { return ib_grid_1d(rows, 256, 256); }
 int mse_parts(int64_t n) { return ib_grid_1d(n, 256 * 8, 1024); }
 
@@ -358,6 +419,48 @@ extern "C" int ib_mse_loss_finalize(const void* workspace, size_t workspace_byte
   if (workspace_bytes < (size_t)parts * sizeof(float)) return IB_E_WORKSPACE;
   hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, ib_s(stream), reinterpret_cast<const float*>(workspace),
                      parts, result, 1.f / (float)n);
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+extern "C" int ib_mse_loss_partial_cond(const void* pred, int64_t ld_pred, const void* target, void* dpred,
+                                        int64_t ld_dpred, void* workspace, size_t workspace_bytes, int64_t rows,
+                                        int64_t cols, int64_t cond_cols, int dtype, ib_stream_t stream) {
+  if (cond_cols < 0 || cond_cols >= cols) return IB_E_ARG;
+  if (cond_cols == 0)                                  // no conditioning columns: ib_mse_loss_partial's own launch
+    return ib_mse_loss_partial(pred, ld_pred, target, dpred, ld_dpred, workspace, workspace_bytes, rows, cols, dtype, stream);
+  if (!pred || !target || rows <= 0 || cols <= 0 || ld_pred < cols || (dpred && ld_dpred < cols)) return IB_E_ARG;
+  const int parts = mse_parts(rows * cols);            // the launch covers every column: the conditioning ones get dpred = 0
+  if (!workspace || workspace_bytes < (size_t)parts * sizeof(float)) return IB_E_WORKSPACE;
+  float* partial = reinterpret_cast<float*>(workspace);
+  hipStream_t s = ib_s(stream);
+  const float gscale = 2.f / (float)(rows * (cols - cond_cols));
+  const int es = dtype == IB_BF16 ? 2 : 4;
+  auto al = [&](const void* q) { return !q || (reinterpret_cast<uintptr_t>(q) % (4 * es)) == 0; };
+  const bool v4 = (cols % 4 == 0) && (ld_pred % 4 == 0) && (!dpred || ld_dpred % 4 == 0) && al(pred) && al(target) && al(dpred);
+#define IB_MSE_COND(TY, V)                                                                                                    \
+  hipLaunchKernelGGL((mse_partial_cond_kernel<TY, V>), dim3(parts), dim3(256), 0, s, (const TY*)pred, ld_pred,                \
+                     (const TY*)target, (TY*)dpred, ld_dpred, partial, rows, cols, cond_cols, gscale)
+  if (dtype == IB_F32) {
+    if (v4) IB_MSE_COND(float, 4); else IB_MSE_COND(float, 1);
+  } else if (dtype == IB_BF16) {
+    if (v4) IB_MSE_COND(bf16_t, 4); else IB_MSE_COND(bf16_t, 1);
+  } else
+    return IB_E_DTYPE;
+#undef IB_MSE_COND
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+// n_launch = rows * cols fixes the number of partials (the geometry of the launch), n_mean = rows * (cols - cond_cols) the
+// mean's denominator; n_mean == n_launch is ib_mse_loss_finalize
+extern "C" int ib_mse_loss_finalize_cond(const void* workspace, size_t workspace_bytes, float* result, int64_t n_launch,
+                                         int64_t n_mean, ib_stream_t stream) {
+  if (!workspace || !result || n_launch <= 0 || n_mean <= 0 || n_mean > n_launch) return IB_E_ARG;
+  const int parts = mse_parts(n_launch);
+  if (workspace_bytes < (size_t)parts * sizeof(float)) return IB_E_WORKSPACE;
+  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, ib_s(stream), reinterpret_cast<const float*>(workspace),
+                     parts, result, 1.f / (float)n_mean);
   IB_CHECK_LAUNCH();
   return IB_OK;
 }

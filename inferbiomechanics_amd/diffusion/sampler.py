@@ -16,7 +16,7 @@ import torch
 
 from .. import hip
 from ..plans import ParamSource
-from .schedule import SOLVERS, SPACINGS
+from .schedule import OBSERVATIONS, SOLVERS, SPACINGS
 
 
 class DDIMSampler:
@@ -95,6 +95,10 @@ class DDIMSampler:
     def _extra_sig(self, tabs) -> tuple:
         return ()
 
+    def _observations(self) -> Optional[str]:
+        """the kind of observation table the loop reads (schedule.OBSERVATIONS); None: it reads none"""
+        return None
+
     def _begin(self, x, tabs):
         """runs once x holds the start draw, before the first step (a subclass's start state)"""
 
@@ -147,8 +151,9 @@ class DDIMSampler:
         m.sync_shadow()
         dev = m._flat.device
         tabs = m.tables(dev)
-        if not tabs.serves(self.S, self.eta, self.solver, self.spacing):
-            tabs.set_sampler(self.S, self.eta, self.solver, self.spacing)
+        obs = self._observations()
+        if not tabs.serves(self.S, self.eta, self.solver, self.spacing, obs):
+            tabs.set_sampler(self.S, self.eta, self.solver, self.spacing, observations=obs or tabs.observations)
         # the captured step bakes in raw pointers: the model's flat parameter buffer and bf16 shadow (a HipTrainer built
         # after a first sample() re-packs them), the schedule tables (set_sampler() of another sampler re-creates the DDIM
         # tables) -- all of them are part of the signature, so a change re-captures instead of replaying stale pointers
@@ -221,12 +226,47 @@ class ConditionalDDIMSampler(DDIMSampler):
     the observation.  With solver = 'dpmpp2m' the free elements take the DPM-Solver++(2M) update instead and the observed ones
     the same pinned value (ib_dpmpp_cond_step).  Same captured single-step graph as DDIMSampler; only the update launch differs (ib_ddim_cond_step, the same
     launch count per step).  The observation, the draw and the mask live in sampler-owned device buffers that the capture
-    reads, so a new batch of the same shape is copied in and the captured step replayed."""
+    reads, so a new batch of the same shape is copied in and the captured step replayed.
+
+    observations = 'clean' is the loop of a denoiser trained on clean conditioning columns (`train --cond-cols`,
+    model.cond_cols > 0): an observed element IS the observation, in the start state and after every step, so the network
+    sees what it saw in training.  Same launches: the observation table's rows are all (1, 0)
+    (schedule.clean_observation_coefficients).  The mask must then be the first model.cond_cols columns of every frame.
+    The attribute may be changed between calls; the step is captured again."""
 
     def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True, eta: float = 0.0,
-                 seed: Optional[int] = None, solver: str = "ddim", spacing: str = "time"):
+                 seed: Optional[int] = None, solver: str = "ddim", spacing: str = "time", observations: str = "noised"):
         super().__init__(model, num_sample_steps, use_graph, eta, seed, solver, spacing)
+        if observations not in OBSERVATIONS:
+            raise ValueError(f"observations must be one of {OBSERVATIONS}, got {observations!r}")
+        self.observations = observations
         self._cond = None
+        self._mask_ok = None                 # (mask, (version, cond_cols)) of the last mask 'clean' mode accepted
+
+    def _observations(self) -> Optional[str]:
+        if self.observations not in OBSERVATIONS:
+            raise ValueError(f"observations must be one of {OBSERVATIONS}, got {self.observations!r}")
+        return self.observations
+
+    def _check_clean_mask(self, mask: torch.Tensor):
+        """'clean' mode: the model was trained with exactly its first cond_cols columns clean and nothing else"""
+        C = int(getattr(self.model, "cond_cols", 0))
+        T, D = mask.shape
+        if not 0 < C < D:
+            raise ValueError(f"observations='clean' needs a denoiser trained with --cond-cols N, 0 < N < {D}; this model's "
+                             f"cond_cols is {C}")
+        # the verdict is kept per mask tensor (held, so its address is not reused), its version counter and C: a loop that
+        # passes the same mask again compares nothing and, with a device mask, does not wait for the device
+        key = (mask._version, C)
+        if self._mask_ok is not None and self._mask_ok[0] is mask and self._mask_ok[1] == key:
+            return
+        want = torch.zeros((T, D), dtype=torch.bool, device=mask.device)
+        want[:, :C] = True
+        if not torch.equal(mask, want):
+            self._mask_ok = None
+            raise ValueError(f"observations='clean': the mask must mark the first cond_cols = {C} columns of every frame as "
+                             f"observed and no other element (the model was trained on nothing else)")
+        self._mask_ok = (mask, key)
 
     @torch.no_grad()
     def sample(self, x_T: torch.Tensor, observed: torch.Tensor, mask: torch.Tensor,
@@ -239,6 +279,8 @@ class ConditionalDDIMSampler(DDIMSampler):
             raise ValueError(f"observed must be {(B, T, D)} like x_T, got {tuple(observed.shape)}")
         if tuple(mask.shape) != (T, D) or mask.dtype != torch.bool:
             raise ValueError(f"mask must be a [T, D] = {(T, D)} bool tensor, got {tuple(mask.shape)} {mask.dtype}")
+        if self._observations() == "clean":
+            self._check_clean_mask(mask)
         self._cond = (observed, mask)
         try:
             return super().sample(x_T, steps, window_ids)
@@ -253,7 +295,8 @@ class ConditionalDDIMSampler(DDIMSampler):
         return self.sample(self.draw_start(batch, window, feat, seed, draw), observed, mask, steps, window_ids)
 
     def _extra_sig(self, tabs) -> tuple:
-        return (tabs.obs_coef.data_ptr(),)
+        # the table's pointer and its kind: a table made for the other mode may come back at a freed table's address
+        return (tabs.obs_coef.data_ptr(), tabs.observations)
 
     def _extra_buffers(self, B, T, D, Dp, dev, dtype):
         # pitched like the state, pad columns 0 (the mask's pad columns are free, so they stay 0 in x)

@@ -6,7 +6,7 @@ embedding [sin(t w_i), cos(t w_i)], w_i = exp(-ln(1e4) i / half)), cast ONCE to 
 kernels only index the tables, so schedule values and timestep indices are bit-exact.
 """
 import math
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
@@ -34,6 +34,7 @@ def log_snr(num_train_steps: int = 1000) -> torch.Tensor:
 
 SPACINGS = ("time", "logsnr")
 SOLVERS = ("ddim", "dpmpp2m")
+OBSERVATIONS = ("noised", "clean")
 
 
 def sample_timesteps(num_train_steps: int = 1000, num_sample_steps: int = 100, spacing: str = "time") -> torch.Tensor:
@@ -86,6 +87,18 @@ def observation_coefficients(num_train_steps: int = 1000, num_sample_steps: int 
     levels = [ab[ts[0]]] + [ab[ts[i + 1]] if i + 1 < len(ts) else torch.tensor(1.0, dtype=torch.float64)
                             for i in range(len(ts))]
     return torch.stack([torch.stack([torch.sqrt(a), torch.sqrt(1 - a)]) for a in levels])
+
+
+def clean_observation_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100,
+                                   spacing: str = "time") -> torch.Tensor:
+    """[S + 1, 2] float64, every row (1, 0): the observation table of a denoiser trained on clean conditioning columns
+    (`train --cond-cols`).  An observed element is then c_x0 x0 + c_z z = the observation itself in the start state and after
+    every step, through the update kernels the noised table goes through.  Same shape as observation_coefficients (the
+    grid only fixes the row count)."""
+    S = int(sample_timesteps(num_train_steps, num_sample_steps, spacing).numel())
+    out = torch.zeros((S + 1, 2), dtype=torch.float64)
+    out[:, 0] = 1.0
+    return out
 
 
 def _levels(num_train_steps: int, num_sample_steps: int, spacing: str = "time"):
@@ -188,12 +201,18 @@ class DiffusionTables:
         self.sqrt_ab = torch.sqrt(ab).to(torch.float32).to(device)
         self.sqrt_1mab = torch.sqrt(1.0 - ab).to(torch.float32).to(device)
         self.temb = timestep_embedding_table(num_train_steps, temb_dim).to(torch.float32).to(device).contiguous()
+        self.observations = "noised"
         self.set_sampler(num_sample_steps)
         self.device = device
 
-    def set_sampler(self, num_sample_steps: int, eta: float = 0.0, solver: str = "ddim", spacing: str = "time"):
+    def set_sampler(self, num_sample_steps: int, eta: float = 0.0, solver: str = "ddim", spacing: str = "time",
+                    observations: str = "noised"):
         """the sampler's tables for S steps on the `spacing` grid; eta > 0 adds the stochastic loop's (c_x, c_eps, sigma) and
-        (r, q) tables, solver 'dpmpp2m' the second-order multistep solver's (A, E, C, hx, he) table"""
+        (r, q) tables, solver 'dpmpp2m' the second-order multistep solver's (A, E, C, hx, he) table.  observations: what
+        obs_coef holds -- 'noised', the observation forward-noised to each level (observation_coefficients), or 'clean',
+        every row (1, 0) (clean_observation_coefficients: a denoiser trained on clean conditioning columns)"""
+        if observations not in OBSERVATIONS:
+            raise ValueError(f"observations must be one of {OBSERVATIONS}, got {observations!r}")
         if not 0.0 <= float(eta) <= 1.0:
             raise ValueError(f"eta must be in [0, 1], got {eta}")
         if solver not in SOLVERS:
@@ -208,7 +227,9 @@ class DiffusionTables:
         self.num_sample_steps, self.eta, self.solver, self.spacing = num_sample_steps, float(eta), solver, spacing
         self.ddim_t = ddim_t
         self.ddim_coef = ddim_coefficients(N, num_sample_steps, spacing).to(torch.float32).to(dev).contiguous()
-        self.obs_coef = observation_coefficients(N, num_sample_steps, spacing).to(torch.float32).to(dev).contiguous()
+        self.observations = observations
+        obs = clean_observation_coefficients if observations == "clean" else observation_coefficients
+        self.obs_coef = obs(N, num_sample_steps, spacing).to(torch.float32).to(dev).contiguous()
         self.ddim_coef_eta = self.obs_noise_coef = self.dpmpp_coef = None
         if self.eta > 0.0:
             self.ddim_coef_eta = ddim_coefficients_eta(N, num_sample_steps, eta, spacing).to(torch.float32).to(dev).contiguous()
@@ -216,10 +237,13 @@ class DiffusionTables:
         if solver == "dpmpp2m":
             self.dpmpp_coef = dpmpp_coefficients(N, num_sample_steps, spacing).to(torch.float32).to(dev).contiguous()
 
-    def serves(self, num_sample_steps: int, eta: float = 0.0, solver: str = "ddim", spacing: str = "time") -> bool:
+    def serves(self, num_sample_steps: int, eta: float = 0.0, solver: str = "ddim", spacing: str = "time",
+               observations: Optional[str] = None) -> bool:
         """whether the current tables are the ones a loop with these settings reads: the grid (S, spacing) must match; the
-        eta tables only matter to an eta > 0 loop and the solver's table only to 'dpmpp2m'"""
+        eta tables only matter to an eta > 0 loop, the solver's table only to 'dpmpp2m' and the observation table only to a
+        masked loop, which names the kind it reads (None: the loop reads no observation table)"""
         return (self.num_sample_steps == num_sample_steps and self.spacing == spacing
+                and (observations is None or self.observations == observations)
                 and (float(eta) == 0.0 or self.eta == float(eta))
                 and (solver != "dpmpp2m" or self.dpmpp_coef is not None))
 

@@ -270,14 +270,20 @@ class HipTrainer:
 
     def __init__(self, model: HipModule, task: str, opt_type: str = "rmsprop", lr: float = 1e-4, args=None,
                  group=None, bucket_mb: float = 13.0, use_graph: bool = True, overlap_comm: Optional[bool] = None,
-                 ema_decay: float = 0.0, ema_warmup: bool = True):
+                 ema_decay: float = 0.0, ema_warmup: bool = True, cond_cols: int = 0):
         if task not in ("diffusion", "regression"):
             raise ValueError(task)
+        if int(cond_cols) < 0 or (cond_cols and task != "diffusion"):
+            raise ValueError(f"cond_cols must be >= 0 and is a diffusion-task setting, got {cond_cols} for task '{task}'")
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
         if opt_type not in hip.OPT:
             raise ValueError("Invalid optimizer type: " + opt_type)          # train.py:195-197
         self.model, self.task, self.opt_type, self.lr = model, task, opt_type, lr
+        # diffusion: the first cond_cols columns of every frame row are conditioning -- they reach the denoiser clean at every
+        # noise level and are not scored (csrc/diffusion.hip q_sample_cond_kernel, csrc/loss.hip mse_partial_cond_kernel).
+        # 0: the unconditional step, through the entry points it always used.  Checked against D on the first batch.
+        self.cond_cols = int(cond_cols)
         self.group = group
         self.world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
         import os
@@ -457,6 +463,9 @@ class HipTrainer:
             tabs = m.tables(self.device)
             B, T, D = x0.shape
             M = B * T
+            C = self.cond_cols
+            if not 0 <= C < D:
+                raise ValueError(f"cond_cols must lie in [0, {D}) for windows of {D} columns, got {C}")
             if "draw" in st:
                 # the batch is made on the device by ONE launch: x0 gathered out of the HBM window table (or already staged),
                 # t and eps drawn from the counter-based generator keyed by the device-resident step counter -- a replayed
@@ -465,7 +474,7 @@ class HipTrainer:
                 hip.diffusion_draw(self.noise_seed, step_dev=self.step_dev, stream_id=self.noise_stream, eps=eps, t=t,
                                    num_train_steps=m.num_train_steps, table=None if mc is None else mc.table,
                                    idx=st.get("widx"), x0=x0 if mc is not None else None)
-            if hasattr(plan, "chain_ok") and plan.chain_ok(D):
+            if hasattr(plan, "chain_ok") and plan.chain_ok(D, C):
                 plan.fuse_reduce_into_optimizer = not self.ddp and not TU.no_opt_fuse
                 # MLP denoiser, bf16: q_sample + forward + loss + the dgrad chain are ONE launch (csrc/chain.hip)
                 if self._slots is None:
@@ -501,12 +510,20 @@ class HipTrainer:
             xt = plan.buf.get("tr.xt", (M, Dp), dt, zero=True)[:, :D]
             pred = plan.buf.get("tr.pred", (M, Dp), dt, zero=True)[:, :D]
             dpred = plan.buf.get("tr.dpred", (M, Dp), dt, zero=True)[:, :D]
-            hip.q_sample(x0, eps, t, tabs.sqrt_ab, tabs.sqrt_1mab, xt)
+            if C:
+                hip.q_sample_cond(x0, eps, t, tabs.sqrt_ab, tabs.sqrt_1mab, xt, C)
+            else:
+                hip.q_sample(x0, eps, t, tabs.sqrt_ab, tabs.sqrt_1mab, xt)
             plan.forward(xt, t, tabs.temb, P, out=pred, BT=(B, T))
             ws = plan.buf.bytes("tr.mse", hip.mse_loss_workspace_bytes(M * D))
-            hip.mse_loss_partial(pred, eps, ws, dpred=dpred)          # dL/dpred + per-block partial sums
             n = M * D
-            self._br_loss.run(lambda: hip.mse_loss_finalize(ws, self.result, n))   # the scalar: off the chain
+            if C:
+                # free columns only; dpred = 0 on the conditioning columns, rewritten every step
+                hip.mse_loss_partial_cond(pred, eps.view(M, D), ws, C, dpred=dpred)
+                self._br_loss.run(lambda: hip.mse_loss_finalize_cond(ws, self.result, n, M * (D - C)))
+            else:
+                hip.mse_loss_partial(pred, eps, ws, dpred=dpred)          # dL/dpred + per-block partial sums
+                self._br_loss.run(lambda: hip.mse_loss_finalize(ws, self.result, n))   # the scalar: off the chain
             plan.backward(dpred, P, accumulate=False)
             self._br_loss.join()
             P.flush()                                  # buckets completed after the plan's last flush point
@@ -901,6 +918,8 @@ class HipTrainer:
         st = self._stage(batch)
         # model.training is baked into a captured graph (Groundlink / dropout layers choose their launches by it)
         sig = tuple((k, tuple(v.shape)) for k, v in st.items()) + (("training", bool(self.model.training)),)
+        if self.cond_cols:
+            sig += (("cond_cols", self.cond_cols),)     # chooses the step's launches: part of what a captured graph is
         if sig != self._sig:
             self._sig, self._rec, self._warm = sig, None, 0
             self._pinned, self._seen = {}, {}

@@ -99,6 +99,8 @@ _SIGS = {
     "ib_mse_loss": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _i64, _c.c_int, _vp]),
     "ib_mse_loss_partial": (_c.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _sz, _i64, _i64, _c.c_int, _vp]),
     "ib_mse_loss_finalize": (_c.c_int, [_vp, _sz, _vp, _i64, _vp]),
+    "ib_mse_loss_partial_cond": (_c.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _sz, _i64, _i64, _i64, _c.c_int, _vp]),
+    "ib_mse_loss_finalize_cond": (_c.c_int, [_vp, _sz, _vp, _i64, _i64, _vp]),
     "ib_optim_step": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _vp]),
     "ib_optim_step_sources": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _c.c_int, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp]),
@@ -160,6 +162,7 @@ _SIGS = {
     "ib_time_mlp_bwd": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "ib_sum_partials": (_c.c_int, [_vp, _i64, _f32, _vp, _vp]),
     "ib_q_sample": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
+    "ib_q_sample_cond": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
     "ib_ddim_step": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _c.c_int, _vp]),
     "ib_ddim_cond_step": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i64, _i64,
                                      _c.c_int, _vp]),
@@ -1356,6 +1359,46 @@ def mse_loss_finalize(workspace, result, n):
     _check(lib().ib_mse_loss_finalize(_ptr(workspace), wsb, _ptr(result), int(n), stream_ptr()), "ib_mse_loss_finalize")
 
 
+def mse_loss_partial_cond(pred, target, workspace, cond_cols: int, dpred=None):
+    """mse_loss_partial over the free columns of a conditional denoiser: pred / dpred are 2-D [rows, cols] (contiguous or
+    row-padded), the first `cond_cols` columns of every row are conditioning -- not scored, dpred = 0 there.  The workspace
+    is that of rows * cols elements."""
+    dt = pred.dtype
+    rows, cols, ldp = _mat(pred, "pred", dt)            # 2-D: the columns carry the split
+    _req(target, "target", dt)
+    if not target.is_contiguous() or target.numel() != rows * cols:
+        raise HipError("mse_loss: target must be contiguous with rows * cols elements")
+    ldd = 0
+    if dpred is not None:
+        r2, c2, ldd = _mat(dpred, "dpred", dt)
+        if (r2, c2) != (rows, cols):
+            raise HipError("mse_loss: dpred shape mismatch")
+    wsb = workspace.numel() * workspace.element_size()
+    if wsb < mse_loss_workspace_bytes(rows * cols):
+        raise HipError("mse_loss: workspace too small")
+    cond_cols = int(cond_cols)
+    if not 0 <= cond_cols < cols:
+        raise HipError(f"mse_loss_partial_cond: cond_cols must lie in [0, {cols}), got {cond_cols}")
+    if cond_cols == 0 and pred.is_contiguous() and (dpred is None or dpred.is_contiguous()):
+        # no split: mse_loss_partial's view of contiguous operands (one row of rows * cols elements), so that the vector
+        # width it chooses -- and with it the order of the sums -- is the same here
+        rows, cols = 1, rows * cols
+        ldp, ldd = cols, (0 if dpred is None else cols)
+    _check(lib().ib_mse_loss_partial_cond(_ptr(pred), ldp, _ptr(target), _ptr(dpred), ldd, _ptr(workspace), wsb, rows, cols,
+                                          cond_cols, dtype_code(dt), stream_ptr()), "ib_mse_loss_partial_cond")
+
+
+def mse_loss_finalize_cond(workspace, result, n_launch: int, n_mean: int):
+    """n_launch = rows * cols of the partial launch (its partial count), n_mean = rows * (cols - cond_cols)"""
+    _req(result, "result", torch.float32)
+    n_launch, n_mean = int(n_launch), int(n_mean)
+    if not 0 < n_mean <= n_launch:
+        raise HipError(f"mse_loss_finalize_cond: 0 < n_mean <= n_launch required, got {n_mean}, {n_launch}")
+    wsb = workspace.numel() * workspace.element_size()
+    _check(lib().ib_mse_loss_finalize_cond(_ptr(workspace), wsb, _ptr(result), n_launch, n_mean, stream_ptr()),
+           "ib_mse_loss_finalize_cond")
+
+
 # --------------------------------------------------------------------------------------------
 # optimizer
 # --------------------------------------------------------------------------------------------
@@ -1901,8 +1944,8 @@ def philox_words(out, seed: int, step: int, stream_id: int, domain: int):
                                  int(stream_id) & 0xFFFFFFFF, int(domain), stream_ptr()), "ib_philox_words")
 
 
-def q_sample(x0, eps, t, sqrt_ab, sqrt_1mab, x_t):
-    """x0 / eps: contiguous [B,T,D]; x_t: contiguous [B,T,D] or a row-padded 2-D [B*T, D] view"""
+def _q_sample_args(x0, eps, t, sqrt_ab, sqrt_1mab, x_t):
+    """shape / stride checks shared by q_sample and q_sample_cond -> (B, T, D, ld, dtype)"""
     dt = x0.dtype
     for a, n in ((x0, "x0"), (eps, "eps")):
         _req(a, n, dt, 3)
@@ -1923,8 +1966,26 @@ def q_sample(x0, eps, t, sqrt_ab, sqrt_1mab, x_t):
         raise HipError("t must be int64 [B]")
     _req(sqrt_ab, "sqrt_ab", torch.float32, 1)
     _req(sqrt_1mab, "sqrt_1mab", torch.float32, 1)
+    return B, T, D, ld, dt
+
+
+def q_sample(x0, eps, t, sqrt_ab, sqrt_1mab, x_t):
+    """x0 / eps: contiguous [B,T,D]; x_t: contiguous [B,T,D] or a row-padded 2-D [B*T, D] view"""
+    B, T, D, ld, dt = _q_sample_args(x0, eps, t, sqrt_ab, sqrt_1mab, x_t)
     _check(lib().ib_q_sample(_ptr(x0), _ptr(eps), _ptr(t), _ptr(sqrt_ab), _ptr(sqrt_1mab), _ptr(x_t), ld, B, T, D,
                              sqrt_ab.numel(), dtype_code(dt), stream_ptr()), "ib_q_sample")
+    return x_t
+
+
+def q_sample_cond(x0, eps, t, sqrt_ab, sqrt_1mab, x_t, cond_cols: int):
+    """q_sample for a denoiser conditioned on the first `cond_cols` columns of every frame: x_t[..., :cond_cols] is x0's
+    (copied clean), x_t[..., cond_cols:] is q_sample's.  Tensors as for q_sample."""
+    B, T, D, ld, dt = _q_sample_args(x0, eps, t, sqrt_ab, sqrt_1mab, x_t)
+    cond_cols = int(cond_cols)
+    if not 0 <= cond_cols < D:
+        raise HipError(f"q_sample_cond: cond_cols must lie in [0, {D}), got {cond_cols}")
+    _check(lib().ib_q_sample_cond(_ptr(x0), _ptr(eps), _ptr(t), _ptr(sqrt_ab), _ptr(sqrt_1mab), _ptr(x_t), ld, B, T, D,
+                                  sqrt_ab.numel(), cond_cols, dtype_code(dt), stream_ptr()), "ib_q_sample_cond")
     return x_t
 
 

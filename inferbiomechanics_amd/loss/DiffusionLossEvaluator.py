@@ -39,14 +39,51 @@ class _MSEFn(torch.autograd.Function):
         return hip.scale_by_device_scalar(ctx.dpred, _as_f32_scalar(dloss)), None
 
 
+class _CondMSEFn(torch.autograd.Function):
+    """_MSEFn over the free columns of a conditional denoiser: the mean runs over [..., cond_cols:], the gradient is 0 on
+    the conditioning columns (csrc/loss.hip, mse_partial_cond_kernel)"""
+
+    @staticmethod
+    def forward(ctx, pred, target, cond_cols):
+        D = pred.shape[-1]
+        rows = pred.numel() // D
+        result = torch.zeros(1, dtype=torch.float32, device=pred.device)
+        ws = torch.empty(hip.mse_loss_workspace_bytes(rows * D), dtype=torch.uint8, device=pred.device)
+        dpred = torch.empty_like(pred) if pred.requires_grad else None
+        hip.mse_loss_partial_cond(pred.view(rows, D), target, ws, cond_cols,
+                                  dpred=None if dpred is None else dpred.view(rows, D))
+        hip.mse_loss_finalize_cond(ws, result, rows * D, rows * (D - cond_cols))
+        ctx.dpred = dpred
+        return result[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        if ctx.dpred is None:
+            return None, None, None
+        if getattr(ctx, "consumed", False):          # the consume-once rule of _MSEFn
+            raise RuntimeError("eps-MSE loss: backward was already run on this graph; its gradient buffer is scaled in "
+                               "place and cannot be reused (call the evaluator again for a second backward)")
+        ctx.consumed = True
+        return hip.scale_by_device_scalar(ctx.dpred, _as_f32_scalar(dloss)), None, None
+
+
 class DiffusionLossEvaluator:
-    def __init__(self, split: str = 'train'):
-        self.split = split
+    def __init__(self, split: str = 'train', cond_cols: int = 0):
+        """cond_cols > 0: the loss of a denoiser conditioned on the first cond_cols columns of every frame -- the mean over
+        the other columns only"""
+        if int(cond_cols) < 0:
+            raise ValueError(f"cond_cols must be >= 0, got {cond_cols}")
+        self.split, self.cond_cols = split, int(cond_cols)
         self.losses: List[torch.Tensor] = []
 
     def __call__(self, eps_pred: torch.Tensor, eps: torch.Tensor) -> torch.Tensor:
         eps = eps.to(device=eps_pred.device, dtype=eps_pred.dtype).contiguous()
-        loss = _MSEFn.apply(eps_pred.contiguous(), eps)
+        if self.cond_cols:
+            if not self.cond_cols < eps_pred.shape[-1]:
+                raise ValueError(f"cond_cols must lie in [0, {eps_pred.shape[-1]}), got {self.cond_cols}")
+            loss = _CondMSEFn.apply(eps_pred.contiguous(), eps, self.cond_cols)
+        else:
+            loss = _MSEFn.apply(eps_pred.contiguous(), eps)
         self.losses.append(loss.detach())
         return loss
 

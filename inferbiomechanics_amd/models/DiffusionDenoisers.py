@@ -20,6 +20,10 @@ class _DenoiserBase(HipModule):
     def __init__(self, compute_dtype, temb_dim, num_train_steps):
         super().__init__(compute_dtype)
         self.temb_dim, self.num_train_steps = temb_dim, num_train_steps
+        # the first cond_cols columns of every frame are conditioning: the model was trained with them clean at every noise
+        # level and scored on the other columns only (`train --cond-cols`; saved in the checkpoint).  0: unconditional.  Not a
+        # parameter of the network -- the trainer, the loss evaluator and the sampler read it.
+        self.cond_cols = 0
         self._tables = None
         self._plan = None
 

@@ -33,7 +33,9 @@ class DiffusionLabelPredictor:
     window i = draw + b is replicated K times inside the sampler batch (B K rows); member k has window id i K + k for both its
     start draw and its step noise (eta > 0), the outputs are the members' mean and ``last_std`` their unbiased standard
     deviation, in the same four-key layout (None on the default eta = 0, K = 1 path, which is the single deterministic
-    trajectory).  solver / spacing choose the sampler's update and grid (diffusion/sampler.py)."""
+    trajectory).  solver / spacing choose the sampler's update and grid (diffusion/sampler.py).  A denoiser trained on
+    clean conditioning columns (model.cond_cols > 0, `train --cond-cols`; it must be feat_dim - 30) gets its observations
+    pinned clean at every step (ConditionalDDIMSampler, observations = 'clean'); at 0 they are forward-noised as before."""
 
     def __init__(self, model, num_sample_steps: int = 100, seed: int = 0, output_data_format: str = 'all_frames',
                  use_graph: bool = True, eta: float = 0.0, num_samples: int = 1, solver: str = 'ddim',
@@ -49,6 +51,12 @@ class DiffusionLabelPredictor:
         self.last_std: Optional[Dict[str, torch.Tensor]] = None
         self.sampler = ConditionalDDIMSampler(model, num_sample_steps, use_graph=use_graph, eta=self.eta, seed=self.seed,
                                               solver=solver, spacing=spacing)
+        self._mask = None                    # label_mask of the last (F, D): one tensor, so the sampler checks it once
+
+    def _label_mask(self, frames: int, feat: int) -> torch.Tensor:
+        if self._mask is None or tuple(self._mask.shape) != (frames, feat):
+            self._mask = label_mask(frames, feat)
+        return self._mask
 
     def member_ids(self, draw: int, batch: int):
         """window ids of the sampler rows of a call: member k of window i = draw + b is i K + k"""
@@ -85,15 +93,20 @@ class DiffusionLabelPredictor:
             raise ValueError(f"a window row has {D} columns but the denoiser was built for feat_dim = {self.model.feat_dim}")
         if getattr(self.model, 'window', F) != F:
             raise ValueError(f"a window has {F} frames but the denoiser was built for window = {self.model.window}")
+        C = int(getattr(self.model, 'cond_cols', 0))
+        if C and C != D - LABEL_WIDTH:
+            raise ValueError(f"the denoiser was trained with cond_cols = {C}; label inference observes the {D - LABEL_WIDTH} "
+                             f"input columns of a {D}-column row, so it needs cond_cols = {D - LABEL_WIDTH} (or 0)")
+        self.sampler.observations = 'clean' if C else 'noised'     # read per call: a checkpoint may be loaded after __init__
         K = self.num_samples
         if K == 1 and self.eta == 0.0:
             z = torch.cat([self.sampler.draw_start(1, F, D, self.seed, draw + b) for b in range(B)])
-            x = self.sampler.sample(z, obs, label_mask(F, D))
+            x = self.sampler.sample(z, obs, self._label_mask(F, D))
             return self.split_labels(x)
         ids = self.member_ids(draw, B)
         z = torch.cat([self.sampler.draw_start(1, F, D, self.seed, i) for i in ids])
         members = obs.unsqueeze(1).expand(B, K, F, D).reshape(B * K, F, D)
-        x = self.sampler.sample(z, members, label_mask(F, D), window_ids=ids)
+        x = self.sampler.sample(z, members, self._label_mask(F, D), window_ids=ids)
         mean, std = hip.ensemble_stats(x.view(B, K, F, D))
         self.last_std = self.split_labels(std)
         return self.split_labels(mean)
