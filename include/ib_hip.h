@@ -684,7 +684,10 @@ enum {
   IB_PATH_FFN_CHAIN = 14,   /* ffn_chain.hip: fused feed-forward sublayer (Linear + ReLU + Linear + residual + LayerNorm) */
   IB_PATH_LINLN_PANEL = 15, /* linln_panel.hip: Linear + residual + LayerNorm over row panels, one launch (sampler) */
   IB_PATH_FFN_INFER = 16,   /* linln_panel.hip: feed-forward sublayer, panels shared by their hidden chunks (sampler) */
-  IB_PATH_LIN_PANEL = 17    /* linln_panel.hip: Linear over (row panel, 512-column chunk) workgroups (sampler in-projection) */
+  IB_PATH_LIN_PANEL = 17,   /* linln_panel.hip: Linear over (row panel, 512-column chunk) workgroups (sampler in-projection) */
+  IB_PATH_ATTN_VALU = 18,   /* attention.hip: exact-fp32 VALU attention core, forward or backward (fp32, or bf16 outside the MFMA domain) */
+  IB_PATH_ATTN_MFMA = 19,   /* attention_mfma.hip: bf16 MFMA attention core, one-pass forward or the backward */
+  IB_PATH_ATTN_MFMA_2P = 20 /* attention_mfma.hip: bf16 MFMA forward, eight-wave two-pass kernel (long windows on a full chip) */
 };
 int ib_debug_last_path(void);
 int ib_selftest_tr16(const void* in_bf16_64x16, void* out_bf16_64x4, ib_stream_t stream);

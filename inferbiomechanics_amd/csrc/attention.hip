@@ -242,6 +242,7 @@ int launch_fwd_valu(const void* qkv, void* out, float* lse, int64_t B, int64_t T
                     float scale, const IbAttnDrop& a, int& cur, hipStream_t s) {
   auto k = attention_fwd_kernel<T, DROP>;
   if (ensure_lds(k, lds, cur) != IB_OK) return IB_E_LAUNCH;
+  IB_PATH(IB_PATH_ATTN_VALU);
   hipLaunchKernelGGL(k, dim3((unsigned)(B * H)), dim3(256), lds, s, (const T*)qkv, (T*)out, lse, (int)T_, (int)H, (int)dh,
                      scale, a);
   IB_CHECK_LAUNCH();
@@ -252,6 +253,7 @@ int launch_bwd_valu(const void* qkv, const void* out, const void* dout, const fl
                     int64_t H, int64_t dh, size_t lds, float scale, const IbAttnDrop& a, int& cur, hipStream_t s) {
   auto k = attention_bwd_kernel<T, DROP>;
   if (ensure_lds(k, lds, cur) != IB_OK) return IB_E_LAUNCH;
+  IB_PATH(IB_PATH_ATTN_VALU);
   hipLaunchKernelGGL(k, dim3((unsigned)(B * H)), dim3(256), lds, s, (const T*)qkv, (const T*)out, (const T*)dout, lse,
                      (T*)dqkv, (int)T_, (int)H, (int)dh, scale, a);
   IB_CHECK_LAUNCH();

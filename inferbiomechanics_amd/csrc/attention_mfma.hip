@@ -426,6 +426,7 @@ int launch_fwd2(const void* qkv, void* out, float* lse, int64_t B, int64_t T, in
   if (NT > 4 && !one_pass && B * H * ((T + 127) / 128) >= 256) {
     auto k2 = attn_fwd_mfma_2p<NT, DROP>;
     if (ensure_lds(k2, lds, g_lds_f2[DROP][slot]) != IB_OK) return IB_E_LAUNCH;
+    IB_PATH(IB_PATH_ATTN_MFMA_2P);
     const int groups8 = (int)((T + 127) / 128);                // groups of eight query blocks (one per wave)
     int qs = 1;
     if (B * H < 256) qs = (int)std::min<int64_t>(groups8, std::max<int64_t>(1, 256 / (B * H)));
@@ -436,6 +437,7 @@ int launch_fwd2(const void* qkv, void* out, float* lse, int64_t B, int64_t T, in
   }
   auto k = attn_fwd_mfma<NT, DROP>;
   if (ensure_lds(k, lds, g_lds_f[DROP][slot]) != IB_OK) return IB_E_LAUNCH;
+  IB_PATH(IB_PATH_ATTN_MFMA);
   // fewer (window, head) pairs than CUs: split the query blocks of a pair over several workgroups
   const int groups = (int)((T + 63) / 64);                     // groups of four query blocks (one per wave)
   int qsplit = 1;
@@ -457,6 +459,7 @@ int launch_bwd2(const void* qkv, const void* out, const void* dout, const float*
   const size_t lds = (size_t)4 * NT * 16 * LDR * 2 + (size_t)2 * NT * 16 * 4;
   auto k = attn_bwd_mfma<NT, DROP>;
   if (ensure_lds(k, lds, g_lds_b[DROP][slot]) != IB_OK) return IB_E_LAUNCH;
+  IB_PATH(IB_PATH_ATTN_MFMA);
   hipLaunchKernelGGL(k, dim3((unsigned)(B * H)), dim3(256), lds, s, (const bf16_t*)qkv, (const bf16_t*)out,
                      (const bf16_t*)dout, lse, (bf16_t*)dqkv, (int)T, (int)H, scale, a);
   IB_CHECK_LAUNCH();

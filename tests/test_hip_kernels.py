@@ -226,11 +226,15 @@ def test_attention_fwd_bwd(hip, dtype, B, T, H, dh):
     o.backward(dout.double())
     out = torch.empty(B, T, d, dtype=dtype, device=DEV)
     lse = torch.empty(B, H, T, dtype=torch.float32, device=DEV)
+    want = "attn_mfma" if dtype == torch.bfloat16 and dh == 64 else "attn_valu"      # few (window, head) pairs: one-pass
+    hip.lib().ib_debug_last_path()                       # read-and-clear
     hip.attention_fwd(qkv.to(DEV), out, lse, H)
+    assert hip.PATH_NAMES[int(hip.lib().ib_debug_last_path())] == want
     close(out, o, TIGHT[dtype], "attention out")
     close(lse, torch.logsumexp(s, dim=-1), 1e-4 if dtype == torch.float32 else 2e-2, "lse")
     dqkv = torch.empty(B, T, 3 * d, dtype=dtype, device=DEV)
     hip.attention_bwd(qkv.to(DEV), out, dout.to(DEV), lse, dqkv, H)
+    assert hip.PATH_NAMES[int(hip.lib().ib_debug_last_path())] == want
     close(dqkv, q64.grad, 1e-4 if dtype == torch.float32 else 4e-2, "attention dqkv")
 
 
