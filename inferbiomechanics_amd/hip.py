@@ -4,6 +4,9 @@ PyTorch is used here only for device memory and streams: every wrapper takes tor
 shape / dtype / contiguity on the host (a faulting kernel can reset the whole node), and passes raw
 device pointers + sizes + the current HIP stream to the library.  There is NO CPU or eager-PyTorch
 fallback: if the library is missing or a call fails, a ``HipError`` is raised.
+
+The header is the only declaration of the ABI: the ctypes signatures (``_SIGS``) are parsed from it when this
+module is imported, so a new entry point needs its declaration there and its wrapper here, nothing else.
 """
 from __future__ import annotations
 
@@ -36,176 +39,72 @@ _lib = None
 
 _c = ctypes
 _vp, _i64, _i32, _f32, _sz = _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_float, _c.c_size_t
-_SIGS = {
-    "ib_version": (_c.c_int, []),
-    "ib_error_string": (_c.c_char_p, [_c.c_int]),
-    "ib_linear_fwd": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _c.c_int, _vp, _i64, _vp,
-                                 _i64, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_linear_dgrad": (_c.c_int, [_vp, _i64, _vp, _i64, _c.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64,
-                                   _c.c_int, _vp]),
-    "ib_linear_dgrad_wt": (_c.c_int, [_vp, _i64, _vp, _i64, _c.c_int, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64,
-                                      _c.c_int, _vp]),
-    "ib_transpose_multi": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp]),
-    "ib_linear_dgrad_skinny": (_c.c_int, [_vp, _i64, _vp, _i64, _c.c_int, _vp, _i64, _vp, _i64, _vp, _c.c_int, _i64, _i64,
-                                          _i64, _c.c_int, _vp]),
-    "ib_linear_wgrad_bias": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _c.c_int, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_linear_wgrad_workspace": (_sz, [_i64, _i64, _i64]),
-    "ib_linear_wgrad": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _c.c_int, _vp, _sz, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_linear_ln_fwd_workspace": (_sz, [_i64, _i64, _i64]),
-    "ib_linear_ln_fwd": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _sz,
-                                    _i64, _i64, _i64, _f32, _c.c_int, _vp]),
-    "ib_linear_ln_panel_workgroups": (_c.c_int, [_i64, _i64, _i64, _vp]),
-    "ib_linear_ln_panel_fwd": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32, _vp]),
-    "ib_linear_panel_workgroups": (_c.c_int, [_i64, _i64, _i64]),
-    "ib_linear_panel_fwd": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "ib_ffn_infer_workspace": (_sz, [_i64, _i64, _i64]),
-    "ib_ffn_infer_workgroups": (_c.c_int, [_i64, _i64, _i64, _vp, _vp]),
-    "ib_ffn_infer_fwd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i64, _i64, _i64, _f32, _vp]),
-    "ib_linear_wgrad_slabs_workspace": (_sz, [_i64, _i64, _i64]),
-    "ib_linear_wgrad_slabs": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _sz, _vp, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_linear_wgrad_slabs_multi": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp]),
-    "ib_linear_wgrad_slabs_multi_bias": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int,
-                                                    _vp]),
-    "ib_slab_reduce_multi": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp]),
-    "ib_step_reduce": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _c.c_int, _vp, _vp, _vp, _vp, _vp,
-                                  _c.c_int, _vp]),
-    "ib_step_reduce_parts": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                        _c.c_int, _vp]),
-    "ib_segment_colsum": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _c.c_int, _c.c_int, _c.c_int, _vp]),
-    "ib_layernorm_bwd_reduce": (_c.c_int, [_vp, _sz, _vp, _vp, _c.c_int, _i64, _i64, _vp]),
-    "ib_layernorm_fwd": (_c.c_int, [_vp, _vp, _c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _f32,
-                                    _c.c_int, _vp]),
-    "ib_layernorm_bwd_workspace": (_sz, [_i64, _i64]),
-    "ib_layernorm_bwd": (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp, _sz,
-                                    _vp, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_attention_fwd": (_c.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_attention_bwd": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_tiny_matmul": (_c.c_int, [_vp, _c.c_int, _i64, _i64, _vp, _c.c_int, _i64, _i64, _vp, _c.c_int, _i64, _c.c_int, _i64, _i64,
-                                  _i64, _vp]),
-    "ib_attention_fwd_drop": (_c.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _c.c_float, _c.c_uint32, _c.c_int32, _vp,
-                                         _c.c_int, _vp]),
-    "ib_attention_bwd_drop": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _c.c_float, _c.c_uint32, _c.c_int32,
-                                         _vp, _c.c_int, _vp]),
-    "ib_attention_drop_mask": (_c.c_int, [_vp, _i64, _i64, _i64, _c.c_float, _c.c_uint32, _c.c_int32, _vp, _vp]),
-    "ib_concat_keys": (_c.c_int, [_vp, _vp, _i32, _vp, _i64, _c.c_int, _vp]),
-    "ib_cast": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_int, _i64, _vp]),
-    "ib_cast2d": (_c.c_int, [_vp, _i64, _c.c_int, _vp, _i64, _c.c_int, _i64, _i64, _vp]),
-    "ib_regression_loss_workspace": (_sz, [_i64, _i64]),
-    "ib_regression_loss": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp,
-                                      _vp, _vp, _vp, _sz, _i64, _i64, _c.c_int, _vp]),
-    "ib_regression_loss_strided": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp,
-                                              _vp, _vp, _vp, _vp, _sz, _i64, _i64, _c.c_int, _vp]),
-    "ib_mse_loss_workspace": (_sz, [_i64]),
-    "ib_mse_loss": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _i64, _c.c_int, _vp]),
-    "ib_mse_loss_partial": (_c.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _sz, _i64, _i64, _c.c_int, _vp]),
-    "ib_mse_loss_finalize": (_c.c_int, [_vp, _sz, _vp, _i64, _vp]),
-    "ib_mse_loss_partial_cond": (_c.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _sz, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_mse_loss_finalize_cond": (_c.c_int, [_vp, _sz, _vp, _i64, _i64, _vp]),
-    "ib_optim_step": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _vp]),
-    "ib_optim_step_sources": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _c.c_int, _vp,
-                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp]),
-    "ib_optim_step_ema": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _f32, _c.c_int,
-                                     _vp]),
-    "ib_optim_step_sources_ema": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _c.c_int,
-                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _f32,
-                                             _c.c_int, _vp]),
-    "ib_im2col_replicate": (_c.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _c.c_int, _c.c_int, _vp]),
-    "ib_col2im_replicate": (_c.c_int, [_vp, _i64, _vp, _c.c_int, _vp, _i64, _i64, _i64, _c.c_int, _c.c_int, _vp]),
-    "ib_dropout": (_c.c_int, [_vp, _vp, _i64, _f32, _c.c_uint32, _i32, _vp, _c.c_int, _vp]),
-    "ib_debug_set_ffn_prof": (_c.c_int, [_vp]),
-    "ib_ffn_chain_supported": (_c.c_int, [_i64, _i64]),
-    "ib_ffn_chain_packed_elems": (_sz, [_i64, _i64]),
-    "ib_ffn_chain_workgroups": (_c.c_int, [_i64, _i64, _i64, _vp]),
-    "ib_ffn_chain_mask_bytes": (_sz, [_i64, _i64, _i64]),
-    "ib_ffn_chain_pack": (_c.c_int, [_vp] * 9 + [_c.c_int, _i64, _i64, _vp]),
-    "ib_ffn_chain_fwd": (_c.c_int, [_vp] * 23 + [_i64, _i64, _i64, _f32, _vp]),
-    "ib_ffn_chain_bwd": (_c.c_int, [_vp] * 20 + [_i64, _i64, _i64, _vp]),
-    "ib_ffn_chain_fwd_infer": (_c.c_int, [_vp] * 14 + [_i64, _i64, _i64, _f32, _vp]),
-    "ib_ffn_chain_attn_workgroups": (_c.c_int, [_i64, _i64, _i64, _i64]),
-    "ib_ffn_chain_attn_mask_bytes": (_sz, [_i64, _i64, _i64, _i64]),
-    "ib_ffn_chain_fwd_attn": (_c.c_int, [_vp] * 25 + [_i64, _i64, _i64, _i64, _f32, _vp]),
-    "ib_ffn_chain_bwd_attn": (_c.c_int, [_vp] * 19 + [_i64, _i64, _i64, _i64, _vp]),
-    "ib_sqdiff_mean": (_c.c_int, [_vp, _vp, _vp, _i64, _i64, _c.c_int, _vp]),
-    "ib_sqdiff_mean_bwd": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _c.c_int, _vp]),
-    "ib_mask_by_threes": (_c.c_int, [_vp, _vp, _i64, _f32, _c.c_int, _vp]),
-    "ib_mean_norm_error": (_c.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _c.c_int, _c.c_int, _c.c_int, _vp]),
-    "ib_gather_rows_bwd": (_c.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp]),
-    "ib_diffusion_draw": (_c.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _c.c_uint64, _i32, _vp,
-                                     _c.c_uint32, _c.c_int, _vp]),
-    "ib_philox_words": (_c.c_int, [_vp, _i64, _c.c_uint64, _c.c_uint32, _c.c_uint32, _c.c_uint32, _vp]),
-    "ib_gather_windows": (_c.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _c.c_int, _vp, _vp, _vp]),
-    "ib_gather_rows": (_c.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_mlp_chain_supported": (_c.c_int, [_i64, _i64, _c.c_int]),
-    "ib_mlp_chain_packed_elems": (_sz, [_i64, _i64, _c.c_int]),
-    "ib_mlp_chain_workgroups": (_c.c_int, [_i64, _vp]),
-    "ib_mlp_chain_pack": (_c.c_int, [_vp, _vp, _vp, _i64, _i64, _c.c_int, _vp]),
-    "ib_mlp_chain_partial_width": (_i64, [_i64, _i64, _c.c_int]),
-    "ib_mlp_chain_train": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
-                                      _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _c.c_int,
-                                      _f32, _vp]),
-    "ib_set_ptrs": (_c.c_int, [_vp, _c.c_int, _vp, _vp]),
-    "ib_colsum_segments": (_c.c_int, [_vp, _i64, _i64, _c.c_int, _vp, _vp, _vp, _vp, _vp, _c.c_int, _vp]),
-    "ib_debug_set_chain_prof": (_c.c_int, [_vp]),
-    "ib_debug_set_gemm_prof": (_c.c_int, [_vp]),
-    "ib_debug_set_nt_prof": (_c.c_int, [_vp]),
-    "ib_debug_stamp": (_c.c_int, [_vp, _vp]),
-    "ib_time_mlp_fwd_supported": (_c.c_int, [_i64, _i64, _i64]),
-    "ib_mlp_chain_prep": (_c.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
-                                     _i64, _i64, _vp, _vp, _vp, _i64, _i64, _c.c_int, _vp, _vp]),
-    "ib_time_mlp_fwd": (_c.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
-                                   _i64, _i64, _vp]),
-    "ib_linear_wgrad_slabs_multi_tb": (_c.c_int, [_c.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.c_int,
-                                                  _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "ib_time_mlp_bwd_supported": (_c.c_int, [_i64, _i64, _i64]),
-    "ib_time_mlp_bwd_slab_count": (_c.c_int, [_i64]),
-    "ib_optim_ticket_words": (_c.c_int, []),
-    "ib_time_mlp_bwd": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "ib_sum_partials": (_c.c_int, [_vp, _i64, _f32, _vp, _vp]),
-    "ib_q_sample": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_q_sample_cond": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_ddim_step": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _c.c_int, _vp]),
-    "ib_ddim_cond_step": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i64, _i64,
-                                     _c.c_int, _vp]),
-    "ib_ddim_cond_init": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_ddim_step_noise": (_c.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _c.c_uint64, _i64, _i64, _i64, _i64,
-                                      _c.c_int, _vp]),
-    "ib_ddim_cond_step_noise": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp,
-                                           _c.c_uint64, _i64, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_dpmpp_step": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _c.c_int, _vp]),
-    "ib_dpmpp_cond_step": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _i64,
-                                      _i64, _c.c_int, _vp]),
-    "ib_ensemble_stats": (_c.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _c.c_int, _vp]),
-    "ib_counter_add": (_c.c_int, [_vp, _i32, _vp]),
-    "ib_batchnorm_fwd": (_c.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _f32, _f32, _c.c_int,
-                                    _c.c_int, _vp]),
-    "ib_batchnorm_bwd": (_c.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _c.c_int, _c.c_int, _vp, _i64,
-                                    _i64, _i64, _c.c_int, _c.c_int, _vp]),
-    "ib_scale_by_device_scalar": (_c.c_int, [_vp, _vp, _i64, _c.c_int, _vp]),
-    "ib_fill_i64": (_c.c_int, [_vp, _i64, _i64, _vp]),
-    "ib_graph_begin": (_c.c_int, [_vp]),
-    "ib_graph_end": (_c.c_int, [_vp, _c.POINTER(_vp)]),
-    "ib_graph_launch": (_c.c_int, [_vp, _vp]),
-    "ib_graph_destroy": (_c.c_int, [_vp]),
-    "ib_stream_create": (_c.c_int, [_c.POINTER(_vp)]),
-    "ib_stream_destroy": (_c.c_int, [_vp]),
-    "ib_event_create": (_c.c_int, [_c.POINTER(_vp)]),
-    "ib_event_record": (_c.c_int, [_vp, _vp]),
-    "ib_event_elapsed_ms": (_c.c_int, [_vp, _vp, _c.POINTER(_f32)]),
-    "ib_event_destroy": (_c.c_int, [_vp]),
-    "ib_selftest_tr16": (_c.c_int, [_vp, _vp, _vp]),
-    "ib_debug_set_ablate": (_c.c_int, [_c.c_int]),
-    "ib_debug_last_path": (_c.c_int, []),
-}
+_SCALARS = {"int": _c.c_int, "int32_t": _i32, "int64_t": _i64, "uint32_t": _c.c_uint32, "uint64_t": _c.c_uint64, "float": _f32,
+            "size_t": _sz}
+
+
+def _parse_header(text: str) -> dict:
+    """name -> (restype, [argtypes]) of every `ret ib_name(params);` in a C header.  Every pointer and ib_stream_t is a
+    c_void_p (ctypes takes an int, None, a c_void_p or a byref() there), a `const char*` result a c_char_p, scalars map by
+    _SCALARS.  Whatever it cannot map -- an unknown type, a parameter list with parentheses in it, a name declared twice --
+    raises HipError naming the function and the parameter: a guessed width shifts what the kernel reads as sizes and pointers."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    sigs = {}
+    for statement in re.split(r"[;{}]", text):
+        m = re.match(r"(.*?)\b(ib_[a-z0-9_]+)\s*\((.*)", statement, flags=re.S)
+        if m is None:
+            continue
+        ret, name, params = (g.strip() for g in m.groups())
+        if name in sigs:
+            raise HipError(f"{name} is declared twice")
+        if not params.endswith(")") or "(" in params or ")" in params[:-1]:
+            raise HipError(f"{name}: cannot split the parameter list '({params}'")
+        ret = " ".join(w for w in ret.replace("*", " * ").split() if w != "const")
+        if ret != "char *" and ret not in _SCALARS:
+            raise HipError(f"{name}: unknown return type '{ret}'")
+        args = []
+        for p in ([] if params[:-1].strip() == "void" else params[:-1].split(",")):
+            words = [w for w in p.split() if w != "const"]
+            if "*" in p or words[:1] == ["ib_stream_t"]:
+                args.append(_vp)
+            elif words and words[0] in _SCALARS and (len(words) == 1 or len(words) == 2 and words[1].isidentifier()):
+                args.append(_SCALARS[words[0]])
+            else:
+                raise HipError(f"{name}: unknown type of parameter '{p.strip()}'")
+        sigs[name] = (_c.c_char_p if ret == "char *" else _SCALARS[ret], args)
+    return sigs
+
+
+def _read_header() -> str:
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise HipError(f"the C-ABI header is missing: looked for {HEADER_PATH} ({e.strerror}); the ctypes signatures are "
+                       f"derived from it, so the binding cannot work without it") from None
+
+
+_SIGS = _parse_header(_read_header())
 
 
 def declared_symbols() -> List[str]:
     """Every function the public header declares (used by the CPU test that checks the exports)."""
-    src = open(HEADER_PATH).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(ib_[a-z0-9_]+)\s*\(", src)))
+    return sorted(_SIGS)
 
 
-_HOST_ONLY = ("_workspace", "_supported", "_workgroups", "_packed_elems", "_partial_width", "_last_path", "_slab_count", "_ticket_words", "_mask_bytes")   # pure host queries: no launch, no stream
+# pure host queries: no launch, no stream
+_HOST_ONLY = ("_workspace", "_supported", "_workgroups", "_packed_elems", "_partial_width", "_last_path", "_slab_count",
+              "_ticket_words", "_mask_bytes")
+_HOST_NAMES = ("ib_version", "ib_error_string")
+
+
+def _is_launch(name: str, handed_through=("ib_event", "ib_graph")) -> bool:
+    """The proxies' one test: does a proxy take `name` over (bracket / record / fake it)?  Everything the library exports
+    except the pure host queries and the families in `handed_through`: the event and graph calls are the brackets' own
+    instruments, so a proxy over the live library hands them through."""
+    return name.startswith("ib_") and not name.startswith(tuple(handed_through)) and not name.endswith(_HOST_ONLY) \
+        and name not in _HOST_NAMES
 
 
 class _DryRunLib:
@@ -217,11 +116,12 @@ class _DryRunLib:
         self._real = real
         self.calls = []
         self.ema_ranges = []     # per EMA optimizer launch: (ema pointer, n, [(start, len) of its kind-3 ranges])
+        self.args = []           # per faked call: (name, the arguments as the wrapper passed them)
 
     def __getattr__(self, name):
         res, args = _SIGS[name]
         real = getattr(self._real, name)
-        if name.endswith(_HOST_ONLY) or name in ("ib_version", "ib_error_string"):
+        if not _is_launch(name, handed_through=()):      # nothing but the host queries may reach the real library
             return real
 
         def call(*a):
@@ -231,6 +131,7 @@ class _DryRunLib:
                 if v is not None or t not in (_vp,):
                     t.from_param(v) if hasattr(t, "from_param") else None
             self.calls.append(name)
+            self.args.append((name, a))
             if name == "ib_optim_step_ema":
                 self.ema_ranges.append((a[12], int(a[5]), []))
             elif name == "ib_optim_step_sources_ema":
@@ -252,8 +153,7 @@ class _TimingLib:
 
     def __getattr__(self, name):
         real = getattr(self._real, name)
-        if not name.startswith("ib_") or name.startswith(("ib_event", "ib_graph")) or name.endswith(_HOST_ONLY) \
-                or name in ("ib_version", "ib_error_string"):
+        if not _is_launch(name):
             return real
 
         def call(*a):
@@ -287,8 +187,7 @@ class _RecordingLib:
 
     def __getattr__(self, name):
         real = getattr(self._real, name)
-        if not name.startswith("ib_") or name.startswith(("ib_event", "ib_graph")) or name.endswith(_HOST_ONLY) \
-                or name in ("ib_version", "ib_error_string"):
+        if not _is_launch(name):
             return real
 
         def call(*a):
@@ -323,8 +222,7 @@ class _StampLib:
 
     def __getattr__(self, name):
         real = getattr(self._real, name)
-        if not name.startswith("ib_") or name.startswith(("ib_event", "ib_graph", "ib_debug")) \
-                or name.endswith(_HOST_ONLY) or name in ("ib_version", "ib_error_string") \
+        if not _is_launch(name, handed_through=("ib_event", "ib_graph", "ib_debug")) \
                 or (self.only is not None and name not in self.only):
             return real
 
@@ -349,35 +247,37 @@ class _StampLib:
                 for k in range(n)]
 
 
-class stamp_launches:
+class _proxy_installed:
+    """context-manager base: put `make(the loaded library)` in lib()'s place, yield it, restore the library on exit"""
+    make = None
+
+    def __enter__(self):
+        global _lib
+        self._saved = lib()
+        _lib = self.make(self._saved)
+        return _lib
+
+    def __exit__(self, *exc):
+        global _lib
+        _lib = self._saved
+        return False
+
+
+class stamp_launches(_proxy_installed):
+    """`with hip.stamp_launches(only=names) as sl: ...; sl.timeline()`"""
+
     def __init__(self, only=None):
-        self.only = only
-
-    def __enter__(self):
-        global _lib
-        self._saved = lib()
-        self.lib = _StampLib(self._saved, only=self.only)
-        _lib = self.lib
-        return self.lib
-
-    def __exit__(self, *exc):
-        global _lib
-        _lib = self._saved
-        return False
+        self.make = lambda real: _StampLib(real, only=only)
 
 
-class record_launches:
-    def __enter__(self):
-        global _lib
-        self._saved = lib()
-        self.rec = _RecordingLib(self._saved)
-        _lib = self.rec
-        return self.rec
+class record_launches(_proxy_installed):
+    """`with hip.record_launches() as rec: ...; rec.calls, rec.paths, rec.notes`"""
+    make = _RecordingLib
 
-    def __exit__(self, *exc):
-        global _lib
-        _lib = self._saved
-        return False
+
+class time_launches(_proxy_installed):
+    """`with hip.time_launches() as tl: ...; tl.summary()`"""
+    make = _TimingLib
 
 
 _free_streams: dict = {}          # device index -> handles whose torch wrapper has died: handed out again, never destroyed
@@ -445,22 +345,6 @@ def time_recorded_call(name: str, args, reps: int = 20, rounds: int = 3) -> floa
         ms = e0.elapsed_ms(e1)
     torch.cuda.synchronize()
     return ms * 1e3 / (reps * rounds)
-
-
-class time_launches:
-    """context manager: `with hip.time_launches() as tl: ...; tl.summary()`"""
-
-    def __enter__(self):
-        global _lib
-        self._saved = lib()
-        self.tl = _TimingLib(self._saved)
-        _lib = self.tl
-        return self.tl
-
-    def __exit__(self, *exc):
-        global _lib
-        _lib = self._saved
-        return False
 
 
 _dry_run = False
@@ -2215,41 +2099,60 @@ def sum_partials(partial, parts: int, scale: float, out):
     return out
 
 
-def ddim_step(x, eps, coef, timesteps, step=0, step_dev=None, t_out=None):
-    dt = x.dtype
-    _req(x, "x", dt)
-    _req(eps, "eps", dt)
-    if eps.shape != x.shape or not x.is_contiguous() or not eps.is_contiguous():
-        raise HipError("ddim_step: x/eps must be contiguous with one shape")
-    _req(coef, "coef", torch.float32, 2)
-    _req(timesteps, "timesteps", torch.int64, 1)
-    S = coef.shape[0]
-    if coef.shape[1] != 2 or timesteps.numel() != S or not coef.is_contiguous():
-        raise HipError("coef must be [S,2] fp32, timesteps [S] int64")
-    B = x.shape[0]
-    if t_out is not None:
-        _req(t_out, "t_out", torch.int64, 1)
-        if t_out.numel() != B:
-            raise HipError("t_out must be int64 [B]")
-    _check(lib().ib_ddim_step(_ptr(x), _ptr(eps), _ptr(coef), _ptr(timesteps), S, int(step), _ptr(step_dev),
-                              _ptr(t_out), B, x.numel(), dtype_code(dt), stream_ptr()), "ib_ddim_step")
-    return x
+# ---- sampler updates: one copy of each operand check; `what` is the wrapper that was called
+def _like_x(what, name, t, x, dtype=None):
+    """t is contiguous, shaped like the state x and of `dtype` (default: x's)"""
+    dtype = x.dtype if dtype is None else dtype
+    _req(t, name, dtype)
+    if t.shape != x.shape or not t.is_contiguous():
+        raise HipError(f"{what}: {name} must be contiguous {tuple(x.shape)} {dtype}, like x")
 
 
-def _cond_operands(what, x, x0, z, mask, obs_coef, D):
-    """shared checks of ddim_cond_step / ddim_cond_init -> (B, T, D, ld)"""
-    dt = x.dtype
-    _req(x, "x", dt, 3)
+def _flat_state(what, x):
+    """the state of an element-wise update: contiguous [B, ...] -> B"""
+    _req(x, "x", x.dtype)
+    if x.dim() < 1 or not x.is_contiguous():
+        raise HipError(f"{what}: x must be a contiguous [B, ...] state")
+    return x.shape[0]
+
+
+def _pitched_state(what, x, D):
+    """the state of an update that knows the row pitch: contiguous [B, T, ld], D (default ld) feature columns -> (B, T, D, ld)"""
+    _req(x, "x", x.dtype, 3)
     if not x.is_contiguous():
         raise HipError(f"{what}: x must be a contiguous [B, T, ld] state")
     B, T, ld = x.shape
     D = ld if D is None else int(D)
     if D <= 0 or D > ld:
         raise HipError(f"{what}: D = {D} must be in 1 .. ld = {ld}")
-    for name, t in (("x0", x0), ("z", z)):
-        _req(t, name, dt)
-        if t.shape != x.shape or not t.is_contiguous():
-            raise HipError(f"{what}: {name} must be contiguous {tuple(x.shape)} {dt}, like x")
+    return B, T, D, ld
+
+
+def _step_tables(what, coef, ncols, timesteps, B, t_out, step_dev, obs_coef=None):
+    """the tables and counters every update reads: coef fp32 [S, ncols], timesteps int64 [S], t_out (optional) int64 [B],
+    step_dev (optional) int32 -- the kernel reads it as the int32 row index into coef; obs_coef (masked updates): S + 1 rows.
+    -> S"""
+    _req(coef, "coef", torch.float32, 2)
+    _req(timesteps, "timesteps", torch.int64, 1)
+    S = coef.shape[0]
+    if coef.shape[1] != ncols or timesteps.numel() != S or not coef.is_contiguous():
+        raise HipError(f"{what}: coef must be contiguous [S, {ncols}] fp32, timesteps [S] int64")
+    if t_out is not None:
+        _req(t_out, "t_out", torch.int64, 1)
+        if t_out.numel() != B:
+            raise HipError(f"{what}: t_out must be int64 [B] = [{B}]")
+    if step_dev is not None:
+        _req(step_dev, "step_dev", torch.int32)
+    if obs_coef is not None and obs_coef.shape[0] != S + 1:
+        raise HipError(f"{what}: obs_coef must have S + 1 = {S + 1} rows, got {obs_coef.shape[0]}")
+    return S
+
+
+def _cond_operands(what, x, x0, z, mask, obs_coef, D):
+    """the masked state: x as _pitched_state, x0 / z like x, mask uint8 [T, ld], obs_coef fp32 [., 2] -> (B, T, D, ld)"""
+    B, T, D, ld = _pitched_state(what, x, D)
+    _like_x(what, "x0", x0, x)
+    _like_x(what, "z", z, x)
     _req(mask, "mask", torch.uint8, 2)
     if tuple(mask.shape) != (T, ld) or not mask.is_contiguous():
         raise HipError(f"{what}: mask must be contiguous uint8 [T, ld] = [{T}, {ld}], got {tuple(mask.shape)}")
@@ -2259,27 +2162,30 @@ def _cond_operands(what, x, x0, z, mask, obs_coef, D):
     return B, T, D, ld
 
 
+def _win_ids(what, win_id, B):
+    _req(win_id, "win_id", torch.int64, 1)
+    if win_id.numel() != B or not win_id.is_contiguous():
+        raise HipError(f"{what}: win_id must be contiguous int64 [B] = [{B}]")
+
+
+def ddim_step(x, eps, coef, timesteps, step=0, step_dev=None, t_out=None):
+    """x <- coef[s][0] x + coef[s][1] eps in place, coef [S, 2]; s = *step_dev (int32 device counter) or `step`;
+    t_out (optional, int64 [B]) receives the next step's timestep"""
+    B = _flat_state("ddim_step", x)
+    _like_x("ddim_step", "eps", eps, x)
+    S = _step_tables("ddim_step", coef, 2, timesteps, B, t_out, step_dev)
+    _check(lib().ib_ddim_step(_ptr(x), _ptr(eps), _ptr(coef), _ptr(timesteps), S, int(step), _ptr(step_dev),
+                              _ptr(t_out), B, x.numel(), dtype_code(x.dtype), stream_ptr()), "ib_ddim_step")
+    return x
+
+
 def ddim_cond_step(x, eps, x0, z, mask, coef, obs_coef, timesteps, step=0, step_dev=None, t_out=None, D=None):
     """masked DDIM update in place over the state x [B, T, ld] (csrc/diffusion.hip): elements with mask [T, ld] == 0 take the
     ddim_step update from eps, the others obs_coef[s + 1] (x0, z); t_out / step_dev as in ddim_step.  D (default ld): the
     feature columns in front of the row pitch."""
     B, T, D, ld = _cond_operands("ddim_cond_step", x, x0, z, mask, obs_coef, D)
-    _req(eps, "eps", x.dtype)
-    if eps.shape != x.shape or not eps.is_contiguous():
-        raise HipError("ddim_cond_step: eps must be contiguous with the shape of x")
-    _req(coef, "coef", torch.float32, 2)
-    _req(timesteps, "timesteps", torch.int64, 1)
-    S = coef.shape[0]
-    if coef.shape[1] != 2 or timesteps.numel() != S or not coef.is_contiguous():
-        raise HipError("coef must be [S,2] fp32, timesteps [S] int64")
-    if obs_coef.shape[0] != S + 1:
-        raise HipError(f"ddim_cond_step: obs_coef must have S + 1 = {S + 1} rows, got {obs_coef.shape[0]}")
-    if t_out is not None:
-        _req(t_out, "t_out", torch.int64, 1)
-        if t_out.numel() != B:
-            raise HipError("t_out must be int64 [B]")
-    if step_dev is not None:
-        _req(step_dev, "step_dev", torch.int32)
+    _like_x("ddim_cond_step", "eps", eps, x)
+    S = _step_tables("ddim_cond_step", coef, 2, timesteps, B, t_out, step_dev, obs_coef)
     _check(lib().ib_ddim_cond_step(_ptr(x), _ptr(eps), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef),
                                    _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out), B, T, D, ld,
                                    dtype_code(x.dtype), stream_ptr()), "ib_ddim_cond_step")
@@ -2294,40 +2200,14 @@ def ddim_cond_init(x, x0, z, mask, obs_coef, D=None):
     return x
 
 
-def _noise_operands(what, x, coef, timesteps, win_id, t_out, step_dev, D):
-    """shared checks of the stochastic updates -> (B, T, D, ld, S)"""
-    _req(x, "x", x.dtype, 3)
-    if not x.is_contiguous():
-        raise HipError(f"{what}: x must be a contiguous [B, T, ld] state")
-    B, T, ld = x.shape
-    D = ld if D is None else int(D)
-    if D <= 0 or D > ld:
-        raise HipError(f"{what}: D = {D} must be in 1 .. ld = {ld}")
-    _req(coef, "coef", torch.float32, 2)
-    _req(timesteps, "timesteps", torch.int64, 1)
-    S = coef.shape[0]
-    if coef.shape[1] != 3 or timesteps.numel() != S or not coef.is_contiguous():
-        raise HipError(f"{what}: coef must be [S, 3] fp32 (c_x, c_eps, sigma), timesteps [S] int64")
-    _req(win_id, "win_id", torch.int64, 1)
-    if win_id.numel() != B or not win_id.is_contiguous():
-        raise HipError(f"{what}: win_id must be contiguous int64 [B] = [{B}]")
-    if t_out is not None:
-        _req(t_out, "t_out", torch.int64, 1)
-        if t_out.numel() != B:
-            raise HipError("t_out must be int64 [B]")
-    if step_dev is not None:
-        _req(step_dev, "step_dev", torch.int32)
-    return B, T, D, ld, S
-
-
 def ddim_step_noise(x, eps, coef, timesteps, win_id, seed, step=0, step_dev=None, t_out=None, D=None):
     """stochastic DDIM / DDPM update in place over the state x [B, T, ld] (csrc/diffusion.hip): coef [S, 3] = (c_x, c_eps,
     sigma); the noise of window b is keyed by (seed, win_id[b], step, frame, column) and generated inside the kernel.
     D (default ld): the feature columns in front of the row pitch; pad columns get no noise."""
-    B, T, D, ld, S = _noise_operands("ddim_step_noise", x, coef, timesteps, win_id, t_out, step_dev, D)
-    _req(eps, "eps", x.dtype)
-    if eps.shape != x.shape or not eps.is_contiguous():
-        raise HipError("ddim_step_noise: eps must be contiguous with the shape of x")
+    B, T, D, ld = _pitched_state("ddim_step_noise", x, D)
+    _like_x("ddim_step_noise", "eps", eps, x)
+    S = _step_tables("ddim_step_noise", coef, 3, timesteps, B, t_out, step_dev)
+    _win_ids("ddim_step_noise", win_id, B)
     _check(lib().ib_ddim_step_noise(_ptr(x), _ptr(eps), _ptr(coef), _ptr(timesteps), S, int(step), _ptr(step_dev),
                                     _ptr(t_out), _ptr(win_id), int(seed) & 0xFFFFFFFFFFFFFFFF, B, T, D, ld,
                                     dtype_code(x.dtype), stream_ptr()), "ib_ddim_step_noise")
@@ -2338,17 +2218,14 @@ def ddim_cond_step_noise(x, eps, x0, z, mask, coef, obs_coef, obs_noise_coef, ti
                          step_dev=None, t_out=None, D=None):
     """masked stochastic update in place: free elements as ddim_step_noise; observed ones update their stored noise z in
     place (obs_noise_coef [S, 2] = (r, q): z <- r z + q z') and are pinned to obs_coef[s + 1] (x0, z)."""
-    B, T, D, ld = _cond_operands("ddim_cond_step_noise", x, x0, z, mask, obs_coef, D)
-    _noise_operands("ddim_cond_step_noise", x, coef, timesteps, win_id, t_out, step_dev, D)
-    S = coef.shape[0]
-    _req(eps, "eps", x.dtype)
-    if eps.shape != x.shape or not eps.is_contiguous():
-        raise HipError("ddim_cond_step_noise: eps must be contiguous with the shape of x")
-    if obs_coef.shape[0] != S + 1:
-        raise HipError(f"ddim_cond_step_noise: obs_coef must have S + 1 = {S + 1} rows, got {obs_coef.shape[0]}")
+    what = "ddim_cond_step_noise"
+    B, T, D, ld = _cond_operands(what, x, x0, z, mask, obs_coef, D)
+    _like_x(what, "eps", eps, x)
+    S = _step_tables(what, coef, 3, timesteps, B, t_out, step_dev, obs_coef)
+    _win_ids(what, win_id, B)
     _req(obs_noise_coef, "obs_noise_coef", torch.float32, 2)
     if tuple(obs_noise_coef.shape) != (S, 2) or not obs_noise_coef.is_contiguous():
-        raise HipError(f"ddim_cond_step_noise: obs_noise_coef must be contiguous [S, 2] = [{S}, 2] fp32")
+        raise HipError(f"{what}: obs_noise_coef must be contiguous [S, 2] = [{S}, 2] fp32")
     _check(lib().ib_ddim_cond_step_noise(_ptr(x), _ptr(eps), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef),
                                          _ptr(obs_noise_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out),
                                          _ptr(win_id), int(seed) & 0xFFFFFFFFFFFFFFFF, B, T, D, ld, dtype_code(x.dtype),
@@ -2356,36 +2233,16 @@ def ddim_cond_step_noise(x, eps, x0, z, mask, coef, obs_coef, obs_noise_coef, ti
     return x
 
 
-def _dpmpp_operands(what, x, eps, hist, coef, timesteps, t_out, step_dev):
-    """shared checks of the DPM-Solver++(2M) updates -> S"""
-    _req(eps, "eps", x.dtype)
-    if eps.shape != x.shape or not x.is_contiguous() or not eps.is_contiguous():
-        raise HipError(f"{what}: x/eps must be contiguous with one shape")
-    _req(hist, "hist", torch.float32)
-    if hist.shape != x.shape or not hist.is_contiguous():
-        raise HipError(f"{what}: hist must be contiguous fp32 {tuple(x.shape)}, like x")
-    _req(coef, "coef", torch.float32, 2)
-    _req(timesteps, "timesteps", torch.int64, 1)
-    S = coef.shape[0]
-    if coef.shape[1] != 5 or timesteps.numel() != S or not coef.is_contiguous():
-        raise HipError(f"{what}: coef must be [S, 5] fp32 (A, E, C, hx, he), timesteps [S] int64")
-    if t_out is not None:
-        _req(t_out, "t_out", torch.int64, 1)
-        if t_out.numel() != x.shape[0]:
-            raise HipError("t_out must be int64 [B]")
-    if step_dev is not None:
-        _req(step_dev, "step_dev", torch.int32)
-    return S
-
-
 def dpmpp_step(x, eps, hist, coef, timesteps, step=0, step_dev=None, t_out=None):
     """DPM-Solver++(2M) update in place (csrc/diffusion.hip): coef [S, 5] = (A, E, C, hx, he), x <- A x + E eps + C hist, then
     hist <- hx x + he eps over the x it was given (fp32, the shape of x); a row with C == 0 does not read hist and equals
     ddim_step given (A, E).  t_out / step_dev as in ddim_step."""
-    _req(x, "x", x.dtype)
-    S = _dpmpp_operands("dpmpp_step", x, eps, hist, coef, timesteps, t_out, step_dev)
+    B = _flat_state("dpmpp_step", x)
+    _like_x("dpmpp_step", "eps", eps, x)
+    _like_x("dpmpp_step", "hist", hist, x, torch.float32)
+    S = _step_tables("dpmpp_step", coef, 5, timesteps, B, t_out, step_dev)
     _check(lib().ib_dpmpp_step(_ptr(x), _ptr(eps), _ptr(hist), _ptr(coef), _ptr(timesteps), S, int(step), _ptr(step_dev),
-                               _ptr(t_out), x.shape[0], x.numel(), dtype_code(x.dtype), stream_ptr()), "ib_dpmpp_step")
+                               _ptr(t_out), B, x.numel(), dtype_code(x.dtype), stream_ptr()), "ib_dpmpp_step")
     return x
 
 
@@ -2393,9 +2250,9 @@ def dpmpp_cond_step(x, eps, hist, x0, z, mask, coef, obs_coef, timesteps, step=0
     """masked DPM-Solver++(2M) update in place over the state x [B, T, ld]: elements with mask [T, ld] == 0 take the
     dpmpp_step update (hist fp32 [B, T, ld]), the others obs_coef[s + 1] (x0, z) as in ddim_cond_step."""
     B, T, D, ld = _cond_operands("dpmpp_cond_step", x, x0, z, mask, obs_coef, D)
-    S = _dpmpp_operands("dpmpp_cond_step", x, eps, hist, coef, timesteps, t_out, step_dev)
-    if obs_coef.shape[0] != S + 1:
-        raise HipError(f"dpmpp_cond_step: obs_coef must have S + 1 = {S + 1} rows, got {obs_coef.shape[0]}")
+    _like_x("dpmpp_cond_step", "eps", eps, x)
+    _like_x("dpmpp_cond_step", "hist", hist, x, torch.float32)
+    S = _step_tables("dpmpp_cond_step", coef, 5, timesteps, B, t_out, step_dev, obs_coef)
     _check(lib().ib_dpmpp_cond_step(_ptr(x), _ptr(eps), _ptr(hist), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef),
                                     _ptr(obs_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out), B, T, D, ld,
                                     dtype_code(x.dtype), stream_ptr()), "ib_dpmpp_cond_step")

@@ -22,6 +22,204 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert b"workspace" in lib.ib_error_string(-4)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the ctypes signatures are parsed from the header (hip._parse_header): the parser on texts written here
+# ---------------------------------------------------------------------------------------------------------------------
+HEADER_TEXT = """
+#ifndef X_H
+#define X_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+typedef void* ib_stream_t; /* a stream */
+enum { IB_A = 0, IB_B = 1 /* ib_not_a_call(int) */ };
+int ib_scalars(int a, int32_t b, int64_t c, uint32_t d, uint64_t e, float f, size_t g, ib_stream_t s);
+const char* ib_text(const int code);   // ib_in_a_comment(double x);
+size_t ib_bytes(const int64_t n, const float* p, const void *q, int64_t unnamed_follows, int);
+int64_t ib_arrays(void** out, const void* const* in, float* const* dst, const uint8_t* mask);
+int ib_nothing(void);
+int ib_split(const void* x,   /* the input,
+                                 described over two lines; with a semicolon */
+             int64_t n,
+             ib_stream_t stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_parser_maps_every_declaration_form():
+    from inferbiomechanics_amd import hip
+    c = ctypes
+    vp = c.c_void_p
+    assert hip._parse_header(HEADER_TEXT) == {
+        "ib_scalars": (c.c_int, [c.c_int, c.c_int32, c.c_int64, c.c_uint32, c.c_uint64, c.c_float, c.c_size_t, vp]),
+        "ib_text": (c.c_char_p, [c.c_int]),
+        "ib_bytes": (c.c_size_t, [c.c_int64, vp, vp, c.c_int64, c.c_int]),
+        "ib_arrays": (c.c_int64, [vp, vp, vp, vp]),
+        "ib_nothing": (c.c_int, []),
+        "ib_split": (c.c_int, [vp, c.c_int64, vp]),
+    }
+    assert hip._parse_header("") == {}
+
+
+@pytest.mark.parametrize("text,words", [
+    ("int ib_ok(int a);\nint ib_bad_type(int64_t n, double x, float y);", ("ib_bad_type", "double x")),
+    ("int ib_unsigned(unsigned int n);", ("ib_unsigned", "unsigned int n")),
+    ("int ib_array(int n[4]);", ("ib_array", "n[4]")),
+    ("int ib_empty();", ("ib_empty",)),
+    ("int ib_callback(int n, void (*done)(int), ib_stream_t s);", ("ib_callback", "done")),
+    ("int ib_unclosed(int n;\nint ib_next(void);", ("ib_unclosed",)),
+    ("double ib_ret(int n);", ("ib_ret", "double")),
+    ("void* ib_ret_ptr(int n);", ("ib_ret_ptr",)),
+    ("int ib_twice(int a);\nint ib_other(void);\nint ib_twice(int a);", ("ib_twice", "twice")),
+])
+def test_parser_refuses_what_it_cannot_map(text, words):
+    from inferbiomechanics_amd import hip
+    with pytest.raises(hip.HipError) as e:
+        hip._parse_header(text)
+    for w in words:
+        assert w in str(e.value), str(e.value)
+
+
+def test_missing_header_is_a_hip_error_that_names_the_path(monkeypatch, tmp_path):
+    from inferbiomechanics_amd import hip
+    gone = str(tmp_path / "include" / "ib_hip.h")
+    monkeypatch.setattr(hip, "HEADER_PATH", gone)
+    with pytest.raises(hip.HipError) as e:
+        hip._read_header()
+    assert "missing" in str(e.value) and gone in str(e.value)
+
+
+# the entry points that are not pure host queries and still do not take the stream last, as the header shows them: a new one
+# has to be added here by name (time_recorded_call and the stamping proxy put the stream into the last argument)
+NO_TRAILING_STREAM = {
+    "ib_debug_set_ablate", "ib_debug_set_chain_prof", "ib_debug_set_ffn_prof", "ib_debug_set_gemm_prof", "ib_debug_set_nt_prof",
+    "ib_event_create", "ib_event_destroy", "ib_event_elapsed_ms", "ib_graph_destroy", "ib_graph_end", "ib_stream_create",
+    "ib_stream_destroy",
+}
+
+
+def test_real_header_gives_one_signature_per_declared_symbol():
+    import re
+    from inferbiomechanics_amd import hip
+    c = ctypes
+    assert len(hip._SIGS) == len(hip.declared_symbols()) == 127
+    assert hip.declared_symbols() == sorted(hip._SIGS)
+    src = re.sub(r"/\*.*?\*/", "", open(hip.HEADER_PATH).read(), flags=re.S)
+    assert set(hip._SIGS) == set(re.findall(r"\b(ib_[a-z0-9_]+)\s*\(", src))        # the rule declared_symbols() had
+    for name, (res, args) in hip._SIGS.items():
+        assert res in (c.c_int, c.c_size_t, c.c_int64, c.c_char_p), name
+        if name.endswith(hip._HOST_ONLY) or name in ("ib_version", "ib_error_string"):
+            continue                                                              # pure host queries: no stream
+        last = re.search(rf"\b{name}\s*\(([^)]*)\)", src).group(1).split(",")[-1].split()
+        assert (last[0] != "ib_stream_t") == (name in NO_TRAILING_STREAM), (name, last)
+        if name not in NO_TRAILING_STREAM:
+            assert args[-1] is c.c_void_p, name
+    # every out-parameter is a plain c_void_p like the other pointers (ctypes takes byref() there), not a POINTER(...) type
+    assert hip._SIGS["ib_graph_end"][1] == [c.c_void_p, c.c_void_p]
+    assert hip._SIGS["ib_stream_create"][1] == hip._SIGS["ib_event_create"][1] == [c.c_void_p]
+    assert hip._SIGS["ib_event_elapsed_ms"][1] == [c.c_void_p] * 3
+    lib = hip.lib()
+    for name, (res, args) in hip._SIGS.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    h, ms = c.c_void_p(), c.c_float()
+    for fn, a in ((lib.ib_graph_end, (None, c.byref(h))), (lib.ib_event_elapsed_ms, (None, None, c.byref(ms)))):
+        fn.argtypes[-1].from_param(a[-1])                                         # byref() marshals into a c_void_p parameter
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# which entry points the four proxies take over (hip._is_launch): the sets of the code before the predicate was shared
+# ---------------------------------------------------------------------------------------------------------------------
+HOST_QUERIES = {
+    "ib_debug_last_path", "ib_error_string", "ib_ffn_chain_attn_mask_bytes", "ib_ffn_chain_attn_workgroups",
+    "ib_ffn_chain_mask_bytes", "ib_ffn_chain_packed_elems", "ib_ffn_chain_supported", "ib_ffn_chain_workgroups",
+    "ib_ffn_infer_workgroups", "ib_ffn_infer_workspace", "ib_layernorm_bwd_workspace", "ib_linear_ln_fwd_workspace",
+    "ib_linear_ln_panel_workgroups", "ib_linear_panel_workgroups", "ib_linear_wgrad_slabs_workspace",
+    "ib_linear_wgrad_workspace", "ib_mlp_chain_packed_elems", "ib_mlp_chain_partial_width", "ib_mlp_chain_supported",
+    "ib_mlp_chain_workgroups", "ib_mse_loss_workspace", "ib_optim_ticket_words", "ib_regression_loss_workspace",
+    "ib_time_mlp_bwd_slab_count", "ib_time_mlp_bwd_supported", "ib_time_mlp_fwd_supported", "ib_version",
+}
+EVENTS_AND_GRAPHS = {"ib_event_create", "ib_event_destroy", "ib_event_elapsed_ms", "ib_event_record", "ib_graph_begin",
+                     "ib_graph_destroy", "ib_graph_end", "ib_graph_launch"}
+DEBUG_HOOKS = {"ib_debug_set_ablate", "ib_debug_set_chain_prof", "ib_debug_set_ffn_prof", "ib_debug_set_gemm_prof",
+               "ib_debug_set_nt_prof", "ib_debug_stamp"}
+PASSED_THROUGH = {                       # proxy -> the names it hands to the library untouched; it wraps every other one
+    "_DryRunLib": HOST_QUERIES,          # ... so no event, graph or stream call of a dry run reaches the real library
+    "_TimingLib": HOST_QUERIES | EVENTS_AND_GRAPHS,
+    "_RecordingLib": HOST_QUERIES | EVENTS_AND_GRAPHS,
+    "_StampLib": HOST_QUERIES | EVENTS_AND_GRAPHS | DEBUG_HOOKS,
+}
+
+
+class _StubLib:
+    """stands where the loaded library does: one distinct function per name, nothing behind it"""
+
+    def __getattr__(self, name):
+        fn = self.__dict__[name] = lambda *a: 0
+        return fn
+
+
+def _proxy_over_stub(cls, **attrs):
+    proxy = object.__new__(cls)          # not __init__: _StampLib's allocates its stamp buffer on the device
+    proxy._real = _StubLib()
+    proxy.__dict__.update(attrs)
+    return proxy
+
+
+@pytest.mark.parametrize("cls", sorted(PASSED_THROUGH))
+def test_each_proxy_takes_over_exactly_the_entry_points_it_did(cls):
+    from inferbiomechanics_amd import hip
+    proxy = _proxy_over_stub(getattr(hip, cls), only=None)
+    passed = {n for n in hip._SIGS if getattr(proxy, n) is getattr(proxy._real, n)}
+    assert passed == PASSED_THROUGH[cls]
+    assert len(hip._SIGS) - len(passed) == {"_DryRunLib": 100, "_TimingLib": 92, "_RecordingLib": 92, "_StampLib": 86}[cls]
+    if cls != "_DryRunLib":              # (the dry-run stand-in looks every name up in _SIGS)
+        assert proxy.some_attribute is proxy._real.some_attribute
+
+
+def test_stamp_proxy_honours_only():
+    from inferbiomechanics_amd import hip
+    proxy = _proxy_over_stub(hip._StampLib, only={"ib_cast", "ib_debug_stamp", "ib_event_record", "ib_version"})
+    wrapped = {n for n in hip._SIGS if getattr(proxy, n) is not getattr(proxy._real, n)}
+    assert wrapped == {"ib_cast"}
+
+
+def test_predicate_is_the_one_rule_behind_the_proxies():
+    from inferbiomechanics_amd import hip
+    names = set(hip._SIGS)
+    assert {n for n in names if not hip._is_launch(n)} == HOST_QUERIES | EVENTS_AND_GRAPHS
+    assert {n for n in names if not hip._is_launch(n, handed_through=())} == HOST_QUERIES
+    assert not hip._is_launch("calls") and not hip._is_launch("_real")
+    assert hip._RecordingLib.SKIP == ("ib_optim_step", "ib_optim_step_ema", "ib_counter_add")
+
+
+def test_launch_context_managers_install_their_proxy_and_restore_the_library():
+    from inferbiomechanics_amd import hip
+    hip.set_dry_run(True)
+    try:
+        base = hip.lib()
+        with hip.record_launches() as rec:
+            assert isinstance(rec, hip._RecordingLib) and hip.lib() is rec and rec._real is base
+            assert (rec.calls, rec.paths, rec.notes) == ([], [], {})
+            hip.cast(torch.zeros(4), torch.zeros(4, dtype=torch.bfloat16))
+            assert [n for n, _ in rec.calls] == ["ib_cast"] and base.calls[-1] == "ib_cast"
+        assert hip.lib() is base
+        with hip.time_launches() as tl:
+            assert isinstance(tl, hip._TimingLib) and hip.lib() is tl and tl.summary() == {}
+        assert hip.lib() is base
+        with pytest.raises(KeyError):
+            with hip.record_launches():
+                raise KeyError("left through an exception")
+        assert hip.lib() is base
+        assert callable(hip.time_recorded_call) and issubclass(hip.stamp_launches, hip._proxy_installed)
+    finally:
+        hip.set_dry_run(False)
+
+
 def test_null_arguments_return_error_codes_not_crashes():
     from inferbiomechanics_amd import hip
     lib = hip.lib()

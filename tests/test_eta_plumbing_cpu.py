@@ -209,6 +209,127 @@ def test_bindings_reject_wrong_arguments(dry):
         dry.ensemble_stats(ens, mean=torch.zeros(3, 10, 29))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the seven sampler-update wrappers (the DPM-Solver++ pair included: one harness) on the smallest state on which every operand
+# check can fire: x [2, 3, 8], fp32 and bf16, S = 4 steps, and D = 6 feature columns in front of the pitch ld = 8
+# ---------------------------------------------------------------------------------------------------------------------
+S_, B_, T_, LD_ = 4, 2, 3, 8
+# wrapper -> (its positional operands, columns of coef, the entry's pointer arguments in ABI order, its scalar arguments)
+WRAPPERS = {
+    "ddim_step": ("x eps coef timesteps", 2, "x eps coef timesteps step_dev t_out", "S step B n dtype"),
+    "ddim_cond_step": ("x eps x0 z mask coef obs_coef timesteps", 2,
+                       "x eps x0 z mask coef obs_coef timesteps step_dev t_out", "S step B T D ld dtype"),
+    "ddim_cond_init": ("x x0 z mask obs_coef", None, "x x0 z mask obs_coef", "B T D ld dtype"),
+    "ddim_step_noise": ("x eps coef timesteps win_id seed", 3, "x eps coef timesteps step_dev t_out win_id",
+                        "S step seed B T D ld dtype"),
+    "ddim_cond_step_noise": ("x eps x0 z mask coef obs_coef obs_noise_coef timesteps win_id seed", 3,
+                             "x eps x0 z mask coef obs_coef obs_noise_coef timesteps step_dev t_out win_id",
+                             "S step seed B T D ld dtype"),
+    "dpmpp_step": ("x eps hist coef timesteps", 5, "x eps hist coef timesteps step_dev t_out", "S step B n dtype"),
+    "dpmpp_cond_step": ("x eps hist x0 z mask coef obs_coef timesteps", 5,
+                        "x eps hist x0 z mask coef obs_coef timesteps step_dev t_out", "S step B T D ld dtype"),
+}
+
+
+def sampler_operands(dt, ncols):
+    st = lambda: torch.zeros(B_, T_, LD_, dtype=dt)
+    return dict(x=st(), eps=st(), x0=st(), z=st(), hist=torch.zeros(B_, T_, LD_), mask=torch.zeros(T_, LD_, dtype=torch.uint8),
+                coef=torch.zeros(S_, ncols or 2), obs_coef=torch.zeros(S_ + 1, 2), obs_noise_coef=torch.zeros(S_, 2),
+                timesteps=torch.zeros(S_, dtype=torch.int64), win_id=torch.zeros(B_, dtype=torch.int64), seed=-5,
+                t_out=torch.zeros(B_, dtype=torch.int64), step_dev=torch.zeros(1, dtype=torch.int32))
+
+
+def call_wrapper(hip, name, ops, **kw):
+    return getattr(hip, name)(*[ops[k] for k in WRAPPERS[name][0].split()], **kw)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("name", sorted(WRAPPERS))
+def test_sampler_wrapper_marshals_one_call_of_its_entry(dry, name, dt):
+    positional, ncols, pointers, scalars = WRAPPERS[name]
+    ops = sampler_operands(dt, ncols)
+    masked_or_noise = "D" in scalars
+    has_tables = ncols is not None
+    rec = dry.lib()
+    # the call the sampler loops make: device counter, next-timestep vector, D columns in front of the pitch
+    kw = dict(step=3, step_dev=ops["step_dev"], t_out=ops["t_out"]) if has_tables else {}
+    if masked_or_noise:
+        kw["D"] = 6
+    assert call_wrapper(dry, name, ops, **kw) is ops["x"]
+    assert rec.calls == ["ib_" + name] and [n for n, _ in rec.args] == rec.calls
+    sig = dry._SIGS["ib_" + name][1]
+    args = rec.args[0][1]
+    assert len(args) == len(sig)
+    got_ptrs = [v for v, t in zip(args, sig) if t is ctypes.c_void_p]
+    got_scalars = [v for v, t in zip(args, sig) if t is not ctypes.c_void_p]
+    assert got_ptrs == [ops[k].data_ptr() for k in pointers.split()] + [0]          # ... and the (dry-run) stream last
+    code = {torch.float32: 0, torch.bfloat16: 1}[dt]
+    want = dict(S=4, step=3, seed=2 ** 64 - 5, B=2, T=3, D=6, ld=8, n=48, dtype=code)
+    assert got_scalars == [want[k] for k in scalars.split()], (got_scalars, scalars)
+    # the defaults: host step 0, no counter, no t_out, D = ld
+    call_wrapper(dry, name, ops)
+    args = rec.args[1][1]
+    want.update(step=0, D=8)
+    assert [v for v, t in zip(args, sig) if t is not ctypes.c_void_p] == [want[k] for k in scalars.split()]
+    none_at = [k for k, v in zip(pointers.split(), [v for v, t in zip(args, sig) if t is ctypes.c_void_p]) if v is None]
+    assert none_at == (["step_dev", "t_out"] if has_tables else [])
+    assert rec.calls == ["ib_" + name] * 2
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("name", sorted(WRAPPERS))
+def test_sampler_wrapper_refuses_every_wrong_operand_before_the_library(dry, name, dt):
+    positional, ncols, pointers, scalars = WRAPPERS[name]
+    good = sampler_operands(dt, ncols)
+    other = torch.float32 if dt == torch.bfloat16 else torch.bfloat16
+    i64, i32 = torch.int64, torch.int32
+    has = lambda k: k in positional.split()
+    bad = []                                                        # (what is wrong, operands replaced, keywords)
+    if has("eps"):
+        bad += [("eps of another shape", dict(eps=torch.zeros(B_, T_, LD_ - 1, dtype=dt)), {}),
+                ("eps of another dtype", dict(eps=torch.zeros(B_, T_, LD_, dtype=other)), {}),
+                ("eps not contiguous", dict(eps=torch.zeros(B_, T_, 2 * LD_, dtype=dt)[:, :, ::2]), {})]
+    if has("hist"):
+        bad += [("hist in the state's dtype", dict(hist=torch.zeros(B_, T_, LD_, dtype=torch.bfloat16)), {}),
+                ("hist of another shape", dict(hist=torch.zeros(B_, T_, LD_ - 1)), {})]
+    if has("coef"):
+        bad += [("coef one column short", dict(coef=torch.zeros(S_, ncols - 1)), {}),
+                ("coef not contiguous", dict(coef=torch.zeros(S_, 2 * ncols)[:, ::2]), {}),
+                ("timesteps one short", dict(timesteps=torch.zeros(S_ - 1, dtype=i64)), {}),
+                ("t_out of B + 1", {}, dict(t_out=torch.zeros(B_ + 1, dtype=i64))),
+                ("t_out int32", {}, dict(t_out=torch.zeros(B_, dtype=i32))),
+                ("step_dev int64", {}, dict(step_dev=torch.zeros(1, dtype=i64)))]
+    if has("mask"):
+        bad += [("mask [T, ld - 1]", dict(mask=torch.zeros(T_, LD_ - 1, dtype=torch.uint8)), {}),
+                ("mask bool", dict(mask=torch.zeros(T_, LD_, dtype=torch.bool)), {}),
+                ("x0 of another shape", dict(x0=torch.zeros(B_, T_, LD_ - 1, dtype=dt)), {}),
+                ("z of another dtype", dict(z=torch.zeros(B_, T_, LD_, dtype=other)), {}),
+                ("obs_coef with three columns", dict(obs_coef=torch.zeros(S_ + 1, 3)), {})]
+        if has("coef"):                                             # (ddim_cond_init reads row 0 only: it has no S)
+            bad += [("obs_coef with S rows", dict(obs_coef=torch.zeros(S_, 2)), {})]
+    if has("obs_noise_coef"):
+        bad += [("obs_noise_coef with S + 1 rows", dict(obs_noise_coef=torch.zeros(S_ + 1, 2)), {})]
+    if has("win_id"):
+        bad += [("win_id of B + 1", dict(win_id=torch.zeros(B_ + 1, dtype=i64)), {}),
+                ("win_id int32", dict(win_id=torch.zeros(B_, dtype=i32)), {})]
+    if "D" in scalars:
+        bad += [("D = 0", {}, dict(D=0)), ("D = ld + 1", {}, dict(D=LD_ + 1)),
+                ("x without the frame axis", dict(x=torch.zeros(B_ * T_, LD_, dtype=dt)), {})]
+    else:
+        bad += [("x without any axis", dict(x=torch.zeros((), dtype=dt), eps=torch.zeros((), dtype=dt),
+                                            hist=torch.zeros(())), {})]
+    bad += [("x not contiguous", dict(x=torch.zeros(B_, T_, 2 * LD_, dtype=dt)[:, :, ::2]), {})]
+    rec = dry.lib()
+    for what, ops, kw in bad:
+        with pytest.raises(dry.HipError) as e:
+            call_wrapper(dry, name, {**good, **ops}, **kw)
+        assert rec.calls == [] and rec.args == [], f"{name}, {what}: the library was called"
+        assert not str(e.value).startswith(tuple(w + ":" for w in WRAPPERS if w != name)), \
+            f"{name}, {what}: the message names another wrapper: {e.value}"
+    call_wrapper(dry, name, good)                                   # and the operands they were derived from are accepted
+    assert rec.calls == ["ib_" + name]
+
+
 def test_new_entries_return_error_codes_on_bad_arguments():
     from inferbiomechanics_amd import hip
     lib = hip.lib()
