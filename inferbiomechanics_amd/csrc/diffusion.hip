@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "ib_common.h"
+#include "launch.h"
 #include "philox.h"
 
 namespace {
@@ -647,35 +648,28 @@ extern "C" int ib_gather_rows(const float* table, const int64_t* idx, void* out,
                               int64_t table_rows, int dtype_out, ib_stream_t stream) {
   if (!table || !idx || !out || B <= 0 || dim <= 0 || table_rows <= 0) return IB_E_ARG;
   const int grid = ib_grid_1d(B * dim, 256);
-  if (dtype_out == IB_F32)
-    hipLaunchKernelGGL((gather_rows_kernel<float>), dim3(grid), dim3(256), 0, ib_s(stream), table, idx, (float*)out, B, dim, table_rows);
-  else if (dtype_out == IB_BF16)
-    hipLaunchKernelGGL((gather_rows_kernel<bf16_t>), dim3(grid), dim3(256), 0, ib_s(stream), table, idx, (bf16_t*)out, B, dim, table_rows);
-  else return IB_E_DTYPE;
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  return ib_dispatch_dtype(dtype_out, [&](auto tag) {
+    using TY = decltype(tag);
+    hipLaunchKernelGGL((gather_rows_kernel<TY>), dim3(grid), dim3(256), 0, ib_s(stream), table, idx, (TY*)out, B, dim, table_rows);
+  });
 }
+
+// The launchers below share one shape: the entry point's own argument checks in its own order, the launch geometry from
+// launch_geom.h (the width rule is stated there, once), then launch.h's dispatch of dtype (and width) onto the kernel.
 
 extern "C" int ib_q_sample(const void* x0, const void* eps, const int64_t* t, const float* sqrt_ab, const float* sqrt_1mab,
                            void* x_t, int64_t ld_xt, int64_t B, int64_t T, int64_t D, int64_t table_rows, int dtype,
                            ib_stream_t stream) {
   if (!x0 || !eps || !t || !sqrt_ab || !sqrt_1mab || !x_t || B <= 0 || T <= 0 || D <= 0 || table_rows <= 0 || ld_xt < D)
     return IB_E_ARG;
-  const int es = dtype == IB_BF16 ? 2 : 4;
-  auto al = [&](const void* q) { return (reinterpret_cast<uintptr_t>(q) % (4 * es)) == 0; };
-  const bool v4 = (D % 4 == 0) && (ld_xt % 4 == 0) && al(x0) && al(eps) && al(x_t);
+  const bool v4 = ib_q_sample_v4(D, ld_xt, dtype == IB_BF16 ? 2 : 4, x0, eps, x_t);
   const int64_t rows = B * T;
   const int grid = ib_grid_1d(rows * D / (v4 ? 4 : 1), 256);
-  hipStream_t s = ib_s(stream);
-  if (dtype == IB_F32) {
-    if (v4) hipLaunchKernelGGL((q_sample_kernel<float, 4>), dim3(grid), dim3(256), 0, s, (const float*)x0, (const float*)eps, t, sqrt_ab, sqrt_1mab, (float*)x_t, ld_xt, rows, T, D, table_rows);
-    else hipLaunchKernelGGL((q_sample_kernel<float, 1>), dim3(grid), dim3(256), 0, s, (const float*)x0, (const float*)eps, t, sqrt_ab, sqrt_1mab, (float*)x_t, ld_xt, rows, T, D, table_rows);
-  } else if (dtype == IB_BF16) {
-    if (v4) hipLaunchKernelGGL((q_sample_kernel<bf16_t, 4>), dim3(grid), dim3(256), 0, s, (const bf16_t*)x0, (const bf16_t*)eps, t, sqrt_ab, sqrt_1mab, (bf16_t*)x_t, ld_xt, rows, T, D, table_rows);
-    else hipLaunchKernelGGL((q_sample_kernel<bf16_t, 1>), dim3(grid), dim3(256), 0, s, (const bf16_t*)x0, (const bf16_t*)eps, t, sqrt_ab, sqrt_1mab, (bf16_t*)x_t, ld_xt, rows, T, D, table_rows);
-  } else return IB_E_DTYPE;
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  return ib_dispatch_dtype_width<4>(dtype, v4, [&](auto tag, auto width) {
+    using TY = decltype(tag);
+    hipLaunchKernelGGL((q_sample_kernel<TY, decltype(width)::value>), dim3(grid), dim3(256), 0, ib_s(stream), (const TY*)x0, (const TY*)eps, t,
+                       sqrt_ab, sqrt_1mab, (TY*)x_t, ld_xt, rows, T, D, table_rows);
+  });
 }
 
 extern "C" int ib_q_sample_cond(const void* x0, const void* eps, const int64_t* t, const float* sqrt_ab,
@@ -686,23 +680,14 @@ extern "C" int ib_q_sample_cond(const void* x0, const void* eps, const int64_t* 
     return ib_q_sample(x0, eps, t, sqrt_ab, sqrt_1mab, x_t, ld_xt, B, T, D, table_rows, dtype, stream);
   if (!x0 || !eps || !t || !sqrt_ab || !sqrt_1mab || !x_t || B <= 0 || T <= 0 || D <= 0 || table_rows <= 0 || ld_xt < D)
     return IB_E_ARG;
-  const int es = dtype == IB_BF16 ? 2 : 4;
-  auto al = [&](const void* q) { return (reinterpret_cast<uintptr_t>(q) % (4 * es)) == 0; };
-  const bool v4 = (D % 4 == 0) && (ld_xt % 4 == 0) && al(x0) && al(eps) && al(x_t);      // ib_q_sample's choice
+  const bool v4 = ib_q_sample_v4(D, ld_xt, dtype == IB_BF16 ? 2 : 4, x0, eps, x_t);
   const int64_t rows = B * T;
   const int grid = ib_grid_1d(rows * D / (v4 ? 4 : 1), 256);
-  hipStream_t s = ib_s(stream);
-#define IB_QS_COND(TY, V)                                                                                                     \
-  hipLaunchKernelGGL((q_sample_cond_kernel<TY, V>), dim3(grid), dim3(256), 0, s, (const TY*)x0, (const TY*)eps, t, sqrt_ab,   \
-                     sqrt_1mab, (TY*)x_t, ld_xt, rows, T, D, table_rows, cond_cols)
-  if (dtype == IB_F32) {
-    if (v4) IB_QS_COND(float, 4); else IB_QS_COND(float, 1);
-  } else if (dtype == IB_BF16) {
-    if (v4) IB_QS_COND(bf16_t, 4); else IB_QS_COND(bf16_t, 1);
-  } else return IB_E_DTYPE;
-#undef IB_QS_COND
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  return ib_dispatch_dtype_width<4>(dtype, v4, [&](auto tag, auto width) {
+    using TY = decltype(tag);
+    hipLaunchKernelGGL((q_sample_cond_kernel<TY, decltype(width)::value>), dim3(grid), dim3(256), 0, ib_s(stream), (const TY*)x0, (const TY*)eps,
+                       t, sqrt_ab, sqrt_1mab, (TY*)x_t, ld_xt, rows, T, D, table_rows, cond_cols);
+  });
 }
 
 extern "C" int ib_ddim_step(void* x, const void* eps, const float* coef, const int64_t* timesteps, int64_t num_steps,
@@ -710,19 +695,13 @@ extern "C" int ib_ddim_step(void* x, const void* eps, const float* coef, const i
                             ib_stream_t stream) {
   if (!x || !eps || !coef || num_steps <= 0 || n <= 0) return IB_E_ARG;
   if (t_out && (!timesteps || B <= 0)) return IB_E_ARG;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
-  const bool v8 = (n % 8 == 0) && al16(x) && al16(eps);
-  const int grid = ib_grid_1d(n / (v8 ? 8 : 1), 256);
-  hipStream_t s = ib_s(stream);
-  if (dtype == IB_F32) {
-    if (v8) hipLaunchKernelGGL((ddim_step_kernel<float, 8>), dim3(grid), dim3(256), 0, s, (float*)x, (const float*)eps, coef, timesteps, num_steps, step, step_dev, t_out, B, n);
-    else hipLaunchKernelGGL((ddim_step_kernel<float, 1>), dim3(grid), dim3(256), 0, s, (float*)x, (const float*)eps, coef, timesteps, num_steps, step, step_dev, t_out, B, n);
-  } else if (dtype == IB_BF16) {
-    if (v8) hipLaunchKernelGGL((ddim_step_kernel<bf16_t, 8>), dim3(grid), dim3(256), 0, s, (bf16_t*)x, (const bf16_t*)eps, coef, timesteps, num_steps, step, step_dev, t_out, B, n);
-    else hipLaunchKernelGGL((ddim_step_kernel<bf16_t, 1>), dim3(grid), dim3(256), 0, s, (bf16_t*)x, (const bf16_t*)eps, coef, timesteps, num_steps, step, step_dev, t_out, B, n);
-  } else return IB_E_DTYPE;
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  const SamplerGeom g = ib_sampler_geom(n, 0, x, eps, nullptr, nullptr, nullptr, nullptr);
+  const int grid = ib_grid_1d(n / (g.v8 ? 8 : 1), 256);
+  return ib_dispatch_dtype_width<8>(dtype, g.v8, [&](auto tag, auto width) {
+    using TY = decltype(tag);
+    hipLaunchKernelGGL((ddim_step_kernel<TY, decltype(width)::value>), dim3(grid), dim3(256), 0, ib_s(stream), (TY*)x, (const TY*)eps, coef,
+                       timesteps, num_steps, step, step_dev, t_out, B, n);
+  });
 }
 
 extern "C" int ib_ddim_cond_step(void* x, const void* eps, const void* x0, const void* z, const uint8_t* mask,
@@ -732,61 +711,35 @@ extern "C" int ib_ddim_cond_step(void* x, const void* eps, const void* x0, const
   if (!x || !eps || !x0 || !z || !mask || !coef || !obs_coef || num_steps <= 0) return IB_E_ARG;
   if (B <= 0 || T <= 0 || D <= 0 || ld < D) return IB_E_ARG;
   if (t_out && !timesteps) return IB_E_ARG;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
-  const int64_t per = T * ld, n = B * per;
-  const bool mix8 = (n % 8 == 0) && al16(x) && al16(eps);          // ib_ddim_step's choice of its 8-wide kernel
-  const bool v8 = mix8 && (per % 8 == 0) && al16(x0) && al16(z) && (reinterpret_cast<uintptr_t>(mask) % 8) == 0;
-  const int grid = ib_grid_1d(n / (v8 ? 8 : 1), 256);
-  hipStream_t s = ib_s(stream);
-#define IB_COND_STEP(TY, V)                                                                                                   \
-  hipLaunchKernelGGL((ddim_cond_step_kernel<TY, V, false>), dim3(grid), dim3(256), 0, s, (TY*)x, (const TY*)eps,             \
-                     (const TY*)x0, (const TY*)z, mask, coef, obs_coef, timesteps, num_steps, step, step_dev, t_out, B, per, n, \
-                     (int)mix8)
-  if (dtype == IB_F32) {
-    if (v8) IB_COND_STEP(float, 8); else IB_COND_STEP(float, 1);
-  } else if (dtype == IB_BF16) {
-    if (v8) IB_COND_STEP(bf16_t, 8); else IB_COND_STEP(bf16_t, 1);
-  } else return IB_E_DTYPE;
-#undef IB_COND_STEP
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  const SamplerGeom g = ib_sampler_geom(B * T * ld, T * ld, x, eps, nullptr, x0, z, mask);
+  const int grid = ib_grid_1d(g.n / (g.v8 ? 8 : 1), 256);
+  return ib_dispatch_dtype_width<8>(dtype, g.v8, [&](auto tag, auto width) {
+    using TY = decltype(tag);
+    hipLaunchKernelGGL((ddim_cond_step_kernel<TY, decltype(width)::value, false>), dim3(grid), dim3(256), 0, ib_s(stream), (TY*)x,
+                       (const TY*)eps, (const TY*)x0, (const TY*)z, mask, coef, obs_coef, timesteps, num_steps, step, step_dev,
+                       t_out, B, g.per, g.n, (int)g.mix8);
+  });
 }
 
 extern "C" int ib_ddim_cond_init(void* x, const void* x0, const void* z, const uint8_t* mask, const float* obs_coef,
                                  int64_t B, int64_t T, int64_t D, int64_t ld, int dtype, ib_stream_t stream) {
   if (!x || !x0 || !z || !mask || !obs_coef || B <= 0 || T <= 0 || D <= 0 || ld < D) return IB_E_ARG;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
-  const int64_t per = T * ld, n = B * per;
-  const bool v8 = (per % 8 == 0) && al16(x) && al16(x0) && al16(z) && (reinterpret_cast<uintptr_t>(mask) % 8) == 0;
-  const int grid = ib_grid_1d(n / (v8 ? 8 : 1), 256);
-  hipStream_t s = ib_s(stream);
-#define IB_COND_INIT(TY, V)                                                                                                   \
-  hipLaunchKernelGGL((ddim_cond_step_kernel<TY, V, true>), dim3(grid), dim3(256), 0, s, (TY*)x, (const TY*)nullptr,          \
-                     (const TY*)x0, (const TY*)z, mask, (const float*)nullptr, obs_coef, (const int64_t*)nullptr, (int64_t)1, 0, \
-                     (const int32_t*)nullptr, (int64_t*)nullptr, B, per, n, 0)
-  if (dtype == IB_F32) {
-    if (v8) IB_COND_INIT(float, 8); else IB_COND_INIT(float, 1);
-  } else if (dtype == IB_BF16) {
-    if (v8) IB_COND_INIT(bf16_t, 8); else IB_COND_INIT(bf16_t, 1);
-  } else return IB_E_DTYPE;
-#undef IB_COND_INIT
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  const SamplerGeom g = ib_sampler_geom(B * T * ld, T * ld, x, nullptr, nullptr, x0, z, mask);
+  const int grid = ib_grid_1d(g.n / (g.v8 ? 8 : 1), 256);
+  return ib_dispatch_dtype_width<8>(dtype, g.v8, [&](auto tag, auto width) {      // no eps, no update: mix8 = 0
+    using TY = decltype(tag);
+    hipLaunchKernelGGL((ddim_cond_step_kernel<TY, decltype(width)::value, true>), dim3(grid), dim3(256), 0, ib_s(stream), (TY*)x,
+                       (const TY*)nullptr, (const TY*)x0, (const TY*)z, mask, (const float*)nullptr, obs_coef,
+                       (const int64_t*)nullptr, (int64_t)1, 0, (const int32_t*)nullptr, (int64_t*)nullptr, B, g.per, g.n, 0);
+  });
 }
 
-// shared argument checks and launch geometry of the two stochastic updates
+// the per-window arguments of the two stochastic updates, checked, and the generator's parameters made of them
 namespace {
-struct NoiseLaunch { bool v8, blk, mix8; int64_t per, n; StepNoise nz; };
-int noise_launch(NoiseLaunch& L, const void* x, const void* eps, const void* x0, const void* z, const uint8_t* mask,
-                 const int64_t* win_id, uint64_t seed, int64_t B, int64_t T, int64_t D, int64_t ld) {
+int step_noise_of(StepNoise& nz, const int64_t* win_id, uint64_t seed, int64_t B, int64_t T, int64_t D, int64_t ld) {
   if (!win_id || B <= 0 || T <= 0 || D <= 0 || ld < D) return IB_E_ARG;
   if (T * ld >= (int64_t)1 << 31) return IB_E_UNSUPPORTED;             // offsets inside a window are 32-bit
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
-  L.per = T * ld; L.n = B * L.per;
-  L.mix8 = (L.n % 8 == 0) && al16(x) && al16(eps);                     // ib_ddim_step's choice of its 8-wide kernel
-  L.v8 = L.mix8 && (L.per % 8 == 0) && al16(x0) && al16(z) && (reinterpret_cast<uintptr_t>(mask) % 8) == 0;
-  L.blk = (D % 4 == 0) && (ld == D || ld % 8 == 0);
-  L.nz = StepNoise{(uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), win_id, (int32_t)D, (int32_t)ld, (int32_t)L.per};
+  nz = StepNoise{(uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), win_id, (int32_t)D, (int32_t)ld, (int32_t)(T * ld)};
   return IB_OK;
 }
 }  // namespace
@@ -796,25 +749,23 @@ extern "C" int ib_ddim_step_noise(void* x, const void* eps, const float* coef, c
                                   uint64_t seed, int64_t B, int64_t T, int64_t D, int64_t ld, int dtype, ib_stream_t stream) {
   if (!x || !eps || !coef || num_steps <= 0) return IB_E_ARG;
   if (t_out && !timesteps) return IB_E_ARG;
-  if (dtype != IB_F32 && dtype != IB_BF16) return IB_E_DTYPE;
-  NoiseLaunch L;
-  if (const int rc = noise_launch(L, x, eps, nullptr, nullptr, nullptr, win_id, seed, B, T, D, ld)) return rc;
-  const int grid = ib_grid_1d(L.n / (L.v8 ? 8 : 1), 256);
-  hipStream_t s = ib_s(stream);
-#define IB_STEP_NOISE(TY, V, BLK)                                                                                             \
-  hipLaunchKernelGGL((ddim_step_noise_kernel<TY, V, BLK>), dim3(grid), dim3(256), 0, s, (TY*)x, (const TY*)eps, coef, timesteps, \
-                     num_steps, step, step_dev, t_out, B, L.n, (int)L.mix8, L.nz)
-#define IB_STEP_NOISE_T(TY)                                                                                                   \
-  do {                                                                                                                        \
-    if (!L.v8) IB_STEP_NOISE(TY, 1, false);                                                                                   \
-    else if (L.blk) IB_STEP_NOISE(TY, 8, true);                                                                               \
-    else IB_STEP_NOISE(TY, 8, false);                                                                                         \
-  } while (0)
-  if (dtype == IB_F32) IB_STEP_NOISE_T(float); else IB_STEP_NOISE_T(bf16_t);
-#undef IB_STEP_NOISE_T
-#undef IB_STEP_NOISE
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  if (!ib_dtype_known(dtype)) return IB_E_DTYPE;                       // refused before the window arguments
+  StepNoise nz;
+  if (const int rc = step_noise_of(nz, win_id, seed, B, T, D, ld)) return rc;
+  const SamplerGeom g = ib_sampler_geom(B * T * ld, T * ld, x, eps, nullptr, nullptr, nullptr, nullptr);
+  const bool blk = ib_step_noise_blk(D, ld);
+  const int grid = ib_grid_1d(g.n / (g.v8 ? 8 : 1), 256);
+  return ib_dispatch_dtype(dtype, [&](auto tag) {
+    using TY = decltype(tag);
+    auto go = [&](auto width, auto whole_blocks) {
+      hipLaunchKernelGGL((ddim_step_noise_kernel<TY, decltype(width)::value, decltype(whole_blocks)::value>), dim3(grid),
+                         dim3(256), 0, ib_s(stream), (TY*)x, (const TY*)eps, coef, timesteps, num_steps, step, step_dev, t_out, B, g.n,
+                         (int)g.mix8, nz);
+    };
+    if (!g.v8) go(ib_width<1>{}, std::false_type{});
+    else if (blk) go(ib_width<8>{}, std::true_type{});
+    else go(ib_width<8>{}, std::false_type{});
+  });
 }
 
 extern "C" int ib_ddim_cond_step_noise(void* x, const void* eps, const void* x0, void* z, const uint8_t* mask,
@@ -824,26 +775,23 @@ extern "C" int ib_ddim_cond_step_noise(void* x, const void* eps, const void* x0,
                                        int64_t ld, int dtype, ib_stream_t stream) {
   if (!x || !eps || !x0 || !z || !mask || !coef || !obs_coef || !obs_noise_coef || num_steps <= 0) return IB_E_ARG;
   if (t_out && !timesteps) return IB_E_ARG;
-  if (dtype != IB_F32 && dtype != IB_BF16) return IB_E_DTYPE;
-  NoiseLaunch L;
-  if (const int rc = noise_launch(L, x, eps, x0, z, mask, win_id, seed, B, T, D, ld)) return rc;
-  const int grid = ib_grid_1d(L.n / (L.v8 ? 8 : 1), 256);
-  hipStream_t s = ib_s(stream);
-#define IB_COND_NOISE(TY, V, BLK)                                                                                             \
-  hipLaunchKernelGGL((ddim_cond_step_noise_kernel<TY, V, BLK>), dim3(grid), dim3(256), 0, s, (TY*)x, (const TY*)eps,         \
-                     (const TY*)x0, (TY*)z, mask, coef, obs_coef, obs_noise_coef, timesteps, num_steps, step, step_dev, t_out, \
-                     B, L.per, L.n, (int)L.mix8, L.nz)
-#define IB_COND_NOISE_T(TY)                                                                                                   \
-  do {                                                                                                                        \
-    if (!L.v8) IB_COND_NOISE(TY, 1, false);                                                                                   \
-    else if (L.blk) IB_COND_NOISE(TY, 8, true);                                                                               \
-    else IB_COND_NOISE(TY, 8, false);                                                                                         \
-  } while (0)
-  if (dtype == IB_F32) IB_COND_NOISE_T(float); else IB_COND_NOISE_T(bf16_t);
-#undef IB_COND_NOISE_T
-#undef IB_COND_NOISE
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  if (!ib_dtype_known(dtype)) return IB_E_DTYPE;                       // refused before the window arguments
+  StepNoise nz;
+  if (const int rc = step_noise_of(nz, win_id, seed, B, T, D, ld)) return rc;
+  const SamplerGeom g = ib_sampler_geom(B * T * ld, T * ld, x, eps, nullptr, x0, z, mask);
+  const bool blk = ib_step_noise_blk(D, ld);
+  const int grid = ib_grid_1d(g.n / (g.v8 ? 8 : 1), 256);
+  return ib_dispatch_dtype(dtype, [&](auto tag) {
+    using TY = decltype(tag);
+    auto go = [&](auto width, auto whole_blocks) {
+      hipLaunchKernelGGL((ddim_cond_step_noise_kernel<TY, decltype(width)::value, decltype(whole_blocks)::value>), dim3(grid),
+                         dim3(256), 0, ib_s(stream), (TY*)x, (const TY*)eps, (const TY*)x0, (TY*)z, mask, coef, obs_coef, obs_noise_coef,
+                         timesteps, num_steps, step, step_dev, t_out, B, g.per, g.n, (int)g.mix8, nz);
+    };
+    if (!g.v8) go(ib_width<1>{}, std::false_type{});
+    else if (blk) go(ib_width<8>{}, std::true_type{});
+    else go(ib_width<8>{}, std::false_type{});
+  });
 }
 
 extern "C" int ib_dpmpp_step(void* x, const void* eps, float* hist, const float* coef, const int64_t* timesteps,
@@ -851,23 +799,13 @@ extern "C" int ib_dpmpp_step(void* x, const void* eps, float* hist, const float*
                              int dtype, ib_stream_t stream) {
   if (!x || !eps || !hist || !coef || num_steps <= 0 || n <= 0) return IB_E_ARG;
   if (t_out && (!timesteps || B <= 0)) return IB_E_ARG;
-  if (dtype != IB_F32 && dtype != IB_BF16) return IB_E_DTYPE;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
-  const bool mix8 = (n % 8 == 0) && al16(x) && al16(eps);          // ib_ddim_step's choice of its 8-wide kernel
-  const bool v8 = mix8 && al16(hist);
-  const int grid = ib_grid_1d(n / (v8 ? 8 : 1), 256);
-  hipStream_t s = ib_s(stream);
-#define IB_DPMPP_STEP(TY, V)                                                                                                  \
-  hipLaunchKernelGGL((dpmpp_step_kernel<TY, V>), dim3(grid), dim3(256), 0, s, (TY*)x, (const TY*)eps, hist, coef, timesteps,  \
-                     num_steps, step, step_dev, t_out, B, n, (int)mix8)
-  if (dtype == IB_F32) {
-    if (v8) IB_DPMPP_STEP(float, 8); else IB_DPMPP_STEP(float, 1);
-  } else {
-    if (v8) IB_DPMPP_STEP(bf16_t, 8); else IB_DPMPP_STEP(bf16_t, 1);
-  }
-#undef IB_DPMPP_STEP
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  const SamplerGeom g = ib_sampler_geom(n, 0, x, eps, hist, nullptr, nullptr, nullptr);
+  const int grid = ib_grid_1d(n / (g.v8 ? 8 : 1), 256);
+  return ib_dispatch_dtype_width<8>(dtype, g.v8, [&](auto tag, auto width) {
+    using TY = decltype(tag);
+    hipLaunchKernelGGL((dpmpp_step_kernel<TY, decltype(width)::value>), dim3(grid), dim3(256), 0, ib_s(stream), (TY*)x, (const TY*)eps, hist,
+                       coef, timesteps, num_steps, step, step_dev, t_out, B, n, (int)g.mix8);
+  });
 }
 
 extern "C" int ib_dpmpp_cond_step(void* x, const void* eps, float* hist, const void* x0, const void* z, const uint8_t* mask,
@@ -877,38 +815,24 @@ extern "C" int ib_dpmpp_cond_step(void* x, const void* eps, float* hist, const v
   if (!x || !eps || !hist || !x0 || !z || !mask || !coef || !obs_coef || num_steps <= 0) return IB_E_ARG;
   if (B <= 0 || T <= 0 || D <= 0 || ld < D) return IB_E_ARG;
   if (t_out && !timesteps) return IB_E_ARG;
-  if (dtype != IB_F32 && dtype != IB_BF16) return IB_E_DTYPE;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
-  const int64_t per = T * ld, n = B * per;
-  const bool mix8 = (n % 8 == 0) && al16(x) && al16(eps);          // ib_ddim_step's choice of its 8-wide kernel
-  const bool v8 = mix8 && (per % 8 == 0) && al16(hist) && al16(x0) && al16(z) && (reinterpret_cast<uintptr_t>(mask) % 8) == 0;
-  const int grid = ib_grid_1d(n / (v8 ? 8 : 1), 256);
-  hipStream_t s = ib_s(stream);
-#define IB_DPMPP_COND(TY, V)                                                                                                  \
-  hipLaunchKernelGGL((dpmpp_cond_step_kernel<TY, V>), dim3(grid), dim3(256), 0, s, (TY*)x, (const TY*)eps, hist,             \
-                     (const TY*)x0, (const TY*)z, mask, coef, obs_coef, timesteps, num_steps, step, step_dev, t_out, B, per, n, \
-                     (int)mix8)
-  if (dtype == IB_F32) {
-    if (v8) IB_DPMPP_COND(float, 8); else IB_DPMPP_COND(float, 1);
-  } else {
-    if (v8) IB_DPMPP_COND(bf16_t, 8); else IB_DPMPP_COND(bf16_t, 1);
-  }
-#undef IB_DPMPP_COND
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  const SamplerGeom g = ib_sampler_geom(B * T * ld, T * ld, x, eps, hist, x0, z, mask);
+  const int grid = ib_grid_1d(g.n / (g.v8 ? 8 : 1), 256);
+  return ib_dispatch_dtype_width<8>(dtype, g.v8, [&](auto tag, auto width) {
+    using TY = decltype(tag);
+    hipLaunchKernelGGL((dpmpp_cond_step_kernel<TY, decltype(width)::value>), dim3(grid), dim3(256), 0, ib_s(stream), (TY*)x, (const TY*)eps,
+                       hist, (const TY*)x0, (const TY*)z, mask, coef, obs_coef, timesteps, num_steps, step, step_dev, t_out, B,
+                       g.per, g.n, (int)g.mix8);
+  });
 }
 
 extern "C" int ib_ensemble_stats(const void* x, float* mean, float* std_out, int64_t B, int64_t K, int64_t n, int dtype,
                                  ib_stream_t stream) {
   if (!x || !mean || !std_out || B <= 0 || K <= 0 || n <= 0) return IB_E_ARG;
   const int grid = ib_grid_1d(B * n, 256);
-  if (dtype == IB_F32)
-    hipLaunchKernelGGL((ensemble_stats_kernel<float>), dim3(grid), dim3(256), 0, ib_s(stream), (const float*)x, mean, std_out, B, K, n);
-  else if (dtype == IB_BF16)
-    hipLaunchKernelGGL((ensemble_stats_kernel<bf16_t>), dim3(grid), dim3(256), 0, ib_s(stream), (const bf16_t*)x, mean, std_out, B, K, n);
-  else return IB_E_DTYPE;
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  return ib_dispatch_dtype(dtype, [&](auto tag) {
+    using TY = decltype(tag);
+    hipLaunchKernelGGL((ensemble_stats_kernel<TY>), dim3(grid), dim3(256), 0, ib_s(stream), (const TY*)x, mean, std_out, B, K, n);
+  });
 }
 
 extern "C" int ib_counter_add(int32_t* counter, int32_t delta, ib_stream_t stream) {
