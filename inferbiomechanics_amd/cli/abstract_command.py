@@ -89,6 +89,27 @@ class AbstractCommand:
         raise NotImplementedError("model type 'analytical' is a nimblephysics CPU heuristic with no parameters "
                                   "(src/models/AnalyticalBaseline.py); it is outside the GPU hot path")
 
+    def diffusion_view(self, args: argparse.Namespace, split: str, geometry):
+        """[analyze, visualize --trial-frames] the split as denoiser windows that carry labels: seeded synthetic regression
+        windows (the seeds of open_dataset) or the .b3d windows, both through MotionWindowView"""
+        from ..data.AddBiomechanicsDataset import MotionWindowView, SyntheticWindowDataset
+        from ._common import open_dataset
+        if args.synthetic_windows > 0:
+            seed = {'train': 0, 'dev': 1, 'test': 2}.get(split, 3)
+            return MotionWindowView(SyntheticWindowDataset(args.synthetic_windows, args.history_len, args.stride,
+                                                           output_data_format=args.output_data_format, seed=seed))
+        return open_dataset(args, split, args.history_len, args.stride, args.output_data_format, geometry)
+
+    def diffusion_model(self, args: argparse.Namespace, view, device):
+        """the denoiser as `train` builds it (cli/train.py): feat_dim = the window row's width, window = F frames"""
+        from ._common import dtype_of
+        window = args.history_len // args.stride if args.stride > 1 else args.history_len
+        return self.get_model(view.num_dofs, view.num_contact_bodies, args.model_type, history_len=args.history_len,
+                              stride=args.stride, hidden_dims=args.hidden_dims, activation=args.activation,
+                              batchnorm=False, dropout=False, dropout_prob=0.0, root_history_len=10,
+                              output_data_format=args.output_data_format, device=device,
+                              compute_dtype=dtype_of(args), feat_dim=view.feat, window=window).to(device)
+
     @staticmethod
     def _model_device(device):
         """The reference default is device='cpu' (and analyze / visualize default to --device cpu).  This build has no CPU

@@ -11,7 +11,6 @@ import os
 import torch
 from torch.utils.data import DataLoader
 
-from ..data.AddBiomechanicsDataset import MotionWindowView, SyntheticWindowDataset
 from ..loss.RegressionLossEvaluator import RegressionLossEvaluator
 from ._common import add_additive_flags, add_component_flags, dtype_of, is_diffusion, open_dataset, pick_device
 from .abstract_command import AbstractCommand
@@ -161,24 +160,6 @@ class AnalyzeCommand(AbstractCommand):
             if spread is not None:
                 print(spread.line(split, num_samples))
         return True
-
-    def diffusion_view(self, args: argparse.Namespace, split: str, geometry) -> MotionWindowView:
-        """the split as denoiser windows that carry labels: seeded synthetic regression windows (the seeds of
-        open_dataset) or the .b3d windows, both through MotionWindowView"""
-        if args.synthetic_windows > 0:
-            seed = {'train': 0, 'dev': 1, 'test': 2}.get(split, 3)
-            return MotionWindowView(SyntheticWindowDataset(args.synthetic_windows, args.history_len, args.stride,
-                                                           output_data_format=args.output_data_format, seed=seed))
-        return open_dataset(args, split, args.history_len, args.stride, args.output_data_format, geometry)
-
-    def diffusion_model(self, args: argparse.Namespace, view: MotionWindowView, device):
-        """the denoiser as `train` builds it (cli/train.py): feat_dim = the window row's width, window = F frames"""
-        window = args.history_len // args.stride if args.stride > 1 else args.history_len
-        return self.get_model(view.num_dofs, view.num_contact_bodies, args.model_type, history_len=args.history_len,
-                              stride=args.stride, hidden_dims=args.hidden_dims, activation=args.activation,
-                              batchnorm=False, dropout=False, dropout_prob=0.0, root_history_len=10,
-                              output_data_format=args.output_data_format, device=device,
-                              compute_dtype=dtype_of(args), feat_dim=view.feat, window=window).to(device)
 
 
 class EnsembleSpread:

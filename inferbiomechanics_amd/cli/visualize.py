@@ -2,15 +2,25 @@
 is a nimblephysics NimbleGUI browser playback (:126-258), which is third-party GUI code outside the GPU hot
 path.  What IS on the path -- a batch-1 model forward + loss evaluation per tick
 (:157-200) -- is run here over the first windows of the split and printed, so a checkpoint can be inspected
-without the GUI."""
+without the GUI.
+
+`--trial-frames F` (diffusion-transformer checkpoints) is the command-line route to stitched trial sampling
+(models/DiffusionLabelPredictor.predict_trial): F consecutive frames of a trial, read at the dataset's frame stride, are
+labelled as ONE sequence of overlapping windows and printed next to the labels the per-window sampler gives on disjoint
+windows of the same frames."""
 import argparse
 import os
 
 import torch
 
 from ..loss.RegressionLossEvaluator import RegressionLossEvaluator
-from ._common import add_additive_flags, add_component_flags, dtype_of, open_dataset, pick_device
+from ..data.AddBiomechanicsDataset import LOSS_KEY_ORDER
+from ..diffusion.schedule import STITCH_BLENDS, stitch_layout
+from ._common import add_additive_flags, add_component_flags, dtype_of, is_diffusion, open_dataset, pick_device
 from .abstract_command import AbstractCommand
+from .analyze import window_subject, window_trial
+
+LABEL_NAMES = ('cop', 'force', 'torque', 'wrench')       # LOSS_KEY_ORDER, as the trial report names the keys
 
 
 class VisualizeCommand(AbstractCommand):
@@ -38,6 +48,15 @@ class VisualizeCommand(AbstractCommand):
         p.add_argument('--num-frames', type=int, default=8, help='How many windows to evaluate and print.')
         p.add_argument('--use-ema', action='store_true', default=False,
                        help='Load the EMA weights of the checkpoint (`train --ema-decay`) instead of its last weights.')
+        p.add_argument('--trial-frames', type=int, default=0,
+                       help='[diffusion-transformer] label this many consecutive frames of a trial (at the frame stride) as '
+                            'one stitched sequence and print them next to the per-window labels; --num-frames trials.')
+        p.add_argument('--trial-hop', type=int, default=None,
+                       help='[--trial-frames] frames between the starts of the overlapping windows (default: window // 2).')
+        p.add_argument('--trial-blend', type=str, default='ramp', choices=list(STITCH_BLENDS),
+                       help='[--trial-frames] how the windows that cover a frame are blended.')
+        p.add_argument('--sample-steps', type=int, default=100, help='[--trial-frames] steps of the sampling loop.')
+        p.add_argument('--sample-seed', type=int, default=0, help='[--trial-frames] seed of the start noise.')
 
     def run(self, args: argparse.Namespace):
         if 'command' in args and args.command != 'visualize':
@@ -49,6 +68,8 @@ class VisualizeCommand(AbstractCommand):
             have_gui = False
         checkpoint_dir = os.path.join(os.path.abspath(args.checkpoint_dir), args.model_type)
         device = pick_device(args)
+        if getattr(args, 'trial_frames', 0):
+            return self.run_trials(args, checkpoint_dir, device)
         dataset = open_dataset(args, 'test', args.history_len, args.stride, args.output_data_format,
                                self.ensure_geometry(args.geometry_folder))
         model = self.get_model(dataset.num_dofs, dataset.num_contact_bodies, args.model_type,
@@ -72,4 +93,72 @@ class VisualizeCommand(AbstractCommand):
                 loss = evaluator(inputs, outputs, labels, [subj], [trial], args)
                 print(f"window {frame}: loss {float(loss):.6f}")
         evaluator.print_report(args)
+        return True
+
+    def run_trials(self, args: argparse.Namespace, checkpoint_dir: str, device) -> bool:
+        """--trial-frames F: for each of the first --num-frames trials (trial k starts at window k F of the split) the four
+        label blocks of its F frames from predict_trial, and from the per-window sampler on the disjoint windows at 0, T,
+        2 T, ... plus a last one ending on the last frame (a frame takes the first window that covers it).  Per frame one
+        row with the force block of both; per trial and label key the RMS error of both against the labels, their RMS
+        difference, and for the force block the mean jump |x[f] - x[f - 1]| across the per-window boundaries."""
+        from ..models.DiffusionLabelPredictor import DiffusionLabelPredictor
+        F = int(args.trial_frames)
+        if not is_diffusion(args.model_type):
+            raise SystemExit("--trial-frames labels a trial with a diffusion denoiser: pass --model-type diffusion-transformer")
+        if args.sample_steps < 1 or args.num_frames < 1:
+            raise SystemExit("--sample-steps and --num-frames must be >= 1")
+        view = self.diffusion_view(args, 'test', self.ensure_geometry(args.geometry_folder))
+        dataset = view.dataset
+        model = self.diffusion_model(args, view, device)
+        T = getattr(model, 'window', None)
+        if T is None:
+            raise SystemExit(f"--trial-frames needs a denoiser with a window (--model-type diffusion-transformer); "
+                             f"{args.model_type} has none")
+        self.load_latest_checkpoint(model, checkpoint_dir=checkpoint_dir, use_ema=getattr(args, 'use_ema', False))
+        model.eval()
+        hop = T // 2 if args.trial_hop is None else int(args.trial_hop)
+        try:
+            W = stitch_layout(F, T, hop, args.trial_blend)[0].numel()
+            start, cover = stitch_layout(F, T, T, 'uniform')[:2]        # the disjoint windows of the per-window sampler
+        except ValueError as e:
+            raise SystemExit(f"--trial-frames / --trial-hop: {e}")
+        predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
+                                            output_data_format=args.output_data_format)
+        gather = start.long()[:, None] + torch.arange(T)[None, :]      # [Wd, T] trial frames of the disjoint windows
+        w0 = cover[:, 0].long()
+        t0 = torch.arange(F) - start.long()[w0]
+        seams = start[1:].long()
+        done = 0
+        for k in range(args.num_frames):
+            index = k * F
+            if index >= len(dataset):
+                break
+            try:
+                inputs, labels, subj, trial = dataset.read_trial(index, F)
+            except ValueError as e:
+                print(f"trial {k}: skipped ({e})")
+                continue
+            inputs = {key: v.unsqueeze(0) for key, v in inputs.items()}
+            stitched = predictor.predict_trial(inputs, hop=hop, blend=args.trial_blend, draw=k)
+            windows = predictor({key: v[0, gather] for key, v in inputs.items()}, draw=k * gather.shape[0])
+            print(f"trial {k} ({window_subject(dataset, [subj])} / {window_trial(dataset, [subj], [trial])}): {F} frames, "
+                  f"stitched as {W} windows of {T} every {hop} frames ({args.trial_blend}) | {gather.shape[0]} disjoint windows")
+            print(f"{'frame':>5} {'win':>3}  {'stitched force':<48} | per-window force")
+            fmt = lambda row: ' '.join(f'{float(v):+7.3f}' for v in row)
+            sf = stitched[LOSS_KEY_ORDER[1]][0].cpu()
+            wf = windows[LOSS_KEY_ORDER[1]].cpu()[w0, t0]
+            for f in range(F):
+                print(f"{f:>5} {int(w0[f]):>3}  {fmt(sf[f])} | {fmt(wf[f])}")
+            rms = lambda d: float(d.double().pow(2).mean().sqrt())
+            for name, key in zip(LABEL_NAMES, LOSS_KEY_ORDER):
+                s, w, y = stitched[key][0].cpu(), windows[key].cpu()[w0, t0], labels[key].float()
+                print(f"trial {k} {name:>6}: RMS err stitched {rms(s - y):.6f}, per-window {rms(w - y):.6f}, "
+                      f"RMS stitched - per-window {rms(s - w):.6f}")
+            if seams.numel():
+                jump = lambda x: float((x[seams] - x[seams - 1]).abs().mean())
+                print(f"trial {k}  force: mean jump across the {seams.numel()} per-window boundaries: stitched {jump(sf):.6f}, "
+                      f"per-window {jump(wf):.6f}")
+            done += 1
+        if not done:
+            raise SystemExit(f"--trial-frames {F}: no trial of the split holds {F} frames at stride {args.stride}")
         return True

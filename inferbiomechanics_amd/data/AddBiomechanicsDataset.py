@@ -213,10 +213,14 @@ class AddBiomechanicsDataset(Dataset):
     def _np_dtype(self):
         return torch.empty(0, dtype=self.dtype).numpy().dtype
 
-    def _read(self, index: int):
+    def _read(self, index: int, frames: Optional[int] = None):
         subject_index, trial, start = (int(v) for v in self.windows[index])
         subject = self.subjects[subject_index]
-        n = self.window_size // self.stride
+        n = self.window_size // self.stride if frames is None else int(frames)
+        if frames is not None and (n < 1 or start + (n - 1) * self.stride >= subject.getTrialLength(trial)):
+            raise ValueError(f"read_trial: {n} frames at stride {self.stride} from frame {start} do not fit trial {trial} of "
+                             f"{os.path.basename(self.subject_paths[subject_index])} "
+                             f"({subject.getTrialLength(trial)} frames)")
         frames = subject.readFrames(trial, start, n, stride=self.stride, includeSensorData=False,
                                     includeProcessingPasses=True)
         assert len(frames) == n
@@ -242,7 +246,16 @@ class AddBiomechanicsDataset(Dataset):
         return np.stack([np.asarray(getattr(p, field), dtype=np.float64) for p in passes])
 
     def __getitem__(self, index: int) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor], int, int]:
-        subject, subject_index, trial, first, first_out, last = self._read(index)
+        return self._item(*self._read(index))
+
+    def read_trial(self, index: int, frames: int):
+        """`frames` consecutive frames (at the frame stride) of the trial of window `index`, from that window's first frame,
+        as the tuple of ``__getitem__`` with `frames` rows per tensor: the window itself is its first ``window_size // stride``
+        rows.  Only the window's own taps are known to carry measured ground-reaction forces; labels of later frames may be
+        unmeasured.  A stretch that runs past the end of the trial is a ValueError."""
+        return self._item(*self._read(index, frames))
+
+    def _item(self, subject, subject_index, trial, first, first_out, last):
         npd = self._np_dtype()
         tens = lambda passes, field: torch.from_numpy(self._stack(passes, field).astype(npd))
         inputs = {
@@ -368,10 +381,21 @@ class SyntheticWindowDataset(Dataset):
         return self.num_windows
 
     def __getitem__(self, index: int) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor], int, int]:
+        return self._draw(index, self.frames, self.out_frames)
+
+    def read_trial(self, index: int, frames: int):
+        """a synthetic trial of `frames` frames in the tuple layout of ``__getitem__`` (its own seeded draw: the synthetic
+        windows are independent of each other, so none is a stretch of it)"""
+        if self.output_data_format != 'all_frames':
+            raise ValueError("read_trial: a trial carries labels for every frame, it needs output_data_format 'all_frames'")
+        if int(frames) < 1:
+            raise ValueError(f"read_trial: frames must be >= 1, got {frames}")
+        return self._draw(index, int(frames), int(frames))
+
+    def _draw(self, index: int, frames: int, F: int):
         g = torch.Generator().manual_seed(self.seed * 1000003 + index)
         ws = input_key_widths(self.num_dofs, self.history_width)
-        inputs = {k: torch.randn(self.frames, w, generator=g) for k, w in zip(INPUT_KEY_ORDER, ws)}
-        F = self.out_frames
+        inputs = {k: torch.randn(frames, w, generator=g) for k, w in zip(INPUT_KEY_ORDER, ws)}
         labels = {
             OutputDataKeys.GROUND_CONTACT_COPS_IN_ROOT_FRAME: 0.3 * torch.randn(F, 6, generator=g),
             OutputDataKeys.GROUND_CONTACT_FORCES_IN_ROOT_FRAME: 10.0 * torch.randn(F, 6, generator=g),

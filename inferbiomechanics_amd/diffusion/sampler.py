@@ -16,7 +16,7 @@ import torch
 
 from .. import hip
 from ..plans import ParamSource
-from .schedule import OBSERVATIONS, SOLVERS, SPACINGS
+from .schedule import OBSERVATIONS, SOLVERS, SPACINGS, stitch_layout
 
 
 class DDIMSampler:
@@ -327,3 +327,177 @@ class ConditionalDDIMSampler(DDIMSampler):
             hip.ddim_cond_step_noise(x, eps, b["x0"], b["z"], b["mask"], tabs.ddim_coef_eta, tabs.obs_coef,
                                      tabs.obs_noise_coef, tabs.ddim_t, b["win"], self.seed, step_dev=ctr, t_out=t_vec,
                                      D=self._D)
+
+
+class StitchedDDIMSampler(DDIMSampler):
+    """Samples a whole trial of F >= model.window frames with a denoiser that sees windows of T = model.window frames
+    (MultiDiffusion / DiffCollage stitching).  The trial is covered by overlapping windows (schedule.stitch_layout: a window
+    every `hop` frames, default T // 2, and a last one that ends on the last frame); after every denoiser evaluation the
+    noise predictions of all windows that cover a trial frame are blended ('ramp': a window fades in and out over its
+    overlap; 'uniform') and every copy of that frame receives the same updated value, so the windows stay one sequence all
+    the way down instead of diverging from the first step.  The state is the window batch [N * W, T, D] the denoiser plan
+    consumes: the plans, the captured one-step graph and the launch count per step are DDIMSampler's; only the update launch
+    differs (ib_stitch_ddim_step / ib_stitch_dpmpp_step, csrc/stitch.hip).  With F == T it is ConditionalDDIMSampler (or
+    DDIMSampler without observations) bit for bit, with hop == T and F a multiple of T the per-window sampler on disjoint
+    windows.
+
+    observed / mask_cols make it the masked loop of ConditionalDDIMSampler: mask_cols is a [D] bool, the same columns
+    observed in every frame (a per-frame mask would disagree with itself where windows overlap).  Deterministic only:
+    eta > 0 is refused, the step noise of the stochastic update is keyed by window and in-window frame and would have to be
+    keyed by trial frame.  The constructor takes `eta` only to refuse it: code that builds its samplers from one set of
+    arguments gets the reason instead of a TypeError; any value but 0 is a ValueError.
+
+    `layout` (the tables of the last trial sampled) and `to_windows` (a trial tensor cut into that layout's windows) are
+    for callers that want the same windows for a per-window sampler.  One layout is kept: a trial of another length
+    replaces it, and the step is captured again."""
+
+    def __init__(self, model, num_sample_steps: int = 100, hop: Optional[int] = None, blend: str = "ramp",
+                 use_graph: bool = True, solver: str = "ddim", spacing: str = "time", observations: str = "noised",
+                 seed: Optional[int] = None, eta: float = 0.0):
+        if float(eta) != 0.0:
+            raise ValueError(f"StitchedDDIMSampler is deterministic: eta must be 0, got {eta} (the step noise of an eta > 0 "
+                             f"loop is keyed by window and in-window frame, not by trial frame)")
+        super().__init__(model, num_sample_steps, use_graph, 0.0, seed, solver, spacing)
+        if observations not in OBSERVATIONS:
+            raise ValueError(f"observations must be one of {OBSERVATIONS}, got {observations!r}")
+        self.observations = observations
+        if getattr(model, "window", None) is None:
+            raise ValueError("StitchedDDIMSampler needs a denoiser that states its window (model.window frames)")
+        self.T = int(model.window)
+        self.hop = self.T // 2 if hop is None else int(hop)
+        self.blend = blend
+        stitch_layout(3 * self.T, self.T, self.hop, blend)     # refuses a bad hop or blend here, not at the first call
+        self._cond = None
+        self._lay = None                     # the layout of the last trial length sampled, the only one kept
+        self._mask_ok = None                 # (mask_cols, (version, cond_cols)) of the last mask 'clean' mode accepted
+
+    @property
+    def layout(self) -> Optional[dict]:
+        """the layout of the last trial sampled (None before the first call): the kernel's tables 'start', 'cover', 'wn' on
+        the device, 'F' and 'W', the gather index 'gather' ([W, T] trial frames) and each frame's first copy 'w0', 't0'"""
+        return self._lay
+
+    def _layout(self, F: int, dev):
+        """the layout of a trial of F frames on `dev`: the kernel's tables, the gather index trial -> windows ([W, T] trial
+        frames) and each frame's first copy (window, in-window frame).  Built when F or the device changes."""
+        key = (F, str(dev), self.hop, self.blend)
+        if self._lay is None or self._lay["key"] != key:
+            start, cover, wn, _ = stitch_layout(F, self.T, self.hop, self.blend)
+            gather = start.long()[:, None] + torch.arange(self.T)[None, :]
+            w0 = cover[:, 0].long()
+            t0 = torch.arange(F) - start.long()[w0]
+            self._lay = {"start": start.to(dev), "cover": cover.to(dev), "wn": wn.to(dev), "gather": gather.to(dev),
+                         "w0": w0.to(dev), "t0": t0.to(dev), "F": F, "W": start.numel(), "key": key}
+        return self._lay
+
+    def to_windows(self, trial: torch.Tensor) -> torch.Tensor:
+        """[N, F, D] -> [N * W, T, D]: every window's frames in the layout of the last trial sampled (plumbing: an index, no
+        arithmetic)"""
+        if self._lay is None or trial.dim() != 3 or trial.shape[1] != self._lay["F"]:
+            raise ValueError(f"to_windows: a [N, F, D] trial of the last sampled length is needed, got {tuple(trial.shape)}")
+        N, F, D = trial.shape
+        return trial[:, self._lay["gather"].to(trial.device)].reshape(N * self._lay["W"], self.T, D)
+
+    def _to_trial(self, windows: torch.Tensor, N: int) -> torch.Tensor:
+        """[N * W, T, D] -> [N, F, D] from each frame's first copy"""
+        lay = self._lay
+        w = windows.view(N, lay["W"], self.T, windows.shape[-1])
+        return w[:, lay["w0"].to(w.device), lay["t0"].to(w.device)].contiguous()
+
+    def _observations(self) -> Optional[str]:
+        return None if self._cond is None else self.observations      # sample() checked the attribute for this call
+
+    def _check_clean_cols(self, mask_cols: torch.Tensor, D: int):
+        """'clean' mode: the model was trained with exactly its first cond_cols columns clean.  The verdict is kept per mask
+        tensor, its version and cond_cols (as ConditionalDDIMSampler keeps it), so a loop that passes the same mask again
+        compares nothing and, with a device mask, does not wait for the device."""
+        C = int(getattr(self.model, "cond_cols", 0))
+        key = (mask_cols._version, C)
+        if self._mask_ok is not None and self._mask_ok[0] is mask_cols and self._mask_ok[1] == key:
+            return
+        want = torch.zeros(D, dtype=torch.bool, device=mask_cols.device)
+        want[:max(C, 0)] = True
+        if not 0 < C < D or not torch.equal(mask_cols, want):
+            self._mask_ok = None
+            raise ValueError(f"observations='clean': mask_cols must mark exactly the first cond_cols columns the denoiser "
+                             f"was trained on (`train --cond-cols N`, 0 < N < {D}); this model's cond_cols is {C}")
+        self._mask_ok = (mask_cols, key)
+
+    @torch.no_grad()
+    def sample(self, z: torch.Tensor, observed: Optional[torch.Tensor] = None, mask_cols: Optional[torch.Tensor] = None,
+               steps: Optional[int] = None) -> torch.Tensor:
+        """z [N, F, D] ~ N(0, 1), the trial's start draw -> x_0 [N, F, D].  observed [N, F, D] and mask_cols [D] bool (True:
+        the column is observed in every frame) come together; the result equals the observation, in the compute dtype, in
+        those columns.  `steps` truncates the loop."""
+        if z.dim() != 3:
+            raise ValueError(f"z must be [N, F, D], got {tuple(z.shape)}")
+        N, F, D = z.shape
+        if (observed is None) != (mask_cols is None):
+            raise ValueError("observed and mask_cols come together (the masked loop) or not at all")
+        if observed is not None:
+            if tuple(observed.shape) != (N, F, D):
+                raise ValueError(f"observed must be {(N, F, D)} like z, got {tuple(observed.shape)}")
+            if not isinstance(mask_cols, torch.Tensor) or tuple(mask_cols.shape) != (D,) or mask_cols.dtype != torch.bool:
+                raise ValueError(f"mask_cols must be a [D] = [{D}] bool tensor (the same columns are observed in every "
+                                 f"frame), got {tuple(getattr(mask_cols, 'shape', ()))} {getattr(mask_cols, 'dtype', None)}")
+            if self.observations not in OBSERVATIONS:           # the attribute may be changed between calls
+                raise ValueError(f"observations must be one of {OBSERVATIONS}, got {self.observations!r}")
+            if self.observations == "clean":
+                self._check_clean_cols(mask_cols, D)
+        dev = z.device if (z.is_cuda or hip._dry_run) else next(self.model.parameters()).device
+        self._lay = self._layout(F, dev)                       # refuses F < model.window
+        self._N = N
+        self._cond = None if observed is None else (observed, mask_cols)
+        try:
+            out = super().sample(self.to_windows(z.to(dev)), steps)
+            return self._to_trial(out, N)
+        finally:
+            self._cond = None
+
+    @torch.no_grad()
+    def sample_noise(self, batch: int, frames: int, feat: int, observed: Optional[torch.Tensor] = None,
+                     mask_cols: Optional[torch.Tensor] = None, seed: Optional[int] = None, draw: int = 0,
+                     steps: Optional[int] = None) -> torch.Tensor:
+        """as DDIMSampler.sample_noise: z [batch, frames, feat] drawn on the device from (seed, draw)"""
+        return self.sample(self.draw_start(batch, frames, feat, seed, draw), observed, mask_cols, steps)
+
+    def _extra_sig(self, tabs) -> tuple:
+        lay = self._lay
+        cond = () if self._cond is None else (tabs.obs_coef.data_ptr(), tabs.observations)
+        return ("stitch", self._N, lay["F"], self.hop, self.blend, lay["start"].data_ptr(), lay["cover"].data_ptr(),
+                lay["wn"].data_ptr()) + cond
+
+    def _extra_buffers(self, B, T, D, Dp, dev, dtype):
+        if self._cond is None:
+            return {}
+        return {"x0": torch.zeros((B, T, Dp), dtype=dtype, device=dev),
+                "z": torch.zeros((B, T, Dp), dtype=dtype, device=dev),
+                "mask": torch.zeros((T, Dp), dtype=torch.uint8, device=dev)}
+
+    def _begin(self, x, tabs):
+        if self._cond is None:
+            return
+        observed, mask_cols = self._cond
+        D = self._D
+        x0, z, m = self._bufs["x0"], self._bufs["z"], self._bufs["mask"]
+        x0[:, :, :D].copy_(self.to_windows(observed.to(device=x0.device, dtype=x0.dtype)))
+        m[:, :D].copy_(mask_cols.to(device=m.device, dtype=torch.uint8)[None, :].expand(m.shape[0], D))
+        z.copy_(x)
+        hip.ddim_cond_init(x, x0, z, m, tabs.obs_coef, D=D)
+        if self._lay["W"] > 1:
+            # the invariant at the start: every copy of a trial element holds its first copy's bits (the start kernel rounds
+            # by position in the window batch, which differs between the copies when the row pitch is no multiple of 8)
+            x.copy_(self.to_windows(self._to_trial(x, self._N)))
+
+    def _update(self, x, eps, ctr, t_vec, tabs):
+        b, lay = self._bufs, self._lay
+        shape = (self._N, lay["W"]) + tuple(x.shape[1:])
+        v = lambda t: t.view(shape)
+        cond = self._cond is not None
+        x0, z, m, oc = (v(b["x0"]), v(b["z"]), b["mask"], tabs.obs_coef) if cond else (None, None, None, None)
+        if self.solver == "dpmpp2m":
+            hip.stitch_dpmpp_step(v(x), v(eps), v(b["hist"]), x0, z, m, tabs.dpmpp_coef, oc, tabs.ddim_t, lay["start"],
+                                  lay["cover"], lay["wn"], step_dev=ctr, t_out=t_vec, D=self._D)
+        else:
+            hip.stitch_ddim_step(v(x), v(eps), x0, z, m, tabs.ddim_coef, oc, tabs.ddim_t, lay["start"], lay["cover"],
+                                 lay["wn"], step_dev=ctr, t_out=t_vec, D=self._D)

@@ -183,6 +183,47 @@ def dpmpp_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100,
     return torch.stack(rows)
 
 
+STITCH_KMAX = 8                 # IB_STITCH_KMAX (include/ib_hip_stitch.h): the most windows that may cover one trial frame
+STITCH_BLENDS = ("uniform", "ramp")
+
+
+def stitch_layout(F: int, T: int, hop: int, blend: str = "ramp"):
+    """The layout of a trial of F frames denoised as overlapping windows of T frames (sampler.StitchedDDIMSampler, the tables
+    of ib_stitch_ddim_step) -> (start, cover, wn, KMAX):
+      start int32 [W]       window starts 0, hop, 2 hop, ... while start + T <= F, plus a last window at F - T when the grid
+                            does not land there: every frame is covered, the starts strictly increase
+      cover int32 [F, 2]    per trial frame the first covering window and how many cover it (they are consecutive)
+      wn    fp32  [F, KMAX] the blend weights of the covering windows in window order, normalised per frame in float64 to sum
+                            to 1 and cast once; slots beyond the count are 0
+    blend 'uniform': equal weights.  'ramp': the raw weight of in-window frame t is min(t + 1, T - t, R) / R with
+    R = max(T - hop, 1), a trapezoid, so a window fades in and out over its overlap."""
+    F, T, hop = int(F), int(T), int(hop)
+    if T < 1 or F < T:
+        raise ValueError(f"F = {F} must be at least the window T = {T}: a trial shorter than a window cannot be stitched")
+    if hop < 1 or hop > T:
+        raise ValueError(f"hop = {hop} must be in 1 .. T = {T} (a larger hop leaves frames uncovered)")
+    if blend not in STITCH_BLENDS:
+        raise ValueError(f"blend must be one of {STITCH_BLENDS}, got {blend!r}")
+    starts = list(range(0, F - T + 1, hop))
+    if starts[-1] != F - T:
+        starts.append(F - T)
+    R = max(T - hop, 1)
+    start = torch.tensor(starts, dtype=torch.int32)
+    cover = torch.zeros((F, 2), dtype=torch.int32)
+    w64 = torch.zeros((F, STITCH_KMAX), dtype=torch.float64)
+    for f in range(F):
+        ws = [w for w, s0 in enumerate(starts) if s0 <= f < s0 + T]
+        if len(ws) > STITCH_KMAX:
+            raise ValueError(f"hop = {hop} is too small for T = {T}: frame {f} is covered by {len(ws)} windows, more than "
+                             f"{STITCH_KMAX}")
+        cover[f, 0], cover[f, 1] = ws[0], len(ws)
+        for k, w in enumerate(ws):
+            t = f - starts[w]
+            w64[f, k] = 1.0 if blend == "uniform" else min(t + 1, T - t, R) / R
+    wn = (w64 / w64.sum(dim=1, keepdim=True)).to(torch.float32)
+    return start, cover, wn, STITCH_KMAX
+
+
 def timestep_embedding_table(num_steps: int, dim: int, max_period: float = 10000.0) -> torch.Tensor:
     """[num_steps, dim] float64: row t = [sin(t w), cos(t w)]."""
     half = dim // 2

@@ -6,7 +6,8 @@ device pointers + sizes + the current HIP stream to the library.  There is NO CP
 fallback: if the library is missing or a call fails, a ``HipError`` is raised.
 
 The header is the only declaration of the ABI: the ctypes signatures (``_SIGS``) are parsed from it when this
-module is imported, so a new entry point needs its declaration there and its wrapper here, nothing else.
+module is imported, so a new entry point needs its declaration there and its wrapper here, nothing else.  The stitched
+sampler updates are declared in a second header, ``include/ib_hip_stitch.h``, parsed the same way into ``_STITCH_SIGS``.
 """
 from __future__ import annotations
 
@@ -24,6 +25,7 @@ LIB_PATH = os.environ.get("IB_HIP_LIB") or os.path.join(_HERE, "lib", "libib_hip
 # IB_HIP_LIB by tools/ and by the tests that compare kernel families -- the product never loads it
 AB_LIB_PATH = os.path.join(_HERE, "lib", "ab", "libib_hip_ab.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip.h")
+STITCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_stitch.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -76,21 +78,42 @@ def _parse_header(text: str) -> dict:
     return sigs
 
 
-def _read_header() -> str:
+def _read_header(path: Optional[str] = None) -> str:
+    path = HEADER_PATH if path is None else path
     try:
-        with open(HEADER_PATH) as f:
+        with open(path) as f:
             return f.read()
     except OSError as e:
-        raise HipError(f"the C-ABI header is missing: looked for {HEADER_PATH} ({e.strerror}); the ctypes signatures are "
+        raise HipError(f"the C-ABI header is missing: looked for {path} ({e.strerror}); the ctypes signatures are "
                        f"derived from it, so the binding cannot work without it") from None
 
 
 _SIGS = _parse_header(_read_header())
+# the second header (stitched trial sampling), a table of its own: _SIGS and declared_symbols() describe ib_hip.h only
+_STITCH_SIGS = _parse_header(_read_header(STITCH_HEADER_PATH))
+if set(_SIGS) & set(_STITCH_SIGS):
+    raise HipError(f"declared in both headers: {sorted(set(_SIGS) & set(_STITCH_SIGS))}")
+_kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_STITCH_KMAX[ \t]+(\d+)[ \t]*$", _read_header(STITCH_HEADER_PATH), flags=re.M)
+if _kmax is None:
+    raise HipError(f"{STITCH_HEADER_PATH} does not define IB_STITCH_KMAX")
+# the header's value, the one the kernels are compiled with; schedule.STITCH_KMAX (the host layout) is checked against it by
+# tests/test_stitch_plumbing_cpu.py
+STITCH_KMAX = int(_kmax.group(1))
 
 
 def declared_symbols() -> List[str]:
     """Every function the public header declares (used by the CPU test that checks the exports)."""
     return sorted(_SIGS)
+
+
+def stitch_symbols() -> List[str]:
+    """Every function include/ib_hip_stitch.h declares"""
+    return sorted(_STITCH_SIGS)
+
+
+def _sig(name: str):
+    """(restype, argtypes) of an entry point of either header"""
+    return _SIGS[name] if name in _SIGS else _STITCH_SIGS[name]
 
 
 # pure host queries: no launch, no stream
@@ -119,7 +142,7 @@ class _DryRunLib:
         self.args = []           # per faked call: (name, the arguments as the wrapper passed them)
 
     def __getattr__(self, name):
-        res, args = _SIGS[name]
+        res, args = _sig(name)
         real = getattr(self._real, name)
         if not _is_launch(name, handed_through=()):      # nothing but the host queries may reach the real library
             return real
@@ -365,7 +388,7 @@ def lib():
             raise HipError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C inferbiomechanics_amd/csrc` (hipcc --offload-arch=gfx950). There is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in list(_SIGS.items()) + list(_STITCH_SIGS.items()):
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -2256,6 +2279,96 @@ def dpmpp_cond_step(x, eps, hist, x0, z, mask, coef, obs_coef, timesteps, step=0
     _check(lib().ib_dpmpp_cond_step(_ptr(x), _ptr(eps), _ptr(hist), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef),
                                     _ptr(obs_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out), B, T, D, ld,
                                     dtype_code(x.dtype), stream_ptr()), "ib_dpmpp_cond_step")
+    return x
+
+
+def _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D):
+    """the window-batch state of a stitched update, x [N, W, T, ld] with eps like it, and its layout tables (schedule.
+    stitch_layout, on x's device): start int32 [W], cover int32 [F, 2], wn fp32 [F, STITCH_KMAX], checked for what the kernel
+    trusts -- every window inside the trial, every frame's windows really covering it.  x0 / z / mask / obs_coef: all None
+    (the unconditional loop) or all given, as _cond_operands takes them.  -> (N, W, T, F, D, ld)"""
+    _req(x, "x", x.dtype, 4)
+    if not x.is_contiguous():
+        raise HipError(f"{what}: x must be a contiguous [N, W, T, ld] state")
+    N, W, T, ld = x.shape
+    D = ld if D is None else int(D)
+    if D <= 0 or D > ld:
+        raise HipError(f"{what}: D = {D} must be in 1 .. ld = {ld}")
+    _like_x(what, "eps", eps, x)
+    given = [t is not None for t in (x0, z, mask, obs_coef)]
+    if any(given) and not all(given):
+        raise HipError(f"{what}: x0, z, mask and obs_coef come together (the masked loop) or not at all")
+    if all(given):
+        _like_x(what, "x0", x0, x)
+        _like_x(what, "z", z, x)
+        _req(mask, "mask", torch.uint8, 2)
+        if tuple(mask.shape) != (T, ld) or not mask.is_contiguous():
+            raise HipError(f"{what}: mask must be contiguous uint8 [T, ld] = [{T}, {ld}], got {tuple(mask.shape)}")
+        _req(obs_coef, "obs_coef", torch.float32, 2)
+        if obs_coef.shape[1] != 2 or not obs_coef.is_contiguous():
+            raise HipError(f"{what}: obs_coef must be contiguous [S + 1, 2] fp32")
+    _req(start, "start", torch.int32, 1)
+    _req(cover, "cover", torch.int32, 2)
+    _req(wn, "wn", torch.float32, 2)
+    F = cover.shape[0]
+    if start.numel() != W or tuple(cover.shape) != (F, 2) or tuple(wn.shape) != (F, STITCH_KMAX) or F < T:
+        raise HipError(f"{what}: the layout tables must be start [W] = [{W}], cover [F, 2], wn [F, {STITCH_KMAX}] with "
+                       f"F >= T = {T}; got {tuple(start.shape)}, {tuple(cover.shape)}, {tuple(wn.shape)}")
+    for name, t in (("start", start), ("cover", cover), ("wn", wn)):
+        if not t.is_contiguous() or t.device != x.device:
+            raise HipError(f"{what}: {name} must be contiguous and on the device of x ({x.device})")
+    # the kernel trusts start and cover: check them when the tables change.  The verdict of the last pair is kept (by
+    # identity, so the addresses are not reused, and by version), so a loop that passes its tables again copies nothing back
+    # from the device.  A captured step relies on that: DDIMSampler._loop runs one eager step right before the capture with
+    # the same tables, and the .cpu() below would fail inside a capture.
+    global _stitch_checked
+    key = (start._version, cover._version, W, T, F)
+    c = _stitch_checked
+    if c is None or c[0] is not start or c[1] is not cover or c[2] != key:
+        st, cv = start.cpu().long(), cover.cpu().long()
+        fr = torch.arange(F)
+        ok = bool((st >= 0).all() and (st + T <= F).all() and (cv[:, 1] >= 1).all() and (cv[:, 1] <= STITCH_KMAX).all()
+                  and (cv[:, 0] >= 0).all() and (cv[:, 0] + cv[:, 1] <= W).all())
+        if ok:
+            first, last = st[cv[:, 0]], st[cv[:, 0] + cv[:, 1] - 1]
+            ok = bool((first <= fr).all() and (fr < first + T).all() and (last <= fr).all() and (fr < last + T).all()
+                      and (W == 1 or (st[1:] > st[:-1]).all()))
+        if not ok:
+            raise HipError(f"{what}: start / cover do not describe {W} windows of {T} frames covering a trial of {F} frames")
+        _stitch_checked = (start, cover, key)
+    return N, W, T, F, D, ld
+
+
+_stitch_checked = None   # (start, cover, key) of the last layout tables _stitch_operands accepted
+
+
+def stitch_ddim_step(x, eps, x0, z, mask, coef, obs_coef, timesteps, start, cover, wn, step=0, step_dev=None, t_out=None,
+                     D=None):
+    """DDIM update of a stitched trial in place (csrc/stitch.hip) over the window batch x [N, W, T, ld]: the noise predictions
+    of the windows that cover a trial frame are blended with the weights wn, the element is updated once and every copy
+    receives the result; start / cover / wn: schedule.stitch_layout on the device.  x0, z, mask [T, ld], obs_coef: all None,
+    or the masked loop's operands as in ddim_cond_step.  t_out int64 [N * W]."""
+    what = "stitch_ddim_step"
+    N, W, T, F, D, ld = _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D)
+    S = _step_tables(what, coef, 2, timesteps, N * W, t_out, step_dev, obs_coef)
+    _check(lib().ib_stitch_ddim_step(_ptr(x), _ptr(eps), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef),
+                                     _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out), _ptr(start), _ptr(cover),
+                                     _ptr(wn), N, W, T, F, D, ld, dtype_code(x.dtype), stream_ptr()), "ib_stitch_ddim_step")
+    return x
+
+
+def stitch_dpmpp_step(x, eps, hist, x0, z, mask, coef, obs_coef, timesteps, start, cover, wn, step=0, step_dev=None,
+                      t_out=None, D=None):
+    """DPM-Solver++(2M) update of a stitched trial in place: as stitch_ddim_step with coef [S, 5] and the fp32 history hist
+    [N, W, T, ld], read from an element's first copy and written to all of them (dpmpp_step's arithmetic)."""
+    what = "stitch_dpmpp_step"
+    N, W, T, F, D, ld = _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D)
+    _like_x(what, "hist", hist, x, torch.float32)
+    S = _step_tables(what, coef, 5, timesteps, N * W, t_out, step_dev, obs_coef)
+    _check(lib().ib_stitch_dpmpp_step(_ptr(x), _ptr(eps), _ptr(hist), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef),
+                                      _ptr(obs_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out), _ptr(start),
+                                      _ptr(cover), _ptr(wn), N, W, T, F, D, ld, dtype_code(x.dtype), stream_ptr()),
+           "ib_stitch_dpmpp_step")
     return x
 
 

@@ -12,7 +12,7 @@ import torch
 
 from .. import hip
 from ..data.AddBiomechanicsDataset import INPUT_KEY_ORDER, LOSS_KEY_ORDER, LOSS_KEY_WIDTHS, MotionWindowView
-from ..diffusion.sampler import ConditionalDDIMSampler
+from ..diffusion.sampler import ConditionalDDIMSampler, StitchedDDIMSampler
 
 LABEL_WIDTH = sum(LOSS_KEY_WIDTHS)          # 30: the label block at the end of every frame's row
 
@@ -52,6 +52,7 @@ class DiffusionLabelPredictor:
         self.sampler = ConditionalDDIMSampler(model, num_sample_steps, use_graph=use_graph, eta=self.eta, seed=self.seed,
                                               solver=solver, spacing=spacing)
         self._mask = None                    # label_mask of the last (F, D): one tensor, so the sampler checks it once
+        self._trial = None                   # ((hop, blend), StitchedDDIMSampler, mask_cols) of the last predict_trial
 
     def _label_mask(self, frames: int, feat: int) -> torch.Tensor:
         if self._mask is None or tuple(self._mask.shape) != (frames, feat):
@@ -110,3 +111,39 @@ class DiffusionLabelPredictor:
         mean, std = hip.ensemble_stats(x.view(B, K, F, D))
         self.last_std = self.split_labels(std)
         return self.split_labels(mean)
+
+    @torch.no_grad()
+    def predict_trial(self, inputs: Dict[str, torch.Tensor], hop: Optional[int] = None, blend: str = 'ramp',
+                      draw: int = 0) -> Dict[str, torch.Tensor]:
+        """Labels of whole trials: inputs is ``{key: [N, F, c]}`` with F >= model.window consecutive frames (at the
+        dataset's frame stride); the trial is denoised as overlapping windows stitched into one sequence
+        (``StitchedDDIMSampler``: a window every ``hop`` frames, default window // 2, blended by ``blend``), so every frame
+        gets one answer and there are no seams.  Returns the four ``LOSS_KEY_ORDER`` outputs as fp32 ``[N, F, C]``.  Trial b
+        draws its start noise from (seed, draw + b).  Deterministic: needs eta = 0 and num_samples = 1."""
+        if self.eta != 0.0 or self.num_samples != 1:
+            raise ValueError(f"predict_trial: stitched sampling is deterministic, it needs eta = 0 and num_samples = 1 (got "
+                             f"eta = {self.eta}, num_samples = {self.num_samples})")
+        obs = self.window_matrix(inputs)
+        N, F, D = obs.shape
+        T = int(getattr(self.model, 'window', F))
+        if D != self.model.feat_dim:
+            raise ValueError(f"a trial row has {D} columns but the denoiser was built for feat_dim = {self.model.feat_dim}")
+        if F < T:
+            raise ValueError(f"a trial of {F} frames is shorter than the denoiser's window of {T} frames")
+        C = int(getattr(self.model, 'cond_cols', 0))
+        if C and C != D - LABEL_WIDTH:
+            raise ValueError(f"the denoiser was trained with cond_cols = {C}; label inference observes the {D - LABEL_WIDTH} "
+                             f"input columns of a {D}-column row, so it needs cond_cols = {D - LABEL_WIDTH} (or 0)")
+        key = (hop, blend, D)
+        if self._trial is None or self._trial[0] != key:
+            # one sampler is kept, with one layout and one captured step: another hop, blend or trial length replaces them,
+            # so a service fed trials of many lengths holds the tables and the graph of the last one only
+            s = self.sampler
+            self._trial = (key, StitchedDDIMSampler(self.model, s.S, hop=hop, blend=blend, use_graph=s.use_graph,
+                                                    solver=s.solver, spacing=s.spacing, seed=self.seed),
+                           label_mask(1, D)[0].contiguous())
+        _, sampler, mask_cols = self._trial
+        sampler.observations = 'clean' if C else 'noised'
+        z = torch.cat([sampler.draw_start(1, F, D, self.seed, draw + b) for b in range(N)])
+        x = sampler.sample(z, obs, mask_cols)
+        return self.split_labels(x)

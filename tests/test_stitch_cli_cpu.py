@@ -1,0 +1,130 @@
+"""`main.py visualize --trial-frames F --trial-hop H --trial-blend B` (no GPU: the kernels in dry-run), the trial readers of the
+datasets behind it, and the one value of IB_STITCH_KMAX."""
+import argparse
+import os
+import re
+import sys
+
+import pytest
+import torch
+
+
+@pytest.fixture()
+def dry():
+    from inferbiomechanics_amd import hip
+    hip.set_dry_run(True)
+    yield hip
+    hip.set_dry_run(False)
+
+
+def test_kmax_has_one_value():
+    from inferbiomechanics_amd import hip
+    from inferbiomechanics_amd.diffusion import schedule
+    text = open(hip.STITCH_HEADER_PATH).read()
+    defined = re.findall(r"#define\s+IB_STITCH_KMAX\s+(\d+)", text)
+    assert defined == [str(hip.STITCH_KMAX)] and hip.STITCH_KMAX == schedule.STITCH_KMAX == 8
+    assert schedule.stitch_layout(16, 8, 4)[3] == hip.STITCH_KMAX
+    src = open(os.path.join(os.path.dirname(hip.__file__), "csrc", "stitch.hip")).read()
+    assert "KMAX = IB_STITCH_KMAX" in src                              # the kernels take the header's value
+
+
+def test_visualize_trial_flags_parse():
+    from inferbiomechanics_amd.cli.visualize import VisualizeCommand
+    p = argparse.ArgumentParser()
+    VisualizeCommand().register_subcommand(p.add_subparsers(dest="command"))
+    a = p.parse_args(["visualize"])
+    assert (a.trial_frames, a.trial_hop, a.trial_blend, a.sample_steps, a.sample_seed) == (0, None, "ramp", 100, 0)
+    a = p.parse_args(["visualize", "--trial-frames", "120", "--trial-hop", "7", "--trial-blend", "uniform"])
+    assert (a.trial_frames, a.trial_hop, a.trial_blend) == (120, 7, "uniform")
+    with pytest.raises(SystemExit):
+        p.parse_args(["visualize", "--trial-blend", "cosine"])
+
+
+def test_visualize_trial_dry_run_prints_stitched_next_to_per_window(dry, tmp_path, capsys):
+    from inferbiomechanics_amd.main import main
+    common = ["visualize", "--synthetic-windows", "60", "--checkpoint-dir", str(tmp_path / "ck"), "--sample-steps", "4"]
+    tr = common + ["--model-type", "diffusion-transformer"]
+    capsys.readouterr()
+    dry.lib().calls.clear()
+    assert main(tr + ["--trial-frames", "25", "--trial-hop", "4", "--trial-blend", "uniform", "--num-frames", "2"])
+    out = capsys.readouterr().out.splitlines()
+    calls = dry.lib().calls
+    # per trial: one stitched loop over the whole trial, one per-window loop over its 3 disjoint windows (0, 10, 15)
+    assert calls.count("ib_stitch_ddim_step") == 2 * 4 and calls.count("ib_ddim_cond_step") == 2 * 4
+    assert calls.count("ib_diffusion_draw") == 2 * (1 + 3)
+    # a dry run computes nothing: the figures are whatever the unwritten buffers hold, so only their layout is checked
+    num, fig = r"[+-](?:\d+\.\d{3}|nan|inf)", r"(?:\d+\.\d+|nan|inf)"
+    row = re.compile(rf"^\s*(\d+)\s+(\d+)\s+((?:\s*{num}){{6}}) \| ((?:\s*{num}){{6}})$")
+    for k in range(2):
+        at = next(i for i, line in enumerate(out) if line.startswith(f"trial {k} ("))
+        head = out[at]
+        assert f"(synthetic_subject_0 / window_{25 * k}): 25 frames" in head
+        assert "stitched as 5 windows of 10 every 4 frames (uniform) | 3 disjoint windows" in head
+        assert "stitched force" in out[at + 1] and out[at + 1].rstrip().endswith("| per-window force")
+        rows = [row.match(line) for line in out[at + 2:at + 2 + 25]]
+        assert all(rows), out[at + 2:at + 2 + 25]
+        assert [int(m.group(1)) for m in rows] == list(range(25))
+        assert [int(m.group(2)) for m in rows] == [0] * 10 + [1] * 10 + [2] * 5     # a frame's first covering window
+        tail = out[at + 27:at + 32]
+        for name, line in zip(("cop", "force", "torque", "wrench"), tail):
+            assert re.match(rf"^trial {k} +{name}: RMS err stitched {fig}, per-window {fig}, "
+                            rf"RMS stitched - per-window {fig}$", line), line
+        assert re.match(rf"^trial {k}  force: mean jump across the 2 per-window boundaries: stitched {fig}, "
+                        rf"per-window {fig}$", tail[4]), tail[4]
+    # defaults: hop = window // 2, ramp; F == T is one window and has no boundary line
+    assert main(tr + ["--trial-frames", "10", "--num-frames", "1"])
+    text = capsys.readouterr().out
+    assert "stitched as 1 windows of 10 every 5 frames (ramp) | 1 disjoint windows" in text and "mean jump" not in text
+
+    for bad, msg in ((common + ["--trial-frames", "25"], "diffusion"),
+                     (common + ["--model-type", "diffusion-mlp", "--trial-frames", "25"], "window"),
+                     (tr + ["--trial-frames", "9"], "F = 9"),
+                     (tr + ["--trial-frames", "25", "--trial-hop", "11"], "hop"),
+                     (tr + ["--trial-frames", "40", "--trial-hop", "1"], "more than 8"),
+                     (tr + ["--trial-frames", "25", "--sample-steps", "0"], "sample-steps")):
+        with pytest.raises(SystemExit, match=msg):
+            main(bad)
+    # without the flag the command is what it was
+    assert main(["visualize", "--synthetic-windows", "2", "--checkpoint-dir", str(tmp_path / "ck"), "--num-frames", "1"])
+    assert "window 0: loss" in capsys.readouterr().out
+
+
+def test_synthetic_read_trial():
+    from inferbiomechanics_amd.data.AddBiomechanicsDataset import INPUT_KEY_ORDER, LOSS_KEY_ORDER, SyntheticWindowDataset
+    ds = SyntheticWindowDataset(4, 50, 5)
+    before = ds[1]
+    inputs, labels, subj, trial = ds.read_trial(1, 37)
+    assert (subj, trial) == (0, 1)
+    assert all(inputs[k].shape[0] == 37 for k in INPUT_KEY_ORDER) and all(labels[k].shape[0] == 37 for k in LOSS_KEY_ORDER)
+    again = ds.read_trial(1, 37)
+    assert all(torch.equal(inputs[k], again[0][k]) for k in inputs)
+    after = ds[1]                                                      # the window reader is untouched by it
+    assert all(torch.equal(before[0][k], after[0][k]) for k in before[0]) and ds.frames == 10
+    with pytest.raises(ValueError, match="frames"):
+        ds.read_trial(0, 0)
+    with pytest.raises(ValueError, match="all_frames"):
+        SyntheticWindowDataset(4, 50, 5, output_data_format="last_frame").read_trial(0, 20)
+
+
+def test_b3d_read_trial_continues_the_window(tmp_path, monkeypatch):
+    from oracle import fake_nimble
+    from inferbiomechanics_amd.data.AddBiomechanicsDataset import AddBiomechanicsDataset
+    monkeypatch.setitem(sys.modules, "nimblephysics", fake_nimble)
+    root = str(tmp_path / "test")
+    fake_nimble.make_tree(root)
+    ds = AddBiomechanicsDataset(root, 50, None, stride=5, output_data_format="all_frames", skip_loading_skeletons=True)
+    index = 3
+    si, trial, start = (int(v) for v in ds.windows[index])
+    length = ds.subjects[si].getTrialLength(trial)
+    fit = (length - 1 - start) // 5 + 1                                # frames at stride 5 from `start` inside the trial
+    assert fit > 10
+    win = ds[index]
+    inputs, labels, subj, tr = ds.read_trial(index, fit)
+    assert (subj, tr) == (win[2], win[3])
+    for got, want in ((inputs, win[0]), (labels, win[1])):
+        for k in want:
+            assert got[k].shape[0] == fit and torch.equal(got[k][:10], want[k]), k
+    later = next(i for i in range(len(ds)) if tuple(ds.windows[i][:2]) == (si, trial) and int(ds.windows[i][2]) == start + 5)
+    assert torch.equal(inputs["pos"][1:11], ds[later][0]["pos"])       # frame stride: row 1 is `stride` frames on
+    with pytest.raises(ValueError, match="do not fit"):
+        ds.read_trial(index, fit + 1)

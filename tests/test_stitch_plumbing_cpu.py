@@ -1,0 +1,181 @@
+"""Host-side plumbing of stitched trial sampling (no GPU): the second C-ABI header and its table, schedule.stitch_layout,
+the refusals of StitchedDDIMSampler, and its launches in dry-run mode."""
+import os
+import subprocess
+
+import pytest
+import torch
+
+
+@pytest.fixture()
+def dry():
+    from inferbiomechanics_amd import hip
+    hip.set_dry_run(True)
+    yield hip
+    hip.set_dry_run(False)
+
+
+def _exports(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
+    return {line.split()[-1] for line in out.splitlines() if line.strip()}
+
+
+def test_stitch_header_has_its_own_table_and_both_builds_export_it():
+    from inferbiomechanics_amd import hip
+    names = hip.stitch_symbols()
+    assert names == ["ib_stitch_ddim_step", "ib_stitch_dpmpp_step"]
+    assert not set(names) & set(hip._SIGS) and not set(names) & set(hip.declared_symbols())
+    for n in names:
+        res, args = hip._STITCH_SIGS[n]
+        assert res is hip._c.c_int and args[-1] is hip._vp
+        assert hip._is_launch(n)
+    assert len(hip._STITCH_SIGS["ib_stitch_ddim_step"][1]) == 23
+    assert len(hip._STITCH_SIGS["ib_stitch_dpmpp_step"][1]) == 24
+    for path in (hip.LIB_PATH, hip.AB_LIB_PATH):
+        if not os.path.exists(path):
+            pytest.fail(f"{path} is not built")
+        assert set(names) <= _exports(path), path
+    lib = hip.lib()
+    for n in names:
+        fn = getattr(lib, n)
+        assert fn.restype is hip._c.c_int and list(fn.argtypes) == hip._STITCH_SIGS[n][1]
+
+
+@pytest.mark.parametrize("F", [8, 9, 17, 23])
+@pytest.mark.parametrize("hop", [1, 3, 5, 8])
+@pytest.mark.parametrize("blend", ["uniform", "ramp"])
+def test_stitch_layout_properties(F, hop, blend):
+    from inferbiomechanics_amd.diffusion.schedule import stitch_layout
+    T = 8
+    start, cover, wn, K = stitch_layout(F, T, hop, blend)
+    assert K == 8 and start.dtype == torch.int32 and cover.dtype == torch.int32 and wn.dtype == torch.float32
+    assert cover.shape == (F, 2) and wn.shape == (F, 8)
+    st = start.tolist()
+    assert st[0] == 0 and st[-1] + T == F and all(b > a for a, b in zip(st, st[1:]))
+    assert all(s % hop == 0 for s in st[:-1])
+    for f in range(F):
+        covering = [w for w, s in enumerate(st) if s <= f < s + T]
+        assert covering, f                                             # every frame is covered
+        w0, cnt = cover[f].tolist()
+        assert 1 <= cnt <= 8 and covering == list(range(w0, w0 + cnt))
+        assert abs(float(wn[f].double().sum()) - 1.0) <= 1e-6
+        assert (wn[f, :cnt] > 0).all() and not wn[f, cnt:].any()
+        if blend == "uniform":
+            assert torch.equal(wn[f, :cnt], torch.full((cnt,), 1.0 / cnt, dtype=torch.float64).float())
+        else:
+            R = max(T - hop, 1)
+            raw = torch.tensor([min(f - st[w] + 1, T - (f - st[w]), R) / R for w in covering], dtype=torch.float64)
+            assert torch.equal(wn[f, :cnt], (raw / raw.sum()).float())
+
+
+def test_stitch_layout_refusals():
+    from inferbiomechanics_amd.diffusion.schedule import stitch_layout
+    with pytest.raises(ValueError, match="F"):
+        stitch_layout(7, 8, 4)
+    with pytest.raises(ValueError, match="hop"):
+        stitch_layout(16, 8, 9)
+    with pytest.raises(ValueError, match="hop"):
+        stitch_layout(16, 8, 0)
+    with pytest.raises(ValueError, match="hop.*more than 8"):
+        stitch_layout(40, 16, 1)
+    with pytest.raises(ValueError, match="blend"):
+        stitch_layout(16, 8, 4, "cosine")
+
+
+def _tr(dt=torch.float32, D=44, T=8):
+    from inferbiomechanics_amd.models.DiffusionDenoisers import DiffusionTransformer
+    return DiffusionTransformer(D, T, d_model=32, num_heads=4, dim_feedforward=64, num_layers=1, temb_dim=16, temb_hidden=24,
+                                compute_dtype=dt)
+
+
+def test_sampler_refusals(dry):
+    from inferbiomechanics_amd.diffusion import StitchedDDIMSampler
+    from inferbiomechanics_amd.models.DiffusionDenoisers import DiffusionTransformer
+    m = _tr()
+    with pytest.raises(ValueError, match="eta"):
+        StitchedDDIMSampler(m, 5, eta=0.5)
+    with pytest.raises(ValueError, match="hop"):
+        StitchedDDIMSampler(m, 5, hop=9)
+    with pytest.raises(ValueError, match="blend"):
+        StitchedDDIMSampler(m, 5, blend="cosine")
+    m16 = DiffusionTransformer(44, 16, d_model=32, num_heads=4, dim_feedforward=64, num_layers=1, temb_dim=16, temb_hidden=24)
+    with pytest.raises(ValueError, match="more than 8"):
+        StitchedDDIMSampler(m16, 5, hop=1)
+    s = StitchedDDIMSampler(m, 5)
+    assert s.hop == 4 and s.blend == "ramp"
+    z = torch.randn(2, 17, 44)
+    with pytest.raises(ValueError, match="F"):
+        s.sample(torch.randn(2, 7, 44))
+    with pytest.raises(ValueError, match="mask_cols"):
+        s.sample(z, torch.randn(2, 17, 44), torch.ones(17, 44, dtype=torch.bool))
+    with pytest.raises(ValueError, match="mask_cols"):
+        s.sample(z, torch.randn(2, 17, 44), torch.ones(43, dtype=torch.bool))
+    with pytest.raises(ValueError, match="together"):
+        s.sample(z, torch.randn(2, 17, 44), None)
+    cols = torch.zeros(44, dtype=torch.bool)
+    cols[:14] = True
+    clean = StitchedDDIMSampler(m, 5, observations="clean")
+    with pytest.raises(ValueError, match="cond_cols"):
+        clean.sample(z, torch.randn(2, 17, 44), cols)                  # the model has no conditioning columns
+    m.cond_cols = 12
+    with pytest.raises(ValueError, match="cond_cols"):
+        clean.sample(z, torch.randn(2, 17, 44), cols)                  # 14 columns marked, 12 trained
+    from inferbiomechanics_amd.models.DiffusionLabelPredictor import DiffusionLabelPredictor
+    with pytest.raises(ValueError, match="eta"):
+        DiffusionLabelPredictor(_tr(D=177, T=10), 5, eta=0.5).predict_trial({})
+    with pytest.raises(ValueError, match="num_samples"):
+        DiffusionLabelPredictor(_tr(D=177, T=10), 5, num_samples=2).predict_trial({})
+
+
+@pytest.mark.parametrize("solver,cond", [("ddim", False), ("ddim", True), ("dpmpp2m", True)])
+def test_dry_run_issues_one_update_launch_per_step_in_header_order(dry, solver, cond):
+    from inferbiomechanics_amd import hip
+    from inferbiomechanics_amd.diffusion import StitchedDDIMSampler
+    N, F, D, T, S = 2, 17, 44, 8, 5
+    m = _tr(torch.bfloat16)
+    s = StitchedDDIMSampler(m, S, hop=3, solver=solver)
+    cols = torch.zeros(D, dtype=torch.bool)
+    cols[:14] = True
+    dry.lib().calls.clear()
+    dry.lib().args.clear()
+    out = s.sample(torch.randn(N, F, D), *((torch.randn(N, F, D), cols) if cond else ()))
+    assert out.shape == (N, F, D)
+    name = "ib_stitch_dpmpp_step" if solver == "dpmpp2m" else "ib_stitch_ddim_step"
+    calls = dry.lib().calls
+    assert calls.count(name) == S and calls.count("ib_ddim_cond_init") == (1 if cond else 0)
+    for other in ("ib_ddim_step", "ib_ddim_cond_step", "ib_dpmpp_step", "ib_dpmpp_cond_step"):
+        assert other not in calls
+    b, lay, tabs = s._bufs, s.layout, m.tables(torch.device("cpu"))
+    Dp = b["x"].shape[-1]
+    assert Dp % 8 == 0 and Dp >= D
+    W = lay["W"]
+    assert W == 4
+    p = lambda t: None if t is None else t.data_ptr()
+    cnd = [p(b["x0"]), p(b["z"]), p(b["mask"])] if cond else [None, None, None]
+    coef = tabs.dpmpp_coef if solver == "dpmpp2m" else tabs.ddim_coef
+    want = [p(b["x"]), p(b["eps"])] + ([p(b["hist"])] if solver == "dpmpp2m" else []) + cnd + \
+           [p(coef), p(tabs.obs_coef) if cond else None, p(tabs.ddim_t), S, 0, p(b["ctr"]), p(b["t"]), p(lay["start"]),
+            p(lay["cover"]), p(lay["wn"]), N, W, T, F, D, Dp, hip.BF16, 0]
+    got = [a for n, a in dry.lib().args if n == name]
+    assert len(got) == S
+    for a in got:
+        assert list(a) == want
+    assert b["t"].numel() == N * W
+
+
+def test_predict_trial_layout_in_dry_run(dry):
+    from inferbiomechanics_amd.data.AddBiomechanicsDataset import LOSS_KEY_ORDER, LOSS_KEY_WIDTHS, SyntheticWindowDataset
+    from inferbiomechanics_amd.models.DiffusionLabelPredictor import DiffusionLabelPredictor
+    ds = SyntheticWindowDataset(4, 50, 5)                              # windows of 10 frames
+    items = [ds[i] for i in range(4)]
+    inputs = {k: torch.cat([it[0][k] for it in items[:2]]).unsqueeze(0).repeat(3, 1, 1) for k in items[0][0]}   # [3, 20, c]
+    pred = DiffusionLabelPredictor(_tr(D=177, T=10), 5)
+    dry.lib().calls.clear()
+    out = pred.predict_trial(inputs, hop=4, blend="uniform", draw=1)
+    assert list(out) == LOSS_KEY_ORDER
+    for k, w in zip(LOSS_KEY_ORDER, LOSS_KEY_WIDTHS):
+        assert out[k].shape == (3, 20, w) and out[k].dtype == torch.float32
+    assert dry.lib().calls.count("ib_stitch_ddim_step") == 5 and dry.lib().calls.count("ib_diffusion_draw") == 3
+    short = {k: v[:, :9] for k, v in inputs.items()}
+    with pytest.raises(ValueError, match="shorter"):
+        pred.predict_trial(short)
