@@ -7,7 +7,10 @@ without the GUI.
 `--trial-frames F` (diffusion-transformer checkpoints) is the command-line route to stitched trial sampling
 (models/DiffusionLabelPredictor.predict_trial): F consecutive frames of a trial, read at the dataset's frame stride, are
 labelled as ONE sequence of overlapping windows and printed next to the labels the per-window sampler gives on disjoint
-windows of the same frames."""
+windows of the same frames.  With `--sample-eta E --num-samples K` (E > 0 or K > 1) both are posterior ensembles
+(predict_trial_ensemble, and the per-window predictor with the same eta and K): the labels printed are the members' means,
+and one more line per trial and label key reports the mean standard deviation over the K members.  `--sampler dpmpp2m`
+runs both loops with DPM-Solver++(2M); it is deterministic and refuses E > 0 or K > 1."""
 import argparse
 import os
 
@@ -57,6 +60,14 @@ class VisualizeCommand(AbstractCommand):
                        help='[--trial-frames] how the windows that cover a frame are blended.')
         p.add_argument('--sample-steps', type=int, default=100, help='[--trial-frames] steps of the sampling loop.')
         p.add_argument('--sample-seed', type=int, default=0, help='[--trial-frames] seed of the start noise.')
+        p.add_argument('--sample-eta', type=float, default=0.0,
+                       help='[--trial-frames] eta of the sampler: 0 = deterministic DDIM, 1 = DDPM ancestral sampling.')
+        p.add_argument('--num-samples', type=int, default=1,
+                       help='[--trial-frames] posterior samples per trial and per window; the means are printed and the '
+                            'spread over the members reported.')
+        p.add_argument('--sampler', type=str, default='ddim', choices=['ddim', 'dpmpp2m'],
+                       help='[--trial-frames] update of both sampling loops: first-order DDIM, or DPM-Solver++(2M) '
+                            '(deterministic: needs --sample-eta 0 and --num-samples 1).')
 
     def run(self, args: argparse.Namespace):
         if 'command' in args and args.command != 'visualize':
@@ -100,13 +111,22 @@ class VisualizeCommand(AbstractCommand):
         label blocks of its F frames from predict_trial, and from the per-window sampler on the disjoint windows at 0, T,
         2 T, ... plus a last one ending on the last frame (a frame takes the first window that covers it).  Per frame one
         row with the force block of both; per trial and label key the RMS error of both against the labels, their RMS
-        difference, and for the force block the mean jump |x[f] - x[f - 1]| across the per-window boundaries."""
+        difference, and for the force block the mean jump |x[f] - x[f - 1]| across the per-window boundaries.  With
+        --sample-eta > 0 or --num-samples > 1 both are ensemble means (predict_trial_ensemble; the per-window predictor with
+        the same eta and K), and one more line per trial and label key gives the mean standard deviation over the members."""
         from ..models.DiffusionLabelPredictor import DiffusionLabelPredictor
         F = int(args.trial_frames)
         if not is_diffusion(args.model_type):
             raise SystemExit("--trial-frames labels a trial with a diffusion denoiser: pass --model-type diffusion-transformer")
         if args.sample_steps < 1 or args.num_frames < 1:
             raise SystemExit("--sample-steps and --num-frames must be >= 1")
+        eta, num_samples = float(getattr(args, 'sample_eta', 0.0)), int(getattr(args, 'num_samples', 1))
+        if not 0.0 <= eta <= 1.0 or num_samples < 1:
+            raise SystemExit("--sample-eta must be in [0, 1] and --num-samples >= 1")
+        solver = getattr(args, 'sampler', 'ddim')
+        ensemble = eta > 0.0 or num_samples > 1
+        if solver == 'dpmpp2m' and ensemble:
+            raise SystemExit("--sampler dpmpp2m is deterministic: it needs --sample-eta 0 and --num-samples 1")
         view = self.diffusion_view(args, 'test', self.ensure_geometry(args.geometry_folder))
         dataset = view.dataset
         model = self.diffusion_model(args, view, device)
@@ -123,7 +143,8 @@ class VisualizeCommand(AbstractCommand):
         except ValueError as e:
             raise SystemExit(f"--trial-frames / --trial-hop: {e}")
         predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
-                                            output_data_format=args.output_data_format)
+                                            output_data_format=args.output_data_format, eta=eta, num_samples=num_samples,
+                                            solver=solver)
         gather = start.long()[:, None] + torch.arange(T)[None, :]      # [Wd, T] trial frames of the disjoint windows
         w0 = cover[:, 0].long()
         t0 = torch.arange(F) - start.long()[w0]
@@ -139,8 +160,13 @@ class VisualizeCommand(AbstractCommand):
                 print(f"trial {k}: skipped ({e})")
                 continue
             inputs = {key: v.unsqueeze(0) for key, v in inputs.items()}
-            stitched = predictor.predict_trial(inputs, hop=hop, blend=args.trial_blend, draw=k)
+            if ensemble:
+                stitched = predictor.predict_trial_ensemble(inputs, hop=hop, blend=args.trial_blend, draw=k)
+                stitched_std = predictor.last_std
+            else:
+                stitched = predictor.predict_trial(inputs, hop=hop, blend=args.trial_blend, draw=k)
             windows = predictor({key: v[0, gather] for key, v in inputs.items()}, draw=k * gather.shape[0])
+            windows_std = predictor.last_std if ensemble else None
             print(f"trial {k} ({window_subject(dataset, [subj])} / {window_trial(dataset, [subj], [trial])}): {F} frames, "
                   f"stitched as {W} windows of {T} every {hop} frames ({args.trial_blend}) | {gather.shape[0]} disjoint windows")
             print(f"{'frame':>5} {'win':>3}  {'stitched force':<48} | per-window force")
@@ -154,6 +180,11 @@ class VisualizeCommand(AbstractCommand):
                 s, w, y = stitched[key][0].cpu(), windows[key].cpu()[w0, t0], labels[key].float()
                 print(f"trial {k} {name:>6}: RMS err stitched {rms(s - y):.6f}, per-window {rms(w - y):.6f}, "
                       f"RMS stitched - per-window {rms(s - w):.6f}")
+            if ensemble:
+                for name, key in zip(LABEL_NAMES, LOSS_KEY_ORDER):
+                    ss, ws = stitched_std[key][0].cpu(), windows_std[key].cpu()[w0, t0]
+                    print(f"trial {k} {name:>6}: mean std over {num_samples} samples stitched {float(ss.double().mean()):.6f}, "
+                          f"per-window {float(ws.double().mean()):.6f}")
             if seams.numel():
                 jump = lambda x: float((x[seams] - x[seams - 1]).abs().mean())
                 print(f"trial {k}  force: mean jump across the {seams.numel()} per-window boundaries: stitched {jump(sf):.6f}, "

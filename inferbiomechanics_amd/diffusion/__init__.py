@@ -1,2 +1,2 @@
-from .sampler import ConditionalDDIMSampler, DDIMSampler, StitchedDDIMSampler  # noqa: F401
+from .sampler import ConditionalDDIMSampler, DDIMSampler, StitchedDDIMSampler, StochasticStitchedSampler  # noqa: F401
 from .schedule import stitch_layout  # noqa: F401

@@ -88,6 +88,10 @@ class DDIMSampler:
             raise ValueError("window_ids must be in 0 .. 2^32 - 1 (one word of the generator's counter)")
         self._bufs["win"].copy_(ids)
 
+    def _noise_ids(self, B: int) -> int:
+        """how many ids key the step noise of a batch of B windows: one per window (a subclass may key it otherwise)"""
+        return B
+
     def _extra_buffers(self, B, T, D, Dp, dev, dtype):
         """more device buffers that live as long as the captured step (a subclass's)"""
         return {}
@@ -173,7 +177,7 @@ class DDIMSampler:
                 self._bufs["eps"] = torch.zeros((B, T, Dp), dtype=m.compute_dtype, device=dev)
             self._bufs.update(self._extra_buffers(B, T, D, Dp, dev, m.compute_dtype))
             if self.eta > 0.0:
-                self._bufs["win"] = torch.zeros(B, dtype=torch.int64, device=dev)
+                self._bufs["win"] = torch.zeros(self._noise_ids(B), dtype=torch.int64, device=dev)
             if self.solver == "dpmpp2m":
                 # the previous step's data prediction, fp32 whatever the state's dtype, pitched like the state.  The first
                 # row of the table does not read it, so a new batch needs no reset
@@ -501,3 +505,69 @@ class StitchedDDIMSampler(DDIMSampler):
         else:
             hip.stitch_ddim_step(v(x), v(eps), x0, z, m, tabs.ddim_coef, oc, tabs.ddim_t, lay["start"], lay["cover"],
                                  lay["wn"], step_dev=ctr, t_out=t_vec, D=self._D)
+
+
+class StochasticStitchedSampler(StitchedDDIMSampler):
+    """StitchedDDIMSampler with eta in [0, 1]: the stochastic DDIM / DDPM loop over a whole trial.  The step noise is drawn
+    inside the update kernel per TRIAL element, keyed by (seed, trial id, step, trial frame, column), so every copy of an
+    element in the overlapping windows receives the same normal and the windows stay one sequence; a trial's result depends
+    on its id, not on its place in the batch or on the batch's size.  With observations, an observed element's stored noise
+    follows the DDIM posterior given the observation (ConditionalDDIMSampler's eta > 0 loop), in every copy.  Layout,
+    to_windows, the start state, the captured one-step graph and the launch count per step are the parent's; only the update
+    launch differs (ib_stitch_ddim_step_noise, csrc/stitch_noise.hip).  eta = 0 is the parent class bit for bit.  With
+    F == T it is ConditionalDDIMSampler(eta, seed) (or DDIMSampler without observations) with window ids = trial ids.  The
+    solver is 'ddim': DPM-Solver++ stays deterministic.  The trial ids live in a device buffer the captured update reads, so
+    a new batch or new ids of the same shape replay the captured step."""
+
+    def __init__(self, model, num_sample_steps: int = 100, eta: float = 1.0, hop: Optional[int] = None, blend: str = "ramp",
+                 use_graph: bool = True, spacing: str = "time", observations: str = "noised", seed: Optional[int] = None):
+        if not 0.0 <= float(eta) <= 1.0:
+            raise ValueError(f"eta must be in [0, 1], got {eta}")
+        super().__init__(model, num_sample_steps, hop, blend, use_graph, "ddim", spacing, observations, seed)
+        self.eta = float(eta)                # the parent's constructor hands DDIMSampler eta = 0
+        self._tid = None
+
+    @torch.no_grad()
+    def sample(self, z: torch.Tensor, observed: Optional[torch.Tensor] = None, mask_cols: Optional[torch.Tensor] = None,
+               steps: Optional[int] = None, trial_ids: Union[None, Sequence[int], torch.Tensor] = None) -> torch.Tensor:
+        """as StitchedDDIMSampler.sample.  trial_ids (default 0 .. N-1): the step noise of trial n is keyed by (seed,
+        trial_ids[n], step), whatever its place in the batch; unused at eta = 0."""
+        self._tid = trial_ids
+        try:
+            return super().sample(z, observed, mask_cols, steps)
+        finally:
+            self._tid = None
+
+    @torch.no_grad()
+    def sample_noise(self, batch: int, frames: int, feat: int, observed: Optional[torch.Tensor] = None,
+                     mask_cols: Optional[torch.Tensor] = None, seed: Optional[int] = None, draw: int = 0,
+                     steps: Optional[int] = None, trial_ids=None) -> torch.Tensor:
+        """as StitchedDDIMSampler.sample_noise, with the trial ids of sample()"""
+        return self.sample(self.draw_start(batch, frames, feat, seed, draw), observed, mask_cols, steps, trial_ids)
+
+    def _noise_ids(self, B: int) -> int:
+        return self._N                       # the 'win' buffer holds one id per TRIAL, not one per window (B = N W)
+
+    def _set_window_ids(self, B: int):
+        """DDIMSampler._sample asks for one id per window (B = N W); this loop's noise is keyed per trial: copies the call's
+        trial ids (default 0 .. N-1) into the device buffer 'win' [N] the captured update reads"""
+        N = self._N
+        ids = self._tid
+        ids = torch.arange(N, dtype=torch.int64) if ids is None else torch.as_tensor(ids, dtype=torch.int64).reshape(-1).cpu()
+        if ids.numel() != N:
+            raise ValueError(f"trial_ids must hold one id per trial ({N}), got {ids.numel()}")
+        if N and (int(ids.min()) < 0 or int(ids.max()) >= 1 << 32):
+            raise ValueError("trial_ids must be in 0 .. 2^32 - 1 (one word of the generator's counter)")
+        self._bufs["win"].copy_(ids)
+
+    def _update(self, x, eps, ctr, t_vec, tabs):
+        if self.eta == 0.0:
+            return super()._update(x, eps, ctr, t_vec, tabs)
+        b, lay = self._bufs, self._lay
+        shape = (self._N, lay["W"]) + tuple(x.shape[1:])
+        v = lambda t: t.view(shape)
+        cond = self._cond is not None
+        x0, z, m, oc, on = (v(b["x0"]), v(b["z"]), b["mask"], tabs.obs_coef, tabs.obs_noise_coef) if cond \
+            else (None, None, None, None, None)
+        hip.stitch_ddim_step_noise(v(x), v(eps), x0, z, m, tabs.ddim_coef_eta, oc, on, tabs.ddim_t, lay["start"], lay["cover"],
+                                   lay["wn"], b["win"], self.seed, step_dev=ctr, t_out=t_vec, D=self._D)

@@ -7,7 +7,8 @@ fallback: if the library is missing or a call fails, a ``HipError`` is raised.
 
 The header is the only declaration of the ABI: the ctypes signatures (``_SIGS``) are parsed from it when this
 module is imported, so a new entry point needs its declaration there and its wrapper here, nothing else.  The stitched
-sampler updates are declared in a second header, ``include/ib_hip_stitch.h``, parsed the same way into ``_STITCH_SIGS``.
+sampler updates are declared in a second header, ``include/ib_hip_stitch.h``, parsed the same way into ``_STITCH_SIGS``,
+and the stochastic stitched update in a third, ``include/ib_hip_stitch_noise.h``, into ``_STITCH_NOISE_SIGS``.
 """
 from __future__ import annotations
 
@@ -26,6 +27,7 @@ LIB_PATH = os.environ.get("IB_HIP_LIB") or os.path.join(_HERE, "lib", "libib_hip
 AB_LIB_PATH = os.path.join(_HERE, "lib", "ab", "libib_hip_ab.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip.h")
 STITCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_stitch.h")
+STITCH_NOISE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_stitch_noise.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -93,6 +95,10 @@ _SIGS = _parse_header(_read_header())
 _STITCH_SIGS = _parse_header(_read_header(STITCH_HEADER_PATH))
 if set(_SIGS) & set(_STITCH_SIGS):
     raise HipError(f"declared in both headers: {sorted(set(_SIGS) & set(_STITCH_SIGS))}")
+# the third header (the stochastic stitched update), again a table of its own: the two above stay what they were
+_STITCH_NOISE_SIGS = _parse_header(_read_header(STITCH_NOISE_HEADER_PATH))
+if set(_STITCH_NOISE_SIGS) & (set(_SIGS) | set(_STITCH_SIGS)):
+    raise HipError(f"declared in two headers: {sorted(set(_STITCH_NOISE_SIGS) & (set(_SIGS) | set(_STITCH_SIGS)))}")
 _kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_STITCH_KMAX[ \t]+(\d+)[ \t]*$", _read_header(STITCH_HEADER_PATH), flags=re.M)
 if _kmax is None:
     raise HipError(f"{STITCH_HEADER_PATH} does not define IB_STITCH_KMAX")
@@ -111,9 +117,17 @@ def stitch_symbols() -> List[str]:
     return sorted(_STITCH_SIGS)
 
 
+def stitch_noise_symbols() -> List[str]:
+    """Every function include/ib_hip_stitch_noise.h declares"""
+    return sorted(_STITCH_NOISE_SIGS)
+
+
 def _sig(name: str):
-    """(restype, argtypes) of an entry point of either header"""
-    return _SIGS[name] if name in _SIGS else _STITCH_SIGS[name]
+    """(restype, argtypes) of an entry point of any of the headers"""
+    for table in (_SIGS, _STITCH_SIGS):
+        if name in table:
+            return table[name]
+    return _STITCH_NOISE_SIGS[name]
 
 
 # pure host queries: no launch, no stream
@@ -388,7 +402,7 @@ def lib():
             raise HipError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C inferbiomechanics_amd/csrc` (hipcc --offload-arch=gfx950). There is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGS.items()) + list(_STITCH_SIGS.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_STITCH_SIGS.items()) + list(_STITCH_NOISE_SIGS.items()):
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -2369,6 +2383,33 @@ def stitch_dpmpp_step(x, eps, hist, x0, z, mask, coef, obs_coef, timesteps, star
                                       _ptr(obs_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out), _ptr(start),
                                       _ptr(cover), _ptr(wn), N, W, T, F, D, ld, dtype_code(x.dtype), stream_ptr()),
            "ib_stitch_dpmpp_step")
+    return x
+
+
+def stitch_ddim_step_noise(x, eps, x0, z, mask, coef, obs_coef, obs_noise_coef, timesteps, start, cover, wn, trial_ids, seed,
+                           step=0, step_dev=None, t_out=None, D=None):
+    """stochastic DDIM / DDPM update of a stitched trial in place (csrc/stitch_noise.hip): as stitch_ddim_step with coef
+    [S, 3] = (c_x, c_eps, sigma); the noise of trial n is keyed by (seed, trial_ids[n], step, TRIAL frame, column) and
+    generated inside the kernel, so every copy of an element receives the same normal.  x0, z, mask, obs_coef and
+    obs_noise_coef [S, 2]: all None, or the masked loop's operands as in ddim_cond_step_noise (z is updated in place at the
+    observed elements, in every copy).  trial_ids: int64 [N] on the device."""
+    what = "stitch_ddim_step_noise"
+    if (obs_noise_coef is None) != (obs_coef is None):
+        raise HipError(f"{what}: x0, z, mask, obs_coef and obs_noise_coef come together (the masked loop) or not at all")
+    N, W, T, F, D, ld = _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D)
+    S = _step_tables(what, coef, 3, timesteps, N * W, t_out, step_dev, obs_coef)
+    if obs_noise_coef is not None:
+        _req(obs_noise_coef, "obs_noise_coef", torch.float32, 2)
+        if tuple(obs_noise_coef.shape) != (S, 2) or not obs_noise_coef.is_contiguous():
+            raise HipError(f"{what}: obs_noise_coef must be contiguous [S, 2] = [{S}, 2] fp32")
+    _req(trial_ids, "trial_ids", torch.int64, 1)
+    if trial_ids.numel() != N or not trial_ids.is_contiguous() or trial_ids.device != x.device:
+        raise HipError(f"{what}: trial_ids must be contiguous int64 [N] = [{N}] on the device of x ({x.device})")
+    _check(lib().ib_stitch_ddim_step_noise(_ptr(x), _ptr(eps), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef),
+                                           _ptr(obs_noise_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out),
+                                           _ptr(start), _ptr(cover), _ptr(wn), _ptr(trial_ids),
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, N, W, T, F, D, ld, dtype_code(x.dtype),
+                                           stream_ptr()), "ib_stitch_ddim_step_noise")
     return x
 
 

@@ -12,7 +12,7 @@ import torch
 
 from .. import hip
 from ..data.AddBiomechanicsDataset import INPUT_KEY_ORDER, LOSS_KEY_ORDER, LOSS_KEY_WIDTHS, MotionWindowView
-from ..diffusion.sampler import ConditionalDDIMSampler, StitchedDDIMSampler
+from ..diffusion.sampler import ConditionalDDIMSampler, StitchedDDIMSampler, StochasticStitchedSampler
 
 LABEL_WIDTH = sum(LOSS_KEY_WIDTHS)          # 30: the label block at the end of every frame's row
 
@@ -53,6 +53,7 @@ class DiffusionLabelPredictor:
                                               solver=solver, spacing=spacing)
         self._mask = None                    # label_mask of the last (F, D): one tensor, so the sampler checks it once
         self._trial = None                   # ((hop, blend), StitchedDDIMSampler, mask_cols) of the last predict_trial
+        self._trial_ens = None               # the same of the last predict_trial_ensemble, a StochasticStitchedSampler
 
     def _label_mask(self, frames: int, feat: int) -> torch.Tensor:
         if self._mask is None or tuple(self._mask.shape) != (frames, feat):
@@ -123,17 +124,8 @@ class DiffusionLabelPredictor:
         if self.eta != 0.0 or self.num_samples != 1:
             raise ValueError(f"predict_trial: stitched sampling is deterministic, it needs eta = 0 and num_samples = 1 (got "
                              f"eta = {self.eta}, num_samples = {self.num_samples})")
-        obs = self.window_matrix(inputs)
+        obs, C = self._trial_checks(inputs)
         N, F, D = obs.shape
-        T = int(getattr(self.model, 'window', F))
-        if D != self.model.feat_dim:
-            raise ValueError(f"a trial row has {D} columns but the denoiser was built for feat_dim = {self.model.feat_dim}")
-        if F < T:
-            raise ValueError(f"a trial of {F} frames is shorter than the denoiser's window of {T} frames")
-        C = int(getattr(self.model, 'cond_cols', 0))
-        if C and C != D - LABEL_WIDTH:
-            raise ValueError(f"the denoiser was trained with cond_cols = {C}; label inference observes the {D - LABEL_WIDTH} "
-                             f"input columns of a {D}-column row, so it needs cond_cols = {D - LABEL_WIDTH} (or 0)")
         key = (hop, blend, D)
         if self._trial is None or self._trial[0] != key:
             # one sampler is kept, with one layout and one captured step: another hop, blend or trial length replaces them,
@@ -147,3 +139,48 @@ class DiffusionLabelPredictor:
         z = torch.cat([sampler.draw_start(1, F, D, self.seed, draw + b) for b in range(N)])
         x = sampler.sample(z, obs, mask_cols)
         return self.split_labels(x)
+
+    def _trial_checks(self, inputs: Dict[str, torch.Tensor]):
+        """predict_trial's checks of a batch of trials -> (obs [N, F, D], cond_cols)"""
+        obs = self.window_matrix(inputs)
+        N, F, D = obs.shape
+        T = int(getattr(self.model, 'window', F))
+        if D != self.model.feat_dim:
+            raise ValueError(f"a trial row has {D} columns but the denoiser was built for feat_dim = {self.model.feat_dim}")
+        if F < T:
+            raise ValueError(f"a trial of {F} frames is shorter than the denoiser's window of {T} frames")
+        C = int(getattr(self.model, 'cond_cols', 0))
+        if C and C != D - LABEL_WIDTH:
+            raise ValueError(f"the denoiser was trained with cond_cols = {C}; label inference observes the {D - LABEL_WIDTH} "
+                             f"input columns of a {D}-column row, so it needs cond_cols = {D - LABEL_WIDTH} (or 0)")
+        return obs, C
+
+    @torch.no_grad()
+    def predict_trial_ensemble(self, inputs: Dict[str, torch.Tensor], hop: Optional[int] = None, blend: str = 'ramp',
+                               draw: int = 0) -> Dict[str, torch.Tensor]:
+        """Posterior ensembles of whole trials: as ``predict_trial`` with the predictor's own ``eta`` and ``num_samples`` = K
+        (``StochasticStitchedSampler``, solver 'ddim').  Trial i = draw + b is replicated K times inside the sampler batch;
+        member k has trial id i K + k for both its start draw and its step noise.  Returns the members' mean as the four
+        ``LOSS_KEY_ORDER`` outputs, fp32 ``[N, F, C]``, and sets ``last_std`` to their unbiased standard deviation in the
+        same layout (0 for K = 1), summed in member order (``ib_ensemble_stats``)."""
+        if self.sampler.solver != 'ddim':
+            raise ValueError(f"predict_trial_ensemble: the stochastic stitched loop is DDIM / DDPM, solver "
+                             f"{self.sampler.solver!r} is deterministic")
+        obs, C = self._trial_checks(inputs)
+        N, F, D = obs.shape
+        K = self.num_samples
+        key = (hop, blend, D)
+        if self._trial_ens is None or self._trial_ens[0] != key:
+            s = self.sampler
+            self._trial_ens = (key, StochasticStitchedSampler(self.model, s.S, eta=self.eta, hop=hop, blend=blend,
+                                                              use_graph=s.use_graph, spacing=s.spacing, seed=self.seed),
+                               label_mask(1, D)[0].contiguous())
+        _, sampler, mask_cols = self._trial_ens
+        sampler.observations = 'clean' if C else 'noised'
+        ids = self.member_ids(draw, N)
+        z = torch.cat([sampler.draw_start(1, F, D, self.seed, i) for i in ids])
+        members = obs.unsqueeze(1).expand(N, K, F, D).reshape(N * K, F, D)
+        x = sampler.sample(z, members, mask_cols, trial_ids=ids)
+        mean, std = hip.ensemble_stats(x.view(N, K, F, D))
+        self.last_std = self.split_labels(std)
+        return self.split_labels(mean)

@@ -7,8 +7,9 @@ steps; N trials of F frames are covered by W windows every T // 2 frames.  `stit
 every column but the last 30.  The denoiser evaluations are the same launches, only the update launch differs, so the
 expectation is "within noise of the per-window loop".  Each timed call is a whole `sample()` between two device
 synchronisations; the order rotates from one repetition to the next, and a second per-window sampler (`windows_b`, its own
-capture of the same step) is the A / A control: how far two identical captured loops differ on the machine.  One JSON line
-per (N, F).
+capture of the same step) is the A / A control: how far two identical captured loops differ on the machine.
+`stitched_eta1` is the stochastic stitched loop (StochasticStitchedSampler, eta = 1: the update draws one Philox block per
+four trial elements inside the kernel) on the same trials, in the same rotation.  One JSON line per (N, F).
 
     python tools/stitch_rate.py [--trials 1 8] [--frames 200 1000] [--reps 10]"""
 import argparse
@@ -33,7 +34,7 @@ def main():
     ap.add_argument("--frames", type=int, nargs="+", default=[200, 1000])
     ap.add_argument("--reps", type=int, default=10)
     a = ap.parse_args()
-    from inferbiomechanics_amd.diffusion.sampler import ConditionalDDIMSampler, StitchedDDIMSampler
+    from inferbiomechanics_amd.diffusion.sampler import ConditionalDDIMSampler, StitchedDDIMSampler, StochasticStitchedSampler
     from inferbiomechanics_amd.models.DiffusionDenoisers import DiffusionTransformer
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -52,10 +53,12 @@ def main():
             W = st.layout["W"]
             zw, ow = st.to_windows(z).contiguous(), st.to_windows(obs).contiguous()
             win, win_b = ConditionalDDIMSampler(model, S), ConditionalDDIMSampler(model, S)
+            st1 = StochasticStitchedSampler(model, S, eta=1.0, seed=0)
             runs = {"windows": lambda: win.sample(zw, ow, mask), "windows_b": lambda: win_b.sample(zw, ow, mask),
-                    "stitched": lambda: st.sample(z, obs, cols)}
-            for fn in runs.values():
-                fn()
+                    "stitched": lambda: st.sample(z, obs, cols), "stitched_eta1": lambda: st1.sample(z, obs, cols)}
+            for _ in range(2):               # twice: the eta = 1 sampler's first call replaces the model's sampler tables,
+                for fn in runs.values():     # so the captures made before it are made again on the second pass
+                    fn()
             torch.cuda.synchronize()
             times = {k: [] for k in runs}
             names = list(runs)
@@ -73,6 +76,7 @@ def main():
                 line[f"{k}_steps_per_s"] = round(S / med, 1)
                 line[f"{k}_spread_pct"] = round(100 * (max(ts) - min(ts)) / med, 1)
             line["stitched_over_windows"] = round(line["stitched_steps_per_s"] / line["windows_steps_per_s"], 4)
+            line["stitched_eta1_over_stitched"] = round(line["stitched_eta1_steps_per_s"] / line["stitched_steps_per_s"], 4)
             line["windows_b_over_windows"] = round(line["windows_b_steps_per_s"] / line["windows_steps_per_s"], 4)
             print(json.dumps(line), flush=True)
 
