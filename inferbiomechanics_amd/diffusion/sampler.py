@@ -514,7 +514,7 @@ class StochasticStitchedSampler(StitchedDDIMSampler):
     on its id, not on its place in the batch or on the batch's size.  With observations, an observed element's stored noise
     follows the DDIM posterior given the observation (ConditionalDDIMSampler's eta > 0 loop), in every copy.  Layout,
     to_windows, the start state, the captured one-step graph and the launch count per step are the parent's; only the update
-    launch differs (ib_stitch_ddim_step_noise, csrc/stitch_noise.hip).  eta = 0 is the parent class bit for bit.  With
+    launch differs (ib_stitch_ddim_step_noise, csrc/stitch.hip).  eta = 0 is the parent class bit for bit.  With
     F == T it is ConditionalDDIMSampler(eta, seed) (or DDIMSampler without observations) with window ids = trial ids.  The
     solver is 'ddim': DPM-Solver++ stays deterministic.  The trial ids live in a device buffer the captured update reads, so
     a new batch or new ids of the same shape replay the captured step."""

@@ -7,8 +7,8 @@ fallback: if the library is missing or a call fails, a ``HipError`` is raised.
 
 The header is the only declaration of the ABI: the ctypes signatures (``_SIGS``) are parsed from it when this
 module is imported, so a new entry point needs its declaration there and its wrapper here, nothing else.  The stitched
-sampler updates are declared in a second header, ``include/ib_hip_stitch.h``, parsed the same way into ``_STITCH_SIGS``,
-and the stochastic stitched update in a third, ``include/ib_hip_stitch_noise.h``, into ``_STITCH_NOISE_SIGS``.
+sampler updates (csrc/stitch.hip) are declared in a second header, ``include/ib_hip_stitch.h``, parsed the same way into
+``_STITCH_SIGS``; a name may be declared once in the two.
 """
 from __future__ import annotations
 
@@ -27,7 +27,6 @@ LIB_PATH = os.environ.get("IB_HIP_LIB") or os.path.join(_HERE, "lib", "libib_hip
 AB_LIB_PATH = os.path.join(_HERE, "lib", "ab", "libib_hip_ab.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip.h")
 STITCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_stitch.h")
-STITCH_NOISE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_stitch_noise.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -90,15 +89,11 @@ def _read_header(path: Optional[str] = None) -> str:
                        f"derived from it, so the binding cannot work without it") from None
 
 
-_SIGS = _parse_header(_read_header())
-# the second header (stitched trial sampling), a table of its own: _SIGS and declared_symbols() describe ib_hip.h only
-_STITCH_SIGS = _parse_header(_read_header(STITCH_HEADER_PATH))
+# a table per header: _SIGS and declared_symbols() describe ib_hip.h only, _STITCH_SIGS the stitched trial sampling
+_SIGS, _STITCH_SIGS = (_parse_header(_read_header(_path)) for _path in (HEADER_PATH, STITCH_HEADER_PATH))
 if set(_SIGS) & set(_STITCH_SIGS):
-    raise HipError(f"declared in both headers: {sorted(set(_SIGS) & set(_STITCH_SIGS))}")
-# the third header (the stochastic stitched update), again a table of its own: the two above stay what they were
-_STITCH_NOISE_SIGS = _parse_header(_read_header(STITCH_NOISE_HEADER_PATH))
-if set(_STITCH_NOISE_SIGS) & (set(_SIGS) | set(_STITCH_SIGS)):
-    raise HipError(f"declared in two headers: {sorted(set(_STITCH_NOISE_SIGS) & (set(_SIGS) | set(_STITCH_SIGS)))}")
+    raise HipError(f"declared in two headers: {sorted(set(_SIGS) & set(_STITCH_SIGS))}")
+_ALL_SIGS = {**_SIGS, **_STITCH_SIGS}   # every entry point of the ABI: what _sig() looks up and lib() binds
 _kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_STITCH_KMAX[ \t]+(\d+)[ \t]*$", _read_header(STITCH_HEADER_PATH), flags=re.M)
 if _kmax is None:
     raise HipError(f"{STITCH_HEADER_PATH} does not define IB_STITCH_KMAX")
@@ -117,17 +112,9 @@ def stitch_symbols() -> List[str]:
     return sorted(_STITCH_SIGS)
 
 
-def stitch_noise_symbols() -> List[str]:
-    """Every function include/ib_hip_stitch_noise.h declares"""
-    return sorted(_STITCH_NOISE_SIGS)
-
-
 def _sig(name: str):
-    """(restype, argtypes) of an entry point of any of the headers"""
-    for table in (_SIGS, _STITCH_SIGS):
-        if name in table:
-            return table[name]
-    return _STITCH_NOISE_SIGS[name]
+    """(restype, argtypes) of an entry point of either header"""
+    return _ALL_SIGS[name]
 
 
 # pure host queries: no launch, no stream
@@ -402,7 +389,7 @@ def lib():
             raise HipError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C inferbiomechanics_amd/csrc` (hipcc --offload-arch=gfx950). There is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGS.items()) + list(_STITCH_SIGS.items()) + list(_STITCH_NOISE_SIGS.items()):
+        for name, (res, args) in _ALL_SIGS.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -2185,9 +2172,9 @@ def _step_tables(what, coef, ncols, timesteps, B, t_out, step_dev, obs_coef=None
     return S
 
 
-def _cond_operands(what, x, x0, z, mask, obs_coef, D):
-    """the masked state: x as _pitched_state, x0 / z like x, mask uint8 [T, ld], obs_coef fp32 [., 2] -> (B, T, D, ld)"""
-    B, T, D, ld = _pitched_state(what, x, D)
+def _masked_operands(what, x, x0, z, mask, obs_coef):
+    """the masked loop's operands beside a state x [..., T, ld]: x0 / z like x, mask uint8 [T, ld], obs_coef fp32 [., 2]"""
+    T, ld = x.shape[-2:]
     _like_x(what, "x0", x0, x)
     _like_x(what, "z", z, x)
     _req(mask, "mask", torch.uint8, 2)
@@ -2196,13 +2183,27 @@ def _cond_operands(what, x, x0, z, mask, obs_coef, D):
     _req(obs_coef, "obs_coef", torch.float32, 2)
     if obs_coef.shape[1] != 2 or not obs_coef.is_contiguous():
         raise HipError(f"{what}: obs_coef must be contiguous [S + 1, 2] fp32")
+
+
+def _cond_operands(what, x, x0, z, mask, obs_coef, D):
+    """the masked state: x as _pitched_state and its _masked_operands -> (B, T, D, ld)"""
+    B, T, D, ld = _pitched_state(what, x, D)
+    _masked_operands(what, x, x0, z, mask, obs_coef)
     return B, T, D, ld
 
 
-def _win_ids(what, win_id, B):
-    _req(win_id, "win_id", torch.int64, 1)
-    if win_id.numel() != B or not win_id.is_contiguous():
-        raise HipError(f"{what}: win_id must be contiguous int64 [B] = [{B}]")
+def _obs_noise_coef(what, obs_noise_coef, S):
+    _req(obs_noise_coef, "obs_noise_coef", torch.float32, 2)
+    if tuple(obs_noise_coef.shape) != (S, 2) or not obs_noise_coef.is_contiguous():
+        raise HipError(f"{what}: obs_noise_coef must be contiguous [S, 2] = [{S}, 2] fp32")
+
+
+def _win_ids(what, win_id, B, name="win_id", dim="B", device=None):
+    """the ids that key a sequence's noise: int64 [B], on `device` where one is given"""
+    _req(win_id, name, torch.int64, 1)
+    if win_id.numel() != B or not win_id.is_contiguous() or (device is not None and win_id.device != device):
+        where = "" if device is None else f" on the device of x ({device})"
+        raise HipError(f"{what}: {name} must be contiguous int64 [{dim}] = [{B}]{where}")
 
 
 def ddim_step(x, eps, coef, timesteps, step=0, step_dev=None, t_out=None):
@@ -2260,9 +2261,7 @@ def ddim_cond_step_noise(x, eps, x0, z, mask, coef, obs_coef, obs_noise_coef, ti
     _like_x(what, "eps", eps, x)
     S = _step_tables(what, coef, 3, timesteps, B, t_out, step_dev, obs_coef)
     _win_ids(what, win_id, B)
-    _req(obs_noise_coef, "obs_noise_coef", torch.float32, 2)
-    if tuple(obs_noise_coef.shape) != (S, 2) or not obs_noise_coef.is_contiguous():
-        raise HipError(f"{what}: obs_noise_coef must be contiguous [S, 2] = [{S}, 2] fp32")
+    _obs_noise_coef(what, obs_noise_coef, S)
     _check(lib().ib_ddim_cond_step_noise(_ptr(x), _ptr(eps), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef),
                                          _ptr(obs_noise_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out),
                                          _ptr(win_id), int(seed) & 0xFFFFFFFFFFFFFFFF, B, T, D, ld, dtype_code(x.dtype),
@@ -2300,7 +2299,7 @@ def _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D):
     """the window-batch state of a stitched update, x [N, W, T, ld] with eps like it, and its layout tables (schedule.
     stitch_layout, on x's device): start int32 [W], cover int32 [F, 2], wn fp32 [F, STITCH_KMAX], checked for what the kernel
     trusts -- every window inside the trial, every frame's windows really covering it.  x0 / z / mask / obs_coef: all None
-    (the unconditional loop) or all given, as _cond_operands takes them.  -> (N, W, T, F, D, ld)"""
+    (the unconditional loop) or all given, as _masked_operands takes them.  -> (N, W, T, F, D, ld)"""
     _req(x, "x", x.dtype, 4)
     if not x.is_contiguous():
         raise HipError(f"{what}: x must be a contiguous [N, W, T, ld] state")
@@ -2313,14 +2312,7 @@ def _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D):
     if any(given) and not all(given):
         raise HipError(f"{what}: x0, z, mask and obs_coef come together (the masked loop) or not at all")
     if all(given):
-        _like_x(what, "x0", x0, x)
-        _like_x(what, "z", z, x)
-        _req(mask, "mask", torch.uint8, 2)
-        if tuple(mask.shape) != (T, ld) or not mask.is_contiguous():
-            raise HipError(f"{what}: mask must be contiguous uint8 [T, ld] = [{T}, {ld}], got {tuple(mask.shape)}")
-        _req(obs_coef, "obs_coef", torch.float32, 2)
-        if obs_coef.shape[1] != 2 or not obs_coef.is_contiguous():
-            raise HipError(f"{what}: obs_coef must be contiguous [S + 1, 2] fp32")
+        _masked_operands(what, x, x0, z, mask, obs_coef)
     _req(start, "start", torch.int32, 1)
     _req(cover, "cover", torch.int32, 2)
     _req(wn, "wn", torch.float32, 2)
@@ -2388,7 +2380,7 @@ def stitch_dpmpp_step(x, eps, hist, x0, z, mask, coef, obs_coef, timesteps, star
 
 def stitch_ddim_step_noise(x, eps, x0, z, mask, coef, obs_coef, obs_noise_coef, timesteps, start, cover, wn, trial_ids, seed,
                            step=0, step_dev=None, t_out=None, D=None):
-    """stochastic DDIM / DDPM update of a stitched trial in place (csrc/stitch_noise.hip): as stitch_ddim_step with coef
+    """stochastic DDIM / DDPM update of a stitched trial in place (csrc/stitch.hip): as stitch_ddim_step with coef
     [S, 3] = (c_x, c_eps, sigma); the noise of trial n is keyed by (seed, trial_ids[n], step, TRIAL frame, column) and
     generated inside the kernel, so every copy of an element receives the same normal.  x0, z, mask, obs_coef and
     obs_noise_coef [S, 2]: all None, or the masked loop's operands as in ddim_cond_step_noise (z is updated in place at the
@@ -2399,12 +2391,8 @@ def stitch_ddim_step_noise(x, eps, x0, z, mask, coef, obs_coef, obs_noise_coef, 
     N, W, T, F, D, ld = _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D)
     S = _step_tables(what, coef, 3, timesteps, N * W, t_out, step_dev, obs_coef)
     if obs_noise_coef is not None:
-        _req(obs_noise_coef, "obs_noise_coef", torch.float32, 2)
-        if tuple(obs_noise_coef.shape) != (S, 2) or not obs_noise_coef.is_contiguous():
-            raise HipError(f"{what}: obs_noise_coef must be contiguous [S, 2] = [{S}, 2] fp32")
-    _req(trial_ids, "trial_ids", torch.int64, 1)
-    if trial_ids.numel() != N or not trial_ids.is_contiguous() or trial_ids.device != x.device:
-        raise HipError(f"{what}: trial_ids must be contiguous int64 [N] = [{N}] on the device of x ({x.device})")
+        _obs_noise_coef(what, obs_noise_coef, S)
+    _win_ids(what, trial_ids, N, "trial_ids", "N", x.device)
     _check(lib().ib_stitch_ddim_step_noise(_ptr(x), _ptr(eps), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef),
                                            _ptr(obs_noise_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out),
                                            _ptr(start), _ptr(cover), _ptr(wn), _ptr(trial_ids),

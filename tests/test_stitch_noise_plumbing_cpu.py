@@ -1,4 +1,4 @@
-"""Host-side plumbing of stochastic stitched sampling (no GPU): the third C-ABI header and its table, the refusals and the
+"""Host-side plumbing of stochastic stitched sampling (no GPU): its declaration in the stitched header, the refusals and the
 dry-run launches of StochasticStitchedSampler, predict_trial_ensemble, the visualize flags, and the kernel's registers."""
 import os
 import re
@@ -30,12 +30,12 @@ def _tr(dt=torch.float32, D=44, T=8):
 
 
 def test_third_header_has_its_own_table_and_both_builds_export_it():
+    """ib_stitch_ddim_step_noise is declared in the stitched header, bound from its table, exported by both builds"""
     from inferbiomechanics_amd import hip
-    assert hip.stitch_noise_symbols() == [NAME]
-    assert NAME not in hip._SIGS and NAME not in hip._STITCH_SIGS and NAME not in hip.declared_symbols()
-    assert hip.stitch_symbols() == ["ib_stitch_ddim_step", "ib_stitch_dpmpp_step"]      # the other tables are what they were
+    assert hip.stitch_symbols() == ["ib_stitch_ddim_step", NAME, "ib_stitch_dpmpp_step"]
+    assert NAME not in hip._SIGS and NAME not in hip.declared_symbols()                 # ib_hip.h's table is what it was
     assert len(hip._SIGS) == 127
-    res, args = hip._STITCH_NOISE_SIGS[NAME]
+    res, args = hip._STITCH_SIGS[NAME]
     assert res is hip._c.c_int and len(args) == 26 and args[-1] is hip._vp and args[17] is hip._c.c_uint64
     assert hip._is_launch(NAME) and hip._sig(NAME) == (res, args)
     for path in (hip.LIB_PATH, hip.AB_LIB_PATH):
@@ -47,12 +47,12 @@ def test_third_header_has_its_own_table_and_both_builds_export_it():
 
 
 def test_a_symbol_declared_in_two_headers_is_refused(monkeypatch):
-    """the module is loaded again under another name with a third header that declares ib_stitch_dpmpp_step (the second
-    header's) or ib_ddim_step (the first's) once more: the import must raise"""
+    """the module is loaded again under another name with a stitched header that declares ib_ddim_step (the first header's)
+    once more: the import must raise; so must a name repeated inside the one header"""
     import importlib.util
 
     from inferbiomechanics_amd import hip
-    third = open(hip.STITCH_NOISE_HEADER_PATH).read()
+    second = open(hip.STITCH_HEADER_PATH).read()
 
     def load(extra):
         spec = importlib.util.spec_from_file_location("inferbiomechanics_amd._hip_twice", hip.__file__)
@@ -61,21 +61,22 @@ def test_a_symbol_declared_in_two_headers_is_refused(monkeypatch):
 
         def fake_open(path, *a, **kw):
             f = real_open(path, *a, **kw)
-            if os.path.abspath(str(path)) != os.path.abspath(hip.STITCH_NOISE_HEADER_PATH):
+            if os.path.abspath(str(path)) != os.path.abspath(hip.STITCH_HEADER_PATH):
                 return f
             f.close()
             import io
-            return io.StringIO(third.replace("#ifdef __cplusplus\n}", extra + "\n#ifdef __cplusplus\n}"))
+            return io.StringIO(second.replace("#ifdef __cplusplus\n}", extra + "\n#ifdef __cplusplus\n}"))
 
         mod.__dict__["open"] = fake_open                               # the module's own lookup of open() finds this one
         spec.loader.exec_module(mod)
         return mod
 
-    assert load("").stitch_noise_symbols() == [NAME]                   # the loader itself works on the real text
-    for dup in ("int ib_stitch_dpmpp_step(void* x, ib_stream_t stream);", "int ib_ddim_step(void* x, ib_stream_t stream);"):
-        # the second copy of the module raises its own HipError class, a RuntimeError like the first
-        with pytest.raises(RuntimeError, match="declared in two headers.*" + dup.split("(")[0].split()[-1]):
-            load(dup)
+    assert NAME in load("").stitch_symbols()                           # the loader itself works on the real text
+    # the second copy of the module raises its own HipError class, a RuntimeError like the first
+    with pytest.raises(RuntimeError, match="declared in two headers.*ib_ddim_step"):
+        load("int ib_ddim_step(void* x, ib_stream_t stream);")
+    with pytest.raises(RuntimeError, match="ib_stitch_dpmpp_step is declared twice"):
+        load("int ib_stitch_dpmpp_step(void* x, ib_stream_t stream);")
 
 
 @pytest.mark.parametrize("cond", [False, True])
@@ -269,9 +270,11 @@ def test_kernel_resources_no_scratch_no_spill():
     if kr.hipcc() is None:
         pytest.skip("hipcc not installed")
     resources = kr.resources
-    rows = resources("stitch_noise.hip")
-    kernels = [r for r in rows if "stitch_noise_step_kernel" in r["kernel"]]
-    # fp32 / bf16 x {8-wide: cond x whole blocks, element-wise: cond}
-    assert len(kernels) == 2 * (4 + 2), [r["kernel"] for r in rows]
+    rows = resources("stitch.hip")
+    kernels = [r for r in rows if "stitch_step_kernel" in r["kernel"]]
+    # the 16 deterministic forms + the noise forms: fp32 / bf16 x {8-wide: cond x whole blocks, element-wise: cond}
+    assert len(kernels) == 16 + 2 * (4 + 2), [r["kernel"] for r in rows]
+    noise = [r for r in kernels if re.search(r"Li[18]ELb[01]ELi2ELb[01]E", r["mangled"])]
+    assert len(noise) == 2 * (4 + 2), [r["mangled"] for r in kernels]
     for r in rows:
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0, r

@@ -23,7 +23,7 @@ def _exports(path):
 def test_stitch_header_has_its_own_table_and_both_builds_export_it():
     from inferbiomechanics_amd import hip
     names = hip.stitch_symbols()
-    assert names == ["ib_stitch_ddim_step", "ib_stitch_dpmpp_step"]
+    assert names == ["ib_stitch_ddim_step", "ib_stitch_ddim_step_noise", "ib_stitch_dpmpp_step"]
     assert not set(names) & set(hip._SIGS) and not set(names) & set(hip.declared_symbols())
     for n in names:
         res, args = hip._STITCH_SIGS[n]
