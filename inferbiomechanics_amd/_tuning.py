@@ -19,6 +19,7 @@ _SPEC = {
     "no_layer_branch": ("IB_NO_LAYER_BRANCH", False),
     "layer_branch": ("IB_LAYER_BRANCH", False),
     "no_outproj_branch": ("IB_NO_OUTPROJ_BRANCH", False),
+    "no_head_merge": ("IB_NO_HEAD_MERGE", False),     # round 7: the transformer step's head as separate launches + the tr_time fork
     "pos_own_branch": ("IB_POS_OWN_BRANCH", False),   # frame-embedding gradients on a fifth branch of the step's tail (rounds 2-4)
     # ---- GEMM families
     "no_nt": ("IB_NO_NT", False),

@@ -17,7 +17,10 @@
 // row, so bias / embedding / gamma loads and every store are 8- or 16-byte pieces.
 // LayerNorm row statistics: 16-lane-group shuffles + one cross-wave exchange through LDS, fixed order (deterministic).
 #include "ib_common.h"
+#include "../../include/ib_hip_head.h"
+#include "head_jobs.h"
 #include "time_bwd.h"
+#include "launch_geom.h"
 #include <stdlib.h>
 
 namespace {
@@ -1531,9 +1534,45 @@ struct TimeFwdParams {
   const bf16_t* w1; int64_t ldw1; const float* b1;
   const bf16_t* w2; int64_t ldw2; const float* b2;
   bf16_t* s; bf16_t* zu; bf16_t* u; bf16_t* e; int64_t ld_e;
-  int B, out, ncg, time_blocks;
+  int B, out, ncg, time_blocks, pack_wgs;
   long long* prof;      // TIMING-ONLY: [time_blocks][8] stamps (ib_debug_set_chain_prof), else NULL
 };
+
+// The other independent jobs at the head of the TRANSFORMER step (ib_tr_head_prep), run by the blocks behind the time-MLP's
+// (and the packing blocks, of which that step has none): each a block range of CH_THREADS-wide blocks over a body of
+// head_jobs.h -- the very code of the stand-alone launch it replaces.  A job with no blocks is absent.
+struct HeadJobs {
+  // frame-embedding projection posproj = pos . W_p^T (tiny_matmul_kernel<false>'s body; all bf16)
+  const bf16_t* pos; int64_t sam, sak; const bf16_t* wp; int64_t sbk, sbn; bf16_t* posproj; int64_t ldc; int pm, pn, pk;
+  int pp_blocks;
+  // padded copy of a weight's column slice (cast2d_kernel's body)
+  CastJob cast; int cast_blocks;
+  // q_sample (q_sample_kernel<bf16_t, 4 or 1>'s body); t is the time-MLP's
+  const bf16_t* x0; const bf16_t* eps; const float* sqrt_ab; const float* sqrt_1mab; bf16_t* xt;
+  int64_t ld_xt, rows, rows_per_window, cols, sched_rows; int qs_v4, qs_blocks;
+};
+__device__ __forceinline__ void head_jobs_block(const HeadJobs& h, const int64_t* t, int b, int tid) {
+  if (b < h.pp_blocks) {
+    tiny_matmul_thread_body(h.pos, IB_BF16, h.sam, h.sak, h.wp, IB_BF16, h.sbk, h.sbn, h.posproj, IB_BF16, h.ldc, 0, h.pm, h.pn,
+                            h.pk, b * CH_THREADS + tid, h.pp_blocks * CH_THREADS);
+    return;
+  }
+  b -= h.pp_blocks;
+  if (b < h.cast_blocks) {
+    cast2d_job(h.cast, (int64_t)b * CH_THREADS + tid, (int64_t)h.cast_blocks * CH_THREADS);
+    return;
+  }
+  b -= h.cast_blocks;
+  if (b < h.qs_blocks) {
+    const int64_t first = (int64_t)b * CH_THREADS + tid, stride = (int64_t)h.qs_blocks * CH_THREADS;
+    if (h.qs_v4)
+      q_sample_body<bf16_t, 4>(h.x0, h.eps, t, h.sqrt_ab, h.sqrt_1mab, h.xt, h.ld_xt, h.rows, h.rows_per_window, h.cols,
+                               h.sched_rows, first, stride);
+    else
+      q_sample_body<bf16_t, 1>(h.x0, h.eps, t, h.sqrt_ab, h.sqrt_1mab, h.xt, h.ld_xt, h.rows, h.rows_per_window, h.cols,
+                               h.sched_rows, first, stride);
+  }
+}
 
 // NT1 = hidden / 128, KB1 = temb / 32 ; hidden = 128 * NT1 = 32 * KB2 ; output columns: 128 per workgroup (16 per wave);
 // rows (windows) per workgroup: 16 * MT.  Every column group recomputes the hidden layer of its rows, and that epilogue is
@@ -1542,8 +1581,10 @@ struct TimeFwdParams {
 // still fits the chip in one round; large batches keep MT = 4.
 // Blocks >= p.time_blocks of the same launch pack the chain kernel's weights (ib_mlp_chain_prep): the two jobs are
 // independent and each far too small to fill the chip; one launch saves a kernel boundary (~4.5 us in a captured step).
+// Blocks behind those run the transformer step's other head jobs (HeadJobs, ib_tr_head_prep).  The time-MLP blocks come
+// first: they are the launch's longest dependency chains.
 template <int NT1, int KB1, int MT>
-__global__ __launch_bounds__(CH_THREADS) void time_mlp_fwd_kernel(TimeFwdParams p, PackParams pp) {
+__global__ __launch_bounds__(CH_THREADS) void time_mlp_fwd_kernel(TimeFwdParams p, PackParams pp, HeadJobs hj) {
   constexpr int HID = 128 * NT1, KB2 = 4 * NT1, TE = 32 * KB1, ROWS = 16 * MT;
   constexpr int RS1 = TE * 2 + 16, RS2 = HID * 2 + 16;
   __shared__ __attribute__((aligned(16))) unsigned char smem[ROWS * RS1 + ROWS * RS2];
@@ -1551,7 +1592,9 @@ __global__ __launch_bounds__(CH_THREADS) void time_mlp_fwd_kernel(TimeFwdParams 
   unsigned char* uimg = smem + ROWS * RS1;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l16 = lane & 15;
   if ((int)blockIdx.x >= p.time_blocks) {
-    pack_blocks(pp, ((int)blockIdx.x - p.time_blocks) * CH_WAVES + wave, ((int)gridDim.x - p.time_blocks) * CH_WAVES, lane);
+    const int b = (int)blockIdx.x - p.time_blocks;
+    if (b < p.pack_wgs) pack_blocks(pp, b * CH_WAVES + wave, p.pack_wgs * CH_WAVES, lane);
+    else head_jobs_block(hj, p.slots ? reinterpret_cast<const int64_t*>(p.slots[2]) : p.t, b - p.pack_wgs, tid);
     return;
   }
   const int r0 = ((int)blockIdx.x / p.ncg) * ROWS, cg = (int)blockIdx.x % p.ncg;
@@ -1661,10 +1704,13 @@ extern "C" int ib_time_mlp_fwd_supported(int64_t temb, int64_t hidden, int64_t o
 }
 
 namespace {
+// 16 windows per workgroup (MT = 1) while that grid fits the chip in one round, else 64 (MT = 4)
+bool time_fwd_mt1(int64_t B, int64_t temb, int64_t out) { return temb == 128 && (out / 128) * ((B + 15) / 16) <= 256; }
+
 int time_fwd_launch(const float* table, int64_t table_rows, const int64_t* t, const void* w1, int64_t ldw1,
                     const float* b1, const void* w2, int64_t ldw2, const float* b2, void* s, void* zu, void* u, void* e,
                     int64_t ld_e, int64_t B, int64_t temb, int64_t hidden, int64_t out, const PackParams& pp,
-                    const void* const* in_slots, hipStream_t st) {
+                    const void* const* in_slots, hipStream_t st, const HeadJobs& hj = HeadJobs{}) {
   if (!ib_time_mlp_fwd_supported(temb, hidden, out)) return IB_E_UNSUPPORTED;
   if (!table || !t || !w1 || !b1 || !w2 || !b2 || !s || !zu || !u || !e || B <= 0 || table_rows <= 0) return IB_E_ARG;
   if (ldw1 < temb || ldw2 < hidden || ld_e < out || ldw1 % 8 != 0 || ldw2 % 8 != 0 || ld_e % 4 != 0) return IB_E_ARG;
@@ -1680,17 +1726,18 @@ int time_fwd_launch(const float* table, int64_t table_rows, const int64_t* t, co
   p.ncg = (int)(out / 128);
   // 16 windows per workgroup while that grid fits one round of the chip (beside the packing workgroups), else 64
   static const bool no_mt1 = ib_ab_set("IB_TIME_FWD_MT4");
-  const bool mt1 = !no_mt1 && temb == 128 && (int64_t)p.ncg * ((B + 15) / 16) <= 256;
+  const bool mt1 = !no_mt1 && time_fwd_mt1(B, temb, out);
   const int rows = mt1 ? 16 : CH_ROWS;
   p.time_blocks = p.ncg * (int)((B + rows - 1) / rows);
   p.prof = IB_AB_PROF(g_chain_prof);
   const int pack_wgs = pp.total_blocks > 0 ? ib_grid_1d(pp.total_blocks, CH_WAVES, mt1 ? 128 : 224) : 0;
-  const dim3 grid((unsigned)(p.time_blocks + pack_wgs));
+  p.pack_wgs = pack_wgs;
+  const dim3 grid((unsigned)(p.time_blocks + pack_wgs + hj.pp_blocks + hj.cast_blocks + hj.qs_blocks));
   if (temb == 128 && hidden == 512) {
-    if (mt1) hipLaunchKernelGGL((time_mlp_fwd_kernel<4, 4, 1>), grid, dim3(CH_THREADS), 0, st, p, pp);
-    else hipLaunchKernelGGL((time_mlp_fwd_kernel<4, 4, 4>), grid, dim3(CH_THREADS), 0, st, p, pp);
+    if (mt1) hipLaunchKernelGGL((time_mlp_fwd_kernel<4, 4, 1>), grid, dim3(CH_THREADS), 0, st, p, pp, hj);
+    else hipLaunchKernelGGL((time_mlp_fwd_kernel<4, 4, 4>), grid, dim3(CH_THREADS), 0, st, p, pp, hj);
   } else {
-    hipLaunchKernelGGL((time_mlp_fwd_kernel<1, 1, 4>), grid, dim3(CH_THREADS), 0, st, p, pp);
+    hipLaunchKernelGGL((time_mlp_fwd_kernel<1, 1, 4>), grid, dim3(CH_THREADS), 0, st, p, pp, hj);
   }
   IB_CHECK_LAUNCH();
   return IB_OK;
@@ -1717,6 +1764,51 @@ extern "C" int ib_mlp_chain_prep(const float* table, int64_t table_rows, const i
   if (rc != IB_OK) return rc;
   return time_fwd_launch(table, table_rows, t, w1, ldw1, b1, w2, ldw2, b2, s, zu, u, e, ld_e, B, temb, hidden, out, pp,
                          in_slots, ib_s(stream));
+}
+
+// The head of the TRANSFORMER denoiser's training step as one launch: the time-MLP forward (ib_time_mlp_fwd's arguments and
+// blocks, unchanged) and, each optional, q_sample (x0 .. sched_rows as ib_q_sample, bf16, the same t), the frame-embedding
+// projection posproj [pm, pn] = A . B with A(m, k) = pos[m sam + k sak], B(k, n) = wp[k sbk + n sbn] (ib_tiny_matmul's
+// short-reduction form, pk < 64, all bf16) and a pitched bf16 copy cast_dst[r][c] = cast_src[r][c] (ib_cast2d).  They are
+// mutually independent; before, two of them ran in series on the main stream beside a forked branch for the others.
+// Behind the time-MLP's blocks come the latency-bound jobs (projection, copy), then q_sample's, which only stream.
+extern "C" int ib_tr_head_prep_supported(int64_t temb, int64_t hidden, int64_t out, int64_t B) {
+  // the 16-window time kernel holds 21 KB of LDS: four blocks of the element-wise jobs share a CU.  Behind the 64-window
+  // kernel (84 KB) they would run one to a CU: such batches keep the separate launches.
+  return (ib_time_mlp_fwd_supported(temb, hidden, out) && B > 0 && time_fwd_mt1(B, temb, out)) ? 1 : 0;
+}
+extern "C" int ib_tr_head_prep(const float* table, int64_t table_rows, const int64_t* t, const void* w1, int64_t ldw1,
+                               const float* b1, const void* w2, int64_t ldw2, const float* b2, void* s, void* zu, void* u,
+                               void* e, int64_t ld_e, int64_t B, int64_t temb, int64_t hidden, int64_t out,
+                               const void* x0, const void* eps, const float* sqrt_ab, const float* sqrt_1mab, void* x_t,
+                               int64_t ld_xt, int64_t T, int64_t D, int64_t sched_rows,
+                               const void* pos, int64_t sam, int64_t sak, const void* wp, int64_t sbk, int64_t sbn,
+                               void* posproj, int64_t ldc, int64_t pm, int64_t pn, int64_t pk,
+                               const void* cast_src, int64_t cast_lds, void* cast_dst, int64_t cast_ldd, int64_t cast_rows,
+                               int64_t cast_cols, ib_stream_t stream) {
+  HeadJobs h{};
+  if (x0) {
+    if (!eps || !sqrt_ab || !sqrt_1mab || !x_t || T <= 0 || D <= 0 || sched_rows <= 0 || ld_xt < D) return IB_E_ARG;
+    h.x0 = (const bf16_t*)x0; h.eps = (const bf16_t*)eps; h.sqrt_ab = sqrt_ab; h.sqrt_1mab = sqrt_1mab; h.xt = (bf16_t*)x_t;
+    h.ld_xt = ld_xt; h.rows = B * T; h.rows_per_window = T; h.cols = D; h.sched_rows = sched_rows;
+    h.qs_v4 = ib_q_sample_v4(D, ld_xt, 2, x0, eps, x_t) ? 1 : 0;
+    h.qs_blocks = ib_grid_1d(h.rows * D / (h.qs_v4 ? 4 : 1), CH_THREADS, 768);
+  }
+  if (pos) {
+    if (!wp || !posproj || pm <= 0 || pn <= 0 || pk <= 0 || ldc < pn) return IB_E_ARG;
+    if (pk >= 64 || pm * pn > (1 << 22)) return IB_E_UNSUPPORTED;      // the one-thread-per-element form only
+    h.pos = (const bf16_t*)pos; h.sam = sam; h.sak = sak; h.wp = (const bf16_t*)wp; h.sbk = sbk; h.sbn = sbn;
+    h.posproj = (bf16_t*)posproj; h.ldc = ldc; h.pm = (int)pm; h.pn = (int)pn; h.pk = (int)pk;
+    h.pp_blocks = ib_grid_1d(pm * pn, CH_THREADS, 128);
+  }
+  if (cast_src) {
+    if (!cast_dst || cast_rows <= 0 || cast_cols <= 0 || cast_lds < cast_cols || cast_ldd < cast_cols) return IB_E_ARG;
+    h.cast = CastJob{cast_src, cast_dst, cast_lds, cast_ldd, cast_rows, cast_cols, IB_BF16, IB_BF16};
+    h.cast_blocks = ib_grid_1d(cast_rows * cast_cols, CH_THREADS, 128);
+  }
+  PackParams pp{};
+  return time_fwd_launch(table, table_rows, t, w1, ldw1, b1, w2, ldw2, b2, s, zu, u, e, ld_e, B, temb, hidden, out, pp,
+                         nullptr, ib_s(stream), h);
 }
 
 // ---- fused time-embedding MLP backward (hidden layer):  dzu = (de W2) * silu'(zu),  dW1 = dzu^T s,  db1 = colsum(dzu)

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "ib_common.h"
+#include "head_jobs.h"
 #include "launch.h"
 #include "philox.h"
 
@@ -49,51 +50,14 @@ __device__ __forceinline__ void stv(T* p, const float (&v)[V]) {
   }
 }
 
-// One element of q_sample, a * x + s * e, with its fp32 roundings spelled out.  q_sample_kernel and the free columns of
-// q_sample_cond_kernel both go through it, so the two agree bit for bit however the compiler would contract the bare
-// expression in either kernel.  The forms are those that expression compiled to in q_sample_kernel<T, V> for gfx950 (its
-// ISA is unchanged by the helper): the lone fp32 element sums two rounded products; every other form fuses a * x into the
-// rounded s * e.
-template <typename T, int V>
-__device__ __forceinline__ float q_mix(float a, float x, float s, float e) {
-#pragma clang fp contract(off)
-  if constexpr (V == 1 && sizeof(T) == 4) return a * x + s * e;
-  else return __builtin_fmaf(a, x, s * e);
-}
-
-// rows = B*T tokens, cols = D features; 4 consecutive columns per thread (8 B bf16 / 16 B fp32).  x_t may have a
-// padded leading dimension (the trainer keeps D = 300 activations at ld = 304 so every row starts 16-byte aligned).
+// q_mix (one element of q_sample with its roundings spelled out) and the kernel's body live in head_jobs.h: the merged head
+// launch of the transformer step (chain.hip: ib_tr_head_prep) runs the same body as a block range of its grid.
 template <typename T, int V>
 __global__ void q_sample_kernel(const T* __restrict__ x0, const T* __restrict__ eps, const int64_t* __restrict__ t,
                                 const float* __restrict__ sqrt_ab, const float* __restrict__ sqrt_1mab, T* __restrict__ xt,
                                 int64_t ld_xt, int64_t rows, int64_t rows_per_window, int64_t cols, int64_t table_rows) {
-  const int64_t cv = cols / V;
-  const int64_t n = rows * cv;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / cv, c = (i % cv) * V;
-    int64_t k = t[r / rows_per_window];
-    k = k < 0 ? 0 : (k >= table_rows ? table_rows - 1 : k);
-    const float a = sqrt_ab[k], s = sqrt_1mab[k];
-    if constexpr (V == 4) {
-      float x[4], e[4];
-      if constexpr (sizeof(T) == 2) {
-        bf16x4_t tx = *reinterpret_cast<const bf16x4_t*>(x0 + r * cols + c), te = *reinterpret_cast<const bf16x4_t*>(eps + r * cols + c);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { x[j] = (float)tx[j]; e[j] = (float)te[j]; }
-        bf16x4_t o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (bf16_t)q_mix<T, 4>(a, x[j], s, e[j]);
-        *reinterpret_cast<bf16x4_t*>(xt + r * ld_xt + c) = o;
-      } else {
-        const float4 tx = *reinterpret_cast<const float4*>(x0 + r * cols + c), te = *reinterpret_cast<const float4*>(eps + r * cols + c);
-        *reinterpret_cast<float4*>(xt + r * ld_xt + c) =
-            make_float4(q_mix<T, 4>(a, tx.x, s, te.x), q_mix<T, 4>(a, tx.y, s, te.y), q_mix<T, 4>(a, tx.z, s, te.z),
-                        q_mix<T, 4>(a, tx.w, s, te.w));
-      }
-    } else {
-      xt[r * ld_xt + c] = ib_from_f32<T>(q_mix<T, 1>(a, ib_to_f32(x0[r * cols + c]), s, ib_to_f32(eps[r * cols + c])));
-    }
-  }
+  q_sample_body<T, V>(x0, eps, t, sqrt_ab, sqrt_1mab, xt, ld_xt, rows, rows_per_window, cols, table_rows,
+                      (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 // q_sample for a denoiser conditioned on the first C columns of every row (0 < C < cols): those columns reach x_t as they

@@ -24,6 +24,8 @@
 // read back by this path.  Bound: the matrix pipes (64-row panels: 8 GEMM phases of [64 x 512 x 512] per direction) and the
 // L2 -> CU weight stream (4 MB per workgroup and direction).
 #include "ffn_chain.h"
+#include "../../include/ib_hip_head.h"
+#include "head_jobs.h"
 
 #ifdef IB_AB
 long long* g_ffn_prof = nullptr;     // TIMING-ONLY (tools/ffn_prof.py, tools/layer_prof.py): [workgroups][64] wall-clock stamps,
@@ -314,11 +316,16 @@ constexpr int FF_MAXDESC = 96;                            // layers x ({fwd1, fw
 struct FfnPackParams { FfnPackDesc d[FF_MAXDESC]; int count; };
 constexpr int FF_BLOCKS_PER_DESC = 32 * FF_KB;            // 512 one-KiB blocks
 
-__global__ __launch_bounds__(256) void ffn_pack_kernel(FfnPackParams p) {
-  __shared__ bf16_t tile[4][32][17];                      // per wave: a [32 k][16 n] source tile, transposed through LDS
+// The step's other per-step weight refreshes ride in the same launch (ib_ffn_chain_pack_ex) as block ranges BEHIND the
+// packing blocks -- layer 0's images are read first: the transposed weight copies (transpose_multi_kernel's body, one
+// 64 x 64 tile per block) and up to two pitched copies (cast2d_kernel's body).  Both counts 0: the packing launch as it was.
+constexpr int FF_MAXTR = 16, FF_MAXCAST = 2;
+struct FfnPackExtra { TrMultiT<FF_MAXTR> tr; CastJob cast[FF_MAXCAST]; int pack_blocks, tr_blocks, cast_blocks[FF_MAXCAST]; };
+
+__device__ __forceinline__ void ffn_pack_body(const FfnPackParams& p, bf16_t (*tile)[32][17], int first, int stride) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int total = p.count * FF_BLOCKS_PER_DESC;
-  for (int blk = blockIdx.x * 4 + w; blk < total; blk += gridDim.x * 4) {
+  for (int blk = first; blk < total; blk += stride) {
     const FfnPackDesc& d = p.d[blk / FF_BLOCKS_PER_DESC];
     const int local = blk % FF_BLOCKS_PER_DESC;
     const int nt = local % 32, kb = local / 32;
@@ -344,6 +351,36 @@ __global__ __launch_bounds__(256) void ffn_pack_kernel(FfnPackParams p) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     reinterpret_cast<bf16x8_t*>(d.dst)[(int64_t)local * 64 + lane] = v;
+  }
+}
+
+__global__ __launch_bounds__(256) void ffn_pack_kernel(FfnPackParams p) {
+  __shared__ bf16_t tile[4][32][17];                      // per wave: a [32 k][16 n] source tile, transposed through LDS
+  ffn_pack_body(p, tile, blockIdx.x * 4 + (threadIdx.x >> 6), gridDim.x * 4);
+}
+
+__global__ __launch_bounds__(256) void ffn_pack_ex_kernel(FfnPackParams p, FfnPackExtra x) {
+  // one buffer for the packing waves' tiles (4352 B) or a transpose tile (9216 B): a block runs one job
+  __shared__ __attribute__((aligned(16))) bf16_t smem[64 * TR_TILE_LD];
+  static_assert(sizeof(bf16_t) * 4 * 32 * 17 <= sizeof(bf16_t) * 64 * TR_TILE_LD, "packing tiles must fit");
+  int b = (int)blockIdx.x;
+  if (b < x.pack_blocks) {
+    ffn_pack_body(p, reinterpret_cast<bf16_t (*)[32][17]>(smem), b * 4 + (threadIdx.x >> 6), x.pack_blocks * 4);
+    return;
+  }
+  b -= x.pack_blocks;
+  if (b < x.tr_blocks) {
+    transpose_multi_body(x.tr, b, reinterpret_cast<bf16_t (*)[TR_TILE_LD]>(smem));
+    return;
+  }
+  b -= x.tr_blocks;
+#pragma unroll
+  for (int j = 0; j < FF_MAXCAST; ++j) {
+    if (b < x.cast_blocks[j]) {
+      cast2d_job(x.cast[j], (int64_t)b * 256 + threadIdx.x, (int64_t)x.cast_blocks[j] * 256);
+      return;
+    }
+    b -= x.cast_blocks[j];
   }
 }
 
@@ -385,13 +422,13 @@ extern "C" size_t ib_ffn_chain_attn_mask_bytes(int64_t M, int64_t d, int64_t ffn
   return (size_t)n * nc * FF_THREADS * sizeof(uint2);
 }
 
-extern "C" int ib_ffn_chain_pack(const void* const* w1, const int64_t* ld1, const void* const* w2, const int64_t* ld2,
-                                 const void* const* wo, const int64_t* ldo, const void* const* wqkv, const int64_t* ldq,
-                                 void* const* packed, int layers, int64_t d, int64_t ffn, ib_stream_t stream) {
+namespace {
+int ffn_pack_build(const void* const* w1, const int64_t* ld1, const void* const* w2, const int64_t* ld2,
+                   const void* const* wo, const int64_t* ldo, const void* const* wqkv, const int64_t* ldq,
+                   void* const* packed, int layers, int64_t d, int64_t ffn, FfnPackParams& pp) {
   if (!w1 || !ld1 || !w2 || !ld2 || !packed || layers < 1 || !ib_ffn_chain_supported(d, ffn)) return IB_E_ARG;
   const int nc = (int)(ffn / FF_CHUNK);
   if (layers * (4 * nc + 8) > FF_MAXDESC) return IB_E_UNSUPPORTED;
-  FfnPackParams pp{};
   int c = 0;
   for (int l = 0; l < layers; ++l) {
     if (!w1[l] || !w2[l] || !packed[l] || ld1[l] < d || ld2[l] < ffn || ld1[l] % 8 || ld2[l] % 8) return IB_E_ARG;
@@ -433,7 +470,56 @@ extern "C" int ib_ffn_chain_pack(const void* const* w1, const int64_t* ld1, cons
     }
   }
   pp.count = c;
-  hipLaunchKernelGGL(ffn_pack_kernel, dim3(ib_grid_1d((int64_t)c * FF_BLOCKS_PER_DESC, 4, 2048)), dim3(256), 0, ib_s(stream), pp);
+  return IB_OK;
+}
+}  // namespace
+
+extern "C" int ib_ffn_chain_pack(const void* const* w1, const int64_t* ld1, const void* const* w2, const int64_t* ld2,
+                                 const void* const* wo, const int64_t* ldo, const void* const* wqkv, const int64_t* ldq,
+                                 void* const* packed, int layers, int64_t d, int64_t ffn, ib_stream_t stream) {
+  FfnPackParams pp{};
+  const int rc = ffn_pack_build(w1, ld1, w2, ld2, wo, ldo, wqkv, ldq, packed, layers, d, ffn, pp);
+  if (rc != IB_OK) return rc;
+  hipLaunchKernelGGL(ffn_pack_kernel, dim3(ib_grid_1d((int64_t)pp.count * FF_BLOCKS_PER_DESC, 4, 2048)), dim3(256), 0, ib_s(stream), pp);
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+// ib_ffn_chain_pack + ib_transpose_multi (ntr <= 16 bf16 pairs, arguments as there) + up to two ib_cast2d copies
+// (ncast <= 2; dtype codes per copy) as ONE launch: everything the training step refreshes from the weights the optimizer
+// just moved.  The packing blocks come first (layer 0's images are the first to be read).
+extern "C" int ib_ffn_chain_pack_ex(const void* const* w1, const int64_t* ld1, const void* const* w2, const int64_t* ld2,
+                                    const void* const* wo, const int64_t* ldo, const void* const* wqkv, const int64_t* ldq,
+                                    void* const* packed, int layers, int64_t d, int64_t ffn,
+                                    int ntr, const void* const* tr_src, const int64_t* tr_lds, void* const* tr_dst,
+                                    const int64_t* tr_ldd, const int64_t* tr_rows, const int64_t* tr_cols,
+                                    int ncast, const void* const* c_src, const int64_t* c_lds, const int32_t* c_sdtype,
+                                    void* const* c_dst, const int64_t* c_ldd, const int32_t* c_ddtype, const int64_t* c_rows,
+                                    const int64_t* c_cols, ib_stream_t stream) {
+  FfnPackParams pp{};
+  const int rc = ffn_pack_build(w1, ld1, w2, ld2, wo, ldo, wqkv, ldq, packed, layers, d, ffn, pp);
+  if (rc != IB_OK) return rc;
+  if (ntr < 0 || ntr > FF_MAXTR || ncast < 0 || ncast > FF_MAXCAST) return IB_E_UNSUPPORTED;
+  if (ntr && (!tr_src || !tr_lds || !tr_dst || !tr_ldd || !tr_rows || !tr_cols)) return IB_E_ARG;
+  if (ncast && (!c_src || !c_lds || !c_sdtype || !c_dst || !c_ldd || !c_ddtype || !c_rows || !c_cols)) return IB_E_ARG;
+  FfnPackExtra x{};
+  x.pack_blocks = ib_grid_1d((int64_t)pp.count * FF_BLOCKS_PER_DESC, 4, 2048);
+  x.tr.n = ntr;
+  int blk = 0;
+  for (int i = 0; i < ntr; ++i)
+    if (!tr_multi_add(x.tr, i, tr_src[i], tr_lds[i], tr_dst[i], tr_ldd[i], tr_rows[i], tr_cols[i], blk)) return IB_E_ARG;
+  x.tr.blk0[ntr] = blk;
+  x.tr_blocks = blk;
+  int total = x.pack_blocks + x.tr_blocks;
+  for (int j = 0; j < ncast; ++j) {
+    if (!c_src[j] || !c_dst[j] || c_rows[j] <= 0 || c_cols[j] <= 0 || c_lds[j] < c_cols[j] || c_ldd[j] < c_cols[j]) return IB_E_ARG;
+    for (int dt : {(int)c_sdtype[j], (int)c_ddtype[j]})
+      if (dt != IB_F32 && dt != IB_BF16) return IB_E_DTYPE;
+    x.cast[j] = CastJob{c_src[j], c_dst[j], c_lds[j], c_ldd[j], c_rows[j], c_cols[j], (int)c_sdtype[j], (int)c_ddtype[j]};
+    x.cast_blocks[j] = ib_grid_1d(c_rows[j] * c_cols[j], 256, 256);
+    total += x.cast_blocks[j];
+  }
+  hipLaunchKernelGGL(ffn_pack_ex_kernel, dim3(total), dim3(256), 0, ib_s(stream), pp, x);
   IB_CHECK_LAUNCH();
   return IB_OK;
 }

@@ -25,6 +25,7 @@
 //                                                            ib_transpose_multi)
 #include "ib_common.h"
 #include "gemm_nt.h"
+#include "head_jobs.h"
 #include <type_traits>
 
 namespace {
@@ -494,45 +495,11 @@ extern "C" int ib_debug_set_nt_prof(void*) { return IB_E_UNSUPPORTED; }       //
 // GEMMs read k-contiguously; refreshed once per step after the optimizer moved the weights).  64 x 64 tiles through LDS.
 namespace {
 constexpr int TR_MAX = 32;
-struct TrMulti { const bf16_t* src[TR_MAX]; bf16_t* dst[TR_MAX]; int rows[TR_MAX], cols[TR_MAX], lds[TR_MAX], ldd[TR_MAX], blk0[TR_MAX + 1]; int n; unsigned vec; };
+using TrMulti = TrMultiT<TR_MAX>;
+// body: head_jobs.h (ib_ffn_chain_pack_ex runs the same tiles as a block range of the packing launch)
 __global__ __launch_bounds__(256) void transpose_multi_kernel(TrMulti m) {
-  __shared__ __attribute__((aligned(16))) bf16_t tile[64][72];      // 144-byte rows: 16-byte row writes stay aligned
-  int e = 0;
-  for (int j = 1; j < m.n; ++j)
-    if ((int)blockIdx.x >= m.blk0[j]) e = j;
-  const int b = (int)blockIdx.x - m.blk0[e];
-  const int R = m.rows[e], Cc = m.cols[e];
-  const int tc = (Cc + 63) / 64;
-  const int r0 = (b / tc) * 64, c0 = (b % tc) * 64;
-  const bf16_t* src = m.src[e];
-  bf16_t* dst = m.dst[e];
-  if ((m.vec >> e) & 1u) {
-    // whole 64 x 64 tiles of 16-byte aligned matrices (every layer weight): 16-byte global accesses on both sides -- two
-    // loads and two stores per thread instead of sixteen 2-byte ones each way (the launch was 21.7 us for 52 MB)
-    const int pr = threadIdx.x >> 3, pc = threadIdx.x & 7;          // row 0..31 (+32), 16-byte piece 0..7
-    uint4 v[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-      v[h] = *reinterpret_cast<const uint4*>(src + (int64_t)(r0 + pr + 32 * h) * m.lds[e] + c0 + 8 * pc);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) *reinterpret_cast<uint4*>(&tile[pr + 32 * h][8 * pc]) = v[h];
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int c = pr + 32 * h;                                    // destination row = source column
-      bf16x8_t o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = tile[8 * pc + k][c];
-      *reinterpret_cast<bf16x8_t*>(dst + (int64_t)(c0 + c) * m.ldd[e] + r0 + 8 * pc) = o;
-    }
-    return;
-  }
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  for (int r = ty; r < 64; r += 4)
-    tile[r][tx] = (r0 + r < R && c0 + tx < Cc) ? src[(int64_t)(r0 + r) * m.lds[e] + c0 + tx] : (bf16_t)0.f;
-  __syncthreads();
-  for (int c = ty; c < 64; c += 4)
-    if (c0 + c < Cc && r0 + tx < R) dst[(int64_t)(c0 + c) * m.ldd[e] + r0 + tx] = tile[tx][c];
+  __shared__ __attribute__((aligned(16))) bf16_t tile[64][TR_TILE_LD];
+  transpose_multi_body(m, (int)blockIdx.x, tile);
 }
 }  // namespace
 
@@ -543,16 +510,8 @@ extern "C" int ib_transpose_multi(int n, const void* const* src, const int64_t* 
   TrMulti m{};
   m.n = n;
   int blk = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!src[i] || !dst[i] || rows[i] <= 0 || cols[i] <= 0 || lds[i] < cols[i] || ldd[i] < rows[i]) return IB_E_ARG;
-    m.src[i] = (const bf16_t*)src[i]; m.dst[i] = (bf16_t*)dst[i];
-    m.rows[i] = (int)rows[i]; m.cols[i] = (int)cols[i]; m.lds[i] = (int)lds[i]; m.ldd[i] = (int)ldd[i];
-    m.blk0[i] = blk;
-    if (rows[i] % 64 == 0 && cols[i] % 64 == 0 && lds[i] % 8 == 0 && ldd[i] % 8 == 0 &&
-        (reinterpret_cast<uintptr_t>(src[i]) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst[i]) & 15) == 0)
-      m.vec |= 1u << i;
-    blk += (int)(((rows[i] + 63) / 64) * ((cols[i] + 63) / 64));
-  }
+  for (int i = 0; i < n; ++i)
+    if (!tr_multi_add(m, i, src[i], lds[i], dst[i], ldd[i], rows[i], cols[i], blk)) return IB_E_ARG;
   m.blk0[n] = blk;
   hipLaunchKernelGGL(transpose_multi_kernel, dim3(blk), dim3(256), 0, ib_s(stream), m);
   IB_CHECK_LAUNCH();

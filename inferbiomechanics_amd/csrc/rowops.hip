@@ -3,6 +3,7 @@
 // One wave (64 lanes) owns one row; a lane holds CH chunks of 4 consecutive elements in registers
 // (8- or 16-byte loads), so every tensor crosses HBM exactly once per kernel.
 #include "ib_common.h"
+#include "head_jobs.h"
 #include <stdlib.h>
 
 namespace {
@@ -550,11 +551,7 @@ __global__ void concat_keys_kernel(ConcatArgs a, T* __restrict__ out, int64_t ro
 template <typename S, typename D>
 __global__ void cast2d_kernel(const S* __restrict__ src, int64_t lds, D* __restrict__ dst, int64_t ldd, int64_t rows,
                               int64_t cols) {
-  const int64_t n = rows * cols;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = i / cols, c = i % cols;
-    dst[r * ldd + c] = ib_from_f32<D>(ib_to_f32(src[r * lds + c]));
-  }
+  cast2d_body(src, lds, dst, ldd, rows, cols, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 template <typename T, int LPR, int CH>
@@ -777,18 +774,7 @@ extern "C" int ib_cast(const void* src, int src_dtype, void* dst, int dst_dtype,
 // scalar loads for 1.5 MFLOP.  K >= 64: one wave per output element (lanes stride the reduction, butterfly sum);
 // shorter reductions: one thread per output element.  fp32 accumulation in a fixed order (bitwise reproducible).
 namespace {
-__device__ __forceinline__ float tiny_ld(const void* p, int dtype, int64_t i) {
-  return dtype == IB_F32 ? static_cast<const float*>(p)[i] : static_cast<float>(static_cast<const bf16_t*>(p)[i]);
-}
-__device__ __forceinline__ void tiny_st(void* p, int dtype, int64_t i, float v, int accumulate) {
-  if (dtype == IB_F32) {
-    float* q = static_cast<float*>(p) + i;
-    *q = accumulate ? *q + v : v;
-  } else {
-    bf16_t* q = static_cast<bf16_t*>(p) + i;
-    *q = static_cast<bf16_t>(accumulate ? static_cast<float>(*q) + v : v);
-  }
-}
+// tiny_ld / tiny_st and the one-thread-per-element body: head_jobs.h (shared with the merged head launch, chain.hip)
 template <bool WAVE>
 __global__ __launch_bounds__(256) void tiny_matmul_kernel(const void* __restrict__ A, int ad, int64_t sam, int64_t sak,
                                                           const void* __restrict__ B, int bd, int64_t sbk, int64_t sbn,
@@ -816,25 +802,8 @@ __global__ __launch_bounds__(256) void tiny_matmul_kernel(const void* __restrict
       if (lane == 0) tiny_st(C, cd, (int64_t)m * ldc + n, acc, accumulate);
     }
   } else {
-    for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < total; o += gridDim.x * blockDim.x) {
-      const int m = o / N, n = o - m * N;
-      // a rolled loop is one memory round trip per k in sequence (K = 30: 31 us for the [50, 30] x [30, 512] frame-embedding
-      // projection at the head of every step): batches of 8 operand pairs are requested together, the sum keeps its order
-      float acc = 0.f;
-      for (int k0 = 0; k0 < K; k0 += 8) {
-        float a[8], b[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int k = min(k0 + e, K - 1);
-          a[e] = tiny_ld(A, ad, m * sam + k * sak);
-          b[e] = tiny_ld(B, bd, k * sbk + n * sbn);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (k0 + e < K) acc += a[e] * b[e];
-      }
-      tiny_st(C, cd, (int64_t)m * ldc + n, acc, accumulate);
-    }
+    tiny_matmul_thread_body(A, ad, sam, sak, B, bd, sbk, sbn, C, cd, ldc, accumulate, M, N, K,
+                            (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)(gridDim.x * blockDim.x));
   }
 }
 }  // namespace

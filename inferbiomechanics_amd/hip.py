@@ -8,7 +8,8 @@ fallback: if the library is missing or a call fails, a ``HipError`` is raised.
 The header is the only declaration of the ABI: the ctypes signatures (``_SIGS``) are parsed from it when this
 module is imported, so a new entry point needs its declaration there and its wrapper here, nothing else.  The stitched
 sampler updates (csrc/stitch.hip) are declared in a second header, ``include/ib_hip_stitch.h``, parsed the same way into
-``_STITCH_SIGS``; a name may be declared once in the two.
+``_STITCH_SIGS``, the merged head launches of the transformer step (csrc/head_jobs.h) in a third, ``include/ib_hip_head.h``
+(``_HEAD_SIGS``); a name may be declared once in the three.
 """
 from __future__ import annotations
 
@@ -27,6 +28,7 @@ LIB_PATH = os.environ.get("IB_HIP_LIB") or os.path.join(_HERE, "lib", "libib_hip
 AB_LIB_PATH = os.path.join(_HERE, "lib", "ab", "libib_hip_ab.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip.h")
 STITCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_stitch.h")
+HEAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_head.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -90,10 +92,12 @@ def _read_header(path: Optional[str] = None) -> str:
 
 
 # a table per header: _SIGS and declared_symbols() describe ib_hip.h only, _STITCH_SIGS the stitched trial sampling
-_SIGS, _STITCH_SIGS = (_parse_header(_read_header(_path)) for _path in (HEADER_PATH, STITCH_HEADER_PATH))
-if set(_SIGS) & set(_STITCH_SIGS):
-    raise HipError(f"declared in two headers: {sorted(set(_SIGS) & set(_STITCH_SIGS))}")
-_ALL_SIGS = {**_SIGS, **_STITCH_SIGS}   # every entry point of the ABI: what _sig() looks up and lib() binds
+_SIGS, _STITCH_SIGS, _HEAD_SIGS = (_parse_header(_read_header(_path))
+                                   for _path in (HEADER_PATH, STITCH_HEADER_PATH, HEAD_HEADER_PATH))
+_ALL_SIGS = {**_SIGS, **_STITCH_SIGS, **_HEAD_SIGS}   # every entry point of the ABI: what _sig() looks up and lib() binds
+if len(_ALL_SIGS) != len(_SIGS) + len(_STITCH_SIGS) + len(_HEAD_SIGS):
+    _twice = sorted(n for n in _ALL_SIGS if (n in _SIGS) + (n in _STITCH_SIGS) + (n in _HEAD_SIGS) > 1)
+    raise HipError(f"declared in two headers: {_twice}")
 _kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_STITCH_KMAX[ \t]+(\d+)[ \t]*$", _read_header(STITCH_HEADER_PATH), flags=re.M)
 if _kmax is None:
     raise HipError(f"{STITCH_HEADER_PATH} does not define IB_STITCH_KMAX")
@@ -110,6 +114,11 @@ def declared_symbols() -> List[str]:
 def stitch_symbols() -> List[str]:
     """Every function include/ib_hip_stitch.h declares"""
     return sorted(_STITCH_SIGS)
+
+
+def head_symbols() -> List[str]:
+    """Every function include/ib_hip_head.h declares"""
+    return sorted(_HEAD_SIGS)
 
 
 def _sig(name: str):
@@ -1454,10 +1463,15 @@ def ffn_chain_mask_bytes(M: int, d: int, ffn: int, T: int = 0) -> int:
     return int(lib().ib_ffn_chain_mask_bytes(int(M), int(d), int(ffn)))
 
 
-def ffn_chain_pack(layers):
+FFN_PACK_MAX_TRANSPOSES, FFN_PACK_MAX_CASTS = 16, 2       # csrc/ffn_chain.hip: FF_MAXTR, FF_MAXCAST
+
+
+def ffn_chain_pack(layers, transposes=None, casts=None):
     """layers: [(w1 [ffn, d] bf16, w2 [d, ffn] bf16, packed bf16 [ffn_chain_packed_elems])], optionally with a 4th element,
     the attention out-projection weight [d, d] (the attention epilogue's images), and a 5th, the layer's in-projection
-    weight [3 d, d] (the QKV tail / head of the NEIGHBOURING layer's launches) -- ONE launch for all of them"""
+    weight [3 d, d] (the QKV tail / head of the NEIGHBOURING layer's launches) -- ONE launch for all of them.
+    transposes: [(src [R, C], dst [C, R])] bf16 as for transpose_multi, casts: [(src, dst)] as for cast2d -- done by further
+    blocks of the SAME launch (bit-identical to the separate launches)"""
     n = len(layers)
     ffn, d = layers[0][0].shape
     for it in layers:
@@ -1481,8 +1495,35 @@ def ffn_chain_pack(layers):
     w1s, w2s, pks = [l[0] for l in layers], [l[1] for l in layers], [l[2] for l in layers]
     wos = [(l[3] if len(l) > 3 else None) for l in layers]
     wqs = [(l[4] if len(l) > 4 else None) for l in layers]
-    _check(lib().ib_ffn_chain_pack(arr(w1s), lds(w1s), arr(w2s), lds(w2s), arr(wos), lds(wos), arr(wqs), lds(wqs), arr(pks), n,
-                                   d, ffn, stream_ptr()), "ib_ffn_chain_pack")
+    if transposes is None and casts is None:
+        _check(lib().ib_ffn_chain_pack(arr(w1s), lds(w1s), arr(w2s), lds(w2s), arr(wos), lds(wos), arr(wqs), lds(wqs), arr(pks), n,
+                                       d, ffn, stream_ptr()), "ib_ffn_chain_pack")
+        return
+    # the same launch also refreshes the transposed weight copies and up to two pitched copies (ib_ffn_chain_pack_ex)
+    transposes, casts = list(transposes or ()), list(casts or ())
+    if len(transposes) > FFN_PACK_MAX_TRANSPOSES or len(casts) > FFN_PACK_MAX_CASTS:
+        raise HipError(f"ffn_chain_pack: at most {FFN_PACK_MAX_TRANSPOSES} transposes and {FFN_PACK_MAX_CASTS} copies ride in the launch")
+    tg = []
+    for src, dst in transposes:
+        R, C, ls = _mat(src, "src", torch.bfloat16)
+        Cd, Rd, ld = _mat(dst, "dst", torch.bfloat16)
+        if (Cd, Rd) != (C, R):
+            raise HipError(f"ffn_chain_pack: transpose dst must be {C} x {R}, got {tuple(dst.shape)}")
+        tg.append((src.data_ptr(), ls, dst.data_ptr(), ld, R, C))
+    cg = []
+    for src, dst in casts:
+        r, c, ls = _mat(src, "src", src.dtype)
+        r2, c2, ld = _mat(dst, "dst", dst.dtype)
+        if (r, c) != (r2, c2):
+            raise HipError("ffn_chain_pack: copy shape mismatch")
+        cg.append((src.data_ptr(), ls, dtype_code(src.dtype), dst.data_ptr(), ld, dtype_code(dst.dtype), r, c))
+    col = lambda rows, k, ct: ctypes.cast((ct * max(len(rows), 1))(*[r_[k] for r_ in rows]), ctypes.c_void_p)
+    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+    _check(lib().ib_ffn_chain_pack_ex(arr(w1s), lds(w1s), arr(w2s), lds(w2s), arr(wos), lds(wos), arr(wqs), lds(wqs), arr(pks), n,
+                                      d, ffn, len(tg), col(tg, 0, vp), col(tg, 1, i64), col(tg, 2, vp), col(tg, 3, i64),
+                                      col(tg, 4, i64), col(tg, 5, i64), len(cg), col(cg, 0, vp), col(cg, 1, i64),
+                                      col(cg, 2, i32), col(cg, 3, vp), col(cg, 4, i64), col(cg, 5, i32), col(cg, 6, i64),
+                                      col(cg, 7, i64), stream_ptr()), "ib_ffn_chain_pack_ex")
 
 
 def _ffn_rows(t, name, M, N, dtype=torch.bfloat16):
@@ -1941,6 +1982,63 @@ def time_mlp_fwd(table, t, w1, b1, w2, b2, s, zu, u, e, pack=None, slots=None):
     _check(lib().ib_time_mlp_fwd(_ptr(table), rows, _ptr(t), _ptr(w1), ldw1, _ptr(b1), _ptr(w2), ldw2, _ptr(b2),
                                  _ptr(s), _ptr(zu), _ptr(u), _ptr(e), lde, B, temb, hid, out, stream_ptr()),
            "ib_time_mlp_fwd")
+    return e
+
+
+def tr_head_prep_supported(temb: int, hidden: int, out: int, B: int) -> bool:
+    return bool(lib().ib_tr_head_prep_supported(int(temb), int(hidden), int(out), int(B)))
+
+
+def tr_head_prep(table, t, w1, b1, w2, b2, s, zu, u, e, q_sample=None, posproj=None, cast=None):
+    """The transformer step's head as ONE launch: time_mlp_fwd(table .. e) and, each optional, three independent jobs --
+    q_sample = (x0, eps, sqrt_ab, sqrt_1mab, x_t) as for hip.q_sample (bf16, the same t), posproj = (A, B, C) as for
+    tiny_matmul (bf16, K < 64), cast = (src, dst) as for cast2d (bf16).  Bit-identical to the separate launches."""
+    bt = torch.bfloat16
+    rows, temb, _ = _mat(table, "table", torch.float32)
+    hid, k1, ldw1 = _mat(w1, "w1", bt)
+    out, k2, ldw2 = _mat(w2, "w2", bt)
+    _req(t, "t", torch.int64, 1)
+    B = t.numel()
+    if k1 != temb or k2 != hid or not table.is_contiguous():
+        raise HipError("tr_head_prep: weight / table shapes do not chain")
+    for name, a, shape in (("s", s, (B, temb)), ("zu", zu, (B, hid)), ("u", u, (B, hid))):
+        _req(a, name, bt)
+        if tuple(a.shape) != shape or not a.is_contiguous():
+            raise HipError(f"tr_head_prep: {name} must be contiguous {shape}")
+    er, ec, lde = _mat(e, "e", bt)
+    if (er, ec) != (B, out):
+        raise HipError("tr_head_prep: e must be [B, out]")
+    _req(b1, "b1", torch.float32, 1); _req(b2, "b2", torch.float32, 1)
+    if b1.numel() != hid or b2.numel() != out:
+        raise HipError("tr_head_prep: bias sizes")
+    qa = (None, None, None, None, None, 0, 0, 0, 0)
+    if q_sample is not None:
+        x0, eps, sqrt_ab, sqrt_1mab, x_t = q_sample
+        Bq, T, D, ld, dt = _q_sample_args(x0, eps, t, sqrt_ab, sqrt_1mab, x_t)
+        if dt != bt or sqrt_1mab.numel() != sqrt_ab.numel():
+            raise HipError("tr_head_prep: q_sample rides in bf16 only, with two tables of one length")
+        qa = (_ptr(x0), _ptr(eps), _ptr(sqrt_ab), _ptr(sqrt_1mab), _ptr(x_t), ld, T, D, sqrt_ab.numel())
+    pa = (None, 0, 0, None, 0, 0, None, 0, 0, 0, 0)
+    if posproj is not None:
+        A, Bm, C = posproj
+        for m_, n_ in ((A, "A"), (Bm, "B"), (C, "C")):
+            _req(m_, n_, bt, 2)
+        M, K = A.shape
+        K2, N = Bm.shape
+        if K2 != K or tuple(C.shape) != (M, N) or C.stride(1) != 1 or K >= 64:
+            raise HipError(f"tr_head_prep: projection shapes {tuple(A.shape)} x {tuple(Bm.shape)} -> {tuple(C.shape)} (K < 64)")
+        pa = (_ptr(A), A.stride(0), A.stride(1), _ptr(Bm), Bm.stride(0), Bm.stride(1), _ptr(C), C.stride(0), M, N, K)
+    ca = (None, 0, None, 0, 0, 0)
+    if cast is not None:
+        src, dst = cast
+        r, c, ls = _mat(src, "src", bt)
+        r2, c2, ld2 = _mat(dst, "dst", bt)
+        if (r, c) != (r2, c2):
+            raise HipError("tr_head_prep: copy shape mismatch")
+        ca = (_ptr(src), ls, _ptr(dst), ld2, r, c)
+    _check(lib().ib_tr_head_prep(_ptr(table), rows, _ptr(t), _ptr(w1), ldw1, _ptr(b1), _ptr(w2), ldw2, _ptr(b2),
+                                 _ptr(s), _ptr(zu), _ptr(u), _ptr(e), lde, B, temb, hid, out, *qa, *pa, *ca, stream_ptr()),
+           "ib_tr_head_prep")
     return e
 
 

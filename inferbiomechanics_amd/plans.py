@@ -1024,9 +1024,10 @@ class TimeMLPPlan:
         return self.dtype == torch.bfloat16 and not TU.no_time_fuse \
             and hip.time_mlp_fwd_supported(table.shape[1], w1.shape[0], w2.shape[0])
 
-    def forward(self, t: torch.Tensor, table: torch.Tensor, P: ParamSource, pack=None, slots=None) -> torch.Tensor:
+    def forward(self, t: torch.Tensor, table: torch.Tensor, P: ParamSource, pack=None, slots=None, head=None) -> torch.Tensor:
         """pack: (weights, packed, D, H) of the chain kernel -- packed by the same launch when the fused kernel runs
-        (the caller checks fused_ok() first)"""
+        (the caller checks fused_ok() first).  head: {q_sample, posproj, cast} jobs of the transformer step's head, run by
+        further blocks of the same launch (hip.tr_head_prep; the caller checks fused_ok() and tr_head_prep_supported)"""
         B = t.shape[0]
         g, dt, tg = self.buf.get, self.dtype, self.tag
         w1, w2 = P.w("time_mlp.0.weight"), P.w("time_mlp.2.weight")
@@ -1034,6 +1035,10 @@ class TimeMLPPlan:
         u = g(tg + ".u", (B, w1.shape[0]), dt)
         zu = g(tg + ".zu", (B, w1.shape[0]), dt)
         e = g(tg + ".e", (B, w2.shape[0]), dt)
+        if head is not None:
+            hip.tr_head_prep(table, t, w1, P.v("time_mlp.0.bias"), w2, P.v("time_mlp.2.bias"), s, zu, u, e, **head)
+            self.ctx = (s, u, zu)
+            return e
         if self.fused_ok(table, P):
             # one launch instead of gather + two M = B GEMMs (three latency-bound launches on the critical path)
             hip.time_mlp_fwd(table, t, w1, P.v("time_mlp.0.bias"), w2, P.v("time_mlp.2.bias"), s, zu, u, e, pack=pack,
@@ -1541,6 +1546,14 @@ class DenoiserTransformerPlan:
     def branches(self) -> List[Branch]:
         return [lp.branch for lp in self.layers] + [self.br_time, self.br_thid, self.br_pos, self.br_wt, self.br_side]
 
+    def head_merged(self, B: int, table: torch.Tensor, P: ParamSource) -> bool:
+        """training step: the head's independent small jobs -- time-MLP forward, frame-embedding projection, padded
+        in-projection copy -- are ONE launch on the main stream (hip.tr_head_prep) and the weight refreshes ONE launch on the
+        tr_wt branch (hip.ffn_chain_pack with transposes / casts), instead of eight launches on three streams"""
+        w1, w2 = P.w("time_mlp.0.weight"), P.w("time_mlp.2.weight")
+        return (not self.inference and not TU.no_head_merge and self.dtype == torch.bfloat16 and self.Pd < 64
+                and self.time.fused_ok(table, P) and hip.tr_head_prep_supported(table.shape[1], w1.shape[0], w2.shape[0], B))
+
     def forward(self, x3: torch.Tensor, t: torch.Tensor, table: torch.Tensor, P: ParamSource,
                 out: Optional[torch.Tensor] = None, BT: Optional[Tuple[int, int]] = None) -> torch.Tensor:
         """x3 / out: contiguous [B,T,D], or (with BT=(B,T)) row-padded 2-D [B*T, D] views"""
@@ -1556,6 +1569,7 @@ class DenoiserTransformerPlan:
         posproj = g("dt.posproj", (T, self.d), dt)
         pairs = [pr for lp in self.layers for pr in lp.wt_pairs(P, M)]
         ffn_items = [it for it in (lp.ffn_pack_item(P, M) for lp in self.layers) if it is not None]
+        merged = False
         if self.inference and self._e_all is not None:
             e = g("dt.e_rows", (B, self.d), dt)
             hip.gather_rows(self._e_all, t, e)                               # rows of the per-timestep table
@@ -1564,28 +1578,56 @@ class DenoiserTransformerPlan:
         else:
             # training: the time-MLP and the weight transposes (read by the backward only) beside the projection below
             tp = self._tp = self._train_pad(M, D, x2, out)
-            box = []
+            merged = self.head_merged(B, table, P)
+            # whole-layer tier (attention inside every layer's launches): what is left to transpose is the two ends of the
+            # stack, layer 0's in-projection and the output projection.  With separate attention launches the transposes are
+            # every layer's in-projection, a launch's worth of work of their own: that tier keeps ib_transpose_multi.
+            whole = all(lp.attn_T(M, T) for lp in self.layers)
 
-            def t_branch():
-                box.append(self.time.forward(t, table, P))
-                if tp:
-                    hip.cast2d(w_in[:, :D], tp["w_in"][:, :D])
-            self.br_time.run(t_branch)
-            e = box[0]
-            if pairs or tp or ffn_items:
+            def fork_wt():
+                if not (pairs or tp or ffn_items):
+                    return
+
                 def wt_branch():
-                    if ffn_items:        # first: layer 0's feed-forward sublayer is the first reader
-                        hip.ffn_chain_pack(ffn_items)
-                    pr = list(pairs)
+                    pr, casts = list(pairs), []
                     if tp:
                         w_out = P.w("out_proj.weight")
                         pr.append((w_out, tp["w_outT"][:, :D]))
-                        hip.cast2d(w_out, tp["w_out"][:D])
-                        hip.cast2d(P.v("out_proj.bias").view(1, D), tp["b_out"].view(1, -1)[:, :D])
+                        casts = [(w_out, tp["w_out"][:D]), (P.v("out_proj.bias").view(1, D), tp["b_out"].view(1, -1)[:, :D])]
+                    if merged and ffn_items and whole and len(pr) <= hip.FFN_PACK_MAX_TRANSPOSES:
+                        # one launch: the packing blocks first (layer 0's images are the first to be read), then the
+                        # transposes and the padded out-projection copies (read by the backward / the end of the forward)
+                        hip.ffn_chain_pack(ffn_items, transposes=pr, casts=casts)
+                        return
+                    if ffn_items:        # first: layer 0's feed-forward sublayer is the first reader
+                        hip.ffn_chain_pack(ffn_items)
+                    for src, dst in casts:
+                        hip.cast2d(src, dst)
                     hip.transpose_multi(pr)
                 self.br_wt.run(wt_branch)
-        if not (self.inference and self._posproj_T == T):    # frozen weights (sampling): projected once per sample()
-            hip.tiny_matmul(pos, w_in[:, D:].t(), posproj)
+            if merged:
+                # the weight refreshes are forked FIRST, beside the head launch: forked behind it they ran beside the input
+                # projection, which fills the chip (29.6 -> 44.7 us in the stamped timeline)
+                fork_wt()
+                # ONE launch on the main stream, as long as its longest job (the frame-embedding projection, which used to
+                # run in series behind q_sample beside the forked time-MLP): no tr_time fork, no join ahead of the input
+                # projection.  q_sample / q_sample_cond stay the trainer's own launch ahead of this one: the conditional and
+                # the plain step keep one launch sequence.
+                e = self.time.forward(t, table, P, head={
+                    "posproj": (pos, w_in[:, D:].t(), posproj),
+                    "cast": (w_in[:, :D], tp["w_in"][:, :D]) if tp else None})
+            else:
+                box = []
+
+                def t_branch():
+                    box.append(self.time.forward(t, table, P))
+                    if tp:
+                        hip.cast2d(w_in[:, :D], tp["w_in"][:, :D])
+                self.br_time.run(t_branch)
+                e = box[0]
+                fork_wt()
+        if not (self.inference and self._posproj_T == T) and not merged:
+            hip.tiny_matmul(pos, w_in[:, D:].t(), posproj)       # frozen weights (sampling): projected once per sample()
         self.br_time.join()
         h0 = g("dt.h0", (B, T, self.d), dt)
         # sampler with pitched buffers (prepare_inference): both projections over the padded width
