@@ -15,15 +15,15 @@ Reference arithmetic implemented here (file:line relative to the reference root)
 """
 from __future__ import annotations
 
-import os
 import zlib
+from collections import namedtuple
+from dataclasses import dataclass, replace
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import hip
 from ._tuning import tuning as TU
-
 
 
 def mask_seed(site: int) -> int:
@@ -93,7 +93,6 @@ class Branch:
     (runs inline) off-GPU and when `on` is False."""
 
     def __init__(self, device, enabled: bool = True, name: str = ""):
-        import os
         self.name = name
         off = [n for n in TU.no_branch.split(",") if n]
         enabled = enabled and name not in off and "all" not in off
@@ -509,13 +508,117 @@ class GroundlinkPlan:
         return None
 
 
+@dataclass(frozen=True)
+class LayerRoute:
+    """Which launches one layer's step is made of: decided ONCE per step (TransformerLayerPlan.route; a parent plan links the
+    neighbours: DenoiserTransformerPlan.routes) and carried to the backward in the layer's context.  A kernel may still
+    refuse a launch its route offers; the tier functions then fall back."""
+    fused: bool = False         # everything behind the attention core as ONE launch per direction (ffn_fused)
+    att_T: int = 0              # ... with the attention core inside, over one-window panels of att_T frames (attn_T)
+    qkv_next: bool = False      # my fused forward also writes the in-projection of the layer above
+    attn_next: bool = False     # ... and its attention output
+    dgrad_below: bool = False   # my in-projection dgrad (+ residual addend) rides in the fused backward of the layer below
+    wt_names: Tuple[str, ...] = ()   # weights whose transposed copies are refreshed this step: the ones _dgrad may read
+    # sampler (frozen weights): the tiers the shape admits
+    qkv_panel: bool = False     # in-projection over row panels of the packed image
+    infer_chain: bool = False   # everything behind the attention core in ONE launch over 64-row panels
+    lin_ln: bool = False        # Linear + residual + LayerNorm fused (K-split GEMM + reduction)
+    ln_panel: bool = False      # ... the out-projection's as one launch over row panels
+    ffn_infer: bool = False     # the feed-forward sublayer over row panels
+
+
+# what a layer's forward leaves for its backward: x, x1 = the sublayers' inputs, f1 = the hidden activation, a / f2 = the
+# inputs of LayerNorm1 / 2 with their row statistics (m1, r1) / (m2, r2), drop = (p, seed, step, step_dev) or None
+LayerCtx = namedtuple("LayerCtx", "route x qkv attn lse a x1 m1 r1 f1 f2 m2 r2 B T drop")
+# what a layer's backward hands to a parent plan: dx, or None with head = (packed image, dqkv [M, 3 d], ds1 [M, d]) for the
+# layer below; data parallel: lagged = (closure issuing the grouped launch + reduction | None: issued, names to report ready)
+LayerBack = namedtuple("LayerBack", "dx head lagged")
+
+
+def _optimizer_sources(defer: list, later: list):
+    """(slab sets, -, -, partial-sum segments) as ib_optim_step_sources takes them"""
+    return (defer, None, 0, [(0, part.shape[1], dst, None, 1.0, part, rows) for part, rows, dst in later])
+
+
+class _Grads:
+    """Gradient bookkeeping of one backward: weight gradients launched directly, as deferred split-M slabs (`defer`) or
+    collected for ONE grouped launch; bias / LayerNorm gradients finished here or left as partial sums (`later`) for the
+    step's reduction; every gradient reported ready where its launches are enqueued.  `side` runs a closure on the stream the
+    weight gradients go to (default: inline)."""
+
+    def __init__(self, buf: Buffers, P: ParamSource, prefix: str, tag: str, accumulate: bool, defer: Optional[list],
+                 later: Optional[list], grouped: bool = False, side=None):
+        self.buf, self.tag, self.accumulate, self.defer, self.later = buf, tag, accumulate, defer, later
+        self.v, self.g, self.ready = (lambda n: P.v(prefix + n)), (lambda n: P.g(prefix + n)), (lambda n: P.ready(prefix + n))
+        self.group: Optional[list] = [] if grouped else None
+        self.side = side if side is not None else (lambda fn: fn())
+
+    def wgrad(self, dz, x, key: str, name: str, bias: str):
+        """d name = dz^T x and d bias = column sums of dz: with the grouped launch the bias gradient's partial sums come out
+        of the weight-gradient GEMM itself; otherwise a column-sum launch"""
+        def issue():
+            in_gemm = self.group is not None and self.later is not None and dz.shape[0] > 512
+            if self.group is not None:
+                self.group.append((dz, x, self.g(name), f"{self.tag}.ws{key}", self.g(bias) if in_gemm else None, (key, bias)))
+            else:
+                _wgrad(self.buf, dz, x, self.g(name), self.accumulate, ws_tag=f"{self.tag}.ws{key}", defer=self.defer)
+            self.ready(name)
+            if not in_gemm:
+                self.dbias(key, dz, bias)
+            self.ready(bias)
+        self.side(issue)
+
+    def dbias(self, key: str, dz, name: str, plain: bool = True):
+        """plain False: always as per-128-row partial sums for the step's reduction"""
+        if plain and (self.later is None or dz.shape[0] <= 512):
+            return _colsum(self.buf, f"{self.tag}.b{key}", dz, self.g(name), self.accumulate)
+        part = self.buf.get(f"{self.tag}.b{key}.colsum", ((dz.shape[0] + 127) // 128, dz.shape[1]), torch.float32)
+        hip.segment_colsum(dz, part, seg=128, mode=0)
+        self.later.append((part, part.shape[0], self.g(name)))
+
+    def parts(self, part, rows: int, *names: str):
+        """`part`: len(names) stacked blocks of `rows` partial-sum rows, one block per gradient"""
+        for i, name in enumerate(names):
+            self.later.append((part[i * rows:(i + 1) * rows], rows, self.g(name)))
+            self.ready(name)
+
+    def ln_bwd(self, which: str, dy, xin, mean, rstd, dxo, res):
+        """LayerNorm backward; parameter gradients finished here, or their per-block partial sums left for the optimizer"""
+        M, d = dy.shape
+        nb = hip.layernorm_bwd_workspace_bytes(M, d)
+        if self.later is None:
+            hip.layernorm_bwd(dy, xin, self.v(which + ".weight"), mean, rstd, dxo, self.g(which + ".weight"),
+                              self.g(which + ".bias"), self.buf.bytes("ln.ws", nb), res=res, accumulate=self.accumulate)
+            return self.ready(which + ".weight"), self.ready(which + ".bias")
+        ws = self.buf.bytes(f"{self.tag}.lnws.{which}", nb)               # one per LayerNorm: read at the end of the step
+        hip.layernorm_bwd(dy, xin, self.v(which + ".weight"), mean, rstd, dxo, None, None, ws, res=res)
+        rows = nb // (2 * d * 4)
+        self.parts(ws[:nb].view(torch.float32).view(2 * rows, d), rows, which + ".weight", which + ".bias")
+
+    def launch_group(self, problems: list, reduce: bool = False):
+        """the grouped weight-gradient launch; problems it could not take sum their bias gradient the plain way (reported
+        ready already); reduce: this layer's slabs and partial sums finished right behind it (same stream: it reads them)"""
+        for pr in _wgrad_group(self.buf, problems, self.defer, self.later):
+            self.dbias(pr[5][0], pr[0], pr[5][1], plain=False)
+        if reduce:
+            hip.step_reduce_parts(self.defer, list(self.later))
+
+
 # ------------------------------------------------------------------------------------------------
 class TransformerLayerPlan:
     """Post-norm encoder layer (TransformerBaseline.py:24-38): x=LN1(x+Drop(MHA(x))); x=LN2(x+Drop(W2 relu(W1 x))).
 
     dropout_p (train mode only): the layer's three dropouts -- on the attention probabilities inside the attention kernels
     (nn.MultiheadAttention(dropout=p), :12-13), dropout1 on the attention block's output (:30), dropout2 on the feedforward
-    output (:35).  All masks are counter-based hashes of (seed + site, step, element), regenerated in the backward."""
+    output (:35).  All masks are counter-based hashes of (seed + site, step, element), regenerated in the backward.
+
+    `forward` / `backward`: the standalone layer (its own LayerRoute, no neighbours); a parent plan links the routes of its
+    stack and calls `run` / `run_backward`."""
+
+    WT_NAMES = ("feedforward.2.weight", "feedforward.0.weight", "multihead_attention.out_proj.weight",
+                "multihead_attention.in_proj_weight")
+    OUT_PROJ = ("multihead_attention.out_proj.weight", "multihead_attention.out_proj.bias", "norm1")
+    FFN2 = ("feedforward.2.weight", "feedforward.2.bias", "norm2")
 
     def __init__(self, prefix: str, d_model: int, num_heads: int, ffn: int, dtype, device, buf: Optional[Buffers] = None,
                  tag="tl", dropout_p: float = 0.0, seed: Optional[int] = None):
@@ -525,77 +628,40 @@ class TransformerLayerPlan:
         # stacked layers draw different masks ('tl12' and 'tl21' too: a character sum does not see digit order)
         self.seed = mask_seed(0x3A7 + 16 * (zlib.crc32(tag.encode()) & 0xFFFFFF)) if seed is None else int(seed)
         self.buf = buf if buf is not None else Buffers(device)
-        self.ctx = None
+        self.ctx: Optional[LayerCtx] = None
         # the four weight-gradient GEMMs (+ bias sums) hang off the critical dgrad / LayerNorm / attention chain.  One GPU,
-        # large batches: they are ONE grouped launch per layer (csrc/gemm_tn.hip), issued on a side stream of the layer so the
-        # next layer's chain starts beside it (B = 256, T = 50, same box: 2.45 ms inline, 2.41 ms forked; joined once at the
-        # end of the whole backward).  Everything else runs them inline: as separate launches on a side stream they were
-        # slower (3.059 vs 3.123 ms with the round-1 kernels), and a data-parallel layer joins right away for its bucket.
-        # IB_LAYER_BRANCH=1 forces the side stream for every shape, IB_NO_LAYER_BRANCH=1 forces inline.
+        # large batches: ONE grouped launch per layer (csrc/gemm_tn.hip) on a side stream of the layer, so the next layer's
+        # chain starts beside it (joined once at the end of the whole backward).  Everything else runs them inline (DESIGN.md
+        # 5.2 has the measurements).  IB_LAYER_BRANCH=1 forces the side stream for every shape, IB_NO_LAYER_BRANCH=1 inline.
         self.branch = Branch(device, enabled=not TU.no_layer_branch, name="layer")
         self._always_fork = bool(TU.layer_branch)
         # transposed bf16 copies of the four weight matrices: the dgrad GEMMs of large batches read them k-contiguously
-        # (ib_linear_dgrad_wt -> the 256 x 128 LDS-DMA kernel of csrc/gemm_nt.hip); refreshed once per forward
+        # (ib_linear_dgrad_wt -> the 256 x 128 LDS-DMA kernel of csrc/gemm_nt.hip); the route names the ones a step refreshes
         self._wt: Dict[str, torch.Tensor] = {}
-        self._wt_fresh = False
-        # set by a parent plan that stacks layers: the layer ABOVE this one (its in-projection rides behind this layer's
-        # LayerNorm2 in the fused forward launch) and the layer BELOW (this layer's in-projection dgrad + residual addend
-        # ride in front of that layer's fused backward launch) -- csrc/ffn_chain.hip's QKV tail / head
-        self.qkv_tail_for: Optional["TransformerLayerPlan"] = None
-        self.qkv_dgrad_below: Optional["TransformerLayerPlan"] = None
-        self.own_wt = True           # a parent plan refreshes the copies of all its layers in ONE launch instead
-        self.join_on_exit = True     # a parent plan sets this False and joins all layers once at the end
+        self.in_stack(standalone=True)
+        # modes, switched by a parent plan
         self.inference = False       # forward only (DDIM sampler): Linear + residual + LayerNorm fused, nothing saved
-        # set by a parent plan whose trainer lets the optimizer sum partial gradients (one GPU): weight-gradient slabs go
-        # to `defer` [(workspace, nslab, dw)], bias / LayerNorm partial sums to `later` [(partial rows, rows, gradient)]
-        self.defer: Optional[list] = None
-        self.later: Optional[list] = None
+        self.infer_packed = False    # prepare_inference: packed_image() holds the frozen weights
         self.flush_on_exit = False   # data parallel with overlapped all-reduces: join the side stream and let the trainer
                                      # launch the completed buckets at the end of every layer's backward
-        # data parallel, set by a parent plan for every layer but the one whose backward runs last: the layer's grouped
-        # weight-gradient launch + its reduction are NOT issued by backward(); they are handed back (take_lagged) and the
-        # parent forks them beside the NEXT layer's backward, joins them at that layer's end and only then reports the
-        # gradients ready and flushes.  A captured graph segment must end with every side stream joined, so without the lag
-        # each layer's 100-us launch sat on the critical path once per bucket.
+        # data parallel: the layer's grouped weight-gradient launch + its reduction are NOT issued by the backward; they are
+        # handed back (LayerBack.lagged) and the parent forks them beside the NEXT layer's backward, joins them at that
+        # layer's end and only then reports the gradients ready and flushes (a captured graph segment must end with every
+        # side stream joined: without the lag each layer's 100-us launch sat on the critical path once per bucket)
         self.lag_group = False
-        self.tail_done = self.attn_tail_done = False
-        self.split_tail = False       # set by the parent on the layer whose backward runs LAST (see backward())
-        self.infer_packed = False     # set by the parent's prepare_inference: packed_image() holds the frozen weights
         self.parent_flushes = False  # set with lag_group on ALL layers of such a parent: gradients are reported to the parent
-                                     # (take_lagged), which keeps the ready order and does the flushes
-        self._lagged = None
+                                     # (LayerBack.lagged), which keeps the ready order and does the flushes
+
+    def in_stack(self, above: Optional["TransformerLayerPlan"] = None, runs_last: bool = False,
+                 image_of: Optional["TransformerLayerPlan"] = None, standalone: bool = False):
+        """what is fixed when a parent plan builds its stack"""
+        self.standalone = standalone     # refreshes its own weight copies / packed image, joins its own side stream
+        self.above = above               # its in-projection (and attention) may ride in this layer's fused forward launch
+        self.runs_last = runs_last       # the layer whose backward runs LAST (see _bwd_fused: the split tail)
+        self._image_of = image_of        # a side copy reads the main layer's packed image
 
     def branches(self) -> List["Branch"]:
         return [self.branch]
-
-    def take_lagged(self):
-        """(closure issuing the layer's grouped weight-gradient launch + reduction, names to report ready) or None"""
-        lg, self._lagged = self._lagged, None
-        return lg
-
-    WT_NAMES = ("feedforward.2.weight", "feedforward.0.weight", "multihead_attention.out_proj.weight",
-                "multihead_attention.in_proj_weight")
-
-    def wt_pairs(self, P: ParamSource, M: int):
-        """[(weight, its transposed copy)] to refresh before a training forward, or [] when the large-M dgrad path does not
-        apply (fp32 parity mode, inference, small token counts)"""
-        self._wt_fresh = False
-        if self.dtype != torch.bfloat16 or self.inference or M < 4096 or TU.no_nt:
-            return []
-        pairs = []
-        skip = ("feedforward.2.weight", "feedforward.0.weight", "multihead_attention.out_proj.weight") if self.ffn_fused(M) else ()
-        if skip and self.qkv_dgrad_below is not None and self.qkv_dgrad_below.ffn_fused(M) \
-                and not TU.no_qkv_fuse:
-            skip = skip + ("multihead_attention.in_proj_weight",)
-        for n in self.WT_NAMES:
-            if n in skip:          # the fused feed-forward sublayer streams its own packed images (ffn_pack_item)
-                continue
-            w = P.w(self.p + n)
-            wt = self.buf.get(self.tag + ".wt." + n, (w.shape[1], w.shape[0]), self.dtype)
-            self._wt[n] = wt
-            pairs.append((w, wt))
-        self._wt_fresh = True
-        return pairs
 
     def ffn_fused(self, M: int) -> bool:
         """everything of the layer behind the attention core -- out-projection + residual + LayerNorm1, then the feed-forward
@@ -622,33 +688,39 @@ class TransformerLayerPlan:
                 return T
         return 0
 
-    def tail_active(self, M: int, training: bool = False) -> bool:
-        """this layer's fused forward launch also computes the in-projection of the layer above (both packed images are
-        addressed with one chunk count: the two layers must have the same hidden width)"""
-        nxt = self.qkv_tail_for
-        return (nxt is not None and self.ffn_fused(M) and nxt.ffn_fused(M) and not TU.no_qkv_fuse and nxt.ffn == self.ffn
-                and not (training and (self.drop_p > 0.0 or nxt.drop_p > 0.0)))
+    def route(self, M: int, T: int) -> LayerRoute:
+        """this layer's route with no neighbours (a parent plan links them: DenoiserTransformerPlan.routes)"""
+        d, bf16 = self.d, self.dtype == torch.bfloat16
+        fused = self.ffn_fused(M)
+        wt = bf16 and not self.inference and M >= 4096 and not TU.no_nt
+        # the fused launches stream their own packed images (pack_item): only the in-projection's dgrad is a GEMM
+        names = (self.WT_NAMES[3:] if fused else self.WT_NAMES) if wt else ()
+        frozen = self.inference and self.infer_packed and d == 512 and bf16
+        lin_ln = self.inference and bf16 and not TU.no_linear_ln
+        return LayerRoute(
+            fused=fused, att_T=self.attn_T(M, T), wt_names=names, lin_ln=lin_ln,
+            qkv_panel=frozen and not TU.no_qkv_panel and M <= TU.qkv_panel_max_m,
+            infer_chain=bool(frozen and M >= TU.infer_chain_min_m and not TU.no_infer_chain
+                             and hip.ffn_chain_supported(d, self.ffn)),
+            ln_panel=bool(lin_ln and frozen and hip.linear_ln_panel_ok(M, d, d) and M <= TU.linln_panel_max_m),
+            ffn_infer=bool(lin_ln and frozen and not TU.no_ffn_infer and hip.ffn_infer_panels(M, d, self.ffn)
+                           and M <= TU.ffn_infer_max_m))
 
-    def attn_tail_active(self, M: int, T: int, training: bool = False) -> bool:
-        """... and that layer's attention core behind it"""
-        nxt = self.qkv_tail_for
-        return bool(self.tail_active(M, training) and self.attn_T(M, T) and nxt.attn_T(M, T) and nxt.h == self.h)
+    def wt_pairs(self, P: ParamSource, route: LayerRoute):
+        """[(weight, its transposed copy)] to refresh before a training forward ([]: the large-M dgrad path does not apply)"""
+        pairs = []
+        for n in route.wt_names:
+            w = P.w(self.p + n)
+            wt = self._wt[n] = self.buf.get(self.tag + ".wt." + n, (w.shape[1], w.shape[0]), self.dtype)
+            pairs.append((w, wt))
+        return pairs
 
-    def head_active(self, M: int) -> bool:
-        """this layer's in-projection dgrad (+ residual addend) is computed by the fused backward launch of the layer below"""
-        low = self.qkv_dgrad_below
-        return (low is not None and self.ffn_fused(M) and low.ffn_fused(M) and not TU.no_qkv_fuse and low.ffn == self.ffn
-                and getattr(self, "_ffn_fused", False) and getattr(low, "_ffn_fused", False)
-                and not getattr(self, "_att_T", 0))
-
-    def ffn_pack_item(self, P: ParamSource, M: int):
-        """(feedforward.0.weight, feedforward.2.weight, this layer's packed image) for ib_ffn_chain_pack -- refreshed once
-        per training step, all layers of a parent plan in ONE launch -- or None"""
-        if not self.ffn_fused(M):
-            return None
-        pk = self.buf.get(self.tag + ".ffnpk", (hip.ffn_chain_packed_elems(self.d, self.ffn),), self.dtype)
-        return (P.w(self.p + "feedforward.0.weight"), P.w(self.p + "feedforward.2.weight"), pk,
-                P.w(self.p + "multihead_attention.out_proj.weight"), P.w(self.p + "multihead_attention.in_proj_weight"))
+    def pack_item(self, P: ParamSource):
+        """(feedforward.0.weight, feedforward.2.weight, this layer's packed image, out-projection, in-projection) for
+        ib_ffn_chain_pack: refreshed once per training step (fused routes), all layers of a parent plan in ONE launch"""
+        p = self.p
+        return (P.w(p + "feedforward.0.weight"), P.w(p + "feedforward.2.weight"), self.packed_image(),
+                P.w(p + "multihead_attention.out_proj.weight"), P.w(p + "multihead_attention.in_proj_weight"))
 
     def qkv_buffer(self, B: int, T: int) -> torch.Tensor:
         return self.buf.get(self.tag + ".qkv", (B, T, 3 * self.d), self.dtype)
@@ -658,154 +730,161 @@ class TransformerLayerPlan:
                 self.buf.get(self.tag + ".lse", (B, self.h, T), torch.float32))
 
     def packed_image(self) -> torch.Tensor:
+        if self._image_of is not None:
+            return self._image_of.packed_image()
         return self.buf.get(self.tag + ".ffnpk", (hip.ffn_chain_packed_elems(self.d, self.ffn),), self.dtype)
 
-    def _dgrad(self, P: ParamSource, dz, wname: str, dx, act_below="none", aux=None, addend=None):
-        wt = self._wt.get(wname) if self._wt_fresh else None
-        if wt is not None and hip.linear_dgrad_wt(dz, wt, dx, act_below=act_below, aux=aux, addend=addend):
-            return
-        hip.linear_dgrad(dz, P.w(self.p + wname), dx, act_below=act_below, aux=aux, addend=addend)
+    def _image_block(self, first: int, count: int = 1) -> torch.Tensor:
+        """`count` 512 x 512 blocks of the packed image behind the feed-forward chunks: 0 = out-projection, 2..4 = Q, K, V"""
+        base = 4 * (self.ffn // 512) + first
+        return self.packed_image()[base * 512 * 512:(base + count) * 512 * 512]
+
+    def _qkv_tail(self, P: ParamSource, B: int, T: int):
+        """the layer above's operands of a fused forward launch's QKV tail"""
+        nxt = self.above
+        return (nxt.packed_image(), P.v(nxt.p + "multihead_attention.in_proj_bias"),
+                nxt.qkv_buffer(B, T).view(B * T, 3 * self.d))
+
+    def _dgrad(self, P: ParamSource, route: LayerRoute, dz, wname: str, dx, **kw):
+        if not (wname in route.wt_names and hip.linear_dgrad_wt(dz, self._wt[wname], dx, **kw)):
+            hip.linear_dgrad(dz, P.w(self.p + wname), dx, **kw)
 
     def forward(self, x3: torch.Tensor, P: ParamSource, out: Optional[torch.Tensor] = None, training: bool = False,
-                step: int = 0, step_dev: Optional[torch.Tensor] = None, qkv_ready: bool = False,
-                attn_ready: bool = False) -> torch.Tensor:
+                step: int = 0, step_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the standalone layer: its own route, its own weight refreshes"""
+        B, T, _ = x3.shape
+        route = self.route(B * T, T)
+        pairs = self.wt_pairs(P, route)
+        if pairs:
+            hip.transpose_multi(pairs)
+        if route.fused:
+            hip.ffn_chain_pack([self.pack_item(P)])
+        return self.run(route, x3, P, out=out, training=training, step=step, step_dev=step_dev)[0]
+
+    def run(self, route: LayerRoute, x3: torch.Tensor, P: ParamSource, out: Optional[torch.Tensor] = None,
+            training: bool = False, step: int = 0, step_dev: Optional[torch.Tensor] = None, qkv_ready: bool = False,
+            attn_ready: bool = False):
         """qkv_ready: the layer below already wrote this layer's in-projection into `qkv_buffer` (its fused launch's tail);
-        attn_ready: ... and this layer's attention output + row log-sum-exp (`attn_buffers`) behind it"""
+        attn_ready: ... and this layer's attention output + row log-sum-exp (`attn_buffers`) behind it.
+        Returns (x2, this launch wrote the in-projection of the layer above, ... and its attention output)."""
         B, T, d = x3.shape
-        M = B * T
-        g, dt, p, tg = self.buf.get, self.dtype, self.p, self.tag
+        M, p = B * T, self.p
         drop = None
         if training and self.drop_p > 0.0:
             if self.inference:
                 raise hip.HipError("TransformerLayerPlan: inference mode with training=True")
             drop = (self.drop_p, self.seed, step, step_dev)
-        ffn_fused = self.ffn_fused(M) and drop is None
-        if self.own_wt:
-            pairs = self.wt_pairs(P, M)
-            if pairs:
-                hip.transpose_multi(pairs)
-            if ffn_fused:
-                hip.ffn_chain_pack([self.ffn_pack_item(P, M)])
         x = x3.view(M, d)
-        qkv = g(tg + ".qkv", (B, T, 3 * d), dt)
+        qkv = self.qkv_buffer(B, T)
         if not qkv_ready:
-            nc = self.ffn // 512
-            if not (self.inference and self.infer_packed and d == 512 and dt == torch.bfloat16
-                    and not TU.no_qkv_panel and M <= TU.qkv_panel_max_m
-                    and hip.linear_panel_fwd(x, self.packed_image()[(4 * nc + 2) * 512 * 512:(4 * nc + 5) * 512 * 512],
-                                             P.v(p + "multihead_attention.in_proj_bias"), qkv.view(M, 3 * d))):
-                hip.linear_fwd(x, P.w(p + "multihead_attention.in_proj_weight"), P.v(p + "multihead_attention.in_proj_bias"),
-                               qkv.view(M, 3 * d))
+            b_in = P.v(p + "multihead_attention.in_proj_bias")
+            if not (route.qkv_panel and hip.linear_panel_fwd(x, self._image_block(2, 3), b_in, qkv.view(M, 3 * d))):
+                hip.linear_fwd(x, P.w(p + "multihead_attention.in_proj_weight"), b_in, qkv.view(M, 3 * d))
         attn, lse = self.attn_buffers(B, T)
         if not attn_ready:
             hip.attention_fwd(qkv, attn, lse, self.h, drop=drop)
-        x2 = out if out is not None else g(tg + ".x2", (B, T, d), dt)
-        self.tail_done = self.attn_tail_done = False          # read by a parent plan: what this launch did for the layer above
-        if (self.inference and self.infer_packed and d == 512 and dt == torch.bfloat16 and M >= TU.infer_chain_min_m
-                and not TU.no_infer_chain and x2.is_contiguous() and hip.ffn_chain_supported(d, self.ffn)):
-            # frozen weights, more rows than the row-panel kernels take (DDIM at B = 256: 51200 rows): everything behind the
-            # attention core -- and the next layer's in-projection -- in ONE launch over 64-row panels, the training
-            # launch's form that saves nothing (csrc/ffn_chain.hip, INFER).  Round 5: 8 per-op launches per layer before.
-            nxt = self.qkv_tail_for
-            tail = None
-            if nxt is not None and nxt.infer_packed and nxt.ffn == self.ffn and nxt.d == d and not TU.no_qkv_fuse:
-                tail = (nxt.packed_image(), P.v(nxt.p + "multihead_attention.in_proj_bias"), nxt.qkv_buffer(B, T).view(M, 3 * d))
-            if hip.ffn_chain_fwd_infer(x, self.packed_image(), P.v(p + "feedforward.0.bias"), P.v(p + "feedforward.2.bias"),
-                                       P.v(p + "norm2.weight"), P.v(p + "norm2.bias"), x2.view(M, d), attn.view(M, d),
-                                       P.v(p + "multihead_attention.out_proj.bias"), P.v(p + "norm1.weight"),
-                                       P.v(p + "norm1.bias"), qkv_next=tail):
-                self.tail_done = tail is not None
-                self.ctx = None
-                return x2
-        x1 = g(tg + ".x1", (M, d), dt)
+        x2 = out if out is not None else self.buf.get(self.tag + ".x2", (B, T, d), self.dtype)
+        self.ctx = None
+        if route.infer_chain and x2.is_contiguous():
+            tail = self._fwd_infer_chain(route, P, x, attn, x2, B, T)
+            if tail is not None:
+                return x2, tail, False
+        if route.fused and drop is None:
+            return (x2,) + self._fwd_fused(route, P, x, qkv, attn, lse, x2, B, T)
+        (self._fwd_row_panels if route.lin_ln else self._fwd_per_op)(route, P, x, qkv, attn, lse, x2, B, T, drop)
+        return x2, False, False
+
+    def _fwd_infer_chain(self, route, P, x, attn, x2, B, T) -> Optional[bool]:
+        """frozen weights, more rows than the row-panel kernels take (DDIM at B = 256: 51200 rows): everything behind the
+        attention core -- and the next layer's in-projection -- in ONE launch over 64-row panels, the training launch's
+        form that saves nothing (csrc/ffn_chain.hip, INFER).  Returns whether the tail was written; None: the kernel refused."""
+        (M, d), p = x.shape, self.p
+        tail = self._qkv_tail(P, B, T) if route.qkv_next else None
+        ok = hip.ffn_chain_fwd_infer(x, self.packed_image(), P.v(p + "feedforward.0.bias"), P.v(p + "feedforward.2.bias"),
+                                     P.v(p + "norm2.weight"), P.v(p + "norm2.bias"), x2.view(M, d), attn.view(M, d),
+                                     P.v(p + "multihead_attention.out_proj.bias"), P.v(p + "norm1.weight"),
+                                     P.v(p + "norm1.bias"), qkv_next=tail)
+        return (tail is not None) if ok else None
+
+    def _fwd_fused(self, route, P, x, qkv, attn, lse, x2, B, T):
+        """the fused training launch; a / f2 of the context = the LayerNorm INPUTS x + o and x1 + f2 the kernel stores (its
+        backward normalises those; no `res`).  One-window panels in BOTH directions of this layer when route.att_T (the
+        ReLU bit words are laid out per panel)."""
+        M, d = x.shape
+        g, dt, p, tg = self.buf.get, self.dtype, self.p, self.tag
+        x1, a, f2 = (g(tg + n, (M, d), dt) for n in (".x1", ".s1", ".s2"))
+        m1, r1, m2, r2 = (g(tg + n, (M,), torch.float32) for n in (".m1", ".r1", ".m2", ".r2"))
         f1 = g(tg + ".f1", (M, self.ffn), dt)
-        fuse = self.inference and dt == torch.bfloat16 and not TU.no_linear_ln
+        mask = g(tg + ".ffnmask", (hip.ffn_chain_mask_bytes(M, d, self.ffn, route.att_T),), torch.uint8)
+        att_next = None
+        if route.attn_next:
+            na, nl = self.above.attn_buffers(B, T)
+            att_next = (na.view(M, d), nl, route.att_T)
+        hip.ffn_chain_fwd(x, self.packed_image(), P.v(p + "feedforward.0.bias"), P.v(p + "feedforward.2.bias"),
+                          P.v(p + "norm2.weight"), P.v(p + "norm2.bias"), f1, f2, x2.view(M, d), m2, r2, mask,
+                          attn_out=(attn.view(M, d), P.v(p + "multihead_attention.out_proj.bias"),
+                                    P.v(p + "norm1.weight"), P.v(p + "norm1.bias"), a, x1, m1, r1),
+                          qkv_next=self._qkv_tail(P, B, T) if route.qkv_next else None,
+                          attn_next=att_next, panel_T=route.att_T)
+        self.ctx = LayerCtx(route, x, qkv, attn, lse, a, x1, m1, r1, f1, f2, m2, r2, B, T, None)
+        return route.qkv_next, route.attn_next
 
-        def lin_ln(inp, wname, bname, nname, res, y, wtag):
-            """Linear -> +res -> LayerNorm as one K-split GEMM + fused reduction (small M); False = not applicable"""
-            w = P.w(p + wname)
-            # swept on the sampler (T = 200): K = 2048 fused wins up to the NT kernel's territory (M = 3200: 43.6 -> 30.5 us);
-            # K = 512 (two short kernels either way) wins only while the GEMM is far from filling the chip (M <= 2048:
-            # B = 2 / 4 / 8 +4 / +6 / +2 % steps/s; M = 3200: -6 % on the ring kernel).  Round 3: from 640 rows the GEMM of
-            # the fused form is the 256 x 128 kernel in split-K form (ib_gemm_nt_splitk): K = 2048 31.2 -> 24.0 us at
-            # M = 3200, B = 4 / 8 / 16 +7.5 / +8 / +7 % steps/s; K = 512 fused now pays up to M < 4096 too (+1-2 %)
-            if w.shape[1] < 512 or (w.shape[1] < 1024 and M > TU.linln_k512_max_m):
-                return False
-            if M >= TU.linln_max_m and not TU.no_nt:
-                return False           # large batches fill the chip without a K split: the 256 x 128 NT kernel + LayerNorm
-                                       # (M = 51200: 120 + 30 us against 235 us fused)
-            ws = self.buf.bytes(tg + wtag, int(hip.lib().ib_linear_ln_fwd_workspace(M, w.shape[0], w.shape[1])))
-            return hip.linear_ln_fwd(inp, w, P.v(p + bname), res, P.v(p + nname + ".weight"), P.v(p + nname + ".bias"), y, ws)
+    def _lin_ln(self, P, inp, wname, bname, nname, res, y, wtag) -> bool:
+        """Linear -> +res -> LayerNorm as one K-split GEMM + fused reduction (small M); False = not applicable"""
+        M, p = inp.shape[0], self.p
+        w = P.w(p + wname)
+        # swept on the sampler (T = 200, DESIGN.md 5.2): K = 2048 fused wins up to the NT kernel's territory; K = 512 (two
+        # short kernels either way) while the GEMM is far from filling the chip, with the split-K NT kernel up to M < 4096
+        if w.shape[1] < 512 or (w.shape[1] < 1024 and M > TU.linln_k512_max_m):
+            return False
+        if M >= TU.linln_max_m and not TU.no_nt:
+            return False           # large batches fill the chip without a K split: the 256 x 128 NT kernel + LayerNorm
+        ws = self.buf.bytes(self.tag + wtag, int(hip.lib().ib_linear_ln_fwd_workspace(M, w.shape[0], w.shape[1])))
+        return hip.linear_ln_fwd(inp, w, P.v(p + bname), res, P.v(p + nname + ".weight"), P.v(p + nname + ".bias"), y, ws)
 
+    def _sublayer(self, P, inp, wname, bname, nname, res, y, tags, drop, site):
+        """Linear, dropout, + res, LayerNorm as separate launches: (the LayerNorm's input, mean, rstd)"""
+        M, d = res.shape
+        g, p, tg = self.buf.get, self.p, self.tag
+        s = g(tg + tags[0], (M, d), self.dtype)
+        hip.linear_fwd(inp, P.w(p + wname), P.v(p + bname), s)
+        if drop:           # in place: only the dropped block output is read again (LayerNorm input)
+            hip.dropout(s, s, self.drop_p, self.seed + site, drop[2], drop[3])
+        m, r = g(tg + tags[1], (M,), torch.float32), g(tg + tags[2], (M,), torch.float32)
+        hip.layernorm_fwd(s, P.v(p + nname + ".weight"), P.v(p + nname + ".bias"), y, m, r, res=res)
+        return s, m, r
+
+    def _fwd_row_panels(self, route, P, x, qkv, attn, lse, x2, B, T, drop=None):
+        """the sampler (frozen bf16 weights): each sublayer over row panels of the packed image, else Linear + residual +
+        LayerNorm fused, else per-op"""
+        M, d = x.shape
+        g, dt, p, tg = self.buf.get, self.dtype, self.p, self.tag
+        x1, f1 = g(tg + ".x1", (M, d), dt), g(tg + ".f1", (M, self.ffn), dt)
         a = m1 = r1 = f2 = m2 = r2 = None
-        self._ffn_fused = ffn_fused
-        # one-window panels in BOTH directions of this layer (the ReLU bit words are laid out per panel)
-        Ta = self._att_T = self.attn_T(M, T) if ffn_fused else 0
-        if ffn_fused:
-            # a / f2 of the context = the LayerNorm INPUTS x + o and x1 + f2 the kernel stores (its backward normalises
-            # those; no `res`)
-            a, f2 = g(tg + ".s1", (M, d), dt), g(tg + ".s2", (M, d), dt)
-            m1, r1 = g(tg + ".m1", (M,), torch.float32), g(tg + ".r1", (M,), torch.float32)
-            m2, r2 = g(tg + ".m2", (M,), torch.float32), g(tg + ".r2", (M,), torch.float32)
-            mask = self.buf.get(tg + ".ffnmask", (hip.ffn_chain_mask_bytes(M, d, self.ffn, Ta),), torch.uint8)
-            nxt = self.qkv_tail_for
-            att_next = None
-            if Ta and self.attn_tail_active(M, T, training):
-                na, nl = nxt.attn_buffers(B, T)
-                att_next = (na.view(M, d), nl, Ta)
-            hip.ffn_chain_fwd(x, self.buf.get(tg + ".ffnpk", (hip.ffn_chain_packed_elems(d, self.ffn),), dt),
-                              P.v(p + "feedforward.0.bias"), P.v(p + "feedforward.2.bias"), P.v(p + "norm2.weight"),
-                              P.v(p + "norm2.bias"), f1, f2, x2.view(M, d), m2, r2, mask,
-                              attn_out=(attn.view(M, d), P.v(p + "multihead_attention.out_proj.bias"),
-                                        P.v(p + "norm1.weight"), P.v(p + "norm1.bias"), a, x1, m1, r1),
-                              qkv_next=None if not self.tail_active(M, training) else
-                              (nxt.packed_image(), P.v(nxt.p + "multihead_attention.in_proj_bias"),
-                               nxt.qkv_buffer(B, T).view(M, 3 * d)),
-                              attn_next=att_next, panel_T=Ta)
-            self.tail_done = self.tail_active(M, training)
-            self.attn_tail_done = att_next is not None
-            self.ctx = (x, qkv, attn, lse, a, x1, m1, r1, f1, f2, m2, r2, B, T, drop)
-            return x2
-        def panel_ln():
-            """out-projection + residual + LayerNorm1 as one launch over row panels (sampler, frozen packed weights)"""
-            if not (fuse and self.infer_packed and d == 512 and hip.linear_ln_panel_ok(M, d, d)
-                    and M <= TU.linln_panel_max_m):
-                return False
-            nc = self.ffn // 512
-            wo_img = self.packed_image()[4 * nc * 512 * 512:(4 * nc + 1) * 512 * 512]
-            return hip.linear_ln_panel_fwd(attn.view(M, d), wo_img, P.v(p + "multihead_attention.out_proj.bias"), x,
-                                           P.v(p + "norm1.weight"), P.v(p + "norm1.bias"), x1)
-        if panel_ln():
-            pass
-        elif not (fuse and lin_ln(attn.view(M, d), "multihead_attention.out_proj.weight",
-                                  "multihead_attention.out_proj.bias", "norm1", x, x1, ".lnws1")):
-            a = g(tg + ".a", (M, d), dt)
-            hip.linear_fwd(attn.view(M, d), P.w(p + "multihead_attention.out_proj.weight"),
-                           P.v(p + "multihead_attention.out_proj.bias"), a)
-            if drop:           # dropout1, in place: only the dropped block output is read again (LayerNorm input)
-                hip.dropout(a, a, self.drop_p, self.seed + 1, step, step_dev)
-            m1, r1 = g(tg + ".m1", (M,), torch.float32), g(tg + ".r1", (M,), torch.float32)
-            hip.layernorm_fwd(a, P.v(p + "norm1.weight"), P.v(p + "norm1.bias"), x1, m1, r1, res=x)
-        if (fuse and self.infer_packed and d == 512 and not TU.no_ffn_infer
-                and hip.ffn_infer_panels(M, d, self.ffn) and x2.is_contiguous()
-                and M <= TU.ffn_infer_max_m):
+        if not (route.ln_panel and hip.linear_ln_panel_fwd(attn.view(M, d), self._image_block(0), P.v(p + self.OUT_PROJ[1]), x,
+                                                           P.v(p + "norm1.weight"), P.v(p + "norm1.bias"), x1)) \
+                and not self._lin_ln(P, attn.view(M, d), *self.OUT_PROJ, x, x1, ".lnws1"):
+            a, m1, r1 = self._sublayer(P, attn.view(M, d), *self.OUT_PROJ, x, x1, (".a", ".m1", ".r1"), None, 1)
+        if route.ffn_infer and x2.is_contiguous():
             # the feed-forward sublayer: a panel of rows is shared by the workgroups of its hidden chunks (both GEMMs, the
             # hidden activation stays in LDS), the slab-reduction LayerNorm launch finishes it (csrc/linln_panel.hip)
             ws = self.buf.bytes(tg + ".ffws", int(hip.lib().ib_ffn_infer_workspace(M, d, self.ffn)))
             hip.ffn_infer_fwd(x1, self.packed_image(), P.v(p + "feedforward.0.bias"), P.v(p + "feedforward.2.bias"),
                               P.v(p + "norm2.weight"), P.v(p + "norm2.bias"), x2.view(M, d), ws)
-            self.ctx = None
-            return x2
+            return
         hip.linear_fwd(x1, P.w(p + "feedforward.0.weight"), P.v(p + "feedforward.0.bias"), f1, act="relu")
-        if not (fuse and lin_ln(f1, "feedforward.2.weight", "feedforward.2.bias", "norm2", x1, x2.view(M, d), ".lnws2")):
-            f2 = g(tg + ".f2", (M, d), dt)
-            hip.linear_fwd(f1, P.w(p + "feedforward.2.weight"), P.v(p + "feedforward.2.bias"), f2)
-            if drop:           # dropout2
-                hip.dropout(f2, f2, self.drop_p, self.seed + 2, step, step_dev)
-            m2, r2 = g(tg + ".m2", (M,), torch.float32), g(tg + ".r2", (M,), torch.float32)
-            hip.layernorm_fwd(f2, P.v(p + "norm2.weight"), P.v(p + "norm2.bias"), x2.view(M, d), m2, r2, res=x1)
-        self.ctx = (x, qkv, attn, lse, a, x1, m1, r1, f1, f2, m2, r2, B, T, drop)
-        return x2
+        if not self._lin_ln(P, f1, *self.FFN2, x1, x2.view(M, d), ".lnws2"):
+            f2, m2, r2 = self._sublayer(P, f1, *self.FFN2, x1, x2.view(M, d), (".f2", ".m2", ".r2"), None, 2)
+        self.ctx = LayerCtx(route, x, qkv, attn, lse, a, x1, m1, r1, f1, f2, m2, r2, B, T, None)
+
+    def _fwd_per_op(self, route, P, x, qkv, attn, lse, x2, B, T, drop):
+        M, d = x.shape
+        g, dt, p, tg = self.buf.get, self.dtype, self.p, self.tag
+        x1, f1 = g(tg + ".x1", (M, d), dt), g(tg + ".f1", (M, self.ffn), dt)
+        a, m1, r1 = self._sublayer(P, attn.view(M, d), *self.OUT_PROJ, x, x1, (".a", ".m1", ".r1"), drop, 1)     # dropout1
+        hip.linear_fwd(x1, P.w(p + "feedforward.0.weight"), P.v(p + "feedforward.0.bias"), f1, act="relu")
+        f2, m2, r2 = self._sublayer(P, f1, *self.FFN2, x1, x2.view(M, d), (".f2", ".m2", ".r2"), drop, 2)        # dropout2
+        self.ctx = LayerCtx(route, x, qkv, attn, lse, a, x1, m1, r1, f1, f2, m2, r2, B, T, drop)
 
     def ready_order(self) -> List[str]:
         p = self.p
@@ -814,200 +893,124 @@ class TransformerLayerPlan:
                                 "multihead_attention.out_proj.weight", "multihead_attention.out_proj.bias",
                                 "multihead_attention.in_proj_weight", "multihead_attention.in_proj_bias")]
 
-    def backward(self, dx2: Optional[torch.Tensor], P: ParamSource, accumulate=False, qkv_head=None) -> Optional[torch.Tensor]:
-        """qkv_head = (packed image, dqkv [M, 3 d], ds1 [M, d]) of the layer ABOVE: dx2 (may be None) is then computed inside
-        this layer's fused launch.  Returns dx, or None when this layer's own in-projection dgrad is left to the layer below
-        (`head_active`; `self.pending_head` then holds the triple to hand down)."""
-        x, qkv, attn, lse, a, x1, m1, r1, f1, f2, m2, r2, B, T, drop = self.ctx
-        M, d = x.shape
-        self.pending_head = None
-        g, dt, p, tg = self.buf.get, self.dtype, self.p, self.tag
-        lnws = self.buf.bytes("ln.ws", hip.layernorm_bwd_workspace_bytes(M, max(d, 1)))
-        defer, later = self.defer, self.later
+    def backward(self, dx2: torch.Tensor, P: ParamSource, accumulate=False) -> torch.Tensor:
+        """the standalone layer"""
+        return self.run_backward(dx2, P, accumulate).dx
+
+    def run_backward(self, dx2: Optional[torch.Tensor], P: ParamSource, accumulate=False, qkv_head=None,
+                     defer: Optional[list] = None, later: Optional[list] = None) -> LayerBack:
+        """qkv_head = LayerBack.head of the layer ABOVE: dx2 (may be None) is then computed inside this layer's fused launch.
+        defer / later, from a parent plan whose trainer lets the optimizer sum partial gradients (one GPU): weight-gradient
+        slabs go to `defer` [(workspace, nslab, dw)], bias / LayerNorm partial sums to `later` [(rows, count, gradient)]."""
+        c = self.ctx
+        M, bf16 = c.x.shape[0], self.dtype == torch.bfloat16
         # one GPU (slabs go to the optimizer): the layer's four weight-gradient GEMMs are issued as ONE grouped launch at
         # the end of the layer (they share a workgroup budget: fewer, longer slices, half the slab traffic)
-        # data parallel / drop-in autograd tier with large batches: the same grouped launch, its slabs and every partial-sum
-        # matrix of the layer finished by ONE reduction launch at the end of the layer (before the layer's bucket is
-        # all-reduced) instead of a slab reduction per weight and two column-sum launches per bias
-        local = defer is None and dt == torch.bfloat16 and M >= 4096 and not accumulate \
-            and not TU.no_layer_group
+        # data parallel / drop-in autograd tier with large batches (`local`): the same grouped launch, its slabs and every
+        # partial-sum matrix of the layer finished by ONE reduction launch behind it, before the layer's bucket is all-reduced
+        local = defer is None and bf16 and M >= 4096 and not accumulate and not TU.no_layer_group
         if local:
             defer, later = [], []
-        group = [] if (defer is not None and dt == torch.bfloat16 and not TU.no_layer_group) else None
-        lag = self.lag_group and self.parent_flushes and local and group is not None
-        lag_names: List[str] = []
+        grouped = defer is not None and bf16 and not TU.no_layer_group
+        lag = self.lag_group and self.parent_flushes and local and grouped
+        names: List[str] = []
         if self.parent_flushes:       # gradients are reported ready by the parent, in its order, after its joins
-            P = ParamSource(P.w, P.v, P.g, ready=lag_names.append, flush=lambda: None)
-        fork = self._always_fork or (group is not None and not local and not self.flush_on_exit and M >= 4096)
-        side = self.branch.run if fork else (lambda fn: fn())
-
-        def wgrad(dz_, x_, name, tag, bias=None):
-            """bias = (workspace tag, bias parameter name): with the grouped launch the bias gradient's partial sums come
-            out of the weight-gradient GEMM itself; otherwise a column-sum launch"""
-            fused_bias = group is not None and later is not None and bias is not None and dz_.shape[0] > 512
-            if group is not None:
-                group.append((dz_, x_, P.g(p + name), tag, P.g(p + bias[1]) if fused_bias else None, bias))
-            else:
-                _wgrad(self.buf, dz_, x_, P.g(p + name), accumulate, ws_tag=tag, defer=defer)
-            P.ready(p + name)
-            if bias is not None:
-                if fused_bias:
-                    P.ready(p + bias[1])
-                else:
-                    dbias(bias[0], dz_, bias[1])
-
-        def ln_bwd(which, dy, xin, mean, rstd, dxo, res):
-            """LayerNorm backward; parameter gradients finished here, or their per-block partial sums left for the optimizer"""
-            gw, gb = P.g(p + which + ".weight"), P.g(p + which + ".bias")
-            if later is None:
-                hip.layernorm_bwd(dy, xin, P.v(p + which + ".weight"), mean, rstd, dxo, gw, gb, lnws, res=res,
-                                  accumulate=accumulate)
-            else:
-                nb = hip.layernorm_bwd_workspace_bytes(M, d)
-                ws = self.buf.bytes(tg + ".lnws." + which, nb)              # one per LayerNorm: read at the end of the step
-                hip.layernorm_bwd(dy, xin, P.v(p + which + ".weight"), mean, rstd, dxo, None, None, ws, res=res)
-                parts = nb // (2 * d * 4)
-                part = ws[:nb].view(torch.float32).view(2 * parts, d)
-                later.append((part[:parts], parts, gw))
-                later.append((part[parts:], parts, gb))
-            P.ready(p + which + ".weight"); P.ready(p + which + ".bias")
-
-        def dbias(tag, dz, name):
-            if later is None or dz.shape[0] <= 512:
-                _colsum(self.buf, tag, dz, P.g(p + name), accumulate)
-            else:
-                part = self.buf.get(tag + ".colsum", ((dz.shape[0] + 127) // 128, dz.shape[1]), torch.float32)
-                hip.segment_colsum(dz, part, seg=128, mode=0)
-                later.append((part, part.shape[0], P.g(p + name)))
-            P.ready(p + name)
-        # LN2: d(f2 + x1)
-        ds2 = g(tg + ".ds2", (M, d), dt)
-        dz1 = g(tg + ".dz1", (M, self.ffn), dt)
-        dx1 = g(tg + ".dx1", (M, d), dt)
-        fused_ffn = getattr(self, "_ffn_fused", False)
-        ds1 = g(tg + ".ds1", (M, d), dt)
-        dattn = g(tg + ".dattn", (B, T, d), dt)
-        if fused_ffn:
-            # LayerNorm2 backward + both dgrad GEMMs of the feed-forward sublayer + LayerNorm1 backward + the out-projection's
-            # dgrad in ONE launch (csrc/ffn_chain.hip); `f2` / `a` are the saved LayerNorm inputs.  dgamma / dbeta leave as
-            # per-panel partial sums, finished with the layer's other partials.
-            if later is None:
-                raise hip.HipError("fused feed-forward backward needs the deferred partial-sum path (bf16, M >= 4096)")
-            Ta = getattr(self, "_att_T", 0)
-            nwg = hip.ffn_chain_workgroups(M, d, self.ffn, Ta)
-            part = self.buf.get(tg + ".ffnpart", (4 * nwg, d), torch.float32)
-            att_bwd = None
-            if Ta:
-                # the whole layer in this launch: attention backward + in-projection dgrad + residual addend behind the
-                # out-projection's dgrad (dattn never leaves the workgroup)
-                if qkv_head is not None:
-                    raise hip.HipError("TransformerLayerPlan.backward: a QKV head and the attention tail exclude each other")
-                dqkv = g(tg + ".dqkv", (B, T, 3 * d), dt)
-                dx_att = g(tg + ".dx", (B, T, d), dt)
-                att_bwd = (qkv.view(M, 3 * d), lse, dqkv.view(M, 3 * d), dx_att.view(M, d), Ta)
-            hip.ffn_chain_bwd(None if qkv_head is not None else dx2.view(M, d), f2, m2, r2, P.v(p + "norm2.weight"),
-                              self.buf.get(tg + ".ffnpk", (hip.ffn_chain_packed_elems(d, self.ffn),), dt),
-                              self.buf.get(tg + ".ffnmask", (hip.ffn_chain_mask_bytes(M, d, self.ffn, Ta),), torch.uint8),
-                              ds2, dz1, None, part,
-                              attn_out=(a, m1, r1, P.v(p + "norm1.weight"), ds1, None if Ta else dattn.view(M, d)),
-                              qkv_head=qkv_head, attn_bwd=att_bwd)
-            later.append((part[:nwg], nwg, P.g(p + "norm2.weight")))
-            later.append((part[nwg:2 * nwg], nwg, P.g(p + "norm2.bias")))
-            P.ready(p + "norm2.weight"); P.ready(p + "norm2.bias")
+            P = ParamSource(P.w, P.v, P.g, ready=names.append, flush=lambda: None)
+        fork = self._always_fork or (grouped and not local and not self.flush_on_exit and M >= 4096)
+        G = _Grads(self.buf, P, self.p, self.tag, accumulate, defer, later, grouped, side=self.branch.run if fork else None)
+        if c.route.fused:
+            dx, head = self._bwd_fused(c, dx2, P, G, qkv_head, lag)
+        elif qkv_head is not None:
+            raise hip.HipError("TransformerLayerPlan.backward: a QKV head needs the fused token-local launch")
         else:
-            if qkv_head is not None:
-                raise hip.HipError("TransformerLayerPlan.backward: a QKV head needs the fused token-local launch")
-            ln_bwd("norm2", dx2.view(M, d), f2, m2, r2, ds2, x1)
+            dx, head = self._bwd_per_op(c, dx2, P, G), None
+        if G.group:
+            run_group = lambda: G.launch_group(G.group, reduce=local)
+            if lag:
+                return LayerBack(dx, head, (run_group, names))
+            G.side(run_group)
+        elif local:
+            G.launch_group([], reduce=True)        # nothing was grouped: the reduction alone
+        if self.standalone or self.flush_on_exit:
+            self.branch.join()
+        if self.flush_on_exit and not self.parent_flushes:
+            P.flush()
+        return LayerBack(dx, head, (None, names) if self.parent_flushes else None)   # (None: everything is issued)
+
+    def _bwd_fused(self, c: LayerCtx, dx2, P, G: _Grads, qkv_head, lag: bool):
+        """LayerNorm2 backward + both dgrad GEMMs of the feed-forward sublayer + LayerNorm1 backward + the out-projection's
+        dgrad in ONE launch (csrc/ffn_chain.hip); c.f2 / c.a are the saved LayerNorm inputs.  dgamma / dbeta leave as
+        per-panel partial sums, finished with the layer's other partials.  Returns (dx, head for the layer below)."""
+        if G.later is None:
+            raise hip.HipError("fused feed-forward backward needs the deferred partial-sum path (bf16, M >= 4096)")
+        M, d = c.x.shape
+        B, T, Ta = c.B, c.T, c.route.att_T
+        g, dt, p, tg = self.buf.get, self.dtype, self.p, self.tag
+        ds2, ds1, dz1 = g(tg + ".ds2", (M, d), dt), g(tg + ".ds1", (M, d), dt), g(tg + ".dz1", (M, self.ffn), dt)
+        dattn = g(tg + ".dattn", (B, T, d), dt)
+        dx = None if c.route.dgrad_below else g(tg + ".dx", (B, T, d), dt)
+        dq2 = g(tg + ".dqkv", (B, T, 3 * d), dt).view(M, 3 * d)
+        nwg = hip.ffn_chain_workgroups(M, d, self.ffn, Ta)
+        part = g(tg + ".ffnpart", (4 * nwg, d), torch.float32)
+        if Ta and qkv_head is not None:
+            raise hip.HipError("TransformerLayerPlan.backward: a QKV head and the attention tail exclude each other")
+        # Ta: the whole layer in this launch -- attention backward + in-projection dgrad + residual addend behind the
+        # out-projection's dgrad (dattn never leaves the workgroup)
+        hip.ffn_chain_bwd(None if qkv_head is not None else dx2.view(M, d), c.f2, c.m2, c.r2, P.v(p + "norm2.weight"),
+                          self.packed_image(), g(tg + ".ffnmask", (hip.ffn_chain_mask_bytes(M, d, self.ffn, Ta),), torch.uint8),
+                          ds2, dz1, None, part,
+                          attn_out=(c.a, c.m1, c.r1, P.v(p + "norm1.weight"), ds1, None if Ta else dattn.view(M, d)),
+                          qkv_head=qkv_head,
+                          attn_bwd=(c.qkv.view(M, 3 * d), c.lse, dq2, dx.view(M, d), Ta) if Ta else None)
+        G.parts(part, nwg, "norm2.weight", "norm2.bias")
+        G.wgrad(ds2, c.f1, "2", "feedforward.2.weight", "feedforward.2.bias")
+        G.wgrad(dz1, c.x1, "1", "feedforward.0.weight", "feedforward.0.bias")
+        G.parts(part[2 * nwg:], nwg, "norm1.weight", "norm1.bias")
+        G.wgrad(ds1, c.attn.view(M, d), "o", "multihead_attention.out_proj.weight", "multihead_attention.out_proj.bias")
+        if self.runs_last and G.group and not lag and not TU.no_tail_split and not Ta:
+            # the layer whose backward runs last has nothing behind it to hide its weight-gradient launch: the three
+            # problems whose operands the fused launch has just written go off NOW, beside the attention backward and the
+            # in-projection's dgrad (measured and dropped for the other layers, round 4: one more fork per layer against
+            # launches that already fill the chip, 1.97 -> 2.19 ms per step)
+            early, G.group[:] = list(G.group), []
+            G.side = self.branch.run          # the rest of the group follows on the same stream (it may read these slabs)
+            self.branch.run(lambda: G.launch_group(early))
+        if not Ta:
+            hip.attention_bwd(c.qkv, c.attn, dattn, c.lse, dq2.view(B, T, 3 * d), self.h, drop=None)
+        G.wgrad(dq2, c.x, "i", "multihead_attention.in_proj_weight", "multihead_attention.in_proj_bias")
+        if dx is None:
+            return None, (self.packed_image(), dq2, ds1)       # dq2 . Wqkv + ds1: in front of the layer below's launch
+        if not Ta:
+            self._dgrad(P, c.route, dq2, "multihead_attention.in_proj_weight", dx.view(M, d), addend=ds1)
+        return dx, None
+
+    def _bwd_per_op(self, c: LayerCtx, dx2, P, G: _Grads):
+        M, d = c.x.shape
+        B, T, drop, r = c.B, c.T, c.drop, c.route
+        g, dt, tg = self.buf.get, self.dtype, self.tag
+        ds2, dx1, ds1 = (g(tg + n, (M, d), dt) for n in (".ds2", ".dx1", ".ds1"))
+        dz1, dattn, dx = g(tg + ".dz1", (M, self.ffn), dt), g(tg + ".dattn", (B, T, d), dt), g(tg + ".dx", (B, T, d), dt)
+        dqkv = g(tg + ".dqkv", (B, T, 3 * d), dt)
+        G.ln_bwd("norm2", dx2.view(M, d), c.f2, c.m2, c.r2, ds2, c.x1)                      # LN2: d(f2 + x1)
         # ds2 = d(x1 + Drop(f2)): the residual path takes it as is, the feedforward path through dropout2's mask
         df2 = ds2
         if drop:
             df2 = g(tg + ".df2", (M, d), dt)
             hip.dropout(ds2, df2, drop[0], self.seed + 2, drop[2], drop[3])
-
-        def g_ffn2():
-            wgrad(df2, f1, "feedforward.2.weight", tg + ".ws2", bias=(tg + ".b2", "feedforward.2.bias"))
-        side(g_ffn2)
-        if not fused_ffn:
-            self._dgrad(P, df2, "feedforward.2.weight", dz1, act_below="relu", aux=f1)
-
-        def g_ffn1():
-            wgrad(dz1, x1, "feedforward.0.weight", tg + ".ws1", bias=(tg + ".b1", "feedforward.0.bias"))
-        side(g_ffn1)
-        if fused_ffn:
-            later.append((part[2 * nwg:3 * nwg], nwg, P.g(p + "norm1.weight")))
-            later.append((part[3 * nwg:], nwg, P.g(p + "norm1.bias")))
-            P.ready(p + "norm1.weight"); P.ready(p + "norm1.bias")
-        else:
-            self._dgrad(P, dz1, "feedforward.0.weight", dx1, addend=ds2)       # + residual path
-            # LN1: d(a + x)
-            ln_bwd("norm1", dx1, a, m1, r1, ds1, x)
+        G.wgrad(df2, c.f1, "2", "feedforward.2.weight", "feedforward.2.bias")
+        self._dgrad(P, r, df2, "feedforward.2.weight", dz1, act_below="relu", aux=c.f1)
+        G.wgrad(dz1, c.x1, "1", "feedforward.0.weight", "feedforward.0.bias")
+        self._dgrad(P, r, dz1, "feedforward.0.weight", dx1, addend=ds2)                    # + residual path
+        G.ln_bwd("norm1", dx1, c.a, c.m1, c.r1, ds1, c.x)                                   # LN1: d(a + x)
         da = ds1                       # d(x + Drop(a)): dropout1's mask on the attention path only
         if drop:
             da = g(tg + ".da", (M, d), dt)
             hip.dropout(ds1, da, drop[0], self.seed + 1, drop[2], drop[3])
-
-        def g_out():
-            wgrad(da, attn.view(M, d), "multihead_attention.out_proj.weight", tg + ".wso",
-                  bias=(tg + ".bo", "multihead_attention.out_proj.bias"))
-        side(g_out)
-        att_done = fused_ffn and bool(getattr(self, "_att_T", 0))
-        if self.split_tail and group and fused_ffn and not lag and not TU.no_tail_split and not att_done:
-            # the layer whose backward runs last has nothing behind it to hide its weight-gradient launch: the three
-            # problems whose operands the fused launch has just written go off NOW, beside the attention backward and the
-            # in-projection's dgrad (measured and dropped for the other layers, round 4: 5 + 10 slabs per weight instead
-            # of 4 and one more fork per layer against launches that already fill the chip: 1.97 -> 2.19 ms per step)
-            early = list(group)
-            del group[:]
-            side = self.branch.run            # the rest of the group follows on the same stream (it may read these slabs)
-
-            def run_early():
-                for pr in _wgrad_group(self.buf, early, defer, later):
-                    btag, bname = pr[5]
-                    bp = self.buf.get(btag + ".colsum", ((pr[0].shape[0] + 127) // 128, pr[0].shape[1]), torch.float32)
-                    hip.segment_colsum(pr[0], bp, seg=128, mode=0)
-                    later.append((bp, bp.shape[0], P.g(p + bname)))
-            self.branch.run(run_early)
-        if not fused_ffn:
-            self._dgrad(P, da, "multihead_attention.out_proj.weight", dattn.view(M, d))
-        dqkv = g(tg + ".dqkv", (B, T, 3 * d), dt)
-        if not att_done:
-            hip.attention_bwd(qkv, attn, dattn, lse, dqkv, self.h, drop=drop)
-        dq2 = dqkv.view(M, 3 * d)
-
-        def g_in():
-            wgrad(dq2, x, "multihead_attention.in_proj_weight", tg + ".wsi",
-                  bias=(tg + ".bi", "multihead_attention.in_proj_bias"))
-        side(g_in)
-        if att_done:
-            dx = g(tg + ".dx", (B, T, d), dt)      # written by the fused launch
-        elif self.head_active(M):
-            dx = None                  # dq2 . Wqkv + ds1 is computed in front of the layer below's fused backward launch
-            self.pending_head = (self.packed_image(), dq2, ds1)
-        else:
-            dx = g(tg + ".dx", (B, T, d), dt)
-            self._dgrad(P, dq2, "multihead_attention.in_proj_weight", dx.view(M, d), addend=ds1)
-        if group:
-            def run_group():
-                # problems the grouped launch could not take sum their bias gradient the plain way (P.ready already said)
-                for pr in _wgrad_group(self.buf, group, defer, later):
-                    btag, bname = pr[5]
-                    part = self.buf.get(btag + ".colsum", ((pr[0].shape[0] + 127) // 128, pr[0].shape[1]), torch.float32)
-                    hip.segment_colsum(pr[0], part, seg=128, mode=0)
-                    later.append((part, part.shape[0], P.g(p + bname)))
-                if local:     # reads the slabs of the launch above: same stream
-                    hip.step_reduce_parts(defer, [(part, rows, dst) for part, rows, dst in later])
-            if lag:
-                self._lagged = (run_group, lag_names)
-                return dx
-            side(run_group)
-        elif local:
-            hip.step_reduce_parts(defer, [(part, rows, dst) for part, rows, dst in later])
-        if self.join_on_exit or self.flush_on_exit:
-            self.branch.join()
-        if self.parent_flushes:
-            self._lagged = (None, lag_names)          # everything issued; the parent reports and flushes
-        elif self.flush_on_exit:
-            P.flush()
+        G.wgrad(da, c.attn.view(M, d), "o", "multihead_attention.out_proj.weight", "multihead_attention.out_proj.bias")
+        self._dgrad(P, r, da, "multihead_attention.out_proj.weight", dattn.view(M, d))
+        hip.attention_bwd(c.qkv, c.attn, dattn, c.lse, dqkv, self.h, drop=drop)
+        G.wgrad(dqkv.view(M, 3 * d), c.x, "i", "multihead_attention.in_proj_weight", "multihead_attention.in_proj_bias")
+        self._dgrad(P, r, dqkv.view(M, 3 * d), "multihead_attention.in_proj_weight", dx.view(M, d), addend=ds1)
         return dx
 
 
@@ -1035,20 +1038,17 @@ class TimeMLPPlan:
         u = g(tg + ".u", (B, w1.shape[0]), dt)
         zu = g(tg + ".zu", (B, w1.shape[0]), dt)
         e = g(tg + ".e", (B, w2.shape[0]), dt)
+        self.ctx = (s, u, zu)
         if head is not None:
             hip.tr_head_prep(table, t, w1, P.v("time_mlp.0.bias"), w2, P.v("time_mlp.2.bias"), s, zu, u, e, **head)
-            self.ctx = (s, u, zu)
-            return e
-        if self.fused_ok(table, P):
+        elif self.fused_ok(table, P):
             # one launch instead of gather + two M = B GEMMs (three latency-bound launches on the critical path)
             hip.time_mlp_fwd(table, t, w1, P.v("time_mlp.0.bias"), w2, P.v("time_mlp.2.bias"), s, zu, u, e, pack=pack,
                              slots=slots if pack is not None else None)
-            self.ctx = (s, u, zu)
-            return e
-        hip.gather_rows(table, t, s)
-        hip.linear_fwd(s, w1, P.v("time_mlp.0.bias"), u, act="silu", z=zu)
-        hip.linear_fwd(u, w2, P.v("time_mlp.2.bias"), e)
-        self.ctx = (s, u, zu)
+        else:
+            hip.gather_rows(table, t, s)
+            hip.linear_fwd(s, w1, P.v("time_mlp.0.bias"), u, act="silu", z=zu)
+            hip.linear_fwd(u, w2, P.v("time_mlp.2.bias"), e)
         return e
 
     @staticmethod
@@ -1383,6 +1383,12 @@ class DenoiserMLPPlan:
             P.ready(n)
 
 
+# the padded form of the two D-wide projections (D = 300: rows of 600 bytes are not 16-byte aligned): zero-padded weight copies
+# w_in [d, Kp], w_out [Kp, d], b_out [Kp] (training: w_outT [d, Kp], the output projection's dgrad operand) over activation
+# buffers pitched to Kp columns.  Chosen once per forward (DenoiserTransformerPlan._ends; None there = the plain form).
+_Ends = namedtuple("_Ends", "Kp w_in w_out b_out w_outT", defaults=(None,))
+
+
 class DenoiserTransformerPlan:
     """Transformer denoiser (BASELINE configs 3-5): in-proj(x ++ frame-embedding) + time embedding,
     N reference TransformerLayers, out-proj."""
@@ -1393,14 +1399,14 @@ class DenoiserTransformerPlan:
         self.time = TimeMLPPlan(dtype, self.buf)
         self.layers = [TransformerLayerPlan(f"transformer_layers.{l}.", d_model, num_heads, ffn, dtype, device,
                                             buf=self.buf, tag=f"tl{l}") for l in range(num_layers)]
-        for lp in self.layers:
-            lp.join_on_exit = False          # joined once, at the end of the whole backward
-            lp.own_wt = False                # the transposed weight copies of ALL layers are refreshed by one launch
-        for lo, hi in zip(self.layers[:-1], self.layers[1:]):
-            lo.qkv_tail_for, hi.qkv_dgrad_below = hi, lo     # the upper layer's in-projection rides in the lower layer's launches
-        self.layers[0].split_tail = True
-        self.ctx = None
-        self._posproj_T = None
+        # the upper layer's in-projection rides in the lower layer's launches; the backward ends with layer 0
+        for lp, above in zip(self.layers, self.layers[1:] + [None]):
+            lp.in_stack(above=above, runs_last=lp is self.layers[0])
+        self.ctx = None                                 # (x, pos, h, B, T, ends) of the last forward
+        self.inference = False
+        self._side: Optional[List[TransformerLayerPlan]] = None
+        self._posproj_T = self._e_all = None            # prepare_inference: the time embedding of every timestep
+        self._pad: Optional[_Ends] = None               # prepare_inference: the sampler's padded projections
         self.fuse_reduce_into_optimizer = False         # set by HipTrainer for single-GPU steps
         self.pending_sources = None
         self.early_optimizer = None                     # set by HipTrainer: fn(parameter prefix, sources) -- see backward()
@@ -1412,6 +1418,23 @@ class DenoiserTransformerPlan:
         self.br_pos = Branch(device, name="tr_pos")
         self.br_wt = Branch(device, name="tr_wt")
         self.br_side = Branch(device, name="tr_side")    # sampler: the windows beyond the fused launch's last full round
+
+    def routes(self, M: int, T: int) -> List[LayerRoute]:
+        """every layer's route of one step: each layer's own, then what depends on a neighbour, from the neighbour's route
+        (the layers of a stack are built alike: same width, heads and hidden width)"""
+        own = [lp.route(M, T) for lp in self.layers]
+        if TU.no_qkv_fuse:
+            return own
+        out = []
+        for i, (lp, r) in enumerate(zip(self.layers, own)):
+            rn = own[i + 1] if lp.above is not None else None
+            qkv_next = rn is not None and ((r.fused and rn.fused) or (r.infer_chain and lp.above.infer_packed))
+            # both fused: the layer below runs this layer's in-projection GEMMs in its launches -- no transposed copy, and
+            # (token-count panels) no in-projection dgrad launch of this layer's own
+            pair_below = i > 0 and r.fused and own[i - 1].fused
+            out.append(replace(r, qkv_next=qkv_next, attn_next=bool(qkv_next and r.att_T and rn.att_T),
+                               dgrad_below=pair_below and not r.att_T, wt_names=() if pair_below else r.wt_names))
+        return out
 
     def side_windows(self, B: int, T: int) -> int:
         """sampler: how many of the batch's last windows take the per-op side stack (0: none) -- the fused launch's last
@@ -1431,38 +1454,30 @@ class DenoiserTransformerPlan:
         return Bs
 
     def side_layers(self) -> List["TransformerLayerPlan"]:
-        """a second set of layer plans over the same parameters and packed images, with activation buffers of their own"""
+        """a second set of layer plans over the same parameters and packed images (the main layers', packed once per
+        sampling loop), with activation buffers of their own"""
         if self._side is None:
-            self._side = []
-            for lp in self.layers:
-                sl = TransformerLayerPlan(lp.p, lp.d, lp.h, lp.ffn, lp.dtype, self.buf.device, buf=self.buf, tag=lp.tag + "s")
-                sl.join_on_exit, sl.own_wt = False, False
-                sl.packed_image = lp.packed_image             # the main layer's image (packed once per sampling loop)
-                self._side.append(sl)
+            self._side = [TransformerLayerPlan(lp.p, lp.d, lp.h, lp.ffn, lp.dtype, self.buf.device, buf=self.buf,
+                                               tag=lp.tag + "s") for lp in self.layers]
         for sl, lp in zip(self._side, self.layers):
+            sl.in_stack(image_of=lp)
             sl.inference, sl.infer_packed = lp.inference, lp.infer_packed
         return self._side
-
-    _side = None
 
     def flush_each_layer(self, on: bool):
         """overlapped data-parallel steps: keep the layers' side streams, hand completed gradient buckets to the trainer at
         every layer boundary (ParamSource.flush) instead of running the whole backward on one stream"""
         lag = bool(on) and not TU.no_lag_group
-        for i, lp in enumerate(self.layers):
-            lp.flush_on_exit = bool(on)
-            lp.parent_flushes = lag
-            lp.lag_group = lag                      # (round 5: layer 0's too -- it runs beside the step's tail of small launches)
+        for lp in self.layers:       # (round 5: layer 0 lags too -- it runs beside the step's tail of small launches)
+            lp.flush_on_exit, lp.parent_flushes, lp.lag_group = bool(on), lag, lag
 
     def set_inference(self, on: bool):
         """forward-only mode with frozen weights (the DDIM sampler): fused Linear + residual + LayerNorm in every layer,
         the frame-embedding projection computed once"""
         self.inference = bool(on)
-        self._posproj_T = None
-        self._e_all = None
-        for lp in self.layers:
-            lp.inference = bool(on)
-            lp.infer_packed = False                       # prepare_inference packs the (then frozen) weights again
+        self._posproj_T = self._e_all = None
+        for lp in self.layers:       # (prepare_inference packs the then frozen weights again)
+            lp.inference, lp.infer_packed = bool(on), False
 
     def prepare_inference(self, P: ParamSource, T: int, D: int, table: Optional[torch.Tensor] = None):
         """once per sampling loop (weights frozen from here on): the frame-embedding half of the input projection, and --
@@ -1472,13 +1487,11 @@ class DenoiserTransformerPlan:
         pos = P.w("temporal_embedding.embedding.weight")[:T]
         posproj = self.buf.get("dt.posproj", (T, self.d), self.dtype)
         hip.tiny_matmul(pos, w_in[:, D:].t(), posproj)
-        self._posproj_T = T
-        self._e_all = None
-        # zero-padded copies of the two D-wide projections (D = 300: rows of 600 bytes are not 16-byte aligned, so both ran on
-        # the generic register-staged kernel: 18.6 + 13.5 us of a 380-us step at B = 16).  With the sampler's state and
-        # noise buffers pitched to infer_pitch(D) columns (pad columns zero) the input projection reduces over 320 columns on
-        # the LDS-DMA ring kernel and the output projection writes 320 columns on the 256 x 128 NT kernel.
-        self._pad = None
+        self._posproj_T, self._e_all, self._pad = T, None, None
+        # zero-padded copies of the two D-wide projections (_Ends; unpadded both ran on the generic register-staged kernel:
+        # 18.6 + 13.5 us of a 380-us step at B = 16).  With the sampler's state and noise buffers pitched to infer_pitch(D)
+        # columns (pad columns zero) the input projection reduces over 320 columns on the LDS-DMA ring kernel and the output
+        # projection writes 320 columns on the 256 x 128 NT kernel.
         Kp = self.infer_pitch(D)
         if Kp != D and self.dtype == torch.bfloat16:
             w_in_pad = self.buf.get("dt.w_in_pad", (self.d, Kp), self.dtype)
@@ -1488,7 +1501,7 @@ class DenoiserTransformerPlan:
             hip.cast2d(w_in[:, :D], w_in_pad[:, :D])
             hip.cast2d(P.w("out_proj.weight"), w_out_pad[:D])
             b_out_pad[:D].copy_(P.v("out_proj.bias"))
-            self._pad = (Kp, w_in_pad, w_out_pad, b_out_pad)
+            self._pad = _Ends(Kp, w_in_pad, w_out_pad, b_out_pad)
         # frozen weights: every layer's packed image once per sampling loop -- the attention out-projection + residual +
         # LayerNorm1 of a denoise step is then ONE launch over row panels (csrc/linln_panel.hip) while the step has at most a
         # few thousand rows, instead of a split-K GEMM into fp32 slabs + a reduction launch
@@ -1496,9 +1509,7 @@ class DenoiserTransformerPlan:
             lp.infer_packed = False
         if (self.dtype == torch.bfloat16 and self.d == 512 and not TU.no_linln_panel
                 and all(hip.ffn_chain_supported(self.d, lp.ffn) for lp in self.layers)):
-            hip.ffn_chain_pack([(P.w(lp.p + "feedforward.0.weight"), P.w(lp.p + "feedforward.2.weight"), lp.packed_image(),
-                                 P.w(lp.p + "multihead_attention.out_proj.weight"),
-                                 P.w(lp.p + "multihead_attention.in_proj_weight")) for lp in self.layers])
+            hip.ffn_chain_pack([lp.pack_item(P) for lp in self.layers])
             for lp in self.layers:
                 lp.infer_packed = True
         if table is not None and not TU.no_time_table:
@@ -1509,11 +1520,6 @@ class DenoiserTransformerPlan:
             hip.cast2d(e, e_all) if e.dtype != torch.float32 else e_all.copy_(e)
             self._e_all = e_all
 
-    _e_all = None
-    _pad = None
-
-    inference = False
-
     def train_pitch(self, D: int, M: int) -> int:
         """row pitch (elements) of the trainer's D-wide activation buffers (x_t, prediction, dL/dprediction): D rounded up to
         64 when the padded projections below apply (bf16, the large-M kernels), else to 8 (16-byte aligned rows)"""
@@ -1522,37 +1528,132 @@ class DenoiserTransformerPlan:
             return (D + 63) // 64 * 64
         return D if TU.no_pad else (D + 7) // 8 * 8
 
-    def _train_pad(self, M: int, D: int, x2: torch.Tensor, out: Optional[torch.Tensor]):
-        """training step with pitched activation buffers (train_pitch): zero-padded copies of the D-wide projection weights,
-        refreshed every step beside the weight transposes, so that the input projection reduces over 320 columns on the
-        LDS-DMA ring kernel and the output projection / its input gradient run on the 256 x 128 NT kernel (the 300-wide
-        operands put all three on the generic register-staged kernel: 23.6 + 17.1 + 16.8 us per step)"""
-        Kp = self.train_pitch(D, M)
-        if Kp % 64 != 0 or Kp == D or out is None or x2.dim() != 2 or out.dim() != 2 or x2.stride(0) != Kp \
-                or out.stride(0) != Kp or x2.stride(1) != 1:
-            return None
-        g, dt = self.buf.get, self.dtype
-        return {"Kp": Kp, "w_in": g("dt.tp.w_in", (self.d, Kp), dt, zero=True), "w_out": g("dt.tp.w_out", (Kp, self.d), dt, zero=True),
-                "w_outT": g("dt.tp.w_outT", (self.d, Kp), dt, zero=True), "b_out": g("dt.tp.b_out", (Kp,), torch.float32, zero=True)}
-
-    _tp = None
-
     @staticmethod
     def infer_pitch(D: int) -> int:
         """row pitch (elements) the sampler gives its state / noise buffers: D rounded up to 64 (the K step of the LDS-DMA
         kernels) unless IB_NO_PAD; the pad columns must be zero"""
         return D if (TU.no_pad or D % 64 == 0) else (D + 63) // 64 * 64
 
+    def _ends(self, M: int, D: int, x2: torch.Tensor, out: Optional[torch.Tensor]) -> Optional[_Ends]:
+        """the form of the D-wide projections of this step: the padded one when the caller's buffers are pitched for it.
+        Sampler: prepare_inference's copies.  Training step (train_pitch): copies refreshed every step beside the weight
+        transposes -- the 300-wide operands put the input projection, the output projection and its input gradient on the
+        generic register-staged kernel, 23.6 + 17.1 + 16.8 us per step"""
+        Kp = self._pad.Kp if self.inference and self._pad is not None else 0 if self.inference else self.train_pitch(D, M)
+        if Kp == 0 or out is None or x2.dim() != 2 or out.dim() != 2 or x2.stride(0) != Kp or out.stride(0) != Kp \
+                or x2.stride(1) != 1:
+            return None
+        if self.inference:
+            return self._pad if M >= TU.pad_min_m else None      # below: B = 4 / 8 -1.6 %, B = 16 / 32 +3 %
+        if Kp % 64 != 0 or Kp == D:
+            return None
+        g, dt = self.buf.get, self.dtype
+        return _Ends(Kp, g("dt.tp.w_in", (self.d, Kp), dt, zero=True), g("dt.tp.w_out", (Kp, self.d), dt, zero=True),
+                     g("dt.tp.b_out", (Kp,), torch.float32, zero=True), g("dt.tp.w_outT", (self.d, Kp), dt, zero=True))
+
     def branches(self) -> List[Branch]:
         return [lp.branch for lp in self.layers] + [self.br_time, self.br_thid, self.br_pos, self.br_wt, self.br_side]
 
-    def head_merged(self, B: int, table: torch.Tensor, P: ParamSource) -> bool:
-        """training step: the head's independent small jobs -- time-MLP forward, frame-embedding projection, padded
-        in-projection copy -- are ONE launch on the main stream (hip.tr_head_prep) and the weight refreshes ONE launch on the
-        tr_wt branch (hip.ffn_chain_pack with transposes / casts), instead of eight launches on three streams"""
-        w1, w2 = P.w("time_mlp.0.weight"), P.w("time_mlp.2.weight")
-        return (not self.inference and not TU.no_head_merge and self.dtype == torch.bfloat16 and self.Pd < 64
-                and self.time.fused_ok(table, P) and hip.tr_head_prep_supported(table.shape[1], w1.shape[0], w2.shape[0], B))
+    def _refresh_weights(self, P: ParamSource, routes: List[LayerRoute], ends: Optional[_Ends], D: int, merged: bool):
+        """training: the transposed weight copies, the fused layers' packed images and the padded out-projection copies on
+        the tr_wt branch.  Returns whether the forward has to join the branch in front of layer 0 (it reads the images)."""
+        pairs = [pr for lp, r in zip(self.layers, routes) for pr in lp.wt_pairs(P, r)]
+        items = [lp.pack_item(P) for lp, r in zip(self.layers, routes) if r.fused]
+        if not (pairs or ends or items):
+            return False
+        # whole-layer tier (attention inside every layer's launches): what is left to transpose is the two ends of the
+        # stack, layer 0's in-projection and the output projection.  With separate attention launches the transposes are
+        # every layer's in-projection, a launch's worth of work of their own: that tier keeps ib_transpose_multi.
+        whole = all(r.att_T for r in routes)
+
+        def wt_branch():
+            casts = []
+            if ends:
+                w_out = P.w("out_proj.weight")
+                pairs.append((w_out, ends.w_outT[:, :D]))
+                casts = [(w_out, ends.w_out[:D]), (P.v("out_proj.bias").view(1, D), ends.b_out.view(1, -1)[:, :D])]
+            if merged and items and whole and len(pairs) <= hip.FFN_PACK_MAX_TRANSPOSES:
+                # one launch: the packing blocks first (layer 0's images are the first to be read), then the
+                # transposes and the padded out-projection copies (read by the backward / the end of the forward)
+                hip.ffn_chain_pack(items, transposes=pairs, casts=casts)
+                return
+            if items:        # first: layer 0's feed-forward sublayer is the first reader
+                hip.ffn_chain_pack(items)
+            for src, dst in casts:
+                hip.cast2d(src, dst)
+            hip.transpose_multi(pairs)
+        self.br_wt.run(wt_branch)
+        return bool(items)
+
+    def _head(self, t, table, P: ParamSource, routes, ends, B: int, T: int, D: int, pos, w_in, posproj):
+        """the time embedding e [B, d] and the frame-embedding projection, with the training step's weight refreshes beside
+        them.  Returns (e, join tr_wt in front of layer 0)."""
+        g, dt = self.buf.get, self.dtype
+        merged, join_wt = False, False
+        if self.inference and self._e_all is not None:
+            e = g("dt.e_rows", (B, self.d), dt)
+            hip.gather_rows(self._e_all, t, e)                               # rows of the per-timestep table
+        elif self.inference:
+            e = self.time.forward(t, table, P)                               # [B, d]
+        else:
+            # the head's independent small jobs -- time-MLP forward, frame-embedding projection, padded in-projection copy
+            # -- as ONE launch on the main stream (hip.tr_head_prep) and the weight refreshes as ONE launch on the tr_wt
+            # branch (hip.ffn_chain_pack with transposes / casts), instead of eight launches on three streams
+            w1, w2 = P.w("time_mlp.0.weight"), P.w("time_mlp.2.weight")
+            merged = (not TU.no_head_merge and dt == torch.bfloat16 and self.Pd < 64 and self.time.fused_ok(table, P)
+                      and hip.tr_head_prep_supported(table.shape[1], w1.shape[0], w2.shape[0], B))
+            cast_in = (w_in[:, :D], ends.w_in[:, :D]) if ends else None
+        if merged:
+            # the weight refreshes are forked FIRST, beside the head launch: forked behind it they ran beside the input
+            # projection, which fills the chip (29.6 -> 44.7 us in the stamped timeline)
+            join_wt = self._refresh_weights(P, routes, ends, D, merged)
+            # the head launch is as long as its longest job (the frame-embedding projection): no tr_time fork, no join ahead
+            # of the input projection.  q_sample / q_sample_cond stay the trainer's own launch ahead of this one: the
+            # conditional and the plain step keep one launch sequence.
+            e = self.time.forward(t, table, P, head={"posproj": (pos, w_in[:, D:].t(), posproj), "cast": cast_in})
+        elif not self.inference:
+            # the time-MLP and the weight refreshes (read by the backward only) beside the projection below
+            box = []
+
+            def t_branch():
+                box.append(self.time.forward(t, table, P))
+                if cast_in:
+                    hip.cast2d(*cast_in)
+            self.br_time.run(t_branch)
+            e = box[0]
+            join_wt = self._refresh_weights(P, routes, ends, D, merged)
+        if not (self.inference and self._posproj_T == T) and not merged:
+            hip.tiny_matmul(pos, w_in[:, D:].t(), posproj)       # frozen weights (sampling): projected once per sample()
+        self.br_time.join()
+        return e, join_wt
+
+    def _stack(self, routes, h0, P: ParamSource, B: int, T: int):
+        """the layers, bottom to top; each is told what the launch below already wrote for it"""
+        def run(layers, rts, h, out):
+            ready = aready = False
+            for i, (lp, r) in enumerate(zip(layers, rts)):
+                h, ready, aready = lp.run(r, h, P, out=out if i + 1 == len(layers) else None, qkv_ready=ready,
+                                          attn_ready=aready)
+            return h
+        Bs = self.side_windows(B, T)
+        if not Bs:
+            return run(self.layers, routes, h0, None)
+        # Sampler, large batch: a 64-row panel of the fused frozen-weight launch costs what its weight stream costs, so 800
+        # panels (B = 256, T = 200) are FOUR rounds of 256 workgroups for 3.125 rounds of work.  The windows beyond the last
+        # full round go through the whole stack on the row-panel kernels (which spread a weight's columns over the chip) on a
+        # side branch -- forked once, joined once -- beside the full rounds.
+        Bm = B - Bs
+        hL = self.buf.get("dt.hL", (B, T, self.d), self.dtype)
+        side = self.side_layers()
+
+        def side_stack():
+            hh = h0[Bm:]
+            for i, sl in enumerate(side):
+                hh = sl.run(sl.route(Bs * T, T), hh, P, out=hL[Bm:] if i + 1 == len(side) else None)[0]
+        self.br_side.run(side_stack)
+        run(self.layers, self.routes(Bm * T, T), h0[:Bm], hL[:Bm])
+        self.br_side.join()
+        return hL
 
     def forward(self, x3: torch.Tensor, t: torch.Tensor, table: torch.Tensor, P: ParamSource,
                 out: Optional[torch.Tensor] = None, BT: Optional[Tuple[int, int]] = None) -> torch.Tensor:
@@ -1561,132 +1662,31 @@ class DenoiserTransformerPlan:
             (B, T), D = BT, x3.shape[1]
         else:
             B, T, D = x3.shape
-        M = B * T
+        M, d = B * T, self.d
         x2 = x3 if x3.dim() == 2 else x3.view(M, D)
         g, dt = self.buf.get, self.dtype
         w_in = P.w("in_proj.weight")                                         # [d, D + Pd]
         pos = P.w("temporal_embedding.embedding.weight")[:T]                 # [T, Pd]
-        posproj = g("dt.posproj", (T, self.d), dt)
-        pairs = [pr for lp in self.layers for pr in lp.wt_pairs(P, M)]
-        ffn_items = [it for it in (lp.ffn_pack_item(P, M) for lp in self.layers) if it is not None]
-        merged = False
-        if self.inference and self._e_all is not None:
-            e = g("dt.e_rows", (B, self.d), dt)
-            hip.gather_rows(self._e_all, t, e)                               # rows of the per-timestep table
-        elif self.inference:
-            e = self.time.forward(t, table, P)                               # [B, d]
-        else:
-            # training: the time-MLP and the weight transposes (read by the backward only) beside the projection below
-            tp = self._tp = self._train_pad(M, D, x2, out)
-            merged = self.head_merged(B, table, P)
-            # whole-layer tier (attention inside every layer's launches): what is left to transpose is the two ends of the
-            # stack, layer 0's in-projection and the output projection.  With separate attention launches the transposes are
-            # every layer's in-projection, a launch's worth of work of their own: that tier keeps ib_transpose_multi.
-            whole = all(lp.attn_T(M, T) for lp in self.layers)
-
-            def fork_wt():
-                if not (pairs or tp or ffn_items):
-                    return
-
-                def wt_branch():
-                    pr, casts = list(pairs), []
-                    if tp:
-                        w_out = P.w("out_proj.weight")
-                        pr.append((w_out, tp["w_outT"][:, :D]))
-                        casts = [(w_out, tp["w_out"][:D]), (P.v("out_proj.bias").view(1, D), tp["b_out"].view(1, -1)[:, :D])]
-                    if merged and ffn_items and whole and len(pr) <= hip.FFN_PACK_MAX_TRANSPOSES:
-                        # one launch: the packing blocks first (layer 0's images are the first to be read), then the
-                        # transposes and the padded out-projection copies (read by the backward / the end of the forward)
-                        hip.ffn_chain_pack(ffn_items, transposes=pr, casts=casts)
-                        return
-                    if ffn_items:        # first: layer 0's feed-forward sublayer is the first reader
-                        hip.ffn_chain_pack(ffn_items)
-                    for src, dst in casts:
-                        hip.cast2d(src, dst)
-                    hip.transpose_multi(pr)
-                self.br_wt.run(wt_branch)
-            if merged:
-                # the weight refreshes are forked FIRST, beside the head launch: forked behind it they ran beside the input
-                # projection, which fills the chip (29.6 -> 44.7 us in the stamped timeline)
-                fork_wt()
-                # ONE launch on the main stream, as long as its longest job (the frame-embedding projection, which used to
-                # run in series behind q_sample beside the forked time-MLP): no tr_time fork, no join ahead of the input
-                # projection.  q_sample / q_sample_cond stay the trainer's own launch ahead of this one: the conditional and
-                # the plain step keep one launch sequence.
-                e = self.time.forward(t, table, P, head={
-                    "posproj": (pos, w_in[:, D:].t(), posproj),
-                    "cast": (w_in[:, :D], tp["w_in"][:, :D]) if tp else None})
-            else:
-                box = []
-
-                def t_branch():
-                    box.append(self.time.forward(t, table, P))
-                    if tp:
-                        hip.cast2d(w_in[:, :D], tp["w_in"][:, :D])
-                self.br_time.run(t_branch)
-                e = box[0]
-                fork_wt()
-        if not (self.inference and self._posproj_T == T) and not merged:
-            hip.tiny_matmul(pos, w_in[:, D:].t(), posproj)       # frozen weights (sampling): projected once per sample()
-        self.br_time.join()
-        h0 = g("dt.h0", (B, T, self.d), dt)
-        # sampler with pitched buffers (prepare_inference): both projections over the padded width
-        padded = (self.inference and self._pad is not None and out is not None and x2.dim() == 2 and out.dim() == 2
-                  and x2.stride(0) == self._pad[0] and out.stride(0) == self._pad[0] and x2.stride(1) == 1
-                  and M >= TU.pad_min_m)   # below: B = 4 / 8 -1.6 %, B = 16 / 32 +3 %
-        tp = None if self.inference else self._tp
-        if padded:
-            Kp, w_in_pad, w_out_pad, b_out_pad = self._pad
-            hip.linear_fwd(x2.as_strided((M, Kp), (Kp, 1)), w_in_pad, P.v("in_proj.bias"), h0.view(M, self.d), add_div=e,
-                           add_mod=posproj, seg=T)
-        elif tp:
-            hip.linear_fwd(x2.as_strided((M, tp["Kp"]), (tp["Kp"], 1)), tp["w_in"], P.v("in_proj.bias"), h0.view(M, self.d),
-                           add_div=e, add_mod=posproj, seg=T)
-        else:
-            hip.linear_fwd(x2, w_in[:, :D], P.v("in_proj.bias"), h0.view(M, self.d), add_div=e,
-                           add_mod=posproj, seg=T)
-        h = h0
-        if ffn_items and not self.inference:
+        posproj = g("dt.posproj", (T, d), dt)
+        routes = self.routes(M, T)
+        ends = self._ends(M, D, x2, out)
+        e, join_wt = self._head(t, table, P, routes, ends, B, T, D, pos, w_in, posproj)
+        h0 = g("dt.h0", (B, T, d), dt)
+        pitched = lambda a: a.as_strided((M, ends.Kp), (ends.Kp, 1))
+        hip.linear_fwd(pitched(x2) if ends else x2, ends.w_in if ends else w_in[:, :D], P.v("in_proj.bias"), h0.view(M, d),
+                       add_div=e, add_mod=posproj, seg=T)
+        if join_wt:
             self.br_wt.join()                         # layer 0's fused feed-forward sublayer reads the packed images
-        Bs = self.side_windows(B, T)
-        if Bs:
-            # Sampler, large batch: a 64-row panel of the fused frozen-weight launch costs what its weight stream costs,
-            # so 800 panels (B = 256, T = 200) are FOUR rounds of 256 workgroups for 3.125 rounds of work.  The windows
-            # beyond the last full round go through the whole layer stack on the per-op row-panel kernels (which spread a
-            # weight's columns over the chip) on a side branch -- forked once, joined once -- beside the full rounds.
-            Bm = B - Bs
-            hL = g("dt.hL", (B, T, self.d), dt)
-            side = self.side_layers()
-            hs = h0[Bm:]
-
-            def side_stack():
-                hh = hs
-                for i, sl in enumerate(side):
-                    hh = sl.forward(hh, P, out=hL[Bm:] if i + 1 == len(side) else None)
-            self.br_side.run(side_stack)
-            h = h0[:Bm]
-            ready = aready = False
-            for i, lp in enumerate(self.layers):
-                h = lp.forward(h, P, out=hL[:Bm] if i + 1 == len(self.layers) else None, qkv_ready=ready, attn_ready=aready)
-                ready, aready = lp.tail_done, lp.attn_tail_done
-            self.br_side.join()
-            h = hL
-        else:
-            ready = aready = False
-            for lp in self.layers:
-                h = lp.forward(h, P, qkv_ready=ready, attn_ready=aready)
-                ready, aready = lp.tail_done, lp.attn_tail_done  # it wrote the next layer's in-projection / attention output
+        h = self._stack(routes, h0, P, B, T)
         out = out if out is not None else g("dt.out", (B, T, D), dt)
-        if padded:
-            hip.linear_fwd(h.view(M, self.d), w_out_pad, b_out_pad, out.as_strided((M, Kp), (Kp, 1)))
-        elif tp:
-            self.br_wt.join()                     # the padded copies of out_proj (made beside the transposes)
-            hip.linear_fwd(h.view(M, self.d), tp["w_out"], tp["b_out"], out.as_strided((M, tp["Kp"]), (tp["Kp"], 1)))
+        if ends:
+            if not self.inference:
+                self.br_wt.join()                     # the padded copies of out_proj (made beside the transposes)
+            hip.linear_fwd(h.view(M, d), ends.w_out, ends.b_out, pitched(out))
         else:
-            hip.linear_fwd(h.view(M, self.d), P.w("out_proj.weight"), P.v("out_proj.bias"),
-                           out if out.dim() == 2 else out.view(M, D))
+            hip.linear_fwd(h.view(M, d), P.w("out_proj.weight"), P.v("out_proj.bias"), out if out.dim() == 2 else out.view(M, D))
         self.br_wt.join()
-        self.ctx = (x2, pos, h, B, T)
+        self.ctx = (x2, pos, h, B, T, ends)
         return out
 
     def ready_order(self) -> List[str]:
@@ -1702,9 +1702,8 @@ class DenoiserTransformerPlan:
         return [lp.ready_order()[-1] for lp in self.layers]
 
     def backward(self, dout3: torch.Tensor, P: ParamSource, accumulate=False):
-        x, pos, hlast, B, T = self.ctx
+        x, pos, hlast, B, T, ends = self.ctx
         M, D = x.shape
-        g, dt = self.buf.get, self.dtype
         dout = dout3 if dout3.dim() == 2 else dout3.view(M, D)
         # one GPU: every split-M slab set and every per-block partial sum of a bias / LayerNorm gradient is left for the
         # optimizer launch to add up (ib_optim_step_sources, at most 64 sources): per step this removes one reduction
@@ -1715,95 +1714,98 @@ class DenoiserTransformerPlan:
         # weight-gradient launch, beside the backward of the layers below (the optimizer is HBM traffic, those are matrix
         # work); the step's last launch then covers only the projections and the time-MLP
         early = self.early_optimizer if fuse else None
-        # (the layer whose backward runs LAST keeps the step's common source lists: its range of the flat buffers borders the
-        # projections' tail, so the step's last launch takes it along instead of following a launch of its own)
-        last_run = self.layers[0]
-        for lp in self.layers:
-            lp.defer, lp.later = ([], []) if (early and lp is not last_run) else (defer, later)
         self.pending_sources = None
+        ddp_overlap = bool(self.layers and self.layers[0].parent_flushes)
+        dh, flush_joined = self._bwd_outproj(dout, hlast.view(M, self.d), ends, B, T, P, accumulate, defer, early,
+                                             (fuse or ddp_overlap) and not TU.no_outproj_branch, ddp_overlap)
+        Ptop = ParamSource(P.w, P.v, P.g, ready=P.ready, flush=flush_joined)
+        dh, last_lag = self._bwd_layers(dh, Ptop, accumulate, defer, later, early)
+        self._bwd_tail(dh.view(M, self.d), x, pos, B, T, Ptop, accumulate, last_lag)
+        if fuse:
+            self.pending_sources = _optimizer_sources(defer, later)
+
+    def _bwd_outproj(self, dout, hlast, e, B, T, P: ParamSource, accumulate, defer, early, forked: bool, ddp_overlap: bool):
+        """the output projection: its dgrad on the main stream, its own gradients beside it (`forked`).  Returns (dh, the
+        flush of the rest of this backward)"""
+        M, d = hlast.shape
+        op_defer = [] if early else defer
+
         def t_outproj():
             # the output projection's own gradients: three launches nothing downstream waits for -- on a side stream on one
             # GPU, so the main stream goes from the loss straight to the dgrad.  With the per-layer optimizer its parameters
             # (the head of the flat buffers) are updated right here too: the step's last launch then starts behind the layers
-            op_defer = [] if early else defer
-            _wgrad(self.buf, dout, hlast.view(M, self.d), P.g("out_proj.weight"), accumulate, ws_tag="dt.wso", defer=op_defer)
-            P.ready("out_proj.weight")
-            _colsum(self.buf, "dt.bo", dout, P.g("out_proj.bias"), accumulate)
-            P.ready("out_proj.bias")
-            box_op.append(op_defer)
-        box_op: list = []
-        ddp_overlap = bool(self.layers and self.layers[0].parent_flushes)
-        outproj_pending = False
-        if (fuse or ddp_overlap) and not TU.no_outproj_branch:
+            _Grads(self.buf, P, "", "dt", accumulate, op_defer, None).wgrad(dout, hlast, "o", "out_proj.weight", "out_proj.bias")
+        pending = forked and ddp_overlap
+        if forked:
             # one GPU: joined with the tail's branches, before the optimizer.  Overlapped data parallel (round 5): joined in
             # front of the first flush (the first layer boundary), where its bucket goes out with the top layer's -- inline
             # its three launches (53 us, one of them the generic kernel for the 300-wide operand) sat on the critical path
             self.br_wt.run(t_outproj)
-            outproj_pending = ddp_overlap
         else:
             t_outproj()                               # the flush below hands this bucket to the all-reduce
-        dh = g("dt.dh", (B, T, self.d), dt)
-        tp = self._tp
-        if not (tp and dout.stride(0) == tp["Kp"] and dout.stride(1) == 1 and
-                hip.linear_dgrad_wt(dout.as_strided((M, tp["Kp"]), (tp["Kp"], 1)), tp["w_outT"], dh.view(M, self.d))):
-            hip.linear_dgrad(dout, P.w("out_proj.weight"), dh.view(M, self.d))
-        if early is not None and box_op:
+        dh = self.buf.get("dt.dh", (B, T, d), self.dtype)
+        if not (e and e.w_outT is not None and dout.stride(0) == e.Kp and dout.stride(1) == 1 and
+                hip.linear_dgrad_wt(dout.as_strided((M, e.Kp), (e.Kp, 1)), e.w_outT, dh.view(M, d))):
+            hip.linear_dgrad(dout, P.w("out_proj.weight"), dh.view(M, d))
+        if early is not None:
             # forked AGAIN from here: behind the dgrad above (which may read the weight itself) and behind the gradient
             # launches already on that branch
-            self.br_wt.run(lambda: early("out_proj.", (box_op[0], None, 0, [])))
-        Pin = P
+            self.br_wt.run(lambda: early("out_proj.", (op_defer, None, 0, [])))
 
         def flush_joined():
             """every flush of this backward: a flush may end a captured graph segment (a collective goes out between two
             segments), and a segment must end with every side stream joined -- the output projection's branch included"""
-            nonlocal outproj_pending
-            if outproj_pending:
+            nonlocal pending
+            if pending:
                 self.br_wt.join()
-                outproj_pending = False
-            Pin.flush()
-        P = ParamSource(Pin.w, Pin.v, Pin.g, ready=Pin.ready, flush=flush_joined)
-        if not outproj_pending:
-            P.flush()                                 # (pending: its bucket goes out at the first layer boundary instead)
-        prev = None                                   # (layer plan, closure, names) whose launches lag one layer
-        head = None
+                pending = False
+            P.flush()
+        if not pending:
+            flush_joined()                            # (pending: its bucket goes out at the first layer boundary instead)
+        return dh, flush_joined
+
+    def _bwd_layers(self, dh, P: ParamSource, accumulate, defer, later, early):
+        """the layers, top to bottom.  Returns (dh, the last-run layer's lagged launches or None)"""
+        prev = head = None                            # prev: (layer plan, closure, names) whose launches lag one layer
+        # (the layer whose backward runs LAST keeps the step's common source lists: its range of the flat buffers borders the
+        # projections' tail, so the step's last launch takes it along instead of following a launch of its own)
         for lp in reversed(self.layers):
+            own = early is not None and not lp.runs_last
+            l_defer, l_later = ([], []) if own else (defer, later)
             if prev is not None:
                 prev[0].branch.run(prev[1])           # beside this layer's backward
-            dh = lp.backward(dh, P, accumulate, qkv_head=head)
-            head = lp.pending_head                    # its in-projection dgrad is left to the next (lower) layer's launch
-            if early is not None and lp is not last_run:
+            dh, head, lg = lp.run_backward(dh, P, accumulate, qkv_head=head, defer=l_defer, later=l_later)
+            if own:
                 # no launch issued from here on reads this layer's weights: the dgrad the layer below computes for it goes
                 # through the PACKED image (refreshed at the head of the next step), the transposed copies likewise
-                lp.branch.run(lambda lp=lp: early(lp.p, (lp.defer, None, 0, [(0, part.shape[1], dst, None, 1.0, part, rows)
-                                                                          for part, rows, dst in lp.later])))
-            lg = lp.take_lagged()                     # None unless the layers report through this plan (data parallel)
+                lp.branch.run(lambda: early(lp.p, _optimizer_sources(l_defer, l_later)))
+            # data parallel: the layers report through this plan -- the lagged layer's bucket(s), and this layer's when it
+            # issued everything itself (small batches; the last layer)
+            issued = lg is not None and lg[0] is None
             if prev is not None:
                 prev[0].branch.join()
-                for nm in prev[2]:
-                    P.ready(nm)
-                prev = None
-                if lg is None or lg[0] is not None:
-                    P.flush()                         # the bucket(s) completed by the lagged layer
-            if lg is not None:
-                if lg[0] is None:                     # issued by the layer itself (small batches; the last layer)
-                    for nm in lg[1]:
-                        P.ready(nm)
-                    P.flush()
-                else:
-                    prev = (lp, lg[0], lg[1])
-        last_lag, Ptop = prev, P
+            for nm in (prev[2] if prev is not None else []) + (lg[1] if issued else []):
+                P.ready(nm)
+            if prev is not None or issued:
+                P.flush()
+            prev = (lp, lg[0], lg[1]) if lg is not None and not issued else None
+        return dh, prev
+
+    def _bwd_tail(self, dz0, x, pos, B: int, T: int, Ptop: ParamSource, accumulate, last_lag):
+        """the input projection's end: three chains of small launches hang off dz0 -- the time-MLP's two halves and the
+        frame-embedding gradients -- beside the one real GEMM (the input projection's weight gradient): sibling branches"""
+        D = x.shape[1]
+        g, dt = self.buf.get, self.dtype
+        P = Ptop
         if last_lag is not None:
             # the last-run layer's grouped weight-gradient launch + reduction lag too (round 5): forked HERE, beside the
-            # step's tail -- a dozen small launches on the main stream and two branches -- instead of in front of it (inline
-            # it put 130 us between the last backward launch and the tail, `profiles/r05_tr_timeline_ddp.txt`).  The tail's
-            # gradients are reported behind the layer's (the ready order is the flat layout), once everything is joined.
+            # step's tail, instead of in front of it (inline: 130 us between the last backward launch and the tail,
+            # `profiles/r05_tr_timeline_ddp.txt`).  The tail's gradients are reported behind the layer's (the ready order is
+            # the flat layout), once everything is joined.
             last_lag[0].branch.run(last_lag[1])
             tail_names: List[str] = []
             P = ParamSource(Ptop.w, Ptop.v, Ptop.g, ready=tail_names.append, flush=lambda: None)
-        dz0 = dh.view(M, self.d)
         w_in, gw_in = P.w("in_proj.weight"), P.g("in_proj.weight")
-        # tail: three chains of small launches hang off dz0 -- the time-MLP's two halves and the frame-embedding gradients
-        # -- beside the one real GEMM (the input projection's weight gradient): sibling branches
         de32 = g("dt.de32", (B, self.d), torch.float32)
         de_lp = g("dt.de_lp", (B, self.d), dt) if dt == torch.bfloat16 else None
         hip.segment_colsum(dz0, de32, seg=T, mode=0, out_bf16=de_lp)          # d e[window]
@@ -1825,10 +1827,9 @@ class DenoiserTransformerPlan:
             hip.tiny_matmul(dpp32.t(), pos, gw_in[:, D:], accumulate=accumulate)
             hip.tiny_matmul(dpp32, w_in[:, D:], gpos, accumulate=accumulate)
             P.ready("temporal_embedding.embedding.weight")
-        # (round 5: behind the time-MLP hidden layer's chain on ITS branch, not on a branch of its own: with the main stream,
-        # layer 0's weight-gradient branch and the two time-MLP branches the tail already has four concurrent branches, a
-        # captured graph runs four at a time, and the fifth -- three small launches -- only started when another had
-        # finished: alone at the end of the step, `profiles/r05_tr_timeline.txt`)
+        # (round 5: behind the time-MLP hidden layer's chain on ITS branch: with the main stream, layer 0's weight-gradient
+        # branch and the two time-MLP branches the tail already has four concurrent branches, a captured graph runs four at a
+        # time, and a fifth only started when another had finished: alone at the end of the step, `profiles/r05_tr_timeline.txt`)
         (self.br_pos if TU.pos_own_branch else self.br_thid).run(t_pos)
         _wgrad(self.buf, dz0, x, gw_in[:, :D], accumulate)
         self.br_time.join(); self.br_thid.join(); self.br_pos.join(); self.br_wt.join()
@@ -1836,10 +1837,6 @@ class DenoiserTransformerPlan:
         for lp in self.layers:
             lp.branch.join()
         if last_lag is not None:
-            P = Ptop
             for nm in last_lag[2] + tail_names:
-                P.ready(nm)
-        P.flush()
-        if fuse:
-            self.pending_sources = (defer, None, 0, [(0, part.shape[1], dst, None, 1.0, part, rows)
-                                                     for part, rows, dst in later])
+                Ptop.ready(nm)
+        Ptop.flush()
