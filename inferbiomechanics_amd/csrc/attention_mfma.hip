@@ -17,18 +17,16 @@
 //   ever leaves registers).  D[q] = sum_key P dP is summed in phase 1 from the row's P and dP registers (fp32) and
 //   passed to phase 2 through LDS; the saved output O is not read.
 //
-// Lane maps used (same as gemm.hip, verified on hardware by tests/test_hip_kernels.py::test_tr16...):
+// Lane maps used (the transposing read: wave_prims.h; verified on hardware by tests/test_hip_kernels.py::test_tr16...):
 //   mfma(A, B, C): A[row = lane%16][k = 8*(lane/16)+j], B[k = 8*(lane/16)+j][col = lane%16],
 //   D[row = 4*(lane/16)+r][col = lane%16].
-#include "ib_common.h"
+#include "wave_prims.h"
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
 
 constexpr int LDR = 72;  // bf16 elements per LDS row (64 + 8 pad): 144 B
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
 
 __device__ __forceinline__ bf16x8_t row_frag(const bf16_t* img, int row, int ks, int lane) {
   // 8 consecutive d (k index) of one image row: A or B operand of a product that reduces over d
@@ -39,12 +37,7 @@ __device__ __forceinline__ bf16x8_t tr_frag(const bf16_t* img, int row_lo, int r
   const int qq = (lane & 15) >> 2, pp = lane & 3, g = lane >> 4;
   const bf16_t* a0 = img + (row_lo + 4 * g + qq) * LDR + dt * 16 + 4 * pp;
   const bf16_t* a1 = img + (row_hi + 4 * g + qq) * LDR + dt * 16 + 4 * pp;
-  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(a0));
-  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(a1));
-  s16x8_t v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8_t, v);
+  return lds_read_tr16(a0, a1);
 }
 // accumulator pair -> operand of the next product: element j<4 <- tile a reg j, j>=4 <- tile b reg j-4
 __device__ __forceinline__ bf16x8_t acc_frag(const f32x4_t& a, const f32x4_t& b) {
@@ -472,7 +465,6 @@ int launch_bwd(const void* qkv, const void* out, const void* dout, const float* 
               : launch_bwd2<NT, false>(qkv, out, dout, lse, dqkv, B, T, H, scale, slot, IbAttnDrop{}, s);
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; }
 
 }  // namespace
 
@@ -480,7 +472,7 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 16) =
 // Return IB_E_UNSUPPORTED when the shape / alignment is outside this kernel's domain.
 int ib_attention_fwd_mfma_bf16(const void* qkv, void* out, float* lse, int64_t B, int64_t T, int64_t H, int64_t dh,
                                const IbAttnDrop* drop, hipStream_t s) {
-  if (dh != 64 || T > 256 || !al16(qkv) || !al16(out)) return IB_E_UNSUPPORTED;
+  if (dh != 64 || T > 256 || !ib_al16({qkv, out})) return IB_E_UNSUPPORTED;
   const float scale = 0.125f;
   if (T <= 64) return launch_fwd<4>(qkv, out, lse, B, T, H, scale, 0, drop, s);
   if (T <= 128) return launch_fwd<8>(qkv, out, lse, B, T, H, scale, 1, drop, s);
@@ -490,7 +482,7 @@ int ib_attention_fwd_mfma_bf16(const void* qkv, void* out, float* lse, int64_t B
 
 int ib_attention_bwd_mfma_bf16(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                                int64_t B, int64_t T, int64_t H, int64_t dh, const IbAttnDrop* drop, hipStream_t s) {
-  if (dh != 64 || T > 256 || !al16(qkv) || !al16(out) || !al16(dout) || !al16(dqkv)) return IB_E_UNSUPPORTED;
+  if (dh != 64 || T > 256 || !ib_al16({qkv, out, dout, dqkv})) return IB_E_UNSUPPORTED;
   const float scale = 0.125f;
   if (T <= 64) return launch_bwd<4>(qkv, out, dout, lse, dqkv, B, T, H, scale, 0, drop, s);
   if (T <= 128) return launch_bwd<8>(qkv, out, dout, lse, dqkv, B, T, H, scale, 1, drop, s);

@@ -16,11 +16,10 @@
 // MFMA is issued "swapped" (a = weights, b = activations): a lane ends up with 4 consecutive output columns of one
 // row, so bias / embedding / gamma loads and every store are 8- or 16-byte pieces.
 // LayerNorm row statistics: 16-lane-group shuffles + one cross-wave exchange through LDS, fixed order (deterministic).
-#include "ib_common.h"
+#include "wave_prims.h"
 #include "../../include/ib_hip_head.h"
 #include "head_jobs.h"
 #include "time_bwd.h"
-#include "launch_geom.h"
 #include <stdlib.h>
 
 namespace {
@@ -29,7 +28,6 @@ constexpr int CH_ROWS = 64, CH_WAVES = 8, CH_THREADS = 512, CH_MAXL = 4;
 #ifdef IB_AB
 long long* g_chain_prof = nullptr;     // TIMING-ONLY, measurement builds
 #endif
-#define CH_STAMP(k) do { if (p.prof && tid == 0) p.prof[blockIdx.x * 64 + (k)] = wall_clock64(); } while (0)
 
 struct ChainParams {
   const bf16_t* x0; const bf16_t* eps; const int64_t* t;
@@ -67,13 +65,6 @@ __device__ __forceinline__ float row16_sum(float v) {
 
 // keeps per-phase index arithmetic (divisions by runtime row widths) from being computed once and spilled across phases
 __device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-// lane id recomputed at every use (2 VALU): a cached copy of threadIdx.x was spilled and its reload -- a VMEM
-// operation, retired in order -- stalled on the weight prefetch issued just before it
-__device__ __forceinline__ int lane_id_now() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
 
 // v_exp_f32 + v_rcp_f32 (1 ulp each; __frcp_rn / 1.f/x expand to the 10-instruction IEEE division sequence)
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
@@ -285,7 +276,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);     // scalar copy: thread ids for the row movers are rebuilt
-#define TIDV ((wave_s << 6) | lane_id_now())                    // from it, never kept in a (spillable) VGPR
+#define TIDV ((wave_s << 6) | lane_now())                    // from it, never kept in a (spillable) VGPR
   const int g = lane >> 4, l16 = lane & 15;
   const int r0 = blockIdx.x * p.P;
   const int D = p.D, M = p.M;
@@ -294,7 +285,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
   const int64_t* in_t = p.slots ? reinterpret_cast<const int64_t*>(p.slots[2]) : p.t;
   const int nrows = min(p.P, M - r0);                      // valid token rows of this panel
   const float invH = 1.f / (float)H;
-  CH_STAMP(0);
+  IB_STAMP(p.prof, 64, 0, tid == 0);
 
   int rowg[4]; bool valid[4];
 #pragma unroll
@@ -353,7 +344,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
     }
   }
   __syncthreads();
-  CH_STAMP(1);
+  IB_STAMP(p.prof, 64, 1, tid == 0);
 
   unsigned char* cur = buf0;
   unsigned char* nxt = buf1;
@@ -370,7 +361,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
       auto side = [&](int kb, auto) {
         if (kb == 0) er = in_piece16(esrc, p.ld_e, min(nwin, CH_NWIN), PPR, TIDV);
       };
-      chain_gemm<NTH, KBD>(p.wf[0], wave_s * NTH, cur, RS, lane_id_now(), acc, side);
+      chain_gemm<NTH, KBD>(p.wf[0], wave_s * NTH, cur, RS, lane_now(), acc, side);
     } else {
       bf16_t* hprev = p.h[i - 1] + (int64_t)r0 * H;
       auto side = [&](int kb, auto kbc) {
@@ -380,10 +371,10 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
         for (int j = 0; j < NPH; ++j)
           if (j % KB == kb) out_piece16(cur, RS, hprev, H, nrows, PPR, TIDV + j * CH_THREADS);
       };
-      chain_gemm<NTH, C::KBH>(p.wf[i], wave_s * NTH, cur, RS, lane_id_now(), acc, side);
+      chain_gemm<NTH, C::KBH>(p.wf[i], wave_s * NTH, cur, RS, lane_now(), acc, side);
     }
     if (tid < CH_NWIN * PPR) *reinterpret_cast<uint4*>(eimg + tid * 16) = er;
-    CH_STAMP(2 + 4 * i);
+    IB_STAMP(p.prof, 64, 2 + 4 * i, tid == 0);
     __syncthreads();                       // every wave is done reading `cur`: it becomes the u image; e image complete
     const int colb = wave * 16 * NTH + 4 * g;
     // u = z + bias + e (bf16) ; v = silu(u) ; one-pass row statistics (sum, sum of squares)
@@ -421,9 +412,9 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
     };
     if (estage) pass_u(IntC<1>{});
     else pass_u(IntC<0>{});
-    CH_STAMP(3 + 4 * i);
+    IB_STAMP(p.prof, 64, 3 + 4 * i, tid == 0);
     row_reduce2<4>(s1, s2, (i & 1) ? redB : redA, lane, wave, 0);
-    CH_STAMP(4 + 4 * i);
+    IB_STAMP(p.prof, 64, 4 + 4 * i, tid == 0);
 #pragma unroll
     for (int j = 0; j < NPH; ++j)          // u image complete after the barrier inside the reduction
       out_piece16(cur, RS, p.u[i] + (int64_t)r0 * H, H, nrows, PPR, TIDV + j * CH_THREADS);
@@ -456,7 +447,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
       }
     }
     __syncthreads();
-    CH_STAMP(5 + 4 * i);
+    IB_STAMP(p.prof, 64, 5 + 4 * i, tid == 0);
     unsigned char* t = cur; cur = nxt; nxt = t;
   }
 
@@ -477,8 +468,8 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
       for (int j = 0; j < KBD; ++j)
         if (j % KB == kb) re[j] = in_piece8(epsg, D, nrows, ppr, TIDV + j * CH_THREADS);
     };
-    chain_gemm<NTD, C::KBH>(p.wf[p.L], wave_s * NTD, cur, RS, lane_id_now(), acc, side);
-    CH_STAMP(2 + 4 * p.L);
+    chain_gemm<NTD, C::KBH>(p.wf[p.L], wave_s * NTD, cur, RS, lane_now(), acc, side);
+    IB_STAMP(p.prof, 64, 2 + 4 * p.L, tid == 0);
     store_rows8<KBD>(nxt, RS, ppr, TIDV, re);     // eps image; dpred overwrites it in place
     __syncthreads();
     const int colb = wave * 16 * NTD + 4 * g;
@@ -524,7 +515,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
       for (int w = 0; w < CH_WAVES; ++w) s += lossred[w];
       prow[3 * p.L * H + C::DN] = s;
     }
-    CH_STAMP(3 + 4 * p.L);
+    IB_STAMP(p.prof, 64, 3 + 4 * p.L, tid == 0);
     unsigned char* t = cur; cur = nxt; nxt = t;
   }
 
@@ -556,7 +547,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
               *reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(dpg + (int64_t)row * p.ld_dpred) + pc * 16) = v;
             }
         };
-        chain_gemm<NTH, KBD>(p.wb[p.L], wave_s * NTH, cur, RS, lane_id_now(), acc, side);
+        chain_gemm<NTH, KBD>(p.wb[p.L], wave_s * NTH, cur, RS, lane_now(), acc, side);
       } else {
         auto side = [&](int kb, auto kbc) {
           constexpr int KB = decltype(kbc)::value;
@@ -572,7 +563,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
               *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(dpg + (int64_t)row * p.ld_dpred) + pc * 8) = v;
             }
         };
-        chain_gemm<NTH, KBD>(p.wb[p.L], wave_s * NTH, cur, RS, lane_id_now(), acc, side);
+        chain_gemm<NTH, KBD>(p.wb[p.L], wave_s * NTH, cur, RS, lane_now(), acc, side);
       }
     } else {
       bf16_t* dzg = p.dz[i + 1] + (int64_t)r0 * H;
@@ -585,12 +576,12 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
             out_piece16(cur, RS, dzg, H, nrows, PPR, TIDV + j * CH_THREADS);
           }
       };
-      chain_gemm<NTH, C::KBH>(p.wb[i + 1], wave_s * NTH, cur, RS, lane_id_now(), acc, side);
+      chain_gemm<NTH, C::KBH>(p.wb[i + 1], wave_s * NTH, cur, RS, lane_now(), acc, side);
     }
-    CH_STAMP(4 + 4 * p.L + 9 * (p.L - 1 - i));
+    IB_STAMP(p.prof, 64, 4 + 4 * p.L + 9 * (p.L - 1 - i), tid == 0);
     store_rows16<NPH>(nxt, RS, PPR, TIDV, ru);
     __syncthreads();
-    CH_STAMP(5 + 4 * p.L + 9 * (p.L - 1 - i));
+    IB_STAMP(p.prof, 64, 5 + 4 * p.L + 9 * (p.L - 1 - i), tid == 0);
     const int colb = wave * 16 * NTH + 4 * g;
     float mean[4], rstd[4];
 #pragma unroll
@@ -644,9 +635,9 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
         }
       }
       __builtin_amdgcn_sched_barrier(0);    // keep the dgamma / dbeta FMAs inside their pass (hipcc deferred them with their operands spilled)
-      CH_STAMP(6 + 4 * p.L + 9 * (p.L - 1 - i) + 2 * hf);
+      IB_STAMP(p.prof, 64, 6 + 4 * p.L + 9 * (p.L - 1 - i) + 2 * hf, tid == 0);
       row_reduce2<MPH>(sa, sb, hf ? redA : redB, lane, wave, MPH * hf);
-      CH_STAMP(7 + 4 * p.L + 9 * (p.L - 1 - i) + 2 * hf);
+      IB_STAMP(p.prof, 64, 7 + 4 * p.L + 9 * (p.L - 1 - i) + 2 * hf, tid == 0);
 #pragma unroll
       for (int m2 = 0; m2 < MPH; ++m2) {
         const int mt = MPH * hf + m2;
@@ -665,7 +656,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    CH_STAMP(10 + 4 * p.L + 9 * (p.L - 1 - i));
+    IB_STAMP(p.prof, 64, 10 + 4 * p.L + 9 * (p.L - 1 - i), tid == 0);
     {
       // per-workgroup column sums dgamma | dbeta.  Scratch = the u image (`nxt`): every wave finished reading it before
       // the barrier inside the second reduction above.
@@ -679,7 +670,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
         pg[H + col] = sb_;
       }
     }
-    CH_STAMP(11 + 4 * p.L + 9 * (p.L - 1 - i));
+    IB_STAMP(p.prof, 64, 11 + 4 * p.L + 9 * (p.L - 1 - i), tid == 0);
     __syncthreads();
     {
       // dbias = column sums of the bf16 dz image (rows beyond the panel are zero), one column per thread, fixed order.
@@ -697,7 +688,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
 #pragma unroll
       for (int j = 0; j < NPH; ++j) out_piece16(cur, RS, p.dz[0] + (int64_t)r0 * H, H, nrows, PPR, TIDV + j * CH_THREADS);
     }
-    CH_STAMP(12 + 4 * p.L + 9 * (p.L - 1 - i));
+    IB_STAMP(p.prof, 64, 12 + 4 * p.L + 9 * (p.L - 1 - i), tid == 0);
   }
 }
 
@@ -784,7 +775,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-#define TIDV ((wave_s << 6) | lane_id_now())
+#define TIDV ((wave_s << 6) | lane_now())
   const int g = lane >> 4, l16 = lane & 15;
   const int r0 = blockIdx.x * p.P;
   const int D = p.D, M = p.M;
@@ -796,7 +787,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
   // row-wise ownership
   const int sub = lane / LPR, c8 = (lane % LPR) * 8;
   const int wrow = wave_s * RPW + sub;              // this lane's row of iteration 0 (wave-uniform at H = 512)
-  CH_STAMP(0);
+  IB_STAMP(p.prof, 64, 0, tid == 0);
 
   int rowg[4]; bool valid[4];
 #pragma unroll
@@ -860,7 +851,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
     }
   }
   __syncthreads();
-  CH_STAMP(1);
+  IB_STAMP(p.prof, 64, 1, tid == 0);
 
   uint4 ukeep[KEEP ? 2 : 1][NJ];
 
@@ -896,9 +887,9 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
         }
       }
     };
-    if (i == 0) chain_gemm<NTH, KBD>(p.wf[0], wave_s * NTH, imgA, RS, lane_id_now(), acc, side);
-    else chain_gemm<NTH, C::KBH>(p.wf[i], wave_s * NTH, imgA, RS, lane_id_now(), acc, side);
-    CH_STAMP(2 + 3 * i);
+    if (i == 0) chain_gemm<NTH, KBD>(p.wf[0], wave_s * NTH, imgA, RS, lane_now(), acc, side);
+    else chain_gemm<NTH, C::KBH>(p.wf[i], wave_s * NTH, imgA, RS, lane_now(), acc, side);
+    IB_STAMP(p.prof, 64, 2 + 3 * i, tid == 0);
     if (nwin == 1) {
       // column owners: u = bf16(z + bias + e) -> image B
 #pragma unroll
@@ -935,7 +926,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
       else pre(IntC<0>{});
     }
     __syncthreads();                       // u image complete; every wave is done reading image A
-    CH_STAMP(3 + 3 * i);
+    IB_STAMP(p.prof, 64, 3 + 3 * i, tid == 0);
     {
       bf16_t* ug = p.u[i];
       bf16_t* hg = p.h[i] + (int64_t)r0 * H;
@@ -994,7 +985,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
       }
     }
     __syncthreads();                       // image A = h_i complete
-    CH_STAMP(4 + 3 * i);
+    IB_STAMP(p.prof, 64, 4 + 3 * i, tid == 0);
   };
   if constexpr (KEEP) {
     fwd_layer(IntC<0>{}, 0);
@@ -1025,7 +1016,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
           const int rc = min(wave_s + CH_WAVES * j, nrows - 1);
           const bf16_t* er_ = in_eps + (int64_t)(r0 + rc) * D;
 #pragma unroll
-          for (int q = 0; q < 2; ++q) re[j][q] = *reinterpret_cast<const uint2*>(er_ + min(lane_id_now() + 64 * q, ppr - 1) * 4);
+          for (int q = 0; q < 2; ++q) re[j][q] = *reinterpret_cast<const uint2*>(er_ + min(lane_now() + 64 * q, ppr - 1) * 4);
         }
       }
 #endif
@@ -1046,8 +1037,8 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
       for (int q = 0; q < 2; ++q) re[j][q] = *reinterpret_cast<const uint2*>(er_ + min(lane + 64 * q, ppr - 1) * 4);
     }
 #endif
-    chain_gemm<NTD, C::KBH>(p.wf[p.L], wave_s * NTD, imgA, RS, lane_id_now(), acc, side);
-    CH_STAMP(2 + 3 * p.L);
+    chain_gemm<NTD, C::KBH>(p.wf[p.L], wave_s * NTD, imgA, RS, lane_now(), acc, side);
+    IB_STAMP(p.prof, 64, 2 + 3 * p.L, tid == 0);
 #pragma unroll
     for (int j = 0; j < CH_ROWS / CH_WAVES; ++j) {
       const int r = wave_s + CH_WAVES * j;
@@ -1119,7 +1110,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
         }
       }
     }
-    CH_STAMP(3 + 3 * p.L);
+    IB_STAMP(p.prof, 64, 3 + 3 * p.L, tid == 0);
   }
 
   // ---- backward of block i: dh = (dz_{i+1} or dpred) . W^T (GEMM input = image B) -> LayerNorm / SiLU backward -> dz_i
@@ -1143,9 +1134,9 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
       constexpr int KB = decltype(kbc)::value;
       if (kb == KB - 1) load8f(p.gamma[i] + c8, gm);
     };
-    if (i == p.L - 1) chain_gemm<NTH, KBD>(p.wb[p.L], wave_s * NTH, imgB, RS, lane_id_now(), acc, side);
-    else chain_gemm<NTH, C::KBH>(p.wb[i + 1], wave_s * NTH, imgB, RS, lane_id_now(), acc, side);
-    CH_STAMP(sb0);
+    if (i == p.L - 1) chain_gemm<NTH, KBD>(p.wb[p.L], wave_s * NTH, imgB, RS, lane_now(), acc, side);
+    else chain_gemm<NTH, C::KBH>(p.wb[i + 1], wave_s * NTH, imgB, RS, lane_now(), acc, side);
+    IB_STAMP(p.prof, 64, sb0, tid == 0);
     float dgam[8], dbet[8], dbs[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) { dgam[k] = 0.f; dbet[k] = 0.f; dbs[k] = 0.f; }
@@ -1160,7 +1151,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
         for (int u = 0; u < NTH; ++u)
           *reinterpret_cast<f32x4_t*>(imgA + (16 * m2 + l16) * RSX + (colb + 16 * u) * 4) = acc[2 * half + m2][u];
       __syncthreads();
-      CH_STAMP(sb0 + 1 + 2 * half);
+      IB_STAMP(p.prof, 64, sb0 + 1 + 2 * half, tid == 0);
       constexpr int G = NJH >= 2 ? 2 : 1;
 #pragma unroll
       for (int jj0 = 0; jj0 < NJH; jj0 += G) {
@@ -1217,7 +1208,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
         }
       }
       __syncthreads();                     // exchange image free again; after the second half image B = dz_i
-      CH_STAMP(sb0 + 2 + 2 * half);
+      IB_STAMP(p.prof, 64, sb0 + 2 + 2 * half, tid == 0);
     }
     {
       // dgamma | dbeta | dbias of this panel: the waves' per-lane sums over their rows, added in row-group order
@@ -1259,7 +1250,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
       }
       __syncthreads();                     // the next block's exchange writes reuse this storage
     }
-    CH_STAMP(sb0 + 5);
+    IB_STAMP(p.prof, 64, sb0 + 5, tid == 0);
   };
   if constexpr (KEEP) {
     if (p.L > 1) bwd_layer(IntC<1>{}, 1);
@@ -1429,9 +1420,9 @@ extern "C" int ib_mlp_chain_train(const void* x0, const void* eps, const int64_t
       !dz || !dpred || !partial || M <= 0 || T <= 0 || table_rows <= 0)
     return IB_E_ARG;
   if (ld_e < (int64_t)L * H || ld_e % 4 != 0 || ld_xt < D || ld_xt % 4 != 0 || ld_dpred < D || ld_dpred % 4 != 0) return IB_E_ARG;
-  auto al8 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 8) == 0; };
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
-  if (!al8(x0) || !al8(eps) || !al8(e) || !al8(xt) || !al8(dpred) || !al16(packed) || !al16(partial)) return IB_E_ARG;
+  if (!ib_aligned(x0, 8) || !ib_aligned(eps, 8) || !ib_aligned(e, 8) || !ib_aligned(xt, 8) || !ib_aligned(dpred, 8) ||
+      !ib_al16({packed, partial}))
+    return IB_E_ARG;
   if (ld_part < ib_mlp_chain_partial_width(D, H, L) || ld_part % 4 != 0) return IB_E_ARG;
   PackLayout lo;
   chain_layout(D, H, L, s, &lo);
@@ -1444,19 +1435,19 @@ extern "C" int ib_mlp_chain_train(const void* x0, const void* eps, const int64_t
   const int nwg = ib_mlp_chain_workgroups(M, &P);
   p.P = P;
   if (de_lp) {   // only meaningful when every workgroup's panel is exactly one window
-    if (P != T || M % T != 0 || ld_de < (int64_t)L * H || ld_de % 4 != 0 || !al8(de_lp)) return IB_E_ARG;
+    if (P != T || M % T != 0 || ld_de < (int64_t)L * H || ld_de % 4 != 0 || !ib_aligned(de_lp, 8)) return IB_E_ARG;
   }
   p.de_lp = (bf16_t*)de_lp; p.ld_de = ld_de;
   const bf16_t* pk = (const bf16_t*)packed;
   for (int i = 0; i <= L; ++i) {
     p.wf[i] = pk + lo.off_f[i];
     p.wb[i] = lo.off_b[i] >= 0 ? pk + lo.off_b[i] : nullptr;
-    if (!bias[i] || !al16(bias[i])) return IB_E_ARG;
+    if (!bias[i] || !ib_aligned(bias[i], 16)) return IB_E_ARG;
     p.bias[i] = bias[i];
   }
   for (int i = 0; i < L; ++i) {
     if (!gamma[i] || !beta[i] || !h[i] || !dz[i]) return IB_E_ARG;
-    if (!al16(gamma[i]) || !al16(beta[i]) || (u[i] && !al16(u[i])) || !al16(h[i]) || !al16(dz[i])) return IB_E_ARG;
+    if (!ib_al16({gamma[i], beta[i], u[i], h[i], dz[i]})) return IB_E_ARG;
     p.gamma[i] = gamma[i]; p.beta[i] = beta[i];
     p.u[i] = (bf16_t*)u[i]; p.h[i] = (bf16_t*)h[i]; p.dz[i] = (bf16_t*)dz[i];
   }
@@ -1599,8 +1590,7 @@ __global__ __launch_bounds__(CH_THREADS) void time_mlp_fwd_kernel(TimeFwdParams 
   }
   const int r0 = ((int)blockIdx.x / p.ncg) * ROWS, cg = (int)blockIdx.x % p.ncg;
   const int nrows = min(ROWS, p.B - r0);
-#define T_STAMP(k) do { if (p.prof && tid == 0) p.prof[blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
-  T_STAMP(0);
+  IB_STAMP(p.prof, 8, 0, tid == 0);
   bf16x8_t wr1[KB1][NT1], wr2[KB2][1];
   // gather: sinusoid rows (fp32 table) -> bf16 image; the first column group also writes them out (wgrad operand).
   // Thread (row group tid / (TE/4), column piece tid % (TE/4)) handles NG rows (threads beyond the rows idle).  Issue
@@ -1640,7 +1630,7 @@ __global__ __launch_bounds__(CH_THREADS) void time_mlp_fwd_kernel(TimeFwdParams 
     }
   }
   __syncthreads();
-  T_STAMP(1);
+  IB_STAMP(p.prof, 8, 1, tid == 0);
   {
     f32x4_t acc[MT][NT1];
 #pragma unroll
@@ -1674,14 +1664,14 @@ __global__ __launch_bounds__(CH_THREADS) void time_mlp_fwd_kernel(TimeFwdParams 
     }
   }
   __syncthreads();
-  T_STAMP(2);
+  IB_STAMP(p.prof, 8, 2, tid == 0);
   {
     f32x4_t acc[MT][1];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[mt][0] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const int n0 = cg * 128 + wave * 16;
     reg_gemm<1, KB2, MT>(wr2, uimg, RS2, lane, acc);
-    T_STAMP(3);
+    IB_STAMP(p.prof, 8, 3, tid == 0);
     const int col = n0 + 4 * g;
     const float4 b4 = *reinterpret_cast<const float4*>(p.b2 + col);
     const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
@@ -1693,8 +1683,7 @@ __global__ __launch_bounds__(CH_THREADS) void time_mlp_fwd_kernel(TimeFwdParams 
             pack4(acc[mt][0][0] + bb[0], acc[mt][0][1] + bb[1], acc[mt][0][2] + bb[2], acc[mt][0][3] + bb[3]);
     }
   }
-  T_STAMP(4);
-#undef T_STAMP
+  IB_STAMP(p.prof, 8, 4, tid == 0);
 }
 }  // namespace
 
@@ -1714,9 +1703,7 @@ int time_fwd_launch(const float* table, int64_t table_rows, const int64_t* t, co
   if (!ib_time_mlp_fwd_supported(temb, hidden, out)) return IB_E_UNSUPPORTED;
   if (!table || !t || !w1 || !b1 || !w2 || !b2 || !s || !zu || !u || !e || B <= 0 || table_rows <= 0) return IB_E_ARG;
   if (ldw1 < temb || ldw2 < hidden || ld_e < out || ldw1 % 8 != 0 || ldw2 % 8 != 0 || ld_e % 4 != 0) return IB_E_ARG;
-  auto al = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) % a) == 0; };
-  if (!al(table, 16) || !al(w1, 16) || !al(w2, 16) || !al(b1, 16) || !al(b2, 16) || !al(s, 8) || !al(zu, 8) ||
-      !al(u, 8) || !al(e, 8))
+  if (!ib_al16({table, w1, w2, b1, b2}) || !ib_aligned(s, 8) || !ib_aligned(zu, 8) || !ib_aligned(u, 8) || !ib_aligned(e, 8))
     return IB_E_ARG;
   TimeFwdParams p{};
   p.table = table; p.table_rows = table_rows; p.t = t; p.slots = in_slots;
@@ -1840,8 +1827,7 @@ extern "C" int ib_time_mlp_bwd(const void* de, int64_t ld_de, const void* w2, in
   if (!ib_time_mlp_bwd_supported(temb, hidden, out)) return IB_E_UNSUPPORTED;
   if (!de || !w2 || !zu || !s || !dw1_slabs || !db1_slabs || B <= 0) return IB_E_ARG;
   if (ld_de < out || ldw2 < hidden || ldzu < hidden || lds < temb || ld_de % 8 || ldw2 % 8 || ldzu % 4 || lds % 8) return IB_E_ARG;
-  auto al = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) % a) == 0; };
-  if (!al(de, 16) || !al(w2, 16) || !al(zu, 8) || !al(s, 16) || !al(dw1_slabs, 16) || !al(db1_slabs, 16)) return IB_E_ARG;
+  if (!ib_al16({de, w2, s, dw1_slabs, db1_slabs}) || !ib_aligned(zu, 8)) return IB_E_ARG;
   TimeBwdParams p{(const bf16_t*)de, ld_de, (const bf16_t*)w2, ldw2, (const bf16_t*)zu, ldzu, (const bf16_t*)s, lds,
                   dw1_slabs, db1_slabs, (int)B, (int)out, (int)hidden};
   const dim3 grid((unsigned)(hidden / 16), (unsigned)ib_time_mlp_bwd_slab_count(B));

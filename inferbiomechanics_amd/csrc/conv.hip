@@ -122,7 +122,7 @@ extern "C" int ib_im2col_replicate(const void* x, void* col, int64_t ldcol, int6
                                    ib_stream_t stream) {
   if (!x || !col || N <= 0 || F <= 0 || C <= 0 || k <= 0 || (k & 1) == 0 || ldcol < C * k) return IB_E_ARG;
   if (N * F * ldcol >= (int64_t)1 << 31) return IB_E_UNSUPPORTED;
-  if (dtype == IB_BF16 && ldcol % 8 == 0 && (reinterpret_cast<uintptr_t>(col) % 16) == 0) {
+  if (dtype == IB_BF16 && ldcol % 8 == 0 && ib_aligned(col, 16)) {
     hipLaunchKernelGGL(im2col_vec8_kernel, dim3(ib_grid_1d(N * F * (ldcol / 8), 256, 256 * 16)), dim3(256), 0, ib_s(stream),
                        (const bf16_t*)x, (bf16_t*)col, (int)ldcol, (int)(N * F), (int)F, (int)C, k);
     IB_CHECK_LAUNCH();
@@ -161,7 +161,7 @@ extern "C" int ib_col2im_replicate(const void* dcol, int64_t ldcol, const void* 
 extern "C" int ib_dropout(const void* x, void* y, int64_t n, float p, uint32_t seed, int32_t step, const int32_t* step_dev,
                           int dtype, ib_stream_t stream) {
   if (!x || !y || n <= 0 || !(p >= 0.f) || !(p < 1.f)) return IB_E_ARG;
-  if (dtype == IB_BF16 && n % 8 == 0 && (reinterpret_cast<uintptr_t>(x) % 16) == 0 && (reinterpret_cast<uintptr_t>(y) % 16) == 0) {
+  if (dtype == IB_BF16 && n % 8 == 0 && ib_al16({x, y})) {
     hipLaunchKernelGGL(dropout_vec8_kernel, dim3(ib_grid_1d(n / 8, 256)), dim3(256), 0, ib_s(stream), (const bf16_t*)x,
                        (bf16_t*)y, n / 8, p, seed, step, step_dev);
     IB_CHECK_LAUNCH();

@@ -2,8 +2,7 @@
 // ffn_chain_bwd.hip: backward).  Two translation units: with both directions' <OUT, QKV> instantiations in one module hipcc
 // (ROCm 7.2) dies in its inliner's call-graph update.
 #pragma once
-#include "ib_common.h"
-#include <initializer_list>
+#include "wave_prims.h"
 #include <utility>
 
 #ifdef IB_AB
@@ -17,7 +16,6 @@ constexpr int FF_NT = 4, FF_KB = 16;                      // n-tiles per wave, k
 constexpr int FF_RS = FF_D * 2 + 16;                      // LDS row stride (bytes): +16 -> conflict-free b128 reads
 constexpr int FF_BUF = FF_ROWS * FF_RS;
 constexpr int64_t FF_WELEMS = (int64_t)FF_CHUNK * FF_D;   // elements of one packed [512 x 512] weight image
-#define FF_STAMP(k) do { if (p.prof && tid == 0) p.prof[blockIdx.x * 64 + (k)] = wall_clock64(); } while (0)
 
 template <int CTRL>
 __device__ __forceinline__ float ff_dpp_mov(float v) {
@@ -37,11 +35,6 @@ __device__ __forceinline__ float ff_row_sum(float a) {
   a = ff_dpp_bcast_add<0x142, 0xA>(a);     // row_bcast15
   a = ff_dpp_bcast_add<0x143, 0xC>(a);     // row_bcast31
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, a), 63));
-}
-__device__ __forceinline__ int ff_lane() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
 }
 __device__ __forceinline__ bf16x4_t ff_pack4(float a, float b, float c, float d) {
   bf16x4_t o;
@@ -329,7 +322,7 @@ __device__ __forceinline__ void ff_panel_out(const unsigned char* img, bf16_t* g
   }
 }
 
-#define FF_TIDV ((wave_s << 6) | ff_lane())
+#define FF_TIDV ((wave_s << 6) | lane_now())
 
 // ---- temporal self-attention INSIDE the panel launches (round 5).  With a panel = one window (P == T <= 64 frames) and
 // d = 512 = 8 heads x 64, wave w's 64 output columns of the in-projection GEMMs ARE head w: its Q, K, V (and, in the
@@ -340,8 +333,6 @@ __device__ __forceinline__ void ff_panel_out(const unsigned char* img, bf16_t* g
 // B[k][col = lane % 16], D[row = 4 (lane / 16) + r][col = lane % 16].
 constexpr int FF_HEADS = FF_D / 64;                       // = FF_WAVES: one head per wave
 constexpr float FF_ATT_SCALE = 0.125f;                    // 1 / sqrt(64)
-typedef __attribute__((address_space(3))) s16x4_t ff_lds_s16x4_t;
-typedef __attribute__((ext_vector_type(8))) short ff_s16x8_t;
 
 // accumulator pair -> operand of the next product: elements 0..3 <- tile a, 4..7 <- tile b (the reduction index of the next
 // product is permuted identically on both of its operands)
@@ -374,12 +365,7 @@ __device__ __forceinline__ bf16x8_t ff_sl_tr(const unsigned char* sl, int row_lo
   const int qq = (lane & 15) >> 2, pp = lane & 3, g = lane >> 4;
   const unsigned char* a0 = sl + (row_lo + 4 * g + qq) * FF_RS + dt * 32 + 8 * pp;
   const unsigned char* a1 = sl + (row_hi + 4 * g + qq) * FF_RS + dt * 32 + 8 * pp;
-  s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ff_lds_s16x4_t*)(a0));
-  s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ff_lds_s16x4_t*)(a1));
-  ff_s16x8_t v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-  v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8_t, v);
+  return lds_read_tr16(a0, a1);
 }
 // LDS written by some lanes of this wave, read by others: order the wave's own accesses (no workgroup barrier)
 __device__ __forceinline__ void ff_wave_sync() {
@@ -401,13 +387,6 @@ inline int ffn_geometry(int64_t M, int64_t d, int64_t ffn, int* P, int* nchunk, 
   *P = (int)rows;
   *nchunk = (int)(ffn / FF_CHUNK);
   return (int)((M + rows - 1) / rows);
-}
-
-
-inline bool ff_al16(std::initializer_list<const void*> ptrs) {
-  for (const void* q : ptrs)
-    if (reinterpret_cast<uintptr_t>(q) % 16) return false;
-  return true;
 }
 
 }  // namespace

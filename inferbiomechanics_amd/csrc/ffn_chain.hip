@@ -73,7 +73,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams)
   const int nrows = min(p.P, p.M - r0);
   const int colb = wave * 16 * FF_NT + 4 * g;             // this lane's first column inside a 512-wide GEMM output
   const int c8 = lane * 8;                                // row-wise passes: 8 consecutive columns of the wave's row
-  FF_STAMP(0);
+  IB_STAMP(p.prof, 64, 0, tid == 0);
   // ---- the panel's input rows -> image X (16-byte pieces, rows beyond the panel = copies of the last row: finite)
   ff_panel_in(p.x1 + (int64_t)r0 * FF_D, imgX, nrows, tid);
   if constexpr (OUT) {
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams)
         for (int u = 0; u < FF_NT; ++u) bo4[u] = *reinterpret_cast<const float4*>(p.bo + colb + 16 * u);
       }
     };
-    ff_gemm<FF_RING_B>(p.wop, wave_s * FF_NT, imgH, ff_lane(), acco, sideo);
+    ff_gemm<FF_RING_B>(p.wop, wave_s * FF_NT, imgH, lane_now(), acco, sideo);
     float gm1[8], bt1[8];
     ff_load8f(p.gamma1 + c8, gm1);
     ff_load8f(p.beta1 + c8, bt1);
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams)
                      p.s1 + (int64_t)r0 * FF_D, p.mean1 + r0, p.rstd1 + r0);
   }
   __syncthreads();
-  FF_STAMP(1);
+  IB_STAMP(p.prof, 64, 1, tid == 0);
 
   f32x4_t accy[4][FF_NT];
   ff_zero(accy);
@@ -126,10 +126,10 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams)
         for (int u = 0; u < FF_NT; ++u) b4[u] = *reinterpret_cast<const float4*>(p.b1 + c * FF_CHUNK + colb + 16 * u);
       }
     };
-    ff_gemm<FF_RING_A>(p.w1p + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgX, ff_lane(), acc1, side1);
-    FF_STAMP(2 + 4 * c);
+    ff_gemm<FF_RING_A>(p.w1p + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgX, lane_now(), acc1, side1);
+    IB_STAMP(p.prof, 64, 2 + 4 * c, tid == 0);
     __syncthreads();                     // every wave is past the previous chunk's second GEMM: image H may be rewritten
-    FF_STAMP(3 + 4 * c);
+    IB_STAMP(p.prof, 64, 3 + 4 * c, tid == 0);
     uint32_t mlo = 0u, mhi = 0u;
 #pragma unroll
     for (int u = 0; u < FF_NT; ++u) {
@@ -152,15 +152,15 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams)
       if (p.mask) p.mask[((int64_t)blockIdx.x * p.nchunk + c) * FF_THREADS + tid] = make_uint2(mlo, mhi);
     }
     __syncthreads();                     // image H = ReLU chunk complete
-    FF_STAMP(4 + 4 * c);
+    IB_STAMP(p.prof, 64, 4 + 4 * c, tid == 0);
     bf16_t* f1g = p.f1 + (int64_t)r0 * p.FF + c * FF_CHUNK;
     auto side2 = [&](auto, int kb) {     // the chunk's rows -> HBM: 8 pieces per thread, one per two k-blocks
       if constexpr (!INFER) {
         if ((kb & 1) == 0) ff_out_piece(imgH, f1g, p.FF, nrows, FF_TIDV + (kb >> 1) * FF_THREADS);
       }
     };
-    ff_gemm<FF_RING_B>(p.w2p + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgH, ff_lane(), accy, side2);
-    FF_STAMP(5 + 4 * c);
+    ff_gemm<FF_RING_B>(p.w2p + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgH, lane_now(), accy, side2);
+    IB_STAMP(p.prof, 64, 5 + 4 * c, tid == 0);
   }
 
   // ---- s2 = x1 + y + b2 (column owners, fp32) -> bf16 into image H -> row-wise LayerNorm
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams)
   else
     ff_ln_rows_fwd(imgH, QKV, nrows, wave_s, lane, gm, bt, p.ln_eps, p.y + (int64_t)r0 * FF_D, p.s2 + (int64_t)r0 * FF_D,
                    p.mean + r0, p.rstd + r0);
-  FF_STAMP(2 + 4 * p.nchunk);
+  IB_STAMP(p.prof, 64, 2 + 4 * p.nchunk, tid == 0);
   if constexpr (QKV) {
     // ---- the next layer's in-projection on the rows just normalised (image H = y): per 512-column chunk a GEMM, bias, bf16
     // into image X (free now), whose rows leave for qkv[:, 512 c ..] as the side job of the NEXT chunk's GEMM
@@ -215,8 +215,8 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams)
           for (int u = 0; u < FF_NT; ++u) bq[u] = *reinterpret_cast<const float4*>(p.bqkv + c * FF_CHUNK + colb + 16 * u);
         }
       };
-      ff_gemm<FF_RING_B>(p.wqkvp + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgH, ff_lane(), acq, sideq);
-      FF_STAMP(3 + 4 * p.nchunk + 2 * c);
+      ff_gemm<FF_RING_B>(p.wqkvp + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgH, lane_now(), acq, sideq);
+      IB_STAMP(p.prof, 64, 3 + 4 * p.nchunk + 2 * c, tid == 0);
       __syncthreads();                   // every wave's row pieces of the previous chunk have been read out of image X
       bf16x8_t kf[KEEP == 2 ? 4 : 1][2];
 #pragma unroll
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams)
         }
       }
       __syncthreads();                   // image X = qkv chunk c complete
-      FF_STAMP(4 + 4 * p.nchunk + 2 * c);
+      IB_STAMP(p.prof, 64, 4 + 4 * p.nchunk + 2 * c, tid == 0);
     };
     qkv_chunk(0, FfIntC<0>{}, FfIntC<ATT ? 1 : 0>{});
     qkv_chunk(1, FfIntC<1>{}, FfIntC<ATT ? 2 : 0>{});
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams)
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) ff_out_piece(imgX, qg + 2 * FF_CHUNK, 3 * FF_D, nrows, ff_fresh(tid + j * FF_THREADS));
-    FF_STAMP(9 + 4 * p.nchunk);
+    IB_STAMP(p.prof, 64, 9 + 4 * p.nchunk, tid == 0);
   }
 }
 
@@ -432,8 +432,7 @@ int ffn_pack_build(const void* const* w1, const int64_t* ld1, const void* const*
   int c = 0;
   for (int l = 0; l < layers; ++l) {
     if (!w1[l] || !w2[l] || !packed[l] || ld1[l] < d || ld2[l] < ffn || ld1[l] % 8 || ld2[l] % 8) return IB_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(w1[l]) | reinterpret_cast<uintptr_t>(w2[l]) | reinterpret_cast<uintptr_t>(packed[l])) % 16)
-      return IB_E_ARG;
+    if (!ib_al16({w1[l], w2[l], packed[l]})) return IB_E_ARG;
     const bf16_t* W1 = reinterpret_cast<const bf16_t*>(w1[l]);     // [ffn, d]
     const bf16_t* W2 = reinterpret_cast<const bf16_t*>(w2[l]);     // [d, ffn]
     bf16_t* dst = reinterpret_cast<bf16_t*>(packed[l]);
@@ -451,7 +450,7 @@ int ffn_pack_build(const void* const* w1, const int64_t* ld1, const void* const*
         if (q == 3) { e.src = W1 + (int64_t)FF_CHUNK * k * ld1[l]; e.ld = ld1[l]; e.transpose = 1; }
       }
     if (wo && wo[l]) {                   // the attention out-projection [d, d]: forward image and its transpose
-      if (!ldo || ldo[l] < d || ldo[l] % 8 || reinterpret_cast<uintptr_t>(wo[l]) % 16) return IB_E_ARG;
+      if (!ldo || ldo[l] < d || ldo[l] % 8 || !ib_aligned(wo[l], 16)) return IB_E_ARG;
       for (int q = 0; q < 2; ++q) {
         FfnPackDesc& e = pp.d[c++];
         e.src = reinterpret_cast<const bf16_t*>(wo[l]); e.ld = ldo[l]; e.transpose = q;
@@ -459,7 +458,7 @@ int ffn_pack_build(const void* const* w1, const int64_t* ld1, const void* const*
       }
     }
     if (wqkv && wqkv[l]) {               // this layer's in-projection [3 d, d]: three forward chunks, three transposed chunks
-      if (!ldq || ldq[l] < d || ldq[l] % 8 || reinterpret_cast<uintptr_t>(wqkv[l]) % 16) return IB_E_ARG;
+      if (!ldq || ldq[l] < d || ldq[l] % 8 || !ib_aligned(wqkv[l], 16)) return IB_E_ARG;
       for (int q = 0; q < 2; ++q)
         for (int k = 0; k < 3; ++k) {
           FfnPackDesc& e = pp.d[c++];
@@ -538,9 +537,9 @@ int ffn_chain_fwd_launch(const void* x1, const void* packed, const float* b1, co
   const int nwg = ffn_geometry(M, d, ffn, &P, &nc, T);
   if (!nwg) return IB_E_UNSUPPORTED;
   if (!x1 || !packed || !b1 || !b2 || !gamma || !beta || !f1 || !s2 || !y || !mean || !rstd || !mask) return IB_E_ARG;
-  if (!ff_al16({x1, packed, b1, b2, gamma, beta, f1, s2, y, mask})) return IB_E_ARG;
+  if (!ib_al16({x1, packed, b1, b2, gamma, beta, f1, s2, y, mask})) return IB_E_ARG;
   const bool out = attn != nullptr;
-  if (out && (!bo || !gamma1 || !beta1 || !s1 || !x1_out || !mean1 || !rstd1 || !ff_al16({attn, bo, gamma1, beta1, s1, x1_out})))
+  if (out && (!bo || !gamma1 || !beta1 || !s1 || !x1_out || !mean1 || !rstd1 || !ib_al16({attn, bo, gamma1, beta1, s1, x1_out})))
     return IB_E_ARG;
   const bf16_t* pk = reinterpret_cast<const bf16_t*>(packed);
   p.x1 = (const bf16_t*)x1; p.w1p = pk; p.w2p = pk + (int64_t)nc * FF_WELEMS;
@@ -549,8 +548,8 @@ int ffn_chain_fwd_launch(const void* x1, const void* packed, const float* b1, co
   p.attn = (const bf16_t*)attn; p.wop = pk + (int64_t)4 * nc * FF_WELEMS; p.bo = bo; p.gamma1 = gamma1; p.beta1 = beta1;
   p.s1 = (bf16_t*)s1; p.x1out = (bf16_t*)x1_out; p.mean1 = mean1; p.rstd1 = rstd1;
   const bool tail = qkv_next != nullptr;
-  if (tail && (!out || !packed_next || !bqkv_next || !ff_al16({packed_next, bqkv_next, qkv_next}))) return IB_E_ARG;
-  if (att && (!tail || !lse_next || T <= 0 || P != T || !ff_al16({attn_next}))) return IB_E_ARG;
+  if (tail && (!out || !packed_next || !bqkv_next || !ib_al16({packed_next, bqkv_next, qkv_next}))) return IB_E_ARG;
+  if (att && (!tail || !lse_next || T <= 0 || P != T || !ib_al16({attn_next}))) return IB_E_ARG;
   // the packed images of both layers are addressed with THIS layer's chunk count: the neighbour must have the same width
   p.wqkvp = tail ? reinterpret_cast<const bf16_t*>(packed_next) + (int64_t)(4 * nc + 2) * FF_WELEMS : nullptr;
   p.bqkv = bqkv_next; p.qkv = (bf16_t*)qkv_next;
@@ -587,9 +586,9 @@ extern "C" int ib_ffn_chain_fwd_infer(const void* x, const void* packed, const f
   const int nwg = ffn_geometry(M, d, ffn, &P, &nc);
   if (!nwg) return IB_E_UNSUPPORTED;
   if (!x || !packed || !b1 || !b2 || !gamma || !beta || !y || !attn || !bo || !gamma1 || !beta1) return IB_E_ARG;
-  if (!ff_al16({x, packed, b1, b2, gamma, beta, y, attn, bo, gamma1, beta1})) return IB_E_ARG;
+  if (!ib_al16({x, packed, b1, b2, gamma, beta, y, attn, bo, gamma1, beta1})) return IB_E_ARG;
   const bool tail = qkv_next != nullptr;
-  if (tail && (!packed_next || !bqkv_next || !ff_al16({packed_next, bqkv_next, qkv_next}))) return IB_E_ARG;
+  if (tail && (!packed_next || !bqkv_next || !ib_al16({packed_next, bqkv_next, qkv_next}))) return IB_E_ARG;
   const bf16_t* pk = reinterpret_cast<const bf16_t*>(packed);
   p.x1 = (const bf16_t*)x; p.w1p = pk; p.w2p = pk + (int64_t)nc * FF_WELEMS;
   p.b1 = b1; p.b2 = b2; p.gamma = gamma; p.beta = beta; p.y = (bf16_t*)y;

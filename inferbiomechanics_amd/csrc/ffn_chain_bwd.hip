@@ -62,7 +62,7 @@ __device__ __forceinline__ void ff_qkv_dgrad(const bf16_t* addend, const bf16_t*
       if constexpr (kb == 12) n6 = piece(6);
       if constexpr (kb == 14) n7 = piece(7);
     };
-    ff_gemm<FF_RING_BB>(wqkvtp + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgD, ff_lane(), accd, sided);
+    ff_gemm<FF_RING_BB>(wqkvtp + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgD, lane_now(), accd, sided);
     __syncthreads();                   // every wave is done reading this chunk out of image D
     if (c + 1 < 3) {
       auto put = [&](int j, const uint4& v) {
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
   const int g = lane >> 4, l16 = lane & 15;
   const int r0 = blockIdx.x * p.P;
   const int nrows = min(p.P, p.M - r0);
-  FF_STAMP(0);
+  IB_STAMP(p.prof, 64, 0, tid == 0);
   if constexpr (QKVH) {
     // ---- dy = dqkv_next . Wqkv_next + ds1_next (the NEXT layer's in-projection dgrad + its residual addend) -> image Z
     ff_qkv_dgrad(p.ds1_next + (int64_t)r0 * FF_D, p.dqkv_next + (int64_t)r0 * (3 * FF_D), p.wqkvtp, imgZ, imgD, nrows, tid,
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
   __syncthreads();                       // image Z = dz2 complete; the exchange rows are written
   ff_colsum_out(reinterpret_cast<const float*>(imgD), p.partial, 0, tid);
   __syncthreads();                       // image D is free for the first chunk
-  FF_STAMP(1);
+  IB_STAMP(p.prof, 64, 1, tid == 0);
 
   f32x4_t accx[4][FF_NT];
   ff_zero(accx);
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
     auto sideA = [&](auto, int kb) {
       if (kb == FF_KB - 1) mk = p.mask[((int64_t)blockIdx.x * p.nchunk + c) * FF_THREADS + FF_TIDV];
     };
-    ff_gemm<FF_RING_BA>(p.w2tp + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgZ, ff_lane(), acca, sideA);
+    ff_gemm<FF_RING_BA>(p.w2tp + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgZ, lane_now(), acca, sideA);
     __syncthreads();                     // every wave is past the previous chunk's second GEMM: image D may be rewritten
     const int cb = ff_colb();
 #pragma unroll
@@ -149,11 +149,11 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
     auto sideB = [&](auto, int kb) {
       if ((kb & 1) == 0) ff_out_piece(imgD, dzg, p.FF, nrows, FF_TIDV + (kb >> 1) * FF_THREADS);
     };
-    ff_gemm<FF_RING_BB>(p.w1tp + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgD, ff_lane(), accx, sideB);
+    ff_gemm<FF_RING_BB>(p.w1tp + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgD, lane_now(), accx, sideB);
   }
   // ---- dx1 = dx + dz2 (the residual path) -> image D
   __syncthreads();
-  FF_STAMP(2);
+  IB_STAMP(p.prof, 64, 2, tid == 0);
   const int cb = ff_colb();
 #pragma unroll
   for (int u = 0; u < FF_NT; ++u) {
@@ -178,14 +178,14 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
     __syncthreads();
     ff_colsum_out(reinterpret_cast<const float*>(imgD), p.partial, 2, tid);
     __syncthreads();                     // ... and is free again for the out-projection's result
-    FF_STAMP(3);
+    IB_STAMP(p.prof, 64, 3, tid == 0);
     f32x4_t acco[4][FF_NT];
     ff_zero(acco);
     // (ATT: requesting the K / Q row fragments of the head as side jobs of this phase was measured a wash -- the phase got
     // 3.1 us longer, the load step behind it 2.8 us shorter: the same bytes through the same L2 -> CU path, plus 3 spills)
     const bf16_t* qb = ATT ? p.qkv + (int64_t)r0 * (3 * FF_D) + 64 * wave_s + 8 * g : nullptr;
     auto sideo = [&](auto, int) {};
-    ff_gemm<FF_RING_BB>(p.wotp, wave_s * FF_NT, imgZ, ff_lane(), acco, sideo);
+    ff_gemm<FF_RING_BB>(p.wotp, wave_s * FF_NT, imgZ, lane_now(), acco, sideo);
     const int cb = ff_colb();
 #pragma unroll
     for (int u = 0; u < FF_NT; ++u) {
@@ -204,9 +204,9 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
       // image Z (SA) for the transposed reads.  The slices of other waves are never touched: no workgroup barrier until the
       // results meet in the images.  dQ, dK, dV stay ON CHIP: bf16 in registers until both slices are free, then dQ -> SA,
       // dK -> SB (the operands of the in-projection dgrad's first two phases), dV in registers until image Z is free again.
-      FF_STAMP(4);
+      IB_STAMP(p.prof, 64, 4, tid == 0);
       __syncthreads();                   // every wave is past the out-projection GEMM: image Z (ds1) may be overwritten
-      FF_STAMP(5);
+      IB_STAMP(p.prof, 64, 5, tid == 0);
       unsigned char* SA = imgZ + 128 * wave_s;
       unsigned char* SB = imgD + 128 * wave_s;
       bf16x8_t qf[4][2], kf[4][2], vf[4][2];
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
         for (int ks = 0; ks < 2; ++ks)
           *reinterpret_cast<bf16x8_t*>(SA + (16 * t + l16) * FF_RS + 64 * ks + 16 * g) = kf[t][ks];
       ff_wave_sync();
-      FF_STAMP(6);
+      IB_STAMP(p.prof, 64, 6, tid == 0);
       // ---------------- phase 1: dQ per 16-query tile (the lane owns query 16 it + lane % 16)
       bf16x4_t dqp[4][4], dkp[4][4], dvp[4][4];
 #pragma unroll
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
         // 124 spilled registers measured; one tile at a time fits)
         __builtin_amdgcn_sched_barrier(0);
       }
-      FF_STAMP(7);
+      IB_STAMP(p.prof, 64, 7, tid == 0);
       ff_wave_sync();                    // phase 1 is done reading K out of SA; D of every query is in LDS
 #pragma unroll
       for (int t = 0; t < 4; ++t)
@@ -334,7 +334,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      FF_STAMP(8);
+      IB_STAMP(p.prof, 64, 8, tid == 0);
       ff_wave_sync();                    // this wave is done reading Q / dO out of its slices: they take dQ / dK
       // rows (16 tile + lane % 16), columns (16 dt + 4 g ..) of the slice: the layout every GEMM epilogue writes
 #pragma unroll
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
           *reinterpret_cast<bf16x4_t*>(SB + (16 * t + l16) * FF_RS + (16 * dt + 4 * g) * 2) = dkp[t][dt];
         }
       __syncthreads();                   // image Z = dQ, image D = dK of all eight heads
-      FF_STAMP(9);
+      IB_STAMP(p.prof, 64, 9, tid == 0);
       // ---- dx = dqkv . Wqkv + ds1: the in-projection's dgrad straight from the images; the dqkv rows leave for HBM (the
       // in-projection's weight-gradient operand) as the side jobs of the phases that read them, one piece per two k-blocks
       bf16_t* dqg = p.dqkv + (int64_t)r0 * (3 * FF_D);
@@ -354,11 +354,11 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
       auto side_q = [&](auto, int kb) {
         if ((kb & 1) == 0) ff_out_piece(imgZ, dqg, 3 * FF_D, nrows, FF_TIDV + (kb >> 1) * FF_THREADS);
       };
-      ff_gemm<FF_RING_BB>(p.wqkvtp_own, wave_s * FF_NT, imgZ, ff_lane(), accd, side_q);
+      ff_gemm<FF_RING_BB>(p.wqkvtp_own, wave_s * FF_NT, imgZ, lane_now(), accd, side_q);
       auto side_k = [&](auto, int kb) {
         if ((kb & 1) == 0) ff_out_piece(imgD, dqg + FF_CHUNK, 3 * FF_D, nrows, FF_TIDV + (kb >> 1) * FF_THREADS);
       };
-      ff_gemm<FF_RING_BB>(p.wqkvtp_own + FF_WELEMS, wave_s * FF_NT, imgD, ff_lane(), accd, side_k);
+      ff_gemm<FF_RING_BB>(p.wqkvtp_own + FF_WELEMS, wave_s * FF_NT, imgD, lane_now(), accd, side_k);
       __syncthreads();                   // every wave is past both phases: the images may be rewritten
 #pragma unroll
       for (int t = 0; t < 4; ++t)
@@ -387,7 +387,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
         if constexpr (kb == 13) n6 = piece(6);
         if constexpr (kb == 15) n7 = piece(7);
       };
-      ff_gemm<FF_RING_BB>(p.wqkvtp_own + 2 * FF_WELEMS, wave_s * FF_NT, imgZ, ff_lane(), accd, side_v);
+      ff_gemm<FF_RING_BB>(p.wqkvtp_own + 2 * FF_WELEMS, wave_s * FF_NT, imgZ, lane_now(), accd, side_v);
       {
         auto put = [&](int j, const uint4& v) {           // image D is free since the barrier behind the second phase
           const int idx = tid + j * FF_THREADS;
@@ -408,9 +408,9 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
         }
       }
       __syncthreads();                   // image D = dx
-      FF_STAMP(10);
+      IB_STAMP(p.prof, 64, 10, tid == 0);
       ff_panel_out(imgD, p.dx + (int64_t)r0 * FF_D, nrows, tid);
-      FF_STAMP(11);
+      IB_STAMP(p.prof, 64, 11, tid == 0);
     }
   }
 }
@@ -431,11 +431,11 @@ int ffn_chain_bwd_launch(const void* dy, const void* s2, const float* mean, cons
   if (!nwg) return IB_E_UNSUPPORTED;
   const bool head = dqkv_next != nullptr;
   if ((!dy && !head) || !s2 || !mean || !rstd || !gamma || !packed || !mask || !ds2 || !dz1 || !partial) return IB_E_ARG;
-  if (!ff_al16({dy, s2, gamma, packed, mask, ds2, dz1, dx1, partial})) return IB_E_ARG;
+  if (!ib_al16({dy, s2, gamma, packed, mask, ds2, dz1, dx1, partial})) return IB_E_ARG;
   const bool out = s1 != nullptr;
-  if (head && (!out || !packed_next || !ds1_next || !ff_al16({packed_next, dqkv_next, ds1_next}))) return IB_E_ARG;
-  if (out ? (!mean1 || !rstd1 || !gamma1 || !ds1 || (!dattn && !att) || !ff_al16({s1, gamma1, ds1, dattn})) : !dx1) return IB_E_ARG;
-  if (att && (!out || head || !qkv || !lse || !dx || T <= 0 || P != T || !ff_al16({qkv, dqkv, dx}))) return IB_E_ARG;
+  if (head && (!out || !packed_next || !ds1_next || !ib_al16({packed_next, dqkv_next, ds1_next}))) return IB_E_ARG;
+  if (out ? (!mean1 || !rstd1 || !gamma1 || !ds1 || (!dattn && !att) || !ib_al16({s1, gamma1, ds1, dattn})) : !dx1) return IB_E_ARG;
+  if (att && (!out || head || !qkv || !lse || !dx || T <= 0 || P != T || !ib_al16({qkv, dqkv, dx}))) return IB_E_ARG;
   const bf16_t* pk = reinterpret_cast<const bf16_t*>(packed);
   p.dy = (const bf16_t*)dy; p.s2 = (const bf16_t*)s2; p.mean = mean; p.rstd = rstd; p.gamma = gamma;
   p.w2tp = pk + (int64_t)2 * nc * FF_WELEMS; p.w1tp = pk + (int64_t)3 * nc * FF_WELEMS;

@@ -18,7 +18,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "ib_common.h"
+#include "wave_prims.h"
 #include "gemm_nt.h"
 #include "time_bwd.h"
 
@@ -184,8 +184,6 @@ __device__ __forceinline__ void store_tile(unsigned char* tile, const uint4 (&r)
 // (128 rows x 144 B, or 64 k-rows x 288 B) is 18 chunks; wave w issues chunks w, w+4, ...  Each lane derives
 // WHICH global piece belongs at its LDS slot from the slot's byte offset; lanes that fall into the row padding
 // fetch a duplicate piece (the pad bytes are never read).
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
 constexpr int GLDS_CHUNKS = OPER_BYTES / 1024;   // 18
 
 template <bool KC>
@@ -213,8 +211,6 @@ __device__ __forceinline__ void glds_issue(const bf16_t* base, const int64_t (&o
   }
 }
 
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
-
 // bf16 fragment: 8 consecutive k of tile row (rbase + lane%16), k = kbase + 8*(lane/16) + j
 template <bool KC, int KCS = Tile<bf16_t>::KC_STRIDE>
 __device__ __forceinline__ bf16x8_t read_frag_bf16(const unsigned char* tile, int rbase, int kbase, int lane) {
@@ -222,18 +218,11 @@ __device__ __forceinline__ bf16x8_t read_frag_bf16(const unsigned char* tile, in
     const int off = ((rbase + (lane & 15)) * KCS + kbase + 8 * (lane >> 4)) * 2;
     return *reinterpret_cast<const bf16x8_t*>(tile + off);
   } else {
-    // [k][row] image; transposing read: lane 4q+p of a 16-lane group addresses row (k) q,
-    // columns 4p..4p+3, and receives column (lane%16) of the 4 rows.
+    // [k][row] image, transposing read (wave_prims.h): lane 4q+p of a 16-lane group addresses row (k) q, columns 4p..4p+3
     const int q = (lane & 15) >> 2, pp = lane & 3;
     const int kr = kbase + 8 * (lane >> 4) + q;
     const bf16_t* a0 = reinterpret_cast<const bf16_t*>(tile) + kr * Tile<bf16_t>::KS_STRIDE + rbase + 4 * pp;
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(a0));
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(a0 + 4 * Tile<bf16_t>::KS_STRIDE));
-    typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-    s16x8_t v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8_t, v);
+    return lds_read_tr16(a0, a0 + 4 * Tile<bf16_t>::KS_STRIDE);
   }
 }
 
@@ -275,63 +264,6 @@ __device__ __forceinline__ void compute_tile(const unsigned char* tA, const unsi
         for (int u = 0; u < 4; ++u)
           acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[u], fa[t], acc[t][u], 0, 0, 0);
     }
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ void store4(T* p, const float (&v)[4], int nv, bool vec) {
-  if (nv == 4 && vec) {
-    if constexpr (sizeof(T) == 2) {
-      bf16x4_t o;
-      o[0] = static_cast<bf16_t>(v[0]); o[1] = static_cast<bf16_t>(v[1]);
-      o[2] = static_cast<bf16_t>(v[2]); o[3] = static_cast<bf16_t>(v[3]);
-      *reinterpret_cast<bf16x4_t*>(p) = o;
-    } else {
-      *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (r < nv) p[r] = ib_from_f32<T>(v[r]);
-  }
-}
-
-// activation math with a compile-time selector.  fp32 storage (parity mode) uses the accurate libm
-// forms; bf16 storage uses the hardware exp (v_exp_f32) -- its error is far below bf16 resolution.
-template <typename T, int ACT>
-__device__ __forceinline__ float act_fwd_t(float v) {
-  if constexpr (ACT == IB_ACT_RELU) return v > 0.f ? v : 0.f;
-  else if constexpr (ACT == IB_ACT_TANH) return tanhf(v);
-  else if constexpr (ACT == IB_ACT_SIGMOID) return 1.f / (1.f + (sizeof(T) == 2 ? __expf(-v) : expf(-v)));
-  else if constexpr (ACT == IB_ACT_SILU) return v / (1.f + (sizeof(T) == 2 ? __expf(-v) : expf(-v)));
-  else if constexpr (ACT == IB_ACT_ELU) return v > 0.f ? v : (sizeof(T) == 2 ? __expf(v) : expf(v)) - 1.f;
-  else return v;
-}
-template <typename T, int ACT>
-__device__ __forceinline__ float act_bwd_t(float aux) {
-  if constexpr (ACT == IB_ACT_RELU) return aux > 0.f ? 1.f : 0.f;
-  else if constexpr (ACT == IB_ACT_TANH) return 1.f - aux * aux;
-  else if constexpr (ACT == IB_ACT_SIGMOID) return aux * (1.f - aux);
-  else if constexpr (ACT == IB_ACT_ELU) return aux > 0.f ? 1.f : aux + 1.f;
-  else if constexpr (ACT == IB_ACT_SILU) {
-    const float sg = 1.f / (1.f + (sizeof(T) == 2 ? __expf(-aux) : expf(-aux)));
-    return sg * (1.f + aux * (1.f - sg));
-  } else return 1.f;
-}
-
-template <typename T>
-__device__ __forceinline__ void load4f(const T* p, int nv, bool vec, float (&v)[4]) {
-  if (nv == 4 && vec) {
-    if constexpr (sizeof(T) == 2) {
-      bf16x4_t t = *reinterpret_cast<const bf16x4_t*>(p);
-      v[0] = (float)t[0]; v[1] = (float)t[1]; v[2] = (float)t[2]; v[3] = (float)t[3];
-    } else {
-      float4 t = *reinterpret_cast<const float4*>(p);
-      v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = (r < nv) ? ib_to_f32(p[r]) : 0.f;
   }
 }
 
@@ -428,24 +360,24 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, f32x4_t (&acc)[4][
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] += w4[r];
         }
-        if (p.Z) store4<T>(reinterpret_cast<T*>(p.Z) + (int64_t)i * p.ldz + jb, v, nv, p.vecC);
+        if (p.Z) store4<T>(reinterpret_cast<T*>(p.Z) + (int64_t)i * p.ldz + jb, nv, p.vecC, v);
         if constexpr (ACT != IB_ACT_NONE) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = act_fwd_t<T, ACT>(v[r]);
+          for (int r = 0; r < 4; ++r) v[r] = ib_act_fwd_c<ACT, sizeof(T) == 2>(v[r]);
         }
-        store4<T>(reinterpret_cast<T*>(p.C) + (int64_t)i * p.ldc + jb, v, nv, p.vecC);
+        store4<T>(reinterpret_cast<T*>(p.C) + (int64_t)i * p.ldc + jb, nv, p.vecC, v);
       } else if constexpr (EPI == EPI_DGRAD) {
         if constexpr (ACT != IB_ACT_NONE) {
           unraw4<T>(r1[t][u], w4);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] *= act_bwd_t<T, ACT>(w4[r]);
+          for (int r = 0; r < 4; ++r) v[r] *= ib_act_bwd_c<ACT, sizeof(T) == 2>(w4[r]);
         }
         if (h2) {
           unraw4<T>(r2[t][u], w4);
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] += w4[r];
         }
-        store4<T>(reinterpret_cast<T*>(p.C) + (int64_t)i * p.ldc + jb, v, nv, p.vecC);
+        store4<T>(reinterpret_cast<T*>(p.C) + (int64_t)i * p.ldc + jb, nv, p.vecC, v);
       } else {
         float* c = reinterpret_cast<float*>(p.C) + (int64_t)split_id * p.slab_stride + (int64_t)i * p.ldc + jb;
         if (p.accumulate && p.slab_stride == 0) {
@@ -453,7 +385,7 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, f32x4_t (&acc)[4][
           for (int r = 0; r < 4; ++r)
             if (r < nv) v[r] += c[r];
         }
-        store4<float>(c, v, nv, p.vecC);
+        store4<float>(c, nv, p.vecC, v);
       }
     }
   }
@@ -624,40 +556,18 @@ __device__ __forceinline__ void issue(const bf16_t* base, const int64_t (&off)[3
 }
 template <bool KC> __device__ __forceinline__ int per_wave(int wave) { return (chunks<KC>() - wave + 3) / 4; }
 
-// LDS fragment reads as inline asm: hipcc orders every LDS read it can see behind ALL outstanding LDS-DMA writes
-// (s_waitcnt vmcnt(0) before the first ds_read of the K step), which would drain the ring; reads it cannot see are
-// ordered by hand -- the counted vmcnt + barrier above them, one lgkmcnt(0) (frags_ready) below them.
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
+// LDS fragment reads as inline asm (wave_prims.h): ordered by hand -- the counted vmcnt + barrier above them, one
+// lgkmcnt(0) (frags_ready) below them
 template <bool KC>
 __device__ __forceinline__ bf16x8_t read_frag_asm(const unsigned char* tile, int rbase, int lane) {
   if (KC) {
-    const unsigned a = lds_addr(tile) + ((rbase + (lane & 15)) * KCS + 8 * (lane >> 4)) * 2;
-    u32x4_t v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(a));
-    return __builtin_bit_cast(bf16x8_t, v);
+    return lds_read16<0>(lds_off(tile) + ((rbase + (lane & 15)) * KCS + 8 * (lane >> 4)) * 2);
   } else {
     const int q = (lane & 15) >> 2, pp = lane & 3;
     const int kr = 8 * (lane >> 4) + q;
-    const unsigned a = lds_addr(tile) + (kr * Tile<bf16_t>::KS_STRIDE + rbase + 4 * pp) * 2;
-    u32x2_t lo, hi;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(a));
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(a), "n"(4 * Tile<bf16_t>::KS_STRIDE * 2));
-    u32x4_t v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
-    return __builtin_bit_cast(bf16x8_t, v);
+    return lds_read_tr<0, 4 * Tile<bf16_t>::KS_STRIDE * 2>(lds_off(tile) + (kr * Tile<bf16_t>::KS_STRIDE + rbase + 4 * pp) * 2);
   }
 }
-// the fragments are the asm's in/out operands, so no consumer can be scheduled above the wait
-__device__ __forceinline__ void frags_ready(bf16x8_t (&fa)[4], bf16x8_t (&fb)[4]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]));
-}
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void wait_vmcnt(int n) {      // n is wave-uniform, one of {0, 4, 5, 6, 8, 10, 12}
   switch (n) {
     case 0: wait_vm<0>(); break;
@@ -713,8 +623,7 @@ __device__ __forceinline__ void gemm_ring_body(const GemmParams& p, unsigned cha
     for (int e = 0; e < 8; ++e) ones[e] = (bf16_t)1.0f;
   }
 
-#define RING_STAMP(k) do { if (p.prof && tid == 0) p.prof[blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
-  RING_STAMP(0);
+  IB_STAMP(p.prof, 8, 0, tid == 0);
   int64_t oa[3], ob[3];
   offsets<A_KC>(p.lda, i0, p.M, wave, lane, oa);
   offsets<B_KC>(p.ldb, j0, p.N, wave, lane, ob);
@@ -726,11 +635,11 @@ __device__ __forceinline__ void gemm_ring_body(const GemmParams& p, unsigned cha
     issue<B_KC>(B, ob, B_KC ? (int64_t)k0 : (int64_t)k0 * p.ldb, tA + A_BYTES, wave);
   };
   for (int s = 0; s < NS - 1 && s < nk; ++s) stage(s);
-  RING_STAMP(1);
+  IB_STAMP(p.prof, 8, 1, tid == 0);
   for (int kt = 0; kt < nk; ++kt) {
     wait_vmcnt(min(nk - 1 - kt, NS - 2) * per);             // my pieces of stage kt have landed
     __builtin_amdgcn_s_barrier();                            // everyone's have; everyone finished reading stage kt-1
-    if (kt == 0) RING_STAMP(2);
+    if (kt == 0) IB_STAMP(p.prof, 8, 2, tid == 0);
     if (kt + NS - 1 < nk) stage(kt + NS - 1);
     const unsigned char* tA = smem + (kt % NS) * STAGE;
     const unsigned char* tB = tA + A_BYTES;
@@ -752,7 +661,7 @@ __device__ __forceinline__ void gemm_ring_body(const GemmParams& p, unsigned cha
       }
     }
   }
-  RING_STAMP(3);
+  IB_STAMP(p.prof, 8, 3, tid == 0);
   if constexpr (EPI == EPI_WGRAD) {
     if (do_bias && (lane >> 4) == 0) {         // every output column holds the same sum: column 0 of each row tile
 #pragma unroll
@@ -762,7 +671,7 @@ __device__ __forceinline__ void gemm_ring_body(const GemmParams& p, unsigned cha
       }
     }
     epilogue<bf16_t, EPI, IB_ACT_NONE>(p, acc, i0, j0, wi, wj, lane, split_id);
-    RING_STAMP(4);
+    IB_STAMP(p.prof, 8, 4, tid == 0);
     return;
   }
   switch (p.act) {
@@ -773,8 +682,7 @@ __device__ __forceinline__ void gemm_ring_body(const GemmParams& p, unsigned cha
     case IB_ACT_ELU: epilogue<bf16_t, EPI, IB_ACT_ELU>(p, acc, i0, j0, wi, wj, lane, split_id); break;
     default: epilogue<bf16_t, EPI, IB_ACT_NONE>(p, acc, i0, j0, wi, wj, lane, split_id); break;
   }
-  RING_STAMP(4);
-#undef RING_STAMP
+  IB_STAMP(p.prof, 8, 4, tid == 0);
 }
 
 template <bool A_KC, bool B_KC, int EPI>
@@ -823,16 +731,14 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
   }
 }
 
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 template <typename T> bool vec_load_ok(const void* p, int64_t ld) {
-  return aligned(p, 4) && ((ld * (int64_t)sizeof(T)) % 4 == 0);
+  return ib_aligned(p, 4) && ((ld * (int64_t)sizeof(T)) % 4 == 0);
 }
 template <typename T> bool glds_ok(const void* p, int64_t ld) {
-  return sizeof(T) == 2 && aligned(p, 16) && (ld % 8 == 0);
+  return sizeof(T) == 2 && ib_aligned(p, 16) && (ld % 8 == 0);
 }
 template <typename T> bool vec_store_ok(const void* p, int64_t ld) {
-  return aligned(p, 4 * sizeof(T)) && (ld % 4 == 0);
+  return ib_aligned(p, 4 * sizeof(T)) && (ld % 4 == 0);
 }
 
 // `group`: number of problems sharing the launch (ib_linear_wgrad_slabs_multi).  Each gets ~512 / group workgroups,
@@ -963,7 +869,7 @@ __global__ __launch_bounds__(256) void fwd_smallm_kernel(const bf16_t* __restric
         if (add_div) v[e] += (float)add_div[(int64_t)(gi / seg) * ld_ad + gj + e];
         if (add_mod) v[e] += (float)add_mod[(int64_t)(gi % seg) * ld_am + gj + e];
       }
-      v[e] = act_fwd_t<bf16_t, ACT>(v[e]);
+      v[e] = ib_act_fwd_c<ACT, true>(v[e]);
     }
     bf16_t* dst = y + (int64_t)gi * ldy + gj;
     if (gj + 4 <= N && vst) {
@@ -1052,7 +958,7 @@ __global__ __launch_bounds__(256) void dgrad_smallm_kernel(const bf16_t* __restr
       bf16x4_t a4;
       __builtin_memcpy(&a4, __builtin_assume_aligned(aux + (int64_t)gi * ldaux + gj, 8), 8);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] *= act_bwd_t<bf16_t, ACT>((float)a4[e]);
+      for (int e = 0; e < 4; ++e) v[e] *= ib_act_bwd_c<ACT, true>((float)a4[e]);
     }
     bf16x4_t o4;
 #pragma unroll
@@ -1071,9 +977,9 @@ inline int tile_cap() {
 inline bool dgrad_ok(const GemmParams& p) {
   static const int off = ib_ab_int("IB_NO_SMALLM", 0);
   const int64_t tiles = (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  return !off && tiles <= tile_cap() && !p.addend && p.K >= 64 && p.K <= RMAX && p.N % 16 == 0 && p.lda % 2 == 0 && aligned(p.A, 4) &&
-         p.ldb % 8 == 0 && aligned(p.B, 16) && p.ldc % 4 == 0 && aligned(p.C, 8) &&
-         (p.act == IB_ACT_NONE || (p.aux && p.ldaux % 4 == 0 && aligned(p.aux, 8)));
+  return !off && tiles <= tile_cap() && !p.addend && p.K >= 64 && p.K <= RMAX && p.N % 16 == 0 && p.lda % 2 == 0 &&
+         ib_aligned(p.A, 4) && p.ldb % 8 == 0 && ib_aligned(p.B, 16) && p.ldc % 4 == 0 && ib_aligned(p.C, 8) &&
+         (p.act == IB_ACT_NONE || (p.aux && p.ldaux % 4 == 0 && ib_aligned(p.aux, 8)));
 }
 int launch_dgrad(const GemmParams& p, hipStream_t s) {
   const dim3 grid((unsigned)(p.N / TN), (unsigned)((p.M + TM - 1) / TM)), block(256);
@@ -1097,7 +1003,7 @@ int launch_dgrad(const GemmParams& p, hipStream_t s) {
 inline bool ok(const GemmParams& p) {
   static const int off = ib_ab_int("IB_NO_SMALLM", 0);
   const int64_t tiles = (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  return !off && tiles <= tile_cap() && !p.Z && p.lda % 2 == 0 && p.ldb % 2 == 0 && aligned(p.A, 4) && aligned(p.B, 4) &&
+  return !off && tiles <= tile_cap() && !p.Z && p.lda % 2 == 0 && p.ldb % 2 == 0 && ib_aligned(p.A, 4) && ib_aligned(p.B, 4) &&
          p.K >= 64;
 }
 template <int NT>
@@ -1128,7 +1034,7 @@ int launch_fwd(GemmParams& p, hipStream_t s) {
   p.vecB = vec_load_ok<T>(p.B, p.ldb);
   p.gldsA = glds_ok<T>(p.A, p.lda); p.gldsB = glds_ok<T>(p.B, p.ldb);
   p.vecC = vec_store_ok<T>(p.C, p.ldc) && (!p.Z || vec_store_ok<T>(p.Z, p.ldz));
-  p.vecBias = !p.bias || aligned(p.bias, 16);
+  p.vecBias = !p.bias || ib_aligned(p.bias, 16);
   p.vecAdd = (!p.add_div || vec_store_ok<T>(p.add_div, p.ld_add_div)) &&
              (!p.add_mod || vec_store_ok<T>(p.add_mod, p.ld_add_mod));
   p.tiles_n = (p.N + BN - 1) / BN; p.tiles_m = (p.M + BM - 1) / BM;
@@ -1327,7 +1233,7 @@ __global__ __launch_bounds__(256) void dgrad_skinny_kernel(const bf16_t* __restr
       bf16x4_t a4;
       __builtin_memcpy(&a4, __builtin_assume_aligned(aux + (int64_t)row * ldaux + c0 + 4 * kq, 8), 8);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] *= act_bwd_t<bf16_t, ACT>((float)a4[e]);
+      for (int e = 0; e < 4; ++e) v[e] *= ib_act_bwd_c<ACT, true>((float)a4[e]);
     }
     bf16x4_t o;
 #pragma unroll
@@ -1360,8 +1266,8 @@ extern "C" int ib_linear_dgrad_skinny(const void* dz, int64_t lddz, const void* 
   if (act_below != IB_ACT_NONE && (!aux || ldaux < K)) return IB_E_ARG;
   if (act_below < IB_ACT_NONE || act_below > IB_ACT_ELU) return IB_E_ARG;
   if (dtype != IB_BF16 || M > 256 || N > skinny::NMAX || N % (32 * skinny::PD) != 0 || K % 16 != 0) return IB_E_UNSUPPORTED;
-  if (!aligned(dz, 16) || lddz % 8 != 0 || !aligned(w, 16) || ldw % 8 != 0 || !aligned(dx, 8) || lddx % 4 != 0 ||
-      (aux && (!aligned(aux, 8) || ldaux % 4 != 0)))
+  if (!ib_aligned(dz, 16) || lddz % 8 != 0 || !ib_aligned(w, 16) || ldw % 8 != 0 || !ib_aligned(dx, 8) || lddx % 4 != 0 ||
+      (aux && (!ib_aligned(aux, 8) || ldaux % 4 != 0)))
     return IB_E_UNSUPPORTED;
   const dim3 grid((unsigned)(K / 16)), block(256);
   hipStream_t s = ib_s(stream);
@@ -1418,7 +1324,7 @@ int wgrad_params(const void* dz, int64_t lddz, const void* x, int64_t ldx, float
   } else {
     p.C = dw; p.ldc = lddw; p.slab_stride = 0;
   }
-  p.vecC = aligned(p.C, 16) && (p.ldc % 4 == 0) && (p.slab_stride % 4 == 0);
+  p.vecC = ib_aligned(p.C, 16) && (p.ldc % 4 == 0) && (p.slab_stride % 4 == 0);
   if (dtype == IB_F32) {
     p.vecA = vec_load_ok<float>(p.A, p.lda); p.vecB = vec_load_ok<float>(p.B, p.ldb);
   } else {
@@ -1453,7 +1359,7 @@ int wgrad_gemm(const void* dz, int64_t lddz, const void* x, int64_t ldx, float* 
   if (split_out) *split_out = split;
   if (!slabs_only && split > 1) {
     const int64_t n = (int64_t)N * K;
-    const int rvec = (K % 4 == 0) && (lddw % 4 == 0) && aligned(workspace, 16) && aligned(dw, 16);
+    const int rvec = (K % 4 == 0) && (lddw % 4 == 0) && ib_aligned(workspace, 16) && ib_aligned(dw, 16);
     hipLaunchKernelGGL(slab_reduce_kernel, dim3(ib_grid_1d(rvec ? n / 4 : n, 256)), dim3(256), 0, s,
                        reinterpret_cast<const float*>(workspace), split, (int64_t)N * K, dw, lddw, (int)N, (int)K,
                        accumulate, rvec);
@@ -1474,16 +1380,9 @@ namespace wsmall {
 constexpr int CH = 256, PITCH = 72;       // rows per LDS chunk; image row pitch in elements (64 + 8: 144 B)
 
 __device__ __forceinline__ bf16x8_t frag_tr(const bf16_t* img, int rbase, int lane) {       // img: first row of a 32-row K step
-  using namespace ring;
   const int q = (lane & 15) >> 2, pp = lane & 3;
   const int kr = 8 * (lane >> 4) + q;
-  const unsigned a = lds_addr(img) + (kr * PITCH + rbase + 4 * pp) * 2;
-  u32x2_t lo, hi;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(a));
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(a), "n"(4 * PITCH * 2));
-  u32x4_t v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
-  return __builtin_bit_cast(bf16x8_t, v);
+  return lds_read_tr<0, 4 * PITCH * 2>(lds_off(img) + (kr * PITCH + rbase + 4 * pp) * 2);
 }
 
 __global__ __launch_bounds__(256) void wgrad_smallm_kernel(const bf16_t* __restrict__ dz, int64_t lddz,
@@ -1531,7 +1430,7 @@ __global__ __launch_bounds__(256) void wgrad_smallm_kernel(const bf16_t* __restr
       for (int t = 0; t < 2; ++t) fa[t] = frag_tr(aimg + ks * PITCH, wi * 32 + 16 * t, lane);
 #pragma unroll
       for (int u = 0; u < 2; ++u) fb[u] = frag_tr(bimg + ks * PITCH, wj * 32 + 16 * u, lane);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[0]), "+v"(fa[1]), "+v"(fb[0]), "+v"(fb[1]));
+      frags_ready(fa, fb);
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -1568,7 +1467,7 @@ inline bool ok(const void* dz, int64_t lddz, const void* x, int64_t ldx, int64_t
   static const int off = ib_ab_int("IB_NO_SMALLM", 0);
   // M <= 1024: with 2560 rows (Groundlink, F = 10) the ten serial LDS chunks per workgroup lose to the split-M kernels
   // (step 0.496 -> 0.789 ms when the limit was raised to 4096)
-  return !off && dtype == IB_BF16 && M <= 1024 && lddz % 2 == 0 && ldx % 2 == 0 && aligned(dz, 4) && aligned(x, 4);
+  return !off && dtype == IB_BF16 && M <= 1024 && lddz % 2 == 0 && ldx % 2 == 0 && ib_aligned(dz, 4) && ib_aligned(x, 4);
 }
 }  // namespace wsmall
 
@@ -1618,7 +1517,7 @@ extern "C" int ib_linear_wgrad_slabs(const void* dz, int64_t lddz, const void* x
                                      int dtype, ib_stream_t stream) {
   if (!nslab_out) return IB_E_ARG;
   if (dz && x && workspace && M > 0 && N > 0 && K > 0 && lddz >= N && ldx >= K && K % 4 == 0 &&
-      workspace_bytes >= (size_t)N * K * sizeof(float) && aligned(workspace, 16) && wsmall::ok(dz, lddz, x, ldx, M, dtype)) {
+      workspace_bytes >= (size_t)N * K * sizeof(float) && ib_aligned(workspace, 16) && wsmall::ok(dz, lddz, x, ldx, M, dtype)) {
     // short reduction: the one-pass kernel writes the whole gradient as a single "slab"
     IB_PATH(IB_PATH_WGRAD_SMALL);
     hipLaunchKernelGGL(wsmall::wgrad_smallm_kernel, dim3((unsigned)((K + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0,
@@ -1696,9 +1595,7 @@ extern "C" int ib_linear_wgrad_slabs_multi_tb(int n, const void* const* dz, cons
   if (dtype != IB_BF16 || !ib_time_mlp_bwd_supported(temb, hidden, out)) return IB_E_UNSUPPORTED;
   if (!de || !w2 || !zu || !s_rows || !dw1_slabs || !db1_slabs || B <= 0) return IB_E_ARG;
   if (ld_de < out || ldw2 < hidden || ldzu < hidden || lds < temb || ld_de % 8 || ldw2 % 8 || lds % 8) return IB_E_ARG;
-  if (!aligned(de, 16) || !aligned(w2, 16) || !aligned(zu, 2) || !aligned(s_rows, 16) || !aligned(dw1_slabs, 16) ||
-      !aligned(db1_slabs, 16))
-    return IB_E_ARG;
+  if (!ib_al16({de, w2, s_rows, dw1_slabs, db1_slabs}) || !ib_aligned(zu, 2)) return IB_E_ARG;
   TimeBwdParams tb{(const bf16_t*)de, ld_de, (const bf16_t*)w2, ldw2, (const bf16_t*)zu, ldzu, (const bf16_t*)s_rows, lds,
                    dw1_slabs, db1_slabs, (int)B, (int)out, (int)hidden};
   return ib_gemm_tn_multi(n, dz, lddz, x, ldx, workspace, workspace_bytes, nullptr, nslab_out, M, N, K, ib_s(stream), &tb,
@@ -1835,8 +1732,8 @@ extern "C" int ib_linear_ln_fwd(const void* x, int64_t ldx, const void* w, int64
   if (dtype != IB_BF16 || N % 64 != 0 || N > 1024 || K % 32 != 0) return IB_E_UNSUPPORTED;
   int chunk;
   int split = linear_ln_split(M, N, K, &chunk);
-  if (!aligned(workspace, 16) || !aligned(gamma, 16) || !aligned(beta, 16) || (bias && !aligned(bias, 16)) ||
-      !aligned(y, 8) || ldy % 4 != 0 || (res && (!aligned(res, 8) || ldres % 4 != 0)) || (a_out && !aligned(a_out, 8)))
+  if (!ib_al16({workspace, gamma, beta, bias}) || !ib_aligned(y, 8) || ldy % 4 != 0 || !ib_aligned(res, 8) ||
+      (res && ldres % 4 != 0) || !ib_aligned(a_out, 8))
     return IB_E_ARG;
   hipStream_t s = ib_s(stream);
   // a few thousand rows (the sampler at B = 16: [3200, 512, 2048]): the 256 x 128 LDS-DMA kernel in split-K form -- 52 tiles x

@@ -17,27 +17,6 @@ namespace {
 
 constexpr int FS_PD = 4;         // super-steps in flight per wave
 
-template <int ACT>
-__device__ __forceinline__ float fs_act(float v) {
-  if constexpr (ACT == IB_ACT_RELU) return v > 0.f ? v : 0.f;
-  else if constexpr (ACT == IB_ACT_TANH) return tanhf(v);
-  else if constexpr (ACT == IB_ACT_SIGMOID) return 1.f / (1.f + expf(-v));
-  else if constexpr (ACT == IB_ACT_SILU) return v / (1.f + expf(-v));
-  else if constexpr (ACT == IB_ACT_ELU) return v > 0.f ? v : expf(v) - 1.f;
-  else return v;
-}
-template <int ACT>
-__device__ __forceinline__ float fs_act_bwd(float aux) {
-  if constexpr (ACT == IB_ACT_RELU) return aux > 0.f ? 1.f : 0.f;
-  else if constexpr (ACT == IB_ACT_TANH) return 1.f - aux * aux;
-  else if constexpr (ACT == IB_ACT_SIGMOID) return aux * (1.f - aux);
-  else if constexpr (ACT == IB_ACT_ELU) return aux > 0.f ? 1.f : aux + 1.f;
-  else if constexpr (ACT == IB_ACT_SILU) {
-    const float sg = 1.f / (1.f + expf(-aux));
-    return sg * (1.f + aux * (1.f - sg));
-  } else return 1.f;
-}
-
 // y[M,N] = act(x[M,K] w[N,K]^T + bias)  (+ optional pre-activation z)
 template <int ACT>
 __global__ __launch_bounds__(256) void f32_small_fwd_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w,
@@ -86,7 +65,7 @@ __global__ __launch_bounds__(256) void f32_small_fwd_kernel(const float* __restr
         const int o = row * 16 + c4 + e;
         pre[e] = ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o];
         if (bias && gj + e < N) pre[e] += bias[gj + e];
-        v[e] = fs_act<ACT>(pre[e]);
+        v[e] = ib_act_fwd_c<ACT, false>(pre[e]);
       }
       float* dst = y + (int64_t)gi * ldy + gj;
       float* dz_ = z ? z + (int64_t)gi * ldz + gj : nullptr;
@@ -150,7 +129,7 @@ __global__ __launch_bounds__(256) void f32_small_dgrad_kernel(const float* __res
         if (gj + e < K) {
           const int o = row * 16 + c4 + e;
           float v = ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o];
-          if (ACT != IB_ACT_NONE) v *= fs_act_bwd<ACT>(aux[(int64_t)gi * ldaux + gj + e]);
+          if (ACT != IB_ACT_NONE) v *= ib_act_bwd_c<ACT, false>(aux[(int64_t)gi * ldaux + gj + e]);
           if (addend) v += addend[(int64_t)gi * ldadd + gj + e];
           dx[(int64_t)gi * lddx + gj + e] = v;
         }
@@ -213,7 +192,6 @@ __global__ __launch_bounds__(256) void f32_small_wgrad_kernel(const float* __res
   }
 }
 
-inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 // up to this many 128 x 128 tiles of the generic kernel the 16 x 16 reduction-split tiles win
 inline bool few_tiles(int64_t M, int64_t Ncols) {
   static const int off = ib_ab_int("IB_NO_F32_SMALL", 0);
@@ -225,7 +203,8 @@ inline bool few_tiles(int64_t M, int64_t Ncols) {
 // IB_E_UNSUPPORTED = nothing launched (the caller takes the generic kernel)
 int ib_f32_small_fwd_try(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, int act, float* y,
                          int64_t ldy, float* z, int64_t ldz, int64_t M, int64_t N, int64_t K, hipStream_t s) {
-  if (!few_tiles(M, N) || K < 64 || K % 2 != 0 || ldx % 2 != 0 || ldw % 2 != 0 || !al8(x) || !al8(w)) return IB_E_UNSUPPORTED;
+  if (!few_tiles(M, N) || K < 64 || K % 2 != 0 || ldx % 2 != 0 || ldw % 2 != 0 || !ib_aligned(x, 8) || !ib_aligned(w, 8))
+    return IB_E_UNSUPPORTED;
   const dim3 grid((unsigned)((N + 15) / 16), (unsigned)((M + 15) / 16)), block(256);
 #define IB_FS(ACT) hipLaunchKernelGGL((f32_small_fwd_kernel<ACT>), grid, block, 0, s, x, ldx, w, ldw, bias, y, ldy, z, ldz, (int)M, (int)N, (int)K)
   switch (act) {
@@ -245,7 +224,7 @@ int ib_f32_small_dgrad_try(const float* dz, int64_t lddz, const float* w, int64_
                            int64_t ldaux, const float* addend, int64_t ldadd, float* dx, int64_t lddx, int64_t M, int64_t N,
                            int64_t K, hipStream_t s) {
   // N = reduction length (dz columns), K = output columns
-  if (!few_tiles(M, K) || N < 64 || N % 2 != 0 || lddz % 2 != 0 || !al8(dz)) return IB_E_UNSUPPORTED;
+  if (!few_tiles(M, K) || N < 64 || N % 2 != 0 || lddz % 2 != 0 || !ib_aligned(dz, 8)) return IB_E_UNSUPPORTED;
   if (act != IB_ACT_NONE && !aux) return IB_E_UNSUPPORTED;
   const dim3 grid((unsigned)((K + 15) / 16), (unsigned)((M + 15) / 16)), block(256);
 #define IB_FS(ACT) hipLaunchKernelGGL((f32_small_dgrad_kernel<ACT>), grid, block, 0, s, dz, lddz, w, ldw, aux, ldaux, addend, ldadd, dx, lddx, (int)M, (int)N, (int)K)

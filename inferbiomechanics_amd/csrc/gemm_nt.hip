@@ -23,7 +23,7 @@
 //            backward C = (A B^T) * act'(aux) + addend       (autograd of the layer below + residual path; B = W^T here: the
 //                                                            caller keeps a transposed bf16 copy of the weight, see
 //                                                            ib_transpose_multi)
-#include "ib_common.h"
+#include "wave_prims.h"
 #include "gemm_nt.h"
 #include "head_jobs.h"
 #include <type_traits>
@@ -35,32 +35,6 @@ constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2, STAGE = A_BYTES + B_
 constexpr int LDS_BYTES = NS * STAGE;                                                       // 147456
 constexpr int CS = BN * 2 + 16;                                                             // C staging row stride (bytes)
 static_assert(BM * CS <= 2 * STAGE, "the C staging image overlays two stages");
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-
-__device__ __forceinline__ unsigned lds_off(const void* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
-template <int OFF>
-__device__ __forceinline__ bf16x8_t lds_read16(unsigned addr) {
-  u32x4_t v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-__device__ __forceinline__ void frags_ready(bf16x8_t (&fa)[4], bf16x8_t (&fb)[4]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]));
-}
-// lane id recomputed where it is needed (2 VALU): values derived from a cached threadIdx.x were spilled, and a spill
-// reload is a VMEM operation -- its s_waitcnt vmcnt(0) drains the LDS-DMA stages in flight
-__device__ __forceinline__ int lane_now() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 struct NtParams {
   const bf16_t* A; const bf16_t* B; int64_t lda, ldb;
@@ -78,30 +52,6 @@ struct NtParams {
 #ifdef IB_AB
 long long* g_nt_prof = nullptr;
 #endif
-#define NT_STAMP(k) do { if (p.prof && threadIdx.x == 0 && (k) < 16) p.prof[blockIdx.x * 16 + (k)] = wall_clock64(); } while (0)
-
-template <int ACT> __device__ __forceinline__ float nt_act(float v) {
-  if constexpr (ACT == IB_ACT_RELU) return v > 0.f ? v : 0.f;
-  else if constexpr (ACT == IB_ACT_TANH) return tanhf(v);
-  else if constexpr (ACT == IB_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
-  else if constexpr (ACT == IB_ACT_SILU) return v / (1.f + __expf(-v));
-  else if constexpr (ACT == IB_ACT_ELU) return v > 0.f ? v : __expf(v) - 1.f;
-  else return v;
-}
-template <int ACT> __device__ __forceinline__ float nt_act_bwd(float aux) {
-  if constexpr (ACT == IB_ACT_RELU) return aux > 0.f ? 1.f : 0.f;
-  else if constexpr (ACT == IB_ACT_TANH) return 1.f - aux * aux;
-  else if constexpr (ACT == IB_ACT_SIGMOID) return aux * (1.f - aux);
-  else if constexpr (ACT == IB_ACT_ELU) return aux > 0.f ? 1.f : aux + 1.f;
-  else return 1.f;
-}
-
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-template <int OFF>
-__device__ __forceinline__ void lds_write8(unsigned addr, u32x2_t v) {
-  asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
-}
-__device__ __forceinline__ void lds_drain() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void wait_vm_rt(int n) {          // n wave-uniform, one of {0, 6, 12, 14}
   if (n >= 14) wait_vm<14>();
   else if (n >= 12) wait_vm<12>();
@@ -184,7 +134,7 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_kernel(NtParams p) {
   __builtin_amdgcn_s_barrier();
   bool fresh = true;                                         // no epilogue stores are outstanding (first tile)
   int round = 0;
-  NT_STAMP(0);
+  IB_STAMP(p.prof, 16, 0, threadIdx.x == 0);
 
   for (int tile = first_tile; tile < tiles; tile += nwg) {
     const int tmn = tile % p.tiles_mn;
@@ -280,7 +230,7 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_kernel(NtParams p) {
       step(C0{}, WN{}, C0{}, nk - 1);
     }
 
-    NT_STAMP(1 + 2 * round);
+    IB_STAMP(p.prof, 16, 1 + 2 * round, threadIdx.x == 0 && 1 + 2 * round < 16);
     // ---- epilogue: the C image (two halves of 128 rows) goes through the slot of the tile's last stage -- every wave
     // left that stage at the barrier of the last step.  All LDS traffic is inline asm (LDS accesses the compiler can see
     // would be ordered behind the in-flight LDS-DMA of the next tile with s_waitcnt vmcnt(0)).
@@ -324,7 +274,7 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_kernel(NtParams p) {
             float bb[4] = {0.f, 0.f, 0.f, 0.f};
             if constexpr (HAS_BIAS) { bb[0] = b4[u].x; bb[1] = b4[u].y; bb[2] = b4[u].z; bb[3] = b4[u].w; }
 #pragma unroll
-            for (int r = 0; r < 4; ++r) o[r] = (bf16_t)nt_act<FWD_ACT>(acc[t][u][r] + bb[r]);
+            for (int r = 0; r < 4; ++r) o[r] = (bf16_t)ib_act_fwd_c<FWD_ACT, true>(acc[t][u][r] + bb[r]);
             const u32x2_t raw = __builtin_bit_cast(u32x2_t, o);
             if (t == 0) lds_write8<0 * 16 * CS + u * 32>(wbase, raw);
             else if (t == 1) lds_write8<1 * 16 * CS + u * 32>(wbase, raw);
@@ -341,7 +291,7 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_kernel(NtParams p) {
       const unsigned rbase = cimg + (unsigned)(r0 * CS + pc * 16);
       v[0] = lds_read16<0 * 32 * CS>(rbase); v[1] = lds_read16<1 * 32 * CS>(rbase);
       v[2] = lds_read16<2 * 32 * CS>(rbase); v[3] = lds_read16<3 * 32 * CS>(rbase);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
+      frags_ready(v);
       __builtin_amdgcn_s_barrier();                          // every thread has its pieces: the image may be overwritten
       bf16x8_t vout[4];
 #pragma unroll
@@ -349,7 +299,7 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_kernel(NtParams p) {
         bf16x8_t o = v[q];
         if constexpr (BWD_ACT != IB_ACT_NONE) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = (bf16_t)((float)o[e] * nt_act_bwd<BWD_ACT>((float)xaux[4 * h + q][e]));
+          for (int e = 0; e < 8; ++e) o[e] = (bf16_t)((float)o[e] * ib_act_bwd_c<BWD_ACT, true>((float)xaux[4 * h + q][e]));
         }
         if constexpr (HAS_ADD) {
 #pragma unroll
@@ -370,7 +320,7 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_kernel(NtParams p) {
       }
     }
     }   // !SLAB
-    NT_STAMP(2 + 2 * round);
+    IB_STAMP(p.prof, 16, 2 + 2 * round, threadIdx.x == 0 && 2 + 2 * round < 16);
     ++round;
     fresh = ragged;          // after a ragged tile the store count per thread is not uniform: the next wait is conservative
     if (has_next) {
@@ -382,8 +332,6 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_kernel(NtParams p) {
     }
   }
 }
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int FWD_ACT, int BWD_ACT>
 int launch(const NtParams& p, hipStream_t s) {
@@ -417,11 +365,9 @@ int ib_gemm_nt_try(const void* A, int64_t lda, const void* B, int64_t ldb, void*
   static const int off = ib_ab_int("IB_NO_NT", 0);
   static const int min_m = ib_ab_int("IB_NT_MIN_M", 640);
   if (off || M < min_m || N < 128 || N % 8 != 0 || K < 4 * BK || K % BK != 0) return IB_E_UNSUPPORTED;
-  if (!al16(A) || !al16(B) || !al16(C) || lda % 8 || ldb % 8 || ldc % 8) return IB_E_UNSUPPORTED;
+  if (!ib_al16({A, B, C, bias, aux, addend}) || lda % 8 || ldb % 8 || ldc % 8) return IB_E_UNSUPPORTED;
   if (M * lda >= (int64_t(1) << 31) || N * ldb >= (int64_t(1) << 31)) return IB_E_UNSUPPORTED;     // 32-bit element offsets
-  if (bias && !al16(bias)) return IB_E_UNSUPPORTED;
-  if (aux && (!al16(aux) || ldaux % 8)) return IB_E_UNSUPPORTED;
-  if (addend && (!al16(addend) || ldadd % 8)) return IB_E_UNSUPPORTED;
+  if ((aux && ldaux % 8) || (addend && ldadd % 8)) return IB_E_UNSUPPORTED;
   if (bwd_act != IB_ACT_NONE && (bwd_act == IB_ACT_SILU || !aux || fwd_act != IB_ACT_NONE)) return IB_E_UNSUPPORTED;
   IB_PATH(IB_PATH_NT);
   NtParams p{};
@@ -469,7 +415,7 @@ int ib_gemm_nt_splitk_splits(int64_t M, int64_t N, int64_t K) {
 int ib_gemm_nt_splitk(const void* A, int64_t lda, const void* B, int64_t ldb, float* slab, int splits, int64_t M, int64_t N,
                       int64_t K, hipStream_t s) {
   if (splits < 2 || splits != ib_gemm_nt_splitk_splits(M, N, K)) return IB_E_UNSUPPORTED;
-  if (!al16(A) || !al16(B) || !al16(slab) || lda % 8 || ldb % 8) return IB_E_UNSUPPORTED;
+  if (!ib_al16({A, B, slab}) || lda % 8 || ldb % 8) return IB_E_UNSUPPORTED;
   if (M * lda >= (int64_t(1) << 31) || N * ldb >= (int64_t(1) << 31)) return IB_E_UNSUPPORTED;
   IB_PATH(IB_PATH_NT_SPLITK);
   NtParams p{};

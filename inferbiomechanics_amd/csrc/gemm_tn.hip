@@ -21,7 +21,7 @@
 //     gradient's per-split partial sums ride along as one more MFMA per row tile against an all-ones fragment.
 #include <type_traits>
 
-#include "ib_common.h"
+#include "wave_prims.h"
 #include "gemm_nt.h"
 #include "time_bwd.h"
 
@@ -32,35 +32,6 @@ constexpr int A_ROW = TM * 2, B_ROW = TK * 2;                                  /
 constexpr int A_BYTES = BK * A_ROW, B_BYTES = BK * B_ROW, STAGE = A_BYTES + B_BYTES;      // 32768 + 16384
 constexpr int LDS_BYTES = NS * STAGE;
 constexpr int TN_MAX = 6;
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-
-__device__ __forceinline__ unsigned lds_off(const void* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
-// one MFMA fragment = rows m .. m+3 (lo) and m+4 .. m+7 (hi) of a 16-column chunk, transposed by the LDS
-template <int OFF_LO, int OFF_HI>
-__device__ __forceinline__ bf16x8_t lds_read_tr(unsigned addr) {
-  u32x2_t lo, hi;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(addr), "n"(OFF_LO));
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(addr), "n"(OFF_HI));
-  u32x4_t v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-__device__ __forceinline__ void frags_ready(bf16x8_t (&fa)[4], bf16x8_t (&fb)[4]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(fa[0]), "+v"(fa[1]), "+v"(fa[2]), "+v"(fa[3]), "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]));
-}
-__device__ __forceinline__ int lane_now() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 struct TnProblem {
   const bf16_t* A; const bf16_t* B; int lda, ldb;        // dz [M, N], x [M, K]
@@ -301,7 +272,6 @@ __global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_kernel(TnParams P) {
   }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -343,7 +313,7 @@ int ib_gemm_tn_multi(int n, const void* const* dz, const int64_t* lddz, const vo
   for (int j = 0; j < n; ++j) {
     const int sp = ib_gemm_tn_splits(M[j], N[j], K[j], n);
     if (sp <= 0) return IB_E_UNSUPPORTED;
-    if (!al16(dz[j]) || !al16(x[j]) || !al16(workspace[j]) || lddz[j] % 8 || ldx[j] % 8) return IB_E_UNSUPPORTED;
+    if (!ib_al16({dz[j], x[j], workspace[j]}) || lddz[j] % 8 || ldx[j] % 8) return IB_E_UNSUPPORTED;
     if (lddz[j] < (N[j] + 7) / 8 * 8 || ldx[j] < (K[j] + 7) / 8 * 8) return IB_E_UNSUPPORTED;
     if (M[j] * lddz[j] >= (int64_t(1) << 31) || M[j] * ldx[j] >= (int64_t(1) << 31)) return IB_E_UNSUPPORTED;
     if ((size_t)sp * (size_t)N[j] * (size_t)K[j] * sizeof(float) > workspace_bytes[j]) return IB_E_WORKSPACE;

@@ -20,7 +20,7 @@
 // No ragged tiles (the host refuses them): every address is in range by construction.
 #include <type_traits>
 
-#include "ib_common.h"
+#include "wave_prims.h"
 #include "gemm_nt.h"
 
 namespace {
@@ -32,37 +32,6 @@ constexpr int MAXP = 6;
 #ifndef TN256_ABL
 #define TN256_ABL 0      // TIMING-ONLY build variants (tools/build_variant.sh): 1 no MFMA, 2 no LDS-DMA after the prologue, 3 no fragment reads, 4 neither (four-wave form)
 #endif
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-
-__device__ __forceinline__ unsigned lds_off(const void* p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
-// one MFMA fragment = reduction rows m .. m+3 (lo) and m+4 .. m+7 (hi) of a 16-column chunk, transposed by the LDS
-__device__ __forceinline__ bf16x8_t lds_read_tr(unsigned addr) {
-  u32x2_t lo, hi;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(addr));
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(addr), "n"(4 * ROW));
-  u32x4_t v;
-  v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-__device__ __forceinline__ void frags_ready(bf16x8_t (&f)[4]) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
-}
-__device__ __forceinline__ void frags_ready(bf16x8_t (&a)[4], bf16x8_t (&b)[4]) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
-}
-__device__ __forceinline__ int lane_now() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 struct Prob {
   const bf16_t* A; const bf16_t* B; int lda, ldb;        // dz [M, N], x [M, K]
@@ -99,11 +68,11 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_tn256_kernel(Params P) {
   }
   auto read_a = [&](unsigned so, bf16x8_t (&fa)[4]) {
 #pragma unroll
-    for (int t = 0; t < 4; ++t) fa[t] = lds_read_tr((ab0 + so) ^ (unsigned)(t << 5));
+    for (int t = 0; t < 4; ++t) fa[t] = lds_read_tr<0, 4 * ROW>((ab0 + so) ^ (unsigned)(t << 5));
   };
   auto read_b = [&](unsigned so, int half, bf16x8_t (&fb)[4]) {
 #pragma unroll
-    for (int u = 0; u < 4; ++u) fb[u] = lds_read_tr((bb0 + so) ^ (unsigned)((4 * half + u) << 5));
+    for (int u = 0; u < 4; ++u) fb[u] = lds_read_tr<0, 4 * ROW>((bb0 + so) ^ (unsigned)((4 * half + u) << 5));
   };
 
   // ---- the issue side of the stage stream: (item, stage of the item) -> four LDS-DMA instructions per wave
@@ -264,11 +233,6 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_tn256_kernel(Params P) {
 // A stage's sixteen fragments are held whole (64 registers) and the NEXT stage's sixteen are read under the 64 MFMAs, so
 // the stage's slot is free from the barrier at the head of its own step: one barrier per step, at the step boundary.
 struct Frags { bf16x8_t a[8], b[8]; };
-__device__ __forceinline__ void frags_ready(Frags& f) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.a[3]), "+v"(f.a[4]), "+v"(f.a[5]), "+v"(f.a[6]), "+v"(f.a[7]),
-                 "+v"(f.b[0]), "+v"(f.b[1]), "+v"(f.b[2]), "+v"(f.b[3]), "+v"(f.b[4]), "+v"(f.b[5]), "+v"(f.b[6]), "+v"(f.b[7]));
-}
 constexpr int THREADS4 = 256;
 #ifndef TN256_NS4
 #define TN256_NS4 4
@@ -359,10 +323,10 @@ __global__ __launch_bounds__(THREADS4, 1) void gemm_tn256w4_kernel(Params P) {
     Frags f0, f1;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
-      f0.a[t] = lds_read_tr(ab0 ^ (unsigned)(t << 5));
-      f0.b[t] = lds_read_tr(bb0 ^ (unsigned)(t << 5));
+      f0.a[t] = lds_read_tr<0, 4 * ROW>(ab0 ^ (unsigned)(t << 5));
+      f0.b[t] = lds_read_tr<0, 4 * ROW>(bb0 ^ (unsigned)(t << 5));
     }
-    frags_ready(f0);
+    frags_ready(f0.a, f0.b);
 
     // step kt: the 64 MFMAs of stage kt (fragments in `cur`); under them the fragments of stage kt + 1 are read into `nxt`
     // (NEXT) and stage kt + NS is requested into the slot stage kt came from (ISSUE).  VM = LDS-DMA instructions that may
@@ -378,8 +342,8 @@ __global__ __launch_bounds__(THREADS4, 1) void gemm_tn256w4_kernel(Params P) {
       const unsigned so1 = (unsigned)(slot1 * STAGE);
       unsigned char* st = smem + slot * STAGE;
       auto read_pair = [&](int t) {
-        nxt.a[t] = lds_read_tr((ab0 + so1) ^ (unsigned)(t << 5));
-        nxt.b[t] = lds_read_tr((bb0 + so1) ^ (unsigned)(t << 5));
+        nxt.a[t] = lds_read_tr<0, 4 * ROW>((ab0 + so1) ^ (unsigned)(t << 5));
+        nxt.b[t] = lds_read_tr<0, 4 * ROW>((bb0 + so1) ^ (unsigned)(t << 5));
       };
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
@@ -411,7 +375,7 @@ __global__ __launch_bounds__(THREADS4, 1) void gemm_tn256w4_kernel(Params P) {
           }
         }
       }
-      if constexpr (NEXT) frags_ready(nxt);
+      if constexpr (NEXT) frags_ready(nxt.a, nxt.b);
       slot = slot1;
     };
     using T_ = std::true_type;
@@ -481,7 +445,6 @@ __global__ __launch_bounds__(THREADS4, 1) void gemm_tn256w4_kernel(Params P) {
   }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -523,7 +486,7 @@ int ib_gemm_tn256_multi(int n, const void* const* dz, const int64_t* lddz, const
   bool any_bias = false;
   for (int j = 0; j < n; ++j) {
     if (!dz[j] || !x[j] || !workspace[j]) return IB_E_ARG;
-    if (!al16(dz[j]) || !al16(x[j]) || !al16(workspace[j]) || lddz[j] % 8 || ldx[j] % 8) return IB_E_UNSUPPORTED;
+    if (!ib_al16({dz[j], x[j], workspace[j]}) || lddz[j] % 8 || ldx[j] % 8) return IB_E_UNSUPPORTED;
     if (lddz[j] < N[j] || ldx[j] < K[j]) return IB_E_UNSUPPORTED;
     if (M[j] * lddz[j] >= (int64_t(1) << 31) || M[j] * ldx[j] >= (int64_t(1) << 31)) return IB_E_UNSUPPORTED;
     if ((size_t)sp * (size_t)N[j] * (size_t)K[j] * sizeof(float) > workspace_bytes[j]) return IB_E_UNSUPPORTED;

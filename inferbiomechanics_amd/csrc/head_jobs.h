@@ -174,9 +174,7 @@ static inline bool tr_multi_add(TrMultiT<MAXN>& m, int i, const void* src, int64
   m.src[i] = (const bf16_t*)src; m.dst[i] = (bf16_t*)dst;
   m.rows[i] = (int)rows; m.cols[i] = (int)cols; m.lds[i] = (int)lds; m.ldd[i] = (int)ldd;
   m.blk0[i] = blk;
-  if (rows % 64 == 0 && cols % 64 == 0 && lds % 8 == 0 && ldd % 8 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(dst) & 15) == 0)
-    m.vec |= 1u << i;
+  if (rows % 64 == 0 && cols % 64 == 0 && lds % 8 == 0 && ldd % 8 == 0 && ib_al16({src, dst})) m.vec |= 1u << i;
   blk += (int)(((rows + 63) / 64) * ((cols + 63) / 64));
   return true;
 }

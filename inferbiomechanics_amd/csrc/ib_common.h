@@ -2,8 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 
 #include "../../include/ib_hip.h"
+#include "launch_geom.h"
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -38,7 +40,21 @@ static inline bool ib_ab_set(const char*) { return false; }
 #define IB_AB_PROF(ptr) (nullptr)
 #endif
 
+// In-kernel wall-clock stamp k of this workgroup into prof[gridDim.x][stride] (TIMING-ONLY, tools/*_prof.py), written by
+// the one thread for which `who` holds (the kernel's own spelling of "thread 0", plus a bound where k can run past the
+// stride).  `prof` is IB_AB_PROF(...) on the host side: null in the shipping library, where a stamp is one untaken branch.
+#define IB_STAMP(prof, stride, k, who) \
+  do { if ((prof) && (who)) (prof)[blockIdx.x * (stride) + (k)] = wall_clock64(); } while (0)
+
 static inline hipStream_t ib_s(ib_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// host-side pointer alignment checks of the launchers: ib_aligned(p, bytes) (launch_geom.h) and its 16-byte form over a
+// list.  A null pointer passes: whether an operand may be absent is each entry point's own test.
+static inline bool ib_al16(std::initializer_list<const void*> ptrs) {
+  for (const void* q : ptrs)
+    if (!ib_aligned(q, 16)) return false;
+  return true;
+}
 
 __device__ __forceinline__ float ib_to_f32(float v) { return v; }
 __device__ __forceinline__ float ib_to_f32(bf16_t v) { return static_cast<float>(v); }
@@ -69,6 +85,62 @@ __device__ __forceinline__ float ib_act_bwd(int act, float aux) {
       return s * (1.f + aux * (1.f - s));
     }
     default: return 1.f;
+  }
+}
+// The same two with a compile-time selector (the GEMM epilogues).  FAST: the hardware exp (v_exp_f32, __expf) in place of
+// libm's -- its error is far below bf16 resolution; fp32 storage (parity mode) takes FAST = false.
+template <int ACT, bool FAST>
+__device__ __forceinline__ float ib_act_fwd_c(float v) {
+  if constexpr (ACT == IB_ACT_RELU) return v > 0.f ? v : 0.f;
+  else if constexpr (ACT == IB_ACT_TANH) return tanhf(v);
+  else if constexpr (ACT == IB_ACT_SIGMOID) return 1.f / (1.f + (FAST ? __expf(-v) : expf(-v)));
+  else if constexpr (ACT == IB_ACT_SILU) return v / (1.f + (FAST ? __expf(-v) : expf(-v)));
+  else if constexpr (ACT == IB_ACT_ELU) return v > 0.f ? v : (FAST ? __expf(v) : expf(v)) - 1.f;
+  else return v;
+}
+template <int ACT, bool FAST>
+__device__ __forceinline__ float ib_act_bwd_c(float aux) {
+  if constexpr (ACT == IB_ACT_RELU) return aux > 0.f ? 1.f : 0.f;
+  else if constexpr (ACT == IB_ACT_TANH) return 1.f - aux * aux;
+  else if constexpr (ACT == IB_ACT_SIGMOID) return aux * (1.f - aux);
+  else if constexpr (ACT == IB_ACT_ELU) return aux > 0.f ? 1.f : aux + 1.f;
+  else if constexpr (ACT == IB_ACT_SILU) {
+    const float sg = 1.f / (1.f + (FAST ? __expf(-aux) : expf(-aux)));
+    return sg * (1.f + aux * (1.f - sg));
+  } else return 1.f;
+}
+
+// 4 consecutive elements of a row as fp32: one 8-byte (bf16) / 16-byte (fp32) access when all four are inside the row
+// (nv == 4) and the caller found pointer and pitch aligned (vec), else element by element (elements past nv read as 0)
+template <typename T>
+__device__ __forceinline__ void load4(const T* p, int nv, bool vec, float (&v)[4]) {
+  if (nv == 4 && vec) {
+    if constexpr (sizeof(T) == 2) {
+      bf16x4_t t = *reinterpret_cast<const bf16x4_t*>(p);
+      v[0] = (float)t[0]; v[1] = (float)t[1]; v[2] = (float)t[2]; v[3] = (float)t[3];
+    } else {
+      float4 t = *reinterpret_cast<const float4*>(p);
+      v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (e < nv) ? ib_to_f32(p[e]) : 0.f;
+  }
+}
+template <typename T>
+__device__ __forceinline__ void store4(T* p, int nv, bool vec, const float (&v)[4]) {
+  if (nv == 4 && vec) {
+    if constexpr (sizeof(T) == 2) {
+      bf16x4_t o;
+      o[0] = (bf16_t)v[0]; o[1] = (bf16_t)v[1]; o[2] = (bf16_t)v[2]; o[3] = (bf16_t)v[3];
+      *reinterpret_cast<bf16x4_t*>(p) = o;
+    } else {
+      *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e < nv) p[e] = ib_from_f32<T>(v[e]);
   }
 }
 

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(FF_THREADS) void linln_panel_kernel(LinLnPanelParam
   const int nrows = min(p.P, p.M - r0);
   const int colb = wave * 16 * FF_NT + 4 * g;
   // ---- the weight ring's first two k-blocks are requested ahead of the rows (nothing else is in flight yet)
-  const bf16x8_t* wl = reinterpret_cast<const bf16x8_t*>(p.wp) + (int64_t)(wave_s * FF_NT) * 64 + ff_lane();
+  const bf16x8_t* wl = reinterpret_cast<const bf16x8_t*>(p.wp) + (int64_t)(wave_s * FF_NT) * 64 + lane_now();
   bf16x8_t wr[3][FF_NT];
 #pragma unroll
   for (int s = 0; s < 2; ++s)
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(FF_THREADS) void linear_panel_kernel(LinPanelParams
   // column tiles of this wave inside chunk c: NTW consecutive ones from nt0; its first output column inside the chunk
   const int nt0 = (32 / SUBS) * sb + NTW * wave_s;
   const int col0 = 16 * ((32 / SUBS) * sb + NTW * wave) + 4 * g;
-  const bf16x8_t* wl = reinterpret_cast<const bf16x8_t*>(p.wp + (int64_t)c * FF_WELEMS) + (int64_t)nt0 * 64 + ff_lane();
+  const bf16x8_t* wl = reinterpret_cast<const bf16x8_t*>(p.wp + (int64_t)c * FF_WELEMS) + (int64_t)nt0 * 64 + lane_now();
   bf16x8_t wr[3][NTW];
 #pragma unroll
   for (int s = 0; s < 2; ++s)
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_coop_kernel(FfnCoopParams p) {
         for (int u = 0; u < FF_NT; ++u) b4[u] = *reinterpret_cast<const float4*>(p.b1 + c * FF_CHUNK + colb + 16 * u);
       }
     };
-    ff_gemm<FF_RING_A>(p.w1p + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgX, ff_lane(), acc1, side1);
+    ff_gemm<FF_RING_A>(p.w1p + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgX, lane_now(), acc1, side1);
 #pragma unroll
     for (int u = 0; u < FF_NT; ++u) {
       const float bb[4] = {b4[u].x, b4[u].y, b4[u].z, b4[u].w};
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_coop_kernel(FfnCoopParams p) {
     f32x4_t accy[4][FF_NT];
     ff_zero(accy);
     auto side2 = [&](auto, int) {};
-    ff_gemm<FF_RING_B>(p.w2p + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgH, ff_lane(), accy, side2);
+    ff_gemm<FF_RING_B>(p.w2p + (int64_t)c * FF_WELEMS, wave_s * FF_NT, imgH, lane_now(), accy, side2);
     float* pc = p.part + ((int64_t)c * p.M + r0) * FF_D;
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_coop_small_kernel(FfnCoopParam
     }
   }
   __syncthreads();
-  const int ln = ff_lane();
+  const int ln = lane_now();
   {
     // hidden columns HC * sb + 16 * NT1 * wave ... of chunk c: column tiles nt = (HC / 16) * sb + NT1 * wave + u
     f32x4_t acc1[1][NT1];
@@ -484,9 +484,7 @@ extern "C" int ib_linear_ln_panel_fwd(const void* x, int64_t ldx, const void* w_
   const int nwg = ib_linear_ln_panel_workgroups(M, N, K, &P);
   if (!nwg) return IB_E_UNSUPPORTED;
   if (ldx < K || ldy < N || (res && ldres < N) || ldx % 8 != 0 || ldy % 8 != 0 || (res && ldres % 4 != 0)) return IB_E_ARG;
-  if (!ff_al16({x, w_packed, gamma, beta, y}) || (bias && !ff_al16({bias})) ||
-      (res && (reinterpret_cast<uintptr_t>(res) % 8) != 0))
-    return IB_E_ARG;
+  if (!ib_al16({x, w_packed, gamma, beta, y, bias}) || !ib_aligned(res, 8)) return IB_E_ARG;
   LinLnPanelParams p{};
   p.x = (const bf16_t*)x; p.ldx = ldx; p.wp = (const bf16_t*)w_packed; p.bias = bias;
   p.res = (const bf16_t*)res; p.ldres = ldres; p.gamma = gamma; p.beta = beta; p.y = (bf16_t*)y; p.ldy = ldy;
@@ -522,7 +520,7 @@ extern "C" int ib_ffn_infer_fwd(const void* x1, const void* packed, const float*
   const int panels = ffn_coop_geometry(M, d, ffn, &P, &nc, &sb);
   if (!panels) return IB_E_UNSUPPORTED;
   if (workspace_bytes < ib_ffn_infer_workspace(M, d, ffn)) return IB_E_WORKSPACE;
-  if (!ff_al16({x1, packed, b1, b2, gamma, beta, y, workspace})) return IB_E_ARG;
+  if (!ib_al16({x1, packed, b1, b2, gamma, beta, y, workspace})) return IB_E_ARG;
   FfnCoopParams p{};
   const bf16_t* pk = reinterpret_cast<const bf16_t*>(packed);
   p.x1 = (const bf16_t*)x1; p.w1p = pk; p.w2p = pk + (int64_t)nc * FF_WELEMS;
@@ -552,7 +550,7 @@ extern "C" int ib_linear_panel_fwd(const void* x, int64_t ldx, const void* w_pac
   const int panels = lin_panel_geometry(M, chunks, &P, &subs);
   if (!panels) return IB_E_UNSUPPORTED;
   if (ldx < K || ldy < N || ldx % 8 != 0 || ldy % 4 != 0) return IB_E_ARG;
-  if (!ff_al16({x, w_packed}) || (bias && !ff_al16({bias})) || (reinterpret_cast<uintptr_t>(y) % 8) != 0) return IB_E_ARG;
+  if (!ib_al16({x, w_packed, bias}) || !ib_aligned(y, 8)) return IB_E_ARG;
   LinPanelParams p{};
   p.x = (const bf16_t*)x; p.ldx = ldx; p.wp = (const bf16_t*)w_packed; p.bias = bias; p.y = (bf16_t*)y; p.ldy = ldy;
   p.M = (int)M; p.P = P; p.chunks = chunks;

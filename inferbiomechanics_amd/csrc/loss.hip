@@ -398,8 +398,8 @@ extern "C" int ib_mse_loss_partial(const void* pred, int64_t ld_pred, const void
   hipStream_t s = ib_s(stream);
   const float gscale = 2.f / (float)n;
   const int es = dtype == IB_BF16 ? 2 : 4;
-  auto al = [&](const void* q) { return !q || (reinterpret_cast<uintptr_t>(q) % (4 * es)) == 0; };
-  const bool v4 = (cols % 4 == 0) && (ld_pred % 4 == 0) && (!dpred || ld_dpred % 4 == 0) && al(pred) && al(target) && al(dpred);
+  const bool v4 = (cols % 4 == 0) && (ld_pred % 4 == 0) && (!dpred || ld_dpred % 4 == 0) && ib_aligned(pred, 4 * es) &&
+                  ib_aligned(target, 4 * es) && ib_aligned(dpred, 4 * es);
   if (dtype == IB_F32) {
     if (v4) hipLaunchKernelGGL((mse_partial_kernel<float, 4>), dim3(parts), dim3(256), 0, s, (const float*)pred, ld_pred, (const float*)target, (float*)dpred, ld_dpred, partial, rows, cols, gscale);
     else hipLaunchKernelGGL((mse_partial_kernel<float, 1>), dim3(parts), dim3(256), 0, s, (const float*)pred, ld_pred, (const float*)target, (float*)dpred, ld_dpred, partial, rows, cols, gscale);
@@ -436,8 +436,8 @@ extern "C" int ib_mse_loss_partial_cond(const void* pred, int64_t ld_pred, const
   hipStream_t s = ib_s(stream);
   const float gscale = 2.f / (float)(rows * (cols - cond_cols));
   const int es = dtype == IB_BF16 ? 2 : 4;
-  auto al = [&](const void* q) { return !q || (reinterpret_cast<uintptr_t>(q) % (4 * es)) == 0; };
-  const bool v4 = (cols % 4 == 0) && (ld_pred % 4 == 0) && (!dpred || ld_dpred % 4 == 0) && al(pred) && al(target) && al(dpred);
+  const bool v4 = (cols % 4 == 0) && (ld_pred % 4 == 0) && (!dpred || ld_dpred % 4 == 0) && ib_aligned(pred, 4 * es) &&
+                  ib_aligned(target, 4 * es) && ib_aligned(dpred, 4 * es);
 #define IB_MSE_COND(TY, V)                                                                                                    \
   hipLaunchKernelGGL((mse_partial_cond_kernel<TY, V>), dim3(parts), dim3(256), 0, s, (const TY*)pred, ld_pred,                \
                      (const TY*)target, (TY*)dpred, ld_dpred, partial, rows, cols, cond_cols, gscale)

@@ -107,9 +107,7 @@ extern "C" int ib_diffusion_draw(const void* table, int64_t table_rows, int64_t 
   if (t_out && num_train_steps <= 0) return IB_E_ARG;
   if (dtype != IB_F32 && dtype != IB_BF16) return IB_E_DTYPE;
   if (B * ((per + 3) / 4 + 1) >= (int64_t)1 << 32) return IB_E_UNSUPPORTED;     // block index is one 32-bit counter word
-  const uintptr_t align = reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(x0_out) |
-                          reinterpret_cast<uintptr_t>(eps_out);
-  const bool vec = per % 8 == 0 && align % 16 == 0;
+  const bool vec = per % 8 == 0 && ib_al16({table, x0_out, eps_out});
   Draw p{table, table_rows, row_pitch, idx, x0_out, eps_out, t_out, B, per,
          (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), stream_id, step, step_dev, num_train_steps};
   const dim3 grid(ib_grid_1d(B * ((per + 7) / 8), 256, 256 * 16)), block(256);
@@ -128,7 +126,7 @@ extern "C" int ib_diffusion_draw(const void* table, int64_t table_rows, int64_t 
 
 extern "C" int ib_philox_words(uint32_t* out, int64_t blocks, uint64_t seed, uint32_t step, uint32_t stream_id,
                                uint32_t domain, ib_stream_t stream) {
-  if (!out || blocks <= 0 || blocks >= (int64_t)1 << 32 || (reinterpret_cast<uintptr_t>(out) % 16)) return IB_E_ARG;
+  if (!out || blocks <= 0 || blocks >= (int64_t)1 << 32 || !ib_aligned(out, 16)) return IB_E_ARG;
   hipLaunchKernelGGL(philox_words_kernel, dim3(ib_grid_1d(blocks, 256)), dim3(256), 0, ib_s(stream), out, blocks,
                      (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), step, stream_id, domain);
   IB_CHECK_LAUNCH();

@@ -308,10 +308,7 @@ int optim_plain(int opt, float* p, const float* g, float* s1, float* s2, int64_t
   const bool need1 = opt != IB_OPT_SGD;
   const bool need2 = (opt == IB_OPT_ADAM || opt == IB_OPT_ADADELTA || opt == IB_OPT_ADAMAX);
   if ((need1 && !s1) || (need2 && !s2)) return IB_E_ARG;
-  auto al16 = [](const void* q) { return !q || (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
-  if (!al16(p) || !al16(g) || !al16(s1) || !al16(s2) || !al16(ema) ||
-      (shadow_bf16 && reinterpret_cast<uintptr_t>(shadow_bf16) % 8))
-    return IB_E_ARG;
+  if (!ib_al16({p, g, s1, s2, ema}) || !ib_aligned(shadow_bf16, 8)) return IB_E_ARG;
   OptArgs a{p, g, need1 ? s1 : nullptr, need2 ? s2 : nullptr, reinterpret_cast<bf16_t*>(shadow_bf16),
             n, lr, grad_scale, step, step_dev, ticket, opt, ema, ema_decay, ema_warmup};
   const dim3 grid(ib_grid_1d(n / 4 + 1, 256));
@@ -335,10 +332,7 @@ int optim_sources(int opt, float* p, const float* g, float* s1, float* s2, int64
   const bool need1 = opt != IB_OPT_SGD;
   const bool need2 = (opt == IB_OPT_ADAM || opt == IB_OPT_ADADELTA || opt == IB_OPT_ADAMAX);
   if ((need1 && !s1) || (need2 && !s2)) return IB_E_ARG;
-  auto al16 = [](const void* q) { return !q || (reinterpret_cast<uintptr_t>(q) % 16) == 0; };
-  if (!al16(p) || !al16(g) || !al16(s1) || !al16(s2) || !al16(ema) ||
-      (shadow_bf16 && reinterpret_cast<uintptr_t>(shadow_bf16) % 8))
-    return IB_E_ARG;
+  if (!ib_al16({p, g, s1, s2, ema}) || !ib_aligned(shadow_bf16, 8)) return IB_E_ARG;
   OptSources S{};
   S.n = nsrc;
   for (int j = 0; j < nsrc; ++j) {
@@ -350,9 +344,9 @@ int optim_sources(int opt, float* p, const float* g, float* s1, float* s2, int64
     }
     if (!base[j] || count[j] <= 0) return IB_E_ARG;
     if (kind[j] == 1) {
-      if (len[j] % 4 != 0 || stride[j] % 4 != 0 || !al16(base[j])) return IB_E_ARG;
+      if (len[j] % 4 != 0 || stride[j] % 4 != 0 || !ib_aligned(base[j], 16)) return IB_E_ARG;
     } else if (kind[j] == 2) {
-      if (stride[j] % 4 != 0 || !al16(base[j])) return IB_E_ARG;
+      if (stride[j] % 4 != 0 || !ib_aligned(base[j], 16)) return IB_E_ARG;
     } else return IB_E_ARG;
     S.s[j] = GradSrc{start[j], len[j], reinterpret_cast<const float*>(base[j]), stride[j], count[j], kind[j],
                      scale ? scale[j] : 1.f};
@@ -378,7 +372,7 @@ int optim_sources(int opt, float* p, const float* g, float* s1, float* s2, int64
 
 // the *_ema entries: a 16-byte aligned EMA buffer (like p) and a decay in [0, 1] (NaN fails the comparisons too)
 bool ema_args_ok(const float* ema, float ema_decay) {
-  return ema && reinterpret_cast<uintptr_t>(ema) % 16 == 0 && ema_decay >= 0.f && ema_decay <= 1.f;
+  return ema && ib_aligned(ema, 16) && ema_decay >= 0.f && ema_decay <= 1.f;
 }
 
 }  // namespace

@@ -5,7 +5,6 @@
 #include "ib_common.h"
 
 namespace {
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 constexpr int SR_MAX = 8;
 struct SlabMulti {
@@ -108,7 +107,7 @@ static int build_slab_multi(int n, const void* const* slabs, const int32_t* nsla
   int blocks = 0;
   for (int j = 0; j < n; ++j) {
     if (!slabs[j] || !dw[j] || nslab[j] <= 0 || N[j] <= 0 || K[j] <= 0 || lddw[j] < K[j]) return IB_E_ARG;
-    if (K[j] % 4 != 0 || lddw[j] % 4 != 0 || !aligned(slabs[j], 16) || !aligned(dw[j], 16)) return IB_E_UNSUPPORTED;
+    if (K[j] % 4 != 0 || lddw[j] % 4 != 0 || !ib_al16({slabs[j], dw[j]})) return IB_E_UNSUPPORTED;
     p.slabs[j] = reinterpret_cast<const float*>(slabs[j]); p.dw[j] = dw[j]; p.lddw[j] = lddw[j];
     p.nslab[j] = nslab[j]; p.rows[j] = N[j]; p.cols[j] = K[j];
     p.blk0[j] = blocks;
@@ -123,7 +122,7 @@ static int build_colsum_segs(const float* part, int64_t ld, int64_t rows, int ns
                              const int32_t* ncols, float* const* dst, float* const* dst2, const float* scale,
                              int accumulate, ColsumSegs& p, int* blocks_out) {
   if (!part || rows <= 0 || nseg <= 0 || nseg > CS_MAXSEG || !col0 || !ncols || !dst || ld % 4 != 0) return IB_E_ARG;
-  if ((reinterpret_cast<uintptr_t>(part) % 16) != 0) return IB_E_ARG;
+  if (!ib_aligned(part, 16)) return IB_E_ARG;
   p = ColsumSegs{};
   p.part = part; p.ld = ld; p.rows = (int)rows; p.nseg = nseg; p.accumulate = accumulate;
   int blocks = 0;
@@ -200,7 +199,7 @@ extern "C" int ib_step_reduce_parts(int n, const void* const* slabs, const int32
   int cb = 0;
   for (int j = 0; j < nseg; ++j) {
     if (!part[j] || !dst[j] || rows[j] <= 0 || ncols[j] <= 0 || col0[j] < 0 || col0[j] % 4 != 0 || ld[j] % 4 != 0 ||
-        col0[j] + ncols[j] > ld[j] || (reinterpret_cast<uintptr_t>(part[j]) % 16) != 0)
+        col0[j] + ncols[j] > ld[j] || !ib_aligned(part[j], 16))
       return IB_E_ARG;
     cp.partv[j] = part[j]; cp.ldv[j] = ld[j]; cp.rowsv[j] = rows[j];
     cp.col0[j] = col0[j]; cp.ncols[j] = ncols[j]; cp.dst[j] = dst[j]; cp.dst2[j] = nullptr;

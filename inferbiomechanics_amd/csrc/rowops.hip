@@ -19,38 +19,6 @@ __device__ __forceinline__ float act_bwd_pre(int act, float z) {
   }
 }
 
-template <typename T>
-__device__ __forceinline__ void load4(const T* p, int nv, bool vec, float (&v)[4]) {
-  if (nv == 4 && vec) {
-    if constexpr (sizeof(T) == 2) {
-      bf16x4_t t = *reinterpret_cast<const bf16x4_t*>(p);
-      v[0] = (float)t[0]; v[1] = (float)t[1]; v[2] = (float)t[2]; v[3] = (float)t[3];
-    } else {
-      float4 t = *reinterpret_cast<const float4*>(p);
-      v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (e < nv) ? ib_to_f32(p[e]) : 0.f;
-  }
-}
-template <typename T>
-__device__ __forceinline__ void store4(T* p, int nv, bool vec, const float (&v)[4]) {
-  if (nv == 4 && vec) {
-    if constexpr (sizeof(T) == 2) {
-      bf16x4_t o;
-      o[0] = (bf16_t)v[0]; o[1] = (bf16_t)v[1]; o[2] = (bf16_t)v[2]; o[3] = (bf16_t)v[3];
-      *reinterpret_cast<bf16x4_t*>(p) = o;
-    } else {
-      *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (e < nv) p[e] = ib_from_f32<T>(v[e]);
-  }
-}
-
 // ---------------------------------------------------------------- LayerNorm
 // LPR lanes share a row (16 for N <= 512: four rows in flight per wave, 64 for wider rows); a lane owns
 // CH chunks of 8 consecutive elements (16-byte bf16 / 2 x 16-byte fp32 accesses) kept in registers, so x,
@@ -597,7 +565,6 @@ int launch_ln_bwd(const void* dy, const void* x, const void* res, int act, const
   return IB_OK;
 }
 
-inline bool al(const void* p, size_t a) { return !p || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 }  // namespace
 
@@ -617,14 +584,14 @@ extern "C" int ib_layernorm_fwd(const void* x, const void* res, int act, const f
   if (add_div && (seg <= 0 || ld_add < N)) return IB_E_ARG;
   if (N > 2048) return IB_E_UNSUPPORTED;
   hipStream_t s = ib_s(stream);
-  const int vecp = (N % 4 == 0) && al(gamma, 16) && al(beta, 16);
+  const int vecp = (N % 4 == 0) && ib_al16({gamma, beta});
   if (dtype == IB_F32) {
-    const int vec = (N % 4 == 0) && al(x, 16) && al(res, 16) && al(y, 16) && al(add_div, 16) && (ld_add % 4 == 0);
+    const int vec = (N % 4 == 0) && ib_al16({x, res, y, add_div}) && (ld_add % 4 == 0);
     return LN_DISPATCH(launch_ln_fwd, float, x, res, act, gamma, beta, y, mean, rstd, M, N, eps, vec, vecp, add_div,
                        ld_add, (int)seg, s);
   }
   if (dtype == IB_BF16) {
-    const int vec = (N % 8 == 0) && al(x, 16) && al(res, 16) && al(y, 16) && al(add_div, 16) && (ld_add % 8 == 0);
+    const int vec = (N % 8 == 0) && ib_al16({x, res, y, add_div}) && (ld_add % 8 == 0);
     static const bool no_fast = ib_ab_set("IB_NO_LN_FAST");
     if (!no_fast && N == LNF_N && vec && vecp && act == IB_ACT_NONE && !add_div && M >= 4096) {
       hipLaunchKernelGGL(layernorm_fwd512_kernel, dim3((unsigned)((M + 4 * LNF_ROWS - 1) / (4 * LNF_ROWS))), dim3(256), 0, s,
@@ -656,15 +623,13 @@ extern "C" int ib_layernorm_bwd(const void* dy, const void* x, const void* res, 
   hipStream_t s = ib_s(stream);
   float* partial = reinterpret_cast<float*>(workspace);
   int rc;
-  const int vecp = (N % 4 == 0) && al(gamma, 16);
+  const int vecp = (N % 4 == 0) && ib_aligned(gamma, 16);
   if (dtype == IB_F32) {
-    const int vec = (N % 4 == 0) && al(x, 16) && al(res, 16) && al(dy, 16) && al(dx, 16) && al(dres, 16) &&
-                    al(add_div, 16) && (ld_add % 4 == 0);
+    const int vec = (N % 4 == 0) && ib_al16({x, res, dy, dx, dres, add_div}) && (ld_add % 4 == 0);
     rc = LN_DISPATCH_BWD(launch_ln_bwd, float, dy, x, res, act, gamma, mean, rstd, dx, dres, partial, M, N, vec, vecp,
                      parts, add_div, ld_add, (int)seg, s);
   } else if (dtype == IB_BF16) {
-    const int vec = (N % 8 == 0) && al(x, 16) && al(res, 16) && al(dy, 16) && al(dx, 16) && al(dres, 16) &&
-                    al(add_div, 16) && (ld_add % 8 == 0);
+    const int vec = (N % 8 == 0) && ib_al16({x, res, dy, dx, dres, add_div}) && (ld_add % 8 == 0);
     static const bool no_fast = ib_ab_set("IB_NO_LN_FAST");
     if (!no_fast && N == LNF_N && vec && vecp && act == IB_ACT_NONE && !add_div && !dres && M >= 4096) {
       hipLaunchKernelGGL(layernorm_bwd512_kernel, dim3(parts), dim3(LNF_WAVES * 64), 0, s, (const bf16_t*)dy, (const bf16_t*)x,
@@ -709,11 +674,11 @@ extern "C" int ib_segment_colsum(const void* x, int64_t ldx, float* out, int64_t
   hipStream_t s = ib_s(stream);
   const int rps = (int)((mode == 0) ? (seg < M ? seg : M) : (M + seg - 1) / seg);
   if (dtype == IB_F32) {
-    const int vec = (ldx % 4 == 0) && al(x, 16);
+    const int vec = (ldx % 4 == 0) && ib_aligned(x, 16);
     launch_segment_colsum<float>((const float*)x, ldx, out, ldo, (int)M, (int)N, (int)seg, mode, accumulate, vec,
                                  (int)nseg, rps, s, nullptr, (bf16_t*)out_bf16, ld_bf16);
   } else if (dtype == IB_BF16) {
-    const int vec = (ldx % 4 == 0) && al(x, 8);
+    const int vec = (ldx % 4 == 0) && ib_aligned(x, 8);
     launch_segment_colsum<bf16_t>((const bf16_t*)x, ldx, out, ldo, (int)M, (int)N, (int)seg, mode, accumulate, vec,
                                   (int)nseg, rps, s, nullptr, (bf16_t*)out_bf16, ld_bf16);
   } else {

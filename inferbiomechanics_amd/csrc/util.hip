@@ -1,5 +1,5 @@
 // Version / error strings, hipGraph capture helpers, HIP-event timing, instruction self-tests.
-#include "ib_common.h"
+#include "wave_prims.h"
 
 extern "C" int ib_version(void) { return 100; }
 
@@ -81,10 +81,10 @@ extern "C" int ib_event_destroy(void* ev) {
 
 // Probe of ds_read_b64_tr_b16 (the transposing LDS read the bf16 k-strided GEMM operands rely on):
 // input  in[64 rows][16 cols] bf16 (row-major, a [k][row] image of 64 k x 16 rows),
-// output out[lane][4]: what lane gets from ONE read whose address follows gemm.hip::read_frag_bf16
+// output out[lane][4]: what lane gets from ONE read (one half of wave_prims.h::lds_read_tr16) whose address follows
+// gemm.hip::read_frag_bf16
 // with kbase = 0, rbase = 0, i.e. expected out[lane][q] = in[8*(lane/16) + q][lane%16].
 namespace {
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
 __global__ void selftest_tr16_kernel(const short* __restrict__ in, short* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) short img[64 * 16];
   for (int i = threadIdx.x; i < 64 * 16; i += blockDim.x) img[i] = in[i];
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void scale_by_scalar_kernel(T* __restrict__ y,
 extern "C" int ib_scale_by_device_scalar(void* y, const float* scale, int64_t n, int dtype, ib_stream_t stream) {
   if (!y || !scale || n < 0) return IB_E_ARG;
   if (n == 0) return IB_OK;
-  if ((reinterpret_cast<uintptr_t>(y) & 15) != 0) return IB_E_ARG;
+  if (!ib_aligned(y, 16)) return IB_E_ARG;
   const int grid = ib_grid_1d(n, 256 * 8);
   if (dtype == IB_F32) hipLaunchKernelGGL((scale_by_scalar_kernel<float>), dim3(grid), dim3(256), 0, ib_s(stream), (float*)y, scale, n);
   else if (dtype == IB_BF16) hipLaunchKernelGGL((scale_by_scalar_kernel<bf16_t>), dim3(grid), dim3(256), 0, ib_s(stream), (bf16_t*)y, scale, n);

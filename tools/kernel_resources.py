@@ -1,8 +1,13 @@
 """Register and scratch budget of every kernel in csrc/ sources: compiles each source with the Makefile's flags plus
 -Rpass-analysis=kernel-resource-usage (device side only, no object kept) and prints, per kernel, VGPRs, AGPRs, SGPRs,
 VGPR / SGPR spills, scratch bytes per lane, occupancy (waves per SIMD) and LDS bytes.  Runs without a GPU.
-Usage: python tools/kernel_resources.py [--filter SUBSTR] [--json] [file.hip ...]     (default: ffn_chain.hip ffn_chain_bwd.hip)"""
+Usage: python tools/kernel_resources.py [--filter SUBSTR] [--json] [file.hip ...]     (default: ffn_chain.hip ffn_chain_bwd.hip)
+       python tools/kernel_resources.py --digest [-D IB_AB] [file.hip ...]            (default: every source of the Makefile)
+--digest prints, per source, the sha256 of its normalised device assembly (normalise_asm): a refactor that only moves
+text leaves every line as it was; run it on both checkouts, once per build flavour, and diff the two outputs.  A source
+given by absolute path is compiled where it lies, so one checkout's tool can digest another checkout's csrc/."""
 import argparse
+import hashlib
 import json
 import os
 import re
@@ -76,14 +81,55 @@ def resources(src, extra=()):
     return out
 
 
+def normalise_asm(text):
+    """device assembly without what differs between two compilations of the same code: comment lines, the compiler's
+    .ident, the .file line, and every line that names the translation unit's __hip_cuid_<hash> symbol"""
+    keep = []
+    for line in text.splitlines():
+        t = line.strip()
+        if not t or t.startswith(";") or t.startswith((".ident", ".file")) or "__hip_cuid_" in t:
+            continue
+        keep.append(line.rstrip())
+    return "\n".join(keep) + "\n"
+
+
+def device_asm(src, extra=()):
+    """normalised device assembly of one source, built with the Makefile's flags"""
+    cc = hipcc()
+    if cc is None:
+        raise RuntimeError("hipcc not found")
+    path = src if os.path.isabs(src) else os.path.join(CSRC, src)
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "dev.s")
+        cmd = [cc, *FLAGS, *extra, "--cuda-device-only", "-S", path, "-o", out]
+        r = subprocess.run(cmd, cwd=os.path.dirname(path), capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"{' '.join(cmd)} failed:\n{r.stderr[-4000:]}")
+        with open(out) as f:
+            return normalise_asm(f.read())
+
+
+def makefile_sources():
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        return re.search(r"^SRCS\s*=\s*(.+)$", f.read(), re.M).group(1).split()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("sources", nargs="*", default=["ffn_chain.hip", "ffn_chain_bwd.hip"])
+    ap.add_argument("sources", nargs="*")
     ap.add_argument("--filter", default="", help="only kernels whose short name contains this")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--digest", action="store_true", help="sha256 of each source's normalised device assembly")
     ap.add_argument("-D", action="append", default=[], help="extra -D definitions (e.g. -D IB_AB)")
     a = ap.parse_args()
     extra = [f"-D{d}" for d in a.D]
+    if a.digest:
+        srcs = a.sources or makefile_sources()
+        with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
+            for s, asm in zip(srcs, ex.map(lambda s: device_asm(s, extra), srcs)):
+                print(f"{os.path.basename(s):22s} {hashlib.sha256(asm.encode()).hexdigest()}")
+        return 0
+    a.sources = a.sources or ["ffn_chain.hip", "ffn_chain_bwd.hip"]
     with ThreadPoolExecutor(max_workers=min(4, len(a.sources))) as ex:
         rows = [k for ks in ex.map(lambda s: resources(s, extra), a.sources) for k in ks]
     rows = [k for k in rows if a.filter in k["kernel"]]
