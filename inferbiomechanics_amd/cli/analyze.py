@@ -47,12 +47,14 @@ class AnalyzeCommand(AbstractCommand):
                        help='[diffusion models] eta of the sampler: 0 = deterministic DDIM, 1 = DDPM ancestral sampling.')
         p.add_argument('--num-samples', type=int, default=1,
                        help='[diffusion models] posterior samples per window; the mean is evaluated, the spread reported.')
-        p.add_argument('--sampler', type=str, default='ddim', choices=['ddim', 'dpmpp2m'],
+        p.add_argument('--sampler', type=str, default='ddim', choices=['ddim', 'dpmpp2m', 'dpmpp2m_sde'],
                        help='[diffusion models] update of the sampling loop: first-order DDIM, or DPM-Solver++(2M), second '
-                            'order with one denoiser evaluation per step, like DDIM (deterministic: needs --sample-eta 0).')
+                            'order with one denoiser evaluation per step, like DDIM (deterministic: needs --sample-eta 0), '
+                            'or dpmpp2m_sde, its stochastic form (SDE-DPM-Solver++(2M)): takes --sample-eta > 0 and '
+                            '--num-samples > 1; use it with --sample-spacing logsnr.')
         p.add_argument('--sample-spacing', type=str, default='time', choices=['time', 'logsnr'],
                        help='[diffusion models] sampling grid: uniform in the timestep, or uniform in log-SNR (no need for '
-                            '--sample-steps to divide the training steps; the grid for few-step dpmpp2m sampling).')
+                            '--sample-steps to divide the training steps; the grid for few-step dpmpp2m / dpmpp2m_sde sampling).')
         p.add_argument('--use-ema', action='store_true', default=False,
                        help='Evaluate the EMA weights of the checkpoint (`train --ema-decay`) instead of its last weights.')
 

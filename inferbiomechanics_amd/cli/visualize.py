@@ -10,7 +10,8 @@ labelled as ONE sequence of overlapping windows and printed next to the labels t
 windows of the same frames.  With `--sample-eta E --num-samples K` (E > 0 or K > 1) both are posterior ensembles
 (predict_trial_ensemble, and the per-window predictor with the same eta and K): the labels printed are the members' means,
 and one more line per trial and label key reports the mean standard deviation over the K members.  `--sampler dpmpp2m`
-runs both loops with DPM-Solver++(2M); it is deterministic and refuses E > 0 or K > 1."""
+runs both loops with DPM-Solver++(2M); it is deterministic and refuses E > 0 or K > 1.  `--sampler dpmpp2m_sde` is its
+stochastic form and takes both; it belongs with `--sample-spacing logsnr`."""
 import argparse
 import os
 
@@ -65,9 +66,13 @@ class VisualizeCommand(AbstractCommand):
         p.add_argument('--num-samples', type=int, default=1,
                        help='[--trial-frames] posterior samples per trial and per window; the means are printed and the '
                             'spread over the members reported.')
-        p.add_argument('--sampler', type=str, default='ddim', choices=['ddim', 'dpmpp2m'],
-                       help='[--trial-frames] update of both sampling loops: first-order DDIM, or DPM-Solver++(2M) '
-                            '(deterministic: needs --sample-eta 0 and --num-samples 1).')
+        p.add_argument('--sampler', type=str, default='ddim', choices=['ddim', 'dpmpp2m', 'dpmpp2m_sde'],
+                       help='[--trial-frames] update of both sampling loops: first-order DDIM, DPM-Solver++(2M) '
+                            '(deterministic: needs --sample-eta 0 and --num-samples 1), or dpmpp2m_sde, its stochastic form '
+                            '(takes --sample-eta > 0 and --num-samples > 1; use it with --sample-spacing logsnr).')
+        p.add_argument('--sample-spacing', type=str, default='time', choices=['time', 'logsnr'],
+                       help='[--trial-frames] sampling grid of both loops: uniform in the timestep, or uniform in log-SNR '
+                            '(the grid for few-step dpmpp2m / dpmpp2m_sde sampling).')
 
     def run(self, args: argparse.Namespace):
         if 'command' in args and args.command != 'visualize':
@@ -144,7 +149,7 @@ class VisualizeCommand(AbstractCommand):
             raise SystemExit(f"--trial-frames / --trial-hop: {e}")
         predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
                                             output_data_format=args.output_data_format, eta=eta, num_samples=num_samples,
-                                            solver=solver)
+                                            solver=solver, spacing=getattr(args, 'sample_spacing', 'time'))
         gather = start.long()[:, None] + torch.arange(T)[None, :]      # [Wd, T] trial frames of the disjoint windows
         w0 = cover[:, 0].long()
         t0 = torch.arange(F) - start.long()[w0]

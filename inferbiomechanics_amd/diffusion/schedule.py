@@ -33,7 +33,7 @@ def log_snr(num_train_steps: int = 1000) -> torch.Tensor:
 
 
 SPACINGS = ("time", "logsnr")
-SOLVERS = ("ddim", "dpmpp2m")
+SOLVERS = ("ddim", "dpmpp2m", "dpmpp2m_sde")
 OBSERVATIONS = ("noised", "clean")
 
 
@@ -183,6 +183,82 @@ def dpmpp_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100,
     return torch.stack(rows)
 
 
+def _sde_steps(num_train_steps: int, num_sample_steps: int, spacing: str):
+    """per sampling step but the last: (alpha_s, sigma_s, alpha_t, sigma_t, h, c) of the step from level s = t_i to
+    t = t_{i+1} in float64 -- h = lambda_t - lambda_s, c = h / (2 (lambda_s - lambda_{t_{i-1}})), 0 in the first row.  The last
+    step (to alpha_bar = 1, h infinite) comes as (alpha_s, sigma_s) alone"""
+    ab = alphas_cumprod(num_train_steps)
+    ts = sample_timesteps(num_train_steps, num_sample_steps, spacing).tolist()
+    lam = log_snr(num_train_steps)
+    out = []
+    for i, s in enumerate(ts):
+        al_s, sg_s = torch.sqrt(ab[s]), torch.sqrt(1 - ab[s])
+        if i == len(ts) - 1:
+            out.append((al_s, sg_s))
+            continue
+        t = ts[i + 1]
+        h = lam[t] - lam[s]
+        c = h / (2.0 * (lam[s] - lam[ts[i - 1]])) if i > 0 else torch.tensor(0.0, dtype=torch.float64)
+        out.append((al_s, sg_s, torch.sqrt(ab[t]), torch.sqrt(1 - ab[t]), h, c))
+    return out
+
+
+def sde_dpmpp_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100, eta: float = 0.0,
+                           spacing: str = "time") -> torch.Tensor:
+    """[S, 6] float64 (A, E, C, hx, he, G) of SDE-DPM-Solver++(2M) (Lu et al. 2022; k-diffusion's dpmpp_2m_sde), the
+    stochastic form of dpmpp_coefficients: x' = A x + E eps + C h_prev + G z', z' ~ N(0, I), with the same history
+    h = hx x + he eps.  Step i from level s to level t, h_i = lambda_t - lambda_s, c = h_i / (2 h_{i-1}) (0 in the first
+    row), g = -alpha_t expm1(-(1 + eta) h_i):
+      A = (sigma_t / sigma_s) exp(-eta h_i) + g (1 + c) / alpha_s,  E = -g (1 + c) sigma_s / alpha_s,  C = -g c,
+      G = sigma_t sqrt(-expm1(-2 eta h_i)).
+    The last row goes to alpha_bar = 1: (1 / alpha_s, -sigma_s / alpha_s, 0, hx, he, 0), the last row of ddim_coefficients.
+    At eta = 0 the rows are dpmpp_coefficients' bit for bit (they are returned, not recomputed) and G = 0; at eta = 1 the
+    first row's (A, E, G) is the DDPM row of ddim_coefficients_eta.  It belongs on the 'logsnr' grid: uniform in t its steps
+    in lambda are very uneven and 20 of them are poor (docs/EXPERIMENTS.md)."""
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"eta must be in [0, 1], got {eta}")
+    eta = float(eta)
+    if eta == 0.0:
+        five = dpmpp_coefficients(num_train_steps, num_sample_steps, spacing)
+        return torch.cat([five, torch.zeros((five.shape[0], 1), dtype=torch.float64)], dim=1)
+    zero = torch.tensor(0.0, dtype=torch.float64)
+    rows = []
+    for st in _sde_steps(num_train_steps, num_sample_steps, spacing):
+        al_s, sg_s = st[0], st[1]
+        hx, he = 1.0 / al_s, -sg_s / al_s
+        if len(st) == 2:
+            rows.append(torch.stack([hx, he, zero, hx, he, zero]))
+            continue
+        _, _, al_t, sg_t, h, c = st
+        g = -al_t * torch.expm1(-(1.0 + eta) * h)
+        A = (sg_t / sg_s) * torch.exp(-eta * h) + g * (1 + c) / al_s
+        E = -g * (1 + c) * sg_s / al_s
+        C = -g * c
+        G = sg_t * torch.sqrt(-torch.expm1(-2.0 * eta * h))
+        rows.append(torch.stack([A, E, C, hx, he, G]))
+    return torch.stack(rows)
+
+
+def sde_observation_noise_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100, eta: float = 0.0,
+                                       spacing: str = "time") -> torch.Tensor:
+    """[S, 2] float64 (r, q) of the masked 'dpmpp2m_sde' loop: an observed element keeps x = sqrt(ab) x0 + sqrt(1 - ab) e and
+    its stored noise becomes e' = r e + q z' with r = exp(-eta h), q = sqrt(-expm1(-2 eta h)), r^2 + q^2 = 1 (the true x0 as
+    the data prediction makes the solver's second-order term vanish, which leaves the first-order SDE step).  (0, 0) in the
+    last row, where the level is the observation itself.  At eta = 1 it is observation_noise_coefficients(eta = 1); at
+    eta < 1 the two differ, so a loop reads only its own solver's table."""
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"eta must be in [0, 1], got {eta}")
+    eta = float(eta)
+    rows = []
+    for st in _sde_steps(num_train_steps, num_sample_steps, spacing):
+        if len(st) == 2:
+            rows.append(torch.zeros(2, dtype=torch.float64))
+        else:
+            h = st[4]
+            rows.append(torch.stack([torch.exp(-eta * h), torch.sqrt(-torch.expm1(-2.0 * eta * h))]))
+    return torch.stack(rows)
+
+
 STITCH_KMAX = 8                 # IB_STITCH_KMAX (include/ib_hip_stitch.h): the most windows that may cover one trial frame
 STITCH_BLENDS = ("uniform", "ramp")
 
@@ -249,7 +325,8 @@ class DiffusionTables:
     def set_sampler(self, num_sample_steps: int, eta: float = 0.0, solver: str = "ddim", spacing: str = "time",
                     observations: str = "noised"):
         """the sampler's tables for S steps on the `spacing` grid; eta > 0 adds the stochastic loop's (c_x, c_eps, sigma) and
-        (r, q) tables, solver 'dpmpp2m' the second-order multistep solver's (A, E, C, hx, he) table.  observations: what
+        (r, q) tables -- with solver 'dpmpp2m_sde' that solver's own (sde_coef [S, 6], sde_obs_noise_coef) instead --, solver
+        'dpmpp2m' or 'dpmpp2m_sde' the second-order multistep solver's (A, E, C, hx, he) table.  observations: what
         obs_coef holds -- 'noised', the observation forward-noised to each level (observation_coefficients), or 'clean',
         every row (1, 0) (clean_observation_coefficients: a denoiser trained on clean conditioning columns)"""
         if observations not in OBSERVATIONS:
@@ -271,22 +348,32 @@ class DiffusionTables:
         self.observations = observations
         obs = clean_observation_coefficients if observations == "clean" else observation_coefficients
         self.obs_coef = obs(N, num_sample_steps, spacing).to(torch.float32).to(dev).contiguous()
-        self.ddim_coef_eta = self.obs_noise_coef = self.dpmpp_coef = None
-        if self.eta > 0.0:
-            self.ddim_coef_eta = ddim_coefficients_eta(N, num_sample_steps, eta, spacing).to(torch.float32).to(dev).contiguous()
-            self.obs_noise_coef = observation_noise_coefficients(N, num_sample_steps, eta, spacing).to(torch.float32).to(dev).contiguous()
-        if solver == "dpmpp2m":
-            self.dpmpp_coef = dpmpp_coefficients(N, num_sample_steps, spacing).to(torch.float32).to(dev).contiguous()
+        self.ddim_coef_eta = self.obs_noise_coef = self.dpmpp_coef = self.sde_coef = self.sde_obs_noise_coef = None
+        up = lambda t: t.to(torch.float32).to(dev).contiguous()
+        # an eta > 0 loop gets the stochastic tables of ITS solver and not the other's: the two (r, q) tables differ at
+        # eta < 1, and serves() refuses a loop whose own tables are missing
+        if self.eta > 0.0 and solver == "dpmpp2m_sde":
+            self.sde_coef = up(sde_dpmpp_coefficients(N, num_sample_steps, eta, spacing))
+            self.sde_obs_noise_coef = up(sde_observation_noise_coefficients(N, num_sample_steps, eta, spacing))
+        elif self.eta > 0.0:
+            self.ddim_coef_eta = up(ddim_coefficients_eta(N, num_sample_steps, eta, spacing))
+            self.obs_noise_coef = up(observation_noise_coefficients(N, num_sample_steps, eta, spacing))
+        if solver in ("dpmpp2m", "dpmpp2m_sde"):                 # 'dpmpp2m_sde' at eta = 0 runs the 'dpmpp2m' launches
+            self.dpmpp_coef = up(dpmpp_coefficients(N, num_sample_steps, spacing))
 
     def serves(self, num_sample_steps: int, eta: float = 0.0, solver: str = "ddim", spacing: str = "time",
                observations: Optional[str] = None) -> bool:
         """whether the current tables are the ones a loop with these settings reads: the grid (S, spacing) must match; the
-        eta tables only matter to an eta > 0 loop, the solver's table only to 'dpmpp2m' and the observation table only to a
-        masked loop, which names the kind it reads (None: the loop reads no observation table)"""
+        eta tables only matter to an eta > 0 loop -- and then they must be those of the loop's own solver, first-order
+        ('ddim') or 'dpmpp2m_sde' --, the second-order table only to 'dpmpp2m' and 'dpmpp2m_sde' and the observation table only
+        to a masked loop, which names the kind it reads (None: the loop reads no observation table)"""
+        noisy = float(eta) > 0.0
         return (self.num_sample_steps == num_sample_steps and self.spacing == spacing
                 and (observations is None or self.observations == observations)
-                and (float(eta) == 0.0 or self.eta == float(eta))
-                and (solver != "dpmpp2m" or self.dpmpp_coef is not None))
+                and (not noisy or self.eta == float(eta))
+                and (not (noisy and solver == "ddim") or self.ddim_coef_eta is not None)
+                and (not (noisy and solver == "dpmpp2m_sde") or self.sde_coef is not None)
+                and (solver not in ("dpmpp2m", "dpmpp2m_sde") or self.dpmpp_coef is not None))
 
     def host_tables(self) -> Dict[str, torch.Tensor]:
         return {"sqrt_ab": self.sqrt_ab.cpu(), "sqrt_1mab": self.sqrt_1mab.cpu(), "temb": self.temb.cpu(),

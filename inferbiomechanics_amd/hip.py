@@ -9,7 +9,8 @@ The header is the only declaration of the ABI: the ctypes signatures (``_SIGS``)
 module is imported, so a new entry point needs its declaration there and its wrapper here, nothing else.  The stitched
 sampler updates (csrc/stitch.hip) are declared in a second header, ``include/ib_hip_stitch.h``, parsed the same way into
 ``_STITCH_SIGS``, the merged head launches of the transformer step (csrc/head_jobs.h) in a third, ``include/ib_hip_head.h``
-(``_HEAD_SIGS``); a name may be declared once in the three.
+(``_HEAD_SIGS``), the stochastic second-order sampler update (csrc/sde.hip) in a fourth, ``include/ib_hip_sde.h``
+(``_SDE_SIGS``); a name may be declared once in the four.
 """
 from __future__ import annotations
 
@@ -29,6 +30,7 @@ AB_LIB_PATH = os.path.join(_HERE, "lib", "ab", "libib_hip_ab.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip.h")
 STITCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_stitch.h")
 HEAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_head.h")
+SDE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sde.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -92,11 +94,12 @@ def _read_header(path: Optional[str] = None) -> str:
 
 
 # a table per header: _SIGS and declared_symbols() describe ib_hip.h only, _STITCH_SIGS the stitched trial sampling
-_SIGS, _STITCH_SIGS, _HEAD_SIGS = (_parse_header(_read_header(_path))
-                                   for _path in (HEADER_PATH, STITCH_HEADER_PATH, HEAD_HEADER_PATH))
-_ALL_SIGS = {**_SIGS, **_STITCH_SIGS, **_HEAD_SIGS}   # every entry point of the ABI: what _sig() looks up and lib() binds
-if len(_ALL_SIGS) != len(_SIGS) + len(_STITCH_SIGS) + len(_HEAD_SIGS):
-    _twice = sorted(n for n in _ALL_SIGS if (n in _SIGS) + (n in _STITCH_SIGS) + (n in _HEAD_SIGS) > 1)
+_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS = (_parse_header(_read_header(_path)) for _path in
+                                              (HEADER_PATH, STITCH_HEADER_PATH, HEAD_HEADER_PATH, SDE_HEADER_PATH))
+_TABLES = (_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS)
+_ALL_SIGS = {_n: _v for _t in _TABLES for _n, _v in _t.items()}   # every entry point: what _sig() looks up and lib() binds
+if len(_ALL_SIGS) != sum(len(_t) for _t in _TABLES):
+    _twice = sorted(n for n in _ALL_SIGS if sum(n in _t for _t in _TABLES) > 1)
     raise HipError(f"declared in two headers: {_twice}")
 _kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_STITCH_KMAX[ \t]+(\d+)[ \t]*$", _read_header(STITCH_HEADER_PATH), flags=re.M)
 if _kmax is None:
@@ -121,8 +124,13 @@ def head_symbols() -> List[str]:
     return sorted(_HEAD_SIGS)
 
 
+def sde_symbols() -> List[str]:
+    """Every function include/ib_hip_sde.h declares"""
+    return sorted(_SDE_SIGS)
+
+
 def _sig(name: str):
-    """(restype, argtypes) of an entry point of either header"""
+    """(restype, argtypes) of an entry point of any header"""
     return _ALL_SIGS[name]
 
 
@@ -2496,6 +2504,30 @@ def stitch_ddim_step_noise(x, eps, x0, z, mask, coef, obs_coef, obs_noise_coef, 
                                            _ptr(start), _ptr(cover), _ptr(wn), _ptr(trial_ids),
                                            int(seed) & 0xFFFFFFFFFFFFFFFF, N, W, T, F, D, ld, dtype_code(x.dtype),
                                            stream_ptr()), "ib_stitch_ddim_step_noise")
+    return x
+
+
+def sde_dpmpp_step(x, eps, hist, x0, z, mask, coef, obs_coef, obs_noise_coef, timesteps, start, cover, wn, trial_ids, seed,
+                   step=0, step_dev=None, t_out=None, D=None):
+    """SDE-DPM-Solver++(2M) update of a stitched trial in place (csrc/sde.hip): stitch_dpmpp_step and stitch_ddim_step_noise
+    together, coef [S, 6] = (A, E, C, hx, he, G) (schedule.sde_dpmpp_coefficients), hist fp32 [N, W, T, ld]; the noise of
+    trial n is keyed by (seed, trial_ids[n], step, TRIAL frame, column).  x0, z, mask, obs_coef and obs_noise_coef [S, 2]
+    (schedule.sde_observation_noise_coefficients): all None, or the masked loop's operands (z is updated in place at the
+    observed elements, in every copy).  trial_ids: int64 [N] on the device.  A per-window loop is the same call with W = 1,
+    the layout stitch_layout(T, T, T) and window ids as trial ids."""
+    what = "sde_dpmpp_step"
+    if (obs_noise_coef is None) != (obs_coef is None):
+        raise HipError(f"{what}: x0, z, mask, obs_coef and obs_noise_coef come together (the masked loop) or not at all")
+    N, W, T, F, D, ld = _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D)
+    _like_x(what, "hist", hist, x, torch.float32)
+    S = _step_tables(what, coef, 6, timesteps, N * W, t_out, step_dev, obs_coef)
+    if obs_noise_coef is not None:
+        _obs_noise_coef(what, obs_noise_coef, S)
+    _win_ids(what, trial_ids, N, "trial_ids", "N", x.device)
+    _check(lib().ib_sde_dpmpp_step(_ptr(x), _ptr(eps), _ptr(hist), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef),
+                                   _ptr(obs_noise_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out),
+                                   _ptr(start), _ptr(cover), _ptr(wn), _ptr(trial_ids), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                   N, W, T, F, D, ld, dtype_code(x.dtype), stream_ptr()), "ib_sde_dpmpp_step")
     return x
 
 

@@ -33,7 +33,8 @@ class DiffusionLabelPredictor:
     window i = draw + b is replicated K times inside the sampler batch (B K rows); member k has window id i K + k for both its
     start draw and its step noise (eta > 0), the outputs are the members' mean and ``last_std`` their unbiased standard
     deviation, in the same four-key layout (None on the default eta = 0, K = 1 path, which is the single deterministic
-    trajectory).  solver / spacing choose the sampler's update and grid (diffusion/sampler.py).  A denoiser trained on
+    trajectory).  solver / spacing choose the sampler's update and grid (diffusion/sampler.py); 'dpmpp2m_sde' is the
+    second-order solver that takes eta > 0 and ensembles.  A denoiser trained on
     clean conditioning columns (model.cond_cols > 0, `train --cond-cols`; it must be feat_dim - 30) gets its observations
     pinned clean at every step (ConditionalDDIMSampler, observations = 'clean'); at 0 they are forward-noised as before."""
 
@@ -159,12 +160,12 @@ class DiffusionLabelPredictor:
     def predict_trial_ensemble(self, inputs: Dict[str, torch.Tensor], hop: Optional[int] = None, blend: str = 'ramp',
                                draw: int = 0) -> Dict[str, torch.Tensor]:
         """Posterior ensembles of whole trials: as ``predict_trial`` with the predictor's own ``eta`` and ``num_samples`` = K
-        (``StochasticStitchedSampler``, solver 'ddim').  Trial i = draw + b is replicated K times inside the sampler batch;
+        (``StochasticStitchedSampler``, solver 'ddim' or 'dpmpp2m_sde').  Trial i = draw + b is replicated K times inside the sampler batch;
         member k has trial id i K + k for both its start draw and its step noise.  Returns the members' mean as the four
         ``LOSS_KEY_ORDER`` outputs, fp32 ``[N, F, C]``, and sets ``last_std`` to their unbiased standard deviation in the
         same layout (0 for K = 1), summed in member order (``ib_ensemble_stats``)."""
-        if self.sampler.solver != 'ddim':
-            raise ValueError(f"predict_trial_ensemble: the stochastic stitched loop is DDIM / DDPM, solver "
+        if self.sampler.solver not in ('ddim', 'dpmpp2m_sde'):
+            raise ValueError(f"predict_trial_ensemble: the stochastic stitched loop is DDIM / DDPM or 'dpmpp2m_sde', solver "
                              f"{self.sampler.solver!r} is deterministic")
         obs, C = self._trial_checks(inputs)
         N, F, D = obs.shape
@@ -173,7 +174,8 @@ class DiffusionLabelPredictor:
         if self._trial_ens is None or self._trial_ens[0] != key:
             s = self.sampler
             self._trial_ens = (key, StochasticStitchedSampler(self.model, s.S, eta=self.eta, hop=hop, blend=blend,
-                                                              use_graph=s.use_graph, spacing=s.spacing, seed=self.seed),
+                                                              use_graph=s.use_graph, spacing=s.spacing, seed=self.seed,
+                                                              solver=s.solver),
                                label_mask(1, D)[0].contiguous())
         _, sampler, mask_cols = self._trial_ens
         sampler.observations = 'clean' if C else 'noised'

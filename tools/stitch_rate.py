@@ -9,7 +9,11 @@ expectation is "within noise of the per-window loop".  Each timed call is a whol
 synchronisations; the order rotates from one repetition to the next, and a second per-window sampler (`windows_b`, its own
 capture of the same step) is the A / A control: how far two identical captured loops differ on the machine.
 `stitched_eta1` is the stochastic stitched loop (StochasticStitchedSampler, eta = 1: the update draws one Philox block per
-four trial elements inside the kernel) on the same trials, in the same rotation.  One JSON line per (N, F).
+four trial elements inside the kernel) on the same trials, in the same rotation.  `stitched_sde_eta1` is the same loop with
+solver 'dpmpp2m_sde' (ib_sde_dpmpp_step: the same draw, plus the fp32 history read and written) on the log-SNR grid, at the
+same S so that steps/s compare; it runs on a second model object with the same weights, because one model's sampler tables
+hold the stochastic tables of ONE solver and two loops that alternate on them would re-capture at every call.  One JSON line
+per (N, F).
 
     python tools/stitch_rate.py [--trials 1 8] [--frames 200 1000] [--reps 10]"""
 import argparse
@@ -40,6 +44,9 @@ def main():
     torch.manual_seed(0)
     model = DiffusionTransformer(D, T, d_model=512, num_heads=8, dim_feedforward=2048, num_layers=4, device=dev,
                                  compute_dtype=torch.bfloat16)
+    model_sde = DiffusionTransformer(D, T, d_model=512, num_heads=8, dim_feedforward=2048, num_layers=4, device=dev,
+                                     compute_dtype=torch.bfloat16)
+    model_sde.load_state_dict(model.state_dict())
     cols = torch.ones(D, dtype=torch.bool)
     cols[D - FREE:] = False
     mask = cols[None, :].expand(T, D).contiguous()
@@ -54,8 +61,10 @@ def main():
             zw, ow = st.to_windows(z).contiguous(), st.to_windows(obs).contiguous()
             win, win_b = ConditionalDDIMSampler(model, S), ConditionalDDIMSampler(model, S)
             st1 = StochasticStitchedSampler(model, S, eta=1.0, seed=0)
+            sde1 = StochasticStitchedSampler(model_sde, S, eta=1.0, seed=0, spacing="logsnr", solver="dpmpp2m_sde")
             runs = {"windows": lambda: win.sample(zw, ow, mask), "windows_b": lambda: win_b.sample(zw, ow, mask),
-                    "stitched": lambda: st.sample(z, obs, cols), "stitched_eta1": lambda: st1.sample(z, obs, cols)}
+                    "stitched": lambda: st.sample(z, obs, cols), "stitched_eta1": lambda: st1.sample(z, obs, cols),
+                    "stitched_sde_eta1": lambda: sde1.sample(z, obs, cols)}
             for _ in range(2):               # twice: the eta = 1 sampler's first call replaces the model's sampler tables,
                 for fn in runs.values():     # so the captures made before it are made again on the second pass
                     fn()
@@ -77,6 +86,8 @@ def main():
                 line[f"{k}_spread_pct"] = round(100 * (max(ts) - min(ts)) / med, 1)
             line["stitched_over_windows"] = round(line["stitched_steps_per_s"] / line["windows_steps_per_s"], 4)
             line["stitched_eta1_over_stitched"] = round(line["stitched_eta1_steps_per_s"] / line["stitched_steps_per_s"], 4)
+            line["stitched_sde_eta1_over_stitched_eta1"] = round(line["stitched_sde_eta1_steps_per_s"] /
+                                                                 line["stitched_eta1_steps_per_s"], 4)
             line["windows_b_over_windows"] = round(line["windows_b_steps_per_s"] / line["windows_steps_per_s"], 4)
             print(json.dumps(line), flush=True)
 
