@@ -12,14 +12,76 @@ spacing = 'logsnr'.
 One denoise step = {time-embedding gather, denoiser forward plan, DDIM update, counter++}.  The step index
 lives in DEVICE memory (an int32 counter the update kernel reads), and the update kernel also writes the next
 step's timestep vector, so ONE captured hipGraph of a single step can be replayed for every step of the loop
-with no host involvement between steps (BASELINE config 5)."""
+with no host involvement between steps (BASELINE config 5).
+
+How the four classes share one loop.  The public sample() of a class checks its arguments and states the call as one frozen
+record, SampleCall: the window batch's shape, how it splits into trials, the ids, the observation cut into windows with its
+[T, D] mask (or none), the trial layout (or none).  The record is passed down as an argument; nothing about a call is kept
+on the sampler, so a call that is refused leaves it as it was.  DDIMSampler owns everything below sample(): the signature
+and the buffers of the captured step (_prepare), the masked start state (_start_masked), the loop, and the ONE choice of
+the update launch (_launch_update):
+
+    layout   solver order   eta > 0   entry point (with observations)
+    no       1              no        ib_ddim_step            (ib_ddim_cond_step)
+    no       1              yes       ib_ddim_step_noise      (ib_ddim_cond_step_noise)
+    no       2              no        ib_dpmpp_step           (ib_dpmpp_cond_step)
+    no       2              yes       ib_sde_dpmpp_step over [B, 1, T, ld] with the one-window layout (masked operands or none)
+    yes      1              no        ib_stitch_ddim_step                    "
+    yes      1              yes       ib_stitch_ddim_step_noise              "
+    yes      2              no        ib_stitch_dpmpp_step                   "
+    yes      2              yes       ib_sde_dpmpp_step                      "
+
+(order 2 with eta > 0 is 'dpmpp2m_sde'; 'dpmpp2m_sde' at eta = 0 is an eta = 0 row)."""
+from dataclasses import dataclass
 from typing import Optional, Sequence, Union
 
 import torch
 
 from .. import hip
 from ..plans import ParamSource
-from .schedule import OBSERVATIONS, SOLVERS, SPACINGS, stitch_layout
+from .schedule import OBSERVATIONS, check_sampler_settings, stitch_layout
+
+
+@dataclass(frozen=True)
+class SampleCall:
+    """One sample() call: B windows of [T, D] (state rows pitched to Dp) that are N trials of W windows each -- a
+    per-window loop is N = B, W = 1.  ids: the noise ids as given (None: 0 .. N-1), one per trial.  observed [B, T, D] and
+    mask [T, D] (True / non-zero: observed) come together or not at all; lay: the trial layout's tables, None for a
+    per-window loop."""
+    B: int
+    T: int
+    D: int
+    Dp: int
+    N: int
+    W: int
+    ids: Union[None, Sequence[int], torch.Tensor] = None
+    observed: Optional[torch.Tensor] = None
+    mask: Optional[torch.Tensor] = None
+    lay: Optional[dict] = None
+
+
+def _checked_ids(given, count: int, noun: str) -> torch.Tensor:
+    """the call's `noun` ids (default 0 .. count-1) as the int64 host tensor the device buffer 'win' is filled from"""
+    ids = torch.arange(count, dtype=torch.int64) if given is None else \
+        torch.as_tensor(given, dtype=torch.int64).reshape(-1).cpu()
+    if ids.numel() != count:
+        raise ValueError(f"{noun}_ids must hold one id per {noun} ({count}), got {ids.numel()}")
+    if count and (int(ids.min()) < 0 or int(ids.max()) >= 1 << 32):
+        raise ValueError(f"{noun}_ids must be in 0 .. 2^32 - 1 (one word of the generator's counter)")
+    return ids
+
+
+def _cut(lay: dict, trial: torch.Tensor) -> torch.Tensor:
+    """[N, F, D] -> [N * W, T, D]: every window's frames (plumbing: an index, no arithmetic)"""
+    N, F, D = trial.shape
+    gather = lay["gather"].to(trial.device)
+    return trial[:, gather].reshape(N * lay["W"], gather.shape[1], D)
+
+
+def _join(lay: dict, windows: torch.Tensor, N: int) -> torch.Tensor:
+    """[N * W, T, D] -> [N, F, D] from each frame's first copy"""
+    w = windows.view(N, lay["W"], windows.shape[1], windows.shape[2])
+    return w[:, lay["w0"].to(w.device), lay["t0"].to(w.device)].contiguous()
 
 
 class DDIMSampler:
@@ -28,38 +90,16 @@ class DDIMSampler:
         """eta in [0, 1]; seed (default: torch's initial seed) keys the step noise of an eta > 0 loop; solver 'ddim',
         'dpmpp2m' (deterministic: eta = 0 only) or 'dpmpp2m_sde' (its stochastic form; eta = 0 runs 'dpmpp2m'); spacing
         'time' or 'logsnr', the sampling grid"""
-        if not 0.0 <= float(eta) <= 1.0:
-            raise ValueError(f"eta must be in [0, 1], got {eta}")
-        if solver not in SOLVERS:
-            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
-        if spacing not in SPACINGS:
-            raise ValueError(f"spacing must be one of {SPACINGS}, got {spacing!r}")
-        if solver == "dpmpp2m" and float(eta) > 0.0:
-            raise ValueError("solver 'dpmpp2m' is deterministic: it needs eta = 0")
+        check_sampler_settings(eta, solver, spacing)
         self.model, self.S = model, num_sample_steps
         self.eta = float(eta)
         self.solver, self.spacing = solver, spacing
         self.seed = (int(torch.initial_seed()) if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF
-        self._win = None
         self.use_graph = use_graph and not hip._dry_run
         self._graph: Optional[hip.Graph] = None
+        self._stream = None
         self._sig = None
         self._bufs = {}
-
-    def _step_launches(self, x, t_vec, ctr, tabs, P: ParamSource):
-        plan = self.model._get_plan(x.device)
-        eps_buf = self._bufs.get("eps")
-        if eps_buf is not None:
-            # pitched state / noise buffers [B, T, Dp] with zero pad columns (plans.infer_pitch): the plan sees row-padded
-            # 2-D views; the DDIM update runs over the whole pitched buffers (0 stays 0 in the pad columns)
-            B, T, Dp = x.shape
-            D = self._D
-            plan.forward(x.view(B * T, Dp)[:, :D], t_vec, tabs.temb, P, out=eps_buf.view(B * T, Dp)[:, :D], BT=(B, T))
-            self._update(x, eps_buf, ctr, t_vec, tabs)
-        else:
-            eps = plan.forward(x, t_vec, tabs.temb, P)
-            self._update(x, eps, ctr, t_vec, tabs)
-        hip.counter_add(ctr, 1)
 
     def _second(self) -> bool:
         """a second-order multistep solver: the loop keeps the fp32 history buffer"""
@@ -69,69 +109,36 @@ class DDIMSampler:
         """the stochastic second-order update runs; 'dpmpp2m_sde' at eta = 0 is the 'dpmpp2m' launches"""
         return self.solver == "dpmpp2m_sde" and self.eta > 0.0
 
-    def _sde_update(self, x, eps, ctr, t_vec, tabs, cond: bool):
-        """the per-window 'dpmpp2m_sde' update: ib_sde_dpmpp_step over the state seen as [B, 1, T, ld] -- every window a
-        trial of its own (the layout stitch_layout(T, T, T)), the window ids as trial ids"""
-        b = self._bufs
-        v = lambda t: t.unsqueeze(1)
-        x0, z, m, oc, on = (v(b["x0"]), v(b["z"]), b["mask"], tabs.obs_coef, tabs.sde_obs_noise_coef) if cond \
-            else (None, None, None, None, None)
-        start, cover, wn = b["one_window"]
-        hip.sde_dpmpp_step(v(x), v(eps), v(b["hist"]), x0, z, m, tabs.sde_coef, oc, on, tabs.ddim_t, start, cover, wn,
-                           b["win"], self.seed, step_dev=ctr, t_out=t_vec, D=self._D)
+    def _call(self, x_T: torch.Tensor, N: int, W: int, ids=None, observed=None, mask=None, lay=None) -> SampleCall:
+        """the record of a call whose window batch is x_T [N * W, T, D]"""
+        m = self.model
+        B, T, D = x_T.shape
+        plan = m._get_plan(next(m.parameters()).device)
+        Dp = plan.infer_pitch(D) if (hasattr(plan, "infer_pitch") and m.compute_dtype == torch.bfloat16) else D
+        return SampleCall(B, T, D, Dp, N, W, ids, observed, mask, lay)
 
-    def _update(self, x, eps, ctr, t_vec, tabs):
-        if self._sde():
-            self._sde_update(x, eps, ctr, t_vec, tabs, False)
-        elif self._second():
-            hip.dpmpp_step(x, eps, self._bufs["hist"], tabs.dpmpp_coef, tabs.ddim_t, step_dev=ctr, t_out=t_vec)
-        elif self.eta == 0.0:
-            hip.ddim_step(x, eps, tabs.ddim_coef, tabs.ddim_t, step_dev=ctr, t_out=t_vec)
-        else:
-            hip.ddim_step_noise(x, eps, tabs.ddim_coef_eta, tabs.ddim_t, self._bufs["win"], self.seed, step_dev=ctr,
-                                t_out=t_vec, D=self._D)
-
-    def _noise_sig(self, tabs) -> tuple:
-        """eta and, for a stochastic loop, what its update launch bakes in: the seed and the eta tables' pointers"""
-        if self.eta == 0.0:
-            return (0.0,)
-        if self._sde():
-            return (self.eta, self.seed, tabs.sde_coef.data_ptr(), tabs.sde_obs_noise_coef.data_ptr())
-        return (self.eta, self.seed, tabs.ddim_coef_eta.data_ptr(), tabs.obs_noise_coef.data_ptr())
-
-    def _solver_sig(self, tabs) -> tuple:
-        """solver and grid, and the table a 'dpmpp2m' update launch bakes in; nothing at the defaults"""
-        if self.solver == "ddim" and self.spacing == "time":
-            return ()
-        return (self.solver, self.spacing, tabs.dpmpp_coef.data_ptr() if self._second() else 0)
-
-    def _set_window_ids(self, B: int):
-        """copies the call's window ids (default 0 .. B-1) into the device buffer the captured update reads"""
-        ids = self._win
-        ids = torch.arange(B, dtype=torch.int64) if ids is None else torch.as_tensor(ids, dtype=torch.int64).reshape(-1).cpu()
-        if ids.numel() != B:
-            raise ValueError(f"window_ids must hold one id per window ({B}), got {ids.numel()}")
-        if B and (int(ids.min()) < 0 or int(ids.max()) >= 1 << 32):
-            raise ValueError("window_ids must be in 0 .. 2^32 - 1 (one word of the generator's counter)")
-        self._bufs["win"].copy_(ids)
-
-    def _noise_ids(self, B: int) -> int:
-        """how many ids key the step noise of a batch of B windows: one per window (a subclass may key it otherwise)"""
-        return B
-
-    def _extra_buffers(self, B, T, D, Dp, dev, dtype):
-        """more device buffers that live as long as the captured step (a subclass's)"""
-        return {}
-
-    def _extra_sig(self, tabs) -> tuple:
-        return ()
-
-    def _observations(self) -> Optional[str]:
-        """the kind of observation table the loop reads (schedule.OBSERVATIONS); None: it reads none"""
-        return None
-
-    def _begin(self, x, tabs):
-        """runs once x holds the start draw, before the first step (a subclass's start state)"""
+    def _check_observations(self, mask: torch.Tensor, noun: str):
+        """a masked call's check of `observations` (the attribute may be changed between calls) and, in 'clean' mode, of
+        its mask, whose last dimension is D: the model was trained with exactly its first cond_cols columns clean and
+        nothing else.  The verdict is kept per mask tensor (held, so its address is not reused), its version counter and
+        cond_cols: a loop that passes the same mask again compares nothing and, with a device mask, does not wait for the
+        device."""
+        if self.observations not in OBSERVATIONS:
+            raise ValueError(f"observations must be one of {OBSERVATIONS}, got {self.observations!r}")
+        if self.observations != "clean":
+            return
+        C, D = int(getattr(self.model, "cond_cols", 0)), mask.shape[-1]
+        key = (mask._version, C)
+        if self._mask_ok is not None and self._mask_ok[0] is mask and self._mask_ok[1] == key:
+            return
+        want = torch.zeros(mask.shape, dtype=torch.bool, device=mask.device)
+        want[..., :max(C, 0)] = True
+        if not 0 < C < D or not torch.equal(mask, want):
+            self._mask_ok = None
+            raise ValueError(f"observations='clean': {noun} must mark exactly the first cond_cols columns the denoiser was "
+                             f"trained on (`train --cond-cols N`, 0 < N < {D}) as observed and no other element; this "
+                             f"model's cond_cols is {C}")
+        self._mask_ok = (mask, key)
 
     @torch.no_grad()
     def sample(self, x_T: torch.Tensor, steps: Optional[int] = None,
@@ -139,24 +146,20 @@ class DDIMSampler:
         """x_T [B,T,D] ~ N(0,1) -> x_0.  `steps` (<= num_sample_steps) truncates the loop (benchmarks).  window_ids (default
         0 .. B-1): with eta > 0 the step noise of window b is keyed by (seed, window_ids[b], step), whatever its place in
         the batch; unused at eta = 0."""
-        self._win = window_ids
-        try:
-            return self._sample_on_stream(x_T, steps)
-        finally:
-            self._win = None
+        return self._run(self._call(x_T, x_T.shape[0], 1, window_ids), x_T, steps)
 
-    def _sample_on_stream(self, x_T: torch.Tensor, steps: Optional[int]) -> torch.Tensor:
+    def _run(self, c: SampleCall, x_T: torch.Tensor, steps: Optional[int]) -> torch.Tensor:
         if not x_T.is_cuda and not hip._dry_run:
             x_T = x_T.to(next(self.model.parameters()).device)
         if hip._dry_run:
-            return self._sample(x_T, steps)
+            return self._sample(c, x_T, steps)
         # hipGraph capture is not allowed on the legacy default stream -> run on a side stream
-        if getattr(self, "_stream", None) is None:
+        if self._stream is None:
             self._stream = hip.new_stream(x_T.device)
         cur = torch.cuda.current_stream()
         self._stream.wait_stream(cur)
         with torch.cuda.stream(self._stream):
-            out = self._sample(x_T, steps)
+            out = self._sample(c, x_T, steps)
         cur.wait_stream(self._stream)
         return out
 
@@ -176,77 +179,164 @@ class DDIMSampler:
         hip.diffusion_draw(seed, step=int(draw), stream_id=0x40000000, eps=x_T)
         return x_T
 
-    def _sample(self, x_T: torch.Tensor, steps: Optional[int] = None) -> torch.Tensor:
+    def _prepare(self, c: SampleCall, tabs, dev):
+        """the signature of the captured step and the device buffers that live as long as it does; a new signature drops
+        the graph and makes new buffers.  The captured step bakes in raw pointers: the model's flat parameter buffer and
+        bf16 shadow (a HipTrainer built after a first sample() re-packs them), the schedule tables (set_sampler() of another
+        sampler re-creates them), the layout's tables -- all of them are part of the signature, so a change re-captures
+        instead of replaying stale pointers.  Then, per kind of loop: the observation table's pointer and its kind (a table
+        made for the other mode may come back at a freed table's address); solver and grid and the second-order table,
+        nothing at the defaults; eta and, for a stochastic loop, the seed and its solver's eta tables."""
+        m, lay = self.model, c.lay
+        B, T, D, Dp = c.B, c.T, c.D, c.Dp
+        second, noisy, sde, cond = self._second(), self.eta > 0.0, self._sde(), c.observed is not None
+        ptr = lambda t: t.data_ptr()
+        sig = ((B, T, D), m.compute_dtype, ptr(m._flat), ptr(m._shadow) if m._shadow is not None else 0, ptr(tabs.temb),
+               ptr(tabs.ddim_coef), ptr(tabs.ddim_t), self.S, Dp)
+        if lay is not None:
+            sig += ("stitch", c.N, lay["F"], self.hop, self.blend, ptr(lay["start"]), ptr(lay["cover"]), ptr(lay["wn"]))
+        if cond:
+            sig += (ptr(tabs.obs_coef), tabs.observations)
+        if self.solver != "ddim" or self.spacing != "time":
+            sig += (self.solver, self.spacing, ptr(tabs.dpmpp_coef) if second else 0)
+        if sde:
+            sig += (self.eta, self.seed, ptr(tabs.sde_coef), ptr(tabs.sde_obs_noise_coef))
+        elif noisy:
+            sig += (self.eta, self.seed, ptr(tabs.ddim_coef_eta), ptr(tabs.obs_noise_coef))
+        else:
+            sig += (0.0,)
+        if sig == self._sig:
+            return
+        state = lambda dtype=m.compute_dtype: torch.zeros((B, T, Dp), dtype=dtype, device=dev)
+        bufs = {"x": state(), "t": torch.empty(B, dtype=torch.int64, device=dev),
+                "ctr": torch.zeros(1, dtype=torch.int32, device=dev)}
+        if Dp != D:
+            bufs["eps"] = state()
+        if cond:
+            # pitched like the state, pad columns 0 (the mask's pad columns are free, so they stay 0 in x)
+            bufs.update(x0=state(), z=state(), mask=torch.zeros((T, Dp), dtype=torch.uint8, device=dev))
+        if noisy:
+            bufs["win"] = torch.zeros(c.N, dtype=torch.int64, device=dev)       # one id per trial (per window at W = 1)
+        if second:
+            # the previous step's data prediction, fp32 whatever the state's dtype, pitched like the state.  The first
+            # row of the table does not read it, so a new batch needs no reset
+            bufs["hist"] = state(torch.float32)
+        if sde:
+            bufs["one_window"] = tuple(t.to(dev) for t in stitch_layout(T, T, T)[:3])
+        self._sig, self._graph, self._bufs = sig, None, bufs
+
+    def _start_masked(self, c: SampleCall, x, tabs):
+        """the masked loop's start state, once x holds the start draw: the observation, the mask and the draw z go into
+        their buffers and ib_ddim_cond_init pins the observed elements"""
+        D = c.D
+        x0, z, m = self._bufs["x0"], self._bufs["z"], self._bufs["mask"]
+        x0[:, :, :D].copy_(c.observed.to(device=x0.device, dtype=x0.dtype))
+        m[:, :D].copy_(c.mask.to(device=m.device, dtype=torch.uint8))
+        z.copy_(x)
+        hip.ddim_cond_init(x, x0, z, m, tabs.obs_coef, D=D)
+        if c.W > 1:
+            # the invariant at the start: every copy of a trial element holds its first copy's bits (the start kernel rounds
+            # by position in the window batch, which differs between the copies when the row pitch is no multiple of 8)
+            x.copy_(_cut(c.lay, _join(c.lay, x, c.N)))
+
+    def _sample(self, c: SampleCall, x_T: torch.Tensor, steps: Optional[int] = None) -> torch.Tensor:
+        ids = _checked_ids(c.ids, c.N, "window" if c.lay is None else "trial") if self.eta > 0.0 else None
         m = self.model
         m.ensure_packed()
         m.sync_shadow()
         dev = m._flat.device
         tabs = m.tables(dev)
-        obs = self._observations()
+        obs = self.observations if c.observed is not None else None
         if not tabs.serves(self.S, self.eta, self.solver, self.spacing, obs):
             tabs.set_sampler(self.S, self.eta, self.solver, self.spacing, observations=obs or tabs.observations)
-        # the captured step bakes in raw pointers: the model's flat parameter buffer and bf16 shadow (a HipTrainer built
-        # after a first sample() re-packs them), the schedule tables (set_sampler() of another sampler re-creates the DDIM
-        # tables) -- all of them are part of the signature, so a change re-captures instead of replaying stale pointers
-        shadow = m._shadow.data_ptr() if m._shadow is not None else 0
-        sig = (tuple(x_T.shape), m.compute_dtype, m._flat.data_ptr(), shadow, tabs.temb.data_ptr(),
-               tabs.ddim_coef.data_ptr(), tabs.ddim_t.data_ptr(), self.S)
         plan = m._get_plan(dev)
-        B, T, D = x_T.shape
-        Dp = plan.infer_pitch(D) if (hasattr(plan, "infer_pitch") and m.compute_dtype == torch.bfloat16) else D
-        sig = sig + (Dp,) + self._extra_sig(tabs) + self._solver_sig(tabs) + self._noise_sig(tabs)
-        if sig != self._sig:
-            self._sig, self._graph = sig, None
-            self._bufs = {"x": torch.zeros((B, T, Dp), dtype=m.compute_dtype, device=dev),
-                          "t": torch.empty(x_T.shape[0], dtype=torch.int64, device=dev),
-                          "ctr": torch.zeros(1, dtype=torch.int32, device=dev)}
-            if Dp != D:
-                self._bufs["eps"] = torch.zeros((B, T, Dp), dtype=m.compute_dtype, device=dev)
-            self._bufs.update(self._extra_buffers(B, T, D, Dp, dev, m.compute_dtype))
-            if self.eta > 0.0:
-                self._bufs["win"] = torch.zeros(self._noise_ids(B), dtype=torch.int64, device=dev)
-            if self._second():
-                # the previous step's data prediction, fp32 whatever the state's dtype, pitched like the state.  The first
-                # row of the table does not read it, so a new batch needs no reset
-                self._bufs["hist"] = torch.zeros((B, T, Dp), dtype=torch.float32, device=dev)
-            if self._sde():
-                self._bufs["one_window"] = tuple(t.to(dev) for t in stitch_layout(T, T, T)[:3])
-        self._D = D
-        if self.eta > 0.0:
-            self._set_window_ids(B)
+        self._prepare(c, tabs, dev)
+        if ids is not None:
+            self._bufs["win"].copy_(ids)
         x, t_vec, ctr = self._bufs["x"], self._bufs["t"], self._bufs["ctr"]
-        x[:, :, :D].copy_(x_T.to(device=dev, dtype=m.compute_dtype))
-        self._begin(x, tabs)
+        x[:, :, :c.D].copy_(x_T.to(device=dev, dtype=m.compute_dtype))
+        if c.observed is not None:
+            self._start_masked(c, x, tabs)
         ctr.zero_()
         hip.fill_i64(t_vec, int(tabs.ddim_t[0]))
         P = m.param_source()
         if hasattr(plan, "set_inference"):
             plan.set_inference(True)             # weights are frozen for the whole loop
-            plan.prepare_inference(P, T, D, table=tabs.temb)
+            plan.prepare_inference(P, c.T, c.D, table=tabs.temb)
         try:
-            return self._loop(x, t_vec, ctr, tabs, P, steps)
+            return self._loop(c, x, t_vec, ctr, tabs, P, steps)
         finally:
             if hasattr(plan, "set_inference"):
                 plan.set_inference(False)
 
-    def _loop(self, x, t_vec, ctr, tabs, P, steps):
+    def _loop(self, c: SampleCall, x, t_vec, ctr, tabs, P, steps):
         n = self.S if steps is None else min(steps, self.S)
         done = 0
         if self.use_graph and self._graph is None:
-            self._step_launches(x, t_vec, ctr, tabs, P)          # eager warm-up step allocates plan buffers
+            self._step_launches(c, x, t_vec, ctr, tabs, P)       # eager warm-up step allocates plan buffers
             done = 1
             if n > 1:
                 g = hip.Graph()
                 g.begin()
-                self._step_launches(x, t_vec, ctr, tabs, P)
+                self._step_launches(c, x, t_vec, ctr, tabs, P)
                 g.end()
                 self._graph = g
         for _ in range(done, n):
             if self._graph is not None:
                 self._graph.launch()
             else:
-                self._step_launches(x, t_vec, ctr, tabs, P)
-        return x[:, :, :self._D].clone()
+                self._step_launches(c, x, t_vec, ctr, tabs, P)
+        return x[:, :, :c.D].clone()
+
+    def _step_launches(self, c: SampleCall, x, t_vec, ctr, tabs, P: ParamSource):
+        plan = self.model._get_plan(x.device)
+        eps_buf = self._bufs.get("eps")
+        if eps_buf is not None:
+            # pitched state / noise buffers [B, T, Dp] with zero pad columns (plans.infer_pitch): the plan sees row-padded
+            # 2-D views; the DDIM update runs over the whole pitched buffers (0 stays 0 in the pad columns)
+            B, T, Dp = x.shape
+            plan.forward(x.view(B * T, Dp)[:, :c.D], t_vec, tabs.temb, P, out=eps_buf.view(B * T, Dp)[:, :c.D], BT=(B, T))
+            self._launch_update(c, x, eps_buf, ctr, t_vec, tabs)
+        else:
+            self._launch_update(c, x, plan.forward(x, t_vec, tabs.temb, P), ctr, t_vec, tabs)
+        hip.counter_add(ctr, 1)
+
+    def _launch_update(self, c: SampleCall, x, eps, ctr, t_vec, tabs):
+        """THE choice of the update launch (the module docstring's table): by layout, solver order, eta > 0, observations"""
+        b, lay = self._bufs, c.lay
+        second, noisy, sde, cond = self._second(), self.eta > 0.0, self._sde(), c.observed is not None
+        # the stitched entries and ib_sde_dpmpp_step see the state as [N, W, T, ld]: a per-window 'dpmpp2m_sde' loop as
+        # [B, 1, T, ld], every window a trial of its own (the layout stitch_layout(T, T, T)), the window ids as trial ids
+        wide = lay is not None or sde
+        v = (lambda t: t.view((c.N, c.W) + tuple(t.shape[1:]))) if wide else (lambda t: t)
+        x0, z, m, oc, on = (v(b["x0"]), v(b["z"]), b["mask"], tabs.obs_coef,
+                            tabs.sde_obs_noise_coef if sde else tabs.obs_noise_coef) if cond else (None,) * 5
+        windows = (lay["start"], lay["cover"], lay["wn"]) if lay is not None else b.get("one_window")
+        step = dict(step_dev=ctr, t_out=t_vec)
+        if sde:
+            hip.sde_dpmpp_step(v(x), v(eps), v(b["hist"]), x0, z, m, tabs.sde_coef, oc, on, tabs.ddim_t, *windows, b["win"],
+                               self.seed, D=c.D, **step)
+        elif lay is not None and noisy:
+            hip.stitch_ddim_step_noise(v(x), v(eps), x0, z, m, tabs.ddim_coef_eta, oc, on, tabs.ddim_t, *windows, b["win"],
+                                       self.seed, D=c.D, **step)
+        elif lay is not None and second:
+            hip.stitch_dpmpp_step(v(x), v(eps), v(b["hist"]), x0, z, m, tabs.dpmpp_coef, oc, tabs.ddim_t, *windows, D=c.D,
+                                  **step)
+        elif lay is not None:
+            hip.stitch_ddim_step(v(x), v(eps), x0, z, m, tabs.ddim_coef, oc, tabs.ddim_t, *windows, D=c.D, **step)
+        elif second and cond:
+            hip.dpmpp_cond_step(x, eps, b["hist"], x0, z, m, tabs.dpmpp_coef, oc, tabs.ddim_t, D=c.D, **step)
+        elif second:
+            hip.dpmpp_step(x, eps, b["hist"], tabs.dpmpp_coef, tabs.ddim_t, **step)
+        elif noisy and cond:
+            hip.ddim_cond_step_noise(x, eps, x0, z, m, tabs.ddim_coef_eta, oc, on, tabs.ddim_t, b["win"], self.seed, D=c.D,
+                                     **step)
+        elif noisy:
+            hip.ddim_step_noise(x, eps, tabs.ddim_coef_eta, tabs.ddim_t, b["win"], self.seed, D=c.D, **step)
+        elif cond:
+            hip.ddim_cond_step(x, eps, x0, z, m, tabs.ddim_coef, oc, tabs.ddim_t, D=c.D, **step)
+        else:
+            hip.ddim_step(x, eps, tabs.ddim_coef, tabs.ddim_t, **step)
 
 
 class ConditionalDDIMSampler(DDIMSampler):
@@ -271,37 +361,10 @@ class ConditionalDDIMSampler(DDIMSampler):
 
     def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True, eta: float = 0.0,
                  seed: Optional[int] = None, solver: str = "ddim", spacing: str = "time", observations: str = "noised"):
+        check_sampler_settings(eta, solver, spacing, observations)
         super().__init__(model, num_sample_steps, use_graph, eta, seed, solver, spacing)
-        if observations not in OBSERVATIONS:
-            raise ValueError(f"observations must be one of {OBSERVATIONS}, got {observations!r}")
         self.observations = observations
-        self._cond = None
         self._mask_ok = None                 # (mask, (version, cond_cols)) of the last mask 'clean' mode accepted
-
-    def _observations(self) -> Optional[str]:
-        if self.observations not in OBSERVATIONS:
-            raise ValueError(f"observations must be one of {OBSERVATIONS}, got {self.observations!r}")
-        return self.observations
-
-    def _check_clean_mask(self, mask: torch.Tensor):
-        """'clean' mode: the model was trained with exactly its first cond_cols columns clean and nothing else"""
-        C = int(getattr(self.model, "cond_cols", 0))
-        T, D = mask.shape
-        if not 0 < C < D:
-            raise ValueError(f"observations='clean' needs a denoiser trained with --cond-cols N, 0 < N < {D}; this model's "
-                             f"cond_cols is {C}")
-        # the verdict is kept per mask tensor (held, so its address is not reused), its version counter and C: a loop that
-        # passes the same mask again compares nothing and, with a device mask, does not wait for the device
-        key = (mask._version, C)
-        if self._mask_ok is not None and self._mask_ok[0] is mask and self._mask_ok[1] == key:
-            return
-        want = torch.zeros((T, D), dtype=torch.bool, device=mask.device)
-        want[:, :C] = True
-        if not torch.equal(mask, want):
-            self._mask_ok = None
-            raise ValueError(f"observations='clean': the mask must mark the first cond_cols = {C} columns of every frame as "
-                             f"observed and no other element (the model was trained on nothing else)")
-        self._mask_ok = (mask, key)
 
     @torch.no_grad()
     def sample(self, x_T: torch.Tensor, observed: torch.Tensor, mask: torch.Tensor,
@@ -314,13 +377,8 @@ class ConditionalDDIMSampler(DDIMSampler):
             raise ValueError(f"observed must be {(B, T, D)} like x_T, got {tuple(observed.shape)}")
         if tuple(mask.shape) != (T, D) or mask.dtype != torch.bool:
             raise ValueError(f"mask must be a [T, D] = {(T, D)} bool tensor, got {tuple(mask.shape)} {mask.dtype}")
-        if self._observations() == "clean":
-            self._check_clean_mask(mask)
-        self._cond = (observed, mask)
-        try:
-            return super().sample(x_T, steps, window_ids)
-        finally:
-            self._cond = None
+        self._check_observations(mask, "the mask")
+        return self._run(self._call(x_T, B, 1, window_ids, observed, mask), x_T, steps)
 
     @torch.no_grad()
     def sample_noise(self, batch: int, window: int, feat: int, observed: torch.Tensor, mask: torch.Tensor,
@@ -328,42 +386,6 @@ class ConditionalDDIMSampler(DDIMSampler):
                      window_ids=None) -> torch.Tensor:
         """as DDIMSampler.sample_noise: z = x_T drawn on the device from (seed, draw)"""
         return self.sample(self.draw_start(batch, window, feat, seed, draw), observed, mask, steps, window_ids)
-
-    def _extra_sig(self, tabs) -> tuple:
-        # the table's pointer and its kind: a table made for the other mode may come back at a freed table's address
-        return (tabs.obs_coef.data_ptr(), tabs.observations)
-
-    def _extra_buffers(self, B, T, D, Dp, dev, dtype):
-        # pitched like the state, pad columns 0 (the mask's pad columns are free, so they stay 0 in x)
-        return {"x0": torch.zeros((B, T, Dp), dtype=dtype, device=dev),
-                "z": torch.zeros((B, T, Dp), dtype=dtype, device=dev),
-                "mask": torch.zeros((T, Dp), dtype=torch.uint8, device=dev)}
-
-    def _begin(self, x, tabs):
-        if self._cond is None:
-            raise RuntimeError("ConditionalDDIMSampler: call sample(x_T, observed, mask)")
-        observed, mask = self._cond
-        D = self._D
-        x0, z, m = self._bufs["x0"], self._bufs["z"], self._bufs["mask"]
-        x0[:, :, :D].copy_(observed.to(device=x0.device, dtype=x0.dtype))
-        m[:, :D].copy_(mask.to(device=m.device, dtype=torch.uint8))
-        z.copy_(x)
-        hip.ddim_cond_init(x, x0, z, m, tabs.obs_coef, D=D)
-
-    def _update(self, x, eps, ctr, t_vec, tabs):
-        b = self._bufs
-        if self._sde():
-            self._sde_update(x, eps, ctr, t_vec, tabs, True)
-        elif self._second():
-            hip.dpmpp_cond_step(x, eps, b["hist"], b["x0"], b["z"], b["mask"], tabs.dpmpp_coef, tabs.obs_coef, tabs.ddim_t,
-                                step_dev=ctr, t_out=t_vec, D=self._D)
-        elif self.eta == 0.0:
-            hip.ddim_cond_step(x, eps, b["x0"], b["z"], b["mask"], tabs.ddim_coef, tabs.obs_coef, tabs.ddim_t, step_dev=ctr,
-                               t_out=t_vec, D=self._D)
-        else:
-            hip.ddim_cond_step_noise(x, eps, b["x0"], b["z"], b["mask"], tabs.ddim_coef_eta, tabs.obs_coef,
-                                     tabs.obs_noise_coef, tabs.ddim_t, b["win"], self.seed, step_dev=ctr, t_out=t_vec,
-                                     D=self._D)
 
 
 class StitchedDDIMSampler(DDIMSampler):
@@ -394,9 +416,8 @@ class StitchedDDIMSampler(DDIMSampler):
         if float(eta) != 0.0:
             raise ValueError(f"StitchedDDIMSampler is deterministic: eta must be 0, got {eta} (the step noise of an eta > 0 "
                              f"loop is keyed by window and in-window frame, not by trial frame)")
+        check_sampler_settings(0.0, solver, spacing, observations)
         super().__init__(model, num_sample_steps, use_graph, 0.0, seed, solver, spacing)
-        if observations not in OBSERVATIONS:
-            raise ValueError(f"observations must be one of {OBSERVATIONS}, got {observations!r}")
         self.observations = observations
         if getattr(model, "window", None) is None:
             raise ValueError("StitchedDDIMSampler needs a denoiser that states its window (model.window frames)")
@@ -404,7 +425,6 @@ class StitchedDDIMSampler(DDIMSampler):
         self.hop = self.T // 2 if hop is None else int(hop)
         self.blend = blend
         stitch_layout(3 * self.T, self.T, self.hop, blend)     # refuses a bad hop or blend here, not at the first call
-        self._cond = None
         self._lay = None                     # the layout of the last trial length sampled, the only one kept
         self._mask_ok = None                 # (mask_cols, (version, cond_cols)) of the last mask 'clean' mode accepted
 
@@ -432,33 +452,7 @@ class StitchedDDIMSampler(DDIMSampler):
         arithmetic)"""
         if self._lay is None or trial.dim() != 3 or trial.shape[1] != self._lay["F"]:
             raise ValueError(f"to_windows: a [N, F, D] trial of the last sampled length is needed, got {tuple(trial.shape)}")
-        N, F, D = trial.shape
-        return trial[:, self._lay["gather"].to(trial.device)].reshape(N * self._lay["W"], self.T, D)
-
-    def _to_trial(self, windows: torch.Tensor, N: int) -> torch.Tensor:
-        """[N * W, T, D] -> [N, F, D] from each frame's first copy"""
-        lay = self._lay
-        w = windows.view(N, lay["W"], self.T, windows.shape[-1])
-        return w[:, lay["w0"].to(w.device), lay["t0"].to(w.device)].contiguous()
-
-    def _observations(self) -> Optional[str]:
-        return None if self._cond is None else self.observations      # sample() checked the attribute for this call
-
-    def _check_clean_cols(self, mask_cols: torch.Tensor, D: int):
-        """'clean' mode: the model was trained with exactly its first cond_cols columns clean.  The verdict is kept per mask
-        tensor, its version and cond_cols (as ConditionalDDIMSampler keeps it), so a loop that passes the same mask again
-        compares nothing and, with a device mask, does not wait for the device."""
-        C = int(getattr(self.model, "cond_cols", 0))
-        key = (mask_cols._version, C)
-        if self._mask_ok is not None and self._mask_ok[0] is mask_cols and self._mask_ok[1] == key:
-            return
-        want = torch.zeros(D, dtype=torch.bool, device=mask_cols.device)
-        want[:max(C, 0)] = True
-        if not 0 < C < D or not torch.equal(mask_cols, want):
-            self._mask_ok = None
-            raise ValueError(f"observations='clean': mask_cols must mark exactly the first cond_cols columns the denoiser "
-                             f"was trained on (`train --cond-cols N`, 0 < N < {D}); this model's cond_cols is {C}")
-        self._mask_ok = (mask_cols, key)
+        return _cut(self._lay, trial)
 
     @torch.no_grad()
     def sample(self, z: torch.Tensor, observed: Optional[torch.Tensor] = None, mask_cols: Optional[torch.Tensor] = None,
@@ -466,6 +460,9 @@ class StitchedDDIMSampler(DDIMSampler):
         """z [N, F, D] ~ N(0, 1), the trial's start draw -> x_0 [N, F, D].  observed [N, F, D] and mask_cols [D] bool (True:
         the column is observed in every frame) come together; the result equals the observation, in the compute dtype, in
         those columns.  `steps` truncates the loop."""
+        return self._sample_trials(z, observed, mask_cols, steps, None)
+
+    def _sample_trials(self, z, observed, mask_cols, steps, trial_ids) -> torch.Tensor:
         if z.dim() != 3:
             raise ValueError(f"z must be [N, F, D], got {tuple(z.shape)}")
         N, F, D = z.shape
@@ -477,19 +474,16 @@ class StitchedDDIMSampler(DDIMSampler):
             if not isinstance(mask_cols, torch.Tensor) or tuple(mask_cols.shape) != (D,) or mask_cols.dtype != torch.bool:
                 raise ValueError(f"mask_cols must be a [D] = [{D}] bool tensor (the same columns are observed in every "
                                  f"frame), got {tuple(getattr(mask_cols, 'shape', ()))} {getattr(mask_cols, 'dtype', None)}")
-            if self.observations not in OBSERVATIONS:           # the attribute may be changed between calls
-                raise ValueError(f"observations must be one of {OBSERVATIONS}, got {self.observations!r}")
-            if self.observations == "clean":
-                self._check_clean_cols(mask_cols, D)
-        dev = z.device if (z.is_cuda or hip._dry_run) else next(self.model.parameters()).device
-        self._lay = self._layout(F, dev)                       # refuses F < model.window
-        self._N = N
-        self._cond = None if observed is None else (observed, mask_cols)
-        try:
-            out = super().sample(self.to_windows(z.to(dev)), steps)
-            return self._to_trial(out, N)
-        finally:
-            self._cond = None
+            self._check_observations(mask_cols, "mask_cols")
+        m = self.model
+        dev = z.device if (z.is_cuda or hip._dry_run) else next(m.parameters()).device
+        lay = self._lay = self._layout(F, dev)                 # refuses F < model.window
+        x_T = _cut(lay, z.to(dev))
+        if observed is not None:
+            observed = _cut(lay, observed.to(device=dev, dtype=m.compute_dtype))
+            mask_cols = mask_cols.to(device=dev, dtype=torch.uint8)[None, :].expand(self.T, D)
+        c = self._call(x_T, N, lay["W"], trial_ids, observed, mask_cols, lay)
+        return _join(lay, self._run(c, x_T, steps), N)
 
     @torch.no_grad()
     def sample_noise(self, batch: int, frames: int, feat: int, observed: Optional[torch.Tensor] = None,
@@ -497,47 +491,6 @@ class StitchedDDIMSampler(DDIMSampler):
                      steps: Optional[int] = None) -> torch.Tensor:
         """as DDIMSampler.sample_noise: z [batch, frames, feat] drawn on the device from (seed, draw)"""
         return self.sample(self.draw_start(batch, frames, feat, seed, draw), observed, mask_cols, steps)
-
-    def _extra_sig(self, tabs) -> tuple:
-        lay = self._lay
-        cond = () if self._cond is None else (tabs.obs_coef.data_ptr(), tabs.observations)
-        return ("stitch", self._N, lay["F"], self.hop, self.blend, lay["start"].data_ptr(), lay["cover"].data_ptr(),
-                lay["wn"].data_ptr()) + cond
-
-    def _extra_buffers(self, B, T, D, Dp, dev, dtype):
-        if self._cond is None:
-            return {}
-        return {"x0": torch.zeros((B, T, Dp), dtype=dtype, device=dev),
-                "z": torch.zeros((B, T, Dp), dtype=dtype, device=dev),
-                "mask": torch.zeros((T, Dp), dtype=torch.uint8, device=dev)}
-
-    def _begin(self, x, tabs):
-        if self._cond is None:
-            return
-        observed, mask_cols = self._cond
-        D = self._D
-        x0, z, m = self._bufs["x0"], self._bufs["z"], self._bufs["mask"]
-        x0[:, :, :D].copy_(self.to_windows(observed.to(device=x0.device, dtype=x0.dtype)))
-        m[:, :D].copy_(mask_cols.to(device=m.device, dtype=torch.uint8)[None, :].expand(m.shape[0], D))
-        z.copy_(x)
-        hip.ddim_cond_init(x, x0, z, m, tabs.obs_coef, D=D)
-        if self._lay["W"] > 1:
-            # the invariant at the start: every copy of a trial element holds its first copy's bits (the start kernel rounds
-            # by position in the window batch, which differs between the copies when the row pitch is no multiple of 8)
-            x.copy_(self.to_windows(self._to_trial(x, self._N)))
-
-    def _update(self, x, eps, ctr, t_vec, tabs):
-        b, lay = self._bufs, self._lay
-        shape = (self._N, lay["W"]) + tuple(x.shape[1:])
-        v = lambda t: t.view(shape)
-        cond = self._cond is not None
-        x0, z, m, oc = (v(b["x0"]), v(b["z"]), b["mask"], tabs.obs_coef) if cond else (None, None, None, None)
-        if self._second():
-            hip.stitch_dpmpp_step(v(x), v(eps), v(b["hist"]), x0, z, m, tabs.dpmpp_coef, oc, tabs.ddim_t, lay["start"],
-                                  lay["cover"], lay["wn"], step_dev=ctr, t_out=t_vec, D=self._D)
-        else:
-            hip.stitch_ddim_step(v(x), v(eps), x0, z, m, tabs.ddim_coef, oc, tabs.ddim_t, lay["start"], lay["cover"],
-                                 lay["wn"], step_dev=ctr, t_out=t_vec, D=self._D)
 
 
 class StochasticStitchedSampler(StitchedDDIMSampler):
@@ -551,8 +504,8 @@ class StochasticStitchedSampler(StitchedDDIMSampler):
     F == T it is ConditionalDDIMSampler(eta, seed) (or DDIMSampler without observations) with window ids = trial ids.  The
     solver is 'ddim' unless the keyword solver = 'dpmpp2m_sde' is given: the stochastic second-order update
     (ib_sde_dpmpp_step, csrc/sde.hip; it belongs with spacing = 'logsnr'), under the same keys.  'dpmpp2m' stays
-    deterministic and is StitchedDDIMSampler's.  The trial ids live in a device buffer the captured update reads, so a new
-    batch or new ids of the same shape replay the captured step."""
+    deterministic and is StitchedDDIMSampler's.  The trial ids live in a device buffer the captured update reads ('win',
+    one id per TRIAL), so a new batch or new ids of the same shape replay the captured step."""
 
     def __init__(self, model, num_sample_steps: int = 100, eta: float = 1.0, hop: Optional[int] = None, blend: str = "ramp",
                  use_graph: bool = True, spacing: str = "time", observations: str = "noised", seed: Optional[int] = None,
@@ -563,27 +516,21 @@ class StochasticStitchedSampler(StitchedDDIMSampler):
         solver = keywords.pop("solver", "ddim")
         if keywords:
             raise TypeError(f"StochasticStitchedSampler: unexpected keyword arguments {sorted(keywords)}")
-        if not 0.0 <= float(eta) <= 1.0:
-            raise ValueError(f"eta must be in [0, 1], got {eta}")
         if solver == "dpmpp2m":
             raise ValueError("solver 'dpmpp2m' is deterministic: use StitchedDDIMSampler for it; the stochastic loop takes "
                              "'ddim' or 'dpmpp2m_sde'")
         if solver not in ("ddim", "dpmpp2m_sde"):
             raise ValueError(f"solver must be 'ddim' or 'dpmpp2m_sde', got {solver!r}")
+        check_sampler_settings(eta, solver, spacing, observations)
         super().__init__(model, num_sample_steps, hop, blend, use_graph, solver, spacing, observations, seed)
         self.eta = float(eta)                # the parent's constructor hands DDIMSampler eta = 0
-        self._tid = None
 
     @torch.no_grad()
     def sample(self, z: torch.Tensor, observed: Optional[torch.Tensor] = None, mask_cols: Optional[torch.Tensor] = None,
                steps: Optional[int] = None, trial_ids: Union[None, Sequence[int], torch.Tensor] = None) -> torch.Tensor:
         """as StitchedDDIMSampler.sample.  trial_ids (default 0 .. N-1): the step noise of trial n is keyed by (seed,
         trial_ids[n], step), whatever its place in the batch; unused at eta = 0."""
-        self._tid = trial_ids
-        try:
-            return super().sample(z, observed, mask_cols, steps)
-        finally:
-            self._tid = None
+        return self._sample_trials(z, observed, mask_cols, steps, trial_ids)
 
     @torch.no_grad()
     def sample_noise(self, batch: int, frames: int, feat: int, observed: Optional[torch.Tensor] = None,
@@ -591,36 +538,3 @@ class StochasticStitchedSampler(StitchedDDIMSampler):
                      steps: Optional[int] = None, trial_ids=None) -> torch.Tensor:
         """as StitchedDDIMSampler.sample_noise, with the trial ids of sample()"""
         return self.sample(self.draw_start(batch, frames, feat, seed, draw), observed, mask_cols, steps, trial_ids)
-
-    def _noise_ids(self, B: int) -> int:
-        return self._N                       # the 'win' buffer holds one id per TRIAL, not one per window (B = N W)
-
-    def _set_window_ids(self, B: int):
-        """DDIMSampler._sample asks for one id per window (B = N W); this loop's noise is keyed per trial: copies the call's
-        trial ids (default 0 .. N-1) into the device buffer 'win' [N] the captured update reads"""
-        N = self._N
-        ids = self._tid
-        ids = torch.arange(N, dtype=torch.int64) if ids is None else torch.as_tensor(ids, dtype=torch.int64).reshape(-1).cpu()
-        if ids.numel() != N:
-            raise ValueError(f"trial_ids must hold one id per trial ({N}), got {ids.numel()}")
-        if N and (int(ids.min()) < 0 or int(ids.max()) >= 1 << 32):
-            raise ValueError("trial_ids must be in 0 .. 2^32 - 1 (one word of the generator's counter)")
-        self._bufs["win"].copy_(ids)
-
-    def _update(self, x, eps, ctr, t_vec, tabs):
-        if self.eta == 0.0:
-            return super()._update(x, eps, ctr, t_vec, tabs)
-        b, lay = self._bufs, self._lay
-        shape = (self._N, lay["W"]) + tuple(x.shape[1:])
-        v = lambda t: t.view(shape)
-        cond = self._cond is not None
-        if self._sde():
-            x0, z, m, oc, on = (v(b["x0"]), v(b["z"]), b["mask"], tabs.obs_coef, tabs.sde_obs_noise_coef) if cond \
-                else (None, None, None, None, None)
-            hip.sde_dpmpp_step(v(x), v(eps), v(b["hist"]), x0, z, m, tabs.sde_coef, oc, on, tabs.ddim_t, lay["start"],
-                               lay["cover"], lay["wn"], b["win"], self.seed, step_dev=ctr, t_out=t_vec, D=self._D)
-            return
-        x0, z, m, oc, on = (v(b["x0"]), v(b["z"]), b["mask"], tabs.obs_coef, tabs.obs_noise_coef) if cond \
-            else (None, None, None, None, None)
-        hip.stitch_ddim_step_noise(v(x), v(eps), x0, z, m, tabs.ddim_coef_eta, oc, on, tabs.ddim_t, lay["start"], lay["cover"],
-                                   lay["wn"], b["win"], self.seed, step_dev=ctr, t_out=t_vec, D=self._D)

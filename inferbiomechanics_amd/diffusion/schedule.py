@@ -37,6 +37,20 @@ SOLVERS = ("ddim", "dpmpp2m", "dpmpp2m_sde")
 OBSERVATIONS = ("noised", "clean")
 
 
+def check_sampler_settings(eta: float, solver: str, spacing: str, observations: str = "noised"):
+    """the refusals of a sampling loop's settings, for the sampler constructors and DiffusionTables.set_sampler alike"""
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"eta must be in [0, 1], got {eta}")
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    if spacing not in SPACINGS:
+        raise ValueError(f"spacing must be one of {SPACINGS}, got {spacing!r}")
+    if solver == "dpmpp2m" and float(eta) > 0.0:
+        raise ValueError("solver 'dpmpp2m' is deterministic: it needs eta = 0")
+    if observations not in OBSERVATIONS:
+        raise ValueError(f"observations must be one of {OBSERVATIONS}, got {observations!r}")
+
+
 def sample_timesteps(num_train_steps: int = 1000, num_sample_steps: int = 100, spacing: str = "time") -> torch.Tensor:
     """[S] int64, strictly decreasing: the sampling grid.  'time' is ddim_timesteps (uniform in t, needs S | N).  'logsnr' is
     uniform in lambda: S targets from lambda_{N-1} to lambda_0, each rounded to the timestep whose lambda is nearest; the
@@ -329,16 +343,7 @@ class DiffusionTables:
         'dpmpp2m' or 'dpmpp2m_sde' the second-order multistep solver's (A, E, C, hx, he) table.  observations: what
         obs_coef holds -- 'noised', the observation forward-noised to each level (observation_coefficients), or 'clean',
         every row (1, 0) (clean_observation_coefficients: a denoiser trained on clean conditioning columns)"""
-        if observations not in OBSERVATIONS:
-            raise ValueError(f"observations must be one of {OBSERVATIONS}, got {observations!r}")
-        if not 0.0 <= float(eta) <= 1.0:
-            raise ValueError(f"eta must be in [0, 1], got {eta}")
-        if solver not in SOLVERS:
-            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
-        if spacing not in SPACINGS:
-            raise ValueError(f"spacing must be one of {SPACINGS}, got {spacing!r}")
-        if solver == "dpmpp2m" and float(eta) > 0.0:
-            raise ValueError("solver 'dpmpp2m' is deterministic: it needs eta = 0")
+        check_sampler_settings(eta, solver, spacing, observations)
         N = self.num_train_steps
         dev = self.sqrt_ab.device
         ddim_t = sample_timesteps(N, num_sample_steps, spacing).to(dev)          # raises before anything is replaced

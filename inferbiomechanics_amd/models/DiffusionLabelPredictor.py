@@ -83,36 +83,62 @@ class DiffusionLabelPredictor:
             c += w
         return out
 
-    @torch.no_grad()
-    def __call__(self, inputs: Dict[str, torch.Tensor], labels: Optional[Dict[str, torch.Tensor]] = None,
-                 draw: int = 0) -> Dict[str, torch.Tensor]:
+    def _checks(self, inputs: Dict[str, torch.Tensor], what: str):
+        """the checks of a batch of windows (`what` = 'window': F must be the denoiser's window) or of trials ('trial': F at
+        least that) -> (obs [B, F, D], the kind of observation table the denoiser was trained for)"""
         obs = self.window_matrix(inputs)
         B, F, D = obs.shape
-        if labels is not None:
-            for k in LOSS_KEY_ORDER:
-                if labels[k].shape[1] != F:
-                    raise ValueError("DiffusionLabelPredictor: labels must be 'all_frames' (one row per input frame)")
+        T = int(getattr(self.model, 'window', F))
         if D != self.model.feat_dim:
-            raise ValueError(f"a window row has {D} columns but the denoiser was built for feat_dim = {self.model.feat_dim}")
-        if getattr(self.model, 'window', F) != F:
-            raise ValueError(f"a window has {F} frames but the denoiser was built for window = {self.model.window}")
+            raise ValueError(f"a {what} row has {D} columns but the denoiser was built for feat_dim = {self.model.feat_dim}")
+        if what == 'window' and F != T:
+            raise ValueError(f"a window has {F} frames but the denoiser was built for window = {T}")
+        if F < T:
+            raise ValueError(f"a trial of {F} frames is shorter than the denoiser's window of {T} frames")
         C = int(getattr(self.model, 'cond_cols', 0))
         if C and C != D - LABEL_WIDTH:
             raise ValueError(f"the denoiser was trained with cond_cols = {C}; label inference observes the {D - LABEL_WIDTH} "
                              f"input columns of a {D}-column row, so it needs cond_cols = {D - LABEL_WIDTH} (or 0)")
-        self.sampler.observations = 'clean' if C else 'noised'     # read per call: a checkpoint may be loaded after __init__
+        return obs, 'clean' if C else 'noised'      # read per call: a checkpoint may be loaded after __init__
+
+    def _sample(self, sampler, obs: torch.Tensor, mask: torch.Tensor, draw: int, ids_name: Optional[str]):
+        """the labels of obs [B, F, D] from `sampler`, a masked one.  ids_name None: row b starts from the draw
+        (seed, draw + b) and follows its one deterministic trajectory.  Otherwise it is the id keyword of the sampler's
+        sample(): every row is replicated K times, the member ids (member_ids) key both the start draws and the step noise,
+        and the result is the members' mean, with their standard deviation in last_std (ib_ensemble_stats)."""
+        B, F, D = obs.shape
         K = self.num_samples
-        if K == 1 and self.eta == 0.0:
-            z = torch.cat([self.sampler.draw_start(1, F, D, self.seed, draw + b) for b in range(B)])
-            x = self.sampler.sample(z, obs, self._label_mask(F, D))
-            return self.split_labels(x)
+        if ids_name is None:
+            z = torch.cat([sampler.draw_start(1, F, D, self.seed, draw + b) for b in range(B)])
+            return self.split_labels(sampler.sample(z, obs, mask))
         ids = self.member_ids(draw, B)
-        z = torch.cat([self.sampler.draw_start(1, F, D, self.seed, i) for i in ids])
+        z = torch.cat([sampler.draw_start(1, F, D, self.seed, i) for i in ids])
         members = obs.unsqueeze(1).expand(B, K, F, D).reshape(B * K, F, D)
-        x = self.sampler.sample(z, members, self._label_mask(F, D), window_ids=ids)
+        x = sampler.sample(z, members, mask, **{ids_name: ids})
         mean, std = hip.ensemble_stats(x.view(B, K, F, D))
         self.last_std = self.split_labels(std)
         return self.split_labels(mean)
+
+    @staticmethod
+    def _kept(kept, key, make):
+        """`kept` = (key, trial sampler, mask_cols) if it is the one for key = (hop, blend, D), else a new one.  One sampler
+        is kept per kind, with one layout and one captured step: another hop, blend or trial length replaces them, so a
+        service fed trials of many lengths holds the tables and the graph of the last one only"""
+        if kept is not None and kept[0] == key:
+            return kept
+        return key, make(), label_mask(1, key[2])[0].contiguous()
+
+    @torch.no_grad()
+    def __call__(self, inputs: Dict[str, torch.Tensor], labels: Optional[Dict[str, torch.Tensor]] = None,
+                 draw: int = 0) -> Dict[str, torch.Tensor]:
+        F = inputs[INPUT_KEY_ORDER[0]].shape[1]
+        if labels is not None:
+            for k in LOSS_KEY_ORDER:
+                if labels[k].shape[1] != F:
+                    raise ValueError("DiffusionLabelPredictor: labels must be 'all_frames' (one row per input frame)")
+        obs, self.sampler.observations = self._checks(inputs, 'window')
+        single = self.num_samples == 1 and self.eta == 0.0
+        return self._sample(self.sampler, obs, self._label_mask(F, obs.shape[2]), draw, None if single else 'window_ids')
 
     @torch.no_grad()
     def predict_trial(self, inputs: Dict[str, torch.Tensor], hop: Optional[int] = None, blend: str = 'ramp',
@@ -125,36 +151,13 @@ class DiffusionLabelPredictor:
         if self.eta != 0.0 or self.num_samples != 1:
             raise ValueError(f"predict_trial: stitched sampling is deterministic, it needs eta = 0 and num_samples = 1 (got "
                              f"eta = {self.eta}, num_samples = {self.num_samples})")
-        obs, C = self._trial_checks(inputs)
-        N, F, D = obs.shape
-        key = (hop, blend, D)
-        if self._trial is None or self._trial[0] != key:
-            # one sampler is kept, with one layout and one captured step: another hop, blend or trial length replaces them,
-            # so a service fed trials of many lengths holds the tables and the graph of the last one only
-            s = self.sampler
-            self._trial = (key, StitchedDDIMSampler(self.model, s.S, hop=hop, blend=blend, use_graph=s.use_graph,
-                                                    solver=s.solver, spacing=s.spacing, seed=self.seed),
-                           label_mask(1, D)[0].contiguous())
+        obs, kind = self._checks(inputs, 'trial')
+        s = self.sampler
+        self._trial = self._kept(self._trial, (hop, blend, obs.shape[2]), lambda: StitchedDDIMSampler(
+            self.model, s.S, hop=hop, blend=blend, use_graph=s.use_graph, solver=s.solver, spacing=s.spacing, seed=self.seed))
         _, sampler, mask_cols = self._trial
-        sampler.observations = 'clean' if C else 'noised'
-        z = torch.cat([sampler.draw_start(1, F, D, self.seed, draw + b) for b in range(N)])
-        x = sampler.sample(z, obs, mask_cols)
-        return self.split_labels(x)
-
-    def _trial_checks(self, inputs: Dict[str, torch.Tensor]):
-        """predict_trial's checks of a batch of trials -> (obs [N, F, D], cond_cols)"""
-        obs = self.window_matrix(inputs)
-        N, F, D = obs.shape
-        T = int(getattr(self.model, 'window', F))
-        if D != self.model.feat_dim:
-            raise ValueError(f"a trial row has {D} columns but the denoiser was built for feat_dim = {self.model.feat_dim}")
-        if F < T:
-            raise ValueError(f"a trial of {F} frames is shorter than the denoiser's window of {T} frames")
-        C = int(getattr(self.model, 'cond_cols', 0))
-        if C and C != D - LABEL_WIDTH:
-            raise ValueError(f"the denoiser was trained with cond_cols = {C}; label inference observes the {D - LABEL_WIDTH} "
-                             f"input columns of a {D}-column row, so it needs cond_cols = {D - LABEL_WIDTH} (or 0)")
-        return obs, C
+        sampler.observations = kind
+        return self._sample(sampler, obs, mask_cols, draw, None)
 
     @torch.no_grad()
     def predict_trial_ensemble(self, inputs: Dict[str, torch.Tensor], hop: Optional[int] = None, blend: str = 'ramp',
@@ -167,22 +170,11 @@ class DiffusionLabelPredictor:
         if self.sampler.solver not in ('ddim', 'dpmpp2m_sde'):
             raise ValueError(f"predict_trial_ensemble: the stochastic stitched loop is DDIM / DDPM or 'dpmpp2m_sde', solver "
                              f"{self.sampler.solver!r} is deterministic")
-        obs, C = self._trial_checks(inputs)
-        N, F, D = obs.shape
-        K = self.num_samples
-        key = (hop, blend, D)
-        if self._trial_ens is None or self._trial_ens[0] != key:
-            s = self.sampler
-            self._trial_ens = (key, StochasticStitchedSampler(self.model, s.S, eta=self.eta, hop=hop, blend=blend,
-                                                              use_graph=s.use_graph, spacing=s.spacing, seed=self.seed,
-                                                              solver=s.solver),
-                               label_mask(1, D)[0].contiguous())
+        obs, kind = self._checks(inputs, 'trial')
+        s = self.sampler
+        self._trial_ens = self._kept(self._trial_ens, (hop, blend, obs.shape[2]), lambda: StochasticStitchedSampler(
+            self.model, s.S, eta=self.eta, hop=hop, blend=blend, use_graph=s.use_graph, spacing=s.spacing, seed=self.seed,
+            solver=s.solver))
         _, sampler, mask_cols = self._trial_ens
-        sampler.observations = 'clean' if C else 'noised'
-        ids = self.member_ids(draw, N)
-        z = torch.cat([sampler.draw_start(1, F, D, self.seed, i) for i in ids])
-        members = obs.unsqueeze(1).expand(N, K, F, D).reshape(N * K, F, D)
-        x = sampler.sample(z, members, mask_cols, trial_ids=ids)
-        mean, std = hip.ensemble_stats(x.view(N, K, F, D))
-        self.last_std = self.split_labels(std)
-        return self.split_labels(mean)
+        sampler.observations = kind
+        return self._sample(sampler, obs, mask_cols, draw, 'trial_ids')

@@ -11,6 +11,8 @@ A canonical trace is a list of entries in issue order:
   * ["operands:linear_wgrad_slabs_multi", "p<k>", ...]  in front of a grouped weight-gradient launch: per problem dz, x,
     workspace, then the bias partial-sum buffers and the time-MLP rider's operands (the dry-run wrapper of that one launch
     passes no operands to the C-ABI, so the call itself would not show them);
+  * ["state:<what>", value, ...]  host-side state a case records (tools/sampler_trace.py: a sampler's signature and
+    buffers): nested tuples as lists, every integer that is an address taken during the trace as its "p<k>", dtypes as text;
   * "begin:step" / "begin:round" / "begin:sample" / "begin:layer"   where a repetition of the case starts;
   * "fork:<branch>:<on>" ... "endfork:<branch>" around what a Branch.run issues, "join:<branch>" for every Branch.join
     (<branch> = the branch's name + "#k" for the k-th distinct branch of that name in the case: the layers' branches are
@@ -72,6 +74,7 @@ class _Trace:
         torch.manual_seed(0)
         self.log = hip.lib().args
         self._keep = keep = []
+        self._addr = addr = set()           # every address taken: what a "state:" entry may hold as a plain integer
         self._seen = {}                     # branch name -> [Branch, ...] in first-use order
         self._saved = (plans.Branch.run, plans.Branch.join, hip.linear_wgrad_slabs_multi)
         data_ptr = torch.Tensor.data_ptr
@@ -79,6 +82,7 @@ class _Trace:
 
         def kept_ptr(t):
             keep.append(t)
+            addr.add(data_ptr(t))
             return data_ptr(t)
 
         def run(br, fn):
@@ -141,12 +145,23 @@ class _Trace:
             if hasattr(v, "value"):
                 return v.value
             return "host"                   # byref(...)
+
+        def state(v):
+            if isinstance(v, (tuple, list)):
+                return [state(e) for e in v]
+            if v is None or isinstance(v, (bool, str, float)):
+                return v
+            if isinstance(v, int):
+                return ptr(v) if v in self._addr else v
+            return str(v)                   # a dtype
         out = []
         for name, a in self.log:
             if a is None:
                 out.append(name)
             elif name.startswith("operands:"):
                 out.append([name] + [ptr(v) for v in a])
+            elif name.startswith("state:"):
+                out.append([name] + state(a))
             else:
                 out.append([name] + [arg(v, t) for v, t in zip(a, hip._sig(name)[1])])
         return out
