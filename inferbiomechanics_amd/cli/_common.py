@@ -87,3 +87,18 @@ def pick_device(args) -> torch.device:
         local = 0
     torch.cuda.set_device(local)
     return torch.device('cuda', local)
+
+
+GUIDANCE_HELP = ('classifier-free guidance strength S of the sampler: the noise prediction becomes '
+                 'eps_c + S (eps_c - eps_u), eps_u the prediction with the conditioning columns zeroed. Needs a checkpoint '
+                 'of `train --cond-cols N --cond-drop P` with P > 0. 0 = off.')
+
+
+def checked_guidance(args, model) -> float:
+    """--guidance S of analyze / visualize, once the checkpoint is loaded: refused for a denoiser that never saw the null
+    condition"""
+    s = float(getattr(args, 'guidance', 0.0))
+    if s != 0.0 and not float(getattr(model, 'cond_drop', 0.0)) > 0.0:
+        raise SystemExit(f"--guidance {s} needs a denoiser trained with condition dropout (`train --cond-drop P`, P > 0): this "
+                         f"checkpoint's cond_drop is 0, so it has no unconditional prediction to guide away from")
+    return s

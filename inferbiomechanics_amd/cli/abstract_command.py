@@ -151,6 +151,8 @@ class AbstractCommand:
         target.load_state_dict(state)
         if hasattr(target, 'cond_cols'):                     # denoisers: `train --cond-cols`; older checkpoints have no key
             target.cond_cols = int(checkpoint.get('cond_cols', 0))
+        if hasattr(target, 'cond_drop'):                     # denoisers: `train --cond-drop`
+            target.cond_drop = float(checkpoint.get('cond_drop', 0.0))
         osd = checkpoint.get('optimizer_state_dict')
         if optimizer is not None and hasattr(optimizer, 'load_optimizer_state_dict'):      # HipTrainer
             if osd is not None:

@@ -12,7 +12,8 @@ import torch
 from torch.utils.data import DataLoader
 
 from ..loss.RegressionLossEvaluator import RegressionLossEvaluator
-from ._common import add_additive_flags, add_component_flags, dtype_of, is_diffusion, open_dataset, pick_device
+from ._common import (GUIDANCE_HELP, add_additive_flags, add_component_flags, checked_guidance, dtype_of, is_diffusion,
+                      open_dataset, pick_device)
 from .abstract_command import AbstractCommand
 
 
@@ -55,6 +56,7 @@ class AnalyzeCommand(AbstractCommand):
         p.add_argument('--sample-spacing', type=str, default='time', choices=['time', 'logsnr'],
                        help='[diffusion models] sampling grid: uniform in the timestep, or uniform in log-SNR (no need for '
                             '--sample-steps to divide the training steps; the grid for few-step dpmpp2m / dpmpp2m_sde sampling).')
+        p.add_argument('--guidance', type=float, default=0.0, help='[diffusion models] ' + GUIDANCE_HELP)
         p.add_argument('--use-ema', action='store_true', default=False,
                        help='Evaluate the EMA weights of the checkpoint (`train --ema-decay`) instead of its last weights.')
 
@@ -127,7 +129,8 @@ class AnalyzeCommand(AbstractCommand):
                 model.eval()
                 predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
                                                     output_data_format=args.output_data_format, eta=eta,
-                                                    num_samples=num_samples, solver=solver, spacing=spacing)
+                                                    num_samples=num_samples, solver=solver, spacing=spacing,
+                                                    guidance=checked_guidance(args, model))
             evaluator = RegressionLossEvaluator(dataset=dataset, split=split, device=device)
             loader = DataLoader(dataset, batch_size=args.sample_batch, shuffle=False, num_workers=args.data_loading_workers)
             compute_report = bool(getattr(dataset, 'skeletons', None))

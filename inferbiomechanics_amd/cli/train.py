@@ -96,6 +96,11 @@ class TrainCommand(AbstractCommand):
                             'network clean at every noise level, only the other columns are noised and scored. For label '
                             'inference N = feat_dim - 30; `analyze` / `visualize` read N from the checkpoint. 0 = '
                             'unconditional.')
+        p.add_argument('--cond-drop', type=float, default=0.0,
+                       help='[diffusion, with --cond-cols] Classifier-free guidance training: with probability P a window\'s '
+                            'conditioning columns reach the denoiser all zero (the null condition), decided on the device per '
+                            'step and window. `analyze --guidance S` / `visualize --guidance S` then sample with the guided '
+                            'noise prediction. 0 = off; 0.1-0.2 are usual. Not with --eager.')
         p.add_argument('--no-ema-warmup', action='store_true',
                        help='Use --ema-decay from the first step (default: min(decay, (1 + step) / (10 + step))).')
 
@@ -111,6 +116,7 @@ class TrainCommand(AbstractCommand):
 
         check_ema_args(args)
         check_cond_cols(model_type, getattr(args, 'cond_cols', 0))
+        check_cond_drop(args)
         if getattr(args, 'seed', None) is not None:
             torch.manual_seed(args.seed)
         geometry = self.ensure_geometry(args.geometry_folder)
@@ -168,9 +174,11 @@ class TrainCommand(AbstractCommand):
             return False
 
         cond_cols = getattr(args, 'cond_cols', 0) if diffusion else 0
+        cond_drop = float(getattr(args, 'cond_drop', 0.0)) if diffusion else 0.0
         if diffusion:
             check_cond_cols(model_type, cond_cols, feat_dim=model.feat_dim)
             model.cond_cols = cond_cols
+            model.cond_drop = cond_drop
             train_eval, dev_eval = DiffusionLossEvaluator('train', cond_cols), DiffusionLossEvaluator(DEV, cond_cols)
         else:
             train_eval = RegressionLossEvaluator(dataset=train_dataset, split='train', device=device)
@@ -187,7 +195,8 @@ class TrainCommand(AbstractCommand):
             trainer = HipTrainer(model, "diffusion" if diffusion else "regression", args.opt_type, args.learning_rate,
                                  args=args, use_graph=not args.no_graph, bucket_mb=args.bucket_mb,
                                  ema_decay=getattr(args, 'ema_decay', 0.0),
-                                 ema_warmup=not getattr(args, 'no_ema_warmup', False), cond_cols=cond_cols)
+                                 ema_warmup=not getattr(args, 'no_ema_warmup', False), cond_cols=cond_cols,
+                                 cond_drop=cond_drop)
 
         if getattr(args, 'loss_every', 1) < 1:
             raise SystemExit("--loss-every must be >= 1")
@@ -239,6 +248,9 @@ class TrainCommand(AbstractCommand):
         if diffusion and model.cond_cols != cond_cols:       # the checkpoint's value: a resumed run keeps training that model
             raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained with --cond-cols {model.cond_cols}, this run "
                              f"asks for {cond_cols}: resume with the same value or use another --checkpoint-dir")
+        if diffusion and model.cond_drop != cond_drop:
+            raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained with --cond-drop {model.cond_drop}, this run "
+                             f"asks for {cond_drop}: resume with the same value or use another --checkpoint-dir")
         from .. import hip
         noise_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
 
@@ -257,7 +269,8 @@ class TrainCommand(AbstractCommand):
             return xd, td, ed
 
         def noise_batch(xd, ed, td, tabs, xt):
-            """x_t of the dev-set evaluation and the --eager loop: conditioning columns clean when --cond-cols N > 0"""
+            """x_t of the dev-set evaluation and the --eager loop: conditioning columns clean when --cond-cols N > 0.  No
+            condition dropout here (--cond-drop is the fused trainer's): the dev loss reported is the conditional one"""
             if cond_cols:
                 hip.q_sample_cond(xd, ed, td, tabs.sqrt_ab, tabs.sqrt_1mab, xt, cond_cols)
             else:
@@ -397,6 +410,19 @@ def check_cond_cols(model_type: str, cond_cols: int, feat_dim: int = None):
         raise SystemExit(f"--cond-cols must lie in 0 .. {hi} (at least one column has to stay free), got {cond_cols}")
 
 
+def check_cond_drop(args: argparse.Namespace):
+    """--cond-drop P: P in [0, 1], with a diffusion model type and --cond-cols N > 0; the drop is decided inside the fused
+    trainer's noising launch, so --eager has none"""
+    p = getattr(args, 'cond_drop', 0.0)
+    if not 0.0 <= p <= 1.0:
+        raise SystemExit(f"--cond-drop must lie in [0, 1] (0 = off, 0.1-0.2 are usual), got {p}")
+    if p > 0 and not (is_diffusion(args.model_type) and getattr(args, 'cond_cols', 0) > 0):
+        raise SystemExit("--cond-drop drops the conditioning columns of a conditional denoiser: it needs a diffusion model "
+                         "type and --cond-cols N > 0")
+    if p > 0 and getattr(args, 'eager', False):
+        raise SystemExit("--cond-drop needs the fused trainer: the drop is decided inside its noising launch, --eager has none")
+
+
 def make_torch_optimizer(opt_type: str, params, lr: float):
     table = {'adagrad': torch.optim.Adagrad, 'adam': torch.optim.Adam, 'sgd': torch.optim.SGD,
              'rmsprop': torch.optim.RMSprop, 'adadelta': torch.optim.Adadelta, 'adamax': torch.optim.Adamax}
@@ -409,7 +435,8 @@ def make_torch_optimizer(opt_type: str, params, lr: float):
 def save_checkpoint(checkpoint_dir: str, epoch: int, batch: int, model, opt):
     """file grammar of train.py:271-278; keys are saved WITHOUT DDP's `module.` prefix.  A trainer with an EMA adds
     'ema_state_dict' (the model's state dict over the EMA weights) and 'ema' ({'decay', 'warmup'}); without one the file
-    holds the three reference keys only.  A denoiser trained with --cond-cols N > 0 adds 'cond_cols': N."""
+    holds the three reference keys only.  A denoiser trained with --cond-cols N > 0 adds 'cond_cols': N, one trained with
+    --cond-drop P > 0 'cond_drop': P."""
     os.makedirs(checkpoint_dir, exist_ok=True)
     path = f"{checkpoint_dir}/epoch_{epoch}_batch_{batch}.pt"
     osd = opt.optimizer_state_dict() if hasattr(opt, 'optimizer_state_dict') else opt.state_dict()
@@ -418,6 +445,8 @@ def save_checkpoint(checkpoint_dir: str, epoch: int, batch: int, model, opt):
             'optimizer_state_dict': osd}
     if getattr(model, 'cond_cols', 0):
         ckpt['cond_cols'] = int(model.cond_cols)
+    if getattr(model, 'cond_drop', 0.0) > 0:
+        ckpt['cond_drop'] = float(model.cond_drop)
     if getattr(opt, 'ema', None) is not None:
         ckpt['ema_state_dict'] = opt.ema_state_dict()
         ckpt['ema'] = {'decay': opt.ema_decay, 'warmup': opt.ema_warmup}

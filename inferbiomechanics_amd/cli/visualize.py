@@ -20,7 +20,8 @@ import torch
 from ..loss.RegressionLossEvaluator import RegressionLossEvaluator
 from ..data.AddBiomechanicsDataset import LOSS_KEY_ORDER
 from ..diffusion.schedule import STITCH_BLENDS, stitch_layout
-from ._common import add_additive_flags, add_component_flags, dtype_of, is_diffusion, open_dataset, pick_device
+from ._common import (GUIDANCE_HELP, add_additive_flags, add_component_flags, checked_guidance, dtype_of, is_diffusion,
+                      open_dataset, pick_device)
 from .abstract_command import AbstractCommand
 from .analyze import window_subject, window_trial
 
@@ -70,6 +71,7 @@ class VisualizeCommand(AbstractCommand):
                        help='[--trial-frames] update of both sampling loops: first-order DDIM, DPM-Solver++(2M) '
                             '(deterministic: needs --sample-eta 0 and --num-samples 1), or dpmpp2m_sde, its stochastic form '
                             '(takes --sample-eta > 0 and --num-samples > 1; use it with --sample-spacing logsnr).')
+        p.add_argument('--guidance', type=float, default=0.0, help='[--trial-frames] ' + GUIDANCE_HELP)
         p.add_argument('--sample-spacing', type=str, default='time', choices=['time', 'logsnr'],
                        help='[--trial-frames] sampling grid of both loops: uniform in the timestep, or uniform in log-SNR '
                             '(the grid for few-step dpmpp2m / dpmpp2m_sde sampling).')
@@ -149,7 +151,8 @@ class VisualizeCommand(AbstractCommand):
             raise SystemExit(f"--trial-frames / --trial-hop: {e}")
         predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
                                             output_data_format=args.output_data_format, eta=eta, num_samples=num_samples,
-                                            solver=solver, spacing=getattr(args, 'sample_spacing', 'time'))
+                                            solver=solver, spacing=getattr(args, 'sample_spacing', 'time'),
+                                            guidance=checked_guidance(args, model))
         gather = start.long()[:, None] + torch.arange(T)[None, :]      # [Wd, T] trial frames of the disjoint windows
         w0 = cover[:, 0].long()
         t0 = torch.arange(F) - start.long()[w0]

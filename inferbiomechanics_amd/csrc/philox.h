@@ -1,14 +1,15 @@
 // The counter-based generator shared by the diffusion draw (noise.hip) and the stochastic sampler update (diffusion.hip):
 // Philox4x32-10 (Salmon et al., SC'11) and Box-Muller over its words.  counter = (block, step, stream, domain), key = the
 // 64-bit seed.  The domains keep the streams of one (seed, step, stream) apart: 0 = the eps / start draw, 1 = timesteps,
-// 2 = the noise term of a sampling step (there `stream` is the window id and `step` the sampling step).
+// 2 = the noise term of a sampling step (there `stream` is the window id and `step` the sampling step), 3 = the condition
+// dropout of a training step (cfg.hip: `block` is the window's place in the batch, one decision per window).
 #pragma once
 #include "ib_common.h"
 
 namespace {
 
 constexpr uint32_t kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u, kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
-constexpr uint32_t kDomainEps = 0u, kDomainT = 1u, kDomainStep = 2u;
+constexpr uint32_t kDomainEps = 0u, kDomainT = 1u, kDomainStep = 2u, kDomainDrop = 3u;
 
 struct U4 { uint32_t x, y, z, w; };
 

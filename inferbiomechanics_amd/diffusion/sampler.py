@@ -31,7 +31,15 @@ the update launch (_launch_update):
     yes      2              no        ib_stitch_dpmpp_step                   "
     yes      2              yes       ib_sde_dpmpp_step                      "
 
-(order 2 with eta > 0 is 'dpmpp2m_sde'; 'dpmpp2m_sde' at eta = 0 is an eta = 0 row)."""
+(order 2 with eta > 0 is 'dpmpp2m_sde'; 'dpmpp2m_sde' at eta = 0 is an eta = 0 row).
+
+Classifier-free guidance (guidance = s != 0; the three masked classes, observations = 'clean', a denoiser trained with
+`train --cond-drop`) changes none of those rows: it is a seam around them, in _prepare and _step_launches alone.  The state
+and the noise buffer hold 2B windows, the B of the call and their twins under the null condition (all-zero conditioning
+columns, never written after allocation).  One step = {forward over the 2B windows, ib_cfg_combine: the first half of the
+noise buffer becomes eps_c + s (eps_c - eps_u), the row's update launch over the first half exactly as without guidance,
+ib_cfg_mirror: the free columns and the timesteps of the first half copied to the second, counter++} (csrc/cfg.hip).  At
+guidance = 0 none of it exists: the launches, buffers, signature and bits are the unguided loop's."""
 from dataclasses import dataclass
 from typing import Optional, Sequence, Union
 
@@ -100,6 +108,32 @@ class DDIMSampler:
         self._stream = None
         self._sig = None
         self._bufs = {}
+
+    guidance = 0.0                           # the classes that take observations set it (classifier-free guidance)
+
+    def _check_guidance(self, guidance: float, observations: str):
+        """the constructor's check of `guidance` for the classes that take observations"""
+        g = float(guidance)
+        if g != g or g in (float("inf"), float("-inf")):
+            raise ValueError(f"guidance must be finite, got {guidance}")
+        if g != 0.0:
+            if observations != "clean":
+                raise ValueError(f"guidance = {g} needs observations='clean' (the loop of a denoiser trained on clean "
+                                 f"conditioning columns), got observations={observations!r}")
+            if not float(getattr(self.model, "cond_drop", 0.0)) > 0.0:
+                raise ValueError(f"guidance = {g} needs a denoiser that was trained with its conditioning dropped for a share "
+                                 f"of the windows (`train --cond-drop P`, model.cond_drop > 0): this one never saw the null "
+                                 f"condition, so it has no unconditional prediction")
+        self.guidance = g
+
+    def _guided(self, c: SampleCall) -> bool:
+        """this call runs the guided loop.  `observations` may be changed between calls: anything but 'clean' is refused"""
+        if self.guidance == 0.0:
+            return False
+        if c.observed is None or self.observations != "clean":
+            raise ValueError(f"guidance = {self.guidance} needs observations (observations='clean'): without them there is "
+                             f"no condition to guide by")
+        return True
 
     def _second(self) -> bool:
         """a second-order multistep solver: the loop keeps the fp32 history buffer"""
@@ -205,12 +239,25 @@ class DDIMSampler:
             sig += (self.eta, self.seed, ptr(tabs.ddim_coef_eta), ptr(tabs.obs_noise_coef))
         else:
             sig += (0.0,)
+        guided = self._guided(c)
+        if guided:
+            # the seam's launches bake in the strength, the conditioning width and xin's address.  xin belongs to the
+            # signature it is part of: while that one is current its pointer is the live buffer's
+            sig += ("cfg", self.guidance, int(m.cond_cols))
+            if self._sig is not None and sig == self._sig[:-1] and self._sig[-1] == ptr(self._bufs["xin"]):
+                return
         if sig == self._sig:
             return
-        state = lambda dtype=m.compute_dtype: torch.zeros((B, T, Dp), dtype=dtype, device=dev)
-        bufs = {"x": state(), "t": torch.empty(B, dtype=torch.int64, device=dev),
+        state = lambda dtype=m.compute_dtype, n=B: torch.zeros((n, T, Dp), dtype=dtype, device=dev)
+        # guided: the B windows and their null-condition twins.  The conditioning and pad columns of the second half of xin
+        # are zero from here on (no launch writes them); x, the state every other launch sees, is the first half
+        xin = state(n=2 * B) if guided else None
+        bufs = {"x": xin[:B] if guided else state(), "t": torch.empty(2 * B if guided else B, dtype=torch.int64, device=dev),
                 "ctr": torch.zeros(1, dtype=torch.int32, device=dev)}
-        if Dp != D:
+        if guided:
+            bufs.update(xin=xin, eps=state(n=2 * B))             # the noise buffer is pitched even when Dp == D
+            sig += (ptr(xin),)
+        elif Dp != D:
             bufs["eps"] = state()
         if cond:
             # pitched like the state, pad columns 0 (the mask's pad columns are free, so they stay 0 in x)
@@ -259,6 +306,8 @@ class DDIMSampler:
             self._start_masked(c, x, tabs)
         ctr.zero_()
         hip.fill_i64(t_vec, int(tabs.ddim_t[0]))
+        if "xin" in self._bufs:
+            hip.cfg_mirror(self._bufs["xin"], t_vec, int(m.cond_cols), D=c.D)
         P = m.param_source()
         if hasattr(plan, "set_inference"):
             plan.set_inference(True)             # weights are frozen for the whole loop
@@ -291,7 +340,16 @@ class DDIMSampler:
     def _step_launches(self, c: SampleCall, x, t_vec, ctr, tabs, P: ParamSource):
         plan = self.model._get_plan(x.device)
         eps_buf = self._bufs.get("eps")
-        if eps_buf is not None:
+        xin = self._bufs.get("xin")
+        if xin is not None:
+            # the guided step (the module docstring): x is the first half of xin, the update writes t_vec[:B]
+            B2, T, Dp = xin.shape
+            plan.forward(xin.view(B2 * T, Dp)[:, :c.D], t_vec, tabs.temb, P, out=eps_buf.view(B2 * T, Dp)[:, :c.D],
+                         BT=(B2, T))
+            hip.cfg_combine(eps_buf, self.guidance)
+            self._launch_update(c, x, eps_buf[:c.B], ctr, t_vec[:c.B], tabs)
+            hip.cfg_mirror(xin, t_vec, int(self.model.cond_cols), D=c.D)
+        elif eps_buf is not None:
             # pitched state / noise buffers [B, T, Dp] with zero pad columns (plans.infer_pitch): the plan sees row-padded
             # 2-D views; the DDIM update runs over the whole pitched buffers (0 stays 0 in the pad columns)
             B, T, Dp = x.shape
@@ -360,10 +418,12 @@ class ConditionalDDIMSampler(DDIMSampler):
     The attribute may be changed between calls; the step is captured again."""
 
     def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True, eta: float = 0.0,
-                 seed: Optional[int] = None, solver: str = "ddim", spacing: str = "time", observations: str = "noised"):
+                 seed: Optional[int] = None, solver: str = "ddim", spacing: str = "time", observations: str = "noised",
+                 guidance: float = 0.0):
         check_sampler_settings(eta, solver, spacing, observations)
         super().__init__(model, num_sample_steps, use_graph, eta, seed, solver, spacing)
         self.observations = observations
+        self._check_guidance(guidance, observations)
         self._mask_ok = None                 # (mask, (version, cond_cols)) of the last mask 'clean' mode accepted
 
     @torch.no_grad()
@@ -412,13 +472,14 @@ class StitchedDDIMSampler(DDIMSampler):
 
     def __init__(self, model, num_sample_steps: int = 100, hop: Optional[int] = None, blend: str = "ramp",
                  use_graph: bool = True, solver: str = "ddim", spacing: str = "time", observations: str = "noised",
-                 seed: Optional[int] = None, eta: float = 0.0):
+                 seed: Optional[int] = None, eta: float = 0.0, guidance: float = 0.0):
         if float(eta) != 0.0:
             raise ValueError(f"StitchedDDIMSampler is deterministic: eta must be 0, got {eta} (the step noise of an eta > 0 "
                              f"loop is keyed by window and in-window frame, not by trial frame)")
         check_sampler_settings(0.0, solver, spacing, observations)
         super().__init__(model, num_sample_steps, use_graph, 0.0, seed, solver, spacing)
         self.observations = observations
+        self._check_guidance(guidance, observations)
         if getattr(model, "window", None) is None:
             raise ValueError("StitchedDDIMSampler needs a denoiser that states its window (model.window frames)")
         self.T = int(model.window)
@@ -509,7 +570,7 @@ class StochasticStitchedSampler(StitchedDDIMSampler):
 
     def __init__(self, model, num_sample_steps: int = 100, eta: float = 1.0, hop: Optional[int] = None, blend: str = "ramp",
                  use_graph: bool = True, spacing: str = "time", observations: str = "noised", seed: Optional[int] = None,
-                 **keywords):
+                 guidance: float = 0.0, **keywords):
         """keywords: solver = 'ddim' (the default) or 'dpmpp2m_sde', by keyword only.  It is not a named parameter:
         tests/test_stitch_noise_plumbing_cpu.py pins that this signature names no `solver`, from when the class had one
         solver; a misspelt keyword is still a TypeError"""
@@ -522,7 +583,8 @@ class StochasticStitchedSampler(StitchedDDIMSampler):
         if solver not in ("ddim", "dpmpp2m_sde"):
             raise ValueError(f"solver must be 'ddim' or 'dpmpp2m_sde', got {solver!r}")
         check_sampler_settings(eta, solver, spacing, observations)
-        super().__init__(model, num_sample_steps, hop, blend, use_graph, solver, spacing, observations, seed)
+        super().__init__(model, num_sample_steps, hop, blend, use_graph, solver, spacing, observations, seed,
+                         guidance=guidance)
         self.eta = float(eta)                # the parent's constructor hands DDIMSampler eta = 0
 
     @torch.no_grad()

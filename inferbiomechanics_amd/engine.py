@@ -270,11 +270,16 @@ class HipTrainer:
 
     def __init__(self, model: HipModule, task: str, opt_type: str = "rmsprop", lr: float = 1e-4, args=None,
                  group=None, bucket_mb: float = 13.0, use_graph: bool = True, overlap_comm: Optional[bool] = None,
-                 ema_decay: float = 0.0, ema_warmup: bool = True, cond_cols: int = 0):
+                 ema_decay: float = 0.0, ema_warmup: bool = True, cond_cols: int = 0, cond_drop: float = 0.0):
         if task not in ("diffusion", "regression"):
             raise ValueError(task)
         if int(cond_cols) < 0 or (cond_cols and task != "diffusion"):
             raise ValueError(f"cond_cols must be >= 0 and is a diffusion-task setting, got {cond_cols} for task '{task}'")
+        if not 0.0 <= float(cond_drop) <= 1.0:
+            raise ValueError(f"cond_drop must lie in [0, 1], got {cond_drop}")
+        if float(cond_drop) > 0.0 and (task != "diffusion" or int(cond_cols) <= 0):
+            raise ValueError(f"cond_drop > 0 drops the conditioning columns of a diffusion denoiser: it needs task 'diffusion' "
+                             f"and cond_cols > 0, got task '{task}' and cond_cols = {cond_cols}")
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
         if opt_type not in hip.OPT:
@@ -284,6 +289,9 @@ class HipTrainer:
         # noise level and are not scored (csrc/diffusion.hip q_sample_cond_kernel, csrc/loss.hip mse_partial_cond_kernel).
         # 0: the unconditional step, through the entry points it always used.  Checked against D on the first batch.
         self.cond_cols = int(cond_cols)
+        # classifier-free guidance: each window's conditioning columns reach the denoiser all zero (the null condition) with
+        # probability cond_drop, decided on the device per (seed, step, rank, window) (csrc/cfg.hip).  0: the launch above.
+        self.cond_drop = float(cond_drop)
         self.group = group
         self.world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
         import os
@@ -510,7 +518,10 @@ class HipTrainer:
             xt = plan.buf.get("tr.xt", (M, Dp), dt, zero=True)[:, :D]
             pred = plan.buf.get("tr.pred", (M, Dp), dt, zero=True)[:, :D]
             dpred = plan.buf.get("tr.dpred", (M, Dp), dt, zero=True)[:, :D]
-            if C:
+            if C and self.cond_drop > 0.0:
+                hip.q_sample_cond_drop(x0, eps, t, tabs.sqrt_ab, tabs.sqrt_1mab, xt, C, self.cond_drop, self.noise_seed,
+                                       step_dev=self.step_dev, stream_id=self.noise_stream)
+            elif C:
                 hip.q_sample_cond(x0, eps, t, tabs.sqrt_ab, tabs.sqrt_1mab, xt, C)
             else:
                 hip.q_sample(x0, eps, t, tabs.sqrt_ab, tabs.sqrt_1mab, xt)
@@ -920,6 +931,8 @@ class HipTrainer:
         sig = tuple((k, tuple(v.shape)) for k, v in st.items()) + (("training", bool(self.model.training)),)
         if self.cond_cols:
             sig += (("cond_cols", self.cond_cols),)     # chooses the step's launches: part of what a captured graph is
+        if self.cond_drop > 0.0:
+            sig += (("cond_drop", self.cond_drop),)     # the drop threshold is an argument the captured launch bakes in
         if sig != self._sig:
             self._sig, self._rec, self._warm = sig, None, 0
             self._pinned, self._seen = {}, {}

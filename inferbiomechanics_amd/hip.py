@@ -10,7 +10,8 @@ module is imported, so a new entry point needs its declaration there and its wra
 sampler updates (csrc/stitch.hip) are declared in a second header, ``include/ib_hip_stitch.h``, parsed the same way into
 ``_STITCH_SIGS``, the merged head launches of the transformer step (csrc/head_jobs.h) in a third, ``include/ib_hip_head.h``
 (``_HEAD_SIGS``), the stochastic second-order sampler update (csrc/sde.hip) in a fourth, ``include/ib_hip_sde.h``
-(``_SDE_SIGS``); a name may be declared once in the four.
+(``_SDE_SIGS``), classifier-free guidance (csrc/cfg.hip) in a fifth, ``include/ib_hip_cfg.h`` (``_CFG_SIGS``); a name may be
+declared once in the five.
 """
 from __future__ import annotations
 
@@ -31,6 +32,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip.h")
 STITCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_stitch.h")
 HEAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_head.h")
 SDE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sde.h")
+CFG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_cfg.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -94,9 +96,10 @@ def _read_header(path: Optional[str] = None) -> str:
 
 
 # a table per header: _SIGS and declared_symbols() describe ib_hip.h only, _STITCH_SIGS the stitched trial sampling
-_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS = (_parse_header(_read_header(_path)) for _path in
-                                              (HEADER_PATH, STITCH_HEADER_PATH, HEAD_HEADER_PATH, SDE_HEADER_PATH))
-_TABLES = (_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS)
+_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS, _CFG_SIGS = (
+    _parse_header(_read_header(_path)) for _path in
+    (HEADER_PATH, STITCH_HEADER_PATH, HEAD_HEADER_PATH, SDE_HEADER_PATH, CFG_HEADER_PATH))
+_TABLES = (_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS, _CFG_SIGS)
 _ALL_SIGS = {_n: _v for _t in _TABLES for _n, _v in _t.items()}   # every entry point: what _sig() looks up and lib() binds
 if len(_ALL_SIGS) != sum(len(_t) for _t in _TABLES):
     _twice = sorted(n for n in _ALL_SIGS if sum(n in _t for _t in _TABLES) > 1)
@@ -127,6 +130,11 @@ def head_symbols() -> List[str]:
 def sde_symbols() -> List[str]:
     """Every function include/ib_hip_sde.h declares"""
     return sorted(_SDE_SIGS)
+
+
+def cfg_symbols() -> List[str]:
+    """Every function include/ib_hip_cfg.h declares"""
+    return sorted(_CFG_SIGS)
 
 
 def _sig(name: str):
@@ -1945,6 +1953,73 @@ def q_sample_cond(x0, eps, t, sqrt_ab, sqrt_1mab, x_t, cond_cols: int):
     _check(lib().ib_q_sample_cond(_ptr(x0), _ptr(eps), _ptr(t), _ptr(sqrt_ab), _ptr(sqrt_1mab), _ptr(x_t), ld, B, T, D,
                                   sqrt_ab.numel(), cond_cols, dtype_code(dt), stream_ptr()), "ib_q_sample_cond")
     return x_t
+
+
+def cond_drop_threshold(p: float) -> int:
+    """floor(p * 2^32) for p in [0, 1]: a window is dropped when its 32-bit draw is below it, so 1 gives 2^32 (every window)
+    and 0 gives 0 (none; the generator is skipped).  Scaling a double by a power of two is exact."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"cond_drop must lie in [0, 1], got {p}")
+    return int(p * 4294967296.0)
+
+
+def q_sample_cond_drop(x0, eps, t, sqrt_ab, sqrt_1mab, x_t, cond_cols: int, p: float, seed: int, step: int = 0,
+                       step_dev=None, stream_id: int = 0, dropped_out=None):
+    """q_sample_cond with condition dropout (csrc/cfg.hip): with probability p a window's conditioning columns reach x_t all
+    +0 (the null condition of classifier-free guidance) instead of x0's bits; the free columns are q_sample_cond's bit for
+    bit.  Window b's decision is a function of (seed, step + *step_dev, stream_id, b) alone.  dropped_out (optional, uint8
+    [B]) receives it.  p = 0 is q_sample_cond bit for bit."""
+    B, T, D, ld, dt = _q_sample_args(x0, eps, t, sqrt_ab, sqrt_1mab, x_t)
+    cond_cols = int(cond_cols)
+    if not 0 <= cond_cols < D:
+        raise HipError(f"q_sample_cond_drop: cond_cols must lie in [0, {D}), got {cond_cols}")
+    thr = cond_drop_threshold(p)
+    if step_dev is not None:
+        _req(step_dev, "step_dev", torch.int32)
+    if dropped_out is not None:
+        _req(dropped_out, "dropped_out", torch.uint8, 1)
+        if dropped_out.numel() != B or not dropped_out.is_contiguous():
+            raise HipError(f"q_sample_cond_drop: dropped_out must be contiguous uint8 [B] = [{B}]")
+    _check(lib().ib_q_sample_cond_drop(_ptr(x0), _ptr(eps), _ptr(t), _ptr(sqrt_ab), _ptr(sqrt_1mab), _ptr(x_t), ld, B, T, D,
+                                       sqrt_ab.numel(), cond_cols, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), _ptr(step_dev),
+                                       int(stream_id) & 0xFFFFFFFF, thr, _ptr(dropped_out), dtype_code(dt), stream_ptr()),
+           "ib_q_sample_cond_drop")
+    return x_t
+
+
+def _cfg_pair(what, buf):
+    """a buffer of the guided sampling step: contiguous [2B, T, ld], the conditional windows then their null-condition twins
+    -> (B, T, ld)"""
+    _req(buf, what, buf.dtype, 3)
+    if not buf.is_contiguous() or buf.shape[0] < 2 or buf.shape[0] % 2:
+        raise HipError(f"{what}: a contiguous [2B, T, ld] buffer is required, got {tuple(buf.shape)}")
+    return buf.shape[0] // 2, buf.shape[1], buf.shape[2]
+
+
+def cfg_combine(eps, guidance: float):
+    """the guided noise prediction in place (csrc/cfg.hip): eps [2B, T, ld] holds the conditional predictions in windows
+    0 .. B-1 and the null-condition ones in B .. 2B-1; the first half becomes ec + s (ec - eu), three fp32 roundings as
+    written, then the dtype's; the second half is not written"""
+    B, T, ld = _cfg_pair("cfg_combine", eps)
+    _check(lib().ib_cfg_combine(_ptr(eps), float(guidance), B, T * ld, dtype_code(eps.dtype), stream_ptr()), "ib_cfg_combine")
+    return eps
+
+
+def cfg_mirror(x, t, cond_cols: int, D=None):
+    """the guided step's input (csrc/cfg.hip): over x [2B, T, ld] the free columns cond_cols .. D-1 (D defaults to ld) of
+    window b are copied to window B + b, and t[B + b] = t[b] (int64 [2B]).  The conditioning and pad columns of the second
+    half are never written: they stay the zeros they were allocated as, the null condition"""
+    B, T, ld = _cfg_pair("cfg_mirror", x)
+    D = ld if D is None else int(D)
+    cond_cols = int(cond_cols)
+    if not 0 < D <= ld or not 0 <= cond_cols < D:
+        raise HipError(f"cfg_mirror: need 0 <= cond_cols < D <= ld, got cond_cols = {cond_cols}, D = {D}, ld = {ld}")
+    _req(t, "t", torch.int64, 1)
+    if t.numel() != 2 * B or not t.is_contiguous():
+        raise HipError(f"cfg_mirror: t must be contiguous int64 [2B] = [{2 * B}]")
+    _check(lib().ib_cfg_mirror(_ptr(x), _ptr(t), B, T, D, ld, cond_cols, dtype_code(x.dtype), stream_ptr()), "ib_cfg_mirror")
+    return x
 
 
 def time_mlp_fwd_supported(temb: int, hidden: int, out: int) -> bool:

@@ -24,6 +24,9 @@ class _DenoiserBase(HipModule):
         # level and scored on the other columns only (`train --cond-cols`; saved in the checkpoint).  0: unconditional.  Not a
         # parameter of the network -- the trainer, the loss evaluator and the sampler read it.
         self.cond_cols = 0
+        # the share of training windows whose conditioning columns were all zero, the null condition of classifier-free
+        # guidance (`train --cond-drop`; saved in the checkpoint).  0: the model never saw it and cannot be guided.
+        self.cond_drop = 0.0
         self._tables = None
         self._plan = None
 

@@ -36,11 +36,14 @@ class DiffusionLabelPredictor:
     trajectory).  solver / spacing choose the sampler's update and grid (diffusion/sampler.py); 'dpmpp2m_sde' is the
     second-order solver that takes eta > 0 and ensembles.  A denoiser trained on
     clean conditioning columns (model.cond_cols > 0, `train --cond-cols`; it must be feat_dim - 30) gets its observations
-    pinned clean at every step (ConditionalDDIMSampler, observations = 'clean'); at 0 they are forward-noised as before."""
+    pinned clean at every step (ConditionalDDIMSampler, observations = 'clean'); at 0 they are forward-noised as before.
+    guidance = S != 0 is classifier-free guidance of strength S in every sampler the predictor builds (windows, trials,
+    ensembles): the noise prediction becomes eps_c + S (eps_c - eps_u).  It needs a denoiser trained with `train --cond-drop`
+    (model.cond_drop > 0, read when the predictor is built) on clean conditioning columns."""
 
     def __init__(self, model, num_sample_steps: int = 100, seed: int = 0, output_data_format: str = 'all_frames',
                  use_graph: bool = True, eta: float = 0.0, num_samples: int = 1, solver: str = 'ddim',
-                 spacing: str = 'time'):
+                 spacing: str = 'time', guidance: float = 0.0):
         if output_data_format != 'all_frames':
             raise ValueError("DiffusionLabelPredictor: the diffusion models need --output-data-format all_frames")
         if not 0.0 <= float(eta) <= 1.0:
@@ -50,8 +53,11 @@ class DiffusionLabelPredictor:
         self.model, self.seed = model, int(seed)
         self.eta, self.num_samples = float(eta), int(num_samples)
         self.last_std: Optional[Dict[str, torch.Tensor]] = None
+        self.guidance = float(guidance)
+        # `observations` is set again by every call (_checks); a guided sampler is built for the only kind it takes
         self.sampler = ConditionalDDIMSampler(model, num_sample_steps, use_graph=use_graph, eta=self.eta, seed=self.seed,
-                                              solver=solver, spacing=spacing)
+                                              solver=solver, spacing=spacing, guidance=self.guidance,
+                                              observations='clean' if self.guidance != 0.0 else 'noised')
         self._mask = None                    # label_mask of the last (F, D): one tensor, so the sampler checks it once
         self._trial = None                   # ((hop, blend), StitchedDDIMSampler, mask_cols) of the last predict_trial
         self._trial_ens = None               # the same of the last predict_trial_ensemble, a StochasticStitchedSampler
@@ -154,7 +160,8 @@ class DiffusionLabelPredictor:
         obs, kind = self._checks(inputs, 'trial')
         s = self.sampler
         self._trial = self._kept(self._trial, (hop, blend, obs.shape[2]), lambda: StitchedDDIMSampler(
-            self.model, s.S, hop=hop, blend=blend, use_graph=s.use_graph, solver=s.solver, spacing=s.spacing, seed=self.seed))
+            self.model, s.S, hop=hop, blend=blend, use_graph=s.use_graph, solver=s.solver, spacing=s.spacing, seed=self.seed,
+            observations=s.observations, guidance=self.guidance))
         _, sampler, mask_cols = self._trial
         sampler.observations = kind
         return self._sample(sampler, obs, mask_cols, draw, None)
@@ -174,7 +181,7 @@ class DiffusionLabelPredictor:
         s = self.sampler
         self._trial_ens = self._kept(self._trial_ens, (hop, blend, obs.shape[2]), lambda: StochasticStitchedSampler(
             self.model, s.S, eta=self.eta, hop=hop, blend=blend, use_graph=s.use_graph, spacing=s.spacing, seed=self.seed,
-            solver=s.solver))
+            solver=s.solver, observations=s.observations, guidance=self.guidance))
         _, sampler, mask_cols = self._trial_ens
         sampler.observations = kind
         return self._sample(sampler, obs, mask_cols, draw, 'trial_ids')
