@@ -94,6 +94,39 @@ GUIDANCE_HELP = ('classifier-free guidance strength S of the sampler: the noise 
                  'of `train --cond-cols N --cond-drop P` with P > 0. 0 = off.')
 
 
+RESAMPLE_HELP = ('RePaint resampling of the masked loop (Lugmayr et al. 2022): after denoising, the state is diffused back '
+                 'J levels with fresh noise and denoised again, --resample-times R times in all at every J-th level, so the '
+                 'free columns harmonise with the observed ones. Needs --sample-eta 0 and --sampler ddim, J in 1 .. '
+                 '--sample-steps - 1; costs about R times the denoiser evaluations. Its effect on label accuracy of trained '
+                 'checkpoints is unmeasured. 0 = off.')
+
+
+def add_resample_flags(p, scope: str):
+    """--resample-jump J --resample-times R of analyze / visualize; the defaults 0 / 1 mean off"""
+    p.add_argument('--resample-jump', type=int, default=0, help=f'[{scope}] ' + RESAMPLE_HELP)
+    p.add_argument('--resample-times', type=int, default=1,
+                   help=f'[{scope}] visits of every jump point of --resample-jump (1 = the plain loop).')
+
+
+def checked_resample(args, steps: int, eta: float, solver: str):
+    """--resample-jump / --resample-times of analyze / visualize -> (J, R), or None when off"""
+    J, R = int(getattr(args, 'resample_jump', 0)), int(getattr(args, 'resample_times', 1))
+    if J == 0 and R == 1:
+        return None
+    if R < 1:
+        raise SystemExit(f"--resample-times {R} must be >= 1")
+    if not 1 <= J <= steps - 1:
+        raise SystemExit(f"--resample-jump {J} must be in 1 .. --sample-steps - 1 = {steps - 1} (a jump goes back J of the "
+                         f"loop's steps); 0 with --resample-times 1 turns resampling off")
+    if eta > 0.0:
+        raise SystemExit(f"--resample-jump needs --sample-eta 0, got {eta}: the step noise of an eta > 0 loop is keyed by the "
+                         f"step index, so a revisited step would repeat its draw")
+    if solver != 'ddim':
+        raise SystemExit(f"--resample-jump needs --sampler ddim, got {solver}: the multistep history of a second-order "
+                         f"solver is invalid after a jump")
+    return (J, R)
+
+
 def checked_guidance(args, model) -> float:
     """--guidance S of analyze / visualize, once the checkpoint is loaded: refused for a denoiser that never saw the null
     condition"""

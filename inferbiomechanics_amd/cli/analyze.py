@@ -12,8 +12,8 @@ import torch
 from torch.utils.data import DataLoader
 
 from ..loss.RegressionLossEvaluator import RegressionLossEvaluator
-from ._common import (GUIDANCE_HELP, add_additive_flags, add_component_flags, checked_guidance, dtype_of, is_diffusion,
-                      open_dataset, pick_device)
+from ._common import (GUIDANCE_HELP, add_additive_flags, add_component_flags, add_resample_flags, checked_guidance,
+                      checked_resample, dtype_of, is_diffusion, open_dataset, pick_device)
 from .abstract_command import AbstractCommand
 
 
@@ -57,6 +57,7 @@ class AnalyzeCommand(AbstractCommand):
                        help='[diffusion models] sampling grid: uniform in the timestep, or uniform in log-SNR (no need for '
                             '--sample-steps to divide the training steps; the grid for few-step dpmpp2m / dpmpp2m_sde sampling).')
         p.add_argument('--guidance', type=float, default=0.0, help='[diffusion models] ' + GUIDANCE_HELP)
+        add_resample_flags(p, 'diffusion models')
         p.add_argument('--use-ema', action='store_true', default=False,
                        help='Evaluate the EMA weights of the checkpoint (`train --ema-decay`) instead of its last weights.')
 
@@ -118,6 +119,7 @@ class AnalyzeCommand(AbstractCommand):
         solver, spacing = getattr(args, 'sampler', 'ddim'), getattr(args, 'sample_spacing', 'time')
         if solver == 'dpmpp2m' and eta > 0.0:
             raise SystemExit("--sampler dpmpp2m is deterministic: it needs --sample-eta 0")
+        resample = checked_resample(args, args.sample_steps, eta, solver)
         predictor = None
         for split, csv_name in (('dev', 'dev_analysis.csv'), ('train', 'train_analysis.csv')):
             logging.info(f'## Loading {split} dataset:')
@@ -130,7 +132,7 @@ class AnalyzeCommand(AbstractCommand):
                 predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
                                                     output_data_format=args.output_data_format, eta=eta,
                                                     num_samples=num_samples, solver=solver, spacing=spacing,
-                                                    guidance=checked_guidance(args, model))
+                                                    guidance=checked_guidance(args, model), resample=resample)
             evaluator = RegressionLossEvaluator(dataset=dataset, split=split, device=device)
             loader = DataLoader(dataset, batch_size=args.sample_batch, shuffle=False, num_workers=args.data_loading_workers)
             compute_report = bool(getattr(dataset, 'skeletons', None))

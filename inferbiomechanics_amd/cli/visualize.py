@@ -20,8 +20,8 @@ import torch
 from ..loss.RegressionLossEvaluator import RegressionLossEvaluator
 from ..data.AddBiomechanicsDataset import LOSS_KEY_ORDER
 from ..diffusion.schedule import STITCH_BLENDS, stitch_layout
-from ._common import (GUIDANCE_HELP, add_additive_flags, add_component_flags, checked_guidance, dtype_of, is_diffusion,
-                      open_dataset, pick_device)
+from ._common import (GUIDANCE_HELP, add_additive_flags, add_component_flags, add_resample_flags, checked_guidance,
+                      checked_resample, dtype_of, is_diffusion, open_dataset, pick_device)
 from .abstract_command import AbstractCommand
 from .analyze import window_subject, window_trial
 
@@ -72,6 +72,7 @@ class VisualizeCommand(AbstractCommand):
                             '(deterministic: needs --sample-eta 0 and --num-samples 1), or dpmpp2m_sde, its stochastic form '
                             '(takes --sample-eta > 0 and --num-samples > 1; use it with --sample-spacing logsnr).')
         p.add_argument('--guidance', type=float, default=0.0, help='[--trial-frames] ' + GUIDANCE_HELP)
+        add_resample_flags(p, '--trial-frames')
         p.add_argument('--sample-spacing', type=str, default='time', choices=['time', 'logsnr'],
                        help='[--trial-frames] sampling grid of both loops: uniform in the timestep, or uniform in log-SNR '
                             '(the grid for few-step dpmpp2m / dpmpp2m_sde sampling).')
@@ -131,7 +132,9 @@ class VisualizeCommand(AbstractCommand):
         if not 0.0 <= eta <= 1.0 or num_samples < 1:
             raise SystemExit("--sample-eta must be in [0, 1] and --num-samples >= 1")
         solver = getattr(args, 'sampler', 'ddim')
-        ensemble = eta > 0.0 or num_samples > 1
+        resample = checked_resample(args, args.sample_steps, eta, solver)
+        # a resampled loop keys its re-noise draws by trial id, so it takes the ensemble path (at eta = 0, also at K = 1)
+        ensemble = eta > 0.0 or num_samples > 1 or resample is not None and resample[1] > 1
         if solver == 'dpmpp2m' and ensemble:
             raise SystemExit("--sampler dpmpp2m is deterministic: it needs --sample-eta 0 and --num-samples 1")
         view = self.diffusion_view(args, 'test', self.ensure_geometry(args.geometry_folder))
@@ -152,7 +155,7 @@ class VisualizeCommand(AbstractCommand):
         predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
                                             output_data_format=args.output_data_format, eta=eta, num_samples=num_samples,
                                             solver=solver, spacing=getattr(args, 'sample_spacing', 'time'),
-                                            guidance=checked_guidance(args, model))
+                                            guidance=checked_guidance(args, model), resample=resample)
         gather = start.long()[:, None] + torch.arange(T)[None, :]      # [Wd, T] trial frames of the disjoint windows
         w0 = cover[:, 0].long()
         t0 = torch.arange(F) - start.long()[w0]

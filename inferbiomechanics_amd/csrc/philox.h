@@ -2,7 +2,8 @@
 // Philox4x32-10 (Salmon et al., SC'11) and Box-Muller over its words.  counter = (block, step, stream, domain), key = the
 // 64-bit seed.  The domains keep the streams of one (seed, step, stream) apart: 0 = the eps / start draw, 1 = timesteps,
 // 2 = the noise term of a sampling step (there `stream` is the window id and `step` the sampling step), 3 = the condition
-// dropout of a training step (cfg.hip: `block` is the window's place in the batch, one decision per window).
+// dropout of a training step (cfg.hip: `block` is the window's place in the batch, one decision per window), 4 = the re-noise
+// of a resampling jump (resample.hip: `stream` is the trial id and `step` the ordinal of the jump within the sampling call).
 #pragma once
 #include "ib_common.h"
 

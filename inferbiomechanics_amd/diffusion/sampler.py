@@ -39,7 +39,20 @@ and the noise buffer hold 2B windows, the B of the call and their twins under th
 columns, never written after allocation).  One step = {forward over the 2B windows, ib_cfg_combine: the first half of the
 noise buffer becomes eps_c + s (eps_c - eps_u), the row's update launch over the first half exactly as without guidance,
 ib_cfg_mirror: the free columns and the timesteps of the first half copied to the second, counter++} (csrc/cfg.hip).  At
-guidance = 0 none of it exists: the launches, buffers, signature and bits are the unguided loop's."""
+guidance = 0 none of it exists: the launches, buffers, signature and bits are the unguided loop's.
+
+RePaint resampling (resample = (jump, times); ConditionalDDIMSampler and, by keyword, StochasticStitchedSampler; eta = 0 and
+solver 'ddim'; Lugmayr et al. 2022) changes no step either.  The masked loop of an unconditional denoiser is the replacement
+method, and it is biased: the free elements are denoised as if the pinned ones had been generated with them.  The loop
+therefore walks schedule.resample_walk instead of 0 .. S-1: a 'step' is the step above, the captured graph replayed
+unchanged; a 'jump' diffuses the state back `jump` levels (ib_resample_renoise, csrc/resample.hip: fresh noise keyed by
+(seed, id, visit) at the free elements, the observed ones pinned to their level) and takes the device counter back with it,
+two launches on the sampler's stream between replays (_jump_launches; a guided loop mirrors after it).  What a jump reads --
+the jump table, the ids, the one-window layout -- is passed at every call and is no part of the captured step or its
+signature, so the setting may change between calls on one capture.  Off (None, or times = 1) nothing of it exists.  One
+exception to "changes no step": a resampled loop over ONE-WINDOW trials (F == T) updates with the per-window entry
+(ib_ddim_cond_step; _one_window_step), which makes it ConditionalDDIMSampler(resample=...) bit for bit at every row pitch;
+that choice is part of the signature, so there the step is captured again when the setting goes on or off."""
 from dataclasses import dataclass
 from typing import Optional, Sequence, Union
 
@@ -47,7 +60,7 @@ import torch
 
 from .. import hip
 from ..plans import ParamSource
-from .schedule import OBSERVATIONS, check_sampler_settings, stitch_layout
+from .schedule import OBSERVATIONS, check_resample, check_sampler_settings, resample_walk, stitch_layout
 
 
 @dataclass(frozen=True)
@@ -110,6 +123,27 @@ class DDIMSampler:
         self._bufs = {}
 
     guidance = 0.0                           # the classes that take observations set it (classifier-free guidance)
+    resample = None                          # (jump, times): the classes that take observations and ids set it
+    _takes_ids = True                        # sample() takes the ids that key a call's draws
+
+    def _resampling(self, c: Optional[SampleCall] = None):
+        """(jump, times) of a resampled loop, None for the plain one (resample None or times == 1), with the refusals of
+        the setting -- at construction (c None) and again at every call, since the attributes may be changed between calls"""
+        r = check_resample(self.resample, self.S)
+        if r is None:
+            return None
+        if not self._takes_ids:
+            raise ValueError(f"{type(self).__name__} takes no trial ids, and the ids key the re-noise draws of a resampled "
+                             f"loop: use StochasticStitchedSampler(eta=0, resample={tuple(r)})")
+        if self.eta > 0.0:
+            raise ValueError(f"resample = {r} needs eta = 0, got eta = {self.eta}: the step noise of the update kernels is "
+                             f"keyed by the step index, so a revisited step would repeat its draw")
+        if self._second():
+            raise ValueError(f"resample = {r} needs solver 'ddim', got {self.solver!r}: the multistep history of a "
+                             f"second-order solver is invalid after a jump")
+        if c is not None and c.observed is None:
+            raise ValueError(f"resample = {r} needs observations: without them there is nothing to harmonise with")
+        return r
 
     def _check_guidance(self, guidance: float, observations: str):
         """the constructor's check of `guidance` for the classes that take observations"""
@@ -183,6 +217,7 @@ class DDIMSampler:
         return self._run(self._call(x_T, x_T.shape[0], 1, window_ids), x_T, steps)
 
     def _run(self, c: SampleCall, x_T: torch.Tensor, steps: Optional[int]) -> torch.Tensor:
+        self._resampling(c)                  # a refused call leaves the sampler as it was
         if not x_T.is_cuda and not hip._dry_run:
             x_T = x_T.to(next(self.model.parameters()).device)
         if hip._dry_run:
@@ -229,6 +264,8 @@ class DDIMSampler:
                ptr(tabs.ddim_coef), ptr(tabs.ddim_t), self.S, Dp)
         if lay is not None:
             sig += ("stitch", c.N, lay["F"], self.hop, self.blend, ptr(lay["start"]), ptr(lay["cover"]), ptr(lay["wn"]))
+            if self._one_window_step(c):
+                sig += ("one_window_step",)  # another update launch: the step itself changes with the setting here
         if cond:
             sig += (ptr(tabs.obs_coef), tabs.observations)
         if self.solver != "ddim" or self.spacing != "time":
@@ -287,7 +324,8 @@ class DDIMSampler:
             x.copy_(_cut(c.lay, _join(c.lay, x, c.N)))
 
     def _sample(self, c: SampleCall, x_T: torch.Tensor, steps: Optional[int] = None) -> torch.Tensor:
-        ids = _checked_ids(c.ids, c.N, "window" if c.lay is None else "trial") if self.eta > 0.0 else None
+        jumps = self._resampling(c)
+        ids = _checked_ids(c.ids, c.N, "window" if c.lay is None else "trial") if self.eta > 0.0 or jumps else None
         m = self.model
         m.ensure_packed()
         m.sync_shadow()
@@ -296,8 +334,18 @@ class DDIMSampler:
         obs = self.observations if c.observed is not None else None
         if not tabs.serves(self.S, self.eta, self.solver, self.spacing, obs):
             tabs.set_sampler(self.S, self.eta, self.solver, self.spacing, observations=obs or tabs.observations)
+        if jumps and not tabs.serves(self.S, self.eta, self.solver, self.spacing, obs, resample_jump=jumps[0]):
+            tabs.set_resample(jumps[0])      # the jump table alone: the step's tables, and so its capture, stay
         plan = m._get_plan(dev)
         self._prepare(c, tabs, dev)
+        if jumps:
+            # what a jump reads beside the step's buffers.  The eta = 0 step reads neither, so they are no part of the
+            # captured step's signature: resampling goes on, off or to other values and the same capture is replayed
+            b = self._bufs
+            if "win" not in b:
+                b["win"] = torch.zeros(c.N, dtype=torch.int64, device=dev)
+            if c.lay is None and "one_window" not in b:
+                b["one_window"] = tuple(t.to(dev) for t in stitch_layout(c.T, c.T, c.T)[:3])
         if ids is not None:
             self._bufs["win"].copy_(ids)
         x, t_vec, ctr = self._bufs["x"], self._bufs["t"], self._bufs["ctr"]
@@ -313,13 +361,22 @@ class DDIMSampler:
             plan.set_inference(True)             # weights are frozen for the whole loop
             plan.prepare_inference(P, c.T, c.D, table=tabs.temb)
         try:
-            return self._loop(c, x, t_vec, ctr, tabs, P, steps)
+            return self._loop(c, x, t_vec, ctr, tabs, P, steps, jumps)
         finally:
             if hasattr(plan, "set_inference"):
                 plan.set_inference(False)
 
-    def _loop(self, c: SampleCall, x, t_vec, ctr, tabs, P, steps):
-        n = self.S if steps is None else min(steps, self.S)
+    def _loop(self, c: SampleCall, x, t_vec, ctr, tabs, P, steps, jumps=None):
+        """the plain loop, or the walk of a resampled one (schedule.resample_walk): a 'step' is the one step below, eager or
+        the captured graph replayed unchanged; a 'jump' is issued on the same stream between the replays, with no host
+        synchronisation.  `steps` truncates either after that many denoiser evaluations"""
+        if jumps:
+            walk = resample_walk(self.S, *jumps)
+            total = sum(op[0] == "step" for op in walk)
+            n = total if steps is None else min(steps, total)
+        else:
+            walk = None
+            n = self.S if steps is None else min(steps, self.S)
         done = 0
         if self.use_graph and self._graph is None:
             self._step_launches(c, x, t_vec, ctr, tabs, P)       # eager warm-up step allocates plan buffers
@@ -330,12 +387,44 @@ class DDIMSampler:
                 self._step_launches(c, x, t_vec, ctr, tabs, P)
                 g.end()
                 self._graph = g
-        for _ in range(done, n):
+
+        def step():
             if self._graph is not None:
                 self._graph.launch()
             else:
                 self._step_launches(c, x, t_vec, ctr, tabs, P)
+
+        if walk is None:
+            for _ in range(done, n):
+                step()
+        else:
+            # the first two operations of any walk are steps (a jump point lies at position >= 2), so the warm-up step
+            # above is ('step', 0)
+            evals = 0
+            for op in walk:
+                if evals >= n:
+                    break
+                if op[0] == "jump":
+                    self._jump_launches(c, x, t_vec, ctr, tabs, jumps[0], op[2])
+                    continue
+                if evals >= done:
+                    step()
+                evals += 1
         return x[:, :, :c.D].clone()
+
+    def _jump_launches(self, c: SampleCall, x, t_vec, ctr, tabs, jump: int, visit: int):
+        """one jump of a resampled loop: the state at the counter's position is diffused back `jump` levels
+        (ib_resample_renoise, csrc/resample.hip: fresh noise at the free elements keyed by (seed, id, visit), the observed
+        ones pinned to their level), the counter follows, and a guided loop mirrors the re-noised free columns and the new
+        timesteps into the null-condition twins"""
+        b = self._bufs
+        v = lambda t: t.view((c.N, c.W) + tuple(t.shape[1:]))
+        start, cover = (c.lay["start"], c.lay["cover"]) if c.lay is not None else b["one_window"][:2]
+        hip.resample_renoise(v(x), v(b["x0"]), v(b["z"]), b["mask"], tabs.resample_coef, tabs.obs_coef, tabs.ddim_t, start,
+                             cover, b["win"], self.seed, jump, visit, t_vec[:c.B], step_dev=ctr, D=c.D)
+        hip.counter_add(ctr, -jump)
+        if "xin" in b:
+            hip.cfg_mirror(b["xin"], t_vec, int(self.model.cond_cols), D=c.D)
 
     def _step_launches(self, c: SampleCall, x, t_vec, ctr, tabs, P: ParamSource):
         plan = self.model._get_plan(x.device)
@@ -359,9 +448,16 @@ class DDIMSampler:
             self._launch_update(c, x, plan.forward(x, t_vec, tabs.temb, P), ctr, t_vec, tabs)
         hip.counter_add(ctr, 1)
 
+    def _one_window_step(self, c: SampleCall) -> bool:
+        """a resampled loop over one-window trials (F == T) updates with the per-window entry: one window has nothing to
+        blend, and so the loop IS ConditionalDDIMSampler(resample=...) with window ids = trial ids bit for bit at every row
+        pitch -- the stitched entry rounds an observed element by column, the per-window one by flat offset, and the two
+        differ where the pitch is no multiple of 8 (include/ib_hip_stitch.h).  The plain stitched loops keep their entry"""
+        return c.lay is not None and c.W == 1 and self._resampling(c) is not None
+
     def _launch_update(self, c: SampleCall, x, eps, ctr, t_vec, tabs):
         """THE choice of the update launch (the module docstring's table): by layout, solver order, eta > 0, observations"""
-        b, lay = self._bufs, c.lay
+        b, lay = self._bufs, None if self._one_window_step(c) else c.lay
         second, noisy, sde, cond = self._second(), self.eta > 0.0, self._sde(), c.observed is not None
         # the stitched entries and ib_sde_dpmpp_step see the state as [N, W, T, ld]: a per-window 'dpmpp2m_sde' loop as
         # [B, 1, T, ld], every window a trial of its own (the layout stitch_layout(T, T, T)), the window ids as trial ids
@@ -419,11 +515,13 @@ class ConditionalDDIMSampler(DDIMSampler):
 
     def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True, eta: float = 0.0,
                  seed: Optional[int] = None, solver: str = "ddim", spacing: str = "time", observations: str = "noised",
-                 guidance: float = 0.0):
+                 guidance: float = 0.0, resample=None):
         check_sampler_settings(eta, solver, spacing, observations)
         super().__init__(model, num_sample_steps, use_graph, eta, seed, solver, spacing)
         self.observations = observations
         self._check_guidance(guidance, observations)
+        self.resample = resample
+        self._resampling()
         self._mask_ok = None                 # (mask, (version, cond_cols)) of the last mask 'clean' mode accepted
 
     @torch.no_grad()
@@ -472,7 +570,7 @@ class StitchedDDIMSampler(DDIMSampler):
 
     def __init__(self, model, num_sample_steps: int = 100, hop: Optional[int] = None, blend: str = "ramp",
                  use_graph: bool = True, solver: str = "ddim", spacing: str = "time", observations: str = "noised",
-                 seed: Optional[int] = None, eta: float = 0.0, guidance: float = 0.0):
+                 seed: Optional[int] = None, eta: float = 0.0, guidance: float = 0.0, resample=None):
         if float(eta) != 0.0:
             raise ValueError(f"StitchedDDIMSampler is deterministic: eta must be 0, got {eta} (the step noise of an eta > 0 "
                              f"loop is keyed by window and in-window frame, not by trial frame)")
@@ -488,6 +586,10 @@ class StitchedDDIMSampler(DDIMSampler):
         stitch_layout(3 * self.T, self.T, self.hop, blend)     # refuses a bad hop or blend here, not at the first call
         self._lay = None                     # the layout of the last trial length sampled, the only one kept
         self._mask_ok = None                 # (mask_cols, (version, cond_cols)) of the last mask 'clean' mode accepted
+        self.resample = resample             # taken only to be refused with the reason, as eta is: this class has no ids
+        self._resampling()
+
+    _takes_ids = False
 
     @property
     def layout(self) -> Optional[dict]:
@@ -571,10 +673,12 @@ class StochasticStitchedSampler(StitchedDDIMSampler):
     def __init__(self, model, num_sample_steps: int = 100, eta: float = 1.0, hop: Optional[int] = None, blend: str = "ramp",
                  use_graph: bool = True, spacing: str = "time", observations: str = "noised", seed: Optional[int] = None,
                  guidance: float = 0.0, **keywords):
-        """keywords: solver = 'ddim' (the default) or 'dpmpp2m_sde', by keyword only.  It is not a named parameter:
+        """keywords: solver = 'ddim' (the default) or 'dpmpp2m_sde', and resample = (jump, times) (eta = 0 and 'ddim' only:
+        RePaint resampling, ConditionalDDIMSampler's), by keyword only.  `solver` is not a named parameter:
         tests/test_stitch_noise_plumbing_cpu.py pins that this signature names no `solver`, from when the class had one
         solver; a misspelt keyword is still a TypeError"""
         solver = keywords.pop("solver", "ddim")
+        resample = keywords.pop("resample", None)
         if keywords:
             raise TypeError(f"StochasticStitchedSampler: unexpected keyword arguments {sorted(keywords)}")
         if solver == "dpmpp2m":
@@ -586,6 +690,10 @@ class StochasticStitchedSampler(StitchedDDIMSampler):
         super().__init__(model, num_sample_steps, hop, blend, use_graph, solver, spacing, observations, seed,
                          guidance=guidance)
         self.eta = float(eta)                # the parent's constructor hands DDIMSampler eta = 0
+        self.resample = resample
+        self._resampling()
+
+    _takes_ids = True
 
     @torch.no_grad()
     def sample(self, z: torch.Tensor, observed: Optional[torch.Tensor] = None, mask_cols: Optional[torch.Tensor] = None,

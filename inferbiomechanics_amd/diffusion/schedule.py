@@ -273,6 +273,80 @@ def sde_observation_noise_coefficients(num_train_steps: int = 1000, num_sample_s
     return torch.stack(rows)
 
 
+def check_resample(resample, num_sample_steps: int):
+    """the refusals of a `resample = (jump, times)` setting for a loop of S steps -> (jump, times), or None where the loop is
+    the plain one: resample None, or times == 1 (every jump point is left backwards times - 1 = 0 times)"""
+    if resample is None:
+        return None
+    try:
+        jump, times = resample
+        ok = int(jump) == jump and int(times) == times
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"resample must be None or (jump, times), two integers, got {resample!r}")
+    jump, times, S = int(jump), int(times), int(num_sample_steps)
+    if not 1 <= jump <= S - 1:
+        raise ValueError(f"resample: jump = {jump} must be in 1 .. S - 1 = {S - 1} (a jump goes back `jump` of the loop's "
+                         f"{S} steps and must land on a position >= 1)")
+    if times < 1:
+        raise ValueError(f"resample: times = {times} must be at least 1 (1: the plain loop)")
+    return None if times == 1 else (jump, times)
+
+
+def resample_walk(num_sample_steps: int, jump: int, times: int):
+    """The operations of one resampled sampling call (RePaint, Lugmayr et al. 2022, Algorithm 1 and its get_schedule_jump,
+    restated on POSITIONS): the loop's position p in 0 .. S is the noise level of the state, p < S at alpha_bar[t_p] and S at
+    alpha_bar = 1; ('step', p) is update row p and moves p -> p + 1, ('jump', p, visit) diffuses the state back from p to
+    p - jump, visit = 0, 1, 2, ... the ordinal of the jump within the call.  Jump points are p = S - m jump, m = 0, 1, ...
+    while p - jump > 0; on arriving at one the walk leaves it backwards, times - 1 times in total (the counters are not
+    refilled when a later jump passes them again).  Evaluations: S + (ceil(S / jump) - 1) (times - 1) jump.  times == 1 is
+    the plain loop."""
+    S = int(num_sample_steps)
+    if check_resample((jump, times), S) is None:
+        return [("step", p) for p in range(S)]
+    jump, times = int(jump), int(times)
+    left = {}
+    p = S
+    while p - jump > 0:
+        left[p] = times - 1
+        p -= jump
+    ops, p, visit = [], 0, 0
+    while p < S:
+        ops.append(("step", p))
+        p += 1
+        if left.get(p, 0) > 0:
+            left[p] -= 1
+            ops.append(("jump", p, visit))
+            visit += 1
+            p -= jump
+    return ops
+
+
+def resample_evaluations(num_sample_steps: int, jump: int, times: int) -> int:
+    """denoiser evaluations of resample_walk(S, jump, times)"""
+    S, jump, times = int(num_sample_steps), int(jump), int(times)
+    return S + (-(-S // jump) - 1) * (times - 1) * jump
+
+
+def resample_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100, jump: int = 1,
+                          spacing: str = "time") -> torch.Tensor:
+    """[S + 1, 2] float64 (c_x, c_z) of a resampling jump, indexed by the position p the state is at: the forward diffusion
+    from level L[p] back to L[p - jump], x <- sqrt(rho) x + sqrt(1 - rho) z' with rho = L[p - jump] / L[p], L[p] =
+    alpha_bar[t_p] for p < S and L[S] = 1.  Rows p < jump are (0, 0) and never read."""
+    ab = alphas_cumprod(num_train_steps)
+    ts = sample_timesteps(num_train_steps, num_sample_steps, spacing).tolist()
+    S, jump = len(ts), int(jump)
+    if not 1 <= jump <= S - 1:
+        raise ValueError(f"jump = {jump} must be in 1 .. S - 1 = {S - 1}")
+    L = [ab[t] for t in ts] + [torch.tensor(1.0, dtype=torch.float64)]
+    out = torch.zeros((S + 1, 2), dtype=torch.float64)
+    for p in range(jump, S + 1):
+        rho = L[p - jump] / L[p]
+        out[p, 0], out[p, 1] = torch.sqrt(rho), torch.sqrt(1 - rho)
+    return out
+
+
 STITCH_KMAX = 8                 # IB_STITCH_KMAX (include/ib_hip_stitch.h): the most windows that may cover one trial frame
 STITCH_BLENDS = ("uniform", "ramp")
 
@@ -354,6 +428,7 @@ class DiffusionTables:
         obs = clean_observation_coefficients if observations == "clean" else observation_coefficients
         self.obs_coef = obs(N, num_sample_steps, spacing).to(torch.float32).to(dev).contiguous()
         self.ddim_coef_eta = self.obs_noise_coef = self.dpmpp_coef = self.sde_coef = self.sde_obs_noise_coef = None
+        self.resample_jump, self.resample_coef = 0, None         # a new grid drops the jump table: set_resample makes it
         up = lambda t: t.to(torch.float32).to(dev).contiguous()
         # an eta > 0 loop gets the stochastic tables of ITS solver and not the other's: the two (r, q) tables differ at
         # eta < 1, and serves() refuses a loop whose own tables are missing
@@ -366,15 +441,29 @@ class DiffusionTables:
         if solver in ("dpmpp2m", "dpmpp2m_sde"):                 # 'dpmpp2m_sde' at eta = 0 runs the 'dpmpp2m' launches
             self.dpmpp_coef = up(dpmpp_coefficients(N, num_sample_steps, spacing))
 
+    def set_resample(self, jump: int):
+        """the jump table of a resampled loop on the current grid, resample_coef [S + 1, 2] (resample_coefficients), cast once;
+        jump = 0 drops it.  No other table is touched, so a captured step that bakes their pointers in stays valid: the jump
+        launch is issued between the replays and is handed this table at every call"""
+        jump = int(jump)
+        if jump == 0:
+            self.resample_jump, self.resample_coef = 0, None
+            return
+        coef = resample_coefficients(self.num_train_steps, self.num_sample_steps, jump, self.spacing)   # raises first
+        self.resample_jump = jump
+        self.resample_coef = coef.to(torch.float32).to(self.sqrt_ab.device).contiguous()
+
     def serves(self, num_sample_steps: int, eta: float = 0.0, solver: str = "ddim", spacing: str = "time",
-               observations: Optional[str] = None) -> bool:
+               observations: Optional[str] = None, resample_jump: int = 0) -> bool:
         """whether the current tables are the ones a loop with these settings reads: the grid (S, spacing) must match; the
         eta tables only matter to an eta > 0 loop -- and then they must be those of the loop's own solver, first-order
         ('ddim') or 'dpmpp2m_sde' --, the second-order table only to 'dpmpp2m' and 'dpmpp2m_sde' and the observation table only
-        to a masked loop, which names the kind it reads (None: the loop reads no observation table)"""
+        to a masked loop, which names the kind it reads (None: the loop reads no observation table), the jump table only to
+        a resampled loop, which names its jump (0: the loop reads no jump table)"""
         noisy = float(eta) > 0.0
         return (self.num_sample_steps == num_sample_steps and self.spacing == spacing
                 and (observations is None or self.observations == observations)
+                and (not resample_jump or (self.resample_jump == int(resample_jump) and self.resample_coef is not None))
                 and (not noisy or self.eta == float(eta))
                 and (not (noisy and solver == "ddim") or self.ddim_coef_eta is not None)
                 and (not (noisy and solver == "dpmpp2m_sde") or self.sde_coef is not None)

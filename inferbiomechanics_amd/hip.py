@@ -10,8 +10,9 @@ module is imported, so a new entry point needs its declaration there and its wra
 sampler updates (csrc/stitch.hip) are declared in a second header, ``include/ib_hip_stitch.h``, parsed the same way into
 ``_STITCH_SIGS``, the merged head launches of the transformer step (csrc/head_jobs.h) in a third, ``include/ib_hip_head.h``
 (``_HEAD_SIGS``), the stochastic second-order sampler update (csrc/sde.hip) in a fourth, ``include/ib_hip_sde.h``
-(``_SDE_SIGS``), classifier-free guidance (csrc/cfg.hip) in a fifth, ``include/ib_hip_cfg.h`` (``_CFG_SIGS``); a name may be
-declared once in the five.
+(``_SDE_SIGS``), classifier-free guidance (csrc/cfg.hip) in a fifth, ``include/ib_hip_cfg.h`` (``_CFG_SIGS``), the jump of a
+resampled masked loop (csrc/resample.hip) in a sixth, ``include/ib_hip_resample.h`` (``_RESAMPLE_SIGS``); a name may be declared
+once in the six.
 """
 from __future__ import annotations
 
@@ -33,6 +34,7 @@ STITCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sti
 HEAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_head.h")
 SDE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sde.h")
 CFG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_cfg.h")
+RESAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_resample.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -96,10 +98,10 @@ def _read_header(path: Optional[str] = None) -> str:
 
 
 # a table per header: _SIGS and declared_symbols() describe ib_hip.h only, _STITCH_SIGS the stitched trial sampling
-_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS, _CFG_SIGS = (
+_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS, _CFG_SIGS, _RESAMPLE_SIGS = (
     _parse_header(_read_header(_path)) for _path in
-    (HEADER_PATH, STITCH_HEADER_PATH, HEAD_HEADER_PATH, SDE_HEADER_PATH, CFG_HEADER_PATH))
-_TABLES = (_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS, _CFG_SIGS)
+    (HEADER_PATH, STITCH_HEADER_PATH, HEAD_HEADER_PATH, SDE_HEADER_PATH, CFG_HEADER_PATH, RESAMPLE_HEADER_PATH))
+_TABLES = (_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS, _CFG_SIGS, _RESAMPLE_SIGS)
 _ALL_SIGS = {_n: _v for _t in _TABLES for _n, _v in _t.items()}   # every entry point: what _sig() looks up and lib() binds
 if len(_ALL_SIGS) != sum(len(_t) for _t in _TABLES):
     _twice = sorted(n for n in _ALL_SIGS if sum(n in _t for _t in _TABLES) > 1)
@@ -135,6 +137,11 @@ def sde_symbols() -> List[str]:
 def cfg_symbols() -> List[str]:
     """Every function include/ib_hip_cfg.h declares"""
     return sorted(_CFG_SIGS)
+
+
+def resample_symbols() -> List[str]:
+    """Every function include/ib_hip_resample.h declares"""
+    return sorted(_RESAMPLE_SIGS)
 
 
 def _sig(name: str):
@@ -2480,7 +2487,8 @@ def _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D):
     """the window-batch state of a stitched update, x [N, W, T, ld] with eps like it, and its layout tables (schedule.
     stitch_layout, on x's device): start int32 [W], cover int32 [F, 2], wn fp32 [F, STITCH_KMAX], checked for what the kernel
     trusts -- every window inside the trial, every frame's windows really covering it.  x0 / z / mask / obs_coef: all None
-    (the unconditional loop) or all given, as _masked_operands takes them.  -> (N, W, T, F, D, ld)"""
+    (the unconditional loop) or all given, as _masked_operands takes them.  eps and wn are None for an entry point that has
+    no such operand (resample_renoise).  -> (N, W, T, F, D, ld)"""
     _req(x, "x", x.dtype, 4)
     if not x.is_contiguous():
         raise HipError(f"{what}: x must be a contiguous [N, W, T, ld] state")
@@ -2488,7 +2496,8 @@ def _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D):
     D = ld if D is None else int(D)
     if D <= 0 or D > ld:
         raise HipError(f"{what}: D = {D} must be in 1 .. ld = {ld}")
-    _like_x(what, "eps", eps, x)
+    if eps is not None:
+        _like_x(what, "eps", eps, x)
     given = [t is not None for t in (x0, z, mask, obs_coef)]
     if any(given) and not all(given):
         raise HipError(f"{what}: x0, z, mask and obs_coef come together (the masked loop) or not at all")
@@ -2496,12 +2505,17 @@ def _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D):
         _masked_operands(what, x, x0, z, mask, obs_coef)
     _req(start, "start", torch.int32, 1)
     _req(cover, "cover", torch.int32, 2)
-    _req(wn, "wn", torch.float32, 2)
     F = cover.shape[0]
-    if start.numel() != W or tuple(cover.shape) != (F, 2) or tuple(wn.shape) != (F, STITCH_KMAX) or F < T:
+    if wn is None:
+        wn_ok, wn_shape, tables = True, (), (("start", start), ("cover", cover))
+    else:
+        _req(wn, "wn", torch.float32, 2)
+        wn_ok, wn_shape, tables = tuple(wn.shape) == (F, STITCH_KMAX), tuple(wn.shape), (("start", start), ("cover", cover),
+                                                                                       ("wn", wn))
+    if start.numel() != W or tuple(cover.shape) != (F, 2) or not wn_ok or F < T:
         raise HipError(f"{what}: the layout tables must be start [W] = [{W}], cover [F, 2], wn [F, {STITCH_KMAX}] with "
-                       f"F >= T = {T}; got {tuple(start.shape)}, {tuple(cover.shape)}, {tuple(wn.shape)}")
-    for name, t in (("start", start), ("cover", cover), ("wn", wn)):
+                       f"F >= T = {T}; got {tuple(start.shape)}, {tuple(cover.shape)}, {wn_shape}")
+    for name, t in tables:
         if not t.is_contiguous() or t.device != x.device:
             raise HipError(f"{what}: {name} must be contiguous and on the device of x ({x.device})")
     # the kernel trusts start and cover: check them when the tables change.  The verdict of the last pair is kept (by
@@ -2603,6 +2617,44 @@ def sde_dpmpp_step(x, eps, hist, x0, z, mask, coef, obs_coef, obs_noise_coef, ti
                                    _ptr(obs_noise_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out),
                                    _ptr(start), _ptr(cover), _ptr(wn), _ptr(trial_ids), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                    N, W, T, F, D, ld, dtype_code(x.dtype), stream_ptr()), "ib_sde_dpmpp_step")
+    return x
+
+
+def resample_renoise(x, x0, z, mask, coef, obs_coef, timesteps, start, cover, trial_ids, seed, back, visit, t_out, step=0,
+                     step_dev=None, D=None):
+    """the jump of a resampled masked loop in place (csrc/resample.hip) over the window batch x [N, W, T, ld]: the state at
+    position s = step + *step_dev is diffused back `back` levels, x <- coef[s][0] x + coef[s][1] z' at the free elements
+    (coef [S + 1, 2]: schedule.resample_coefficients), z' keyed by (seed, trial_ids[n], visit, TRIAL frame, column) and
+    generated inside the kernel so every copy of an element receives the same normal, and the observed elements are pinned to
+    obs_coef[s - back] (x0, z).  x0, z, mask [T, ld], obs_coef [S + 1, 2]: all None (every element free) or the masked loop's
+    operands as in stitch_ddim_step.  t_out int64 [N * W] receives timesteps[s - back]; the step counter is the caller's:
+    counter_add(step_dev, -back) follows.  trial_ids: int64 [N] on the device; visit: the ordinal of the jump within the
+    call, one 32-bit word of the generator's counter.  A per-window loop is the same call with W = 1 and the layout
+    stitch_layout(T, T, T)."""
+    what = "resample_renoise"
+    N, W, T, F, D, ld = _stitch_operands(what, x, None, x0, z, mask, obs_coef, start, cover, None, D)
+    _req(coef, "coef", torch.float32, 2)
+    _req(timesteps, "timesteps", torch.int64, 1)
+    S = timesteps.numel()
+    if tuple(coef.shape) != (S + 1, 2) or not coef.is_contiguous():
+        raise HipError(f"{what}: coef must be contiguous [S + 1, 2] = [{S + 1}, 2] fp32 for timesteps [S] int64")
+    _req(t_out, "t_out", torch.int64, 1)
+    if t_out.numel() != N * W:
+        raise HipError(f"{what}: t_out must be int64 [N * W] = [{N * W}]")
+    if step_dev is not None:
+        _req(step_dev, "step_dev", torch.int32)
+    if obs_coef is not None and obs_coef.shape[0] != S + 1:
+        raise HipError(f"{what}: obs_coef must have S + 1 = {S + 1} rows, got {obs_coef.shape[0]}")
+    _win_ids(what, trial_ids, N, "trial_ids", "N", x.device)
+    back, visit = int(back), int(visit)
+    if not 1 <= back <= S:
+        raise HipError(f"{what}: back = {back} must be in 1 .. S = {S}")
+    if not 0 <= visit < 1 << 32:
+        raise HipError(f"{what}: visit = {visit} must fit 32 bits (one word of the generator's counter)")
+    _check(lib().ib_resample_renoise(_ptr(x), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef), _ptr(timesteps), S,
+                                     int(step), _ptr(step_dev), back, visit, _ptr(t_out), _ptr(start), _ptr(cover),
+                                     _ptr(trial_ids), int(seed) & 0xFFFFFFFFFFFFFFFF, N, W, T, F, D, ld,
+                                     dtype_code(x.dtype), stream_ptr()), "ib_resample_renoise")
     return x
 
 

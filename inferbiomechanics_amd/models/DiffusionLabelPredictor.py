@@ -39,11 +39,15 @@ class DiffusionLabelPredictor:
     pinned clean at every step (ConditionalDDIMSampler, observations = 'clean'); at 0 they are forward-noised as before.
     guidance = S != 0 is classifier-free guidance of strength S in every sampler the predictor builds (windows, trials,
     ensembles): the noise prediction becomes eps_c + S (eps_c - eps_u).  It needs a denoiser trained with `train --cond-drop`
-    (model.cond_drop > 0, read when the predictor is built) on clean conditioning columns."""
+    (model.cond_drop > 0, read when the predictor is built) on clean conditioning columns.
+    resample = (jump, times) is RePaint resampling of the masked loop (diffusion/sampler.py; eta = 0 and solver 'ddim' only):
+    every call then takes the id path, member ids from ``member_ids`` also at K = 1 -- they key the re-noise draws, so a
+    window's labels do not depend on batching --, and num_samples = K > 1 gives an ensemble at eta = 0 (mean and
+    ``last_std``).  What it does to label accuracy on trained checkpoints is unmeasured."""
 
     def __init__(self, model, num_sample_steps: int = 100, seed: int = 0, output_data_format: str = 'all_frames',
                  use_graph: bool = True, eta: float = 0.0, num_samples: int = 1, solver: str = 'ddim',
-                 spacing: str = 'time', guidance: float = 0.0):
+                 spacing: str = 'time', guidance: float = 0.0, resample=None):
         if output_data_format != 'all_frames':
             raise ValueError("DiffusionLabelPredictor: the diffusion models need --output-data-format all_frames")
         if not 0.0 <= float(eta) <= 1.0:
@@ -57,7 +61,8 @@ class DiffusionLabelPredictor:
         # `observations` is set again by every call (_checks); a guided sampler is built for the only kind it takes
         self.sampler = ConditionalDDIMSampler(model, num_sample_steps, use_graph=use_graph, eta=self.eta, seed=self.seed,
                                               solver=solver, spacing=spacing, guidance=self.guidance,
-                                              observations='clean' if self.guidance != 0.0 else 'noised')
+                                              observations='clean' if self.guidance != 0.0 else 'noised', resample=resample)
+        self.resample = self.sampler._resampling()       # (jump, times), or None for the plain loop
         self._mask = None                    # label_mask of the last (F, D): one tensor, so the sampler checks it once
         self._trial = None                   # ((hop, blend), StitchedDDIMSampler, mask_cols) of the last predict_trial
         self._trial_ens = None               # the same of the last predict_trial_ensemble, a StochasticStitchedSampler
@@ -143,7 +148,7 @@ class DiffusionLabelPredictor:
                 if labels[k].shape[1] != F:
                     raise ValueError("DiffusionLabelPredictor: labels must be 'all_frames' (one row per input frame)")
         obs, self.sampler.observations = self._checks(inputs, 'window')
-        single = self.num_samples == 1 and self.eta == 0.0
+        single = self.num_samples == 1 and self.eta == 0.0 and self.resample is None
         return self._sample(self.sampler, obs, self._label_mask(F, obs.shape[2]), draw, None if single else 'window_ids')
 
     @torch.no_grad()
@@ -154,6 +159,9 @@ class DiffusionLabelPredictor:
         (``StitchedDDIMSampler``: a window every ``hop`` frames, default window // 2, blended by ``blend``), so every frame
         gets one answer and there are no seams.  Returns the four ``LOSS_KEY_ORDER`` outputs as fp32 ``[N, F, C]``.  Trial b
         draws its start noise from (seed, draw + b).  Deterministic: needs eta = 0 and num_samples = 1."""
+        if self.resample is not None:
+            raise ValueError(f"predict_trial: resample = {self.resample} needs trial ids for its re-noise draws and the "
+                             f"deterministic stitched sampler takes none: use predict_trial_ensemble, which runs it at eta = 0")
         if self.eta != 0.0 or self.num_samples != 1:
             raise ValueError(f"predict_trial: stitched sampling is deterministic, it needs eta = 0 and num_samples = 1 (got "
                              f"eta = {self.eta}, num_samples = {self.num_samples})")
@@ -181,7 +189,7 @@ class DiffusionLabelPredictor:
         s = self.sampler
         self._trial_ens = self._kept(self._trial_ens, (hop, blend, obs.shape[2]), lambda: StochasticStitchedSampler(
             self.model, s.S, eta=self.eta, hop=hop, blend=blend, use_graph=s.use_graph, spacing=s.spacing, seed=self.seed,
-            solver=s.solver, observations=s.observations, guidance=self.guidance))
+            solver=s.solver, observations=s.observations, guidance=self.guidance, resample=self.resample))
         _, sampler, mask_cols = self._trial_ens
         sampler.observations = kind
         return self._sample(sampler, obs, mask_cols, draw, 'trial_ids')
