@@ -2743,6 +2743,8 @@ def scale_by_device_scalar(y: torch.Tensor, scale: torch.Tensor):
     _req(scale, "scale", torch.float32)
     if not y.is_contiguous() or scale.numel() != 1:
         raise HipError("scale_by_device_scalar: y must be contiguous, scale a single fp32 element")
+    if y.numel() == 0:                 # nothing to scale; an empty tensor has no address to hand the library
+        return y
     _check(lib().ib_scale_by_device_scalar(_ptr(y), _ptr(scale), y.numel(), dtype_code(y.dtype), stream_ptr()),
            "ib_scale_by_device_scalar")
     return y

@@ -192,3 +192,47 @@ def test_fused_trainer_with_batchnorm_and_dropout_matches_module_path():
     model.eval()
     tr.step(({k: v.to(DEV) for k, v in inputs.items()}, {k: v.to(DEV) for k, v in labels.items()}))
     assert np.isfinite(tr.loss_value())
+
+
+@pytest.mark.parametrize("train", [True, False])
+def test_batchnorm_under_silu_hands_the_pre_activation_down(train):
+    """BatchNorm1d in front of every Linear with act = silu: the only configuration in which DenseStackPlan.backward gives
+    ib_batchnorm_bwd the PRE-ACTIVATION z of the layer below (silu's derivative needs it) and not its output.  fp32 at
+    FF_OPT_B against the float64 oracle, at this file's fp32 tolerances."""
+    from inferbiomechanics_amd import hip
+    from inferbiomechanics_amd.loss.RegressionLossEvaluator import RegressionLossEvaluator
+    rt = 1e-3
+    model = make(True, False, torch.float32, act="silu")
+    model.train(train)
+    inputs, labels = ff_inputs(FF_OPT_B, 10, 23, 5), ff_labels(FF_OPT_B, 10)
+    with hip.record_launches() as rec:
+        out = model(inputs)
+        loss = RegressionLossEvaluator(None, "train", device=DEV)({}, dict(out), labels, [], [], train_args())
+        loss.backward()
+    bwd = [a for n, a in rec.calls if n == "ib_batchnorm_bwd"]           # a[12] = act_below, a[13] = aux (include/ib_hip.h)
+    acts = [a[12] for a in bwd]
+    assert len(acts) == 3 and acts.count(hip.ACT["silu"]) == 2 and acts.count(0) == 1, acts      # the lowest has none below
+    saved = model._plan.saved
+    auxs = [a[13] for a in bwd if a[12]]
+    assert auxs == [saved[1][3].data_ptr(), saved[0][3].data_ptr()], "act_below = silu must read z, not the output"
+    sd = {k: (v.detach().cpu().double().requires_grad_(True) if v.is_floating_point() else v.cpu())
+          for k, v in model.state_dict().items()}
+    lin = [k[:-7] for k in sd if k.endswith(".weight") and sd[k].dim() == 2]
+    bns = [k[:-13] for k in sd if k.endswith(".running_mean")]
+    st0 = ff_opt_state({k: tuple(v.shape) for k, v in model.state_dict().items()})     # the running statistics BEFORE the step
+    bnp = [dict(weight=sd[p + ".weight"], bias=sd[p + ".bias"], running_mean=st0[p + ".running_mean"].to(torch.float32).double(),
+                running_var=st0[p + ".running_var"].to(torch.float32).double()) for p in bns]
+    oexp, stats = R.feedforward_forward_opts([(sd[p + ".weight"], sd[p + ".bias"]) for p in lin],
+                                             {k: v.double() for k, v in inputs.items()}, "silu", 10, bn=bnp, training=train)
+    lexp, _, _ = R.regression_loss(oexp, {k: v.double() for k, v in ff_labels(FF_OPT_B, 10).items()}, range(6), range(6),
+                                   range(6), range(12))
+    lexp.backward()
+    for k, v in out.items():
+        close(v, oexp[k], rt, "out/" + k)
+    close(loss, lexp, rt, "loss")
+    for k, q in model.named_parameters():
+        e = sd[k].grad
+        close(q.grad, e, rt, "grad/" + k, atol=rt * 0.05 * float(e.norm()))
+    for p, (rm, rv) in zip(bns, stats):
+        close(model.state_dict()[p + ".running_mean"], rm, 1e-5, p + ".running_mean", atol=1e-7)
+        close(model.state_dict()[p + ".running_var"], rv, 1e-5, p + ".running_var", atol=1e-7)
