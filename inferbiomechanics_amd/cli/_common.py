@@ -12,6 +12,9 @@ from ..data.AddBiomechanicsDataset import (AddBiomechanicsDataset, MotionWindowV
                                                SyntheticWindowDataset)
 
 
+LABEL_NAMES = ('cop', 'force', 'torque', 'wrench')       # LOSS_KEY_ORDER, as the reports name the keys
+
+
 def add_component_flags(p: argparse.ArgumentParser, train_defaults: bool):
     d6 = list(range(6)) if train_defaults else None
     p.add_argument('--predict-grf-components', type=int, nargs='+', default=d6 if train_defaults else [1],
@@ -125,6 +128,31 @@ def checked_resample(args, steps: int, eta: float, solver: str):
         raise SystemExit(f"--resample-jump needs --sampler ddim, got {solver}: the multistep history of a second-order "
                          f"solver is invalid after a jump")
     return (J, R)
+
+
+INTERVAL_HELP = ('report order statistics of the posterior ensemble: the central interval of nominal coverage L (0 < L < 1) of '
+                 'every label, from the Weibull (type 6) quantiles of the --num-samples members. Needs --num-samples >= 2; K '
+                 'members cover at most (K - 1) / (K + 1), the report states what a calibrated ensemble of that size attains. '
+                 'Default: off.')
+
+
+def add_interval_flag(p, scope: str):
+    """--interval L of analyze / visualize; the default None means off"""
+    p.add_argument('--interval', type=float, default=None, help=f'[{scope}] ' + INTERVAL_HELP)
+
+
+def checked_interval(args, num_samples: int):
+    """--interval L of analyze / visualize -> L, or None when off"""
+    L = getattr(args, 'interval', None)
+    if L is None:
+        return None
+    L = float(L)
+    if not 0.0 < L < 1.0:
+        raise SystemExit(f"--interval {L} must lie strictly between 0 and 1 (the interval's nominal coverage)")
+    if num_samples < 2:
+        raise SystemExit(f"--interval needs --num-samples >= 2, got {num_samples}: an interval is made of the order statistics "
+                         f"of an ensemble")
+    return L
 
 
 def checked_guidance(args, model) -> float:

@@ -11,9 +11,12 @@ import os
 import torch
 from torch.utils.data import DataLoader
 
+from ..data.AddBiomechanicsDataset import LOSS_KEY_ORDER
+from ..diffusion.ensemble import calibrated_coverage
 from ..loss.RegressionLossEvaluator import RegressionLossEvaluator
-from ._common import (GUIDANCE_HELP, add_additive_flags, add_component_flags, add_resample_flags, checked_guidance,
-                      checked_resample, dtype_of, is_diffusion, open_dataset, pick_device)
+from ._common import (GUIDANCE_HELP, LABEL_NAMES, add_additive_flags, add_component_flags, add_interval_flag,
+                      add_resample_flags, checked_guidance, checked_interval, checked_resample, dtype_of, is_diffusion,
+                      open_dataset, pick_device)
 from .abstract_command import AbstractCommand
 
 
@@ -58,6 +61,7 @@ class AnalyzeCommand(AbstractCommand):
                             '--sample-steps to divide the training steps; the grid for few-step dpmpp2m / dpmpp2m_sde sampling).')
         p.add_argument('--guidance', type=float, default=0.0, help='[diffusion models] ' + GUIDANCE_HELP)
         add_resample_flags(p, 'diffusion models')
+        add_interval_flag(p, 'diffusion models')
         p.add_argument('--use-ema', action='store_true', default=False,
                        help='Evaluate the EMA weights of the checkpoint (`train --ema-decay`) instead of its last weights.')
 
@@ -120,6 +124,7 @@ class AnalyzeCommand(AbstractCommand):
         if solver == 'dpmpp2m' and eta > 0.0:
             raise SystemExit("--sampler dpmpp2m is deterministic: it needs --sample-eta 0")
         resample = checked_resample(args, args.sample_steps, eta, solver)
+        interval = checked_interval(args, num_samples)
         predictor = None
         for split, csv_name in (('dev', 'dev_analysis.csv'), ('train', 'train_analysis.csv')):
             logging.info(f'## Loading {split} dataset:')
@@ -132,7 +137,8 @@ class AnalyzeCommand(AbstractCommand):
                 predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
                                                     output_data_format=args.output_data_format, eta=eta,
                                                     num_samples=num_samples, solver=solver, spacing=spacing,
-                                                    guidance=checked_guidance(args, model), resample=resample)
+                                                    guidance=checked_guidance(args, model), resample=resample,
+                                                    interval=interval)
             evaluator = RegressionLossEvaluator(dataset=dataset, split=split, device=device)
             loader = DataLoader(dataset, batch_size=args.sample_batch, shuffle=False, num_workers=args.data_loading_workers)
             compute_report = bool(getattr(dataset, 'skeletons', None))
@@ -141,12 +147,16 @@ class AnalyzeCommand(AbstractCommand):
                 n = min(n, args.max_windows)
             i = 0
             spread = EnsembleSpread() if num_samples > 1 else None
+            calibration = EnsembleCalibration(num_samples, interval) if interval is not None else None
             with torch.no_grad(), open(os.path.join(checkpoint_dir, csv_name), 'a') as f:
                 writer = None
                 for inputs, labels, subj, trial in loader:
                     outputs = predictor(inputs, labels, draw=i)
                     if spread is not None:
                         spread.add(outputs, predictor.last_std, labels, min(len(subj), n - i))
+                    if calibration is not None:
+                        calibration.add(predictor.last_interval, predictor.last_crps, predictor.last_rank,
+                                        predictor.last_inside, min(len(subj), n - i))
                     for b in range(min(len(subj), n - i)):
                         one = lambda d: {k: v[b:b + 1] for k, v in d.items()}
                         evaluator(one(inputs), one(outputs), one(labels), subj[b:b + 1], trial[b:b + 1], args,
@@ -166,6 +176,9 @@ class AnalyzeCommand(AbstractCommand):
             evaluator.print_report(log_to_wandb=False)
             if spread is not None:
                 print(spread.line(split, num_samples))
+            if calibration is not None:
+                print(calibration.line(split))
+                print(calibration.histogram_line(split))
         return True
 
 
@@ -189,6 +202,43 @@ class EnsembleSpread:
         parts = [f'{k}: mean std {self.std_sum[k] / self.n[k]:.6g}, RMS err of mean {(self.sq_sum[k] / self.n[k]) ** 0.5:.6g}'
                  for k in self.n]
         return f'Ensemble spread ({split}, {num_samples} samples per window): ' + '; '.join(parts)
+
+
+class EnsembleCalibration:
+    """per label key, over the windows of a split, from the predictor's order statistics (hip.ensemble_order): how often the
+    label lies inside the level-L interval, the interval's mean width, the mean fair CRPS, and the histogram of the label's
+    rank among the K members (K + 1 bins; flat for a calibrated ensemble).  Report bookkeeping on the host, in float64 and
+    int."""
+
+    def __init__(self, num_samples: int, level: float):
+        self.K, self.level = int(num_samples), float(level)
+        self.names = dict(zip(LOSS_KEY_ORDER, LABEL_NAMES))
+        self.n = {}
+        self.inside = {}
+        self.width_sum = {}
+        self.crps_sum = {}
+        self.hist = {}
+
+    def add(self, interval, crps, rank, inside, windows: int):
+        for k in crps:
+            lo, hi, c = (t[:windows].detach().cpu().double() for t in (interval['lo'][k], interval['hi'][k], crps[k]))
+            r, hit = rank[k][:windows].detach().cpu().long(), inside[k][:windows].detach().cpu().long()
+            self.n[k] = self.n.get(k, 0) + c.numel()
+            self.inside[k] = self.inside.get(k, 0) + int(hit.sum())
+            self.width_sum[k] = self.width_sum.get(k, 0.0) + float((hi - lo).sum())
+            self.crps_sum[k] = self.crps_sum.get(k, 0.0) + float(c.sum())
+            counts = torch.bincount(r.reshape(-1), minlength=self.K + 1).tolist()
+            self.hist[k] = [a + b for a, b in zip(self.hist.get(k, [0] * (self.K + 1)), counts)]
+
+    def line(self, split: str) -> str:
+        cal = calibrated_coverage(self.level, self.K)
+        parts = [f'{self.names.get(k, k)}: coverage {self.inside[k] / self.n[k]:.4f} (calibrated ensemble: {cal:.4f}), mean width '
+                 f'{self.width_sum[k] / self.n[k]:.6g}, CRPS {self.crps_sum[k] / self.n[k]:.6g}' for k in self.n]
+        return f'Ensemble calibration ({split}, {self.K} samples per window, level {self.level:g}): ' + '; '.join(parts)
+
+    def histogram_line(self, split: str) -> str:
+        return f'Rank histogram ({split}): ' + '; '.join(f"{self.names.get(k, k)}: [{' '.join(str(c) for c in self.hist[k])}]"
+                                                           for k in self.hist)
 
 
 def window_subject(dataset, subj) -> str:

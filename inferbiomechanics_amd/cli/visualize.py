@@ -20,12 +20,12 @@ import torch
 from ..loss.RegressionLossEvaluator import RegressionLossEvaluator
 from ..data.AddBiomechanicsDataset import LOSS_KEY_ORDER
 from ..diffusion.schedule import STITCH_BLENDS, stitch_layout
-from ._common import (GUIDANCE_HELP, add_additive_flags, add_component_flags, add_resample_flags, checked_guidance,
-                      checked_resample, dtype_of, is_diffusion, open_dataset, pick_device)
+from ._common import (GUIDANCE_HELP, LABEL_NAMES, add_additive_flags, add_component_flags, add_interval_flag,
+                      add_resample_flags, checked_guidance, checked_interval, checked_resample, dtype_of, is_diffusion,
+                      open_dataset, pick_device)
 from .abstract_command import AbstractCommand
 from .analyze import window_subject, window_trial
 
-LABEL_NAMES = ('cop', 'force', 'torque', 'wrench')       # LOSS_KEY_ORDER, as the trial report names the keys
 
 
 class VisualizeCommand(AbstractCommand):
@@ -73,6 +73,7 @@ class VisualizeCommand(AbstractCommand):
                             '(takes --sample-eta > 0 and --num-samples > 1; use it with --sample-spacing logsnr).')
         p.add_argument('--guidance', type=float, default=0.0, help='[--trial-frames] ' + GUIDANCE_HELP)
         add_resample_flags(p, '--trial-frames')
+        add_interval_flag(p, '--trial-frames')
         p.add_argument('--sample-spacing', type=str, default='time', choices=['time', 'logsnr'],
                        help='[--trial-frames] sampling grid of both loops: uniform in the timestep, or uniform in log-SNR '
                             '(the grid for few-step dpmpp2m / dpmpp2m_sde sampling).')
@@ -121,7 +122,8 @@ class VisualizeCommand(AbstractCommand):
         row with the force block of both; per trial and label key the RMS error of both against the labels, their RMS
         difference, and for the force block the mean jump |x[f] - x[f - 1]| across the per-window boundaries.  With
         --sample-eta > 0 or --num-samples > 1 both are ensemble means (predict_trial_ensemble; the per-window predictor with
-        the same eta and K), and one more line per trial and label key gives the mean standard deviation over the members."""
+        the same eta and K), and one more line per trial and label key gives the mean standard deviation over the members --
+        and, with --interval L, the mean width of the level-L interval of both (DiffusionLabelPredictor, interval)."""
         from ..models.DiffusionLabelPredictor import DiffusionLabelPredictor
         F = int(args.trial_frames)
         if not is_diffusion(args.model_type):
@@ -133,6 +135,7 @@ class VisualizeCommand(AbstractCommand):
             raise SystemExit("--sample-eta must be in [0, 1] and --num-samples >= 1")
         solver = getattr(args, 'sampler', 'ddim')
         resample = checked_resample(args, args.sample_steps, eta, solver)
+        interval = checked_interval(args, num_samples)
         # a resampled loop keys its re-noise draws by trial id, so it takes the ensemble path (at eta = 0, also at K = 1)
         ensemble = eta > 0.0 or num_samples > 1 or resample is not None and resample[1] > 1
         if solver == 'dpmpp2m' and ensemble:
@@ -155,7 +158,7 @@ class VisualizeCommand(AbstractCommand):
         predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
                                             output_data_format=args.output_data_format, eta=eta, num_samples=num_samples,
                                             solver=solver, spacing=getattr(args, 'sample_spacing', 'time'),
-                                            guidance=checked_guidance(args, model), resample=resample)
+                                            guidance=checked_guidance(args, model), resample=resample, interval=interval)
         gather = start.long()[:, None] + torch.arange(T)[None, :]      # [Wd, T] trial frames of the disjoint windows
         w0 = cover[:, 0].long()
         t0 = torch.arange(F) - start.long()[w0]
@@ -173,11 +176,12 @@ class VisualizeCommand(AbstractCommand):
             inputs = {key: v.unsqueeze(0) for key, v in inputs.items()}
             if ensemble:
                 stitched = predictor.predict_trial_ensemble(inputs, hop=hop, blend=args.trial_blend, draw=k)
-                stitched_std = predictor.last_std
+                stitched_std, stitched_iv = predictor.last_std, predictor.last_interval
             else:
                 stitched = predictor.predict_trial(inputs, hop=hop, blend=args.trial_blend, draw=k)
             windows = predictor({key: v[0, gather] for key, v in inputs.items()}, draw=k * gather.shape[0])
             windows_std = predictor.last_std if ensemble else None
+            windows_iv = predictor.last_interval
             print(f"trial {k} ({window_subject(dataset, [subj])} / {window_trial(dataset, [subj], [trial])}): {F} frames, "
                   f"stitched as {W} windows of {T} every {hop} frames ({args.trial_blend}) | {gather.shape[0]} disjoint windows")
             print(f"{'frame':>5} {'win':>3}  {'stitched force':<48} | per-window force")
@@ -194,8 +198,13 @@ class VisualizeCommand(AbstractCommand):
             if ensemble:
                 for name, key in zip(LABEL_NAMES, LOSS_KEY_ORDER):
                     ss, ws = stitched_std[key][0].cpu(), windows_std[key].cpu()[w0, t0]
+                    widths = ""
+                    if interval is not None:
+                        width = lambda iv: (iv['hi'][key] - iv['lo'][key]).cpu().double()
+                        widths = (f"; mean width of the {interval:g} interval stitched {float(width(stitched_iv)[0].mean()):.6f}, "
+                                  f"per-window {float(width(windows_iv)[w0, t0].mean()):.6f}")
                     print(f"trial {k} {name:>6}: mean std over {num_samples} samples stitched {float(ss.double().mean()):.6f}, "
-                          f"per-window {float(ws.double().mean()):.6f}")
+                          f"per-window {float(ws.double().mean()):.6f}{widths}")
             if seams.numel():
                 jump = lambda x: float((x[seams] - x[seams - 1]).abs().mean())
                 print(f"trial {k}  force: mean jump across the {seams.numel()} per-window boundaries: stitched {jump(sf):.6f}, "

@@ -11,8 +11,9 @@ sampler updates (csrc/stitch.hip) are declared in a second header, ``include/ib_
 ``_STITCH_SIGS``, the merged head launches of the transformer step (csrc/head_jobs.h) in a third, ``include/ib_hip_head.h``
 (``_HEAD_SIGS``), the stochastic second-order sampler update (csrc/sde.hip) in a fourth, ``include/ib_hip_sde.h``
 (``_SDE_SIGS``), classifier-free guidance (csrc/cfg.hip) in a fifth, ``include/ib_hip_cfg.h`` (``_CFG_SIGS``), the jump of a
-resampled masked loop (csrc/resample.hip) in a sixth, ``include/ib_hip_resample.h`` (``_RESAMPLE_SIGS``); a name may be declared
-once in the six.
+resampled masked loop (csrc/resample.hip) in a sixth, ``include/ib_hip_resample.h`` (``_RESAMPLE_SIGS``), the order statistics
+of a posterior ensemble (csrc/ensemble.hip) in a seventh, ``include/ib_hip_ensemble.h`` (``_ENSEMBLE_SIGS``); a name may be
+declared once in the seven.
 """
 from __future__ import annotations
 
@@ -35,6 +36,7 @@ HEAD_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_head.
 SDE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sde.h")
 CFG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_cfg.h")
 RESAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_resample.h")
+ENSEMBLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_ensemble.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -101,10 +103,12 @@ def _read_header(path: Optional[str] = None) -> str:
 _SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS, _CFG_SIGS, _RESAMPLE_SIGS = (
     _parse_header(_read_header(_path)) for _path in
     (HEADER_PATH, STITCH_HEADER_PATH, HEAD_HEADER_PATH, SDE_HEADER_PATH, CFG_HEADER_PATH, RESAMPLE_HEADER_PATH))
-_TABLES = (_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS, _CFG_SIGS, _RESAMPLE_SIGS)
-_ALL_SIGS = {_n: _v for _t in _TABLES for _n, _v in _t.items()}   # every entry point: what _sig() looks up and lib() binds
-if len(_ALL_SIGS) != sum(len(_t) for _t in _TABLES):
-    _twice = sorted(n for n in _ALL_SIGS if sum(n in _t for _t in _TABLES) > 1)
+_TABLES = (_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS, _CFG_SIGS, _RESAMPLE_SIGS)   # the training step's and the samplers'
+_ENSEMBLE_SIGS = _parse_header(_read_header(ENSEMBLE_HEADER_PATH))                  # what is done with the samples
+_HEADERS = _TABLES + (_ENSEMBLE_SIGS,)
+_ALL_SIGS = {_n: _v for _t in _HEADERS for _n, _v in _t.items()}  # every entry point: what _sig() looks up and lib() binds
+if len(_ALL_SIGS) != sum(len(_t) for _t in _HEADERS):
+    _twice = sorted(n for n in _ALL_SIGS if sum(n in _t for _t in _HEADERS) > 1)
     raise HipError(f"declared in two headers: {_twice}")
 _kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_STITCH_KMAX[ \t]+(\d+)[ \t]*$", _read_header(STITCH_HEADER_PATH), flags=re.M)
 if _kmax is None:
@@ -142,6 +146,11 @@ def cfg_symbols() -> List[str]:
 def resample_symbols() -> List[str]:
     """Every function include/ib_hip_resample.h declares"""
     return sorted(_RESAMPLE_SIGS)
+
+
+def ensemble_symbols() -> List[str]:
+    """Every function include/ib_hip_ensemble.h declares"""
+    return sorted(_ENSEMBLE_SIGS)
 
 
 def _sig(name: str):
@@ -2680,6 +2689,51 @@ def ensemble_stats(x, mean=None, std=None):
     _check(lib().ib_ensemble_stats(_ptr(x), _ptr(outs[0]), _ptr(outs[1]), B, K, n, dtype_code(x.dtype), stream_ptr()),
            "ib_ensemble_stats")
     return outs[0], outs[1]
+
+
+_kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_ENSEMBLE_KMAX[ \t]+(\d+)[ \t]*$", _read_header(ENSEMBLE_HEADER_PATH), flags=re.M)
+if _kmax is None:
+    raise HipError(f"{ENSEMBLE_HEADER_PATH} does not define IB_ENSEMBLE_KMAX")
+ENSEMBLE_KMAX = int(_kmax.group(1))      # the largest sorting network the library is built with
+
+
+def ensemble_order(x, cols, level, truth=None):
+    """Order statistics of the ensemble x [B, K, rows, ld] (fp32 / bf16, contiguous) over the column window cols = (c0, w)
+    (csrc/ensemble.hip): a dict of fp32 [B, rows, w] tensors 'lo', 'median', 'hi' -- the Weibull (type 6) quantiles at
+    (1 - level) / 2, 0.5 and (1 + level) / 2, positions from diffusion.ensemble.quantile_position -- and, when truth (fp32
+    [B, rows, w], contiguous) is given, 'crps' (fair ensemble CRPS, fp32), 'rank' (#{members < truth}, uint8, 0 .. K) and
+    'inside' (lo <= truth <= hi, uint8).  Only the window's columns of x are read."""
+    from .diffusion.ensemble import interval_levels, quantile_position
+    what = "ensemble_order"
+    _req(x, "x")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise HipError(f"{what}: x must be contiguous [B, K, rows, ld], got {tuple(x.shape)}")
+    B, K, rows, ld = (int(v) for v in x.shape)
+    if min(B, K, rows, ld) <= 0:
+        raise HipError(f"{what}: empty ensemble {tuple(x.shape)}")
+    if K > ENSEMBLE_KMAX:
+        raise HipError(f"{what}: K = {K} members, the sorting networks are built for at most {ENSEMBLE_KMAX}")
+    try:
+        c0, w = (int(v) for v in cols)
+    except (TypeError, ValueError):
+        raise HipError(f"{what}: cols must be (c0, w), got {cols!r}") from None
+    if c0 < 0 or w <= 0 or c0 + w > ld:
+        raise HipError(f"{what}: the column window ({c0}, {w}) does not lie inside a row of {ld} columns")
+    pos = [quantile_position(q, K) for q in interval_levels(level)]
+    shape = (B, rows, w)
+    out = {k: torch.empty(shape, dtype=torch.float32, device=x.device) for k in ("lo", "median", "hi")}
+    if truth is not None:
+        _req(truth, "truth", torch.float32)
+        if tuple(truth.shape) != shape or not truth.is_contiguous() or truth.device != x.device:
+            raise HipError(f"{what}: truth must be contiguous fp32 {shape} on x's device, got {tuple(truth.shape)}")
+        out["crps"] = torch.empty(shape, dtype=torch.float32, device=x.device)
+        out["rank"] = torch.empty(shape, dtype=torch.uint8, device=x.device)
+        out["inside"] = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    _check(lib().ib_ensemble_order(_ptr(x), _ptr(truth), _ptr(out["lo"]), _ptr(out["median"]), _ptr(out["hi"]),
+                                   _ptr(out.get("crps")), _ptr(out.get("rank")), _ptr(out.get("inside")), B, K, rows, ld,
+                                   c0, w, pos[0][0], pos[0][1], pos[1][0], pos[1][1], pos[2][0], pos[2][1],
+                                   dtype_code(x.dtype), stream_ptr()), "ib_ensemble_order")
+    return out
 
 
 def batchnorm_fwd(x, gamma, beta, running_mean, running_var, num_batches_tracked, y, save_mean, save_rstd, training: bool,

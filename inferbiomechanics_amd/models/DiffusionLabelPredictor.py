@@ -12,6 +12,7 @@ import torch
 
 from .. import hip
 from ..data.AddBiomechanicsDataset import INPUT_KEY_ORDER, LOSS_KEY_ORDER, LOSS_KEY_WIDTHS, MotionWindowView
+from ..diffusion.ensemble import interval_levels
 from ..diffusion.sampler import ConditionalDDIMSampler, StitchedDDIMSampler, StochasticStitchedSampler
 
 LABEL_WIDTH = sum(LOSS_KEY_WIDTHS)          # 30: the label block at the end of every frame's row
@@ -43,17 +44,33 @@ class DiffusionLabelPredictor:
     resample = (jump, times) is RePaint resampling of the masked loop (diffusion/sampler.py; eta = 0 and solver 'ddim' only):
     every call then takes the id path, member ids from ``member_ids`` also at K = 1 -- they key the re-noise draws, so a
     window's labels do not depend on batching --, and num_samples = K > 1 gives an ensemble at eta = 0 (mean and
-    ``last_std``).  What it does to label accuracy on trained checkpoints is unmeasured."""
+    ``last_std``).  What it does to label accuracy on trained checkpoints is unmeasured.
+    interval = L (0 < L < 1, needs num_samples >= 2) adds the order statistics of the ensemble, one ``hip.ensemble_order``
+    launch over the 30 label columns after ``ib_ensemble_stats``: ``last_interval`` = {'lo', 'median', 'hi'}, each in the
+    four-key layout of ``last_std`` -- the Weibull (type 6) quantiles at (1 - L) / 2, 0.5, (1 + L) / 2
+    (diffusion/ensemble.py) -- and, for a call that is given labels, ``last_crps`` (fair ensemble CRPS per element),
+    ``last_rank`` (members below the label, 0 .. K) and ``last_inside`` (label inside [lo, hi]), the last two uint8.  The
+    outputs and ``last_std`` do not change by a bit.  With the default None nothing is launched and all four stay None."""
 
     def __init__(self, model, num_sample_steps: int = 100, seed: int = 0, output_data_format: str = 'all_frames',
                  use_graph: bool = True, eta: float = 0.0, num_samples: int = 1, solver: str = 'ddim',
-                 spacing: str = 'time', guidance: float = 0.0, resample=None):
+                 spacing: str = 'time', guidance: float = 0.0, resample=None, interval: Optional[float] = None):
         if output_data_format != 'all_frames':
             raise ValueError("DiffusionLabelPredictor: the diffusion models need --output-data-format all_frames")
         if not 0.0 <= float(eta) <= 1.0:
             raise ValueError(f"DiffusionLabelPredictor: eta must be in [0, 1], got {eta}")
         if int(num_samples) != num_samples or num_samples < 1:
             raise ValueError(f"DiffusionLabelPredictor: num_samples must be an integer >= 1, got {num_samples}")
+        if interval is not None:
+            interval_levels(interval)                                  # ValueError unless 0 < L < 1
+            if num_samples < 2:
+                raise ValueError(f"DiffusionLabelPredictor: interval = {interval} is made of the order statistics of an "
+                                 f"ensemble, it needs num_samples >= 2 (got {num_samples})")
+        self.interval = None if interval is None else float(interval)
+        self.last_interval: Optional[Dict[str, Dict[str, torch.Tensor]]] = None
+        self.last_crps: Optional[Dict[str, torch.Tensor]] = None
+        self.last_rank: Optional[Dict[str, torch.Tensor]] = None
+        self.last_inside: Optional[Dict[str, torch.Tensor]] = None
         self.model, self.seed = model, int(seed)
         self.eta, self.num_samples = float(eta), int(num_samples)
         self.last_std: Optional[Dict[str, torch.Tensor]] = None
@@ -112,13 +129,38 @@ class DiffusionLabelPredictor:
                              f"input columns of a {D}-column row, so it needs cond_cols = {D - LABEL_WIDTH} (or 0)")
         return obs, 'clean' if C else 'noised'      # read per call: a checkpoint may be loaded after __init__
 
-    def _sample(self, sampler, obs: torch.Tensor, mask: torch.Tensor, draw: int, ids_name: Optional[str]):
+    @staticmethod
+    def _split_block(x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """[B, F, 30] (any dtype) -> the four-key layout, dtype kept"""
+        out, c = {}, 0
+        for k, w in zip(LOSS_KEY_ORDER, LOSS_KEY_WIDTHS):
+            out[k] = x[:, :, c:c + w].contiguous()
+            c += w
+        return out
+
+    def _order(self, x: torch.Tensor, labels: Optional[Dict[str, torch.Tensor]]):
+        """the order statistics of the members x [B, K, F, D] over the label columns (one launch) -> last_interval and, with
+        labels, last_crps / last_rank / last_inside"""
+        B, K, F, D = x.shape
+        truth = None
+        if labels is not None:
+            truth = torch.cat([labels[k].to(device=x.device, dtype=torch.float32) for k in LOSS_KEY_ORDER], dim=2).contiguous()
+            if tuple(truth.shape) != (B, F, LABEL_WIDTH):
+                raise ValueError(f"DiffusionLabelPredictor: the labels make a block of {tuple(truth.shape)}, the ensemble's "
+                                 f"label block is {(B, F, LABEL_WIDTH)}")
+        res = hip.ensemble_order(x, (D - LABEL_WIDTH, LABEL_WIDTH), self.interval, truth)
+        self.last_interval = {k: self._split_block(res[k]) for k in ('lo', 'median', 'hi')}
+        if truth is not None:
+            self.last_crps, self.last_rank, self.last_inside = (self._split_block(res[k]) for k in ('crps', 'rank', 'inside'))
+
+    def _sample(self, sampler, obs: torch.Tensor, mask: torch.Tensor, draw: int, ids_name: Optional[str], labels=None):
         """the labels of obs [B, F, D] from `sampler`, a masked one.  ids_name None: row b starts from the draw
         (seed, draw + b) and follows its one deterministic trajectory.  Otherwise it is the id keyword of the sampler's
         sample(): every row is replicated K times, the member ids (member_ids) key both the start draws and the step noise,
         and the result is the members' mean, with their standard deviation in last_std (ib_ensemble_stats)."""
         B, F, D = obs.shape
         K = self.num_samples
+        self.last_interval = self.last_crps = self.last_rank = self.last_inside = None
         if ids_name is None:
             z = torch.cat([sampler.draw_start(1, F, D, self.seed, draw + b) for b in range(B)])
             return self.split_labels(sampler.sample(z, obs, mask))
@@ -128,6 +170,8 @@ class DiffusionLabelPredictor:
         x = sampler.sample(z, members, mask, **{ids_name: ids})
         mean, std = hip.ensemble_stats(x.view(B, K, F, D))
         self.last_std = self.split_labels(std)
+        if self.interval is not None:
+            self._order(x.view(B, K, F, D), labels)
         return self.split_labels(mean)
 
     @staticmethod
@@ -149,7 +193,7 @@ class DiffusionLabelPredictor:
                     raise ValueError("DiffusionLabelPredictor: labels must be 'all_frames' (one row per input frame)")
         obs, self.sampler.observations = self._checks(inputs, 'window')
         single = self.num_samples == 1 and self.eta == 0.0 and self.resample is None
-        return self._sample(self.sampler, obs, self._label_mask(F, obs.shape[2]), draw, None if single else 'window_ids')
+        return self._sample(self.sampler, obs, self._label_mask(F, obs.shape[2]), draw, None if single else 'window_ids', labels)
 
     @torch.no_grad()
     def predict_trial(self, inputs: Dict[str, torch.Tensor], hop: Optional[int] = None, blend: str = 'ramp',
@@ -176,12 +220,13 @@ class DiffusionLabelPredictor:
 
     @torch.no_grad()
     def predict_trial_ensemble(self, inputs: Dict[str, torch.Tensor], hop: Optional[int] = None, blend: str = 'ramp',
-                               draw: int = 0) -> Dict[str, torch.Tensor]:
+                               draw: int = 0, labels: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """Posterior ensembles of whole trials: as ``predict_trial`` with the predictor's own ``eta`` and ``num_samples`` = K
         (``StochasticStitchedSampler``, solver 'ddim' or 'dpmpp2m_sde').  Trial i = draw + b is replicated K times inside the sampler batch;
         member k has trial id i K + k for both its start draw and its step noise.  Returns the members' mean as the four
         ``LOSS_KEY_ORDER`` outputs, fp32 ``[N, F, C]``, and sets ``last_std`` to their unbiased standard deviation in the
-        same layout (0 for K = 1), summed in member order (``ib_ensemble_stats``)."""
+        same layout (0 for K = 1), summed in member order (``ib_ensemble_stats``).  labels ({key: [N, F, c]}, optional) are
+        scored when the predictor has an ``interval`` (``last_crps``, ``last_rank``, ``last_inside``)."""
         if self.sampler.solver not in ('ddim', 'dpmpp2m_sde'):
             raise ValueError(f"predict_trial_ensemble: the stochastic stitched loop is DDIM / DDPM or 'dpmpp2m_sde', solver "
                              f"{self.sampler.solver!r} is deterministic")
@@ -192,4 +237,4 @@ class DiffusionLabelPredictor:
             solver=s.solver, observations=s.observations, guidance=self.guidance, resample=self.resample))
         _, sampler, mask_cols = self._trial_ens
         sampler.observations = kind
-        return self._sample(sampler, obs, mask_cols, draw, 'trial_ids')
+        return self._sample(sampler, obs, mask_cols, draw, 'trial_ids', labels)
