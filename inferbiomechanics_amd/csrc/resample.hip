@@ -12,21 +12,18 @@
 // what the eta = 0 update that stepped to position q wrote, bit for bit.
 //
 // NOISE.  The normal z' of trial element (n, f, d) is Box-Muller over Philox4x32-10 (philox.h) at counter
-// ((f * D + d) >> 2, visit, trial_id[n], kDomainJump), key = seed, the words paired as in stitch.hip.  f is the TRIAL frame,
-// so every copy of an element gets the same normal by construction; `visit`, the ordinal of the jump within the call, sits
-// where the update kernels put the step, in a domain of its own.  Pad columns (d >= D) get no noise: cx * 0 stays 0.
+// ((f * D + d) >> 2, visit, trial_id[n], kDomainJump), key = seed: stitch_step.h's trial_noise, the draw of the update
+// kernels, in a domain of its own, with `visit`, the ordinal of the jump within the call, where they put the step.  f is the
+// TRIAL frame, so every copy of an element gets the same normal by construction.  Pad columns (d >= D) get no noise: cx * 0
+// stays 0.
 //
 // The position lives on the device, so a launch that finds s outside back .. num_steps cannot be refused by the host: it
 // reads no table row and writes nothing.
-#include "ib_common.h"
-#include "launch.h"
-#include "philox.h"
-#include "sampler_elem.h"
+#include "stitch_step.h"
 #include "../../include/ib_hip_resample.h"
 
 namespace {
 
-constexpr int KMAX = IB_STITCH_KMAX;
 constexpr uint32_t kDomainJump = 4u;         // philox.h lists the domains
 
 struct ResampleArgs {
@@ -38,47 +35,9 @@ struct ResampleArgs {
   int64_t N, W, T, F, ld; int D;
 };
 
-// the normals of the V elements from column c (a multiple of V) of trial row f, as stitch.hip's trial_noise makes them, in
-// the jump's domain; bit k of the result: element k is a logical column.  V = 8, BLK (D % 4 == 0): two whole Philox blocks,
-// each made once or -- in the pad columns -- not at all.  Otherwise an element looks its block up.
-template <int V, bool BLK>
-__device__ __forceinline__ unsigned jump_noise(uint32_t k0, uint32_t k1, uint32_t visit, uint32_t tid, int f, int c, int D,
-                                               float (&z)[V]) {
-#pragma unroll
-  for (int k = 0; k < V; ++k) z[k] = 0.f;
-  if constexpr (V == 8 && BLK) {
-    const unsigned ok = (c + 4 <= D ? 0x0fu : 0u) | (c + 8 <= D ? 0xf0u : 0u);
-    const uint32_t q = ((uint32_t)f * (uint32_t)D + (uint32_t)c) >> 2;
-    if (ok & 0x0fu) {
-      const U4 w = philox4x32_10(U4{q, visit, tid, kDomainJump}, k0, k1);
-      box_muller(w.x, w.y, z[0], z[1]); box_muller(w.z, w.w, z[2], z[3]);
-    }
-    if (ok & 0xf0u) {
-      const U4 w = philox4x32_10(U4{q + 1u, visit, tid, kDomainJump}, k0, k1);
-      box_muller(w.x, w.y, z[4], z[5]); box_muller(w.z, w.w, z[6], z[7]);
-    }
-    return ok;
-  } else {
-    unsigned ok = 0;
-    uint32_t cur = 0xffffffffu;                  // no block has this index: F * D / 4 < 2^29
-    U4 w{};
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      if (c + k < D) {
-        const int l = f * D + c + k;
-        const uint32_t q = (uint32_t)l >> 2;
-        if (q != cur) { w = philox4x32_10(U4{q, visit, tid, kDomainJump}, k0, k1); cur = q; }
-        float za, zb;
-        if ((l & 2) == 0) box_muller(w.x, w.y, za, zb); else box_muller(w.z, w.w, za, zb);
-        z[k] = (l & 1) ? zb : za;
-        ok |= 1u << k;
-      }
-    }
-    return ok;
-  }
-}
-
-// COND: x0, z, mask, obs_coef are given.  BLK as jump_noise takes it.
+// COND: x0, z, mask, obs_coef are given.  BLK as trial_noise takes it.  The loop's head -- the copies' offsets and the mask
+// bits -- is stitch_step_kernel's, repeated here: shared as device functions it changes the instructions of every kernel
+// of both.
 template <typename TY, int V, bool COND, bool BLK>
 __global__ __launch_bounds__(256) void resample_renoise_kernel(ResampleArgs p) {
 #pragma clang fp contract(off)
@@ -117,7 +76,7 @@ __global__ __launch_bounds__(256) void resample_renoise_kernel(ResampleArgs p) {
     if (!COND || bits != ALL) {
       float y[V], zn[V];
       ldv<TY, V>(x + off[0], y);
-      const unsigned ok = jump_noise<V, BLK>(p.k0, p.k1, p.visit, (uint32_t)p.trial_id[n], f, c, p.D, zn);
+      const unsigned ok = trial_noise<V, BLK, kDomainJump>(p.k0, p.k1, p.visit, (uint32_t)p.trial_id[n], f, c, p.D, zn);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         const float m = cx * y[j];
@@ -167,21 +126,8 @@ extern "C" int ib_resample_renoise(void* x, const void* x0, const void* z, const
   const ResampleArgs p{x, x0, z, mask, coef, obs_coef, timesteps, num_steps, step, step_dev, back, visit, t_out, start, cover,
                        trial_id, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), N, W, T, F, ld, (int)D};
   const int grid = ib_grid_1d(N * F * ld / (v8 ? 8 : 1), 256);
-  return ib_dispatch_dtype_width<8>(dtype, v8, [&](auto tag, auto width) {
-    using TY = decltype(tag);
-    constexpr int V = decltype(width)::value;
-    auto go = [&](auto c, auto b) {
-      hipLaunchKernelGGL((resample_renoise_kernel<TY, V, decltype(c)::value, decltype(b)::value>), dim3(grid), dim3(256), 0,
-                         ib_s(stream), p);
-    };
-    if constexpr (V == 8) {                                            // BLK exists for the 8-wide kernels alone
-      if (cond && blk) go(std::true_type{}, std::true_type{});
-      else if (cond) go(std::true_type{}, std::false_type{});
-      else if (blk) go(std::false_type{}, std::true_type{});
-      else go(std::false_type{}, std::false_type{});
-    } else {
-      if (cond) go(std::true_type{}, std::false_type{});
-      else go(std::false_type{}, std::false_type{});
-    }
+  return stitch_dispatch<true>(dtype, v8, cond, blk, [&](auto tag, auto width, auto c, auto b) {
+    hipLaunchKernelGGL((resample_renoise_kernel<decltype(tag), decltype(width)::value, decltype(c)::value,
+                                                decltype(b)::value>), dim3(grid), dim3(256), 0, ib_s(stream), p);
   });
 }

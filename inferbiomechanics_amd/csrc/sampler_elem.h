@@ -1,8 +1,9 @@
-// Element helpers of the sampler updates for stitch.hip: COPIES of ldv / stv, ddim_mix and obs_pin1 of diffusion.hip.
-// Copies, not a shared header: diffusion.hip's kernels are pinned bit for bit, and moving their helpers or loops into
-// shared code has changed their instruction order before.  diffusion.hip does not include this file; whether the two fold
-// into one is a later question.  Whoever changes a form here changes it there (tests/test_stitch_kernels_gpu.py compares the
-// two bit for bit).
+// Element helpers of the sampler updates outside diffusion.hip -- the stitched family (stitch_step.h, included by stitch.hip,
+// sde.hip and resample.hip) and cfg.hip: COPIES of ldv / stv, ddim_mix and obs_pin1 of diffusion.hip.  Copies of THAT file
+// only: diffusion.hip's kernels are pinned bit for bit, and moving their helpers or loops into shared code has changed their
+// instruction order before, so it does not include this file; whether the two fold into one is a later question.  Whoever
+// changes a form here changes it there (tests/test_stitch_kernels_gpu.py compares the two bit for bit).  Among the files
+// that do include this one nothing is copied: what the stitched kernels share lives in stitch_step.h.
 // ONE helper here is NOT a copy of source: obs_pin8.  diffusion.hip's 8-wide masked kernels write the bare expression
 // ox * a + oz * b and leave its contraction to the compiler; obs_pin8 restates the code the compiler generates for it today.
 // A compiler that contracts that expression differently changes those kernels and not this file, and the one-window

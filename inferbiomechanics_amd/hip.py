@@ -2552,34 +2552,44 @@ def _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D):
 _stitch_checked = None   # (start, cover, key) of the last layout tables _stitch_operands accepted
 
 
+def _stitch_step(what, dpm, noise, x, eps, hist, x0, z, mask, coef, obs_coef, obs_noise_coef, timesteps, start, cover, wn,
+                 trial_ids, seed, step, step_dev, t_out, D):
+    """the checks and the call of the four stitched updates, entry point ib_<what>.  dpm: coef has the three history columns
+    and hist is an operand; noise: coef has the gain column and obs_noise_coef, trial_ids and seed are operands."""
+    if noise and (obs_noise_coef is None) != (obs_coef is None):
+        raise HipError(f"{what}: x0, z, mask, obs_coef and obs_noise_coef come together (the masked loop) or not at all")
+    N, W, T, F, D, ld = _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D)
+    if dpm:
+        _like_x(what, "hist", hist, x, torch.float32)
+    S = _step_tables(what, coef, (5 if dpm else 2) + (1 if noise else 0), timesteps, N * W, t_out, step_dev, obs_coef)
+    if noise:
+        if obs_noise_coef is not None:
+            _obs_noise_coef(what, obs_noise_coef, S)
+        _win_ids(what, trial_ids, N, "trial_ids", "N", x.device)
+    head = (x, eps) + ((hist,) if dpm else ()) + (x0, z, mask, coef, obs_coef) + ((obs_noise_coef,) if noise else ())
+    key = (_ptr(trial_ids), int(seed) & 0xFFFFFFFFFFFFFFFF) if noise else ()
+    _check(getattr(lib(), "ib_" + what)(*map(_ptr, head), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out),
+                                        _ptr(start), _ptr(cover), _ptr(wn), *key, N, W, T, F, D, ld, dtype_code(x.dtype),
+                                        stream_ptr()), "ib_" + what)
+    return x
+
+
 def stitch_ddim_step(x, eps, x0, z, mask, coef, obs_coef, timesteps, start, cover, wn, step=0, step_dev=None, t_out=None,
                      D=None):
     """DDIM update of a stitched trial in place (csrc/stitch.hip) over the window batch x [N, W, T, ld]: the noise predictions
     of the windows that cover a trial frame are blended with the weights wn, the element is updated once and every copy
     receives the result; start / cover / wn: schedule.stitch_layout on the device.  x0, z, mask [T, ld], obs_coef: all None,
     or the masked loop's operands as in ddim_cond_step.  t_out int64 [N * W]."""
-    what = "stitch_ddim_step"
-    N, W, T, F, D, ld = _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D)
-    S = _step_tables(what, coef, 2, timesteps, N * W, t_out, step_dev, obs_coef)
-    _check(lib().ib_stitch_ddim_step(_ptr(x), _ptr(eps), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef),
-                                     _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out), _ptr(start), _ptr(cover),
-                                     _ptr(wn), N, W, T, F, D, ld, dtype_code(x.dtype), stream_ptr()), "ib_stitch_ddim_step")
-    return x
+    return _stitch_step("stitch_ddim_step", False, False, x, eps, None, x0, z, mask, coef, obs_coef, None, timesteps, start,
+                        cover, wn, None, 0, step, step_dev, t_out, D)
 
 
 def stitch_dpmpp_step(x, eps, hist, x0, z, mask, coef, obs_coef, timesteps, start, cover, wn, step=0, step_dev=None,
                       t_out=None, D=None):
     """DPM-Solver++(2M) update of a stitched trial in place: as stitch_ddim_step with coef [S, 5] and the fp32 history hist
     [N, W, T, ld], read from an element's first copy and written to all of them (dpmpp_step's arithmetic)."""
-    what = "stitch_dpmpp_step"
-    N, W, T, F, D, ld = _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D)
-    _like_x(what, "hist", hist, x, torch.float32)
-    S = _step_tables(what, coef, 5, timesteps, N * W, t_out, step_dev, obs_coef)
-    _check(lib().ib_stitch_dpmpp_step(_ptr(x), _ptr(eps), _ptr(hist), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef),
-                                      _ptr(obs_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out), _ptr(start),
-                                      _ptr(cover), _ptr(wn), N, W, T, F, D, ld, dtype_code(x.dtype), stream_ptr()),
-           "ib_stitch_dpmpp_step")
-    return x
+    return _stitch_step("stitch_dpmpp_step", True, False, x, eps, hist, x0, z, mask, coef, obs_coef, None, timesteps, start,
+                        cover, wn, None, 0, step, step_dev, t_out, D)
 
 
 def stitch_ddim_step_noise(x, eps, x0, z, mask, coef, obs_coef, obs_noise_coef, timesteps, start, cover, wn, trial_ids, seed,
@@ -2589,20 +2599,8 @@ def stitch_ddim_step_noise(x, eps, x0, z, mask, coef, obs_coef, obs_noise_coef, 
     generated inside the kernel, so every copy of an element receives the same normal.  x0, z, mask, obs_coef and
     obs_noise_coef [S, 2]: all None, or the masked loop's operands as in ddim_cond_step_noise (z is updated in place at the
     observed elements, in every copy).  trial_ids: int64 [N] on the device."""
-    what = "stitch_ddim_step_noise"
-    if (obs_noise_coef is None) != (obs_coef is None):
-        raise HipError(f"{what}: x0, z, mask, obs_coef and obs_noise_coef come together (the masked loop) or not at all")
-    N, W, T, F, D, ld = _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D)
-    S = _step_tables(what, coef, 3, timesteps, N * W, t_out, step_dev, obs_coef)
-    if obs_noise_coef is not None:
-        _obs_noise_coef(what, obs_noise_coef, S)
-    _win_ids(what, trial_ids, N, "trial_ids", "N", x.device)
-    _check(lib().ib_stitch_ddim_step_noise(_ptr(x), _ptr(eps), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef),
-                                           _ptr(obs_noise_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out),
-                                           _ptr(start), _ptr(cover), _ptr(wn), _ptr(trial_ids),
-                                           int(seed) & 0xFFFFFFFFFFFFFFFF, N, W, T, F, D, ld, dtype_code(x.dtype),
-                                           stream_ptr()), "ib_stitch_ddim_step_noise")
-    return x
+    return _stitch_step("stitch_ddim_step_noise", False, True, x, eps, None, x0, z, mask, coef, obs_coef, obs_noise_coef,
+                        timesteps, start, cover, wn, trial_ids, seed, step, step_dev, t_out, D)
 
 
 def sde_dpmpp_step(x, eps, hist, x0, z, mask, coef, obs_coef, obs_noise_coef, timesteps, start, cover, wn, trial_ids, seed,
@@ -2613,20 +2611,8 @@ def sde_dpmpp_step(x, eps, hist, x0, z, mask, coef, obs_coef, obs_noise_coef, ti
     (schedule.sde_observation_noise_coefficients): all None, or the masked loop's operands (z is updated in place at the
     observed elements, in every copy).  trial_ids: int64 [N] on the device.  A per-window loop is the same call with W = 1,
     the layout stitch_layout(T, T, T) and window ids as trial ids."""
-    what = "sde_dpmpp_step"
-    if (obs_noise_coef is None) != (obs_coef is None):
-        raise HipError(f"{what}: x0, z, mask, obs_coef and obs_noise_coef come together (the masked loop) or not at all")
-    N, W, T, F, D, ld = _stitch_operands(what, x, eps, x0, z, mask, obs_coef, start, cover, wn, D)
-    _like_x(what, "hist", hist, x, torch.float32)
-    S = _step_tables(what, coef, 6, timesteps, N * W, t_out, step_dev, obs_coef)
-    if obs_noise_coef is not None:
-        _obs_noise_coef(what, obs_noise_coef, S)
-    _win_ids(what, trial_ids, N, "trial_ids", "N", x.device)
-    _check(lib().ib_sde_dpmpp_step(_ptr(x), _ptr(eps), _ptr(hist), _ptr(x0), _ptr(z), _ptr(mask), _ptr(coef), _ptr(obs_coef),
-                                   _ptr(obs_noise_coef), _ptr(timesteps), S, int(step), _ptr(step_dev), _ptr(t_out),
-                                   _ptr(start), _ptr(cover), _ptr(wn), _ptr(trial_ids), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                   N, W, T, F, D, ld, dtype_code(x.dtype), stream_ptr()), "ib_sde_dpmpp_step")
-    return x
+    return _stitch_step("sde_dpmpp_step", True, True, x, eps, hist, x0, z, mask, coef, obs_coef, obs_noise_coef, timesteps,
+                        start, cover, wn, trial_ids, seed, step, step_dev, t_out, D)
 
 
 def resample_renoise(x, x0, z, mask, coef, obs_coef, timesteps, start, cover, trial_ids, seed, back, visit, t_out, step=0,

@@ -77,3 +77,82 @@ def test_digest_default_sources_are_the_makefile_list():
     srcs = kr.makefile_sources()
     assert len(srcs) == len(set(srcs)) >= 21 and all(s.endswith(".hip") for s in srcs)
     assert {"gemm.hip", "gemm_nt.hip", "gemm_tn.hip", "ffn_chain.hip", "diffusion.hip"} <= set(srcs)
+
+
+# --digest --kernels: one digest per kernel.  KERNEL is one kernel as the compiler lays it out, {sym} its mangled name and
+# {n} its ordinal in the file; NOTE is the metadata note at the end of a listing, which names every kernel again
+KERNEL = """\
+\t.section\t.text.{sym},"axG",@progbits,{sym},comdat
+\t.globl\t{sym} ; -- Begin function {sym}
+\t.p2align\t8
+\t.type\t{sym},@function
+{sym}: ; @{sym}
+; %bb.0:
+\ts_load_dwordx2 s[2:3], s[0:1], 0x0
+\ts_cbranch_scc1 .LBB{n}_2
+\ts_waitcnt lgkmcnt(0)
+.LBB{n}_2:
+\ts_endpgm
+\t.section\t.rodata,"a",@progbits
+\t.p2align\t6, 0x0
+\t.amdhsa_kernel {sym}
+\t\t.amdhsa_next_free_vgpr 52
+\t\t.amdhsa_kernarg_size 192
+\t.end_amdhsa_kernel
+\t.section\t.text.{sym},"axG",@progbits,{sym},comdat
+.Lfunc_end{n}:
+\t.size\t{sym}, .Lfunc_end{n}-{sym}
+\t.set {sym}.num_vgpr, 52
+\t.set {sym}.private_seg_size, 0
+\t.section\t.AMDGPU.csdata,"",@progbits
+; Kernel info:
+"""
+NOTE = """\
+\t.amdgpu_metadata
+---
+amdhsa.kernels:
+  - .name:           {a}
+    .symbol:         {a}.kd
+  - .name:           {b}
+    .symbol:         {b}.kd
+...
+\t.end_amdgpu_metadata
+"""
+STEP = "_ZN12_GLOBAL__N_118stitch_step_kernelIfLi8ELb1ELi{mode}ELb0EEEvNS_10StitchArgsE"
+SDE = "_ZN12_GLOBAL__N_115sde_step_kernelIfLi8ELb1ELb0EEEvNS_7SdeArgsE"
+
+
+def _kernels(first, second, edit=lambda text: text):
+    text = KERNEL.format(sym=first, n=0) + edit(KERNEL.format(sym=second, n=1)) + NOTE.format(a=first, b=second)
+    return kr.kernel_digests(kr.normalise_asm(text))
+
+
+def test_kernel_digests_follow_the_kernel_not_its_name_or_place():
+    base = _kernels(STEP.format(mode=1), STEP.format(mode=2))
+    assert [k for k, _ in base] == ["stitch_step_kernel<float,8,1,1,0>", "stitch_step_kernel<float,8,1,2,0>"]
+    assert base[0][1] == base[1][1] and len(base[0][1]) == 64          # the same text under two names and two ordinals
+    # renamed (another template, another argument list in the mangled name) and moved to the other place in the file
+    moved = _kernels(SDE, STEP.format(mode=1))
+    assert [k for k, _ in moved] == ["sde_step_kernel<float,8,1,0>", "stitch_step_kernel<float,8,1,1,0>"]
+    assert {d for _, d in moved} == {base[0][1]}
+    # a symbol that another kernel's name begins with is not taken for that kernel
+    assert {d for _, d in _kernels(STEP.format(mode=1), STEP.format(mode=1) + "x")} == {base[0][1]}
+
+
+def test_kernel_digests_see_instructions_descriptor_registers_and_order():
+    base = _kernels(STEP.format(mode=1), STEP.format(mode=2))
+    swap = ("\ts_load_dwordx2 s[2:3], s[0:1], 0x0\n\ts_cbranch_scc1 .LBB1_2\n",
+            "\ts_cbranch_scc1 .LBB1_2\n\ts_load_dwordx2 s[2:3], s[0:1], 0x0\n")
+    for old, new in (("lgkmcnt(0)", "lgkmcnt(1)"),                     # an instruction
+                     ("kernarg_size 192", "kernarg_size 200"),         # a descriptor field
+                     (".num_vgpr, 52", ".num_vgpr, 64"),               # a resource .set line
+                     ("s_cbranch_scc1 .LBB1_2", "s_cbranch_scc1 .LBB1_3"),   # a branch target
+                     swap):                                            # instruction order
+        got = _kernels(STEP.format(mode=1), STEP.format(mode=2), lambda t: t.replace(old, new))
+        assert old in KERNEL.format(sym="s", n=1) and got[0] == base[0] and got[1][0] == base[1][0], old
+        assert got[1][1] != base[1][1], old
+    # the file-level listing of the other tests: one kernel, no resource lines, no local labels
+    (name, digest), = kr.kernel_digests(kr.normalise_asm(LISTING))
+    assert name == "gemm_tn_kernel<1>"
+    (_, other), = kr.kernel_digests(kr.normalise_asm(LISTING.replace("lgkmcnt(0)", "lgkmcnt(1)")))
+    assert other != digest

@@ -469,14 +469,29 @@ def test_kernel_resources_no_scratch_no_spill():
     if kr.hipcc() is None:
         pytest.skip("hipcc not installed")
     rows = kr.resources("sde.hip")
-    kernels = [r for r in rows if "sde_step_kernel" in r["kernel"]]
-    # fp32 / bf16 x {8-wide: cond x whole blocks, element-wise: cond}
+    kernels = [r for r in rows if "stitch_step_kernel" in r["kernel"]]
+    # stitch_step.h's template with MODE 3: fp32 / bf16 x {8-wide: cond x whole blocks, element-wise: cond}
     assert len(kernels) == 12 == len(rows), [r["kernel"] for r in rows]
-    forms = sorted(re.search(r"I(f|DF16b)Li([18])ELb([01])ELb([01])E", r["mangled"]).groups() for r in kernels)
+    forms = sorted(re.search(r"I(f|DF16b)Li([18])ELb([01])ELi3ELb([01])E", r["mangled"]).groups() for r in kernels)
     assert forms == sorted((ty, v, c, b) for ty in ("f", "DF16b") for v, c, b in
                            (("8", "0", "0"), ("8", "0", "1"), ("8", "1", "0"), ("8", "1", "1"), ("1", "0", "0"), ("1", "1", "0")))
     for r in rows:
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0, r
+
+
+def test_the_stitched_family_copies_nothing():
+    """one definition of the draw and of the kernel under csrc/: sde.hip and resample.hip include stitch_step.h"""
+    import glob
+
+    from inferbiomechanics_amd import hip
+    texts = {os.path.basename(f): open(f).read() for f in glob.glob(os.path.join(os.path.dirname(hip.__file__), "csrc", "*"))
+             if os.path.isfile(f) and f.endswith((".hip", ".h"))}
+    defines = lambda name: sorted(f for f, t in texts.items() if name + "(" in t)     # a use names its template arguments
+    assert defines("trial_noise") == ["stitch_step.h"] and defines("stitch_step_kernel") == ["stitch_step.h"]
+    assert not defines("jump_noise") and not defines("sde_step_kernel")
+    assert not [f for f, t in texts.items() if "jump_noise" in t or "sde_step_kernel" in t]
+    for f in ("stitch.hip", "sde.hip", "resample.hip"):
+        assert '#include "stitch_step.h"' in texts[f]
 
 
 def test_makefile_builds_the_new_source_with_the_new_header():

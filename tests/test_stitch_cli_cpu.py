@@ -24,8 +24,11 @@ def test_kmax_has_one_value():
     defined = re.findall(r"#define\s+IB_STITCH_KMAX\s+(\d+)", text)
     assert defined == [str(hip.STITCH_KMAX)] and hip.STITCH_KMAX == schedule.STITCH_KMAX == 8
     assert schedule.stitch_layout(16, 8, 4)[3] == hip.STITCH_KMAX
-    src = open(os.path.join(os.path.dirname(hip.__file__), "csrc", "stitch.hip")).read()
-    assert "KMAX = IB_STITCH_KMAX" in src                              # the kernels take the header's value
+    csrc = os.path.join(os.path.dirname(hip.__file__), "csrc")
+    assert "KMAX = IB_STITCH_KMAX" in open(os.path.join(csrc, "stitch_step.h")).read()   # the kernels take the header's value
+    for f in ("stitch.hip", "sde.hip", "resample.hip"):               # ... and no source of the family one of its own
+        text = open(os.path.join(csrc, f)).read()
+        assert '#include "stitch_step.h"' in text and not re.search(r"\bKMAX\s*=", text), f
 
 
 def test_visualize_trial_flags_parse():

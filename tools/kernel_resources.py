@@ -5,7 +5,9 @@ Usage: python tools/kernel_resources.py [--filter SUBSTR] [--json] [file.hip ...
        python tools/kernel_resources.py --digest [-D IB_AB] [file.hip ...]            (default: every source of the Makefile)
 --digest prints, per source, the sha256 of its normalised device assembly (normalise_asm): a refactor that only moves
 text leaves every line as it was; run it on both checkouts, once per build flavour, and diff the two outputs.  A source
-given by absolute path is compiled where it lies, so one checkout's tool can digest another checkout's csrc/."""
+given by absolute path is compiled where it lies, so one checkout's tool can digest another checkout's csrc/.
+--digest --kernels prints one line per kernel instead (kernel_digests): its short name and the sha256 of its own text, so a
+kernel that was renamed or moved to another place in its file, and is otherwise the same, keeps its line."""
 import argparse
 import hashlib
 import json
@@ -109,6 +111,27 @@ def device_asm(src, extra=()):
             return normalise_asm(f.read())
 
 
+def kernel_digests(asm):
+    """[(short name, sha256)] of the kernels of a normalised listing, in the listing's order.  A kernel's text is every line
+    from the first to the last that names its symbol outside the metadata note -- its section, label and code, its
+    .amdhsa_kernel descriptor and its resource .set lines -- with its own symbol replaced by "<kernel>", any other kernel's
+    by that kernel's short name, and the kernel's ordinal in the file taken out of its local labels (.LBB<n>_,
+    .Lfunc_end<n>): what remains is the instructions, the descriptor and the register counts"""
+    lines = asm.split(".amdgpu_metadata")[0].splitlines()
+    syms = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", asm, re.M)
+    names = re.compile("|".join(rf"(?<![\w$]){re.escape(s)}(?![\w$])" for s in sorted(syms, key=len, reverse=True)) or "$^")
+    out = []
+    for sym in syms:
+        at = [i for i, l in enumerate(lines) if any(m.group() == sym for m in names.finditer(l))]
+        text = "\n".join(lines[at[0]:at[-1] + 1]) + "\n"
+        n = re.search(r"^\.Lfunc_end(\d+):", text, re.M)
+        if n:
+            text = re.sub(rf"(\.L[A-Za-z_]+){n.group(1)}(?!\d)", r"\1", text)
+        text = names.sub(lambda m: "<kernel>" if m.group() == sym else short_name(m.group()), text)
+        out.append((short_name(sym), hashlib.sha256(text.encode()).hexdigest()))
+    return out
+
+
 def makefile_sources():
     with open(os.path.join(CSRC, "Makefile")) as f:
         return re.search(r"^SRCS\s*=\s*(.+)$", f.read(), re.M).group(1).split()
@@ -120,6 +143,7 @@ def main():
     ap.add_argument("--filter", default="", help="only kernels whose short name contains this")
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--digest", action="store_true", help="sha256 of each source's normalised device assembly")
+    ap.add_argument("--kernels", action="store_true", help="with --digest: one line per kernel, under its short name")
     ap.add_argument("-D", action="append", default=[], help="extra -D definitions (e.g. -D IB_AB)")
     a = ap.parse_args()
     extra = [f"-D{d}" for d in a.D]
@@ -127,7 +151,11 @@ def main():
         srcs = a.sources or makefile_sources()
         with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
             for s, asm in zip(srcs, ex.map(lambda s: device_asm(s, extra), srcs)):
-                print(f"{os.path.basename(s):22s} {hashlib.sha256(asm.encode()).hexdigest()}")
+                if a.kernels:
+                    for k, d in kernel_digests(asm):
+                        print(f"{os.path.basename(s):14s} {k:40s} {d}")
+                else:
+                    print(f"{os.path.basename(s):22s} {hashlib.sha256(asm.encode()).hexdigest()}")
         return 0
     a.sources = a.sources or ["ffn_chain.hip", "ffn_chain_bwd.hip"]
     with ThreadPoolExecutor(max_workers=min(4, len(a.sources))) as ex:
