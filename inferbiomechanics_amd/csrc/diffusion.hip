@@ -8,6 +8,7 @@
 #include "head_jobs.h"
 #include "launch.h"
 #include "philox.h"
+#include "sampler_elem.h"
 
 namespace {
 
@@ -20,33 +21,6 @@ __global__ void gather_rows_kernel(const float* __restrict__ table, const int64_
     int64_t r = idx[b];
     r = r < 0 ? 0 : (r >= table_rows ? table_rows - 1 : r);
     out[i] = ib_from_f32<T>(table[r * dim + d]);
-  }
-}
-
-// 8 elements per thread (16-byte bf16 / 2 x 16-byte fp32 accesses) when `per` is a multiple of 8
-template <typename T, int V>
-__device__ __forceinline__ void ldv(const T* p, float (&v)[V]) {
-  if constexpr (V == 1) { v[0] = ib_to_f32(p[0]); }
-  else if constexpr (sizeof(T) == 2) {
-    bf16x8_t t = *reinterpret_cast<const bf16x8_t*>(p);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
-  } else {
-    float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-}
-template <typename T, int V>
-__device__ __forceinline__ void stv(T* p, const float (&v)[V]) {
-  if constexpr (V == 1) { p[0] = ib_from_f32<T>(v[0]); }
-  else if constexpr (sizeof(T) == 2) {
-    bf16x8_t o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (bf16_t)v[e];
-    *reinterpret_cast<bf16x8_t*>(p) = o;
-  } else {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
   }
 }
 
@@ -106,25 +80,52 @@ __global__ void q_sample_cond_kernel(const T* __restrict__ x0, const T* __restri
   }
 }
 
-// One element k of the DDIM update x' = cx * x + ce * eps of a vector of V, with its fp32 roundings spelled out.
-// ddim_step_kernel and the free elements of ddim_cond_step_kernel both go through it, so the masked update is bit-identical
-// to the unmasked one however the compiler would contract the bare expression in either kernel.  The forms are those that
-// expression compiled to for gfx950: one lone element sums two rounded products; fp32 x 8 fuses cx * x into the rounded
-// ce * eps; bf16 x 8 alternates which of the two products is rounded first (the pairing of the packed fp32 operations).
+// ---- the sampler updates.  Every floating-point result below is spelled with its roundings (ddim_mix, obs_pin1 / obs_pin8
+// of sampler_elem.h, __builtin_fmaf) under `fp contract(off)`, so no result depends on how the compiler would contract an
+// expression in one instantiation or another, and the loops can be shared, moved and inlined freely.
+
+// the step row of a launch: *step_dev (a device counter: a replayed graph serves every step) or `step`, clamped to the table
+__device__ __forceinline__ int step_row(int step, const int32_t* step_dev, int64_t num_steps) {
+  const int s = step_dev ? *step_dev : step;
+  return s < 0 ? 0 : (s >= num_steps ? (int)num_steps - 1 : s);
+}
+
+// block 0 hands the next step's timestep to the B windows of the batch (0 after the last step)
+__device__ __forceinline__ void put_next_timestep(int64_t* __restrict__ t_out, const int64_t* __restrict__ timesteps,
+                                                  int64_t num_steps, int s, int64_t B) {
+  if (t_out && blockIdx.x == 0) {
+    const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
+    for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
+  }
+}
+
+// bit k: element k of the V from offset m0 of the window's mask [T, ld] is observed.  V = 8 reads the 8 bytes at once
+template <int V>
+__device__ __forceinline__ unsigned mask_bits(const uint8_t* __restrict__ mask, int64_t m0) {
+  if constexpr (V == 1) {
+    return mask[m0] != 0;
+  } else {
+    const uint64_t mv = *reinterpret_cast<const uint64_t*>(mask + m0);
+    unsigned bits = 0;
+#pragma unroll
+    for (int k = 0; k < V; ++k) bits |= (((mv >> (8 * k)) & 0xff) != 0 ? 1u : 0u) << k;
+    return bits;
+  }
+}
+
+// ddim_mix of element k of the V from flat offset e0.  mix8: ib_ddim_step would take its 8-wide kernel on these buffers, so
+// an element-wise kernel (a window of T * ld % 8 != 0, an operand off 16-byte alignment) rounds as that one does at e0 & 7
 template <typename T, int V>
-__device__ __forceinline__ float ddim_mix(int k, float cx, float a, float ce, float e) {
-#pragma clang fp contract(off)
-  if constexpr (V == 1) return cx * a + ce * e;
-  else if constexpr (sizeof(T) == 4) return __builtin_fmaf(cx, a, ce * e);
-  else return (k & 1) ? __builtin_fmaf(cx, a, ce * e) : __builtin_fmaf(ce, e, cx * a);
+__device__ __forceinline__ float mix_at(int k, int64_t e0, int mix8, float cx, float a, float ce, float e) {
+  return (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a, ce, e) : ddim_mix<T, V>(k, cx, a, ce, e);
 }
 
 template <typename T, int V>
 __global__ void ddim_step_kernel(T* __restrict__ x, const T* __restrict__ eps, const float* __restrict__ coef,
                                  const int64_t* __restrict__ timesteps, int64_t num_steps, int step,
                                  const int32_t* __restrict__ step_dev, int64_t* __restrict__ t_out, int64_t B, int64_t n) {
-  int s = step_dev ? *step_dev : step;
-  s = s < 0 ? 0 : (s >= num_steps ? (int)num_steps - 1 : s);
+#pragma clang fp contract(off)
+  const int s = step_row(step, step_dev, num_steps);
   const float cx = coef[2 * s], ce = coef[2 * s + 1];
   const int64_t nv = n / V;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
@@ -135,50 +136,36 @@ __global__ void ddim_step_kernel(T* __restrict__ x, const T* __restrict__ eps, c
     for (int k = 0; k < V; ++k) o[k] = ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
     stv<T, V>(x + i * V, o);
   }
-  if (t_out && blockIdx.x == 0) {
-    const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
-    for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
-  }
+  put_next_timestep(t_out, timesteps, num_steps, s, B);
 }
 
-// masked (inpainting) DDIM update over the sampler state x [B, T, ld] with one mask [T, ld] for the whole batch: a free
-// element (mask 0) takes the update of ddim_step_kernel (ddim_mix: the same fp32 roundings), an observed one
-// the forward-noised observation at the next noise level, obs_coef[s+1] = (sqrt ab_prev(s), sqrt(1 - ab_prev(s))) times
-// (x0, z) -- (1, 0) after the last step, so the loop ends on x0 itself.  INIT: the start state, observed elements <-
-// obs_coef[0] (x0, z), free ones keep the drawn noise.  V = 8 reads the mask 8 bytes at a time and loads only what the
-// vector needs: x / eps when one of its elements is free, x0 / z when one is observed.  mix8: ib_ddim_step would take its
-// 8-wide kernel on these buffers, so the element-wise kernel (a window of T * ld % 8 != 0) rounds as that one does.
-template <typename T, int V, bool INIT>
-__global__ void ddim_cond_step_kernel(T* __restrict__ x, const T* __restrict__ eps, const T* __restrict__ x0,
-                                      const T* __restrict__ z, const uint8_t* __restrict__ mask,
-                                      const float* __restrict__ coef, const float* __restrict__ obs_coef,
-                                      const int64_t* __restrict__ timesteps, int64_t num_steps, int step,
-                                      const int32_t* __restrict__ step_dev, int64_t* __restrict__ t_out, int64_t B,
-                                      int64_t per, int64_t n, int mix8) {
-  int s = 0;
-  float cx = 0.f, ce = 0.f, ox, oz;
-  if constexpr (INIT) {
-    ox = obs_coef[0]; oz = obs_coef[1];
-  } else {
-    s = step_dev ? *step_dev : step;
-    s = s < 0 ? 0 : (s >= num_steps ? (int)num_steps - 1 : s);
-    cx = coef[2 * s]; ce = coef[2 * s + 1];
-    ox = obs_coef[2 * (s + 1)]; oz = obs_coef[2 * (s + 1) + 1];
-  }
+// ---- the masked (inpainting) updates over the sampler state x [B, T, ld] with one mask [T, ld] for the whole batch.  A free
+// element (mask 0) takes the unmasked update (ddim_mix: the same fp32 roundings); an observed one the forward-noised
+// observation at the next noise level, obs_coef[s + 1] = (sqrt ab_prev(s), sqrt(1 - ab_prev(s))) times (x0, z) -- (1, 0)
+// after the last step, so the loop ends on x0 itself -- pinned by position in a vector of 8 (obs_pin8) or alone (obs_pin1).
+// V = 8 loads only what the vector needs: x / eps when one of its elements is free, x0 / z when one is observed.
+// The coefficients of one launch: the update's row (cx, ce; DPM: ch, hx, he) and the observation's (ox, oz).
+struct MaskedCoef { float cx, ce, ch, hx, he, ox, oz; };
+
+// THE masked loop of the deterministic updates: ddim_cond_step_kernel, the sigma == 0 rows of ddim_cond_step_noise_kernel and
+// dpmpp_cond_step_kernel all run it.  INIT: the start state, observed elements <- obs_coef[0] (x0, z), free ones keep the
+// drawn noise (eps is not read).  DPM: the vectors that have a free element add the history as dpmpp_step_kernel does;
+// SECOND: the row has C != 0 and reads hist.  What hist holds at an observed element is unspecified (a vector of observed
+// elements only is not touched; in a mixed vector it gets the expression of the free ones) and no step reads it there.
+// i0, stride: the thread's first vector and the grid's step, formed in the kernel (as q_sample_body takes them): blockDim.x
+// read inside a device function compiles to a vector load in the prologue, 0.3 us per launch of the start-state kernel.
+template <typename T, int V, bool INIT, bool DPM, bool SECOND>
+__device__ __forceinline__ void masked_update(T* __restrict__ x, const T* __restrict__ eps, float* hist,
+                                              const T* __restrict__ x0, const T* __restrict__ z,
+                                              const uint8_t* __restrict__ mask, const MaskedCoef c, int64_t per, int64_t n,
+                                              int mix8, int64_t i0, int64_t stride) {
+#pragma clang fp contract(off)
   constexpr unsigned ALL = (1u << V) - 1;
   const int64_t nv = n / V;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t e0 = i * V, m0 = e0 % per;          // per % V == 0: a vector never straddles two windows
-    unsigned bits;
-    if constexpr (V == 1) {
-      bits = mask[m0] != 0;
-    } else {
-      const uint64_t mv = *reinterpret_cast<const uint64_t*>(mask + m0);
-      bits = 0;
-#pragma unroll
-      for (int k = 0; k < V; ++k) bits |= (((mv >> (8 * k)) & 0xff) != 0 ? 1u : 0u) << k;
-    }
-    if (INIT && bits == 0) continue;                  // all free: the drawn noise stays
+  for (int64_t i = i0; i < nv; i += stride) {
+    const int64_t e0 = i * V;
+    const unsigned bits = mask_bits<V>(mask, e0 % per);     // per % V == 0: a vector never straddles two windows
+    if (INIT && bits == 0) continue;                        // all free: the drawn noise stays
     float o[V];
     if (bits != ALL) {
       float a[V];
@@ -190,23 +177,51 @@ __global__ void ddim_cond_step_kernel(T* __restrict__ x, const T* __restrict__ e
         float e[V];
         ldv<T, V>(eps + e0, e);
 #pragma unroll
-        for (int k = 0; k < V; ++k)
-          o[k] = (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a[k], ce, e[k]) : ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
+        for (int k = 0; k < V; ++k) o[k] = mix_at<T, V>(k, e0, mix8, c.cx, a[k], c.ce, e[k]);
+        if constexpr (DPM) {
+          float h[V];
+          if constexpr (SECOND) {
+            ldv<float, V>(hist + e0, h);
+#pragma unroll
+            for (int k = 0; k < V; ++k) o[k] = __builtin_fmaf(c.ch, h[k], o[k]);
+          }
+#pragma unroll
+          for (int k = 0; k < V; ++k) h[k] = __builtin_fmaf(c.hx, a[k], c.he * e[k]);
+          stv<float, V>(hist + e0, h);
+        }
       }
     }
     if (bits != 0) {
       float a[V], b[V];
       ldv<T, V>(x0 + e0, a);
       ldv<T, V>(z + e0, b);
+      __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);    // both loads are issued before the first conversion waits for
+      __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);    // one (obs_pin8's product of x0 alone at k == 1 drew it forward)
 #pragma unroll
       for (int k = 0; k < V; ++k)
-        if ((bits >> k) & 1u) o[k] = ox * a[k] + oz * b[k];
+        if ((bits >> k) & 1u) o[k] = V == 1 ? obs_pin1(c.ox, a[k], c.oz, b[k]) : obs_pin8(k, c.ox, a[k], c.oz, b[k]);
     }
     stv<T, V>(x + e0, o);
   }
-  if (!INIT && t_out && blockIdx.x == 0) {
-    const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
-    for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
+}
+
+template <typename T, int V, bool INIT>
+__global__ void ddim_cond_step_kernel(T* __restrict__ x, const T* __restrict__ eps, const T* __restrict__ x0,
+                                      const T* __restrict__ z, const uint8_t* __restrict__ mask,
+                                      const float* __restrict__ coef, const float* __restrict__ obs_coef,
+                                      const int64_t* __restrict__ timesteps, int64_t num_steps, int step,
+                                      const int32_t* __restrict__ step_dev, int64_t* __restrict__ t_out, int64_t B,
+                                      int64_t per, int64_t n, int mix8) {
+  if constexpr (INIT) {
+    masked_update<T, V, true, false, false>(x, eps, nullptr, x0, z, mask, {0.f, 0.f, 0.f, 0.f, 0.f, obs_coef[0], obs_coef[1]},
+                                            per, n, mix8, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                                            (int64_t)gridDim.x * blockDim.x);
+  } else {
+    const int s = step_row(step, step_dev, num_steps);
+    masked_update<T, V, false, false, false>(x, eps, nullptr, x0, z, mask, {coef[2 * s], coef[2 * s + 1], 0.f, 0.f, 0.f,
+                                             obs_coef[2 * (s + 1)], obs_coef[2 * (s + 1) + 1]}, per, n, mix8,
+                                             (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    put_next_timestep(t_out, timesteps, num_steps, s, B);
   }
 }
 
@@ -222,15 +237,19 @@ struct StepNoise {
   int32_t D, ld, per;               // logical columns, row pitch, T * ld
 };
 
-// the normals of the 8 elements from offset m0 (a multiple of 8) of a window's [T, ld] state; bit k of the result: element
-// k is a logical column.  BLK (D % 4 == 0 and rows that start on a multiple of 8, or no pitch): the vector is two whole
-// Philox blocks, each made once or -- in the pad columns -- not at all.  Otherwise an element looks its block up, and
-// neighbours that share a block share the call.
-template <bool BLK>
-__device__ __forceinline__ unsigned step_noise8(const StepNoise& nz, uint32_t s, uint32_t wid, int m0, float (&z)[8]) {
+// the normals of the V elements from flat offset e0 (a multiple of V) of the state [B, T, ld]; bit k of the result: element
+// k is a logical column (a pad column gets 0).  V = 8, BLK (D % 4 == 0 and rows that start on a multiple of 8, or no pitch):
+// the vector is two whole Philox blocks, each made once or -- in the pad columns -- not at all.  Otherwise an element looks
+// its block up, and neighbours that share a block share the call.  (trial_noise of stitch_step.h is the same draw given
+// (row, column); the unpitched 8-wide launch here has a vector straddle two rows and no division to find them with.)
+template <int V, bool BLK>
+__device__ __forceinline__ unsigned step_noise(const StepNoise& nz, uint32_t s, int64_t e0, float (&z)[V]) {
+  const int64_t b = e0 / nz.per;
+  const int m0 = (int)(e0 - b * nz.per);
+  const uint32_t wid = (uint32_t)nz.win_id[b];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) z[k] = 0.f;
-  if constexpr (BLK) {
+  for (int k = 0; k < V; ++k) z[k] = 0.f;
+  if constexpr (V == 8 && BLK) {
     int l = m0;
     unsigned ok = 0xffu;
     if (nz.ld != nz.D) {
@@ -253,7 +272,7 @@ __device__ __forceinline__ unsigned step_noise8(const StepNoise& nz, uint32_t s,
     uint32_t cur = 0xffffffffu;                  // no block has this index: T * D / 4 < 2^29
     U4 w{};
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < V; ++k) {
       const int mm = m0 + k, f = mm / nz.ld, c = mm - f * nz.ld;
       if (c < nz.D) {
         const int l = f * nz.D + c;
@@ -269,33 +288,7 @@ __device__ __forceinline__ unsigned step_noise8(const StepNoise& nz, uint32_t s,
   }
 }
 
-// one element at offset m of a window's state: its normal, or 0 in a pad column (ok = false)
-__device__ __forceinline__ float step_noise1(const StepNoise& nz, uint32_t s, uint32_t wid, int m, bool& ok) {
-  const int f = m / nz.ld, c = m - f * nz.ld;
-  ok = c < nz.D;
-  if (!ok) return 0.f;
-  const int l = f * nz.D + c;
-  const U4 w = philox4x32_10(U4{(uint32_t)l >> 2, s, wid, kDomainStep}, nz.k0, nz.k1);
-  float za, zb;
-  if ((l & 2) == 0) box_muller(w.x, w.y, za, zb); else box_muller(w.z, w.w, za, zb);
-  return (l & 1) ? zb : za;
-}
-
-template <int V, bool BLK>
-__device__ __forceinline__ unsigned step_noise(const StepNoise& nz, uint32_t s, int64_t e0, float (&z)[V]) {
-  const int64_t b = e0 / nz.per;
-  const int m0 = (int)(e0 - b * nz.per);
-  const uint32_t wid = (uint32_t)nz.win_id[b];
-  if constexpr (V == 8) return step_noise8<BLK>(nz, s, wid, m0, z);
-  else {
-    bool ok;
-    z[0] = step_noise1(nz, s, wid, m0, ok);
-    return ok ? 1u : 0u;
-  }
-}
-
-// mix8: ib_ddim_step would take its 8-wide kernel on these buffers, so the element-wise kernel rounds as that one does
-// (as ddim_cond_step_kernel does).  The noise term is one more fused multiply-add on the ddim_mix value, in every kernel.
+// The noise term is one more fused multiply-add on the ddim_mix value, in every kernel.
 template <typename T, int V, bool BLK>
 __global__ __launch_bounds__(256) void ddim_step_noise_kernel(T* __restrict__ x, const T* __restrict__ eps,
                                                               const float* __restrict__ coef,
@@ -303,8 +296,8 @@ __global__ __launch_bounds__(256) void ddim_step_noise_kernel(T* __restrict__ x,
                                                               int step, const int32_t* __restrict__ step_dev,
                                                               int64_t* __restrict__ t_out, int64_t B, int64_t n, int mix8,
                                                               StepNoise nz) {
-  int s = step_dev ? *step_dev : step;
-  s = s < 0 ? 0 : (s >= num_steps ? (int)num_steps - 1 : s);
+#pragma clang fp contract(off)
+  const int s = step_row(step, step_dev, num_steps);
   const float cx = coef[3 * s], ce = coef[3 * s + 1], sg = coef[3 * s + 2];
   const bool noisy = sg != 0.f;                                        // uniform over the launch
   const int64_t nv = n / V;
@@ -314,8 +307,7 @@ __global__ __launch_bounds__(256) void ddim_step_noise_kernel(T* __restrict__ x,
     ldv<T, V>(x + e0, a);
     ldv<T, V>(eps + e0, e);
 #pragma unroll
-    for (int k = 0; k < V; ++k)
-      o[k] = (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a[k], ce, e[k]) : ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
+    for (int k = 0; k < V; ++k) o[k] = mix_at<T, V>(k, e0, mix8, cx, a[k], ce, e[k]);
     if (noisy) {
       float z[V];
       const unsigned ok = step_noise<V, BLK>(nz, (uint32_t)s, e0, z);
@@ -325,52 +317,7 @@ __global__ __launch_bounds__(256) void ddim_step_noise_kernel(T* __restrict__ x,
     }
     stv<T, V>(x + e0, o);
   }
-  if (t_out && blockIdx.x == 0) {
-    const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
-    for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
-  }
-}
-
-// the loop of ddim_cond_step_kernel<T, V, false>, statement for statement: a step whose sigma is 0 runs it, so that the
-// observed elements' unpinned expression compiles as it does there.  (A copy, not a shared function: moving that kernel's
-// loop into a function reordered its instructions, and its results must not depend on this file's other kernels.)
-template <typename T, int V>
-__device__ __forceinline__ void ddim_cond_update(T* __restrict__ x, const T* __restrict__ eps, const T* __restrict__ x0,
-                                                 const T* __restrict__ z, const uint8_t* __restrict__ mask, float cx, float ce,
-                                                 float ox, float oz, int64_t per, int64_t n, int mix8) {
-  constexpr unsigned ALL = (1u << V) - 1;
-  const int64_t nv = n / V;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t e0 = i * V, m0 = e0 % per;
-    unsigned bits;
-    if constexpr (V == 1) {
-      bits = mask[m0] != 0;
-    } else {
-      const uint64_t mv = *reinterpret_cast<const uint64_t*>(mask + m0);
-      bits = 0;
-#pragma unroll
-      for (int k = 0; k < V; ++k) bits |= (((mv >> (8 * k)) & 0xff) != 0 ? 1u : 0u) << k;
-    }
-    float o[V];
-    if (bits != ALL) {
-      float a[V];
-      ldv<T, V>(x + e0, a);
-      float e[V];
-      ldv<T, V>(eps + e0, e);
-#pragma unroll
-      for (int k = 0; k < V; ++k)
-        o[k] = (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a[k], ce, e[k]) : ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
-    }
-    if (bits != 0) {
-      float a[V], b[V];
-      ldv<T, V>(x0 + e0, a);
-      ldv<T, V>(z + e0, b);
-#pragma unroll
-      for (int k = 0; k < V; ++k)
-        if ((bits >> k) & 1u) o[k] = ox * a[k] + oz * b[k];
-    }
-    stv<T, V>(x + e0, o);
-  }
+  put_next_timestep(t_out, timesteps, num_steps, s, B);
 }
 
 // masked stochastic update.  Free elements: ddim_mix + sigma z'.  Observed elements follow the DDIM posterior given the
@@ -388,27 +335,20 @@ __global__ __launch_bounds__(256) void ddim_cond_step_noise_kernel(T* __restrict
                                                                    int step, const int32_t* __restrict__ step_dev,
                                                                    int64_t* __restrict__ t_out, int64_t B, int64_t per,
                                                                    int64_t n, int mix8, StepNoise nz) {
-  int s = step_dev ? *step_dev : step;
-  s = s < 0 ? 0 : (s >= num_steps ? (int)num_steps - 1 : s);
+#pragma clang fp contract(off)
+  const int s = step_row(step, step_dev, num_steps);
   const float cx = coef[3 * s], ce = coef[3 * s + 1], sg = coef[3 * s + 2];
   const float ox = obs_coef[2 * (s + 1)], oz = obs_coef[2 * (s + 1) + 1];
-  if (sg == 0.f) {                                                     // uniform over the launch
-    ddim_cond_update<T, V>(x, eps, x0, z, mask, cx, ce, ox, oz, per, n, mix8);
+  if (sg == 0.f) {                                                     // uniform over the launch: ib_ddim_cond_step's loop
+    masked_update<T, V, false, false, false>(x, eps, nullptr, x0, z, mask, {cx, ce, 0.f, 0.f, 0.f, ox, oz}, per, n, mix8,
+                                             (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
   } else {
     const float r = obs_noise[2 * s], q = obs_noise[2 * s + 1];
     constexpr unsigned ALL = (1u << V) - 1;
     const int64_t nv = n / V;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
-      const int64_t e0 = i * V, m0 = e0 % per;
-      unsigned bits;
-      if constexpr (V == 1) {
-        bits = mask[m0] != 0;
-      } else {
-        const uint64_t mv = *reinterpret_cast<const uint64_t*>(mask + m0);
-        bits = 0;
-#pragma unroll
-        for (int k = 0; k < V; ++k) bits |= (((mv >> (8 * k)) & 0xff) != 0 ? 1u : 0u) << k;
-      }
+      const int64_t e0 = i * V;
+      const unsigned bits = mask_bits<V>(mask, e0 % per);
       float zn[V], o[V];
       const unsigned ok = step_noise<V, BLK>(nz, (uint32_t)s, e0, zn);
       if (bits != ALL) {
@@ -417,7 +357,7 @@ __global__ __launch_bounds__(256) void ddim_cond_step_noise_kernel(T* __restrict
         ldv<T, V>(eps + e0, e);
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-          o[k] = (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a[k], ce, e[k]) : ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
+          o[k] = mix_at<T, V>(k, e0, mix8, cx, a[k], ce, e[k]);
           if ((ok >> k) & 1u) o[k] = __builtin_fmaf(sg, zn[k], o[k]);
         }
       }
@@ -436,10 +376,7 @@ __global__ __launch_bounds__(256) void ddim_cond_step_noise_kernel(T* __restrict
       stv<T, V>(x + e0, o);
     }
   }
-  if (t_out && blockIdx.x == 0) {
-    const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
-    for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
-  }
+  put_next_timestep(t_out, timesteps, num_steps, s, B);
 }
 
 // ---- DPM-Solver++(2M) update (schedule.dpmpp_coefficients): coef rows (A, E, C, hx, he), x' = A x + E eps + C h_prev, and
@@ -449,15 +386,14 @@ __global__ __launch_bounds__(256) void ddim_cond_step_noise_kernel(T* __restrict
 // value (as the noise term of ddim_step_noise_kernel is).  A row with C == 0 (the first and the last of every table: no
 // history yet, and the step to alpha_bar = 1) does not read hist -- the branch is uniform over the launch -- so its state is
 // ib_ddim_step's given (A, E), bit for bit, and an uninitialised history never reaches the state.  Every row writes hist.
-// mix8: as in ddim_cond_step_kernel.
 template <typename T, int V>
 __global__ __launch_bounds__(256) void dpmpp_step_kernel(T* __restrict__ x, const T* __restrict__ eps, float* hist,
                                                          const float* __restrict__ coef,
                                                          const int64_t* __restrict__ timesteps, int64_t num_steps, int step,
                                                          const int32_t* __restrict__ step_dev, int64_t* __restrict__ t_out,
                                                          int64_t B, int64_t n, int mix8) {
-  int s = step_dev ? *step_dev : step;
-  s = s < 0 ? 0 : (s >= num_steps ? (int)num_steps - 1 : s);
+#pragma clang fp contract(off)
+  const int s = step_row(step, step_dev, num_steps);
   const float cx = coef[5 * s], ce = coef[5 * s + 1], ch = coef[5 * s + 2], hx = coef[5 * s + 3], he = coef[5 * s + 4];
   const bool second = ch != 0.f;                                       // uniform over the launch
   const int64_t nv = n / V;
@@ -467,8 +403,7 @@ __global__ __launch_bounds__(256) void dpmpp_step_kernel(T* __restrict__ x, cons
     ldv<T, V>(x + e0, a);
     ldv<T, V>(eps + e0, e);
 #pragma unroll
-    for (int k = 0; k < V; ++k)
-      o[k] = (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a[k], ce, e[k]) : ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
+    for (int k = 0; k < V; ++k) o[k] = mix_at<T, V>(k, e0, mix8, cx, a[k], ce, e[k]);
     if (second) {
       ldv<float, V>(hist + e0, h);
 #pragma unroll
@@ -479,77 +414,10 @@ __global__ __launch_bounds__(256) void dpmpp_step_kernel(T* __restrict__ x, cons
     stv<float, V>(hist + e0, h);
     stv<T, V>(x + e0, o);
   }
-  if (t_out && blockIdx.x == 0) {
-    const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
-    for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
-  }
+  put_next_timestep(t_out, timesteps, num_steps, s, B);
 }
 
-// the pinned value of a lone observed element as ddim_cond_step_kernel<T, 1, false> compiled it for gfx950: the sum of two
-// rounded products.  (Spelled out: next to the history's arithmetic the bare expression was fused in one instantiation.)
-__device__ __forceinline__ float obs_pin1(float ox, float a, float oz, float b) {
-#pragma clang fp contract(off)
-  return ox * a + oz * b;
-}
-
-// the loop of ddim_cond_step_kernel<T, V, false> with the history added to the vectors that have a free element: the
-// observed elements' pinned expression is that kernel's statement, so that it compiles as it does there (8-wide: checked
-// in the ISA, the same multiply / fused multiply-add pairing per element; element-wise: obs_pin1).  SECOND: the row
-// has C != 0 and reads hist.  What hist holds at an observed element is unspecified (a vector of observed elements only is
-// not touched; in a mixed vector it gets the expression of the free ones) and no step reads it there.
-template <typename T, int V, bool SECOND>
-__device__ __forceinline__ void dpmpp_cond_update(T* __restrict__ x, const T* __restrict__ eps, float* hist,
-                                                  const T* __restrict__ x0, const T* __restrict__ z,
-                                                  const uint8_t* __restrict__ mask, float cx, float ce, float ch, float hx,
-                                                  float he, float ox, float oz, int64_t per, int64_t n, int mix8) {
-  constexpr unsigned ALL = (1u << V) - 1;
-  const int64_t nv = n / V;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t e0 = i * V, m0 = e0 % per;
-    unsigned bits;
-    if constexpr (V == 1) {
-      bits = mask[m0] != 0;
-    } else {
-      const uint64_t mv = *reinterpret_cast<const uint64_t*>(mask + m0);
-      bits = 0;
-#pragma unroll
-      for (int k = 0; k < V; ++k) bits |= (((mv >> (8 * k)) & 0xff) != 0 ? 1u : 0u) << k;
-    }
-    float o[V];
-    if (bits != ALL) {
-      float a[V];
-      ldv<T, V>(x + e0, a);
-      float e[V];
-      ldv<T, V>(eps + e0, e);
-#pragma unroll
-      for (int k = 0; k < V; ++k)
-        o[k] = (V == 1 && mix8) ? ddim_mix<T, 8>((int)(e0 & 7), cx, a[k], ce, e[k]) : ddim_mix<T, V>(k, cx, a[k], ce, e[k]);
-      float h[V];
-      if constexpr (SECOND) {
-        ldv<float, V>(hist + e0, h);
-#pragma unroll
-        for (int k = 0; k < V; ++k) o[k] = __builtin_fmaf(ch, h[k], o[k]);
-      }
-#pragma unroll
-      for (int k = 0; k < V; ++k) h[k] = __builtin_fmaf(hx, a[k], he * e[k]);
-      stv<float, V>(hist + e0, h);
-    }
-    if (bits != 0) {
-      float a[V], b[V];
-      ldv<T, V>(x0 + e0, a);
-      ldv<T, V>(z + e0, b);
-#pragma unroll
-      for (int k = 0; k < V; ++k)
-        if ((bits >> k) & 1u) {
-          if constexpr (V == 1) o[k] = obs_pin1(ox, a[k], oz, b[k]);
-          else o[k] = ox * a[k] + oz * b[k];
-        }
-    }
-    stv<T, V>(x + e0, o);
-  }
-}
-
-// masked DPM-Solver++(2M) update: free elements as dpmpp_step_kernel, observed ones the pinned value of
+// masked DPM-Solver++(2M) update (masked_update): free elements as dpmpp_step_kernel, observed ones the pinned value of
 // ddim_cond_step_kernel, obs_coef[s + 1] (x0, z)
 template <typename T, int V>
 __global__ __launch_bounds__(256) void dpmpp_cond_step_kernel(T* __restrict__ x, const T* __restrict__ eps, float* hist,
@@ -561,18 +429,15 @@ __global__ __launch_bounds__(256) void dpmpp_cond_step_kernel(T* __restrict__ x,
                                                               int step, const int32_t* __restrict__ step_dev,
                                                               int64_t* __restrict__ t_out, int64_t B, int64_t per, int64_t n,
                                                               int mix8) {
-  int s = step_dev ? *step_dev : step;
-  s = s < 0 ? 0 : (s >= num_steps ? (int)num_steps - 1 : s);
-  const float cx = coef[5 * s], ce = coef[5 * s + 1], ch = coef[5 * s + 2], hx = coef[5 * s + 3], he = coef[5 * s + 4];
-  const float ox = obs_coef[2 * (s + 1)], oz = obs_coef[2 * (s + 1) + 1];
-  if (ch == 0.f)                                                       // uniform over the launch
-    dpmpp_cond_update<T, V, false>(x, eps, hist, x0, z, mask, cx, ce, ch, hx, he, ox, oz, per, n, mix8);
+  const int s = step_row(step, step_dev, num_steps);
+  const MaskedCoef c{coef[5 * s], coef[5 * s + 1], coef[5 * s + 2], coef[5 * s + 3], coef[5 * s + 4],
+                     obs_coef[2 * (s + 1)], obs_coef[2 * (s + 1) + 1]};
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  if (c.ch == 0.f)                                                     // uniform over the launch
+    masked_update<T, V, false, true, false>(x, eps, hist, x0, z, mask, c, per, n, mix8, i0, stride);
   else
-    dpmpp_cond_update<T, V, true>(x, eps, hist, x0, z, mask, cx, ce, ch, hx, he, ox, oz, per, n, mix8);
-  if (t_out && blockIdx.x == 0) {
-    const int64_t tn = (s + 1 < num_steps) ? timesteps[s + 1] : 0;
-    for (int64_t b = threadIdx.x; b < B; b += blockDim.x) t_out[b] = tn;
-  }
+    masked_update<T, V, false, true, true>(x, eps, hist, x0, z, mask, c, per, n, mix8, i0, stride);
+  put_next_timestep(t_out, timesteps, num_steps, s, B);
 }
 
 // mean and unbiased standard deviation over the K members of an ensemble x [B, K, n], fp32 out.  One lane per (b, j); the

@@ -34,6 +34,6 @@ static inline bool ib_q_sample_v4(int64_t D, int64_t ld_xt, int elemsize, const 
   return D % 4 == 0 && ld_xt % 4 == 0 && ib_aligned(x0, bytes) && ib_aligned(eps, bytes) && ib_aligned(x_t, bytes);
 }
 
-// step noise of an 8-wide update: an 8-vector is two whole Philox blocks (step_noise8<true>) when D % 4 == 0 and every
+// step noise of an 8-wide update: an 8-vector is two whole Philox blocks (step_noise<8, true>) when D % 4 == 0 and every
 // row starts on a multiple of 8, or there is no pitch
 static inline bool ib_step_noise_blk(int64_t D, int64_t ld) { return D % 4 == 0 && (ld == D || ld % 8 == 0); }

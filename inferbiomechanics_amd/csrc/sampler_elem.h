@@ -1,14 +1,10 @@
-// Element helpers of the sampler updates outside diffusion.hip -- the stitched family (stitch_step.h, included by stitch.hip,
-// sde.hip and resample.hip) and cfg.hip: COPIES of ldv / stv, ddim_mix and obs_pin1 of diffusion.hip.  Copies of THAT file
-// only: diffusion.hip's kernels are pinned bit for bit, and moving their helpers or loops into shared code has changed their
-// instruction order before, so it does not include this file; whether the two fold into one is a later question.  Whoever
-// changes a form here changes it there (tests/test_stitch_kernels_gpu.py compares the two bit for bit).  Among the files
-// that do include this one nothing is copied: what the stitched kernels share lives in stitch_step.h.
-// ONE helper here is NOT a copy of source: obs_pin8.  diffusion.hip's 8-wide masked kernels write the bare expression
-// ox * a + oz * b and leave its contraction to the compiler; obs_pin8 restates the code the compiler generates for it today.
-// A compiler that contracts that expression differently changes those kernels and not this file, and the one-window
-// comparison of tests/test_stitch_kernels_gpu.py (check (a), ld % 8 == 0, observed elements) is what reports it; the
-// durable fix is to spell the form out in diffusion.hip itself, which this file's reason for existing forbids for now.
+// Element helpers of every sampler update: the flat kernels of diffusion.hip, the stitched family (stitch_step.h, included by
+// stitch.hip, sde.hip and resample.hip) and cfg.hip.  The vector load / store and the three rounding forms below are the
+// DEFINITION of the updates' arithmetic: each spells which product is rounded and which is fused, under `fp contract(off)`,
+// so a result never depends on how the compiler would contract an expression in one kernel or another, and two kernels
+// that go through the same form agree bit for bit (tests/test_flat_pins_gpu.py and tests/test_stitch_kernels_gpu.py restate
+// the observed forms in exact rational arithmetic).  The forms are what the bare expressions compiled to for gfx950 when the
+// kernels were written; results are pinned to them, so whoever changes one changes every sampler's output.
 #pragma once
 #include "ib_common.h"
 
@@ -41,9 +37,9 @@ __device__ __forceinline__ void stv(T* p, const float (&v)[V]) {
   }
 }
 
-// One element k of the DDIM update x' = cx * x + ce * eps of a vector of V, with its fp32 roundings spelled out: one lone
-// element sums two rounded products; fp32 x 8 fuses cx * x into the rounded ce * eps; bf16 x 8 alternates which of the two
-// products is rounded first.
+// One element k of the DDIM update x' = cx * x + ce * eps of a vector of V: one lone element sums two rounded products;
+// fp32 x 8 fuses cx * x into the rounded ce * eps; bf16 x 8 alternates which of the two products is rounded first.  The
+// unmasked updates and the free elements of the masked ones all go through it, so they agree bit for bit.
 template <typename T, int V>
 __device__ __forceinline__ float ddim_mix(int k, float cx, float a, float ce, float e) {
 #pragma clang fp contract(off)
@@ -58,10 +54,8 @@ __device__ __forceinline__ float obs_pin1(float ox, float a, float oz, float b) 
   return ox * a + oz * b;
 }
 
-// the same value at element k of a vector of 8.  Mirrors CODE GENERATION, not source (see the head of this file): as the
-// 8-wide kernels of diffusion.hip compile their bare expression for gfx950, either dtype (read off their ISA), oz * b is
-// rounded and ox * a fused into it, except at element 1, where it is the other way round (that element comes out of the
-// high half of a packed fused multiply-add).
+// the same value at element k of a vector of 8, either dtype, start state and step alike: oz * b is rounded and ox * a
+// fused into it, except at element 1, where it is the other way round
 __device__ __forceinline__ float obs_pin8(int k, float ox, float a, float oz, float b) {
 #pragma clang fp contract(off)
   return k == 1 ? __builtin_fmaf(oz, b, ox * a) : __builtin_fmaf(ox, a, oz * b);

@@ -5,8 +5,8 @@
 // element are bitwise equal before and after every launch.  The update blends the noise predictions of the covering
 // windows, updates the element once and writes the one result to every copy.  ONE kernel template (stitch_step.h) holds
 // the loop, so the updates cannot drift apart: MODE 0 = ddim, 1 = dpm, 2 = noise, 3 = dpm and noise together (sde.hip's
-// entry point), and what only some of them do sits behind `if constexpr` on MODE's bits.  diffusion.hip is pinned bit for
-// bit and stays as it is.
+// entry point), and what only some of them do sits behind `if constexpr` on MODE's bits.  The flat updates of diffusion.hip
+// take their rounding forms from the same header (sampler_elem.h), which is why one window here equals them bit for bit.
 //
 // One thread owns V consecutive columns of one trial row (n, f): it alone reads and writes the copies of those elements, so
 // the update is in place with no LDS and no atomics.  Per launch it reads count x the eps bytes of a row (count = windows

@@ -15,11 +15,11 @@ observations; DDIM and DPM-Solver++ rows with C = 0 and C != 0.
 (c) Every output lies within a bound derived from the operation count, see bound().
 (d) Observed elements equal the pinned expression exactly; pad columns stay 0.
 (e) The argument refusals."""
-from fractions import Fraction
-
 import numpy as np
 import pytest
 import torch
+
+from tests.exact_fp32 import pinned
 
 pytestmark = pytest.mark.gpu
 
@@ -206,24 +206,6 @@ def test_one_window_equals_the_existing_kernels(tabs, dt, D, ld, solver, cond, s
 # ---------------------------------------------------------------------------------------------------------------------
 # (b), (c), (d): overlapping windows
 # ---------------------------------------------------------------------------------------------------------------------
-def rn32(fr):
-    """the float32 nearest to a Fraction, ties to even"""
-    x = np.float32(float(fr))
-    cands = [x, np.nextafter(x, np.float32(np.inf)), np.nextafter(x, np.float32(-np.inf))]
-    return min(cands, key=lambda c: (abs(Fraction(float(c)) - fr), int(np.float32(c).view(np.uint32)) & 1))
-
-
-def pinned(ox, a, oz, b, k, vec):
-    """the observed value ox a + oz b in the kernel's fp32 arithmetic, exactly: alone the sum of two rounded products
-    (obs_pin1); at element k of an 8-vector oz b is rounded and ox a fused into it, the other way round at k == 1 (obs_pin8)"""
-    ox, a, oz, b = (Fraction(float(v)) for v in (ox, a, oz, b))
-    if not vec:
-        return rn32(Fraction(float(rn32(ox * a))) + Fraction(float(rn32(oz * b))))
-    if k == 1:
-        return rn32(oz * b + Fraction(float(rn32(ox * a))))
-    return rn32(ox * a + Fraction(float(rn32(oz * b))))
-
-
 def bound(count, mag, ref, dt):
     """|computed - float64 value| of one element.  fp32 roundings: the blend of `count` windows rounds `count` times (one
     product, count - 1 fused multiply-adds; none for one window), each by at most u times a partial sum that Sum |w_k e_k|
