@@ -15,6 +15,7 @@ __device__ __forceinline__ float act_bwd_pre(int act, float z) {
     case IB_ACT_TANH: { float t = tanhf(z); return 1.f - t * t; }
     case IB_ACT_SIGMOID: { float s = 1.f / (1.f + expf(-z)); return s * (1.f - s); }
     case IB_ACT_SILU: { float s = 1.f / (1.f + expf(-z)); return s * (1.f + z * (1.f - s)); }
+    case IB_ACT_ELU: return z > 0.f ? 1.f : expf(z);
     default: return 1.f;
   }
 }
