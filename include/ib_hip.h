@@ -678,7 +678,7 @@ enum {
   IB_PATH_RING_MULTI = 8,   /* gemm.hip: grouped ring weight-gradient launch */
   IB_PATH_LINLN = 9,        /* gemm.hip: K-split Linear + residual + LayerNorm (sampler) */
   IB_PATH_CHAIN2 = 10,      /* chain.hip: fused MLP-denoiser chain, row-wise epilogues */
-  IB_PATH_CHAIN1 = 11,      /* chain.hip: the round-2 chain kernel (IB_CHAIN_V1=1) */
+  IB_PATH_CHAIN1 = 11,      /* retired, never returned: the round-2 chain kernel (the number stays: recorded profiles use it) */
   IB_PATH_TN256 = 12,       /* gemm_tn256.hip: 256 x 256 weight-gradient kernel, grouped, one split count per group */
   IB_PATH_NT_SPLITK = 13,   /* gemm_nt.hip in split-K form (fp32 slabs) under the sampler's Linear + LayerNorm */
   IB_PATH_FFN_CHAIN = 14,   /* ffn_chain.hip: fused feed-forward sublayer (Linear + ReLU + Linear + residual + LayerNorm) */

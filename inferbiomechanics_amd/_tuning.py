@@ -57,7 +57,6 @@ _SPEC = {
     "no_tb_rider": ("IB_NO_TB_RIDER", False),
     "skip_time_bwd": ("IB_SKIP_TIME_BWD", False),      # timing only: drops work, never set outside tools/
     "no_chain": ("IB_NO_CHAIN", False),
-    "chain_v1": ("IB_CHAIN_V1", False),
     "no_defer": ("IB_NO_DEFER", False),
     # ---- trainer
     "no_opt_fuse": ("IB_NO_OPT_FUSE", False),

@@ -9,13 +9,14 @@
 // that owns a panel of <= 64 tokens can run the whole network with its activations resident in LDS and the weights
 // streamed from L2.  The unfused plan moved every [M,512] activation through HBM 2-4 times and paid ~25 launches.
 //
-// Geometry: 512 threads = 8 waves; the panel's activations are the MFMA "b" operand (64 rows = 4 m-tiles), each
-// wave owns a distinct slice of the layer's OUTPUT columns (NT n-tiles of 16) and therefore a distinct slice of the
-// weight matrix -> weights go global -> VGPR directly (no LDS round trip, no sharing to exploit), from a
+// Geometry: 512 threads = 8 waves; the panel's activations are the MFMA "b" operand (64 rows = 4 m-tiles).  In a GEMM
+// phase each wave owns a distinct slice of the layer's OUTPUT columns (NT n-tiles of 16) and therefore a distinct slice of
+// the weight matrix -> weights go global -> VGPR directly (no LDS round trip, no sharing to exploit), from a
 // fragment-major packed image (ib_mlp_chain_pack) so that every wave-instruction reads one contiguous 1 KiB block.
 // MFMA is issued "swapped" (a = weights, b = activations): a lane ends up with 4 consecutive output columns of one
-// row, so bias / embedding / gamma loads and every store are 8- or 16-byte pieces.
-// LayerNorm row statistics: 16-lane-group shuffles + one cross-wave exchange through LDS, fixed order (deterministic).
+// row, so bias / embedding loads and the stores into the LDS image are 8- or 16-byte pieces.
+// The epilogues own whole ROWS (a wave a row, a lane 8 consecutive columns): LayerNorm row statistics are DPP sums within
+// a wave, fixed order (deterministic); see the comment above mlp_chain2_kernel.
 #include "wave_prims.h"
 #include "../../include/ib_hip_head.h"
 #include "head_jobs.h"
@@ -63,9 +64,6 @@ __device__ __forceinline__ float row16_sum(float v) {
   return v;
 }
 
-// keeps per-phase index arithmetic (divisions by runtime row widths) from being computed once and spilled across phases
-__device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-
 // v_exp_f32 + v_rcp_f32 (1 ulp each; __frcp_rn / 1.f/x expand to the 10-instruction IEEE division sequence)
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 
@@ -79,35 +77,19 @@ __device__ __forceinline__ bf16x4_t pack4(float a, float b, float c, float d) {
 // Packed weights: block (nt, kb) is 1 KiB at ((kb * NTOT + nt) * 64 + lane) * 16 bytes, NTOT = 8 * NT n-tiles: the 32 blocks
 // the eight waves of a workgroup request at one k-step are 32 KiB CONTIGUOUS (k-block-major).  (n-tile-major, block
 // (nt, kb) at nt * KB + kb, put those 32 requests 16 KiB apart -- a power-of-two stride that lands them on the same few
-// L2 channels; IB_CHAIN_KBMAJOR=0 builds that layout for the A/B.)
-#ifndef IB_CHAIN_KBMAJOR
-#define IB_CHAIN_KBMAJOR 1
-#endif
-// IB_CHAIN_EPS_LATE (round 4): the head phase requests the panel's eps rows (the loss target) four k-blocks before its GEMM
-// ends instead of ahead of it, and sums the loss with DPP adds; = 0 rebuilds the round-3 head for the A/B (59.9 -> 57.8-58.4 us)
-#ifndef IB_CHAIN_EPS_LATE
-#define IB_CHAIN_EPS_LATE 1
-#endif
+// L2 channels.)
 // Prefetch ring of 3 k-blocks (2 in flight while one is consumed); the loop is fully unrolled so ring slots are
-// static registers.  `side(kb)` is called once per k-block: the row copies of the neighbouring phases (stores of the
-// previous output image, loads of the next epilogue's operands) are issued a piece per k-block BEHIND the first weight
-// loads -- vmcnt retires in order, so a burst of stores issued ahead of the weight stream delayed every GEMM phase by
-// the stores' round trip (+5 us per phase).
+// static registers.  `side(kb)` is called once per k-block: the memory traffic of the neighbouring phases (loads of the
+// next epilogue's operands) is issued at a chosen k-block BEHIND the first weight loads -- vmcnt retires in order, so
+// requests issued ahead of the weight stream delay the GEMM phase by their round trip (a burst of row stores there:
+// +5 us per phase).
 template <int V> struct IntC { static constexpr int value = V; };
 template <int NT, int KB, class Side>
 __device__ __forceinline__ void chain_gemm(const bf16_t* __restrict__ wp, int nt0, const unsigned char* abuf, int rs,
                                            int lane, f32x4_t (&acc)[4][NT], Side&& side) {
-#ifndef IB_CHAIN_RING
-#define IB_CHAIN_RING 3
-#endif
-  constexpr int RING = IB_CHAIN_RING, PD = RING - 1;
-#if IB_CHAIN_KBMAJOR
+  constexpr int RING = 3, PD = RING - 1;
   constexpr int SU = 1, SK = CH_WAVES * NT;       // block strides of the n-tile / k-block index
   const bf16x8_t* wl = reinterpret_cast<const bf16x8_t*>(wp) + (int64_t)nt0 * 64 + lane;
-#else
-  constexpr int SU = KB, SK = 1;
-  const bf16x8_t* wl = reinterpret_cast<const bf16x8_t*>(wp) + ((int64_t)nt0 * KB) * 64 + lane;
-#endif
   const unsigned char* arow = abuf + (lane & 15) * rs + 16 * (lane >> 4);
   bf16x8_t wr[RING][NT];
 #pragma unroll
@@ -143,570 +125,39 @@ __device__ __forceinline__ void zero_acc(f32x4_t (&acc)[4][NT]) {
     for (int u = 0; u < NT; ++u) acc[mt][u] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 }
 
-// Cross-wave row reduction of TWO quantities in one exchange: each lane holds partial sums for NM of its rows (m-tiles
-// mt0 .. mt0+NM-1) over this wave's columns.  red: [64 rows][8 waves] float2.  Returns the full-row totals (fixed order).
-template <int NM>
-__device__ __forceinline__ void row_reduce2(float (&a)[NM], float (&b)[NM], float2* red, int lane, int wave, int mt0) {
-#pragma unroll
-  for (int m = 0; m < NM; ++m) {
-    a[m] += __shfl_xor(a[m], 16, 64); b[m] += __shfl_xor(b[m], 16, 64);
-    a[m] += __shfl_xor(a[m], 32, 64); b[m] += __shfl_xor(b[m], 32, 64);
-  }
-  if (lane < 16) {
-#pragma unroll
-    for (int m = 0; m < NM; ++m) red[(16 * (mt0 + m) + lane) * CH_WAVES + wave] = make_float2(a[m], b[m]);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int m = 0; m < NM; ++m) {
-    const float4* r4 = reinterpret_cast<const float4*>(red + (16 * (mt0 + m) + (lane & 15)) * CH_WAVES);
-    const float4 p0 = r4[0], p1 = r4[1], p2 = r4[2], p3 = r4[3];
-    a[m] = ((((((p0.x + p0.z) + p1.x) + p1.z) + p2.x) + p2.z) + p3.x) + p3.z;
-    b[m] = ((((((p0.y + p0.w) + p1.y) + p1.w) + p2.y) + p2.w) + p3.y) + p3.w;
-  }
-}
-
 // NTH: n-tiles per wave for the hidden width (H = 128 * NTH);  NTD / KBD: n-tiles per wave and k-blocks for the
 // feature width (D <= 128 * NTD, D <= 32 * KBD).
-// IB_CHAIN_NHF: the backward epilogue walks the panel's four m-tiles in NHF groups; the fewer m-tiles are live at once, the
-// fewer registers spill -- and a spill reload is a vector-memory operation that retires in order behind the weight
-// prefetch.  Measured (B = 256, T = 50): NHF = 1 736 B of scratch per lane; NHF = 2 208 B, 97-101 us; NHF = 4 72 B, 88 us.
-#ifndef IB_CHAIN_NHF
-#define IB_CHAIN_NHF 4
-#endif
-constexpr int CH_NWIN = 8;                                 // windows whose time embedding is staged per panel
+constexpr int CH_NWIN = 8;                                // windows whose time embedding is staged per panel
 template <int NTH, int NTD, int KBD>
 struct ChainCfg {
   static constexpr int H = 128 * NTH, KBH = 4 * NTH, DP = 32 * KBD, DN = 128 * NTD;
   static constexpr int WMAX = (H > DP ? (H > DN ? H : DN) : (DP > DN ? DP : DN));
   static constexpr int RS = WMAX * 2 + 16;                 // LDS row stride (bytes): +16 -> conflict-free b128 reads
   static constexpr int BUF = CH_ROWS * RS;
-  static constexpr int RED = CH_ROWS * CH_WAVES * 8;       // one cross-wave exchange array (float2)
+  static constexpr int COEF = 2 * CH_ROWS * CH_WAVES * 8;  // q_sample's per-row float2 coefficients (the first CH_ROWS slots)
   static constexpr int STATS = CH_MAXL * CH_ROWS * 2 * 4;
   static constexpr int EIMG = CH_NWIN * H * 2;
-  static constexpr int LDS = 2 * BUF + 2 * RED + STATS + EIMG + 64;
-  static constexpr int CSS = 16 * NTH + 4;                 // column-sum scratch row stride (floats)
-  static_assert(CH_WAVES * 16 * CSS * 4 <= BUF, "column-sum scratch must fit one image buffer");
+  static constexpr int LDS = 2 * BUF + COEF + STATS + EIMG + 64;
 };
 
-// ---- coalesced row movers between HBM and an LDS image (row stride rs bytes).  Per-lane epilogue accesses are
-// 16 rows x 32 B per wave-instruction (store-issue-bound: ~9k cycles per 16 of them); whole rows move as 16-byte pieces,
-// one piece per thread per call (piece j of thread tid is element tid + 512 j of the row-major piece grid).
-// Branch-free: rows beyond the panel are CLAMPED to its last row (a duplicate store of identical bytes / a finite
-// duplicate load whose consumers are masked).  A divergent branch around a load or store inside the GEMM loop makes
-// hipcc fall back to s_waitcnt vmcnt(0) at the join, which drains the weight prefetch ring every k-block.
-__device__ __forceinline__ void out_piece16(const unsigned char* img, int rs, bf16_t* g, int64_t ldg, int nrows, int ppr,
-                                            int idx) {
-  const int row = min(idx / ppr, nrows - 1), pc = idx % ppr;
-  const uint4 v = *reinterpret_cast<const uint4*>(img + row * rs + pc * 16);
-  *reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(g + (int64_t)row * ldg) + pc * 16) = v;
-}
-__device__ __forceinline__ void out_piece8(const unsigned char* img, int rs, bf16_t* g, int64_t ldg, int nrows, int ppr,
-                                           int idx) {
-  const int row = min(idx / ppr, nrows - 1), pc = idx % ppr;
-  const uint2 v = *reinterpret_cast<const uint2*>(img + row * rs + pc * 8);
-  *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(g + (int64_t)row * ldg) + pc * 8) = v;
-}
+// 16-byte piece idx of a row-major piece grid (ppr pieces per row) of an HBM matrix.  Branch-free: rows beyond nrows are
+// CLAMPED to the last row (a finite duplicate load whose consumers are masked).  A divergent branch around a load inside
+// the GEMM loop makes hipcc fall back to s_waitcnt vmcnt(0) at the join, which drains the weight prefetch ring every k-block.
 __device__ __forceinline__ uint4 in_piece16(const bf16_t* g, int64_t ldg, int nrows, int ppr, int idx) {
   const int row = min(idx / ppr, nrows - 1), pc = idx % ppr;
   return *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(g + (int64_t)row * ldg) + pc * 16);
 }
-__device__ __forceinline__ uint2 in_piece8(const bf16_t* g, int64_t ldg, int nrows, int ppr, int idx) {
-  const int row = min(idx / ppr, nrows - 1), pc = idx % ppr;
-  return *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(g + (int64_t)row * ldg) + pc * 8);
-}
-template <int NP>
-__device__ __forceinline__ void store_rows16(unsigned char* img, int rs, int ppr, int tid, const uint4 (&r)[NP]) {
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    const int idx = tid + j * CH_THREADS;
-    const int row = idx / ppr, pc = idx - row * ppr;
-    if (row < CH_ROWS) *reinterpret_cast<uint4*>(img + row * rs + pc * 16) = r[j];
-  }
-}
-template <int NP>
-__device__ __forceinline__ void store_rows8(unsigned char* img, int rs, int ppr, int tid, const uint2 (&r)[NP]) {
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    const int idx = tid + j * CH_THREADS;
-    const int row = idx / ppr, pc = idx - row * ppr;
-    if (row < CH_ROWS) *reinterpret_cast<uint2*>(img + row * rs + pc * 8) = r[j];
-  }
-}
-
-// column sums over the panel's 64 rows of a per-lane quantity q[u][r] (already summed over the lane's 4 m-tiles):
-// through a wave-private LDS scratch [16 rows][16*NT columns] -- 4 float4 writes + 16 reads per lane instead of 64
-// DPP steps.  Lane j < 16*NT returns the total of column (16*NT*wave + j); other lanes return 0.
-// Lanes exchange data through LDS WITHOUT a workgroup barrier here (the scratch is wave-private and a wave's LDS
-// operations execute in order), so the compiler must be told not to move the accesses across the exchange points.
-__device__ __forceinline__ void wave_sync_lds() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-template <int NT>
-__device__ __forceinline__ float wave_colsum(const float (&q)[NT][4], float* scr, int css, int lane) {
-  const int l16 = lane & 15, g = lane >> 4;
-  wave_sync_lds();                 // earlier reads of the scratch (previous quantity) are done
-#pragma unroll
-  for (int u = 0; u < NT; ++u)
-    *reinterpret_cast<float4*>(scr + l16 * css + 16 * u + 4 * g) = make_float4(q[u][0], q[u][1], q[u][2], q[u][3]);
-  wave_sync_lds();
-  float s = 0.f;
-  if (lane < 16 * NT) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += scr[r * css + lane];
-  }
-  return s;
-}
-
-template <int NTH, int NTD, int KBD>
-__global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
-  using C = ChainCfg<NTH, NTD, KBD>;
-  constexpr int H = C::H, RS = C::RS, PPR = H / 8, NPH = 2 * NTH;   // NPH: 16-byte pieces per thread of a [64, H] image
-  constexpr int NHF = IB_CHAIN_NHF, MPH = 4 / NHF;                  // backward epilogue: m-tile groups processed one after another
-  __shared__ __attribute__((aligned(16))) unsigned char smem[C::LDS];
-  unsigned char* buf0 = smem;
-  unsigned char* buf1 = smem + C::BUF;
-  float2* redA = reinterpret_cast<float2*>(smem + 2 * C::BUF);
-  float2* redB = redA + CH_ROWS * CH_WAVES;
-  float* stats = reinterpret_cast<float*>(redB + CH_ROWS * CH_WAVES);   // [L][64][2] mean, rstd
-  unsigned char* eimg = reinterpret_cast<unsigned char*>(stats + CH_MAXL * CH_ROWS * 2);   // [CH_NWIN][H] bf16
-  float* lossred = reinterpret_cast<float*>(eimg + C::EIMG);            // [8]
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wave_s = __builtin_amdgcn_readfirstlane(wave);     // scalar copy: thread ids for the row movers are rebuilt
-#define TIDV ((wave_s << 6) | lane_now())                    // from it, never kept in a (spillable) VGPR
-  const int g = lane >> 4, l16 = lane & 15;
-  const int r0 = blockIdx.x * p.P;
-  const int D = p.D, M = p.M;
-  const bf16_t* in_x0 = p.slots ? reinterpret_cast<const bf16_t*>(p.slots[0]) : p.x0;
-  const bf16_t* in_eps = p.slots ? reinterpret_cast<const bf16_t*>(p.slots[1]) : p.eps;
-  const int64_t* in_t = p.slots ? reinterpret_cast<const int64_t*>(p.slots[2]) : p.t;
-  const int nrows = min(p.P, M - r0);                      // valid token rows of this panel
-  const float invH = 1.f / (float)H;
-  IB_STAMP(p.prof, 64, 0, tid == 0);
-
-  int rowg[4]; bool valid[4];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) {
-    const int lr = 16 * mt + l16;
-    valid[mt] = lr < nrows;
-    rowg[mt] = min(r0 + lr, M - 1);
-  }
-  // time-embedding rows of the panel's windows are staged in LDS (a panel of <= 64 tokens spans few windows; all 16
-  // rows a lane group touches usually share ONE row of e: per-lane global loads of it were 16 x (16 rows x 32 B))
-  const int w0 = r0 / p.T;
-  const int nwin = (r0 + nrows - 1) / p.T - w0 + 1;
-  const bool estage = nwin <= CH_NWIN;
-  int ewl[4];                                              // local window of the lane's 4 rows
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt) ewl[mt] = min(rowg[mt] / p.T - w0, CH_NWIN - 1);
-
-  // ---- q_sample: xt = sqrt_ab[t] x0 + sqrt_1mab[t] eps -> LDS image (zero-padded to DP columns / 64 rows) + HBM.
-  // The per-row coefficients (two dependent loads) and the x0 / eps rows are fetched concurrently.
-  {
-    const int ppr = D >> 2;                                // 8-byte pieces per row
-    uint2 rx[KBD], re[KBD];
-#pragma unroll
-    for (int j = 0; j < KBD; ++j) {
-      rx[j] = in_piece8(in_x0 + (int64_t)r0 * D, D, nrows, ppr, TIDV + j * CH_THREADS);
-      re[j] = in_piece8(in_eps + (int64_t)r0 * D, D, nrows, ppr, TIDV + j * CH_THREADS);
-    }
-    float2* coef = redA;
-    if (tid < CH_ROWS) {
-      float2 c = make_float2(0.f, 0.f);
-      if (tid < nrows) {
-        int64_t k = in_t[(r0 + tid) / p.T];
-        k = k < 0 ? 0 : (k >= p.table_rows ? p.table_rows - 1 : k);
-        c = make_float2(p.sqrt_ab[k], p.sqrt_1mab[k]);
-      }
-      coef[tid] = c;
-    }
-    // zero the whole image first (pad columns / rows), then the computed pieces overwrite their slots
-    for (int idx = tid; idx < CH_ROWS * (C::DP / 8); idx += CH_THREADS) {
-      const int row = idx / (C::DP / 8), pc = idx % (C::DP / 8);
-      *reinterpret_cast<uint4*>(buf0 + row * RS + pc * 16) = make_uint4(0u, 0u, 0u, 0u);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < KBD; ++j) {
-      const int idx = tid + j * CH_THREADS;
-      const int row = idx / ppr, pc = idx - row * ppr;
-      if (row < nrows) {
-        const float2 c = coef[row];
-        const bf16x4_t xv = __builtin_bit_cast(bf16x4_t, rx[j]), ev = __builtin_bit_cast(bf16x4_t, re[j]);
-        const bf16x4_t o = pack4(c.x * (float)xv[0] + c.y * (float)ev[0], c.x * (float)xv[1] + c.y * (float)ev[1],
-                                 c.x * (float)xv[2] + c.y * (float)ev[2], c.x * (float)xv[3] + c.y * (float)ev[3]);
-        *reinterpret_cast<bf16x4_t*>(p.xt + (int64_t)(r0 + row) * p.ld_xt + pc * 4) = o;
-        *reinterpret_cast<bf16x4_t*>(buf0 + row * RS + pc * 8) = o;
-      }
-    }
-  }
-  __syncthreads();
-  IB_STAMP(p.prof, 64, 1, tid == 0);
-
-  unsigned char* cur = buf0;
-  unsigned char* nxt = buf1;
-
-  // ---- forward blocks
-  for (int i = 0; i < p.L; ++i) {
-    f32x4_t acc[4][NTH];
-    zero_acc<NTH>(acc);
-    // side jobs of the GEMM phase: the previous block's output rows go out (the `cur` image), this block's slice of
-    // the time embedding comes in
-    uint4 er = make_uint4(0u, 0u, 0u, 0u);
-    const bf16_t* esrc = p.e + (int64_t)w0 * p.ld_e + (int64_t)i * H;
-    if (i == 0) {
-      auto side = [&](int kb, auto) {
-        if (kb == 0) er = in_piece16(esrc, p.ld_e, min(nwin, CH_NWIN), PPR, TIDV);
-      };
-      chain_gemm<NTH, KBD>(p.wf[0], wave_s * NTH, cur, RS, lane_now(), acc, side);
-    } else {
-      bf16_t* hprev = p.h[i - 1] + (int64_t)r0 * H;
-      auto side = [&](int kb, auto kbc) {
-        constexpr int KB = decltype(kbc)::value;
-        if (kb == 0) er = in_piece16(esrc, p.ld_e, min(nwin, CH_NWIN), PPR, TIDV);
-#pragma unroll
-        for (int j = 0; j < NPH; ++j)
-          if (j % KB == kb) out_piece16(cur, RS, hprev, H, nrows, PPR, TIDV + j * CH_THREADS);
-      };
-      chain_gemm<NTH, C::KBH>(p.wf[i], wave_s * NTH, cur, RS, lane_now(), acc, side);
-    }
-    if (tid < CH_NWIN * PPR) *reinterpret_cast<uint4*>(eimg + tid * 16) = er;
-    IB_STAMP(p.prof, 64, 2 + 4 * i, tid == 0);
-    __syncthreads();                       // every wave is done reading `cur`: it becomes the u image; e image complete
-    const int colb = wave * 16 * NTH + 4 * g;
-    // u = z + bias + e (bf16) ; v = silu(u) ; one-pass row statistics (sum, sum of squares)
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    float4 b4[NTH];
-#pragma unroll
-    for (int u = 0; u < NTH; ++u) b4[u] = *reinterpret_cast<const float4*>(p.bias[i] + colb + 16 * u);
-    auto pass_u = [&](auto stagedc) {
-      constexpr bool STAGED = decltype(stagedc)::value != 0;
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const bf16_t* erow = p.e + (int64_t)(rowg[mt] / p.T) * p.ld_e + (int64_t)i * H;
-        const unsigned char* el = eimg + ewl[mt] * (H * 2);
-#pragma unroll
-        for (int u = 0; u < NTH; ++u) {
-          const int col = colb + 16 * u;
-          bf16x4_t e4;
-          if constexpr (STAGED) e4 = *reinterpret_cast<const bf16x4_t*>(el + col * 2);
-          else e4 = *reinterpret_cast<const bf16x4_t*>(erow + col);
-          const float bb[4] = {b4[u].x, b4[u].y, b4[u].z, b4[u].w};
-          bf16x4_t ub;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) ub[r] = (bf16_t)(acc[mt][u][r] + bb[r] + (float)e4[r]);
-          *reinterpret_cast<bf16x4_t*>(cur + (16 * mt + l16) * RS + col * 2) = ub;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float x = (float)ub[r];
-            const float v = x * fast_sigmoid(x);
-            acc[mt][u][r] = v;
-            s1[mt] += v;
-            s2[mt] += v * v;
-          }
-        }
-      }
-    };
-    if (estage) pass_u(IntC<1>{});
-    else pass_u(IntC<0>{});
-    IB_STAMP(p.prof, 64, 3 + 4 * i, tid == 0);
-    row_reduce2<4>(s1, s2, (i & 1) ? redB : redA, lane, wave, 0);
-    IB_STAMP(p.prof, 64, 4 + 4 * i, tid == 0);
-#pragma unroll
-    for (int j = 0; j < NPH; ++j)          // u image complete after the barrier inside the reduction
-      out_piece16(cur, RS, p.u[i] + (int64_t)r0 * H, H, nrows, PPR, TIDV + j * CH_THREADS);
-    float mean[4], rstd[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      mean[mt] = s1[mt] * invH;
-      rstd[mt] = __builtin_amdgcn_rsqf(fmaxf(s2[mt] * invH - mean[mt] * mean[mt], 0.f) + p.ln_eps);
-    }
-    if (wave == 0 && lane < 16) {
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        stats[(i * CH_ROWS + 16 * mt + lane) * 2 + 0] = mean[mt];
-        stats[(i * CH_ROWS + 16 * mt + lane) * 2 + 1] = rstd[mt];
-      }
-    }
-    // h = gamma * xhat + beta -> next A image (rows beyond the panel stay zero)
-#pragma unroll
-    for (int u = 0; u < NTH; ++u) {
-      const int col = colb + 16 * u;
-      const float4 g4 = *reinterpret_cast<const float4*>(p.gamma[i] + col);
-      const float4 be4 = *reinterpret_cast<const float4*>(p.beta[i] + col);
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const float m = mean[mt], rsd = rstd[mt];
-        bf16x4_t hb = pack4((acc[mt][u][0] - m) * rsd * g4.x + be4.x, (acc[mt][u][1] - m) * rsd * g4.y + be4.y,
-                            (acc[mt][u][2] - m) * rsd * g4.z + be4.z, (acc[mt][u][3] - m) * rsd * g4.w + be4.w);
-        if (!valid[mt]) hb = pack4(0.f, 0.f, 0.f, 0.f);
-        *reinterpret_cast<bf16x4_t*>(nxt + (16 * mt + l16) * RS + col * 2) = hb;
-      }
-    }
-    __syncthreads();
-    IB_STAMP(p.prof, 64, 5 + 4 * i, tid == 0);
-    unsigned char* t = cur; cur = nxt; nxt = t;
-  }
-
-  // ---- head + loss + dL/dpred  (columns >= D come out as exact zeros: the packed head rows there are zero)
-  {
-    const int ppr = D >> 2;
-    uint2 re[KBD];
-    f32x4_t acc[4][NTD];
-    zero_acc<NTD>(acc);
-    bf16_t* hlast = p.h[p.L - 1] + (int64_t)r0 * H;
-    const bf16_t* epsg = in_eps + (int64_t)r0 * D;
-    auto side = [&](int kb, auto kbc) {
-      constexpr int KB = decltype(kbc)::value;
-#pragma unroll
-      for (int j = 0; j < NPH; ++j)
-        if (j % KB == kb) out_piece16(cur, RS, hlast, H, nrows, PPR, TIDV + j * CH_THREADS);
-#pragma unroll
-      for (int j = 0; j < KBD; ++j)
-        if (j % KB == kb) re[j] = in_piece8(epsg, D, nrows, ppr, TIDV + j * CH_THREADS);
-    };
-    chain_gemm<NTD, C::KBH>(p.wf[p.L], wave_s * NTD, cur, RS, lane_now(), acc, side);
-    IB_STAMP(p.prof, 64, 2 + 4 * p.L, tid == 0);
-    store_rows8<KBD>(nxt, RS, ppr, TIDV, re);     // eps image; dpred overwrites it in place
-    __syncthreads();
-    const int colb = wave * 16 * NTD + 4 * g;
-    float lsum = 0.f;
-    float* prow = p.partial + (int64_t)blockIdx.x * p.ld_part;
-#pragma unroll
-    for (int u = 0; u < NTD; ++u) {
-      const int col = colb + 16 * u;
-      const bool cin = col < D;
-      float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (cin) b4 = *reinterpret_cast<const float4*>(p.bias[p.L] + col);
-      const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
-      float cs[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        bf16x4_t* slot = reinterpret_cast<bf16x4_t*>(nxt + (16 * mt + l16) * RS + col * 2);
-        bf16x4_t dp = pack4(0.f, 0.f, 0.f, 0.f);
-        if (cin && valid[mt]) {
-          const bf16x4_t e4 = *slot;
-          float d[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float pr = (float)(bf16_t)(acc[mt][u][r] + bb[r]);
-            d[r] = pr - (float)e4[r];
-            lsum += d[r] * d[r];
-          }
-          dp = pack4(d[0] * p.gscale, d[1] * p.gscale, d[2] * p.gscale, d[3] * p.gscale);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) cs[r] += (float)dp[r];
-        }
-        *slot = dp;
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) cs[r] = row16_sum(cs[r]);          // head-bias gradient: this panel's column sums
-      if (l16 == 0) *reinterpret_cast<float4*>(prow + 3 * p.L * H + col) = make_float4(cs[0], cs[1], cs[2], cs[3]);
-    }
-    lsum = ib_wave_sum(lsum);
-    if (lane == 0) lossred[wave] = lsum;
-    __syncthreads();
-    if (tid == 0) {
-      float s = 0.f;
-#pragma unroll
-      for (int w = 0; w < CH_WAVES; ++w) s += lossred[w];
-      prow[3 * p.L * H + C::DN] = s;
-    }
-    IB_STAMP(p.prof, 64, 3 + 4 * p.L, tid == 0);
-    unsigned char* t = cur; cur = nxt; nxt = t;
-  }
-
-  // ---- backward: dh_i = d(out of block i) ; through LayerNorm and SiLU -> dz_i ; dh_{i-1} = dz_i W_i.
-  // `cur` = the GEMM input image (dpred, then dz_{i+1}); after the GEMM it receives dz_i.  `nxt` = the u_i image.
-  const bool dp16 = (p.ld_dpred & 7) == 0 && (reinterpret_cast<uintptr_t>(p.dpred) & 15) == 0;
-  for (int i = p.L - 1; i >= 0; --i) {
-    uint4 ru[NPH];
-    f32x4_t acc[4][NTH];
-    zero_acc<NTH>(acc);
-    const bf16_t* usrc = p.u[i] + (int64_t)r0 * H;
-    if (i == p.L - 1) {
-      bf16_t* dpg = p.dpred + (int64_t)r0 * p.ld_dpred;
-      const int ppd = dp16 ? (D + 7) >> 3 : D >> 2;      // 16-byte pieces (pad columns receive the image's zeros) or 8
-      // [64, DP] image: DP/8 16-byte (or DP/4 8-byte) pieces per row cover every ld_dpred <= DP; piece columns beyond
-      // the row pitch are clamped onto the row's last piece
-      if (dp16) {
-        auto side = [&](int kb, auto kbc) {
-          constexpr int KB = decltype(kbc)::value;
-#pragma unroll
-          for (int j = 0; j < NPH; ++j)
-            if (j % KB == kb) ru[j] = in_piece16(usrc, H, nrows, PPR, TIDV + j * CH_THREADS);
-#pragma unroll
-          for (int j = 0; j < (C::DP / 8 * CH_ROWS + CH_THREADS - 1) / CH_THREADS; ++j)
-            if (j % KB == kb) {
-              const int idx = TIDV + j * CH_THREADS;
-              const int row = min(idx / (C::DP / 8), nrows - 1), pc = min(idx % (C::DP / 8), ppd - 1);
-              const uint4 v = *reinterpret_cast<const uint4*>(cur + row * RS + pc * 16);
-              *reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(dpg + (int64_t)row * p.ld_dpred) + pc * 16) = v;
-            }
-        };
-        chain_gemm<NTH, KBD>(p.wb[p.L], wave_s * NTH, cur, RS, lane_now(), acc, side);
-      } else {
-        auto side = [&](int kb, auto kbc) {
-          constexpr int KB = decltype(kbc)::value;
-#pragma unroll
-          for (int j = 0; j < NPH; ++j)
-            if (j % KB == kb) ru[j] = in_piece16(usrc, H, nrows, PPR, TIDV + j * CH_THREADS);
-#pragma unroll
-          for (int j = 0; j < (C::DP / 4 * CH_ROWS + CH_THREADS - 1) / CH_THREADS; ++j)
-            if (j % KB == kb) {
-              const int idx = TIDV + j * CH_THREADS;
-              const int row = min(idx / (C::DP / 4), nrows - 1), pc = min(idx % (C::DP / 4), ppd - 1);
-              const uint2 v = *reinterpret_cast<const uint2*>(cur + row * RS + pc * 8);
-              *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(dpg + (int64_t)row * p.ld_dpred) + pc * 8) = v;
-            }
-        };
-        chain_gemm<NTH, KBD>(p.wb[p.L], wave_s * NTH, cur, RS, lane_now(), acc, side);
-      }
-    } else {
-      bf16_t* dzg = p.dz[i + 1] + (int64_t)r0 * H;
-      auto side = [&](int kb, auto kbc) {
-        constexpr int KB = decltype(kbc)::value;
-#pragma unroll
-        for (int j = 0; j < NPH; ++j)
-          if (j % KB == kb) {
-            ru[j] = in_piece16(usrc, H, nrows, PPR, TIDV + j * CH_THREADS);
-            out_piece16(cur, RS, dzg, H, nrows, PPR, TIDV + j * CH_THREADS);
-          }
-      };
-      chain_gemm<NTH, C::KBH>(p.wb[i + 1], wave_s * NTH, cur, RS, lane_now(), acc, side);
-    }
-    IB_STAMP(p.prof, 64, 4 + 4 * p.L + 9 * (p.L - 1 - i), tid == 0);
-    store_rows16<NPH>(nxt, RS, PPR, TIDV, ru);
-    __syncthreads();
-    IB_STAMP(p.prof, 64, 5 + 4 * p.L + 9 * (p.L - 1 - i), tid == 0);
-    const int colb = wave * 16 * NTH + 4 * g;
-    float mean[4], rstd[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      const float2 st = *reinterpret_cast<const float2*>(stats + (i * CH_ROWS + 16 * mt + l16) * 2);
-      mean[mt] = st.x; rstd[mt] = st.y;
-    }
-    // Two m-tile halves (rows are independent; halving keeps xhat / silu' for only 32 elements per lane live):
-    //   pass 1: xhat, silu'(u); dgamma / dbeta partials; row sums of dxhat and dxhat * xhat
-    //   pass 2: dv = rstd (dxhat - mean(dxhat) - xhat mean(dxhat xhat)) ; dz = dv * silu'(u)
-    float dg[NTH][4], db[NTH][4];
-#pragma unroll
-    for (int u = 0; u < NTH; ++u)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { dg[u][r] = 0.f; db[u][r] = 0.f; }
-#pragma unroll
-    for (int hf = 0; hf < NHF; ++hf) {
-      bf16x4_t xh[MPH][NTH];             // xhat, bf16 (its only later use multiplies it into the bf16 dz)
-      bf16x4_t dsl[MPH][NTH];            // silu'(u), bf16
-      float sa[MPH], sb[MPH];
-#pragma unroll
-      for (int m2 = 0; m2 < MPH; ++m2) { sa[m2] = 0.f; sb[m2] = 0.f; }
-#pragma unroll
-      for (int u = 0; u < NTH; ++u) {
-        const int col = colb + 16 * u;
-        const float4 g4 = *reinterpret_cast<const float4*>(p.gamma[i] + col);
-        const float gg[4] = {g4.x, g4.y, g4.z, g4.w};
-#pragma unroll
-        for (int m2 = 0; m2 < MPH; ++m2) {
-          const int mt = MPH * hf + m2;
-          const bf16x4_t ub = *reinterpret_cast<const bf16x4_t*>(nxt + (16 * mt + l16) * RS + col * 2);
-          float ds[4], xq[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float x = (float)ub[r];                  // rows beyond the panel hold a finite duplicate row
-            const float sg = fast_sigmoid(x);
-            const float v = x * sg;
-            ds[r] = sg * (1.f + x * (1.f - sg));
-            const float xhat = (v - mean[mt]) * rstd[mt];
-            const float dh = valid[mt] ? acc[mt][u][r] : 0.f;
-            dg[u][r] += dh * xhat;
-            db[u][r] += dh;
-            const float dxh = dh * gg[r];
-            acc[mt][u][r] = dxh;
-            xq[r] = xhat;
-            sa[m2] += dxh;
-            sb[m2] += dxh * xhat;
-          }
-          dsl[m2][u] = pack4(ds[0], ds[1], ds[2], ds[3]);
-          xh[m2][u] = pack4(xq[0], xq[1], xq[2], xq[3]);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);    // keep the dgamma / dbeta FMAs inside their pass (hipcc deferred them with their operands spilled)
-      IB_STAMP(p.prof, 64, 6 + 4 * p.L + 9 * (p.L - 1 - i) + 2 * hf, tid == 0);
-      row_reduce2<MPH>(sa, sb, hf ? redA : redB, lane, wave, MPH * hf);
-      IB_STAMP(p.prof, 64, 7 + 4 * p.L + 9 * (p.L - 1 - i) + 2 * hf, tid == 0);
-#pragma unroll
-      for (int m2 = 0; m2 < MPH; ++m2) {
-        const int mt = MPH * hf + m2;
-        const float ma = sa[m2] * invH, mb = sb[m2] * invH, rsd = rstd[mt];
-#pragma unroll
-        for (int u = 0; u < NTH; ++u) {
-          const int col = colb + 16 * u;
-          float dzv[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            dzv[r] = rsd * (acc[mt][u][r] - ma - (float)xh[m2][u][r] * mb) * (float)dsl[m2][u][r];
-          bf16x4_t o = pack4(dzv[0], dzv[1], dzv[2], dzv[3]);
-          if (!valid[mt]) o = pack4(0.f, 0.f, 0.f, 0.f);
-          *reinterpret_cast<bf16x4_t*>(cur + (16 * mt + l16) * RS + col * 2) = o;
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    IB_STAMP(p.prof, 64, 10 + 4 * p.L + 9 * (p.L - 1 - i), tid == 0);
-    {
-      // per-workgroup column sums dgamma | dbeta.  Scratch = the u image (`nxt`): every wave finished reading it before
-      // the barrier inside the second reduction above.
-      float* scr = reinterpret_cast<float*>(nxt) + wave * 16 * C::CSS;
-      float* pg = p.partial + (int64_t)blockIdx.x * p.ld_part + 3 * i * H;
-      const int col = wave * 16 * NTH + lane;
-      const float sg_ = wave_colsum<NTH>(dg, scr, C::CSS, lane);
-      const float sb_ = wave_colsum<NTH>(db, scr, C::CSS, lane);
-      if (lane < 16 * NTH) {
-        pg[col] = sg_;
-        pg[H + col] = sb_;
-      }
-    }
-    IB_STAMP(p.prof, 64, 11 + 4 * p.L + 9 * (p.L - 1 - i), tid == 0);
-    __syncthreads();
-    {
-      // dbias = column sums of the bf16 dz image (rows beyond the panel are zero), one column per thread, fixed order.
-      // panel == one window: they ARE the time-embedding gradient row of that window.
-      if (tid < H) {
-        const unsigned char* cp = cur + tid * 2;
-        float sz = 0.f;
-#pragma unroll 16
-        for (int r = 0; r < CH_ROWS; ++r) sz += (float)*reinterpret_cast<const bf16_t*>(cp + r * RS);
-        p.partial[(int64_t)blockIdx.x * p.ld_part + 3 * i * H + 2 * H + tid] = sz;
-        if (p.de_lp) p.de_lp[(int64_t)blockIdx.x * p.ld_de + i * H + tid] = (bf16_t)sz;
-      }
-    }
-    if (i == 0) {
-#pragma unroll
-      for (int j = 0; j < NPH; ++j) out_piece16(cur, RS, p.dz[0] + (int64_t)r0 * H, H, nrows, PPR, TIDV + j * CH_THREADS);
-    }
-    IB_STAMP(p.prof, 64, 12 + 4 * p.L + 9 * (p.L - 1 - i), tid == 0);
-  }
-}
-
-#undef TIDV
 
 // =====================================================================================================================
-// v2 (round 3): the same chain with ROW-WISE epilogues.
+// The chain kernel: GEMM phases by COLUMN owners, epilogues by ROW owners.
 //
-// What the phase stamps of v1 said: the five GEMM phases take 24 of 74 us; the rest is epilogue time in which each wave
-// owns 64 COLUMNS of all 64 rows -- every LayerNorm statistic is then a cross-wave exchange behind a workgroup barrier
-// (the barrier waits for the SIMD's younger wave: 2-3 us each), every HBM row copy is a separate "piece mover" pass over
-// the LDS image with runtime index arithmetic (divisions by the row width), rows 50..63 of a 50-token panel are computed
-// and stored like real ones, and the pre-activation u makes an HBM round trip (26 MB written, 26 MB read per launch)
-// only to be re-read by the workgroup that wrote it.
-//
-// v2 keeps the GEMM phases (a wave owns output columns, weights stream L2 -> VGPR) and turns the tile through LDS once per
-// layer so that the epilogue owns whole ROWS: wave w takes rows w, w + 8, ... and a lane 8 consecutive columns of the row
-// (H = 512: 64 lanes x 8 columns = one row per wave-instruction).
+// In a GEMM phase a wave owns output columns (weights stream L2 -> VGPR, see chain_gemm).  The tile is then turned through
+// LDS once per layer so that the epilogue owns whole ROWS: wave w takes rows w, w + 8, ... and a lane 8 consecutive columns
+// of the row (H = 512: 64 lanes x 8 columns = one row per wave-instruction).  A row's LayerNorm statistics are then sums
+// within one wave (no cross-wave exchange, no workgroup barrier), a row goes to HBM as one coalesced store from registers
+// (no separate pass over the LDS image, no runtime index arithmetic), and rows beyond the panel are skipped.
+// (History: the first chain kernel, round 2, ran its epilogues by column owners too; its GEMM phases took 24 of its 74 us.
+// It is retired, see docs/EXPERIMENTS.md.)
 //   forward:  GEMM -> column owners write u = bf16(z + bias + e) into the second image -> barrier -> per row: SiLU, the two
 //             row sums by a 64-lane butterfly (no LDS, no barrier), normalise, h row -> first image (next GEMM's input) and
 //             -> HBM as one coalesced 1-KiB store from registers.  u stays IN REGISTERS (8 rows x 16 bytes per lane and
@@ -714,8 +165,9 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain_kernel(ChainParams p) {
 //   backward: GEMM -> column owners write dh (fp32, two halves of 32 rows: 66 KB) -> barrier -> per row: LayerNorm / SiLU
 //             backward entirely in registers, dz row -> image + HBM; dgamma / dbeta / dbias accumulate per lane over the
 //             wave's rows and are summed across waves once per layer, in wave order (deterministic).
-// Rows beyond the panel are skipped (wave-uniform test), not computed and clamped.  Same parameters, same outputs, same
-// partial-sum layout as v1; u[i] may be NULL (then it is not stored at all) when the blocks fit the register plan.
+// Rows beyond the panel are skipped (wave-uniform test), not computed and clamped.  u[i] may be NULL (then it is not stored
+// at all) when the blocks fit the register plan; deeper stacks (KEEP = false) pass u through HBM.
+//
 // Sum of a per-lane value over the LPR lanes that hold one row (LPR = 16, 32, 64); every lane of the group gets the total.
 // DPP only (ds_bpermute / __shfl_xor cross the LDS crossbar: ~100+ cycles of latency per step on the row's critical path):
 // the 16 lanes of a DPP row first, then row_bcast15 (lane 15 of rows 0 / 2 added into rows 1 / 3), row_bcast31 (lane 31
@@ -769,7 +221,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
   unsigned char* imgA = smem;                       // GEMM input of the forward; fp32 exchange / column sums in the backward
   unsigned char* imgB = smem + C::BUF;              // u exchange (forward), eps / dpred, GEMM input of the backward
   float2* coef = reinterpret_cast<float2*>(smem + 2 * C::BUF);
-  float* stats = reinterpret_cast<float*>(coef + 2 * CH_ROWS * CH_WAVES);   // [L][64][2] mean, rstd
+  float* stats = reinterpret_cast<float*>(smem + 2 * C::BUF + C::COEF);     // [L][64][2] mean, rstd
   unsigned char* eimg = reinterpret_cast<unsigned char*>(stats + CH_MAXL * CH_ROWS * 2);   // [CH_NWIN][H] bf16
   float* lossred = reinterpret_cast<float*>(eimg + C::EIMG);            // [8]
 
@@ -1007,9 +459,9 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
     float4 hb4[NTD];
     auto side = [&](int kb, auto kbc) {
       constexpr int KB = decltype(kbc)::value;
-#if IB_CHAIN_EPS_LATE
       // the panel's eps rows (the loss target), requested BEHIND the weight stream, four k-blocks before the GEMM ends:
-      // ahead of it (vmcnt retires in order) the first weight k-blocks waited for these 16 row pieces' round trip
+      // ahead of it (vmcnt retires in order) the first weight k-blocks waited for these 16 row pieces' round trip.  With
+      // the DPP loss sum below this took the launch from 59.9 to 57.8-58.4 us.
       if (kb == KB - 4) {
 #pragma unroll
         for (int j = 0; j < CH_ROWS / CH_WAVES; ++j) {
@@ -1019,7 +471,6 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
           for (int q = 0; q < 2; ++q) re[j][q] = *reinterpret_cast<const uint2*>(er_ + min(lane_now() + 64 * q, ppr - 1) * 4);
         }
       }
-#endif
       if (kb == KB - 1) {
 #pragma unroll
         for (int u = 0; u < NTD; ++u) {
@@ -1028,15 +479,6 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
         }
       }
     };
-#if !IB_CHAIN_EPS_LATE
-#pragma unroll
-    for (int j = 0; j < CH_ROWS / CH_WAVES; ++j) {
-      const int rc = min(wave_s + CH_WAVES * j, nrows - 1);
-      const bf16_t* er_ = in_eps + (int64_t)(r0 + rc) * D;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) re[j][q] = *reinterpret_cast<const uint2*>(er_ + min(lane + 64 * q, ppr - 1) * 4);
-    }
-#endif
     chain_gemm<NTD, C::KBH>(p.wf[p.L], wave_s * NTD, imgA, RS, lane_now(), acc, side);
     IB_STAMP(p.prof, 64, 2 + 3 * p.L, tid == 0);
 #pragma unroll
@@ -1078,11 +520,7 @@ __global__ __launch_bounds__(CH_THREADS) void mlp_chain2_kernel(ChainParams p) {
       for (int r = 0; r < 4; ++r) cs[r] = row16_sum(cs[r]);
       if (l16 == 0) *reinterpret_cast<float4*>(prow + 3 * p.L * H + col) = make_float4(cs[0], cs[1], cs[2], cs[3]);
     }
-#if IB_CHAIN_EPS_LATE
     lsum = group_sum<64>(lsum, lane);      // DPP only (six ds_bpermute round trips through the LDS crossbar before)
-#else
-    lsum = ib_wave_sum(lsum);
-#endif
     if (lane == 0) lossred[wave] = lsum;
     __syncthreads();                       // dpred image complete
     if (tid == 0) {
@@ -1281,11 +719,7 @@ __device__ __forceinline__ void pack_blocks(const PackParams& p, int first, int 
       if (blk >= p.d[j].block0) di = j;
     const PackDesc& d = p.d[di];
     const int local = blk - d.block0;
-#if IB_CHAIN_KBMAJOR
-    const int nt = local % d.n_tiles, kb = local / d.n_tiles;
-#else
-    const int nt = local / d.KB, kb = local % d.KB;
-#endif
+    const int nt = local % d.n_tiles, kb = local / d.n_tiles;      // k-block-major (see chain_gemm)
     const int n = 16 * nt + (lane & 15), k0 = 32 * kb + 8 * (lane >> 4);
     bf16x8_t v;
 #pragma unroll
@@ -1456,19 +890,17 @@ extern "C" int ib_mlp_chain_train(const void* x0, const void* eps, const int64_t
   p.gscale = 2.f / ((float)M * (float)D); p.ln_eps = ln_eps;
   p.prof = IB_AB_PROF(g_chain_prof);
   hipStream_t st = ib_s(stream);
-  // v2 (row-wise epilogues) is the kernel; IB_CHAIN_V1=1 selects the round-2 kernel for A/B measurements.  v2 keeps u in
-  // registers for L <= 2 (u[i] may then be NULL: nothing is stored); deeper stacks pass u through HBM as v1 does.
-  static const bool use_v1 = ib_ab_set("IB_CHAIN_V1");
+  // The kernel keeps u in registers for L <= 2 (u[i] may then be NULL: nothing is stored); deeper stacks pass u through
+  // HBM and need every u[i].
   const bool keep = L <= 2;
   for (int i = 0; i < L; ++i)
-    if (!u[i] && (use_v1 || !keep)) return IB_E_ARG;
+    if (!u[i] && !keep) return IB_E_ARG;
 #define IB_CHAIN_LAUNCH(NTH, NTD, KBD)                                                                                  \
   do {                                                                                                                  \
-    if (use_v1) hipLaunchKernelGGL((mlp_chain_kernel<NTH, NTD, KBD>), dim3(nwg), dim3(CH_THREADS), 0, st, p);           \
-    else if (keep) hipLaunchKernelGGL((mlp_chain2_kernel<NTH, NTD, KBD, true>), dim3(nwg), dim3(CH_THREADS), 0, st, p); \
+    if (keep) hipLaunchKernelGGL((mlp_chain2_kernel<NTH, NTD, KBD, true>), dim3(nwg), dim3(CH_THREADS), 0, st, p);      \
     else hipLaunchKernelGGL((mlp_chain2_kernel<NTH, NTD, KBD, false>), dim3(nwg), dim3(CH_THREADS), 0, st, p);          \
   } while (0)
-  IB_PATH(use_v1 ? IB_PATH_CHAIN1 : IB_PATH_CHAIN2);
+  IB_PATH(IB_PATH_CHAIN2);
   if (s.nth == 4 && s.ntd == 3 && s.kbd == 10) IB_CHAIN_LAUNCH(4, 3, 10);
   else if (s.nth == 4 && s.ntd == 1 && s.kbd == 2) IB_CHAIN_LAUNCH(4, 1, 2);
   else if (s.nth == 4 && s.ntd == 1 && s.kbd == 4) IB_CHAIN_LAUNCH(4, 1, 4);

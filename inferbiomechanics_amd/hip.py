@@ -2240,8 +2240,7 @@ def mlp_chain_train(x0, eps, t, sqrt_ab, sqrt_1mab, e, packed, bias, gamma, beta
     M, L = B * T, len(h)
     H = h[0].shape[1]
     u = [None] * L if u is None else list(u)
-    from ._tuning import tuning as TU
-    if any(a is None for a in u) and (L > 2 or TU.chain_v1):
+    if any(a is None for a in u) and L > 2:
         raise HipError("mlp_chain_train: u buffers are optional only for L <= 2 (pre-activations kept in registers)")
     _req(t, "t", torch.int64, 1); _req(sqrt_ab, "sqrt_ab", torch.float32, 1); _req(sqrt_1mab, "sqrt_1mab", torch.float32, 1)
     er, ec, lde = _mat(e, "e", bt)

@@ -1290,7 +1290,7 @@ class DenoiserMLPPlan:
         xt = g("ch.xt", (M, Dp), dt)[:, :D]
         dpred = g("ch.dpred", (M, Dp), dt)[:, :D]
         # the pre-activations stay in the chain kernel's registers (L <= 2); deeper stacks pass them through HBM
-        u = None if (L <= 2 and not TU.chain_v1) else [g(f"ch.u{i}", (M, H), dt) for i in range(L)]
+        u = None if L <= 2 else [g(f"ch.u{i}", (M, H), dt) for i in range(L)]
         h = [g(f"ch.h{i}", (M, H), dt) for i in range(L)]
         dz = [g(f"ch.dz{i}", (M, H), dt) for i in range(L)]
         nwg = hip.mlp_chain_workgroups(M)

@@ -156,3 +156,34 @@ def test_kernel_digests_see_instructions_descriptor_registers_and_order():
     assert name == "gemm_tn_kernel<1>"
     (_, other), = kr.kernel_digests(kr.normalise_asm(LISTING.replace("lgkmcnt(0)", "lgkmcnt(1)")))
     assert other != digest
+
+
+# a loop header's label as the compiler writes it: the comment behind it names the kernel's ordinal again, without ".L"
+def _loop_label(n, blanks):
+    return lambda t: t.replace(f".LBB{n}_2:\n", f".LBB{n}_2:{blanks}; in Loop: Header=BB{n}_1 Depth=1\n")
+
+
+def _loop_kernels(edit=lambda text: text):
+    text = _loop_label(0, "   ")(KERNEL.format(sym=STEP.format(mode=1), n=0)) + \
+        edit(_loop_label(1, "\t\t\t\t")(KERNEL.format(sym=STEP.format(mode=2), n=1))) + \
+        NOTE.format(a=STEP.format(mode=1), b=STEP.format(mode=2))
+    assert "Header=BB0_1 Depth=1" in text and "Header=BB1_1 Depth=1" in text
+    return kr.kernel_digests(kr.normalise_asm(text))
+
+
+def test_kernel_digests_ignore_trailing_comments_that_name_the_ordinal():
+    base = _loop_kernels()
+    assert base[0][1] == base[1][1]                  # ordinals 0 and 1, different blank widths before the comment
+    assert base[0][1] == _kernels(STEP.format(mode=1), STEP.format(mode=2))[0][1]      # and the same as with no comment
+
+
+def test_kernel_digests_still_see_the_code_in_front_of_a_trailing_comment():
+    base = _loop_kernels()
+    # the label itself, on the line that carries the loop comment
+    relabelled = _loop_kernels(lambda t: t.replace(".LBB1_2:\t", ".LBB1_3:\t"))
+    assert relabelled[0] == base[0] and relabelled[1][1] != base[1][1]
+    # an instruction on a line that also carries a trailing comment: the comment alone changes nothing, the instruction does
+    commented = _loop_kernels(lambda t: t.replace("s_waitcnt lgkmcnt(0)\n", "s_waitcnt lgkmcnt(0) ; 8-byte Folded Reload\n"))
+    changed = _loop_kernels(lambda t: t.replace("s_waitcnt lgkmcnt(0)\n", "s_waitcnt lgkmcnt(1) ; 8-byte Folded Reload\n"))
+    assert commented == base
+    assert changed[0] == base[0] and changed[1][1] != base[1][1]

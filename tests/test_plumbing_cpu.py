@@ -132,6 +132,34 @@ def test_chain_step_plumbing(dry):
         assert names[-1] == "ib_optim_step_sources"              # single GPU: the optimizer sums the partials itself
 
 
+def test_chain_train_u_buffers_are_optional_up_to_two_blocks_only(dry):
+    """hip.mlp_chain_train: the pre-activations stay in registers for L <= 2 (u may be None); deeper stacks need every u"""
+    B, T, D, H = 2, 13, 48, 128
+    M, bf = B * T, torch.bfloat16
+    z = lambda *shape, dtype=bf: torch.zeros(*shape, dtype=dtype)
+    assert not hasattr(TU, "chain_v1")
+    with pytest.raises(AttributeError):
+        TU.chain_v1
+
+    def call(L, u):
+        nwg = dry.mlp_chain_workgroups(M)
+        dry.lib().calls.clear()
+        dry.mlp_chain_train(z(B, T, D), z(B, T, D), z(B, dtype=torch.int64), z(1000, dtype=torch.float32),
+                            z(1000, dtype=torch.float32), z(B, L * H), z(dry.mlp_chain_packed_elems(D, H, L)),
+                            [z(H, dtype=torch.float32)] * L + [z(D, dtype=torch.float32)], [z(H, dtype=torch.float32)] * L,
+                            [z(H, dtype=torch.float32)] * L, z(M, D), u, [z(M, H) for _ in range(L)],
+                            [z(M, H) for _ in range(L)], z(M, D),
+                            z(nwg, dry.mlp_chain_partial_width(D, H, L), dtype=torch.float32), T)
+        return dry.lib().calls
+
+    assert "ib_mlp_chain_train" in call(2, None)
+    assert "ib_mlp_chain_train" in call(2, [None, z(M, H)])
+    assert "ib_mlp_chain_train" in call(3, [z(M, H) for _ in range(3)])
+    for u in (None, [z(M, H), None, z(M, H)]):
+        with pytest.raises(dry.HipError, match="u buffers are optional only for L <= 2"):
+            call(3, u)
+
+
 def test_packed_windows_roundtrip_and_reference_pickle_blocks(tmp_path):
     """the packed row reproduces the reference tuple layout exactly; file round trip (memory-mapped); the reference's
     `pickle-data` blocks (torch.save of a list of window tuples, pickle_data.py:52-64) pack to the same rows"""

@@ -7,7 +7,8 @@ Usage: python tools/kernel_resources.py [--filter SUBSTR] [--json] [file.hip ...
 text leaves every line as it was; run it on both checkouts, once per build flavour, and diff the two outputs.  A source
 given by absolute path is compiled where it lies, so one checkout's tool can digest another checkout's csrc/.
 --digest --kernels prints one line per kernel instead (kernel_digests): its short name and the sha256 of its own text, so a
-kernel that was renamed or moved to another place in its file, and is otherwise the same, keeps its line."""
+kernel that was renamed or moved to another place in its file, and is otherwise the same, keeps its line: neither its
+ordinal in the file nor the compiler's trailing comments (which repeat the ordinal on loop labels) enter the hash."""
 import argparse
 import hashlib
 import json
@@ -115,15 +116,17 @@ def kernel_digests(asm):
     """[(short name, sha256)] of the kernels of a normalised listing, in the listing's order.  A kernel's text is every line
     from the first to the last that names its symbol outside the metadata note -- its section, label and code, its
     .amdhsa_kernel descriptor and its resource .set lines -- with its own symbol replaced by "<kernel>", any other kernel's
-    by that kernel's short name, and the kernel's ordinal in the file taken out of its local labels (.LBB<n>_,
-    .Lfunc_end<n>): what remains is the instructions, the descriptor and the register counts"""
+    by that kernel's short name, the kernel's ordinal in the file taken out of its local labels (.LBB<n>_,
+    .Lfunc_end<n>), and the comment the compiler puts behind a line's code cut off with the blanks before it (on a loop's
+    label it names the ordinal again: "; in Loop: Header=BB<n>_80 Depth=1"; a line with a string in it is left whole):
+    what remains is the instructions, the descriptor and the register counts"""
     lines = asm.split(".amdgpu_metadata")[0].splitlines()
     syms = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", asm, re.M)
     names = re.compile("|".join(rf"(?<![\w$]){re.escape(s)}(?![\w$])" for s in sorted(syms, key=len, reverse=True)) or "$^")
     out = []
     for sym in syms:
         at = [i for i, l in enumerate(lines) if any(m.group() == sym for m in names.finditer(l))]
-        text = "\n".join(lines[at[0]:at[-1] + 1]) + "\n"
+        text = "\n".join(l if '"' in l else re.sub(r"\s*;.*$", "", l) for l in lines[at[0]:at[-1] + 1]) + "\n"
         n = re.search(r"^\.Lfunc_end(\d+):", text, re.M)
         if n:
             text = re.sub(rf"(\.L[A-Za-z_]+){n.group(1)}(?!\d)", r"\1", text)
