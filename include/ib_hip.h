@@ -95,8 +95,8 @@ int ib_linear_wgrad_bias(const void* dz, int64_t lddz, const void* x, int64_t ld
 
 /* y = LayerNorm(res + x W^T + bias) * gamma + beta for small token counts (the DDIM sampler): a K-split GEMM into fp32
  * slabs whose reduction kernel is the LayerNorm (TransformerBaseline.py:29-31 / 34-36: Linear -> add -> norm).  bf16,
- * N % 64 == 0, N <= 1024 (N in {64,128,256,512,1024}), K % 32 == 0, 16-byte aligned operand rows; IB_E_UNSUPPORTED
- * otherwise (use ib_linear_fwd + ib_layernorm_fwd).  a_out / mean / rstd: optional (what a backward pass needs). */
+ * N in {64,128,256,512,1024}, K % 32 == 0, 16-byte aligned operand rows; IB_E_UNSUPPORTED otherwise, with nothing
+ * launched (use ib_linear_fwd + ib_layernorm_fwd).  a_out / mean / rstd: optional (what a backward pass needs). */
 size_t ib_linear_ln_fwd_workspace(int64_t M, int64_t N, int64_t K);
 int ib_linear_ln_fwd(const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias, const void* res,
                      int64_t ldres, const float* gamma, const float* beta, void* y, int64_t ldy, void* a_out,

@@ -1729,7 +1729,9 @@ extern "C" int ib_linear_ln_fwd(const void* x, int64_t ldx, const void* w, int64
   if (!x || !w || !gamma || !beta || !y || !workspace || M <= 0 || N <= 0 || K <= 0 || ldx < K || ldw < K || ldy < N)
     return IB_E_ARG;
   if (res && ldres < N) return IB_E_ARG;
-  if (dtype != IB_BF16 || N % 64 != 0 || N > 1024 || K % 32 != 0) return IB_E_UNSUPPORTED;
+  // the widths slab_ln_kernel is instantiated for (the switch below): refused here, before anything is launched
+  const bool width_ok = N == 64 || N == 128 || N == 256 || N == 512 || N == 1024;
+  if (dtype != IB_BF16 || !width_ok || K % 32 != 0) return IB_E_UNSUPPORTED;
   int chunk;
   int split = linear_ln_split(M, N, K, &chunk);
   if (!ib_al16({workspace, gamma, beta, bias}) || !ib_aligned(y, 8) || ldy % 4 != 0 || !ib_aligned(res, 8) ||
@@ -1768,7 +1770,7 @@ extern "C" int ib_linear_ln_fwd(const void* x, int64_t ldx, const void* w, int64
   switch (N) {
     case 64: IB_SLAB_LN(16, 1); break; case 128: IB_SLAB_LN(16, 2); break; case 256: IB_SLAB_LN(64, 1); break;
     case 512: IB_SLAB_LN(64, 2); break; case 1024: IB_SLAB_LN(64, 4); break;
-    default: return IB_E_UNSUPPORTED;
+    default: return IB_E_UNSUPPORTED;          // not reached: width_ok above admits exactly these five
   }
 #undef IB_SLAB_LN
   IB_CHECK_LAUNCH();
