@@ -155,6 +155,43 @@ def checked_interval(args, num_samples: int):
     return L
 
 
+X0_CLIP_HELP = ('keep the x0 the sampler predicts at every step inside the range each label column took in the training '
+                'windows (`train --record-range`): `range` clamps it to the recorded [min, max], `dynamic` is dynamic '
+                'thresholding (Saharia et al. 2022) in units of each column\'s half range, the --x0-clip-quantile of one '
+                'window. Its effect on label accuracy of trained checkpoints is unmeasured. Default: off.')
+
+
+def add_x0_clip_flags(p, scope: str):
+    """--x0-clip {off,range,dynamic} --x0-clip-quantile P --x0-clip-margin M of analyze / visualize"""
+    p.add_argument('--x0-clip', type=str, default='off', choices=['off', 'range', 'dynamic'], help=f'[{scope}] ' + X0_CLIP_HELP)
+    p.add_argument('--x0-clip-quantile', type=float, default=0.995,
+                   help=f'[{scope}] the quantile P in (0, 1] of --x0-clip dynamic (nearest rank over one window).')
+    p.add_argument('--x0-clip-margin', type=float, default=0.0,
+                   help=f'[{scope}] widen every column\'s recorded range by M times its half width on both sides (M >= 0).')
+
+
+def checked_x0_clip(args, model):
+    """--x0-clip of analyze / visualize, once the checkpoint is loaded -> an X0Clip over the 30 label columns (the recorded
+    range of each, widened by the margin), or None when off"""
+    mode = getattr(args, 'x0_clip', 'off')
+    if mode == 'off':
+        return None
+    P, M = float(getattr(args, 'x0_clip_quantile', 0.995)), float(getattr(args, 'x0_clip_margin', 0.0))
+    if not 0.0 < P <= 1.0:
+        raise SystemExit(f"--x0-clip-quantile {P} must lie in (0, 1]")
+    if not M >= 0.0:
+        raise SystemExit(f"--x0-clip-margin {M} must be >= 0 (it widens the recorded range)")
+    r = getattr(model, 'column_range', None)
+    if r is None:
+        raise SystemExit(f"--x0-clip {mode} takes its bounds from the column ranges recorded in training: this checkpoint has "
+                         f"none (train it with `train --record-range`)")
+    from ..diffusion.sampler import X0Clip
+    from ..models.DiffusionLabelPredictor import LABEL_WIDTH
+    r = torch.as_tensor(r, dtype=torch.float64)[-LABEL_WIDTH:]
+    half = (r[:, 1] - r[:, 0]) / 2.0
+    return X0Clip((r[:, 0] - M * half).tolist(), (r[:, 1] + M * half).tolist(), mode=mode, quantile=P)
+
+
 def checked_guidance(args, model) -> float:
     """--guidance S of analyze / visualize, once the checkpoint is loaded: refused for a denoiser that never saw the null
     condition"""

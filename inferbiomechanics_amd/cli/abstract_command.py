@@ -153,6 +153,9 @@ class AbstractCommand:
             target.cond_cols = int(checkpoint.get('cond_cols', 0))
         if hasattr(target, 'cond_drop'):                     # denoisers: `train --cond-drop`
             target.cond_drop = float(checkpoint.get('cond_drop', 0.0))
+        if hasattr(target, 'column_range'):                  # denoisers: `train --record-range`
+            r = checkpoint.get('column_range')
+            target.column_range = None if r is None else torch.as_tensor(r, dtype=torch.float32).cpu()
         osd = checkpoint.get('optimizer_state_dict')
         if optimizer is not None and hasattr(optimizer, 'load_optimizer_state_dict'):      # HipTrainer
             if osd is not None:

@@ -15,8 +15,8 @@ from ..data.AddBiomechanicsDataset import LOSS_KEY_ORDER
 from ..diffusion.ensemble import calibrated_coverage
 from ..loss.RegressionLossEvaluator import RegressionLossEvaluator
 from ._common import (GUIDANCE_HELP, LABEL_NAMES, add_additive_flags, add_component_flags, add_interval_flag,
-                      add_resample_flags, checked_guidance, checked_interval, checked_resample, dtype_of, is_diffusion,
-                      open_dataset, pick_device)
+                      add_resample_flags, add_x0_clip_flags, checked_guidance, checked_interval, checked_resample,
+                      checked_x0_clip, dtype_of, is_diffusion, open_dataset, pick_device)
 from .abstract_command import AbstractCommand
 
 
@@ -62,6 +62,7 @@ class AnalyzeCommand(AbstractCommand):
         p.add_argument('--guidance', type=float, default=0.0, help='[diffusion models] ' + GUIDANCE_HELP)
         add_resample_flags(p, 'diffusion models')
         add_interval_flag(p, 'diffusion models')
+        add_x0_clip_flags(p, 'diffusion models')
         p.add_argument('--use-ema', action='store_true', default=False,
                        help='Evaluate the EMA weights of the checkpoint (`train --ema-decay`) instead of its last weights.')
 
@@ -138,7 +139,7 @@ class AnalyzeCommand(AbstractCommand):
                                                     output_data_format=args.output_data_format, eta=eta,
                                                     num_samples=num_samples, solver=solver, spacing=spacing,
                                                     guidance=checked_guidance(args, model), resample=resample,
-                                                    interval=interval)
+                                                    interval=interval, x0_clip=checked_x0_clip(args, model))
             evaluator = RegressionLossEvaluator(dataset=dataset, split=split, device=device)
             loader = DataLoader(dataset, batch_size=args.sample_batch, shuffle=False, num_workers=args.data_loading_workers)
             compute_report = bool(getattr(dataset, 'skeletons', None))

@@ -101,6 +101,11 @@ class TrainCommand(AbstractCommand):
                             'conditioning columns reach the denoiser all zero (the null condition), decided on the device per '
                             'step and window. `analyze --guidance S` / `visualize --guidance S` then sample with the guided '
                             'noise prediction. 0 = off; 0.1-0.2 are usual. Not with --eager.')
+        p.add_argument('--record-range', action='store_true', default=False,
+                       help='[diffusion, with --window-cache] Record the minimum and maximum every column takes in the '
+                            'training windows (one pass over the device-resident cache) and save them in the checkpoints; '
+                            '`analyze --x0-clip` / `visualize --x0-clip` take their bounds from there. A resumed run keeps '
+                            'the checkpoint\'s record. Default: off.')
         p.add_argument('--no-ema-warmup', action='store_true',
                        help='Use --ema-decay from the first step (default: min(decay, (1 + step) / (10 + step))).')
 
@@ -117,6 +122,7 @@ class TrainCommand(AbstractCommand):
         check_ema_args(args)
         check_cond_cols(model_type, getattr(args, 'cond_cols', 0))
         check_cond_drop(args)
+        check_record_range(args)
         if getattr(args, 'seed', None) is not None:
             torch.manual_seed(args.seed)
         geometry = self.ensure_geometry(args.geometry_folder)
@@ -251,6 +257,9 @@ class TrainCommand(AbstractCommand):
         if diffusion and model.cond_drop != cond_drop:
             raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained with --cond-drop {model.cond_drop}, this run "
                              f"asks for {cond_drop}: resume with the same value or use another --checkpoint-dir")
+        if diffusion and getattr(args, 'record_range', False) and model.column_range is None:
+            # asked for and not in the checkpoint (a resumed run keeps the checkpoint's record): one pass over the cache
+            model.column_range = cache.column_range().cpu()
         from .. import hip
         noise_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
 
@@ -423,6 +432,19 @@ def check_cond_drop(args: argparse.Namespace):
         raise SystemExit("--cond-drop needs the fused trainer: the drop is decided inside its noising launch, --eager has none")
 
 
+def check_record_range(args: argparse.Namespace):
+    """--record-range: a diffusion model type trained from the device-resident window cache, whose table the range kernel
+    reads (--window-cache; the fused trainer: --eager builds no cache)"""
+    if not getattr(args, 'record_range', False):
+        return
+    if not is_diffusion(args.model_type):
+        raise SystemExit(f"--record-range records the column ranges of a diffusion denoiser's training windows: model type "
+                         f"'{args.model_type}' has none")
+    if not getattr(args, 'window_cache', None) or getattr(args, 'eager', False):
+        raise SystemExit("--record-range reads the device-resident window cache: it needs --window-cache (`hbm` with "
+                         "--synthetic-windows, or a file) and the fused trainer (not --eager)")
+
+
 def make_torch_optimizer(opt_type: str, params, lr: float):
     table = {'adagrad': torch.optim.Adagrad, 'adam': torch.optim.Adam, 'sgd': torch.optim.SGD,
              'rmsprop': torch.optim.RMSprop, 'adadelta': torch.optim.Adadelta, 'adamax': torch.optim.Adamax}
@@ -436,7 +458,7 @@ def save_checkpoint(checkpoint_dir: str, epoch: int, batch: int, model, opt):
     """file grammar of train.py:271-278; keys are saved WITHOUT DDP's `module.` prefix.  A trainer with an EMA adds
     'ema_state_dict' (the model's state dict over the EMA weights) and 'ema' ({'decay', 'warmup'}); without one the file
     holds the three reference keys only.  A denoiser trained with --cond-cols N > 0 adds 'cond_cols': N, one trained with
-    --cond-drop P > 0 'cond_drop': P."""
+    --cond-drop P > 0 'cond_drop': P, one trained with --record-range 'column_range': fp32 [feat_dim, 2]."""
     os.makedirs(checkpoint_dir, exist_ok=True)
     path = f"{checkpoint_dir}/epoch_{epoch}_batch_{batch}.pt"
     osd = opt.optimizer_state_dict() if hasattr(opt, 'optimizer_state_dict') else opt.state_dict()
@@ -447,6 +469,8 @@ def save_checkpoint(checkpoint_dir: str, epoch: int, batch: int, model, opt):
         ckpt['cond_cols'] = int(model.cond_cols)
     if getattr(model, 'cond_drop', 0.0) > 0:
         ckpt['cond_drop'] = float(model.cond_drop)
+    if getattr(model, 'column_range', None) is not None:
+        ckpt['column_range'] = torch.as_tensor(model.column_range, dtype=torch.float32).detach().cpu().clone()
     if getattr(opt, 'ema', None) is not None:
         ckpt['ema_state_dict'] = opt.ema_state_dict()
         ckpt['ema'] = {'decay': opt.ema_decay, 'warmup': opt.ema_warmup}

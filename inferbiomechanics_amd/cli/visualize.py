@@ -21,8 +21,8 @@ from ..loss.RegressionLossEvaluator import RegressionLossEvaluator
 from ..data.AddBiomechanicsDataset import LOSS_KEY_ORDER
 from ..diffusion.schedule import STITCH_BLENDS, stitch_layout
 from ._common import (GUIDANCE_HELP, LABEL_NAMES, add_additive_flags, add_component_flags, add_interval_flag,
-                      add_resample_flags, checked_guidance, checked_interval, checked_resample, dtype_of, is_diffusion,
-                      open_dataset, pick_device)
+                      add_resample_flags, add_x0_clip_flags, checked_guidance, checked_interval, checked_resample,
+                      checked_x0_clip, dtype_of, is_diffusion, open_dataset, pick_device)
 from .abstract_command import AbstractCommand
 from .analyze import window_subject, window_trial
 
@@ -74,6 +74,7 @@ class VisualizeCommand(AbstractCommand):
         p.add_argument('--guidance', type=float, default=0.0, help='[--trial-frames] ' + GUIDANCE_HELP)
         add_resample_flags(p, '--trial-frames')
         add_interval_flag(p, '--trial-frames')
+        add_x0_clip_flags(p, '--trial-frames')
         p.add_argument('--sample-spacing', type=str, default='time', choices=['time', 'logsnr'],
                        help='[--trial-frames] sampling grid of both loops: uniform in the timestep, or uniform in log-SNR '
                             '(the grid for few-step dpmpp2m / dpmpp2m_sde sampling).')
@@ -158,7 +159,8 @@ class VisualizeCommand(AbstractCommand):
         predictor = DiffusionLabelPredictor(model, args.sample_steps, seed=args.sample_seed,
                                             output_data_format=args.output_data_format, eta=eta, num_samples=num_samples,
                                             solver=solver, spacing=getattr(args, 'sample_spacing', 'time'),
-                                            guidance=checked_guidance(args, model), resample=resample, interval=interval)
+                                            guidance=checked_guidance(args, model), resample=resample, interval=interval,
+                                            x0_clip=checked_x0_clip(args, model))
         gather = start.long()[:, None] + torch.arange(T)[None, :]      # [Wd, T] trial frames of the disjoint windows
         w0 = cover[:, 0].long()
         t0 = torch.arange(F) - start.long()[w0]

@@ -282,6 +282,12 @@ class DeviceMotionCache:
     def __len__(self) -> int:
         return self.table.shape[0]
 
+    def column_range(self) -> torch.Tensor:
+        """fp32 [D, 2] on the device: the (minimum, maximum) every column takes over all frames of all windows, exact
+        (hip.column_range, csrc/clip.hip); the pad behind a window's T * D values is not read"""
+        from .. import hip
+        return hip.column_range(self.table, self.window, self.feat)
+
     def batches(self, batch_size: int, rank: int = 0, world: int = 1, drop_last: bool = True,
                 shuffle_seed: Optional[int] = None) -> Iterator[torch.Tensor]:
         return sharded_batches(len(self), self.device, batch_size, rank, world, drop_last, shuffle_seed)

@@ -52,7 +52,20 @@ the jump table, the ids, the one-window layout -- is passed at every call and is
 signature, so the setting may change between calls on one capture.  Off (None, or times = 1) nothing of it exists.  One
 exception to "changes no step": a resampled loop over ONE-WINDOW trials (F == T) updates with the per-window entry
 (ib_ddim_cond_step; _one_window_step), which makes it ConditionalDDIMSampler(resample=...) bit for bit at every row pitch;
-that choice is part of the signature, so there the step is captured again when the setting goes on or off."""
+that choice is part of the signature, so there the step is captured again when the setting goes on or off.
+
+The x0 clip (x0_clip = X0Clip(lo, hi, mode, quantile); all four classes) changes none of those rows either: like guidance it
+is a seam around them, one launch in _step_launches between the denoiser's forward and the row's update launch (in the
+guided step after ib_cfg_combine, over the first half), and nowhere else.  Every step reconstructs the data prediction
+x0 = (x_t - sigma_t eps) / alpha_t; the launch keeps it inside per-column bounds -- 'range': clamped to [lo_c, hi_c]
+(ib_x0_clip_range); 'dynamic': dynamic thresholding (Saharia et al. 2022) in per-column units, the `quantile` of |u|,
+u = (x0 - centre_c) / half_width_c, taken over the free bounded elements of ONE [T, ld] window (ib_x0_clip_dynamic) -- and
+rewrites eps to the prediction that reconstructs the clipped x0, nothing else, so every update row, eta, observations,
+layouts, resampling and the second-order solvers' history follow by themselves.  In the stitched samplers a window is each
+overlapping window on its own, before the update kernel blends the predictions.  Observed elements (the mask), columns
+without finite bounds hi > lo and pad columns are never counted and never changed.  With None no buffer, launch or
+signature entry exists: the loop is the unclipped one bit for bit and launch for launch.  What the clip does to label
+accuracy on trained checkpoints is unmeasured."""
 from dataclasses import dataclass
 from typing import Optional, Sequence, Union
 
@@ -60,7 +73,32 @@ import torch
 
 from .. import hip
 from ..plans import ParamSource
-from .schedule import OBSERVATIONS, check_resample, check_sampler_settings, resample_walk, stitch_layout
+from .schedule import (CLIP_MODES, OBSERVATIONS, check_resample, check_sampler_settings, clip_rank, clip_tables,
+                       resample_walk, stitch_layout)
+
+
+@dataclass(frozen=True)
+class X0Clip:
+    """The x0 clip of a sampling loop (the module docstring): bounds lo[D] <= hi[D] per column of the window row (-inf /
+    +inf: no bound; a column with lo == hi is not bounded either), mode 'range' or 'dynamic', and the quantile in (0, 1] of
+    'dynamic' (nearest rank over one window's free bounded elements, schedule.clip_rank; unused by 'range').  Frozen and
+    hashable: the bounds are kept as tuples of floats."""
+    lo: tuple
+    hi: tuple
+    mode: str = "range"
+    quantile: float = 0.995
+
+    def __post_init__(self):
+        lo = tuple(float(v) for v in torch.as_tensor(self.lo, dtype=torch.float64).reshape(-1).tolist())
+        hi = tuple(float(v) for v in torch.as_tensor(self.hi, dtype=torch.float64).reshape(-1).tolist())
+        clip_tables(lo, hi)                                            # the refusals of the bounds
+        if self.mode not in CLIP_MODES:
+            raise ValueError(f"X0Clip: mode must be one of {CLIP_MODES}, got {self.mode!r}")
+        if not 0.0 < float(self.quantile) <= 1.0:
+            raise ValueError(f"X0Clip: quantile must be in (0, 1], got {self.quantile}")
+        object.__setattr__(self, "lo", lo)
+        object.__setattr__(self, "hi", hi)
+        object.__setattr__(self, "quantile", float(self.quantile))
 
 
 @dataclass(frozen=True)
@@ -107,11 +145,17 @@ def _join(lay: dict, windows: torch.Tensor, N: int) -> torch.Tensor:
 
 class DDIMSampler:
     def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True, eta: float = 0.0,
-                 seed: Optional[int] = None, solver: str = "ddim", spacing: str = "time"):
+                 seed: Optional[int] = None, solver: str = "ddim", spacing: str = "time",
+                 x0_clip: Optional[X0Clip] = None):
         """eta in [0, 1]; seed (default: torch's initial seed) keys the step noise of an eta > 0 loop; solver 'ddim',
         'dpmpp2m' (deterministic: eta = 0 only) or 'dpmpp2m_sde' (its stochastic form; eta = 0 runs 'dpmpp2m'); spacing
-        'time' or 'logsnr', the sampling grid"""
+        'time' or 'logsnr', the sampling grid; x0_clip: an X0Clip keeps every step's predicted x0 inside per-column bounds
+        (the module docstring), None (the default) is the loop without it"""
         check_sampler_settings(eta, solver, spacing)
+        if x0_clip is not None and not isinstance(x0_clip, X0Clip):
+            raise ValueError(f"x0_clip must be None or an X0Clip, got {type(x0_clip).__name__}")
+        self.x0_clip = x0_clip
+        self._clip_n = None                  # (mask, (version, T, bounds), n) of the last count of free bounded elements
         self.model, self.S = model, num_sample_steps
         self.eta = float(eta)
         self.solver, self.spacing = solver, spacing
@@ -276,6 +320,10 @@ class DDIMSampler:
             sig += (self.eta, self.seed, ptr(tabs.ddim_coef_eta), ptr(tabs.obs_noise_coef))
         else:
             sig += (0.0,)
+        clip = self._clip_call(c, tabs)
+        if clip is not None:
+            # the launch bakes in the mode, the rank (a function of the call's mask and the bounds) and the tables' addresses
+            sig += ("x0_clip", self.x0_clip.mode, clip["k"]) + tuple(ptr(clip[n]) for n in ("coef", "lo", "hi", "m", "h", "ih"))
         guided = self._guided(c)
         if guided:
             # the seam's launches bake in the strength, the conditioning width and xin's address.  xin belongs to the
@@ -308,6 +356,46 @@ class DDIMSampler:
         if sde:
             bufs["one_window"] = tuple(t.to(dev) for t in stitch_layout(T, T, T)[:3])
         self._sig, self._graph, self._bufs = sig, None, bufs
+
+    def _clip_call(self, c: SampleCall, tabs):
+        """None without x0_clip; else the clip's tables for this call (DiffusionTables.set_clip, made when the bounds or the
+        grid changed) with 'k': the rank of the 'dynamic' quantile among the n free bounded elements of one window, which
+        depends on the call's mask and the bounds alone (0 when n == 0: nothing is launched).  The count is kept per mask
+        tensor and version, so a loop that passes the same mask again does not wait for the device."""
+        q = self.x0_clip
+        if q is None:
+            return None
+        if len(q.lo) != c.D:
+            raise ValueError(f"x0_clip: the bounds hold {len(q.lo)} columns, a window row has D = {c.D}")
+        if not tabs.clip_serves(self.S, self.spacing, q.lo, q.hi):
+            tabs.set_clip(q.lo, q.hi)
+        clip = tabs.clip
+        key = (None if c.mask is None else c.mask._version, c.T, clip["key"])
+        kept = self._clip_n
+        if kept is None or kept[0] is not c.mask or kept[1] != key:
+            bounded = clip["bounded"]
+            if c.mask is None:
+                n = c.T * int(bounded.sum())
+            else:
+                free = (c.mask.to(device="cpu") == 0).sum(dim=0)          # [D] free frames per column
+                n = int(free[bounded].sum())
+            kept = self._clip_n = (c.mask, key, n)
+        n = kept[2]
+        return dict(clip, n=n, k=clip_rank(q.quantile, n) if n else 0)
+
+    def _launch_clip(self, c: SampleCall, x, eps, ctr, tabs):
+        """the x0 clip's one launch of a step, over the B windows of x / eps as [B, T, ld]; nothing without x0_clip or when no
+        element is both free and bounded"""
+        clip = self._clip_call(c, tabs)
+        if clip is None or clip["n"] == 0:
+            return
+        mask = self._bufs.get("mask") if c.observed is not None else None
+        x3, e3 = x.view(c.B, c.T, -1), eps.view(c.B, c.T, -1)
+        if self.x0_clip.mode == "range":
+            hip.x0_clip_range(x3, e3, mask, clip["lo"], clip["hi"], clip["coef"], step_dev=ctr, D=c.D)
+        else:
+            hip.x0_clip_dynamic(x3, e3, mask, clip["lo"], clip["hi"], clip["coef"], clip["m"], clip["h"], clip["ih"], clip["k"],
+                                step_dev=ctr, D=c.D)
 
     def _start_masked(self, c: SampleCall, x, tabs):
         """the masked loop's start state, once x holds the start draw: the observation, the mask and the draw z go into
@@ -436,6 +524,7 @@ class DDIMSampler:
             plan.forward(xin.view(B2 * T, Dp)[:, :c.D], t_vec, tabs.temb, P, out=eps_buf.view(B2 * T, Dp)[:, :c.D],
                          BT=(B2, T))
             hip.cfg_combine(eps_buf, self.guidance)
+            self._launch_clip(c, x, eps_buf[:c.B], ctr, tabs)
             self._launch_update(c, x, eps_buf[:c.B], ctr, t_vec[:c.B], tabs)
             hip.cfg_mirror(xin, t_vec, int(self.model.cond_cols), D=c.D)
         elif eps_buf is not None:
@@ -443,9 +532,12 @@ class DDIMSampler:
             # 2-D views; the DDIM update runs over the whole pitched buffers (0 stays 0 in the pad columns)
             B, T, Dp = x.shape
             plan.forward(x.view(B * T, Dp)[:, :c.D], t_vec, tabs.temb, P, out=eps_buf.view(B * T, Dp)[:, :c.D], BT=(B, T))
+            self._launch_clip(c, x, eps_buf, ctr, tabs)
             self._launch_update(c, x, eps_buf, ctr, t_vec, tabs)
         else:
-            self._launch_update(c, x, plan.forward(x, t_vec, tabs.temb, P), ctr, t_vec, tabs)
+            eps = plan.forward(x, t_vec, tabs.temb, P)
+            self._launch_clip(c, x, eps, ctr, tabs)
+            self._launch_update(c, x, eps, ctr, t_vec, tabs)
         hip.counter_add(ctr, 1)
 
     def _one_window_step(self, c: SampleCall) -> bool:
@@ -515,9 +607,9 @@ class ConditionalDDIMSampler(DDIMSampler):
 
     def __init__(self, model, num_sample_steps: int = 100, use_graph: bool = True, eta: float = 0.0,
                  seed: Optional[int] = None, solver: str = "ddim", spacing: str = "time", observations: str = "noised",
-                 guidance: float = 0.0, resample=None):
+                 guidance: float = 0.0, resample=None, x0_clip: Optional[X0Clip] = None):
         check_sampler_settings(eta, solver, spacing, observations)
-        super().__init__(model, num_sample_steps, use_graph, eta, seed, solver, spacing)
+        super().__init__(model, num_sample_steps, use_graph, eta, seed, solver, spacing, x0_clip=x0_clip)
         self.observations = observations
         self._check_guidance(guidance, observations)
         self.resample = resample
@@ -570,12 +662,13 @@ class StitchedDDIMSampler(DDIMSampler):
 
     def __init__(self, model, num_sample_steps: int = 100, hop: Optional[int] = None, blend: str = "ramp",
                  use_graph: bool = True, solver: str = "ddim", spacing: str = "time", observations: str = "noised",
-                 seed: Optional[int] = None, eta: float = 0.0, guidance: float = 0.0, resample=None):
+                 seed: Optional[int] = None, eta: float = 0.0, guidance: float = 0.0, resample=None,
+                 x0_clip: Optional[X0Clip] = None):
         if float(eta) != 0.0:
             raise ValueError(f"StitchedDDIMSampler is deterministic: eta must be 0, got {eta} (the step noise of an eta > 0 "
                              f"loop is keyed by window and in-window frame, not by trial frame)")
         check_sampler_settings(0.0, solver, spacing, observations)
-        super().__init__(model, num_sample_steps, use_graph, 0.0, seed, solver, spacing)
+        super().__init__(model, num_sample_steps, use_graph, 0.0, seed, solver, spacing, x0_clip=x0_clip)
         self.observations = observations
         self._check_guidance(guidance, observations)
         if getattr(model, "window", None) is None:
@@ -673,12 +766,13 @@ class StochasticStitchedSampler(StitchedDDIMSampler):
     def __init__(self, model, num_sample_steps: int = 100, eta: float = 1.0, hop: Optional[int] = None, blend: str = "ramp",
                  use_graph: bool = True, spacing: str = "time", observations: str = "noised", seed: Optional[int] = None,
                  guidance: float = 0.0, **keywords):
-        """keywords: solver = 'ddim' (the default) or 'dpmpp2m_sde', and resample = (jump, times) (eta = 0 and 'ddim' only:
-        RePaint resampling, ConditionalDDIMSampler's), by keyword only.  `solver` is not a named parameter:
+        """keywords: solver = 'ddim' (the default) or 'dpmpp2m_sde', resample = (jump, times) (eta = 0 and 'ddim' only:
+        RePaint resampling, ConditionalDDIMSampler's) and x0_clip = X0Clip(...) (the module docstring), by keyword only.  `solver` is not a named parameter:
         tests/test_stitch_noise_plumbing_cpu.py pins that this signature names no `solver`, from when the class had one
         solver; a misspelt keyword is still a TypeError"""
         solver = keywords.pop("solver", "ddim")
         resample = keywords.pop("resample", None)
+        x0_clip = keywords.pop("x0_clip", None)
         if keywords:
             raise TypeError(f"StochasticStitchedSampler: unexpected keyword arguments {sorted(keywords)}")
         if solver == "dpmpp2m":
@@ -688,7 +782,7 @@ class StochasticStitchedSampler(StitchedDDIMSampler):
             raise ValueError(f"solver must be 'ddim' or 'dpmpp2m_sde', got {solver!r}")
         check_sampler_settings(eta, solver, spacing, observations)
         super().__init__(model, num_sample_steps, hop, blend, use_graph, solver, spacing, observations, seed,
-                         guidance=guidance)
+                         guidance=guidance, x0_clip=x0_clip)
         self.eta = float(eta)                # the parent's constructor hands DDIMSampler eta = 0
         self.resample = resample
         self._resampling()

@@ -347,6 +347,50 @@ def resample_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 1
     return out
 
 
+CLIP_MODES = ("range", "dynamic")
+
+
+def x0_coefficients(num_train_steps: int = 1000, num_sample_steps: int = 100, spacing: str = "time") -> torch.Tensor:
+    """[S, 4] float64 (ia, sa, a, is) of the x0 clip (csrc/clip.hip), row s at the level of sampling timestep t_s:
+    ia = 1 / sqrt(ab), sa = sqrt(1 - ab) / sqrt(ab), a = sqrt(ab), is = 1 / sqrt(1 - ab).  The data prediction of a step is
+    x0 = ia x - sa eps, and the noise prediction that reconstructs a clipped x0c is (x - a x0c) is."""
+    ab = alphas_cumprod(num_train_steps)
+    ts = sample_timesteps(num_train_steps, num_sample_steps, spacing)
+    a = torch.sqrt(ab[ts])
+    s = torch.sqrt(1.0 - ab[ts])
+    return torch.stack([1.0 / a, s / a, a, 1.0 / s], dim=1)
+
+
+def clip_tables(lo, hi):
+    """the per-column tables of the x0 clip from bounds lo[D] <= hi[D] -> (m, h, ih, bounded), float64 [D] and bool [D]:
+    the centre (lo + hi) / 2, the half width (hi - lo) / 2 and its reciprocal.  A column is bounded iff both bounds are finite
+    and hi > lo; any other column is never counted and never changed (+-inf is the way to say 'no bound'), and its m, h, ih
+    are never read.  A NaN bound, lo > hi or lengths that differ are a ValueError."""
+    lo = torch.as_tensor(lo, dtype=torch.float64).reshape(-1)
+    hi = torch.as_tensor(hi, dtype=torch.float64).reshape(-1)
+    if lo.numel() != hi.numel() or lo.numel() == 0:
+        raise ValueError(f"clip bounds: lo and hi must have one value per column each, got {lo.numel()} and {hi.numel()}")
+    if bool(torch.isnan(lo).any()) or bool(torch.isnan(hi).any()):
+        raise ValueError("clip bounds: NaN is no bound (use -inf / +inf for 'no bound')")
+    if bool((lo > hi).any()):
+        c = int(torch.nonzero(lo > hi)[0])
+        raise ValueError(f"clip bounds: lo > hi in column {c} ({float(lo[c])} > {float(hi[c])})")
+    bounded = torch.isfinite(lo) & torch.isfinite(hi) & (hi > lo)
+    safe_lo, safe_hi = torch.where(bounded, lo, torch.zeros_like(lo)), torch.where(bounded, hi, torch.ones_like(hi))
+    m, h = (safe_lo + safe_hi) / 2.0, (safe_hi - safe_lo) / 2.0
+    return m, h, 1.0 / h, bounded
+
+
+def clip_rank(p: float, n: int) -> int:
+    """the nearest-rank position of the quantile p in (0, 1] among n values: k = min(n, max(1, ceil(p n))), 1-based"""
+    p, n = float(p), int(n)
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"the clip quantile must be in (0, 1], got {p}")
+    if n < 1:
+        raise ValueError(f"clip_rank: n = {n} values have no order statistic")
+    return min(n, max(1, math.ceil(p * n)))
+
+
 STITCH_KMAX = 8                 # IB_STITCH_KMAX (include/ib_hip_stitch.h): the most windows that may cover one trial frame
 STITCH_BLENDS = ("uniform", "ramp")
 
@@ -452,6 +496,32 @@ class DiffusionTables:
         coef = resample_coefficients(self.num_train_steps, self.num_sample_steps, jump, self.spacing)   # raises first
         self.resample_jump = jump
         self.resample_coef = coef.to(torch.float32).to(self.sqrt_ab.device).contiguous()
+
+    clip = None                              # the x0 clip's tables (set_clip), None until a clipped loop asks for them
+
+    def set_clip(self, lo, hi):
+        """the tables of the x0 clip on the current grid (csrc/clip.hip), each computed in float64 and cast once: `clip` =
+        {'coef': x0_coefficients [S, 4], 'lo', 'hi', 'm', 'h', 'ih': fp32 [D] on the device, 'bounded': bool [D] on the host,
+        decided on the CAST bounds, which are what the kernels test, 'key': what clip_serves compares}.  lo = hi = None drops
+        them.  No other table is touched: set_sampler and what it makes stay as they are, and a new grid is noticed by
+        clip_serves, not here."""
+        if lo is None and hi is None:
+            self.clip = None
+            return
+        m, h, ih, _ = clip_tables(lo, hi)                                  # raises before anything is replaced
+        lo64 = torch.as_tensor(lo, dtype=torch.float64).reshape(-1)
+        hi64 = torch.as_tensor(hi, dtype=torch.float64).reshape(-1)
+        coef = x0_coefficients(self.num_train_steps, self.num_sample_steps, self.spacing)
+        dev = self.sqrt_ab.device
+        up = lambda t: t.to(torch.float32).to(dev).contiguous()
+        lo32, hi32 = lo64.to(torch.float32), hi64.to(torch.float32)
+        self.clip = {"coef": up(coef), "lo": up(lo64), "hi": up(hi64), "m": up(m), "h": up(h), "ih": up(ih),
+                     "bounded": torch.isfinite(lo32) & torch.isfinite(hi32) & (hi32 > lo32),
+                     "key": (self.num_sample_steps, self.spacing, tuple(lo64.tolist()), tuple(hi64.tolist()))}
+
+    def clip_serves(self, num_sample_steps: int, spacing: str, lo, hi) -> bool:
+        """whether `clip` holds the tables of these bounds (tuples of floats) on this grid"""
+        return self.clip is not None and self.clip["key"] == (num_sample_steps, spacing, tuple(lo), tuple(hi))
 
     def serves(self, num_sample_steps: int, eta: float = 0.0, solver: str = "ddim", spacing: str = "time",
                observations: Optional[str] = None, resample_jump: int = 0) -> bool:

@@ -12,8 +12,9 @@ sampler updates (csrc/stitch.hip) are declared in a second header, ``include/ib_
 (``_HEAD_SIGS``), the stochastic second-order sampler update (csrc/sde.hip) in a fourth, ``include/ib_hip_sde.h``
 (``_SDE_SIGS``), classifier-free guidance (csrc/cfg.hip) in a fifth, ``include/ib_hip_cfg.h`` (``_CFG_SIGS``), the jump of a
 resampled masked loop (csrc/resample.hip) in a sixth, ``include/ib_hip_resample.h`` (``_RESAMPLE_SIGS``), the order statistics
-of a posterior ensemble (csrc/ensemble.hip) in a seventh, ``include/ib_hip_ensemble.h`` (``_ENSEMBLE_SIGS``); a name may be
-declared once in the seven.
+of a posterior ensemble (csrc/ensemble.hip) in a seventh, ``include/ib_hip_ensemble.h`` (``_ENSEMBLE_SIGS``), the x0 clip of a
+sampling step and the per-column range of a window table (csrc/clip.hip) in an eighth, ``include/ib_hip_clip.h``
+(``_CLIP_SIGS``); a name may be declared once in the eight.
 """
 from __future__ import annotations
 
@@ -37,6 +38,7 @@ SDE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sde.h"
 CFG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_cfg.h")
 RESAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_resample.h")
 ENSEMBLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_ensemble.h")
+CLIP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_clip.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -105,7 +107,8 @@ _SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS, _CFG_SIGS, _RESAMPLE_SIGS = (
     (HEADER_PATH, STITCH_HEADER_PATH, HEAD_HEADER_PATH, SDE_HEADER_PATH, CFG_HEADER_PATH, RESAMPLE_HEADER_PATH))
 _TABLES = (_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS, _CFG_SIGS, _RESAMPLE_SIGS)   # the training step's and the samplers'
 _ENSEMBLE_SIGS = _parse_header(_read_header(ENSEMBLE_HEADER_PATH))                  # what is done with the samples
-_HEADERS = _TABLES + (_ENSEMBLE_SIGS,)
+_CLIP_SIGS = _parse_header(_read_header(CLIP_HEADER_PATH))                          # a seam of the sampling step, off by default
+_HEADERS = _TABLES + (_ENSEMBLE_SIGS, _CLIP_SIGS)
 _ALL_SIGS = {_n: _v for _t in _HEADERS for _n, _v in _t.items()}  # every entry point: what _sig() looks up and lib() binds
 if len(_ALL_SIGS) != sum(len(_t) for _t in _HEADERS):
     _twice = sorted(n for n in _ALL_SIGS if sum(n in _t for _t in _HEADERS) > 1)
@@ -151,6 +154,11 @@ def resample_symbols() -> List[str]:
 def ensemble_symbols() -> List[str]:
     """Every function include/ib_hip_ensemble.h declares"""
     return sorted(_ENSEMBLE_SIGS)
+
+
+def clip_decls() -> List[str]:
+    """Every function include/ib_hip_clip.h declares"""
+    return sorted(_CLIP_SIGS)
 
 
 def _sig(name: str):
@@ -2650,6 +2658,78 @@ def resample_renoise(x, x0, z, mask, coef, obs_coef, timesteps, start, cover, tr
                                      _ptr(trial_ids), int(seed) & 0xFFFFFFFFFFFFFFFF, N, W, T, F, D, ld,
                                      dtype_code(x.dtype), stream_ptr()), "ib_resample_renoise")
     return x
+
+
+def _clip_operands(what, x, eps, mask, lo, hi, coef, step_dev, D, columns=()):
+    """the operands both x0 clips share: the state x [B, T, ld] (read) and the noise prediction eps like it (rewritten), mask
+    uint8 [T, ld] or None, lo / hi and every tensor of `columns` fp32 [D], coef fp32 [S, 4] -> (B, T, D, ld, S)"""
+    B, T, D, ld = _pitched_state(what, x, D)
+    _like_x(what, "eps", eps, x)
+    if mask is not None:
+        _req(mask, "mask", torch.uint8, 2)
+        if tuple(mask.shape) != (T, ld) or not mask.is_contiguous():
+            raise HipError(f"{what}: mask must be contiguous uint8 [T, ld] = [{T}, {ld}], got {tuple(mask.shape)}")
+    for name, t in (("lo", lo), ("hi", hi)) + tuple(columns):
+        _req(t, name, torch.float32, 1)
+        if t.numel() != D or not t.is_contiguous():
+            raise HipError(f"{what}: {name} must be contiguous fp32 [D] = [{D}], got {tuple(t.shape)}")
+    _req(coef, "coef", torch.float32, 2)
+    if coef.shape[0] < 1 or coef.shape[1] != 4 or not coef.is_contiguous():
+        raise HipError(f"{what}: coef must be contiguous [S, 4] fp32 (schedule.x0_coefficients), got {tuple(coef.shape)}")
+    if step_dev is not None:
+        _req(step_dev, "step_dev", torch.int32)
+    return B, T, D, ld, coef.shape[0]
+
+
+def x0_clip_range(x, eps, mask, lo, hi, coef, step=0, step_dev=None, D=None):
+    """the predicted x0 of a sampling step clipped to per-column bounds, in place over eps (csrc/clip.hip): with row
+    s = *step_dev (or `step`) of coef [S, 4] = (ia, sa, a, is) (schedule.x0_coefficients), x0 = ia x - sa eps of every free
+    element (mask [T, ld] == 0, or mask None) of a bounded column (lo[c], hi[c] finite, hi[c] > lo[c]) is clamped to
+    [lo[c], hi[c]], and where that changed it eps becomes (x - a x0c) is.  Every other element of eps, pad columns
+    D <= c < ld included, keeps its bits.  x is only read."""
+    B, T, D, ld, S = _clip_operands("x0_clip_range", x, eps, mask, lo, hi, coef, step_dev, D)
+    _check(lib().ib_x0_clip_range(_ptr(x), _ptr(eps), _ptr(mask), _ptr(lo), _ptr(hi), _ptr(coef), S, int(step),
+                                  _ptr(step_dev), B, T, D, ld, dtype_code(x.dtype), stream_ptr()), "ib_x0_clip_range")
+    return eps
+
+
+def x0_clip_dynamic(x, eps, mask, lo, hi, coef, m, h, ih, k: int, step=0, step_dev=None, D=None):
+    """dynamic thresholding of the predicted x0 per window, in per-column units, in place over eps (csrc/clip.hip): with
+    u = (x0 - m[c]) ih[c] (schedule.clip_tables) and q the k-th smallest |u| among the free bounded elements of ONE window
+    [T, ld] (k from schedule.clip_rank; selected exactly), sw = max(q, 1), u is clamped to [-sw, sw] and divided by sw, and
+    x0c = h[c] uc + m[c] where that changed u.  Operands and what is left untouched as in x0_clip_range."""
+    B, T, D, ld, S = _clip_operands("x0_clip_dynamic", x, eps, mask, lo, hi, coef, step_dev, D,
+                                    (("m", m), ("h", h), ("ih", ih)))
+    k = int(k)
+    if not 1 <= k <= T * D:
+        raise HipError(f"x0_clip_dynamic: k = {k} must be in 1 .. T D = {T * D}")
+    _check(lib().ib_x0_clip_dynamic(_ptr(x), _ptr(eps), _ptr(mask), _ptr(lo), _ptr(hi), _ptr(coef), S, int(step),
+                                    _ptr(step_dev), _ptr(m), _ptr(h), _ptr(ih), k, B, T, D, ld, dtype_code(x.dtype),
+                                    stream_ptr()), "ib_x0_clip_dynamic")
+    return eps
+
+
+def column_range(table, window: int, feat: int, out=None):
+    """out fp32 [D, 2] = (minimum, maximum) of every column over the windows of a window table [N, pitch] (fp32 / bf16,
+    contiguous; window n holds `window` = T contiguous rows of `feat` = D values, pitch >= T D, the pad is not read) --
+    DeviceMotionCache.table (csrc/clip.hip: two launches, plain comparisons, exact)."""
+    what = "column_range"
+    _req(table, "table", None, 2)
+    T, D = int(window), int(feat)
+    N, pitch = (int(v) for v in table.shape)
+    if not table.is_contiguous() or N < 1 or T < 1 or D < 1 or pitch < T * D:
+        raise HipError(f"{what}: table must be contiguous [N, pitch] with N >= 1 and pitch >= T D = {T * D}, got "
+                       f"{tuple(table.shape)}")
+    if out is None:
+        out = torch.empty((D, 2), dtype=torch.float32, device=table.device)
+    _req(out, "out", torch.float32, 2)
+    if tuple(out.shape) != (D, 2) or not out.is_contiguous():
+        raise HipError(f"{what}: out must be contiguous fp32 [D, 2] = [{D}, 2]")
+    G = max(1, min(1024, (N * T + 63) // 64))                              # at least 64 rows per workgroup
+    partial = torch.empty((G, D, 2), dtype=torch.float32, device=table.device)
+    _check(lib().ib_column_range(_ptr(table), N, T, D, pitch, _ptr(partial), G, _ptr(out), dtype_code(table.dtype),
+                                 stream_ptr()), "ib_column_range")
+    return out
 
 
 def ensemble_stats(x, mean=None, std=None):

@@ -13,7 +13,7 @@ import torch
 from .. import hip
 from ..data.AddBiomechanicsDataset import INPUT_KEY_ORDER, LOSS_KEY_ORDER, LOSS_KEY_WIDTHS, MotionWindowView
 from ..diffusion.ensemble import interval_levels
-from ..diffusion.sampler import ConditionalDDIMSampler, StitchedDDIMSampler, StochasticStitchedSampler
+from ..diffusion.sampler import ConditionalDDIMSampler, StitchedDDIMSampler, StochasticStitchedSampler, X0Clip
 
 LABEL_WIDTH = sum(LOSS_KEY_WIDTHS)          # 30: the label block at the end of every frame's row
 
@@ -50,11 +50,16 @@ class DiffusionLabelPredictor:
     four-key layout of ``last_std`` -- the Weibull (type 6) quantiles at (1 - L) / 2, 0.5, (1 + L) / 2
     (diffusion/ensemble.py) -- and, for a call that is given labels, ``last_crps`` (fair ensemble CRPS per element),
     ``last_rank`` (members below the label, 0 .. K) and ``last_inside`` (label inside [lo, hi]), the last two uint8.  The
-    outputs and ``last_std`` do not change by a bit.  With the default None nothing is launched and all four stay None."""
+    outputs and ``last_std`` do not change by a bit.  With the default None nothing is launched and all four stay None.
+    x0_clip = X0Clip(lo, hi, mode, quantile) (diffusion/sampler.py) keeps the x0 every step predicts inside per-column
+    bounds in every sampler the predictor builds; the bounds are given for the 30 label columns (they are then infinite on
+    the columns in front of them) or for all feat_dim columns -- the observed columns are skipped by the mask anyway.  What
+    it does to label accuracy on trained checkpoints is unmeasured."""
 
     def __init__(self, model, num_sample_steps: int = 100, seed: int = 0, output_data_format: str = 'all_frames',
                  use_graph: bool = True, eta: float = 0.0, num_samples: int = 1, solver: str = 'ddim',
-                 spacing: str = 'time', guidance: float = 0.0, resample=None, interval: Optional[float] = None):
+                 spacing: str = 'time', guidance: float = 0.0, resample=None, interval: Optional[float] = None,
+                 x0_clip: Optional[X0Clip] = None):
         if output_data_format != 'all_frames':
             raise ValueError("DiffusionLabelPredictor: the diffusion models need --output-data-format all_frames")
         if not 0.0 <= float(eta) <= 1.0:
@@ -75,14 +80,32 @@ class DiffusionLabelPredictor:
         self.eta, self.num_samples = float(eta), int(num_samples)
         self.last_std: Optional[Dict[str, torch.Tensor]] = None
         self.guidance = float(guidance)
+        self.x0_clip = self._wide_clip(x0_clip, int(getattr(model, 'feat_dim', 0)))
         # `observations` is set again by every call (_checks); a guided sampler is built for the only kind it takes
         self.sampler = ConditionalDDIMSampler(model, num_sample_steps, use_graph=use_graph, eta=self.eta, seed=self.seed,
                                               solver=solver, spacing=spacing, guidance=self.guidance,
-                                              observations='clean' if self.guidance != 0.0 else 'noised', resample=resample)
+                                              observations='clean' if self.guidance != 0.0 else 'noised', resample=resample,
+                                              x0_clip=self.x0_clip)
         self.resample = self.sampler._resampling()       # (jump, times), or None for the plain loop
         self._mask = None                    # label_mask of the last (F, D): one tensor, so the sampler checks it once
         self._trial = None                   # ((hop, blend), StitchedDDIMSampler, mask_cols) of the last predict_trial
         self._trial_ens = None               # the same of the last predict_trial_ensemble, a StochasticStitchedSampler
+
+    @staticmethod
+    def _wide_clip(x0_clip: Optional[X0Clip], feat: int) -> Optional[X0Clip]:
+        """the clip over all `feat` columns: bounds given for the 30 label columns get -inf / +inf in front of them"""
+        if x0_clip is None:
+            return None
+        if not isinstance(x0_clip, X0Clip):
+            raise ValueError(f"DiffusionLabelPredictor: x0_clip must be None or an X0Clip, got {type(x0_clip).__name__}")
+        n = len(x0_clip.lo)
+        if n == feat:
+            return x0_clip
+        if n != LABEL_WIDTH or feat <= LABEL_WIDTH:
+            raise ValueError(f"DiffusionLabelPredictor: x0_clip holds bounds for {n} columns; give them for the {LABEL_WIDTH} "
+                             f"label columns or for all feat_dim = {feat}")
+        pad = feat - LABEL_WIDTH
+        return X0Clip((float('-inf'),) * pad + x0_clip.lo, (float('inf'),) * pad + x0_clip.hi, x0_clip.mode, x0_clip.quantile)
 
     def _label_mask(self, frames: int, feat: int) -> torch.Tensor:
         if self._mask is None or tuple(self._mask.shape) != (frames, feat):
@@ -213,7 +236,7 @@ class DiffusionLabelPredictor:
         s = self.sampler
         self._trial = self._kept(self._trial, (hop, blend, obs.shape[2]), lambda: StitchedDDIMSampler(
             self.model, s.S, hop=hop, blend=blend, use_graph=s.use_graph, solver=s.solver, spacing=s.spacing, seed=self.seed,
-            observations=s.observations, guidance=self.guidance))
+            observations=s.observations, guidance=self.guidance, x0_clip=self.x0_clip))
         _, sampler, mask_cols = self._trial
         sampler.observations = kind
         return self._sample(sampler, obs, mask_cols, draw, None)
@@ -234,7 +257,8 @@ class DiffusionLabelPredictor:
         s = self.sampler
         self._trial_ens = self._kept(self._trial_ens, (hop, blend, obs.shape[2]), lambda: StochasticStitchedSampler(
             self.model, s.S, eta=self.eta, hop=hop, blend=blend, use_graph=s.use_graph, spacing=s.spacing, seed=self.seed,
-            solver=s.solver, observations=s.observations, guidance=self.guidance, resample=self.resample))
+            solver=s.solver, observations=s.observations, guidance=self.guidance, resample=self.resample,
+            x0_clip=self.x0_clip))
         _, sampler, mask_cols = self._trial_ens
         sampler.observations = kind
         return self._sample(sampler, obs, mask_cols, draw, 'trial_ids', labels)
