@@ -672,9 +672,9 @@ enum {
   IB_PATH_TN = 2,           /* gemm_tn.hip: 256 x 128 weight-gradient kernel, grouped */
   IB_PATH_RING = 3,         /* gemm.hip: 128 x 128 LDS-DMA ring kernel */
   IB_PATH_GENERIC = 4,      /* gemm.hip: register-staged kernel (fp32 exact MFMA, or unaligned / ragged bf16 operands) */
-  IB_PATH_SMALLM = 5,       /* gemm.hip: 64 x 16 tiles for batches of a few hundred rows (forward / dgrad) */
-  IB_PATH_SKINNY = 6,       /* gemm.hip: few-row dgrad (one workgroup per 16 output columns) */
-  IB_PATH_WGRAD_SMALL = 7,  /* gemm.hip: direct weight gradient of a short reduction */
+  IB_PATH_SMALLM = 5,       /* gemm_small.hip (bf16), gemm_f32_small.hip (fp32): 64 x 16 / 16 x 16 tiles for batches of a few hundred rows (forward / dgrad) */
+  IB_PATH_SKINNY = 6,       /* gemm_small.hip: few-row dgrad (one workgroup per 16 output columns) */
+  IB_PATH_WGRAD_SMALL = 7,  /* gemm_small.hip, gemm_f32_small.hip: direct weight gradient of a short reduction */
   IB_PATH_RING_MULTI = 8,   /* gemm.hip: grouped ring weight-gradient launch */
   IB_PATH_LINLN = 9,        /* gemm.hip: K-split Linear + residual + LayerNorm (sampler) */
   IB_PATH_CHAIN2 = 10,      /* chain.hip: fused MLP-denoiser chain, row-wise epilogues */

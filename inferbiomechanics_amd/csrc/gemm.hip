@@ -15,11 +15,10 @@
 // transposing read), everything else with ds_read_b128 / ds_read_b32.
 // The MFMA is issued "swapped" (a = B-tile rows, b = A-tile rows) so that each lane ends up with
 // 4 CONSECUTIVE output columns of one output row -> 8/16-byte epilogue stores and bias loads.
-#include <cstdlib>
 #include <type_traits>
 
 #include "wave_prims.h"
-#include "gemm_nt.h"
+#include "gemm_families.h"
 #include "time_bwd.h"
 
 namespace {
@@ -744,7 +743,7 @@ template <typename T> bool vec_store_ok(const void* p, int64_t ld) {
 // `group`: number of problems sharing the launch (ib_linear_wgrad_slabs_multi).  Each gets ~512 / group workgroups,
 // i.e. the LAUNCH fills the chip twice over instead of every problem doing so: half the slab bytes written here and
 // read back by the reduction (headline step, 4 problems: 0.2403 -> 0.2354 ms at 128 per problem; 96: 0.243, 64: 0.258)
-int wgrad_split(int64_t M, int64_t N, int64_t K, int bk, int* chunk_out, int group = 1) {
+int wgrad_split(int64_t M, int64_t N, int64_t K, int* chunk_out, int group = 1) {
   // reduction length is M; output tiles over [N, K]
   const int64_t tiles = ((N + BM - 1) / BM) * ((K + BN - 1) / BN);
   static const int env_target = ib_ab_int("IB_WGRAD_TARGET", 0);
@@ -758,324 +757,63 @@ int wgrad_split(int64_t M, int64_t N, int64_t K, int bk, int* chunk_out, int gro
   chunk = ((chunk + 63) / 64) * 64;  // multiple of both BKs
   if (chunk < 64) chunk = 64;
   const int64_t split = (M + chunk - 1) / chunk;
-  (void)bk;
   *chunk_out = (int)chunk;
   return (int)split;
 }
 
-// ring kernel: bf16, every staged piece 16-byte aligned, exact reduction tiling, >= 2 K steps of 32
-bool ring_ok(const GemmParams& p, int dtype, int red_len, int red_chunk) {
+// ring kernel: bf16 (gldsA / gldsB are set for no other dtype), every staged piece 16-byte aligned, exact reduction tiling
+// of the whole reduction p.K and of each split's p.k_chunk, >= 2 K steps of 32
+bool ring_ok(const GemmParams& p) {
   static const int off = ib_ab_int("IB_NO_RING", 0);
-  return !off && dtype == IB_BF16 && p.gldsA && p.gldsB && red_len % 32 == 0 && red_chunk % 32 == 0 && red_len >= 64 &&
-         p.lda >= 8 && p.ldb >= 8;
+  return !off && p.gldsA && p.gldsB && p.K % 32 == 0 && p.k_chunk % 32 == 0 && p.K >= 64 && p.lda >= 8 && p.ldb >= 8;
 }
 
-// ---- small-M forward -------------------------------------------------------------------------------------------------
-// y[M,N] = act(x[M,K] w[N,K]^T + bias) when the 128 x 128 tiling yields only a handful of workgroups (a batch of a few
-// hundred rows: the reference's regression models, batch-1 analysis): 64 x 16 output tiles, and the four waves of a
-// workgroup split the REDUCTION (k-blocks w, w+4, ...), so every wave walks a quarter of K.  Both operands are
-// k-contiguous: fragments come straight from global memory (no LDS staging), the four partial accumulators are combined
-// through LDS in a fixed order.  [256, 512, 1470]: 8 workgroups x 46 serial K steps -> 128 workgroups x 12.
-namespace smallm {
-constexpr int TM = 64, TN = 16, PD = 3;
-
-__device__ __forceinline__ bf16x8_t ldfrag(const bf16_t* __restrict__ rowp, int ks, int K) {
-  bf16x8_t v;
-  const int nv = K - ks;
-  if (nv >= 8) {
-    __builtin_memcpy(&v, __builtin_assume_aligned(rowp + ks, 4), 16);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = e < nv ? rowp[ks + e] : (bf16_t)0.f;
-  }
-  return v;
+// the fields that do not depend on the operand layout, for a problem whose A, B, M, N are set: staging legality of the
+// two operands for element type T (no direct-to-LDS staging in fp32), tile counts, the measurement hooks
+template <typename T>
+void fill_common(GemmParams& p) {
+  p.ablate = IB_ABLATE; p.prof = IB_AB_PROF(g_gemm_prof);
+  p.vecA = vec_load_ok<T>(p.A, p.lda); p.vecB = vec_load_ok<T>(p.B, p.ldb);
+  p.gldsA = glds_ok<T>(p.A, p.lda); p.gldsB = glds_ok<T>(p.B, p.ldb);
+  p.tiles_n = (p.N + BN - 1) / BN; p.tiles_m = (p.M + BM - 1) / BM;
 }
 
-// NT = output-tile width / 16.  Only NT = 1 is instantiated: 64 x 64 tiles (NT = 4) were measured for the sampling loop's
-// mid-sized problems (M = 3200, where 128 x 128 tiles leave most CUs idle) and lost to the ring kernel -- [3200, 1536,
-// 512] 35.6 vs 17.6 us, [3200, 2048, 512] 48 vs 20 -- fragment loads straight from global memory are 16 rows x 64 bytes
-// each and do not reach the rate of whole-row LDS-DMA staging once the tile count is in the hundreds.
-template <int ACT, int NT>
-__global__ __launch_bounds__(256) void fwd_smallm_kernel(const bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ w,
-                                                         int64_t ldw, const float* __restrict__ bias,
-                                                         const bf16_t* __restrict__ add_div, int64_t ld_ad,
-                                                         const bf16_t* __restrict__ add_mod, int64_t ld_am, int seg,
-                                                         bf16_t* __restrict__ y, int64_t ldy, int M, int N, int K) {
-  constexpr int TNV = 16 * NT;
-  __shared__ __attribute__((aligned(16))) float red[4][TM * TNV];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 15, kq = lane >> 4;
-  const int i0 = blockIdx.y * TM, j0 = blockIdx.x * TNV;
-  const bf16_t* arow[4];
-  const bf16_t* brow[NT];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) arow[t] = x + (int64_t)min(i0 + 16 * t + r, M - 1) * ldx;
-#pragma unroll
-  for (int u = 0; u < NT; ++u) brow[u] = w + (int64_t)min(j0 + 16 * u + r, N - 1) * ldw;
-  const int nkb = (K + 31) / 32;
-  const int nmine = wave < nkb ? (nkb - wave + 3) / 4 : 0;
-  f32x4_t acc[4][NT];
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int u = 0; u < NT; ++u) acc[t][u] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  bf16x8_t fa[PD][4], fb[PD][NT];
-  auto load = [&](int s, int it) {
-    const int ks = (wave + 4 * it) * 32 + 8 * kq;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) fa[s][t] = ldfrag(arow[t], ks, K);
-#pragma unroll
-    for (int u = 0; u < NT; ++u) fb[s][u] = ldfrag(brow[u], ks, K);
-  };
-#pragma unroll
-  for (int s = 0; s < PD; ++s)
-    if (s < nmine) load(s, s);
-  for (int it0 = 0; it0 < nmine; it0 += PD) {
-#pragma unroll
-    for (int s = 0; s < PD; ++s) {
-      const int it = it0 + s;
-      if (it < nmine) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int u = 0; u < NT; ++u)
-            acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[s][u], fa[s][t], acc[t][u], 0, 0, 0);
-        if (it + PD < nmine) load(s, it + PD);
-      }
+// `blocks` workgroups of the ring kernel where it qualifies (bf16, ring_ok), of the register-staged kernel elsewhere
+template <typename T, bool A_KC, bool B_KC, int EPI>
+int launch_ring_or_generic(const GemmParams& p, int blocks, hipStream_t s) {
+  if constexpr (sizeof(T) == 2) {
+    if (ring_ok(p)) {
+      IB_PATH(IB_PATH_RING);
+      hipLaunchKernelGGL((gemm_ring_kernel<A_KC, B_KC, EPI>), dim3(blocks), dim3(NTHREADS), 0, s, p);
+      IB_CHECK_LAUNCH();
+      return IB_OK;
     }
   }
-  // swapped operands: this lane holds columns 16*u + 4*kq .. +3 of row 16*t + r
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int u = 0; u < NT; ++u)
-      *reinterpret_cast<float4*>(&red[wave][(16 * t + r) * TNV + 16 * u + 4 * kq]) =
-          make_float4(acc[t][u][0], acc[t][u][1], acc[t][u][2], acc[t][u][3]);
-  __syncthreads();
-  const bool vst = (ldy % 4) == 0 && (reinterpret_cast<uintptr_t>(y) % 8) == 0;
-#pragma unroll
-  for (int g = 0; g < NT; ++g) {                            // 256 threads x 4 outputs per pass
-    const int o0 = (g * 256 + tid) * 4;
-    const int row = o0 / TNV, c4 = o0 % TNV;
-    const int gi = i0 + row, gj = j0 + c4;
-    if (gi >= M || gj >= N) continue;
-    float v[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int o = o0 + e;
-      v[e] = ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o];
-      if (gj + e < N) {
-        if (bias) v[e] += bias[gj + e];
-        if (add_div) v[e] += (float)add_div[(int64_t)(gi / seg) * ld_ad + gj + e];
-        if (add_mod) v[e] += (float)add_mod[(int64_t)(gi % seg) * ld_am + gj + e];
-      }
-      v[e] = ib_act_fwd_c<ACT, true>(v[e]);
-    }
-    bf16_t* dst = y + (int64_t)gi * ldy + gj;
-    if (gj + 4 <= N && vst) {
-      bf16x4_t o4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o4[e] = (bf16_t)v[e];
-      *reinterpret_cast<bf16x4_t*>(dst) = o4;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (gj + e < N) dst[e] = (bf16_t)v[e];
-    }
-  }
-}
-
-// dx[M,K] = (dz[M,N] w[N,K]) * act'(aux): the same tiling for the backward.  w is k-STRIDED here (its rows are the
-// reduction index), so the workgroup first transposes its slice w[:, 16 columns] into LDS (rows beyond N zero-filled);
-// dz fragments come straight from global memory.
-constexpr int RMAX = 1024, WS = RMAX + 8;
-template <int ACT>
-__global__ __launch_bounds__(256) void dgrad_smallm_kernel(const bf16_t* __restrict__ dz, int64_t lddz,
-                                                           const bf16_t* __restrict__ w, int64_t ldw,
-                                                           const bf16_t* __restrict__ aux, int64_t ldaux,
-                                                           bf16_t* __restrict__ dx, int64_t lddx, int M, int N) {
-  __shared__ __attribute__((aligned(16))) bf16_t wimg[16 * WS];
-  __shared__ __attribute__((aligned(16))) float red[4][TM * TN];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 15, kq = lane >> 4;
-  const int i0 = blockIdx.y * TM, j0 = blockIdx.x * TN;
-  const int nkb = (N + 31) / 32;
-  for (int pce = tid; pce < nkb * 64; pce += 256) {        // one 16-byte piece = 8 columns of one reduction row
-    const int k = pce >> 1, half = pce & 1;
-    bf16x8_t v;
-    if (k < N) __builtin_memcpy(&v, __builtin_assume_aligned(w + (int64_t)k * ldw + j0 + 8 * half, 16), 16);
-    else
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = (bf16_t)0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) wimg[(8 * half + e) * WS + k] = v[e];
-  }
-  __syncthreads();
-  const bf16_t* arow[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) arow[t] = dz + (int64_t)min(i0 + 16 * t + r, M - 1) * lddz;
-  const bf16_t* brow = wimg + r * WS;
-  const int nmine = wave < nkb ? (nkb - wave + 3) / 4 : 0;
-  f32x4_t acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  bf16x8_t fa[PD][4];
-  auto load = [&](int s, int it) {
-    const int ks = (wave + 4 * it) * 32 + 8 * kq;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) fa[s][t] = ldfrag(arow[t], ks, N);
-  };
-#pragma unroll
-  for (int s = 0; s < PD; ++s)
-    if (s < nmine) load(s, s);
-  for (int it0 = 0; it0 < nmine; it0 += PD) {
-#pragma unroll
-    for (int s = 0; s < PD; ++s) {
-      const int it = it0 + s;
-      if (it < nmine) {
-        bf16x8_t b;
-        __builtin_memcpy(&b, __builtin_assume_aligned(brow + (wave + 4 * it) * 32 + 8 * kq, 16), 16);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, fa[s][t], acc[t], 0, 0, 0);
-        if (it + PD < nmine) load(s, it + PD);
-      }
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-    *reinterpret_cast<float4*>(&red[wave][(16 * t + r) * TN + 4 * kq]) = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
-  __syncthreads();
-  const int row = tid >> 2, c4 = (tid & 3) * 4;
-  const int gi = i0 + row, gj = j0 + c4;
-  if (gi < M) {
-    float v[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int o = row * TN + c4 + e;
-      v[e] = ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o];
-    }
-    if constexpr (ACT != IB_ACT_NONE) {
-      bf16x4_t a4;
-      __builtin_memcpy(&a4, __builtin_assume_aligned(aux + (int64_t)gi * ldaux + gj, 8), 8);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] *= ib_act_bwd_c<ACT, true>((float)a4[e]);
-    }
-    bf16x4_t o4;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o4[e] = (bf16_t)v[e];
-    __builtin_memcpy(__builtin_assume_aligned(dx + (int64_t)gi * lddx + gj, 8), &o4, 8);
-  }
-}
-
-// up to this many 128 x 128 tiles the small tiles win (Groundlink F=10 step: cap 32 0.528 ms, 64 0.489, 128 0.491,
-// 256 0.502; the DDIM step at M = 3200, 100 tiles: 492 us of kernels at 32 / 64, 515 at 128)
-inline int tile_cap() {
-  static const int cap = ib_ab_int("IB_SMALLM_TILES", 64);
-  return cap;
-}
-// GemmParams of a dgrad: A = dz [M, red], B = w [red, cols], C = dx [M, cols]; p.N = output columns, p.K = reduction length
-inline bool dgrad_ok(const GemmParams& p) {
-  static const int off = ib_ab_int("IB_NO_SMALLM", 0);
-  const int64_t tiles = (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  return !off && tiles <= tile_cap() && !p.addend && p.K >= 64 && p.K <= RMAX && p.N % 16 == 0 && p.lda % 2 == 0 &&
-         ib_aligned(p.A, 4) && p.ldb % 8 == 0 && ib_aligned(p.B, 16) && p.ldc % 4 == 0 && ib_aligned(p.C, 8) &&
-         (p.act == IB_ACT_NONE || (p.aux && p.ldaux % 4 == 0 && ib_aligned(p.aux, 8)));
-}
-int launch_dgrad(const GemmParams& p, hipStream_t s) {
-  const dim3 grid((unsigned)(p.N / TN), (unsigned)((p.M + TM - 1) / TM)), block(256);
-#define IB_SMALLM(ACT)                                                                                                    \
-  hipLaunchKernelGGL((dgrad_smallm_kernel<ACT>), grid, block, 0, s, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb,   \
-                     (const bf16_t*)p.aux, p.ldaux, (bf16_t*)p.C, p.ldc, p.M, p.K)
-  switch (p.act) {
-    case IB_ACT_RELU: IB_SMALLM(IB_ACT_RELU); break;
-    case IB_ACT_TANH: IB_SMALLM(IB_ACT_TANH); break;
-    case IB_ACT_SIGMOID: IB_SMALLM(IB_ACT_SIGMOID); break;
-    case IB_ACT_SILU: IB_SMALLM(IB_ACT_SILU); break;
-    case IB_ACT_ELU: IB_SMALLM(IB_ACT_ELU); break;
-    default: IB_SMALLM(IB_ACT_NONE); break;
-  }
-#undef IB_SMALLM
+  IB_PATH(IB_PATH_GENERIC);
+  hipLaunchKernelGGL((gemm_kernel<T, A_KC, B_KC, EPI>), dim3(blocks), dim3(NTHREADS), 0, s, p);
   IB_CHECK_LAUNCH();
   return IB_OK;
 }
-
-// few 128 x 128 tiles (tile_cap()), plain epilogue (bias, the two row-broadcast addends, activation), rows 4-byte aligned
-inline bool ok(const GemmParams& p) {
-  static const int off = ib_ab_int("IB_NO_SMALLM", 0);
-  const int64_t tiles = (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  return !off && tiles <= tile_cap() && !p.Z && p.lda % 2 == 0 && p.ldb % 2 == 0 && ib_aligned(p.A, 4) && ib_aligned(p.B, 4) &&
-         p.K >= 64;
-}
-template <int NT>
-int launch(const GemmParams& p, hipStream_t s) {
-  const dim3 grid((unsigned)((p.N + 16 * NT - 1) / (16 * NT)), (unsigned)((p.M + TM - 1) / TM)), block(256);
-#define IB_SMALLM(ACT)                                                                                                      \
-  hipLaunchKernelGGL((fwd_smallm_kernel<ACT, NT>), grid, block, 0, s, (const bf16_t*)p.A, p.lda, (const bf16_t*)p.B, p.ldb,   \
-                     p.bias, (const bf16_t*)p.add_div, p.ld_add_div, (const bf16_t*)p.add_mod, p.ld_add_mod, p.seg,         \
-                     (bf16_t*)p.C, p.ldc, p.M, p.N, p.K)
-  switch (p.act) {
-    case IB_ACT_RELU: IB_SMALLM(IB_ACT_RELU); break;
-    case IB_ACT_TANH: IB_SMALLM(IB_ACT_TANH); break;
-    case IB_ACT_SIGMOID: IB_SMALLM(IB_ACT_SIGMOID); break;
-    case IB_ACT_SILU: IB_SMALLM(IB_ACT_SILU); break;
-    case IB_ACT_ELU: IB_SMALLM(IB_ACT_ELU); break;
-    default: IB_SMALLM(IB_ACT_NONE); break;
-  }
-#undef IB_SMALLM
-  IB_CHECK_LAUNCH();
-  return IB_OK;
-}
-}  // namespace smallm
 
 template <typename T>
 int launch_fwd(GemmParams& p, hipStream_t s) {
-  p.ablate = IB_ABLATE; p.prof = IB_AB_PROF(g_gemm_prof);
-  p.vecA = vec_load_ok<T>(p.A, p.lda);
-  p.vecB = vec_load_ok<T>(p.B, p.ldb);
-  p.gldsA = glds_ok<T>(p.A, p.lda); p.gldsB = glds_ok<T>(p.B, p.ldb);
+  fill_common<T>(p);
   p.vecC = vec_store_ok<T>(p.C, p.ldc) && (!p.Z || vec_store_ok<T>(p.Z, p.ldz));
   p.vecBias = !p.bias || ib_aligned(p.bias, 16);
   p.vecAdd = (!p.add_div || vec_store_ok<T>(p.add_div, p.ld_add_div)) &&
              (!p.add_mod || vec_store_ok<T>(p.add_mod, p.ld_add_mod));
-  p.tiles_n = (p.N + BN - 1) / BN; p.tiles_m = (p.M + BM - 1) / BM;
   p.k_chunk = p.K; p.slab_stride = 0; p.xcd_group = 1;
-  const int tiles = p.tiles_m * p.tiles_n;
-  if (sizeof(T) == 2 && smallm::ok(p)) { IB_PATH(IB_PATH_SMALLM); return smallm::launch<1>(p, s); }
-  if (sizeof(T) == 2 && ring_ok(p, IB_BF16, p.K, p.K)) {
-    IB_PATH(IB_PATH_RING);
-    hipLaunchKernelGGL((gemm_ring_kernel<true, true, EPI_FWD>), dim3(tiles, 1), dim3(NTHREADS), 0, s, p);
-    IB_CHECK_LAUNCH();
-    return IB_OK;
-  }
-  IB_PATH(IB_PATH_GENERIC);
-  hipLaunchKernelGGL((gemm_kernel<T, true, true, EPI_FWD>), dim3(tiles, 1), dim3(NTHREADS), 0, s, p);
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  return launch_ring_or_generic<T, true, true, EPI_FWD>(p, p.tiles_m * p.tiles_n, s);
 }
 
 template <typename T>
 int launch_dgrad(GemmParams& p, hipStream_t s) {
-  p.ablate = IB_ABLATE; p.prof = IB_AB_PROF(g_gemm_prof);
-  p.vecA = vec_load_ok<T>(p.A, p.lda);
-  p.vecB = vec_load_ok<T>(p.B, p.ldb);
-  p.gldsA = glds_ok<T>(p.A, p.lda); p.gldsB = glds_ok<T>(p.B, p.ldb);
+  fill_common<T>(p);
   p.vecC = vec_store_ok<T>(p.C, p.ldc);
   p.vecAux = !p.aux || vec_store_ok<T>(p.aux, p.ldaux);
   p.vecAdd = !p.addend || vec_store_ok<T>(p.addend, p.ldadd);
-  p.tiles_n = (p.N + BN - 1) / BN; p.tiles_m = (p.M + BM - 1) / BM;
   p.k_chunk = p.K; p.slab_stride = 0; p.xcd_group = 1;
-  const int tiles = p.tiles_m * p.tiles_n;
-  if (sizeof(T) == 2 && smallm::dgrad_ok(p)) { IB_PATH(IB_PATH_SMALLM); return smallm::launch_dgrad(p, s); }
-  if (sizeof(T) == 2 && ring_ok(p, IB_BF16, p.K, p.K)) {
-    IB_PATH(IB_PATH_RING);
-    hipLaunchKernelGGL((gemm_ring_kernel<true, false, EPI_DGRAD>), dim3(tiles, 1), dim3(NTHREADS), 0, s, p);
-    IB_CHECK_LAUNCH();
-    return IB_OK;
-  }
-  IB_PATH(IB_PATH_GENERIC);
-  hipLaunchKernelGGL((gemm_kernel<T, true, false, EPI_DGRAD>), dim3(tiles, 1), dim3(NTHREADS), 0, s, p);
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  return launch_ring_or_generic<T, true, false, EPI_DGRAD>(p, p.tiles_m * p.tiles_n, s);
 }
 
 }  // namespace
@@ -1108,7 +846,12 @@ extern "C" int ib_linear_fwd(const void* x, int64_t ldx, const void* w, int64_t 
   if (dtype == IB_F32 && !add_div && !add_mod) {              // the reference's own batch sizes in fp32: reduction-split tiles
     const int rc = ib_f32_small_fwd_try((const float*)x, ldx, (const float*)w, ldw, bias, act, (float*)y, ldy, (float*)z, ldz,
                                         M, N, K, ib_s(stream));
-    if (rc != IB_E_UNSUPPORTED) { IB_PATH(IB_PATH_SMALLM); return rc; }
+    if (rc != IB_E_UNSUPPORTED) return rc;
+  }
+  if (dtype == IB_BF16) {                                     // a few hundred rows: 64 x 16 tiles (gemm_small.hip)
+    const int rc = ib_bf16_small_fwd_try(x, ldx, w, ldw, bias, add_div, ld_add_div, add_mod, ld_add_mod, p.seg, act, y, ldy, z,
+                                         M, N, K, ib_s(stream));
+    if (rc != IB_E_UNSUPPORTED) return rc;
   }
   if (dtype == IB_F32) return launch_fwd<float>(p, ib_s(stream));
   if (dtype == IB_BF16) return launch_fwd<bf16_t>(p, ib_s(stream));
@@ -1130,7 +873,11 @@ extern "C" int ib_linear_dgrad(const void* dz, int64_t lddz, const void* w, int6
   if (dtype == IB_F32) {
     const int rc = ib_f32_small_dgrad_try((const float*)dz, lddz, (const float*)w, ldw, act_below, (const float*)aux, ldaux,
                                           (const float*)addend, ldadd, (float*)dx, lddx, M, N, K, ib_s(stream));
-    if (rc != IB_E_UNSUPPORTED) { IB_PATH(IB_PATH_SMALLM); return rc; }
+    if (rc != IB_E_UNSUPPORTED) return rc;
+  }
+  if (dtype == IB_BF16) {
+    const int rc = ib_bf16_small_dgrad_try(dz, lddz, w, ldw, act_below, aux, ldaux, addend, dx, lddx, M, N, K, ib_s(stream));
+    if (rc != IB_E_UNSUPPORTED) return rc;
   }
   if (dtype == IB_F32) return launch_dgrad<float>(p, ib_s(stream));
   if (dtype == IB_BF16) return launch_dgrad<bf16_t>(p, ib_s(stream));
@@ -1152,160 +899,31 @@ extern "C" int ib_linear_dgrad_wt(const void* dz, int64_t lddz, const void* wt, 
                         ib_s(stream));
 }
 
-// ---- skinny dgrad: few rows (a batch of time embeddings), long reduction --------------------------------------------
-// dx[M,K] = (dz[M,N] . w[N,K]) * act'(aux), M <= 256.  The tiled kernels give such a problem 8 workgroups that each walk
-// the whole reduction alone (measured 40 us for [256, 1024] x [1024, 512], on the step's critical path).  Here a
-// workgroup owns 16 OUTPUT COLUMNS and all rows: K/16 workgroups, the w slice [N,16] transposed into LDS once, the dz
-// rows streamed straight into MFMA fragments through a 4-deep register ring (each wave its own rows: nothing to share),
-// and -- because a workgroup sees every row of its columns -- the bias gradient (column sums of dx) comes out of the
-// same launch in a fixed order.
-namespace skinny {
-constexpr int NMAX = 1024, WS = NMAX + 8, PD = 4;       // w image: 16 columns x (N + 8 pad) bf16, k-contiguous
-
-template <int ACT>
-__global__ __launch_bounds__(256) void dgrad_skinny_kernel(const bf16_t* __restrict__ dz, int64_t lddz,
-                                                           const bf16_t* __restrict__ w, int64_t ldw,
-                                                           const bf16_t* __restrict__ aux, int64_t ldaux,
-                                                           bf16_t* __restrict__ dx, int64_t lddx, float* __restrict__ dbias,
-                                                           int accumulate, int M, int N) {
-  __shared__ __attribute__((aligned(16))) bf16_t wimg[16 * WS];
-  __shared__ float red[4][16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int c0 = blockIdx.x * 16;
-  // w[:, c0 .. c0+16) -> wimg[col][k]: one 16-byte piece = 8 columns of one reduction row
-  // (four pieces per thread requested before the first is scattered: a rolled loop was N/128 dependent round trips)
-  for (int p0 = tid; p0 < N * 2; p0 += 256 * 4) {
-    bf16x8_t v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int pce = min(p0 + 256 * u, N * 2 - 1), k = pce >> 1, half = pce & 1;
-      __builtin_memcpy(&v[u], __builtin_assume_aligned(w + (int64_t)k * ldw + c0 + 8 * half, 16), 16);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int pce = p0 + 256 * u, k = pce >> 1, half = pce & 1;
-      if (pce < N * 2) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) wimg[(8 * half + e) * WS + k] = v[u][e];
-      }
-    }
-  }
-  __syncthreads();
-  const int mt_total = (M + 15) / 16;
-  const int r = lane & 15, kq = lane >> 4;
-  const bf16_t* arow[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int row = min((wave + 4 * j) * 16 + r, M - 1);   // tiles past the last row read valid memory and store nothing
-    arow[j] = dz + (int64_t)row * lddz + 8 * kq;
-  }
-  f32x4_t acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) acc[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  bf16x8_t ar[PD][4];
-  const int nkb = N / 32;                                  // a multiple of PD by the launch conditions
-#pragma unroll
-  for (int sl = 0; sl < PD; ++sl)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) __builtin_memcpy(&ar[sl][j], __builtin_assume_aligned(arow[j] + sl * 32, 16), 16);
-  const bf16_t* brow = wimg + r * WS + 8 * kq;
-  for (int kb0 = 0; kb0 < nkb; kb0 += PD) {
-#pragma unroll
-    for (int sl = 0; sl < PD; ++sl) {
-      const int kb = kb0 + sl;
-      bf16x8_t b;
-      __builtin_memcpy(&b, __builtin_assume_aligned(brow + kb * 32, 16), 16);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, ar[sl][j], acc[j], 0, 0, 0);
-      const int kn = min(kb + PD, nkb - 1);                // the last PD refills re-read the final block (never used)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) __builtin_memcpy(&ar[sl][j], __builtin_assume_aligned(arow[j] + kn * 32, 16), 16);
-    }
-  }
-  // swapped operands: this lane holds columns c0 + 4*kq .. +3 of row (tile, r)
-  float cs[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int row = (wave + 4 * j) * 16 + r;
-    if (wave + 4 * j >= mt_total || row >= M) continue;
-    float v[4] = {acc[j][0], acc[j][1], acc[j][2], acc[j][3]};
-    if constexpr (ACT != IB_ACT_NONE) {
-      bf16x4_t a4;
-      __builtin_memcpy(&a4, __builtin_assume_aligned(aux + (int64_t)row * ldaux + c0 + 4 * kq, 8), 8);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] *= ib_act_bwd_c<ACT, true>((float)a4[e]);
-    }
-    bf16x4_t o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      o[e] = (bf16_t)v[e];
-      cs[e] += (float)o[e];                                // the bias gradient is the column sum of the STORED tensor
-    }
-    __builtin_memcpy(__builtin_assume_aligned(dx + (int64_t)row * lddx + c0 + 4 * kq, 8), &o, 8);
-  }
-  if (dbias) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) cs[e] += __shfl_xor(cs[e], o, 64);     // the 16 rows of a tile: fixed butterfly
-      if (r == 0) red[wave][4 * kq + e] = cs[e];
-    }
-    __syncthreads();
-    if (tid < 16) {
-      const float sum = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-      dbias[c0 + tid] = accumulate ? dbias[c0 + tid] + sum : sum;
-    }
-  }
-}
-}  // namespace skinny
-
 extern "C" int ib_linear_dgrad_skinny(const void* dz, int64_t lddz, const void* w, int64_t ldw, int act_below,
                                       const void* aux, int64_t ldaux, void* dx, int64_t lddx, float* dbias, int accumulate,
                                       int64_t M, int64_t N, int64_t K, int dtype, ib_stream_t stream) {
   if (!dz || !w || !dx || M <= 0 || N <= 0 || K <= 0 || lddz < N || ldw < K || lddx < K) return IB_E_ARG;
   if (act_below != IB_ACT_NONE && (!aux || ldaux < K)) return IB_E_ARG;
   if (act_below < IB_ACT_NONE || act_below > IB_ACT_ELU) return IB_E_ARG;
-  if (dtype != IB_BF16 || M > 256 || N > skinny::NMAX || N % (32 * skinny::PD) != 0 || K % 16 != 0) return IB_E_UNSUPPORTED;
-  if (!ib_aligned(dz, 16) || lddz % 8 != 0 || !ib_aligned(w, 16) || ldw % 8 != 0 || !ib_aligned(dx, 8) || lddx % 4 != 0 ||
-      (aux && (!ib_aligned(aux, 8) || ldaux % 4 != 0)))
-    return IB_E_UNSUPPORTED;
-  const dim3 grid((unsigned)(K / 16)), block(256);
-  hipStream_t s = ib_s(stream);
-  IB_PATH(IB_PATH_SKINNY);
-#define IB_SKINNY(ACT)                                                                                                  \
-  hipLaunchKernelGGL((skinny::dgrad_skinny_kernel<ACT>), grid, block, 0, s, (const bf16_t*)dz, lddz, (const bf16_t*)w, ldw, \
-                     (const bf16_t*)aux, ldaux, (bf16_t*)dx, lddx, dbias, accumulate, (int)M, (int)N)
-  switch (act_below) {
-    case IB_ACT_RELU: IB_SKINNY(IB_ACT_RELU); break;
-    case IB_ACT_TANH: IB_SKINNY(IB_ACT_TANH); break;
-    case IB_ACT_SIGMOID: IB_SKINNY(IB_ACT_SIGMOID); break;
-    case IB_ACT_SILU: IB_SKINNY(IB_ACT_SILU); break;
-    case IB_ACT_ELU: IB_SKINNY(IB_ACT_ELU); break;
-    default: IB_SKINNY(IB_ACT_NONE); break;
-  }
-#undef IB_SKINNY
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  return ib_skinny_dgrad_try(dz, lddz, w, ldw, act_below, aux, ldaux, dx, lddx, dbias, accumulate, M, N, K, dtype, ib_s(stream));
 }
 
 extern "C" size_t ib_linear_wgrad_workspace(int64_t M, int64_t N, int64_t K) {
   int chunk;
-  const int split = wgrad_split(M, N, K, 64, &chunk);
+  const int split = wgrad_split(M, N, K, &chunk);
   return split > 1 ? (size_t)split * (size_t)N * (size_t)K * sizeof(float) : 0;
 }
 
 namespace {
-// the split-M weight-gradient GEMM.  slabs_only: always write fp32 partial slabs [split][N][K] into the workspace
-// (even for split == 1) and leave the reduction to ib_slab_reduce_multi (one launch for several gradients).
-// fills the GemmParams of dW = dz^T x (split over M); returns the error code, *split_out / *tiles_out on success
+// fills the GemmParams of dW = dz^T x (split over M); returns the error code, *split_out on success
 int wgrad_params(const void* dz, int64_t lddz, const void* x, int64_t ldx, float* dw, int64_t lddw, int accumulate,
                  void* workspace, size_t workspace_bytes, int64_t M, int64_t N, int64_t K, int dtype, bool slabs_only,
-                 GemmParams& p, int* split_out, int* tiles_out, int* chunk_out, int group = 1) {
+                 GemmParams& p, int* split_out, int group = 1) {
   if (!dz || !x || M <= 0 || N <= 0 || K <= 0 || lddz < N || ldx < K) return IB_E_ARG;
   if (!slabs_only && (!dw || lddw < K)) return IB_E_ARG;
   if (dtype != IB_F32 && dtype != IB_BF16) return IB_E_DTYPE;
   int chunk;
-  const int split = wgrad_split(M, N, K, 64, &chunk, group);
+  const int split = wgrad_split(M, N, K, &chunk, group);
   const bool to_ws = slabs_only || split > 1;
   const size_t need = to_ws ? (size_t)split * (size_t)N * (size_t)K * sizeof(float) : 0;
   if (need > 0 && (!workspace || workspace_bytes < need)) return IB_E_WORKSPACE;
@@ -1313,8 +931,7 @@ int wgrad_params(const void* dz, int64_t lddz, const void* x, int64_t ldx, float
   p = GemmParams{};
   p.A = dz; p.lda = lddz; p.B = x; p.ldb = ldx; p.M = (int)N; p.N = (int)K; p.K = (int)M;
   p.seg = 1; p.act = IB_ACT_NONE; p.accumulate = accumulate;
-  p.ablate = IB_ABLATE; p.prof = IB_AB_PROF(g_gemm_prof);
-  p.tiles_n = (p.N + BN - 1) / BN; p.tiles_m = (p.M + BM - 1) / BM;
+  if (dtype == IB_F32) fill_common<float>(p); else fill_common<bf16_t>(p);
   p.k_chunk = chunk;
   // all tiles of one M-chunk on one XCD only while that chunk's dz + x slices fit comfortably in the XCD's 4 MiB
   // L2 (measured: [12800,512,300] 42 -> 36 us grouped, but [12800,1536,512] 48 -> 63 us: 5.2 MB per chunk thrashes)
@@ -1325,13 +942,7 @@ int wgrad_params(const void* dz, int64_t lddz, const void* x, int64_t ldx, float
     p.C = dw; p.ldc = lddw; p.slab_stride = 0;
   }
   p.vecC = ib_aligned(p.C, 16) && (p.ldc % 4 == 0) && (p.slab_stride % 4 == 0);
-  if (dtype == IB_F32) {
-    p.vecA = vec_load_ok<float>(p.A, p.lda); p.vecB = vec_load_ok<float>(p.B, p.ldb);
-  } else {
-    p.vecA = vec_load_ok<bf16_t>(p.A, p.lda); p.vecB = vec_load_ok<bf16_t>(p.B, p.ldb);
-    p.gldsA = glds_ok<bf16_t>(p.A, p.lda); p.gldsB = glds_ok<bf16_t>(p.B, p.ldb);
-  }
-  *split_out = split; *tiles_out = p.tiles_m * p.tiles_n; *chunk_out = chunk;
+  *split_out = split;
   return IB_OK;
 }
 
@@ -1341,21 +952,14 @@ int wgrad_gemm(const void* dz, int64_t lddz, const void* x, int64_t ldx, float* 
                void* workspace, size_t workspace_bytes, int64_t M, int64_t N, int64_t K, int dtype, hipStream_t s,
                bool slabs_only, int* split_out) {
   GemmParams p;
-  int split, tiles, chunk;
+  int split;
   const int rc = wgrad_params(dz, lddz, x, ldx, dw, lddw, accumulate, workspace, workspace_bytes, M, N, K, dtype,
-                              slabs_only, p, &split, &tiles, &chunk);
+                              slabs_only, p, &split);
   if (rc != IB_OK) return rc;
-  if (dtype == IB_F32) {
-    IB_PATH(IB_PATH_GENERIC);
-    hipLaunchKernelGGL((gemm_kernel<float, false, false, EPI_WGRAD>), dim3(tiles * split), dim3(NTHREADS), 0, s, p);
-  } else {
-    IB_PATH(ring_ok(p, IB_BF16, p.K, chunk) ? IB_PATH_RING : IB_PATH_GENERIC);
-    if (ring_ok(p, IB_BF16, p.K, chunk))
-      hipLaunchKernelGGL((gemm_ring_kernel<false, false, EPI_WGRAD>), dim3(tiles * split), dim3(NTHREADS), 0, s, p);
-    else
-      hipLaunchKernelGGL((gemm_kernel<bf16_t, false, false, EPI_WGRAD>), dim3(tiles * split), dim3(NTHREADS), 0, s, p);
-  }
-  IB_CHECK_LAUNCH();
+  const int blocks = p.tiles_m * p.tiles_n * split;
+  const int lrc = dtype == IB_F32 ? launch_ring_or_generic<float, false, false, EPI_WGRAD>(p, blocks, s)
+                                  : launch_ring_or_generic<bf16_t, false, false, EPI_WGRAD>(p, blocks, s);
+  if (lrc != IB_OK) return lrc;
   if (split_out) *split_out = split;
   if (!slabs_only && split > 1) {
     const int64_t n = (int64_t)N * K;
@@ -1368,118 +972,21 @@ int wgrad_gemm(const void* dz, int64_t lddz, const void* x, int64_t ldx, float* 
   return IB_OK;
 }
 
+// the problem count and the per-problem arrays of a grouped weight-gradient entry
+bool wgrad_group_args_ok(int n, const void* const* dz, const int64_t* lddz, const void* const* x, const int64_t* ldx,
+                         void* const* workspace, const size_t* workspace_bytes, const int32_t* nslab_out, const int64_t* M,
+                         const int64_t* N, const int64_t* K) {
+  return n > 0 && n <= WG_MAX && dz && lddz && x && ldx && workspace && workspace_bytes && nslab_out && M && N && K;
+}
+
 }  // namespace
-
-// ---- weight gradient over a SHORT reduction (a batch of a few hundred rows) -----------------------------------------------
-// dw[N,K] (+)= dz[M,N]^T x[M,K] with M <= 1024.  The split-M kernels above exist to find parallelism in a long reduction;
-// here the OUTPUT is the large side ([512, 1470] from 256 rows), so 64 x 64 output tiles alone give hundreds of
-// workgroups: no split, no slabs, no reduction launch.  Both operands are indexed [reduction][column]: a workgroup stages
-// its two [rows][64] slices in LDS (256 rows at a time) and reads MFMA fragments with the transposing ds_read_b64_tr_b16.
-// [256 rows; 512 x 1470]: 20.8 us (GEMM + slab reduction) -> one launch.
-namespace wsmall {
-constexpr int CH = 256, PITCH = 72;       // rows per LDS chunk; image row pitch in elements (64 + 8: 144 B)
-
-__device__ __forceinline__ bf16x8_t frag_tr(const bf16_t* img, int rbase, int lane) {       // img: first row of a 32-row K step
-  const int q = (lane & 15) >> 2, pp = lane & 3;
-  const int kr = 8 * (lane >> 4) + q;
-  return lds_read_tr<0, 4 * PITCH * 2>(lds_off(img) + (kr * PITCH + rbase + 4 * pp) * 2);
-}
-
-__global__ __launch_bounds__(256) void wgrad_smallm_kernel(const bf16_t* __restrict__ dz, int64_t lddz,
-                                                           const bf16_t* __restrict__ x, int64_t ldx, float* __restrict__ dw,
-                                                           int64_t lddw, float* __restrict__ dbias, int accumulate, int M,
-                                                           int N, int K) {
-  __shared__ __attribute__((aligned(16))) bf16_t aimg[CH * PITCH];
-  __shared__ __attribute__((aligned(16))) bf16_t bimg[CH * PITCH];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wi = wave >> 1, wj = wave & 1;
-  const int n0 = blockIdx.y * 64, k0 = blockIdx.x * 64;
-  f32x4_t acc[2][2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) acc[t][u] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  float bsum = 0.f;
-  for (int m0 = 0; m0 < M; m0 += CH) {
-    if (m0) __syncthreads();                               // the previous chunk's fragments have been read
-    const int rows = min(CH, M - m0), rows32 = (rows + 31) / 32 * 32;
-    for (int pce = tid; pce < rows32 * 8; pce += 256) {    // [row][8 pieces of 8 columns], rows past the end zero-filled
-      const int m = pce >> 3, c = (pce & 7) * 8;
-      bf16x8_t va, vb;
-      if (m < rows) {
-        va = smallm::ldfrag(dz + (int64_t)(m0 + m) * lddz, n0 + c, N);
-        vb = smallm::ldfrag(x + (int64_t)(m0 + m) * ldx, k0 + c, K);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { va[e] = (bf16_t)0.f; vb[e] = (bf16_t)0.f; }
-      }
-      __builtin_memcpy(__builtin_assume_aligned(aimg + m * PITCH + c, 16), &va, 16);
-      __builtin_memcpy(__builtin_assume_aligned(bimg + m * PITCH + c, 16), &vb, 16);
-    }
-    __syncthreads();
-    // the bias gradient of the same layer = column sums of dz: the first workgroup of every row of tiles has the slice
-    // in LDS anyway (one thread per column, rows added in order)
-    if (dbias && blockIdx.x == 0 && tid < 64) {
-      float sacc = 0.f;
-      for (int m = 0; m < rows; ++m) sacc += (float)aimg[m * PITCH + tid];
-      bsum += sacc;
-    }
-    for (int ks = 0; ks < rows32; ks += 32) {
-      bf16x8_t fa[2], fb[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) fa[t] = frag_tr(aimg + ks * PITCH, wi * 32 + 16 * t, lane);
-#pragma unroll
-      for (int u = 0; u < 2; ++u) fb[u] = frag_tr(bimg + ks * PITCH, wj * 32 + 16 * u, lane);
-      frags_ready(fa, fb);
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[u], fa[t], acc[t][u], 0, 0, 0);
-    }
-  }
-  if (dbias && blockIdx.x == 0 && tid < 64 && n0 + tid < N) dbias[n0 + tid] = accumulate ? dbias[n0 + tid] + bsum : bsum;
-  // swapped operands: this lane holds output columns (k) 16*u + 4*(lane >> 4) .. +3 of output row (n) 16*t + (lane & 15)
-  const bool vst = (lddw % 4) == 0 && (reinterpret_cast<uintptr_t>(dw) % 16) == 0;
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int n = n0 + wi * 32 + 16 * t + (lane & 15);
-    if (n >= N) continue;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int k = k0 + wj * 32 + 16 * u + 4 * (lane >> 4);
-      if (k >= K) continue;
-      float* o = dw + (int64_t)n * lddw + k;
-      float v[4] = {acc[t][u][0], acc[t][u][1], acc[t][u][2], acc[t][u][3]};
-      if (k + 4 <= K && vst) {
-        float4 w4 = make_float4(v[0], v[1], v[2], v[3]);
-        if (accumulate) { const float4 p4 = *reinterpret_cast<const float4*>(o); w4.x += p4.x; w4.y += p4.y; w4.z += p4.z; w4.w += p4.w; }
-        *reinterpret_cast<float4*>(o) = w4;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (k + e < K) o[e] = accumulate ? o[e] + v[e] : v[e];
-      }
-    }
-  }
-}
-
-inline bool ok(const void* dz, int64_t lddz, const void* x, int64_t ldx, int64_t M, int dtype) {
-  static const int off = ib_ab_int("IB_NO_SMALLM", 0);
-  // M <= 1024: with 2560 rows (Groundlink, F = 10) the ten serial LDS chunks per workgroup lose to the split-M kernels
-  // (step 0.496 -> 0.789 ms when the limit was raised to 4096)
-  return !off && dtype == IB_BF16 && M <= 1024 && lddz % 2 == 0 && ldx % 2 == 0 && ib_aligned(dz, 4) && ib_aligned(x, 4);
-}
-}  // namespace wsmall
 
 extern "C" int ib_linear_wgrad(const void* dz, int64_t lddz, const void* x, int64_t ldx, float* dw,
                                int64_t lddw, int accumulate, void* workspace, size_t workspace_bytes,
                                int64_t M, int64_t N, int64_t K, int dtype, ib_stream_t stream) {
-  if (dz && x && dw && M > 0 && N > 0 && K > 0 && lddz >= N && ldx >= K && lddw >= K && wsmall::ok(dz, lddz, x, ldx, M, dtype)) {
-    IB_PATH(IB_PATH_WGRAD_SMALL);
-    hipLaunchKernelGGL(wsmall::wgrad_smallm_kernel, dim3((unsigned)((K + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0,
-                       ib_s(stream), (const bf16_t*)dz, lddz, (const bf16_t*)x, ldx, dw, lddw, nullptr, accumulate, (int)M, (int)N, (int)K);
-    IB_CHECK_LAUNCH();
-    return IB_OK;
+  if (dz && x && dw && M > 0 && N > 0 && K > 0 && lddz >= N && ldx >= K && lddw >= K) {     // short reduction: one pass
+    const int rc = ib_wgrad_small_try(dz, lddz, x, ldx, dw, lddw, nullptr, accumulate, M, N, K, dtype, ib_s(stream));
+    if (rc != IB_E_UNSUPPORTED) return rc;
   }
   return wgrad_gemm(dz, lddz, x, ldx, dw, lddw, accumulate, workspace, workspace_bytes, M, N, K, dtype, ib_s(stream),
                     false, nullptr);
@@ -1489,24 +996,15 @@ extern "C" int ib_linear_wgrad_bias(const void* dz, int64_t lddz, const void* x,
                                     float* dbias, int accumulate, int64_t M, int64_t N, int64_t K, int dtype,
                                     ib_stream_t stream) {
   if (!dz || !x || !dw || !dbias || M <= 0 || N <= 0 || K <= 0 || lddz < N || ldx < K || lddw < K) return IB_E_ARG;
-  if (dtype == IB_F32) {                                    // the reference's batch sizes in fp32 (gemm_f32_small.hip)
-    const int rc = ib_f32_small_wgrad_bias_try((const float*)dz, lddz, (const float*)x, ldx, dw, lddw, dbias, accumulate, M, N, K,
-                                               ib_s(stream));
-    if (rc == IB_OK) IB_PATH(IB_PATH_WGRAD_SMALL);
-    return rc;
-  }
-  if (!wsmall::ok(dz, lddz, x, ldx, M, dtype)) return IB_E_UNSUPPORTED;
-  IB_PATH(IB_PATH_WGRAD_SMALL);
-  hipLaunchKernelGGL(wsmall::wgrad_smallm_kernel, dim3((unsigned)((K + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0,
-                     ib_s(stream), (const bf16_t*)dz, lddz, (const bf16_t*)x, ldx, dw, lddw, dbias, accumulate, (int)M, (int)N,
-                     (int)K);
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  if (dtype == IB_F32)                                      // the reference's batch sizes in fp32 (gemm_f32_small.hip)
+    return ib_f32_small_wgrad_bias_try((const float*)dz, lddz, (const float*)x, ldx, dw, lddw, dbias, accumulate, M, N, K,
+                                       ib_s(stream));
+  return ib_wgrad_small_try(dz, lddz, x, ldx, dw, lddw, dbias, accumulate, M, N, K, dtype, ib_s(stream));
 }
 
 extern "C" size_t ib_linear_wgrad_slabs_workspace(int64_t M, int64_t N, int64_t K) {
   int chunk;
-  int split = wgrad_split(M, N, K, 64, &chunk);
+  int split = wgrad_split(M, N, K, &chunk);
   const int tn = ib_gemm_tn_splits(M, N, K, 1);              // the 256 x 128 kernel (gemm_tn.hip) splits finest when alone
   if (tn > split) split = tn;
   return (size_t)split * (size_t)N * (size_t)K * sizeof(float);
@@ -1517,15 +1015,12 @@ extern "C" int ib_linear_wgrad_slabs(const void* dz, int64_t lddz, const void* x
                                      int dtype, ib_stream_t stream) {
   if (!nslab_out) return IB_E_ARG;
   if (dz && x && workspace && M > 0 && N > 0 && K > 0 && lddz >= N && ldx >= K && K % 4 == 0 &&
-      workspace_bytes >= (size_t)N * K * sizeof(float) && ib_aligned(workspace, 16) && wsmall::ok(dz, lddz, x, ldx, M, dtype)) {
+      workspace_bytes >= (size_t)N * K * sizeof(float) && ib_aligned(workspace, 16)) {
     // short reduction: the one-pass kernel writes the whole gradient as a single "slab"
-    IB_PATH(IB_PATH_WGRAD_SMALL);
-    hipLaunchKernelGGL(wsmall::wgrad_smallm_kernel, dim3((unsigned)((K + 63) / 64), (unsigned)((N + 63) / 64)), dim3(256), 0,
-                       ib_s(stream), (const bf16_t*)dz, lddz, (const bf16_t*)x, ldx, reinterpret_cast<float*>(workspace), K,
-                       nullptr, 0, (int)M, (int)N, (int)K);
-    IB_CHECK_LAUNCH();
-    *nslab_out = 1;
-    return IB_OK;
+    const int rc = ib_wgrad_small_try(dz, lddz, x, ldx, reinterpret_cast<float*>(workspace), K, nullptr, 0, M, N, K, dtype,
+                                      ib_s(stream));
+    if (rc == IB_OK) *nslab_out = 1;
+    if (rc != IB_E_UNSUPPORTED) return rc;
   }
   if (dtype == IB_BF16 && dz && x && workspace && lddz >= N && ldx >= K) {      // long reduction: the 256 x 128 kernel
     const void* dzs[1] = {dz}; const void* xs[1] = {x}; void* wss[1] = {workspace};
@@ -1551,8 +1046,7 @@ extern "C" int ib_linear_wgrad_slabs_multi_bias(int n, const void* const* dz, co
                                                 const int64_t* ldx, void* const* workspace, const size_t* workspace_bytes,
                                                 float* const* dbias_part, int32_t* nslab_out, const int64_t* M,
                                                 const int64_t* N, const int64_t* K, int dtype, ib_stream_t stream) {
-  if (n <= 0 || n > WG_MAX || !dz || !lddz || !x || !ldx || !workspace || !workspace_bytes || !nslab_out || !M || !N || !K)
-    return IB_E_ARG;
+  if (!wgrad_group_args_ok(n, dz, lddz, x, ldx, workspace, workspace_bytes, nslab_out, M, N, K)) return IB_E_ARG;
   if (dtype != IB_BF16) return IB_E_UNSUPPORTED;
   {   // long reductions: the 256 x 128 LDS-DMA kernel (half the operand re-reads of the 128 x 128 tiles)
     const int rc = ib_gemm_tn_multi(n, dz, lddz, x, ldx, workspace, workspace_bytes, dbias_part, nslab_out, M, N, K,
@@ -1563,15 +1057,15 @@ extern "C" int ib_linear_wgrad_slabs_multi_bias(int n, const void* const* dz, co
   m.n = n;
   int blocks = 0;
   for (int j = 0; j < n; ++j) {
-    int split, tiles, chunk;
+    int split;
     const int rc = wgrad_params(dz[j], lddz[j], x[j], ldx[j], nullptr, 0, 0, workspace[j], workspace_bytes[j], M[j], N[j],
-                                K[j], dtype, true, m.p[j], &split, &tiles, &chunk, n);
+                                K[j], dtype, true, m.p[j], &split, n);
     if (rc != IB_OK) return rc;
-    if (!ring_ok(m.p[j], IB_BF16, m.p[j].K, chunk)) return IB_E_UNSUPPORTED;   // caller falls back to single launches
+    if (!ring_ok(m.p[j])) return IB_E_UNSUPPORTED;   // caller falls back to single launches
     m.p[j].dbias_part = dbias_part ? dbias_part[j] : nullptr;      // [IB_WGRAD_MAX_SPLIT][N] fp32, rows 0 .. split-1 written
     nslab_out[j] = split;
     m.blk0[j] = blocks;
-    blocks += tiles * split;
+    blocks += m.p[j].tiles_m * m.p[j].tiles_n * split;
   }
   m.blk0[n] = blocks;
   IB_PATH(IB_PATH_RING_MULTI);
@@ -1590,8 +1084,7 @@ extern "C" int ib_linear_wgrad_slabs_multi_tb(int n, const void* const* dz, cons
                                               const void* zu, int64_t ldzu, const void* s_rows, int64_t lds, float* dw1_slabs,
                                               float* db1_slabs, int64_t B, int64_t temb, int64_t hidden, int64_t out,
                                               ib_stream_t stream) {
-  if (n <= 0 || n > WG_MAX || !dz || !lddz || !x || !ldx || !workspace || !workspace_bytes || !nslab_out || !M || !N || !K)
-    return IB_E_ARG;
+  if (!wgrad_group_args_ok(n, dz, lddz, x, ldx, workspace, workspace_bytes, nslab_out, M, N, K)) return IB_E_ARG;
   if (dtype != IB_BF16 || !ib_time_mlp_bwd_supported(temb, hidden, out)) return IB_E_UNSUPPORTED;
   if (!de || !w2 || !zu || !s_rows || !dw1_slabs || !db1_slabs || B <= 0) return IB_E_ARG;
   if (ld_de < out || ldw2 < hidden || ldzu < hidden || lds < temb || ld_de % 8 || ldw2 % 8 || lds % 8) return IB_E_ARG;
@@ -1750,14 +1243,12 @@ extern "C" int ib_linear_ln_fwd(const void* x, int64_t ldx, const void* w, int64
   if (workspace_bytes < (size_t)split * M * N * sizeof(float)) return IB_E_WORKSPACE;
   GemmParams p{};
   p.A = x; p.lda = ldx; p.B = w; p.ldb = ldw; p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  p.seg = 1; p.act = IB_ACT_NONE; p.ablate = IB_ABLATE; p.prof = IB_AB_PROF(g_gemm_prof);
-  p.vecA = vec_load_ok<bf16_t>(p.A, p.lda); p.vecB = vec_load_ok<bf16_t>(p.B, p.ldb);
-  p.gldsA = glds_ok<bf16_t>(p.A, p.lda); p.gldsB = glds_ok<bf16_t>(p.B, p.ldb);
-  p.tiles_n = (p.N + BN - 1) / BN; p.tiles_m = (p.M + BM - 1) / BM;
+  p.seg = 1; p.act = IB_ACT_NONE;
+  fill_common<bf16_t>(p);
   p.k_chunk = chunk; p.xcd_group = 1;
   p.C = workspace; p.ldc = N; p.slab_stride = (int64_t)M * N; p.accumulate = 0; p.vecC = 1;
   if (!gemm_done) {
-    if (!ring_ok(p, IB_BF16, p.K, chunk)) return IB_E_UNSUPPORTED;
+    if (!ring_ok(p)) return IB_E_UNSUPPORTED;
     IB_PATH(IB_PATH_LINLN);
     hipLaunchKernelGGL((gemm_ring_kernel<true, true, EPI_WGRAD>), dim3(p.tiles_m * p.tiles_n * split), dim3(NTHREADS), 0, s, p);
     IB_CHECK_LAUNCH();

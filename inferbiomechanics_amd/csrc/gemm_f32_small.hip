@@ -10,7 +10,8 @@
 // MI355X_MICROARCH.md, Matrix cores) with both operands loaded as 8-byte pieces: lane (r, kq) loads k = 8 S + 2 kq + e,
 // e = 0, 1, and MFMA step e of super-step S multiplies the k's {8 S + 2 kq' + e}: the reduction index is permuted
 // identically on both operands, so no lane movement is needed.
-#include "ib_common.h"
+#include "launch.h"
+#include "gemm_families.h"
 #include <stdlib.h>
 
 namespace {
@@ -206,16 +207,11 @@ int ib_f32_small_fwd_try(const float* x, int64_t ldx, const float* w, int64_t ld
   if (!few_tiles(M, N) || K < 64 || K % 2 != 0 || ldx % 2 != 0 || ldw % 2 != 0 || !ib_aligned(x, 8) || !ib_aligned(w, 8))
     return IB_E_UNSUPPORTED;
   const dim3 grid((unsigned)((N + 15) / 16), (unsigned)((M + 15) / 16)), block(256);
-#define IB_FS(ACT) hipLaunchKernelGGL((f32_small_fwd_kernel<ACT>), grid, block, 0, s, x, ldx, w, ldw, bias, y, ldy, z, ldz, (int)M, (int)N, (int)K)
-  switch (act) {
-    case IB_ACT_RELU: IB_FS(IB_ACT_RELU); break;
-    case IB_ACT_TANH: IB_FS(IB_ACT_TANH); break;
-    case IB_ACT_SIGMOID: IB_FS(IB_ACT_SIGMOID); break;
-    case IB_ACT_SILU: IB_FS(IB_ACT_SILU); break;
-    case IB_ACT_ELU: IB_FS(IB_ACT_ELU); break;
-    default: IB_FS(IB_ACT_NONE); break;
-  }
-#undef IB_FS
+  IB_PATH(IB_PATH_SMALLM);
+  ib_dispatch_act(act, [&](auto a) {
+    hipLaunchKernelGGL((f32_small_fwd_kernel<decltype(a)::value>), grid, block, 0, s, x, ldx, w, ldw, bias, y, ldy, z, ldz,
+                       (int)M, (int)N, (int)K);
+  });
   IB_CHECK_LAUNCH();
   return IB_OK;
 }
@@ -227,16 +223,11 @@ int ib_f32_small_dgrad_try(const float* dz, int64_t lddz, const float* w, int64_
   if (!few_tiles(M, K) || N < 64 || N % 2 != 0 || lddz % 2 != 0 || !ib_aligned(dz, 8)) return IB_E_UNSUPPORTED;
   if (act != IB_ACT_NONE && !aux) return IB_E_UNSUPPORTED;
   const dim3 grid((unsigned)((K + 15) / 16), (unsigned)((M + 15) / 16)), block(256);
-#define IB_FS(ACT) hipLaunchKernelGGL((f32_small_dgrad_kernel<ACT>), grid, block, 0, s, dz, lddz, w, ldw, aux, ldaux, addend, ldadd, dx, lddx, (int)M, (int)N, (int)K)
-  switch (act) {
-    case IB_ACT_RELU: IB_FS(IB_ACT_RELU); break;
-    case IB_ACT_TANH: IB_FS(IB_ACT_TANH); break;
-    case IB_ACT_SIGMOID: IB_FS(IB_ACT_SIGMOID); break;
-    case IB_ACT_SILU: IB_FS(IB_ACT_SILU); break;
-    case IB_ACT_ELU: IB_FS(IB_ACT_ELU); break;
-    default: IB_FS(IB_ACT_NONE); break;
-  }
-#undef IB_FS
+  IB_PATH(IB_PATH_SMALLM);
+  ib_dispatch_act(act, [&](auto a) {
+    hipLaunchKernelGGL((f32_small_dgrad_kernel<decltype(a)::value>), grid, block, 0, s, dz, lddz, w, ldw, aux, ldaux, addend,
+                       ldadd, dx, lddx, (int)M, (int)N, (int)K);
+  });
   IB_CHECK_LAUNCH();
   return IB_OK;
 }
@@ -246,6 +237,7 @@ int ib_f32_small_wgrad_bias_try(const float* dz, int64_t lddz, const float* x, i
   static const int off = ib_ab_int("IB_NO_F32_SMALL", 0);
   if (off || M > 256) return IB_E_UNSUPPORTED;
   const dim3 grid((unsigned)((K + 63) / 64), (unsigned)((N + 15) / 16)), block(256);
+  IB_PATH(IB_PATH_WGRAD_SMALL);
   hipLaunchKernelGGL(f32_small_wgrad_kernel, grid, block, 0, s, dz, lddz, x, ldx, dw, lddw, dbias, accumulate, (int)M, (int)N, (int)K);
   IB_CHECK_LAUNCH();
   return IB_OK;

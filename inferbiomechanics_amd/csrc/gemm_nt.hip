@@ -24,7 +24,8 @@
 //                                                            caller keeps a transposed bf16 copy of the weight, see
 //                                                            ib_transpose_multi)
 #include "wave_prims.h"
-#include "gemm_nt.h"
+#include "launch.h"
+#include "gemm_families.h"
 #include "head_jobs.h"
 #include <type_traits>
 
@@ -368,6 +369,7 @@ int ib_gemm_nt_try(const void* A, int64_t lda, const void* B, int64_t ldb, void*
   if (!ib_al16({A, B, C, bias, aux, addend}) || lda % 8 || ldb % 8 || ldc % 8) return IB_E_UNSUPPORTED;
   if (M * lda >= (int64_t(1) << 31) || N * ldb >= (int64_t(1) << 31)) return IB_E_UNSUPPORTED;     // 32-bit element offsets
   if ((aux && ldaux % 8) || (addend && ldadd % 8)) return IB_E_UNSUPPORTED;
+  if (fwd_act < IB_ACT_NONE || fwd_act > IB_ACT_ELU || bwd_act < IB_ACT_NONE || bwd_act > IB_ACT_ELU) return IB_E_UNSUPPORTED;
   if (bwd_act != IB_ACT_NONE && (bwd_act == IB_ACT_SILU || !aux || fwd_act != IB_ACT_NONE)) return IB_E_UNSUPPORTED;
   IB_PATH(IB_PATH_NT);
   NtParams p{};
@@ -377,24 +379,13 @@ int ib_gemm_nt_try(const void* A, int64_t lda, const void* B, int64_t ldb, void*
   p.tiles_m = (int)((M + BM - 1) / BM); p.tiles_n = (int)((N + BN - 1) / BN);
   p.tiles_mn = p.tiles_m * p.tiles_n; p.splits = 1; p.kchunk = (int)K; p.slab = nullptr;
   p.prof = IB_AB_PROF(g_nt_prof);
-  if (bwd_act != IB_ACT_NONE) {
-    switch (bwd_act) {
-      case IB_ACT_RELU: return launch<IB_ACT_NONE, IB_ACT_RELU>(p, s);
-      case IB_ACT_TANH: return launch<IB_ACT_NONE, IB_ACT_TANH>(p, s);
-      case IB_ACT_SIGMOID: return launch<IB_ACT_NONE, IB_ACT_SIGMOID>(p, s);
-      case IB_ACT_ELU: return launch<IB_ACT_NONE, IB_ACT_ELU>(p, s);
-      default: return IB_E_UNSUPPORTED;
-    }
-  }
-  switch (fwd_act) {
-    case IB_ACT_NONE: return launch<IB_ACT_NONE, IB_ACT_NONE>(p, s);
-    case IB_ACT_RELU: return launch<IB_ACT_RELU, IB_ACT_NONE>(p, s);
-    case IB_ACT_TANH: return launch<IB_ACT_TANH, IB_ACT_NONE>(p, s);
-    case IB_ACT_SIGMOID: return launch<IB_ACT_SIGMOID, IB_ACT_NONE>(p, s);
-    case IB_ACT_SILU: return launch<IB_ACT_SILU, IB_ACT_NONE>(p, s);
-    case IB_ACT_ELU: return launch<IB_ACT_ELU, IB_ACT_NONE>(p, s);
-    default: return IB_E_UNSUPPORTED;
-  }
+  if (bwd_act != IB_ACT_NONE)
+    return ib_dispatch_act(bwd_act, [&](auto a) -> int {
+      constexpr int ACT = decltype(a)::value;
+      if constexpr (ACT == IB_ACT_NONE || ACT == IB_ACT_SILU) return IB_E_UNSUPPORTED;   // refused above: no such kernel
+      else return launch<IB_ACT_NONE, ACT>(p, s);
+    });
+  return ib_dispatch_act(fwd_act, [&](auto a) -> int { return launch<decltype(a)::value, IB_ACT_NONE>(p, s); });
 }
 
 // Split-K form for GEMMs with few output tiles and a long reduction (the sampler's FFN output projection at a few thousand

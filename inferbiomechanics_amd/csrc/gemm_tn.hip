@@ -22,7 +22,7 @@
 #include <type_traits>
 
 #include "wave_prims.h"
-#include "gemm_nt.h"
+#include "gemm_families.h"
 #include "time_bwd.h"
 
 namespace {

@@ -23,7 +23,7 @@
 #include <type_traits>
 
 #include "wave_prims.h"
-#include "gemm_nt.h"
+#include "gemm_families.h"
 
 namespace {
 

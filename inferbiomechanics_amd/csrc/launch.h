@@ -1,4 +1,4 @@
-// Host-side dispatch of an entry point's storage dtype (and vector width) onto a kernel template.
+// Host-side dispatch of an entry point's storage dtype (and vector width), or of its activation, onto a kernel template.
 #pragma once
 #include <type_traits>
 
@@ -16,6 +16,21 @@ static inline int ib_dispatch_dtype(int dtype, F&& launch) {
   else return IB_E_DTYPE;
   IB_CHECK_LAUNCH();
   return IB_OK;
+}
+
+// f(tag) with std::integral_constant<int, IB_ACT_...>, `decltype(tag)::value` being a kernel's activation argument, and
+// f's value handed back.  A code outside IB_ACT_RELU .. IB_ACT_ELU runs as IB_ACT_NONE: the entry points refuse unknown
+// codes before they dispatch.
+template <typename F>
+static inline auto ib_dispatch_act(int act, F&& f) {
+  switch (act) {
+    case IB_ACT_RELU: return f(std::integral_constant<int, IB_ACT_RELU>{});
+    case IB_ACT_TANH: return f(std::integral_constant<int, IB_ACT_TANH>{});
+    case IB_ACT_SIGMOID: return f(std::integral_constant<int, IB_ACT_SIGMOID>{});
+    case IB_ACT_SILU: return f(std::integral_constant<int, IB_ACT_SILU>{});
+    case IB_ACT_ELU: return f(std::integral_constant<int, IB_ACT_ELU>{});
+    default: return f(std::integral_constant<int, IB_ACT_NONE>{});
+  }
 }
 
 // a vector width as a type: `decltype(width)::value` is a kernel's template argument

@@ -139,6 +139,33 @@ def test_kernel_digests_follow_the_kernel_not_its_name_or_place():
     assert {d for _, d in _kernels(STEP.format(mode=1), STEP.format(mode=1) + "x")} == {base[0][1]}
 
 
+SMALLM = "_ZN12_GLOBAL__N_16smallm17fwd_smallm_kernelILi{act}ELi1EEEvPKDF16blS3_lPKfS3_lS3_liPDF16bliii"
+SKINNY = "_ZN6skinny19dgrad_skinny_kernelILi0EEEvPKDF16blS2_lS2_lPDF16blPfiii"
+
+
+def test_short_name_walks_nested_namespaces():
+    assert kr.short_name(SMALLM.format(act=1)) == "smallm::fwd_smallm_kernel<1,1>"
+    assert kr.short_name(SKINNY) == "skinny::dgrad_skinny_kernel<0>"
+    assert kr.short_name("_ZN6wsmall19wgrad_smallm_kernelEPKDF16blS2_lPflS3_iiii") == "wsmall::wgrad_smallm_kernel"
+    # two kernels of one nested namespace keep separate names, and the same text still hashes the same under both
+    got = _kernels(SMALLM.format(act=1), SMALLM.format(act=2))
+    assert [k for k, _ in got] == ["smallm::fwd_smallm_kernel<1,1>", "smallm::fwd_smallm_kernel<2,1>"]
+    assert got[0][1] == got[1][1] == _kernels(STEP.format(mode=1), SKINNY)[1][1]
+
+
+def test_kernel_digests_ignore_the_file_wide_count_of_long_branches():
+    def long_branch(k):     # a branch relaxed out of range: its anchor label counts through the whole file, not the kernel
+        return lambda t: t.replace("\ts_waitcnt lgkmcnt(0)\n", f"\ts_getpc_b64 s[4:5]\n.Lpost_getpc{k}:\n"
+                                   f"\ts_add_u32 s4, s4, (.LBB1_2-.Lpost_getpc{k})&4294967295\n\ts_waitcnt lgkmcnt(0)\n")
+
+    a = _kernels(STEP.format(mode=1), STEP.format(mode=2), long_branch(28))
+    assert a[0][1] != a[1][1]                                          # the added instructions are seen
+    assert _kernels(STEP.format(mode=1), STEP.format(mode=2), long_branch(175)) == a
+    assert _kernels(STEP.format(mode=1), STEP.format(mode=2), long_branch(1)) == a      # a count equal to the kernel's ordinal
+    other = _kernels(STEP.format(mode=1), STEP.format(mode=2), lambda t: long_branch(28)(t).replace("(.LBB1_2-", "(.LBB1_3-"))
+    assert other[0] == a[0] and other[1][1] != a[1][1]                 # the branch's target still counts
+
+
 def test_kernel_digests_see_instructions_descriptor_registers_and_order():
     base = _kernels(STEP.format(mode=1), STEP.format(mode=2))
     swap = ("\ts_load_dwordx2 s[2:3], s[0:1], 0x0\n\ts_cbranch_scc1 .LBB1_2\n",

@@ -1,4 +1,5 @@
-"""Exact parity for every kernel family of csrc/gemm.hip and csrc/gemm_f32_small.hip, on both sides of each dispatch edge.
+"""Exact parity for every kernel family of csrc/gemm.hip, csrc/gemm_small.hip and csrc/gemm_f32_small.hip, on both sides of
+each dispatch edge.
 
 Every case of CASES names an entry point, a dtype, a shape, an operand layout, its epilogue options and the kernel family the
 dispatch must pick (hip.PATH_NAMES, read from ib_debug_last_path() right after the call); "-" marks a shape the entry point
@@ -119,6 +120,12 @@ CASES = [
     _c("f32_wgrad_bias_small_256_rows", "wgrad_bias", "fp32", 256, 300, 200, "wgrad_small", acc=True, c_pad=3),
     _c("f32_wgrad_bias_refused_257_rows", "wgrad_bias", "fp32", 257, 300, 200, "-"),
     _c("wgrad_slabs_small", "wgrad_slabs", "bf16", 512, 256, 192, "wgrad_small"),
+    # slabs past the one-pass kernel: M % 64 != 0 (or M < 4096 alone) keeps the TN kernels out; chunk 64, reduction % 32
+    _c("wgrad_slabs_ring_1056_rows", "wgrad_slabs", "bf16", 1056, 256, 192, "ring128"),
+    _c("wgrad_slabs_generic_1025_rows", "wgrad_slabs", "bf16", 1025, 256, 192, "generic"),
+    # K % 4 != 0 fails the one-slab branch, a pitch of 190 the ring's 16-byte pieces; scalar slab stores
+    _c("wgrad_slabs_generic_k190", "wgrad_slabs", "bf16", 512, 256, 190, "generic"),
+    _c("f32_wgrad_slabs_generic", "wgrad_slabs", "fp32", 512, 300, 200, "generic"),
     # ---- grouped weight gradients on the ring kernel: M % 64 != 0, so the TN kernels decline ----------------------------
     _c("multi_ring_m4000", "multi", "bf16", 4000, 0, 0, "ring_multi", probs=[(300, 512, 4, 0), (512, 512, 0, 0),
                                                                             (512, 300, 0, 4)]),
@@ -140,7 +147,8 @@ FAMILIES = {
     ("ib_linear_fwd", "fp32", "generic"), ("ib_linear_dgrad", "fp32", "generic"), ("ib_linear_wgrad", "fp32", "generic"),
     ("ib_linear_dgrad_skinny", "bf16", "skinny"),
     ("ib_linear_wgrad", "bf16", "wgrad_small"), ("ib_linear_wgrad_bias", "bf16", "wgrad_small"),
-    ("ib_linear_wgrad_slabs", "bf16", "wgrad_small"),
+    ("ib_linear_wgrad_slabs", "bf16", "wgrad_small"), ("ib_linear_wgrad_slabs", "bf16", "ring128"),
+    ("ib_linear_wgrad_slabs", "bf16", "generic"), ("ib_linear_wgrad_slabs", "fp32", "generic"),
     ("ib_linear_wgrad_slabs_multi", "bf16", "ring_multi"),
     ("ib_linear_fwd", "fp32", "smallm"), ("ib_linear_dgrad", "fp32", "smallm"), ("ib_linear_wgrad_bias", "fp32", "wgrad_small"),
     ("ib_linear_fwd", "bf16", "nt256x128"),

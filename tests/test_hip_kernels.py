@@ -1,7 +1,7 @@
 """Kernel-level parity: every C-ABI entry point against float64 restatements (oracle / plain math)
 on seeded inputs.  Tolerances: fp32 mode <= 1e-3 relative (north_star; in practice ~1e-6), bf16 mode
 <= 3e-2 relative to the tensor's max magnitude (bf16 storage has 8 significant bits).  The GEMM tests
-(linear fwd / dgrad, the small-M tiles) also bound every element on its own (close_gemm): one bf16
+(linear fwd / dgrad, the small-M tiles of csrc/gemm_small.hip) also bound every element on its own (close_gemm): one bf16
 rounding of the result, 2^-8 |e|, plus fp32 accumulation, K 2^-23 (|x| @ |w|^T), with e the float64
 product of the stored (rounded) operands -- a bias or tile lost on a single column fails there even when
 it hides under 3e-2 of the maximum.  Index / table ops (gathers, schedule tables) are bit-exact.
@@ -61,7 +61,7 @@ def close_gemm(actual, expected, x, w, what, act_scale=1.0):
 
 
 def test_tr16_transposing_read_layout(hip):
-    """ds_read_b64_tr_b16 must deliver in[8*(lane/16)+q][lane%16] as element q (what gemm.hip assumes)."""
+    """ds_read_b64_tr_b16 must deliver in[8*(lane/16)+q][lane%16] as element q (what gemm.hip and gemm_small.hip assume)."""
     img = torch.arange(64 * 16, dtype=torch.int16).reshape(64, 16)
     out = torch.zeros(64, 4, dtype=torch.int16, device=DEV)
     hip.selftest_tr16(img.to(DEV), out)

@@ -38,14 +38,18 @@ def hipcc():
 
 def short_name(mangled):
     """_ZN12_GLOBAL__N_120ffn_chain_fwd_kernelILb1ELb1ELb1ELb0EEEvNS_12FfnFwdParamsE -> ffn_chain_fwd_kernel<1,1,1,0>
-    (template arguments that are float / bf16 element types, bools or ints; anything else keeps the mangled tail)"""
-    m = re.match(r"_ZN(?:12_GLOBAL__N_1)?(\d+)", mangled)
+    _ZN12_GLOBAL__N_16smallm17fwd_smallm_kernelILi1ELi1EEEvPKDF16bl... -> smallm::fwd_smallm_kernel<1,1>
+    (nested namespaces are walked and joined with "::", the anonymous one left out; template arguments that are float /
+    bf16 element types, bools or ints; anything else keeps the mangled tail)"""
+    m = re.match(r"_ZN(?:12_GLOBAL__N_1)?(?=\d)", mangled)
     if not m:
         return mangled
-    n = int(m.group(1))
-    start = m.end()
-    name = mangled[start:start + n]
-    rest = mangled[start + n:]
+    parts, pos = [], m.end()
+    while (d := re.match(r"\d+", mangled[pos:])):
+        n = int(d.group())
+        parts.append(mangled[pos + d.end():pos + d.end() + n])
+        pos += d.end() + n
+    name, rest = "::".join(parts), mangled[pos:]
     if rest.startswith("I"):
         # leading element types (f = float, DF16b = bf16), then bool / int literals
         types, body = [], rest[1:]
@@ -117,7 +121,7 @@ def kernel_digests(asm):
     from the first to the last that names its symbol outside the metadata note -- its section, label and code, its
     .amdhsa_kernel descriptor and its resource .set lines -- with its own symbol replaced by "<kernel>", any other kernel's
     by that kernel's short name, the kernel's ordinal in the file taken out of its local labels (.LBB<n>_,
-    .Lfunc_end<n>), and the comment the compiler puts behind a line's code cut off with the blanks before it (on a loop's
+    .Lfunc_end<n>), the file-wide count of long branches out of their anchors (.Lpost_getpc<k>), and the comment the compiler puts behind a line's code cut off with the blanks before it (on a loop's
     label it names the ordinal again: "; in Loop: Header=BB<n>_80 Depth=1"; a line with a string in it is left whole):
     what remains is the instructions, the descriptor and the register counts"""
     lines = asm.split(".amdgpu_metadata")[0].splitlines()
@@ -127,6 +131,8 @@ def kernel_digests(asm):
     for sym in syms:
         at = [i for i, l in enumerate(lines) if any(m.group() == sym for m in names.finditer(l))]
         text = "\n".join(l if '"' in l else re.sub(r"\s*;.*$", "", l) for l in lines[at[0]:at[-1] + 1]) + "\n"
+        seen = {}      # .Lpost_getpc<k> (a long branch's anchor) counts through the whole file: renumbered per kernel, as #0, #1, ...
+        text = re.sub(r"\.Lpost_getpc(\d+)", lambda m: f".Lpost_getpc#{seen.setdefault(m.group(1), len(seen))}", text)
         n = re.search(r"^\.Lfunc_end(\d+):", text, re.M)
         if n:
             text = re.sub(rf"(\.L[A-Za-z_]+){n.group(1)}(?!\d)", r"\1", text)
