@@ -156,6 +156,9 @@ class AbstractCommand:
         if hasattr(target, 'column_range'):                  # denoisers: `train --record-range`
             r = checkpoint.get('column_range')
             target.column_range = None if r is None else torch.as_tensor(r, dtype=torch.float32).cpu()
+        if hasattr(target, 'column_stats'):                  # denoisers: `train --standardize`; older checkpoints have no key
+            r = checkpoint.get('column_stats')
+            target.column_stats = None if r is None else torch.as_tensor(r, dtype=torch.float32).cpu()
         osd = checkpoint.get('optimizer_state_dict')
         if optimizer is not None and hasattr(optimizer, 'load_optimizer_state_dict'):      # HipTrainer
             if osd is not None:

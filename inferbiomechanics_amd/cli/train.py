@@ -106,6 +106,14 @@ class TrainCommand(AbstractCommand):
                             'training windows (one pass over the device-resident cache) and save them in the checkpoints; '
                             '`analyze --x0-clip` / `visualize --x0-clip` take their bounds from there. A resumed run keeps '
                             'the checkpoint\'s record. Default: off.')
+        p.add_argument('--standardize', action='store_true', default=False,
+                       help='[diffusion] Train on per-column standardised windows z = (x - mean) / scale: the mean and the '
+                            'population standard deviation of every column are taken over the training windows when the '
+                            'window cache is built (--window-cache; one more pass over its fp32 source) and saved in the '
+                            'checkpoints; `analyze` / `visualize` read them from there and give labels in raw units. A '
+                            'resumed run keeps the checkpoint\'s statistics (and may then run with --eager); it must be '
+                            'given the flag again. With --record-range the range is taken over the standardised table: the '
+                            'bounds of --x0-clip are in the sampler\'s units. Default: off.')
         p.add_argument('--no-ema-warmup', action='store_true',
                        help='Use --ema-decay from the first step (default: min(decay, (1 + step) / (10 + step))).')
 
@@ -123,6 +131,7 @@ class TrainCommand(AbstractCommand):
         check_cond_cols(model_type, getattr(args, 'cond_cols', 0))
         check_cond_drop(args)
         check_record_range(args)
+        check_standardize(args)
         if getattr(args, 'seed', None) is not None:
             torch.manual_seed(args.seed)
         geometry = self.ensure_geometry(args.geometry_folder)
@@ -209,6 +218,22 @@ class TrainCommand(AbstractCommand):
         if args.window_cache == 'hbm' and not (diffusion and getattr(args, 'synthetic_windows', 0) > 0):
             raise SystemExit("--window-cache hbm names the device-resident synthetic table: it needs a diffusion model type "
                              "and --synthetic-windows N (a cache FILE takes a path)")
+        epoch_checkpoint, _ = self.load_latest_checkpoint(model, optimizer=trainer if trainer is not None else optimizer,
+                                                          checkpoint_dir=checkpoint_dir)
+        if diffusion and model.cond_cols != cond_cols:       # the checkpoint's value: a resumed run keeps training that model
+            raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained with --cond-cols {model.cond_cols}, this run "
+                             f"asks for {cond_cols}: resume with the same value or use another --checkpoint-dir")
+        if diffusion and model.cond_drop != cond_drop:
+            raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained with --cond-drop {model.cond_drop}, this run "
+                             f"asks for {cond_drop}: resume with the same value or use another --checkpoint-dir")
+        # the checkpoint is read before the cache is built: a resumed run hands its statistics to the cache
+        standardize = diffusion and getattr(args, 'standardize', False)
+        column_stats = model.column_stats if diffusion else None
+        if diffusion and (column_stats is not None) != standardize and (epoch_checkpoint >= 0 or not standardize):
+            was, now = ("with", "without") if column_stats is not None else ("without", "with")
+            raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained {was} --standardize, this run is {now} it: its "
+                             f"weights are for the other units; resume with the same choice or use another --checkpoint-dir")
+        check_standardize(args, have_stats=column_stats is not None)
         cache = None
         if args.window_cache and trainer is not None:
             from ..data.WindowCache import DeviceMotionCache, DeviceWindowCache, PackedWindows, wait_for_file
@@ -239,29 +264,35 @@ class TrainCommand(AbstractCommand):
                 dist.barrier()
             if in_hbm:
                 cache = DeviceMotionCache.synthetic(len(train_dataset), window, train_dataset.feat, device,
-                                                    model.compute_dtype, seed=0)
+                                                    model.compute_dtype, seed=0, standardize=standardize,
+                                                    stats=column_stats)
             elif diffusion:
                 import numpy as np
                 cache = DeviceMotionCache(torch.from_numpy(np.load(args.window_cache, mmap_mode='r')), device,
-                                          model.compute_dtype)
+                                          model.compute_dtype, stats=column_stats, standardize=standardize)
             else:
                 cache = DeviceWindowCache(PackedWindows.load(args.window_cache), device)
             print(f"[rank={rank}] window cache: {len(cache)} windows, "
                   f"{cache.table.numel() * cache.table.element_size() / 2**20:.1f} MiB in HBM")
 
-        epoch_checkpoint, _ = self.load_latest_checkpoint(model, optimizer=trainer if trainer is not None else optimizer,
-                                                          checkpoint_dir=checkpoint_dir)
-        if diffusion and model.cond_cols != cond_cols:       # the checkpoint's value: a resumed run keeps training that model
-            raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained with --cond-cols {model.cond_cols}, this run "
-                             f"asks for {cond_cols}: resume with the same value or use another --checkpoint-dir")
-        if diffusion and model.cond_drop != cond_drop:
-            raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained with --cond-drop {model.cond_drop}, this run "
-                             f"asks for {cond_drop}: resume with the same value or use another --checkpoint-dir")
+        if standardize and model.column_stats is None:       # a new run: the statistics the cache was built with
+            model.column_stats = cache.column_stats.cpu()
         if diffusion and getattr(args, 'record_range', False) and model.column_range is None:
             # asked for and not in the checkpoint (a resumed run keeps the checkpoint's record): one pass over the cache
             model.column_range = cache.column_range().cpu()
         from .. import hip
         noise_seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        std = None                                           # (mean, inv) on the device: every raw window goes through them
+        if standardize:
+            st = model.column_stats.to(device)
+            std = (st[:, 0].contiguous(), hip.inv_scale(st[:, 1].contiguous()))
+
+        def standardized(x0, dtype):
+            """raw windows x0 [B, T, D] (host or device) -> z = (x0 - mean) * inv on the device in `dtype`: standardised in
+            fp32 and rounded once, as the window cache's table is (hip.column_affine)"""
+            xf = x0.to(device, torch.float32).contiguous()
+            return hip.column_affine(xf, torch.empty(tuple(xf.shape), dtype=dtype, device=device), std[0], std[1],
+                                     mode=hip.STANDARDIZE)
 
         def device_batch(x0, stream_id, draw):
             """x0 [B, T, D] (host or device) -> (x0, t, eps) on the device in the model's dtype; t / eps from the
@@ -270,7 +301,7 @@ class TrainCommand(AbstractCommand):
             every epoch (the same noise every time: comparable reports); the --eager training loop's is the global step
             epoch * batches-per-epoch + i, which only ever increases and is right again after a resume -- a window meets
             fresh (t, eps) in every epoch, as with the host generator of the reference-style loop"""
-            xd = x0.to(device, model.compute_dtype).contiguous()
+            xd = x0.to(device, model.compute_dtype).contiguous() if std is None else standardized(x0, model.compute_dtype)
             ed = torch.empty_like(xd)
             td = torch.empty(xd.shape[0], dtype=torch.int64, device=device)
             hip.diffusion_draw(noise_seed, step=int(draw), stream_id=stream_id, eps=ed, t=td,
@@ -331,7 +362,8 @@ class TrainCommand(AbstractCommand):
                     train_eval.record_result(trainer.result)
                 elif diffusion:
                     if trainer is not None:
-                        loss = trainer.step_x0(batch.to(device, non_blocking=True))
+                        loss = trainer.step_x0(batch.to(device, non_blocking=True) if std is None
+                                               else standardized(batch, torch.float32))
                         train_eval.losses.append(loss.detach().clone())
                     else:
                         optimizer.zero_grad()
@@ -445,6 +477,21 @@ def check_record_range(args: argparse.Namespace):
                          "--synthetic-windows, or a file) and the fused trainer (not --eager)")
 
 
+def check_standardize(args: argparse.Namespace, have_stats: bool = None):
+    """--standardize: a diffusion model type; the statistics come from the checkpoint a run resumes (have_stats; --eager is
+    fine then) or, on a new run, from the pass that builds the window cache (--window-cache and the fused trainer).
+    have_stats None: before the checkpoint is read, the model type alone is checked"""
+    if not getattr(args, 'standardize', False):
+        return
+    if not is_diffusion(args.model_type):
+        raise SystemExit(f"--standardize standardises the windows of a diffusion denoiser: model type '{args.model_type}' "
+                         f"has none (the regression models take raw inputs)")
+    if have_stats is False and (not getattr(args, 'window_cache', None) or getattr(args, 'eager', False)):
+        raise SystemExit("--standardize takes the column statistics from the pass that builds the window cache: a run with no "
+                         "checkpoint to take them from needs --window-cache (`hbm` with --synthetic-windows, or a file) and "
+                         "the fused trainer (not --eager)")
+
+
 def make_torch_optimizer(opt_type: str, params, lr: float):
     table = {'adagrad': torch.optim.Adagrad, 'adam': torch.optim.Adam, 'sgd': torch.optim.SGD,
              'rmsprop': torch.optim.RMSprop, 'adadelta': torch.optim.Adadelta, 'adamax': torch.optim.Adamax}
@@ -458,7 +505,9 @@ def save_checkpoint(checkpoint_dir: str, epoch: int, batch: int, model, opt):
     """file grammar of train.py:271-278; keys are saved WITHOUT DDP's `module.` prefix.  A trainer with an EMA adds
     'ema_state_dict' (the model's state dict over the EMA weights) and 'ema' ({'decay', 'warmup'}); without one the file
     holds the three reference keys only.  A denoiser trained with --cond-cols N > 0 adds 'cond_cols': N, one trained with
-    --cond-drop P > 0 'cond_drop': P, one trained with --record-range 'column_range': fp32 [feat_dim, 2]."""
+    --cond-drop P > 0 'cond_drop': P, one trained with --record-range 'column_range': fp32 [feat_dim, 2], one trained with
+    --standardize 'column_stats': fp32 [feat_dim, 2] = per column (mean, scale).  With both, column_range is taken over the
+    standardised table: it is in the units the sampler works in, the units of the x0 clip's bounds."""
     os.makedirs(checkpoint_dir, exist_ok=True)
     path = f"{checkpoint_dir}/epoch_{epoch}_batch_{batch}.pt"
     osd = opt.optimizer_state_dict() if hasattr(opt, 'optimizer_state_dict') else opt.state_dict()
@@ -471,6 +520,8 @@ def save_checkpoint(checkpoint_dir: str, epoch: int, batch: int, model, opt):
         ckpt['cond_drop'] = float(model.cond_drop)
     if getattr(model, 'column_range', None) is not None:
         ckpt['column_range'] = torch.as_tensor(model.column_range, dtype=torch.float32).detach().cpu().clone()
+    if getattr(model, 'column_stats', None) is not None:
+        ckpt['column_stats'] = torch.as_tensor(model.column_stats, dtype=torch.float32).detach().cpu().clone()
     if getattr(opt, 'ema', None) is not None:
         ckpt['ema_state_dict'] = opt.ema_state_dict()
         ckpt['ema'] = {'decay': opt.ema_decay, 'warmup': opt.ema_warmup}

@@ -234,11 +234,14 @@ class DeviceMotionCache:
 
     @classmethod
     def synthetic(cls, num_windows: int, window: int, feat: int, device, dtype: torch.dtype = torch.bfloat16,
-                  seed: int = 0) -> "DeviceMotionCache":
+                  seed: int = 0, standardize: bool = False, stats=None) -> "DeviceMotionCache":
         """x0 ~ N(0,1) synthetic windows drawn straight into HBM by the counter-based generator
-        (csrc/noise.hip) -- a million 50 x 300 windows (30 GB of bf16) in milliseconds, nothing staged through the host"""
+        (csrc/noise.hip) -- a million 50 x 300 windows (30 GB of bf16) in milliseconds, nothing staged through the host.
+        standardize: the moments are taken from the table as stored and applied to it in place (there is no fp32 source);
+        stats (fp32 [D, 2] = (mean, scale), a resumed run's) are applied in place instead"""
         from .. import hip
         self = cls.__new__(cls)
+        self.column_stats = None
         self.device = torch.device(device)
         self.window, self.feat = int(window), int(feat)
         per = self.window * self.feat
@@ -250,10 +253,26 @@ class DeviceMotionCache:
             hip.diffusion_draw(seed, step=a // rows, stream_id=0x20000000, eps=part)
         if self.pitch != per:
             self.table[:, per:].zero_()
+        if stats is not None:
+            mean, scale = cls._given_stats(stats, self.feat, self.device)
+            inv = hip.inv_scale(scale)
+        elif standardize:
+            shift = self.table[0, :self.feat].to(torch.float32).contiguous()
+            acc = hip.column_moments(self.table, self.window, self.feat, shift,
+                                     hip.column_moments_acc(self.feat, self.device))
+            mean, scale, inv = hip.column_moments_finalize(acc, len(self) * self.window, shift)
+        if stats is not None or standardize:
+            hip.column_affine(self.table, self.table, mean, inv, mode=hip.STANDARDIZE, window=self.window)
+            self.column_stats = torch.stack([mean, scale], dim=1)
         return self
 
-    def __init__(self, windows, device, dtype: torch.dtype = torch.bfloat16, chunk_windows: int = 2048):
+    def __init__(self, windows, device, dtype: torch.dtype = torch.bfloat16, chunk_windows: int = 2048, stats=None,
+                 standardize: bool = False):
+        """stats (fp32 [D, 2] = per column (mean, scale), a resumed run's) or standardize=True (computed here: one more
+        pass over the source): the table holds z = (x - mean) / scale, standardised in fp32 and rounded to the compute
+        dtype once, and `column_stats` holds (mean, scale) on the device.  Neither: the raw values, column_stats None."""
         self.device = torch.device(device)
+        self.column_stats = None
         n = len(windows)
         if n == 0:
             raise ValueError("DeviceMotionCache: no windows")
@@ -266,18 +285,53 @@ class DeviceMotionCache:
         self.table = torch.zeros((n, self.pitch), dtype=dtype, device=self.device)
         pin = self.device.type == "cuda"
         stage = torch.zeros((min(chunk_windows, n), per), dtype=torch.float32, pin_memory=pin)
-        for a in range(0, n, stage.shape[0]):
-            b = min(n, a + stage.shape[0])
-            if isinstance(windows, torch.Tensor):
-                stage[:b - a].copy_(windows[a:b].reshape(b - a, per))
-            else:
-                for i in range(a, b):
-                    w = windows[i]
-                    if tuple(w.shape) != (self.window, self.feat):
-                        raise ValueError(f"DeviceMotionCache: window {i} is {tuple(w.shape)}, expected "
-                                         f"{(self.window, self.feat)}")
-                    stage[i - a].copy_(w.reshape(per))
-            self.table[a:b, :per].copy_(stage[:b - a])      # fp32 -> compute dtype on the device (one rounding)
+
+        def chunks():
+            """(a, b) of every chunk, the pinned stage holding windows a .. b - 1 as fp32 rows"""
+            for a in range(0, n, stage.shape[0]):
+                b = min(n, a + stage.shape[0])
+                if isinstance(windows, torch.Tensor):
+                    stage[:b - a].copy_(windows[a:b].reshape(b - a, per))
+                else:
+                    for i in range(a, b):
+                        w = windows[i]
+                        if tuple(w.shape) != (self.window, self.feat):
+                            raise ValueError(f"DeviceMotionCache: window {i} is {tuple(w.shape)}, expected "
+                                             f"{(self.window, self.feat)}")
+                        stage[i - a].copy_(w.reshape(per))
+                yield a, b
+
+        if stats is None and not standardize:
+            for a, b in chunks():
+                self.table[a:b, :per].copy_(stage[:b - a])  # fp32 -> compute dtype on the device (one rounding)
+            return
+        from .. import hip
+        raw = torch.empty(tuple(stage.shape), dtype=torch.float32, device=self.device)   # a chunk in fp32 on the device
+        if stats is None:
+            # pass 1: fp64 sums about the first frame of the first window (include/ib_hip_standardize.h)
+            shift = first[0].to(torch.float32).to(self.device).contiguous()
+            acc = hip.column_moments_acc(self.feat, self.device)
+            for a, b in chunks():
+                raw[:b - a].copy_(stage[:b - a])
+                hip.column_moments(raw[:b - a], self.window, self.feat, shift, acc)
+            mean, scale, inv = hip.column_moments_finalize(acc, n * self.window, shift)
+        else:
+            mean, scale = self._given_stats(stats, self.feat, self.device)
+            inv = hip.inv_scale(scale)
+        # pass 2: standardised in fp32, rounded to the compute dtype once
+        for a, b in chunks():
+            raw[:b - a].copy_(stage[:b - a])
+            hip.column_affine(raw[:b - a], self.table[a:b], mean, inv, mode=hip.STANDARDIZE, window=self.window)
+        self.column_stats = torch.stack([mean, scale], dim=1)
+
+    @staticmethod
+    def _given_stats(stats, feat: int, device):
+        """(mean, scale) fp32 [D] on the device from given statistics [D, 2]"""
+        stats = torch.as_tensor(stats, dtype=torch.float32)
+        if tuple(stats.shape) != (feat, 2) or not bool(torch.isfinite(stats).all()) or not bool((stats[:, 1] > 0).all()):
+            raise ValueError(f"DeviceMotionCache: stats must be finite fp32 [D, 2] = [{feat}, 2] (mean, scale) with "
+                             f"scale > 0, got {tuple(stats.shape)}")
+        return tuple(stats[:, j].contiguous().to(device) for j in (0, 1))
 
     def __len__(self) -> int:
         return self.table.shape[0]

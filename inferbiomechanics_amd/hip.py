@@ -14,7 +14,8 @@ sampler updates (csrc/stitch.hip) are declared in a second header, ``include/ib_
 resampled masked loop (csrc/resample.hip) in a sixth, ``include/ib_hip_resample.h`` (``_RESAMPLE_SIGS``), the order statistics
 of a posterior ensemble (csrc/ensemble.hip) in a seventh, ``include/ib_hip_ensemble.h`` (``_ENSEMBLE_SIGS``), the x0 clip of a
 sampling step and the per-column range of a window table (csrc/clip.hip) in an eighth, ``include/ib_hip_clip.h``
-(``_CLIP_SIGS``); a name may be declared once in the eight.
+(``_CLIP_SIGS``), the per-column standardisation of the diffusion windows (csrc/standardize.hip) in a ninth,
+``include/ib_hip_standardize.h`` (``_STANDARDIZE_SIGS``); a name may be declared once in the nine.
 """
 from __future__ import annotations
 
@@ -39,6 +40,7 @@ CFG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_cfg.h"
 RESAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_resample.h")
 ENSEMBLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_ensemble.h")
 CLIP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_clip.h")
+STANDARDIZE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_standardize.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -109,9 +111,11 @@ _TABLES = (_SIGS, _STITCH_SIGS, _HEAD_SIGS, _SDE_SIGS, _CFG_SIGS, _RESAMPLE_SIGS
 _ENSEMBLE_SIGS = _parse_header(_read_header(ENSEMBLE_HEADER_PATH))                  # what is done with the samples
 _CLIP_SIGS = _parse_header(_read_header(CLIP_HEADER_PATH))                          # a seam of the sampling step, off by default
 _HEADERS = _TABLES + (_ENSEMBLE_SIGS, _CLIP_SIGS)
-_ALL_SIGS = {_n: _v for _t in _HEADERS for _n, _v in _t.items()}  # every entry point: what _sig() looks up and lib() binds
-if len(_ALL_SIGS) != sum(len(_t) for _t in _HEADERS):
-    _twice = sorted(n for n in _ALL_SIGS if sum(n in _t for _t in _HEADERS) > 1)
+_STANDARDIZE_SIGS = _parse_header(_read_header(STANDARDIZE_HEADER_PATH))            # data preparation, off by default
+_EVERY_HEADER = _HEADERS + (_STANDARDIZE_SIGS,)
+_ALL_SIGS = {_n: _v for _t in _EVERY_HEADER for _n, _v in _t.items()}  # every entry point: what _sig() looks up and lib() binds
+if len(_ALL_SIGS) != sum(len(_t) for _t in _EVERY_HEADER):
+    _twice = sorted(n for n in _ALL_SIGS if sum(n in _t for _t in _EVERY_HEADER) > 1)
     raise HipError(f"declared in two headers: {_twice}")
 _kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_STITCH_KMAX[ \t]+(\d+)[ \t]*$", _read_header(STITCH_HEADER_PATH), flags=re.M)
 if _kmax is None:
@@ -159,6 +163,11 @@ def ensemble_symbols() -> List[str]:
 def clip_decls() -> List[str]:
     """Every function include/ib_hip_clip.h declares"""
     return sorted(_CLIP_SIGS)
+
+
+def standardize_decls() -> List[str]:
+    """Every function include/ib_hip_standardize.h declares"""
+    return sorted(_STANDARDIZE_SIGS)
 
 
 def _sig(name: str):
@@ -2730,6 +2739,125 @@ def column_range(table, window: int, feat: int, out=None):
     _check(lib().ib_column_range(_ptr(table), N, T, D, pitch, _ptr(partial), G, _ptr(out), dtype_code(table.dtype),
                                  stream_ptr()), "ib_column_range")
     return out
+
+
+STANDARDIZE, DESTANDARDIZE = 0, 1     # ib_column_affine's modes
+MOMENTS_SLOTS = 1024                  # workgroups (= slots of acc) of a moments pass: four per CU, the rest by grid stride
+
+
+def _column_vector(what, name, t, D=None):
+    """t is a contiguous fp32 [D] vector -> D"""
+    _req(t, name, torch.float32, 1)
+    if not t.is_contiguous() or t.numel() < 1 or (D is not None and t.numel() != D):
+        raise HipError(f"{what}: {name} must be contiguous fp32 [D]" + (f" = [{D}]" if D is not None else "")
+                       + f", got {tuple(t.shape)}")
+    return t.numel()
+
+
+def column_moments_acc(feat: int, device, slots: int = MOMENTS_SLOTS):
+    """the zeroed fp64 [G, D, 2] accumulator of column_moments"""
+    return torch.zeros((int(slots), int(feat), 2), dtype=torch.float64, device=device)
+
+
+def column_moments(src, window: int, feat: int, shift, acc):
+    """acc fp64 [G, D, 2] += per column (sum d, sum d d), d = x - shift[c] in fp64, over the windows of src [n, pitch] (fp32 /
+    bf16, contiguous; window i holds `window` = T contiguous rows of `feat` = D values, pitch >= T D, the pad is not read).
+    shift fp32 [D].  The caller zeroes acc once (column_moments_acc) and may call this chunk after chunk; workgroup g adds
+    into slot g alone in a fixed order, so the sums are bit-reproducible (csrc/standardize.hip)."""
+    what = "column_moments"
+    _req(src, "src", None, 2)
+    T, D = int(window), int(feat)
+    n, pitch = (int(v) for v in src.shape)
+    if not src.is_contiguous() or n < 1 or T < 1 or D < 1 or pitch < T * D:
+        raise HipError(f"{what}: src must be contiguous [n, pitch] with n >= 1 and pitch >= T D = {T * D}, got "
+                       f"{tuple(src.shape)}")
+    _column_vector(what, "shift", shift, D)
+    _req(acc, "acc", torch.float64, 3)
+    if acc.shape[0] < 1 or acc.shape[0] > 65535 or tuple(acc.shape[1:]) != (D, 2) or not acc.is_contiguous():
+        raise HipError(f"{what}: acc must be contiguous fp64 [G, D, 2] = [1 .. 65535, {D}, 2], got {tuple(acc.shape)}")
+    _check(lib().ib_column_moments_accum(_ptr(src), n, T, D, pitch, _ptr(shift), _ptr(acc), int(acc.shape[0]),
+                                         dtype_code(src.dtype), stream_ptr()), "ib_column_moments_accum")
+    return acc
+
+
+def column_moments_finalize(acc, count: int, shift, min_std: float = 1e-6):
+    """(mean, scale, inv) fp32 [D] from the sums of column_moments over `count` rows: the slots summed in order, in fp64
+    md = S1 / count, var = max(S2 / count - md md, 0) (population), mean = shift + md, s = sqrt(var) rounded to fp32,
+    scale = s if s > min_std else 1, inv = 1 / scale from the fp32 scale (inv_scale gives the same)."""
+    what = "column_moments_finalize"
+    _req(acc, "acc", torch.float64, 3)
+    G, D = int(acc.shape[0]), int(acc.shape[1])
+    if G < 1 or G > 65535 or D < 1 or acc.shape[2] != 2 or not acc.is_contiguous():
+        raise HipError(f"{what}: acc must be contiguous fp64 [G, D, 2], got {tuple(acc.shape)}")
+    _column_vector(what, "shift", shift, D)
+    count, min_std = int(count), float(min_std)
+    if count < 1 or not min_std >= 0.0:
+        raise HipError(f"{what}: count = {count} must be positive and min_std = {min_std} not negative")
+    mean = torch.zeros(D, dtype=torch.float32, device=acc.device)
+    scale, inv = torch.ones_like(mean), torch.ones_like(mean)
+    _check(lib().ib_column_moments_finalize(_ptr(acc), G, D, count, _ptr(shift), min_std, _ptr(mean), _ptr(scale), _ptr(inv),
+                                            stream_ptr()), "ib_column_moments_finalize")
+    return mean, scale, inv
+
+
+def inv_scale(scale):
+    """fp32 inv = (float)(1.0 / (double)scale), the header's rule, computed on the host in float64: what a checkpoint's
+    fp32 scale gives is what the moments' finalisation gave"""
+    if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32:
+        raise HipError("inv_scale: scale must be an fp32 tensor")
+    return (1.0 / scale.detach().to("cpu", torch.float64)).to(torch.float32).to(scale.device)
+
+
+def _affine_geometry(what, name, t, window):
+    """(N, T, win, row) of a window table [N, pitch] (row = None: the caller's D) or of a state [B, T, ld]"""
+    _req(t, name)
+    if not t.is_contiguous() or t.dim() not in (2, 3) or t.numel() == 0:
+        raise HipError(f"{what}: {name} must be a contiguous table [N, pitch] or state [B, T, ld], got {tuple(t.shape)}")
+    if t.dim() == 3:
+        N, T, ld = (int(v) for v in t.shape)
+        if window is not None and int(window) != T:
+            raise HipError(f"{what}: window = {window} but {name} is {tuple(t.shape)}")
+        return N, T, T * ld, ld
+    if window is None or int(window) < 1:
+        raise HipError(f"{what}: {name} is a table [N, pitch]: pass window = T")
+    return int(t.shape[0]), int(window), int(t.shape[1]), None
+
+
+def column_affine(src, dst, a, b, cols=None, mode=STANDARDIZE, window=None):
+    """dst = the per-column affine of src over the columns cols = (c0, w) (default: all D = len(b)), csrc/standardize.hip:
+    mode STANDARDIZE (0): (x - a[c]) b[c] with a = mean, b = inv (two fp32 roundings); mode DESTANDARDIZE (1):
+    fma(x, b[c], a[c]) with a = mean (None: x b[c]), b = scale; then rounded to dst's dtype.  src and dst are each a window
+    table [N, pitch] (`window` = T rows of D values per window, pitch >= T D) or a state [B, T, ld] (D <= ld), fp32 / bf16
+    in any pair, with N and T in common; dst may be src.  Columns outside the window and pads are neither read nor written."""
+    what = "column_affine"
+    if mode not in (STANDARDIZE, DESTANDARDIZE):
+        raise HipError(f"{what}: mode must be STANDARDIZE (0) or DESTANDARDIZE (1), got {mode!r}")
+    D = _column_vector(what, "b", b)
+    if a is not None:
+        _column_vector(what, "a", a, D)
+    elif mode == STANDARDIZE:
+        raise HipError(f"{what}: standardising needs a (the mean)")
+    geo = []
+    for name, t in (("src", src), ("dst", dst)):
+        N, T, win, row = _affine_geometry(what, name, t, window)
+        row = D if row is None else row
+        if row < D or win < T * row:
+            raise HipError(f"{what}: {name} {tuple(t.shape)} does not hold {T} rows of D = {D} columns per window")
+        geo.append((N, T, win, row))
+    if geo[0][:2] != geo[1][:2] or src.device != dst.device:
+        raise HipError(f"{what}: src {tuple(src.shape)} and dst {tuple(dst.shape)} differ in windows or rows")
+    try:
+        c0, w = (0, D) if cols is None else (int(v) for v in cols)
+    except (TypeError, ValueError):
+        raise HipError(f"{what}: cols must be (c0, w), got {cols!r}") from None
+    if c0 < 0 or w <= 0 or c0 + w > D:
+        raise HipError(f"{what}: the column window ({c0}, {w}) does not lie inside D = {D} columns")
+    if src.data_ptr() == dst.data_ptr() and (src.dtype != dst.dtype or geo[0] != geo[1]):
+        raise HipError(f"{what}: in place needs equal dtype and strides")
+    (N, T, swin, srow), (_, _, dwin, drow) = geo
+    _check(lib().ib_column_affine(_ptr(src), dtype_code(src.dtype), swin, srow, _ptr(dst), dtype_code(dst.dtype), dwin, drow,
+                                  _ptr(a), _ptr(b), N, T, c0, w, int(mode), stream_ptr()), "ib_column_affine")
+    return dst
 
 
 def ensemble_stats(x, mean=None, std=None):

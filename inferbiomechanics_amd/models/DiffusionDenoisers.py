@@ -30,6 +30,10 @@ class _DenoiserBase(HipModule):
         # fp32 [feat_dim, 2]: the (minimum, maximum) every column takes in the training windows (`train --record-range`; saved
         # in the checkpoint), what `analyze --x0-clip` / `visualize --x0-clip` take their bounds from.  None: not recorded.
         self.column_range = None
+        # fp32 [feat_dim, 2]: per column (mean, scale) of the training windows; the model was trained on
+        # z = (x - mean) / scale (`train --standardize`; saved in the checkpoint).  The predictor standardises what it is given
+        # and de-standardises what it samples; column_range and the x0 clip's bounds are then in z units.  None: raw units.
+        self.column_stats = None
         self._tables = None
         self._plan = None
 

@@ -54,7 +54,15 @@ class DiffusionLabelPredictor:
     x0_clip = X0Clip(lo, hi, mode, quantile) (diffusion/sampler.py) keeps the x0 every step predicts inside per-column
     bounds in every sampler the predictor builds; the bounds are given for the 30 label columns (they are then infinite on
     the columns in front of them) or for all feat_dim columns -- the observed columns are skipped by the mask anyway.  What
-    it does to label accuracy on trained checkpoints is unmeasured."""
+    it does to label accuracy on trained checkpoints is unmeasured.
+    A denoiser trained on standardised windows (model.column_stats = fp32 [D, 2] per column (mean, scale), `train
+    --standardize`; read per call, like cond_cols) is sampled in its own units: the observation matrix goes to the model's
+    device and is standardised over all D columns by one ``ib_column_affine`` launch, the sampler's result (compute dtype)
+    is de-standardised by one more into an fp32 [B K, F, D] tensor -- bf16 would quantise an offset column again -- and
+    everything behind that (the label split, ``ib_ensemble_stats``, ``ib_ensemble_order`` against raw labels) runs on it
+    unchanged, in raw units.  The bounds of x0_clip are then in the sampler's units, z = (x - mean) / scale: the units of
+    the checkpoint's column_range when `train --record-range --standardize` recorded it.  The null condition of a guided
+    step (zeros) is then the column mean."""
 
     def __init__(self, model, num_sample_steps: int = 100, seed: int = 0, output_data_format: str = 'all_frames',
                  use_graph: bool = True, eta: float = 0.0, num_samples: int = 1, solver: str = 'ddim',
@@ -90,6 +98,7 @@ class DiffusionLabelPredictor:
         self._mask = None                    # label_mask of the last (F, D): one tensor, so the sampler checks it once
         self._trial = None                   # ((hop, blend), StitchedDDIMSampler, mask_cols) of the last predict_trial
         self._trial_ens = None               # the same of the last predict_trial_ensemble, a StochasticStitchedSampler
+        self._stats = None                   # (model.column_stats it was made from, mean, scale, inv on the model's device)
 
     @staticmethod
     def _wide_clip(x0_clip: Optional[X0Clip], feat: int) -> Optional[X0Clip]:
@@ -176,7 +185,39 @@ class DiffusionLabelPredictor:
         if truth is not None:
             self.last_crps, self.last_rank, self.last_inside = (self._split_block(res[k]) for k in ('crps', 'rank', 'inside'))
 
+    def _column_stats(self):
+        """(mean, scale, inv) fp32 [D] on the model's device, or None: model.column_stats, read per call"""
+        stats = getattr(self.model, 'column_stats', None)
+        if stats is None:
+            return None
+        if self._stats is None or self._stats[0] is not stats:
+            self.model.ensure_packed()
+            dev = self.model._flat.device
+            st = torch.as_tensor(stats, dtype=torch.float32)
+            if tuple(st.shape) != (self.model.feat_dim, 2):
+                raise ValueError(f"DiffusionLabelPredictor: model.column_stats must be fp32 [feat_dim, 2] = "
+                                 f"[{self.model.feat_dim}, 2] (mean, scale), got {tuple(st.shape)}")
+            mean, scale = (st[:, j].contiguous().to(dev) for j in (0, 1))
+            self._stats = (stats, mean, scale, hip.inv_scale(scale))
+        return self._stats[1:]
+
     def _sample(self, sampler, obs: torch.Tensor, mask: torch.Tensor, draw: int, ids_name: Optional[str], labels=None):
+        """_sample_units in the denoiser's units: with model.column_stats, obs is standardised on the way in and the
+        sampler's result de-standardised into fp32 on the way out (one launch each); without, nothing is launched"""
+        stats = self._column_stats()
+        if stats is None:
+            return self._sample_units(sampler, obs, mask, draw, ids_name, labels, lambda x: x)
+        mean, scale, inv = stats
+        raw = obs.to(device=mean.device, dtype=torch.float32).contiguous()
+        obs = hip.column_affine(raw, torch.empty_like(raw), mean, inv, mode=hip.STANDARDIZE)
+
+        def to_raw(x):
+            out = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+            return hip.column_affine(x.contiguous(), out, mean, scale, mode=hip.DESTANDARDIZE)
+        return self._sample_units(sampler, obs, mask, draw, ids_name, labels, to_raw)
+
+    def _sample_units(self, sampler, obs: torch.Tensor, mask: torch.Tensor, draw: int, ids_name: Optional[str], labels,
+                      to_raw):
         """the labels of obs [B, F, D] from `sampler`, a masked one.  ids_name None: row b starts from the draw
         (seed, draw + b) and follows its one deterministic trajectory.  Otherwise it is the id keyword of the sampler's
         sample(): every row is replicated K times, the member ids (member_ids) key both the start draws and the step noise,
@@ -186,11 +227,11 @@ class DiffusionLabelPredictor:
         self.last_interval = self.last_crps = self.last_rank = self.last_inside = None
         if ids_name is None:
             z = torch.cat([sampler.draw_start(1, F, D, self.seed, draw + b) for b in range(B)])
-            return self.split_labels(sampler.sample(z, obs, mask))
+            return self.split_labels(to_raw(sampler.sample(z, obs, mask)))
         ids = self.member_ids(draw, B)
         z = torch.cat([sampler.draw_start(1, F, D, self.seed, i) for i in ids])
         members = obs.unsqueeze(1).expand(B, K, F, D).reshape(B * K, F, D)
-        x = sampler.sample(z, members, mask, **{ids_name: ids})
+        x = to_raw(sampler.sample(z, members, mask, **{ids_name: ids}))
         mean, std = hip.ensemble_stats(x.view(B, K, F, D))
         self.last_std = self.split_labels(std)
         if self.interval is not None:
