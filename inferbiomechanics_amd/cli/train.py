@@ -116,6 +116,20 @@ class TrainCommand(AbstractCommand):
                             'bounds of --x0-clip are in the sampler\'s units. Default: off.')
         p.add_argument('--no-ema-warmup', action='store_true',
                        help='Use --ema-decay from the first step (default: min(decay, (1 + step) / (10 + step))).')
+        p.add_argument('--lr-schedule', choices=['constant', 'linear', 'cosine'], default='constant',
+                       help='What the learning rate does after the warmup: stay at --learning-rate, or decay to '
+                            '--lr-min-ratio times it at step --lr-total-steps along a line or a half cosine, and stay there. '
+                            'The rate of a step is computed inside the fused optimizer launches from the device step counter. '
+                            'Not with --eager.')
+        p.add_argument('--lr-warmup-steps', type=int, default=0,
+                       help='Raise the rate linearly over the first N optimizer steps: step s <= N runs at s / N times '
+                            '--learning-rate (0 = no warmup).')
+        p.add_argument('--lr-total-steps', type=int, default=0,
+                       help='The step at which a linear / cosine decay ends (0 = --epochs x batches per epoch on this rank, '
+                            'honouring --max-steps). A resumed run must give the same schedule: pass this explicitly when '
+                            '--epochs changes.')
+        p.add_argument('--lr-min-ratio', type=float, default=0.0,
+                       help='The rate a decay ends at, as a fraction of --learning-rate, in [0, 1].')
 
     # ------------------------------------------------------------------------------------------
     def run(self, args: argparse.Namespace):
@@ -128,6 +142,7 @@ class TrainCommand(AbstractCommand):
         diffusion = is_diffusion(model_type)
 
         check_ema_args(args)
+        check_lr_schedule(args)
         check_cond_cols(model_type, getattr(args, 'cond_cols', 0))
         check_cond_drop(args)
         check_record_range(args)
@@ -207,19 +222,35 @@ class TrainCommand(AbstractCommand):
                 ddp_model = DDP(model, device_ids=[device.index], output_device=device.index)
             optimizer = make_torch_optimizer(args.opt_type, model.parameters(), args.learning_rate)
         else:
+            # batches per epoch on this rank, as the loop below will find them: the sampler's share (drop_last), whole batches
+            # only for the denoisers and from a window cache, cut at --max-steps
+            share = len(train_dataset) // world_size
+            whole = diffusion or bool(args.window_cache)
+            per_epoch = share // args.batch_size if whole else -(-share // args.batch_size)
+            lr_schedule = resolve_lr_schedule(args, min(per_epoch, args.max_steps) if args.max_steps else per_epoch)
+            if lr_schedule is not None:
+                print(f"Learning-rate schedule: {lr_schedule} over a base rate of {args.learning_rate:g}")
             trainer = HipTrainer(model, "diffusion" if diffusion else "regression", args.opt_type, args.learning_rate,
                                  args=args, use_graph=not args.no_graph, bucket_mb=args.bucket_mb,
                                  ema_decay=getattr(args, 'ema_decay', 0.0),
                                  ema_warmup=not getattr(args, 'no_ema_warmup', False), cond_cols=cond_cols,
-                                 cond_drop=cond_drop)
+                                 cond_drop=cond_drop, lr_schedule=lr_schedule)
 
         if getattr(args, 'loss_every', 1) < 1:
             raise SystemExit("--loss-every must be >= 1")
         if args.window_cache == 'hbm' and not (diffusion and getattr(args, 'synthetic_windows', 0) > 0):
             raise SystemExit("--window-cache hbm names the device-resident synthetic table: it needs a diffusion model type "
                              "and --synthetic-windows N (a cache FILE takes a path)")
-        epoch_checkpoint, _ = self.load_latest_checkpoint(model, optimizer=trainer if trainer is not None else optimizer,
-                                                          checkpoint_dir=checkpoint_dir)
+        from ..hip import HipError
+        try:
+            epoch_checkpoint, _ = self.load_latest_checkpoint(model, optimizer=trainer if trainer is not None else optimizer,
+                                                              checkpoint_dir=checkpoint_dir)
+        except HipError as exc:
+            if "learning-rate schedule" not in str(exc):
+                raise
+            raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --lr-schedule / --lr-warmup-steps / "
+                             f"--lr-min-ratio and pass --lr-total-steps explicitly (0 derives it from --epochs and "
+                             f"--max-steps, which may have changed), or use another --checkpoint-dir") from None
         if diffusion and model.cond_cols != cond_cols:       # the checkpoint's value: a resumed run keeps training that model
             raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained with --cond-cols {model.cond_cols}, this run "
                              f"asks for {cond_cols}: resume with the same value or use another --checkpoint-dir")
@@ -391,6 +422,8 @@ class TrainCommand(AbstractCommand):
                 if (i + 1) % args.report_every == 0 or last:
                     logging.info(f'[rank={rank}] Batch {i} Training Set Evaluation: ')
                     train_eval.print_report(args, reset=False) if not diffusion else train_eval.print_report(reset=False)
+                    if trainer is not None and trainer._sched_args():
+                        print(f"[rank={rank}] learning rate {trainer.current_lr():.6g} at step {trainer.steps_done + 1}")
                     if rank == 0:
                         save_checkpoint(checkpoint_dir, epoch, i, model, trainer if trainer is not None else optimizer)
                 if last:
@@ -405,6 +438,8 @@ class TrainCommand(AbstractCommand):
             logging.info('-' * 80)
             logging.info(f'[rank={rank}] Epoch {epoch}/{args.epochs} Training Set Evaluation: ')
             train_eval.print_report(args, log_to_wandb=log_to_wandb) if not diffusion else train_eval.print_report()
+            if trainer is not None and trainer._sched_args():
+                print(f"[rank={rank}] epoch {epoch}: learning rate {trainer.current_lr():.6g} at step {trainer.steps_done + 1}")
             logging.info('-' * 80)
 
         if prev_stream is not None:                 # in-process callers (tests, tools) get their stream back
@@ -439,6 +474,34 @@ def check_ema_args(args: argparse.Namespace):
         raise SystemExit(f"--ema-decay must lie in [0, 1) (0 = off, 0.999-0.9999 are usual), got {d}")
     if d > 0 and getattr(args, 'eager', False):
         raise SystemExit("--ema-decay needs the fused trainer: --eager runs torch.optim, which keeps no EMA of the weights")
+
+
+def check_lr_schedule(args: argparse.Namespace):
+    """--lr-schedule / --lr-warmup-steps / --lr-total-steps / --lr-min-ratio: the rate is computed inside the fused optimizer
+    launches, so --eager (torch.optim at one rate) has none; what can be refused before the data is opened is refused here"""
+    kind, w = getattr(args, 'lr_schedule', 'constant'), getattr(args, 'lr_warmup_steps', 0)
+    T, m = getattr(args, 'lr_total_steps', 0), getattr(args, 'lr_min_ratio', 0.0)
+    if not 0.0 <= m <= 1.0:
+        raise SystemExit(f"--lr-min-ratio must lie in [0, 1], got {m}")
+    if w < 0 or T < 0:
+        raise SystemExit(f"--lr-warmup-steps and --lr-total-steps must be >= 0, got {w} and {T}")
+    if (kind != 'constant' or w > 0) and getattr(args, 'eager', False):
+        raise SystemExit("--lr-schedule / --lr-warmup-steps need the fused trainer: --eager runs torch.optim at one rate")
+    if kind != 'constant' and T > 0 and T <= w:
+        raise SystemExit(f"--lr-schedule {kind} needs --lr-total-steps > --lr-warmup-steps, got {T} and {w}")
+
+
+def resolve_lr_schedule(args: argparse.Namespace, batches_per_epoch: int):
+    """the LrSchedule of the flags, or None for a constant rate without warmup.  --lr-total-steps 0: --epochs x
+    batches_per_epoch (this rank's, --max-steps honoured by the caller)"""
+    from ..lr_schedule import LrSchedule, active
+    check_lr_schedule(args)
+    kind, w = getattr(args, 'lr_schedule', 'constant'), getattr(args, 'lr_warmup_steps', 0)
+    T = getattr(args, 'lr_total_steps', 0) or int(args.epochs) * int(batches_per_epoch)
+    if kind != 'constant' and T <= w:
+        raise SystemExit(f"--lr-schedule {kind} needs more steps in all than --lr-warmup-steps {w}: --epochs x batches per "
+                         f"epoch gives {T}; train longer, warm up for fewer steps or pass --lr-total-steps")
+    return active(LrSchedule(kind, w, T if kind != 'constant' else 0, getattr(args, 'lr_min_ratio', 0.0)))
 
 
 def check_cond_cols(model_type: str, cond_cols: int, feat_dim: int = None):

@@ -6,6 +6,7 @@
 // advances an exponential moving average of the parameters from the new value it already holds in registers: one more fp32
 // read and write per parameter, no launch of its own, and the decay follows the device step counter under graph replay.
 #include "ib_common.h"
+#include "../../include/ib_hip_sched.h"
 
 namespace {
 
@@ -34,6 +35,29 @@ struct OptSources {
   GradSrc s[OPT_MAXSRC]; int n;
   const float* loss_col; int64_t loss_ld; int loss_rows; float loss_scale; float* loss_out;   // optional scalar
 };
+
+// Learning-rate schedule (include/ib_hip_sched.h states it): warmup s / w, then 1, a linear or a cosine decay to m over
+// steps w .. T, clamped beyond T.  Double throughout, every operation rounded on its own (contraction off: the host's
+// restatement, lr_schedule.LrSchedule.lr_at, is then bitwise this except for the last place of cos), the result rounded to
+// fp32 once.  s is wave-uniform; the cosine is evaluated only on the decay of a cosine schedule (w < s < T).
+struct SchedArgs { int kind; int32_t warmup, total; float min_ratio; };
+
+__device__ __forceinline__ float lr_scheduled(float lr, const SchedArgs& sc, int s) {
+#pragma clang fp contract(off)
+  const double sd = (double)s, wd = (double)sc.warmup;
+  double f = 1.0;
+  if (s <= sc.warmup) {
+    f = sd / wd;
+  } else if (sc.kind != IB_SCHED_CONSTANT && s >= sc.total) {
+    f = (double)sc.min_ratio;                    // u = 1: m + (1 - m) * 0, without asking cos(pi) for an exact -1
+  } else if (sc.kind != IB_SCHED_CONSTANT) {
+    const double u = (sd - wd) / ((double)sc.total - wd);
+    const double m = (double)sc.min_ratio;
+    const double shape = sc.kind == IB_SCHED_COSINE ? 0.5 * (1.0 + cos(3.14159265358979323846 * u)) : 1.0 - u;
+    f = m + (1.0 - m) * shape;
+  }
+  return (float)((double)lr * f);
+}
 
 __device__ __forceinline__ float opt_update(const OptArgs& a, float p, float g, float& s1, float& s2, float bc1,
                                             float bc2s) {
@@ -157,8 +181,14 @@ __device__ __forceinline__ void apply4(const OptArgs& a, int64_t i, float4 g, fl
 // a column-sum range: 16 float4 columns x 16 row groups, LDS combine in the order of colsum_segments_kernel, update.
 // EMA: every element this launch updates also updates a.ema (kind-3 ranges leave both untouched); EMA = false is the
 // kernel without it, instruction for instruction.
-template <bool SRC, bool EMA>
-__global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int main_blocks) {
+// Sched: empty for the kernel as it always was -- optim_kernel<SRC, EMA> has the argument list (a, S, main_blocks) and the
+// instructions it had -- or one SchedArgs behind main_blocks: the rate of this launch is then the schedule's (lr_scheduled
+// above, from the step number of the bias corrections), put in a.lr's place once at the head.  One kernel template and not a
+// body shared by two kernels: inlined from a device function the same statements compiled to other code (blockDim.x is
+// lowered there without the kernel's uniform-work-group-size attribute, and the sources form came out scheduled differently).
+template <bool SRC, bool EMA, typename... Sched>
+__global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int main_blocks, Sched... sc) {
+  static_assert(sizeof...(Sched) <= 1, "at most one SchedArgs");
   // self-counting mode (ticket != NULL): *step_dev holds the number of COMPLETED steps; every block reads it on
   // entry, and the block that draws the last exit ticket publishes step and resets the ticket -- it exits after
   // every other block has entered (and therefore read the old value), so no block can see the new count.
@@ -166,6 +196,7 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int
   // the buffer (a layer's range, issued as soon as its gradient is complete) takes part in a self-counting step whose
   // last launch publishes.
   const int step = a.step_dev ? *(volatile int32_t*)a.step_dev + (a.ticket ? 1 : a.step) : a.step;
+  if constexpr (sizeof...(Sched) == 1) a.lr = lr_scheduled(a.lr, sc..., step);
   // bias corrections in double (torch computes them as Python floats) -- Adam / Adamax only: two double-precision pow()
   // are several hundred instructions at the head of every thread, ahead of its first load
   float bc1 = 1.f, bc2s = 1.f;
@@ -299,10 +330,18 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int
   }
 }
 
-// the two launchers behind the C entries: ema == NULL launches optim_kernel<SRC, false>, the kernel without the EMA
+// the probe: out[i] = the rate of step steps[i], by the function the kernel above calls
+__global__ __launch_bounds__(256) void lr_schedule_eval_kernel(float lr, SchedArgs sc, const int32_t* __restrict__ steps,
+                                                               float* __restrict__ out, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = lr_scheduled(lr, sc, steps[i]);
+}
+
+// the two launchers behind the C entries: ema == NULL launches optim_kernel<SRC, false>, the kernel without the EMA;
+// sc != NULL launches optim_kernel<SRC, EMA, SchedArgs> in their place (the *_sched entries)
 int optim_plain(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr, float grad_scale, int32_t step,
                 int32_t* step_dev, int32_t* ticket, void* shadow_bf16, float* ema, float ema_decay, int ema_warmup,
-                ib_stream_t stream) {
+                const SchedArgs* sc, ib_stream_t stream) {
   if (!p || !g || n <= 0 || opt < IB_OPT_SGD || opt > IB_OPT_ADAMAX) return IB_E_ARG;
   if (ticket && !step_dev) return IB_E_ARG;
   const bool need1 = opt != IB_OPT_SGD;
@@ -312,7 +351,11 @@ int optim_plain(int opt, float* p, const float* g, float* s1, float* s2, int64_t
   OptArgs a{p, g, need1 ? s1 : nullptr, need2 ? s2 : nullptr, reinterpret_cast<bf16_t*>(shadow_bf16),
             n, lr, grad_scale, step, step_dev, ticket, opt, ema, ema_decay, ema_warmup};
   const dim3 grid(ib_grid_1d(n / 4 + 1, 256));
-  if (ema)
+  if (sc && ema)
+    hipLaunchKernelGGL((optim_kernel<false, true, SchedArgs>), grid, dim3(256), 0, ib_s(stream), a, OptSources{}, 0, *sc);
+  else if (sc)
+    hipLaunchKernelGGL((optim_kernel<false, false, SchedArgs>), grid, dim3(256), 0, ib_s(stream), a, OptSources{}, 0, *sc);
+  else if (ema)
     hipLaunchKernelGGL((optim_kernel<false, true>), grid, dim3(256), 0, ib_s(stream), a, OptSources{}, 0);
   else
     hipLaunchKernelGGL((optim_kernel<false, false>), grid, dim3(256), 0, ib_s(stream), a, OptSources{}, 0);
@@ -324,7 +367,8 @@ int optim_sources(int opt, float* p, const float* g, float* s1, float* s2, int64
                   int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16, int nsrc, const int64_t* start,
                   const int64_t* len, const int32_t* kind, const void* const* base, const int64_t* stride,
                   const int32_t* count, const float* scale, const float* loss_col, int64_t loss_ld, int64_t loss_rows,
-                  float loss_scale, float* loss_out, float* ema, float ema_decay, int ema_warmup, ib_stream_t stream) {
+                  float loss_scale, float* loss_out, float* ema, float ema_decay, int ema_warmup, const SchedArgs* sc,
+                  ib_stream_t stream) {
   if (!p || !g || n <= 0 || opt < IB_OPT_SGD || opt > IB_OPT_ADAMAX) return IB_E_ARG;
   if (ticket && !step_dev) return IB_E_ARG;
   if (nsrc < 0 || nsrc > OPT_MAXSRC || (nsrc > 0 && (!start || !len || !kind || !base || !stride || !count))) return IB_E_ARG;
@@ -362,7 +406,11 @@ int optim_sources(int opt, float* p, const float* g, float* s1, float* s2, int64
   for (int j = 0; j < nsrc; ++j)
     if (kind[j] == 2) cs_blocks += (int)((len[j] + 63) / 64);
   const dim3 grid(main_blocks + cs_blocks);
-  if (ema)
+  if (sc && ema)
+    hipLaunchKernelGGL((optim_kernel<true, true, SchedArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, *sc);
+  else if (sc)
+    hipLaunchKernelGGL((optim_kernel<true, false, SchedArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, *sc);
+  else if (ema)
     hipLaunchKernelGGL((optim_kernel<true, true>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks);
   else
     hipLaunchKernelGGL((optim_kernel<true, false>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks);
@@ -375,6 +423,13 @@ bool ema_args_ok(const float* ema, float ema_decay) {
   return ema && ib_aligned(ema, 16) && ema_decay >= 0.f && ema_decay <= 1.f;
 }
 
+// the *_sched entries and the probe: kind 0..2, warmup >= 0, a decay needs total > warmup, min_ratio in [0, 1] (NaN fails too)
+bool sched_args_ok(int kind, int32_t warmup, int32_t total, float min_ratio) {
+  if (kind < IB_SCHED_CONSTANT || kind > IB_SCHED_COSINE || warmup < 0) return false;
+  if (kind != IB_SCHED_CONSTANT && total <= warmup) return false;
+  return min_ratio >= 0.f && min_ratio <= 1.f;
+}
+
 }  // namespace
 
 extern "C" int ib_optim_ticket_words(void) { return OPT_TICKET_LINE * (1 + OPT_TICKET_SUBS); }
@@ -382,7 +437,8 @@ extern "C" int ib_optim_ticket_words(void) { return OPT_TICKET_LINE * (1 + OPT_T
 extern "C" int ib_optim_step(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
                              float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16,
                              ib_stream_t stream) {
-  return optim_plain(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nullptr, 0.f, 0, stream);
+  return optim_plain(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nullptr, 0.f, 0, nullptr,
+                     stream);
 }
 
 extern "C" int ib_optim_step_ema(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
@@ -390,7 +446,7 @@ extern "C" int ib_optim_step_ema(int opt, float* p, const float* g, float* s1, f
                                  float* ema, float ema_decay, int ema_warmup, ib_stream_t stream) {
   if (!ema_args_ok(ema, ema_decay)) return IB_E_ARG;
   return optim_plain(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup,
-                     stream);
+                     nullptr, stream);
 }
 
 extern "C" int ib_optim_step_sources(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
@@ -401,7 +457,7 @@ extern "C" int ib_optim_step_sources(int opt, float* p, const float* g, float* s
                                      int64_t loss_rows, float loss_scale, float* loss_out, ib_stream_t stream) {
   return optim_sources(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nsrc, start, len, kind,
                        base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out, nullptr, 0.f, 0,
-                       stream);
+                       nullptr, stream);
 }
 
 extern "C" int ib_optim_step_sources_ema(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
@@ -414,5 +470,42 @@ extern "C" int ib_optim_step_sources_ema(int opt, float* p, const float* g, floa
   if (!ema_args_ok(ema, ema_decay)) return IB_E_ARG;
   return optim_sources(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nsrc, start, len, kind,
                        base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out, ema, ema_decay,
-                       ema_warmup, stream);
+                       ema_warmup, nullptr, stream);
+}
+
+extern "C" int ib_optim_step_sched(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
+                                   float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16,
+                                   float* ema, float ema_decay, int ema_warmup, int sched_kind, int32_t sched_warmup,
+                                   int32_t sched_total, float sched_min_ratio, ib_stream_t stream) {
+  if (!sched_args_ok(sched_kind, sched_warmup, sched_total, sched_min_ratio)) return IB_E_ARG;
+  if (ema && !ema_args_ok(ema, ema_decay)) return IB_E_ARG;
+  const SchedArgs sc{sched_kind, sched_warmup, sched_total, sched_min_ratio};
+  return optim_plain(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup,
+                     &sc, stream);
+}
+
+extern "C" int ib_optim_step_sources_sched(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
+                                           float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket,
+                                           void* shadow_bf16, int nsrc, const int64_t* start, const int64_t* len,
+                                           const int32_t* kind, const void* const* base, const int64_t* stride,
+                                           const int32_t* count, const float* scale, const float* loss_col,
+                                           int64_t loss_ld, int64_t loss_rows, float loss_scale, float* loss_out,
+                                           float* ema, float ema_decay, int ema_warmup, int sched_kind,
+                                           int32_t sched_warmup, int32_t sched_total, float sched_min_ratio,
+                                           ib_stream_t stream) {
+  if (!sched_args_ok(sched_kind, sched_warmup, sched_total, sched_min_ratio)) return IB_E_ARG;
+  if (ema && !ema_args_ok(ema, ema_decay)) return IB_E_ARG;
+  const SchedArgs sc{sched_kind, sched_warmup, sched_total, sched_min_ratio};
+  return optim_sources(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nsrc, start, len, kind,
+                       base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out, ema, ema_decay,
+                       ema_warmup, &sc, stream);
+}
+
+extern "C" int ib_lr_schedule_eval(float lr, int kind, int32_t warmup, int32_t total, float min_ratio, const int32_t* steps,
+                                   float* out, int64_t n, ib_stream_t stream) {
+  if (!sched_args_ok(kind, warmup, total, min_ratio) || !steps || !out || n <= 0) return IB_E_ARG;
+  const SchedArgs sc{kind, warmup, total, min_ratio};
+  hipLaunchKernelGGL(lr_schedule_eval_kernel, dim3(ib_grid_1d(n, 256)), dim3(256), 0, ib_s(stream), lr, sc, steps, out, n);
+  IB_CHECK_LAUNCH();
+  return IB_OK;
 }

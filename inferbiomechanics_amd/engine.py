@@ -33,6 +33,7 @@ from . import hip
 from ._tuning import tuning as TU
 from .data.AddBiomechanicsDataset import INPUT_KEY_ORDER, LOSS_KEY_ORDER, LOSS_KEY_WIDTHS
 from .loss.RegressionLossEvaluator import component_weights
+from .lr_schedule import LrSchedule, active as active_schedule
 from .module import HipModule, flat_layout
 from .plans import ParamSource
 
@@ -270,7 +271,8 @@ class HipTrainer:
 
     def __init__(self, model: HipModule, task: str, opt_type: str = "rmsprop", lr: float = 1e-4, args=None,
                  group=None, bucket_mb: float = 13.0, use_graph: bool = True, overlap_comm: Optional[bool] = None,
-                 ema_decay: float = 0.0, ema_warmup: bool = True, cond_cols: int = 0, cond_drop: float = 0.0):
+                 ema_decay: float = 0.0, ema_warmup: bool = True, cond_cols: int = 0, cond_drop: float = 0.0,
+                 lr_schedule=None):
         if task not in ("diffusion", "regression"):
             raise ValueError(task)
         if int(cond_cols) < 0 or (cond_cols and task != "diffusion"):
@@ -284,6 +286,8 @@ class HipTrainer:
             raise ValueError(f"ema_decay must lie in [0, 1), got {ema_decay}")
         if opt_type not in hip.OPT:
             raise ValueError("Invalid optimizer type: " + opt_type)          # train.py:195-197
+        if lr_schedule is not None and not isinstance(lr_schedule, LrSchedule):
+            raise ValueError(f"lr_schedule must be None or an LrSchedule, got {type(lr_schedule).__name__}")
         self.model, self.task, self.opt_type, self.lr = model, task, opt_type, lr
         # diffusion: the first cond_cols columns of every frame row are conditioning -- they reach the denoiser clean at every
         # noise level and are not scored (csrc/diffusion.hip q_sample_cond_kernel, csrc/loss.hip mse_partial_cond_kernel).
@@ -351,6 +355,10 @@ class HipTrainer:
         # (csrc/optim.hip, optim_kernel<SRC, true>); starts equal to the broadcast parameters, so identical on every rank
         self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
         self.ema = flat.clone() if self.ema_decay > 0 else None
+        # learning-rate schedule (lr_schedule.LrSchedule): `lr` is the base rate and every optimizer launch computes the rate of
+        # its own step from the device step counter (csrc/optim.hip, lr_scheduled), so a replayed graph follows it.  None, or a
+        # constant schedule without warmup: the launches without a schedule, as ever.
+        self.lr_schedule = lr_schedule
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)      # completed steps (device-resident)
         self.ticket = torch.zeros(hip.optim_ticket_words(), dtype=torch.int32, device=dev)   # optimizer exit tickets
         self.steps_done = 0
@@ -599,13 +607,28 @@ class HipTrainer:
         sl = lambda t: None if t is None else t[lo:hi]
         hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr, step=0,
                        step_dev=self.step_dev, ticket=self.ticket, grad_scale=1.0 / self.world,
-                       shadow=sl(m._shadow) if dt == torch.bfloat16 else None, sources=src, **self._ema_args(sl))
+                       shadow=sl(m._shadow) if dt == torch.bfloat16 else None, sources=src, **self._ema_args(sl),
+                       **self._sched_args())
 
     def _ema_args(self, sl) -> Dict:
         """optim_step's EMA arguments for a launch over the slice `sl` selects (none with the EMA off: the entries without it)"""
         if self.ema is None:
             return {}
         return {"ema": sl(self.ema), "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup}
+
+    def _sched_args(self) -> Dict:
+        """optim_step's schedule argument, the same for every optimizer launch of a step (none with the schedule off: the
+        entries without it)"""
+        if active_schedule(self.lr_schedule) is None:
+            return {}
+        return {"lr_schedule": self.lr_schedule}
+
+    def current_lr(self) -> float:
+        """the rate the NEXT step's optimizer launches use (host arithmetic, no device read): lr_at(lr, steps_done + 1) of the
+        schedule, the base rate without one"""
+        if active_schedule(self.lr_schedule) is None:
+            return float(self.lr)
+        return self.lr_schedule.lr_at(self.lr, self.steps_done + 1)
 
     def _last_launch_range(self, done, src):
         """[lo, hi) of the flat buffers for the step's last optimizer launch + the done ranges left inside it"""
@@ -651,7 +674,8 @@ class HipTrainer:
                 w.wait()                             # stream-level on the GPU path: the SIDE stream waits, not the backward
             hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr, step=1,
                            step_dev=self.step_dev, grad_scale=1.0 / self.world,
-                           shadow=sl(m._shadow) if dt == torch.bfloat16 else None, **self._ema_args(sl))
+                           shadow=sl(m._shadow) if dt == torch.bfloat16 else None, **self._ema_args(sl),
+                           **self._sched_args())
         self._br_opt.run(fn)
 
     def _prefix_range(self, prefix: str) -> Tuple[int, int]:
@@ -677,7 +701,8 @@ class HipTrainer:
         sl = lambda t: None if t is None else t[lo:hi]
         hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr, step=1,
                        step_dev=self.step_dev, grad_scale=1.0 / self.world,
-                       shadow=sl(m._shadow) if dt == torch.bfloat16 else None, sources=sources, **self._ema_args(sl))
+                       shadow=sl(m._shadow) if dt == torch.bfloat16 else None, sources=sources, **self._ema_args(sl),
+                       **self._sched_args())
         self._early_done.append((lo, hi))
 
     def _stage(self, batch) -> Dict[str, torch.Tensor]:
@@ -1015,7 +1040,11 @@ class HipTrainer:
                         "adadelta": ("square_avg", "acc_delta"), "adamax": ("exp_avg", "exp_inf")}
 
     def optimizer_state_dict(self) -> Dict:
+        """"lr" is the BASE rate; "lr_schedule" the schedule's four fields, or None without one (a constant schedule
+        without warmup counts as none)"""
+        sched = active_schedule(self.lr_schedule)
         return {"opt_type": self.opt_type, "lr": self.lr, "step": self.steps_done,
+                "lr_schedule": None if sched is None else sched.fields(),
                 "layout": {k: list(v) for k, v in self.layout.items()},
                 "s1": None if self.s1 is None else self.s1.detach().cpu(),
                 "s2": None if self.s2 is None else self.s2.detach().cpu()}
@@ -1023,7 +1052,8 @@ class HipTrainer:
     def torch_optimizer_state_dict(self) -> Dict:
         """the same state in torch.optim's own grammar ({'state': {i: {...}}, 'param_groups': [...]}, parameters numbered
         in model.parameters() order as `optim.X(model.parameters(), lr=...)` numbers them, train.py:183-194): what a
-        reference-style (`--eager` / torch.optim) run or the reference itself can load"""
+        reference-style (`--eager` / torch.optim) run or the reference itself can load.  param_groups carry the BASE rate:
+        torch.optim has no place for this trainer's schedule, so a scheduled run's rate at the checkpoint is not in here"""
         names = [k for k, _ in self.model.named_parameters()]
         state = torch_state_from_flat(self.opt_type, self.steps_done, names, lambda k: self._params[k].shape, self.layout,
                                       self.s1, self.s2)
@@ -1036,6 +1066,12 @@ class HipTrainer:
             return self._load_torch_optimizer_state(sd)
         if sd.get("opt_type") != self.opt_type or {k: list(v) for k, v in self.layout.items()} != sd.get("layout"):
             raise hip.HipError("optimizer state does not match this trainer (optimizer type or parameter layout)")
+        if "lr_schedule" in sd:                       # a payload without the key is an older checkpoint: it loads
+            mine = active_schedule(self.lr_schedule)
+            theirs = active_schedule(LrSchedule.from_fields(sd["lr_schedule"]))
+            if mine != theirs:
+                raise hip.HipError(f"the checkpoint's learning-rate schedule ({theirs if theirs else 'none'}) differs from "
+                                   f"this trainer's ({mine if mine else 'none'})")
         if self.s1 is not None:
             self.s1.copy_(sd["s1"])
         if self.s2 is not None:

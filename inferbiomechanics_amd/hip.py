@@ -15,7 +15,8 @@ resampled masked loop (csrc/resample.hip) in a sixth, ``include/ib_hip_resample.
 of a posterior ensemble (csrc/ensemble.hip) in a seventh, ``include/ib_hip_ensemble.h`` (``_ENSEMBLE_SIGS``), the x0 clip of a
 sampling step and the per-column range of a window table (csrc/clip.hip) in an eighth, ``include/ib_hip_clip.h``
 (``_CLIP_SIGS``), the per-column standardisation of the diffusion windows (csrc/standardize.hip) in a ninth,
-``include/ib_hip_standardize.h`` (``_STANDARDIZE_SIGS``); a name may be declared once in the nine.
+``include/ib_hip_standardize.h`` (``_STANDARDIZE_SIGS``), the learning-rate schedule of the fused optimizer (csrc/optim.hip)
+in a tenth, ``include/ib_hip_sched.h`` (``_SCHED_SIGS``); a name may be declared once in the ten.
 """
 from __future__ import annotations
 
@@ -41,6 +42,7 @@ RESAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_r
 ENSEMBLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_ensemble.h")
 CLIP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_clip.h")
 STANDARDIZE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_standardize.h")
+SCHED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sched.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -117,6 +119,12 @@ _ALL_SIGS = {_n: _v for _t in _EVERY_HEADER for _n, _v in _t.items()}  # every e
 if len(_ALL_SIGS) != sum(len(_t) for _t in _EVERY_HEADER):
     _twice = sorted(n for n in _ALL_SIGS if sum(n in _t for _t in _EVERY_HEADER) > 1)
     raise HipError(f"declared in two headers: {_twice}")
+# the tenth header has a table of its own beside _ALL_SIGS (the nine headers', as the tests of those pin it); _sig() and lib()
+# go through _BOUND, which holds both
+_SCHED_SIGS = _parse_header(_read_header(SCHED_HEADER_PATH))                        # the optimizer's rate, off by default
+_BOUND = {**_ALL_SIGS, **_SCHED_SIGS}
+if len(_BOUND) != len(_ALL_SIGS) + len(_SCHED_SIGS):
+    raise HipError(f"declared in two headers: {sorted(n for n in _SCHED_SIGS if n in _ALL_SIGS)}")
 _kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_STITCH_KMAX[ \t]+(\d+)[ \t]*$", _read_header(STITCH_HEADER_PATH), flags=re.M)
 if _kmax is None:
     raise HipError(f"{STITCH_HEADER_PATH} does not define IB_STITCH_KMAX")
@@ -170,9 +178,14 @@ def standardize_decls() -> List[str]:
     return sorted(_STANDARDIZE_SIGS)
 
 
+def sched_decls() -> List[str]:
+    """Every function include/ib_hip_sched.h declares"""
+    return sorted(_SCHED_SIGS)
+
+
 def _sig(name: str):
     """(restype, argtypes) of an entry point of any header"""
-    return _ALL_SIGS[name]
+    return _BOUND[name]
 
 
 # pure host queries: no launch, no stream
@@ -217,6 +230,13 @@ class _DryRunLib:
             if name == "ib_optim_step_ema":
                 self.ema_ranges.append((a[12], int(a[5]), []))
             elif name == "ib_optim_step_sources_ema":
+                m = int(a[12])
+                rd = lambda p, ct: ctypes.cast(p, ctypes.POINTER(ct))
+                st, ln, kd = rd(a[13], ctypes.c_int64), rd(a[14], ctypes.c_int64), rd(a[15], ctypes.c_int32)
+                self.ema_ranges.append((a[25], int(a[5]), [(st[j], ln[j]) for j in range(m) if kd[j] == 3]))
+            elif name == "ib_optim_step_sched" and a[12] is not None:
+                self.ema_ranges.append((a[12], int(a[5]), []))
+            elif name == "ib_optim_step_sources_sched" and a[25] is not None:
                 m = int(a[12])
                 rd = lambda p, ct: ctypes.cast(p, ctypes.POINTER(ct))
                 st, ln, kd = rd(a[13], ctypes.c_int64), rd(a[14], ctypes.c_int64), rd(a[15], ctypes.c_int32)
@@ -447,7 +467,7 @@ def lib():
             raise HipError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C inferbiomechanics_amd/csrc` (hipcc --offload-arch=gfx950). There is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _ALL_SIGS.items():
+        for name, (res, args) in _BOUND.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -1375,7 +1395,7 @@ def optim_ticket_words() -> int:
 
 
 def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=1.0, shadow=None, ticket=None,
-               sources=None, ema=None, ema_decay=0.0, ema_warmup=True):
+               sources=None, ema=None, ema_decay=0.0, ema_warmup=True, lr_schedule=None):
     """step: the step number of the bias corrections; with `step_dev` the kernel uses `*step_dev + step`, so the default is
     0 there (the device counter alone) and 1 without a device counter.
     sources = (items, part, rows, segs): the gradient of some ranges of g is still partial sums -- items =
@@ -1385,7 +1405,17 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
     the buffers with step_dev, no ticket and step=1: same step number as the self-counting launch that follows).
     ema: an fp32 buffer like p that the same pass advances, ema = d * ema + (1 - d) * p_new over every element it updates,
     d = min(ema_decay, (1 + step) / (10 + step)) with ema_warmup, else ema_decay (the *_ema entries); None: the entries
-    without it."""
+    without it.
+    lr_schedule: None or an lr_schedule.LrSchedule.  None or a constant schedule without warmup: the four entries above, as
+    ever.  Anything else: the *_sched entries (include/ib_hip_sched.h) -- `lr` is then the BASE rate and the kernel computes
+    the rate of its own step number from it, LrSchedule.lr_at(lr, step), so a replayed graph follows the device counter."""
+    sched = ()
+    if lr_schedule is not None:
+        from .lr_schedule import LrSchedule
+        if not isinstance(lr_schedule, LrSchedule):
+            raise HipError(f"lr_schedule must be None or an LrSchedule, got {type(lr_schedule).__name__}")
+        if not lr_schedule.is_constant():
+            sched = (lr_schedule.kind_code, lr_schedule.warmup, lr_schedule.total, lr_schedule.min_ratio)
     if step is None:
         step = 0 if step_dev is not None else 1
     _req(p, "p", torch.float32, 1)
@@ -1458,7 +1488,10 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
                 _ptr(ticket), _ptr(shadow), m, cv(start), cv(ln), cv(kind), cv(base), cv(stride), cv(count), cv(scale),
                 ctypes.c_void_p(loss[0]) if loss else None, ld, int(rows), loss[1] if loss else 0.0,
                 _ptr(loss[2]) if loss else None)
-        if ema is None:
+        if sched:
+            _check(lib().ib_optim_step_sources_sched(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), *sched,
+                                                     stream_ptr()), "ib_optim_step_sources_sched")
+        elif ema is None:
             _check(lib().ib_optim_step_sources(*args, stream_ptr()), "ib_optim_step_sources")
         else:
             _check(lib().ib_optim_step_sources_ema(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), stream_ptr()),
@@ -1466,11 +1499,34 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
         return
     args = (OPT[opt], _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), n, float(lr), float(grad_scale), int(step), _ptr(step_dev),
             _ptr(ticket), _ptr(shadow))
-    if ema is None:
+    if sched:
+        _check(lib().ib_optim_step_sched(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), *sched, stream_ptr()),
+               "ib_optim_step_sched")
+    elif ema is None:
         _check(lib().ib_optim_step(*args, stream_ptr()), "ib_optim_step")
     else:
         _check(lib().ib_optim_step_ema(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), stream_ptr()),
                "ib_optim_step_ema")
+
+
+def lr_schedule_eval(lr: float, lr_schedule, steps, out=None):
+    """out[i] = the rate the scheduled optimizer kernel uses at step steps[i] (1-based; int32 on the device) for the base rate
+    `lr`: one launch of the kernel's own device function (ib_lr_schedule_eval).  Returns out (fp32, like steps)."""
+    from .lr_schedule import LrSchedule
+    if not isinstance(lr_schedule, LrSchedule):
+        raise HipError(f"lr_schedule must be an LrSchedule, got {type(lr_schedule).__name__}")
+    _req(steps, "steps", torch.int32, 1)
+    if steps.numel() == 0 or not steps.is_contiguous():
+        raise HipError("lr_schedule_eval: a non-empty contiguous int32 vector of step numbers required")
+    if out is None:
+        out = torch.empty(steps.numel(), dtype=torch.float32, device=steps.device)
+    _req(out, "out", torch.float32, 1)
+    if out.numel() != steps.numel() or not out.is_contiguous() or out.device != steps.device:
+        raise HipError("lr_schedule_eval: out must be a contiguous fp32 vector of the length and device of steps")
+    _check(lib().ib_lr_schedule_eval(float(lr), lr_schedule.kind_code, lr_schedule.warmup, lr_schedule.total,
+                                     lr_schedule.min_ratio, _ptr(steps), _ptr(out), steps.numel(), stream_ptr()),
+           "ib_lr_schedule_eval")
+    return out
 
 
 # --------------------------------------------------------------------------------------------
