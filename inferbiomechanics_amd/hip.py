@@ -3071,13 +3071,15 @@ class Graph:
 
     def __init__(self):
         self._exec = None
+        self._owner = None       # the library object that captured the graph: it destroys it, whichever is loaded by then
 
     def begin(self):
         _check(lib().ib_graph_begin(stream_ptr()), "ib_graph_begin")
 
     def end(self):
         h = ctypes.c_void_p()
-        _check(lib().ib_graph_end(stream_ptr(), ctypes.byref(h)), "ib_graph_end")
+        self._owner = lib()
+        _check(self._owner.ib_graph_end(stream_ptr(), ctypes.byref(h)), "ib_graph_end")
         self._exec = h
 
     def launch(self):
@@ -3087,8 +3089,8 @@ class Graph:
 
     def __del__(self):
         try:
-            if self._exec is not None and _lib is not None:
-                _lib.ib_graph_destroy(self._exec)
+            if self._exec is not None and self._owner is not None:
+                self._owner.ib_graph_destroy(self._exec)
         except Exception:
             pass
 
