@@ -130,6 +130,12 @@ class TrainCommand(AbstractCommand):
                             '--epochs changes.')
         p.add_argument('--lr-min-ratio', type=float, default=0.0,
                        help='The rate a decay ends at, as a fraction of --learning-rate, in [0, 1].')
+        p.add_argument('--weight-decay', type=float, default=0.0,
+                       help='Decoupled weight decay (AdamW with --opt-type adam; any --opt-type): each step multiplies the '
+                            'weight matrices and embedding tables (parameters with 2 or more dimensions; not biases or '
+                            'normalisation gains / offsets) by 1 - rate x W before the update, inside the fused optimizer '
+                            'launches, at the rate of that step. Saved in the checkpoints; a resumed run must give the same '
+                            'value. Not with --eager. Default: 0 (off).')
 
     # ------------------------------------------------------------------------------------------
     def run(self, args: argparse.Namespace):
@@ -143,6 +149,7 @@ class TrainCommand(AbstractCommand):
 
         check_ema_args(args)
         check_lr_schedule(args)
+        check_weight_decay_args(args)
         check_cond_cols(model_type, getattr(args, 'cond_cols', 0))
         check_cond_drop(args)
         check_record_range(args)
@@ -234,7 +241,11 @@ class TrainCommand(AbstractCommand):
                                  args=args, use_graph=not args.no_graph, bucket_mb=args.bucket_mb,
                                  ema_decay=getattr(args, 'ema_decay', 0.0),
                                  ema_warmup=not getattr(args, 'no_ema_warmup', False), cond_cols=cond_cols,
-                                 cond_drop=cond_drop, lr_schedule=lr_schedule)
+                                 cond_drop=cond_drop, lr_schedule=lr_schedule,
+                                 weight_decay=getattr(args, 'weight_decay', 0.0))
+            if trainer.weight_decay > 0:
+                print(f"Weight decay {trainer.weight_decay:g} (decoupled) on {len(trainer.decayed)} of "
+                      f"{len(trainer.layout)} parameter tensors")
 
         if getattr(args, 'loss_every', 1) < 1:
             raise SystemExit("--loss-every must be >= 1")
@@ -246,6 +257,9 @@ class TrainCommand(AbstractCommand):
             epoch_checkpoint, _ = self.load_latest_checkpoint(model, optimizer=trainer if trainer is not None else optimizer,
                                                               checkpoint_dir=checkpoint_dir)
         except HipError as exc:
+            if "weight decay" in str(exc):
+                raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --weight-decay or use another "
+                                 f"--checkpoint-dir") from None
             if "learning-rate schedule" not in str(exc):
                 raise
             raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --lr-schedule / --lr-warmup-steps / "
@@ -474,6 +488,16 @@ def check_ema_args(args: argparse.Namespace):
         raise SystemExit(f"--ema-decay must lie in [0, 1) (0 = off, 0.999-0.9999 are usual), got {d}")
     if d > 0 and getattr(args, 'eager', False):
         raise SystemExit("--ema-decay needs the fused trainer: --eager runs torch.optim, which keeps no EMA of the weights")
+
+
+def check_weight_decay_args(args: argparse.Namespace):
+    """--weight-decay W: finite and >= 0; the decay is applied inside the fused optimizer launches, so --eager (torch.optim
+    with only lr set) has none"""
+    wd = getattr(args, 'weight_decay', 0.0)
+    if not 0.0 <= wd < float('inf'):                    # NaN fails the comparison
+        raise SystemExit(f"--weight-decay must be finite and >= 0, got {wd}")
+    if wd > 0 and getattr(args, 'eager', False):
+        raise SystemExit("--weight-decay needs the fused trainer: --eager runs torch.optim with only the rate set")
 
 
 def check_lr_schedule(args: argparse.Namespace):

@@ -5,8 +5,12 @@
 // bf16 GEMMs never need a separate cast kernel.  With EMA on (optim_kernel<SRC, true>, the *_ema entries) the same pass also
 // advances an exponential moving average of the parameters from the new value it already holds in registers: one more fp32
 // read and write per parameter, no launch of its own, and the decay follows the device step counter under graph replay.
+// Decoupled weight decay (the *_decay entries, include/ib_hip_decay.h; AdamW with Adam) multiplies the quads a range table
+// covers by 1 - lr_s * wd in the same pass, before the update: optim_kernel<SRC, EMA, ..., DecayArgs>.
 #include "ib_common.h"
-#include "../../include/ib_hip_sched.h"
+#include "../../include/ib_hip_decay.h"
+#include <type_traits>
+#include <vector>
 
 namespace {
 
@@ -57,6 +61,62 @@ __device__ __forceinline__ float lr_scheduled(float lr, const SchedArgs& sc, int
     f = m + (1.0 - m) * shape;
   }
   return (float)((double)lr * f);
+}
+
+// Decoupled weight decay (include/ib_hip_decay.h states it): f = (float)(1 - lr_s * wd) in double (the product of two fp32 values
+// is exact there, so f is rounded once), p' = p * f as a multiply of its own -- contraction is off in decay_mul, so the
+// product carries no `contract` flag and cannot be fused into the update's subtraction -- then the update of (p', g).
+// table: n pairs (start, end) of int64 in device memory, global flat-buffer coordinates, sorted and disjoint, every bound a
+// multiple of 4 (ib_decay_table_build rounds the ends up); origin: the global offset of this launch's p[0].
+struct DecayArgs { float wd; int n; const int64_t* table; int64_t origin; };
+
+__device__ __forceinline__ float decay_factor(float lr, float wd) {
+#pragma clang fp contract(off)
+  return (float)(1.0 - (double)lr * (double)wd);
+}
+
+__device__ __forceinline__ float decay_mul(float p, float f) {
+#pragma clang fp contract(off)
+  return p * f;
+}
+
+// The quad as the update sees it: p * f where `dec` holds, p's own bits elsewhere, handed on through an empty asm that the
+// compiler cannot look through.  Without it the multiply and the select in front of the update changed how the update
+// itself was vectorised and contracted (Adam's s1 and p came out one rounding apart from the launch without decay, on
+// undecayed elements too); behind it the update starts from four opaque registers, as it does behind the load of p.
+__device__ __forceinline__ float4 decay4(float4 p, bool dec, float f) {
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  f4v v;
+  v.x = dec ? decay_mul(p.x, f) : p.x; v.y = dec ? decay_mul(p.y, f) : p.y;
+  v.z = dec ? decay_mul(p.z, f) : p.z; v.w = dec ? decay_mul(p.w, f) : p.w;
+  asm("" : "+v"(v));
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+
+// is the quad at local element idx decayed?  As source_grad4 finds a gradient source: the wave's first element picks the first
+// range that ends beyond it by a UNIFORM binary search (the active lane with the lowest index holds the lowest element), each
+// lane walks on from there.
+__device__ __forceinline__ bool decayed4(const DecayArgs& D, int64_t idx) {
+  const int64_t gi = D.origin + idx;
+  const int64_t g0 = ((int64_t)__builtin_amdgcn_readfirstlane((int)(gi >> 32)) << 32) |
+                     (uint32_t)__builtin_amdgcn_readfirstlane((int)(gi & 0xffffffff));
+  int lo = 0, hi = D.n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (D.table[2 * mid + 1] <= g0) lo = mid + 1; else hi = mid;
+  }
+  for (int j = lo; j < D.n; ++j) {
+    if (gi < D.table[2 * j]) break;
+    if (gi < D.table[2 * j + 1]) return true;
+  }
+  return false;
+}
+
+// the optional trailing arguments of optim_kernel: is T among them, and which one is it
+template <typename T, typename... P> constexpr bool pack_has = (std::is_same<T, P>::value || ...);
+template <typename T, typename F, typename... R>
+__device__ __forceinline__ const T& pack_get(const F& f, const R&... r) {
+  if constexpr (std::is_same<T, F>::value) return f; else return pack_get<T>(r...);
 }
 
 __device__ __forceinline__ float opt_update(const OptArgs& a, float p, float g, float& s1, float& s2, float bc1,
@@ -151,14 +211,17 @@ __device__ __forceinline__ bool source_grad4(const OptSources& S, const float* g
   return true;
 }
 
-template <bool EMA>
-__device__ __forceinline__ void apply4(const OptArgs& a, int64_t i, float4 g, float bc1, float bc2s, float d, int nvalid) {
-  // nvalid < 4 only at the ragged end of a column-sum range (the remaining lanes belong to alignment padding)
+template <bool EMA, bool DECAY = false>
+__device__ __forceinline__ void apply4(const OptArgs& a, int64_t i, float4 g, float bc1, float bc2s, float d, int nvalid,
+                                       bool dec = false, float f = 1.f) {
+  // nvalid < 4 only at the ragged end of a column-sum range (the remaining lanes belong to alignment padding: they get back
+  // the bits they had, p0, from before the decay)
   const bool has1 = a.s1 != nullptr, has2 = a.s2 != nullptr;
   float4 p = reinterpret_cast<float4*>(a.p)[i];
   float4 s1 = has1 ? reinterpret_cast<float4*>(a.s1)[i] : make_float4(0, 0, 0, 0);
   float4 s2 = has2 ? reinterpret_cast<float4*>(a.s2)[i] : make_float4(0, 0, 0, 0);
   const float4 p0 = p, s10 = s1, s20 = s2;
+  if constexpr (DECAY) p = decay4(p, dec, f);
   p.x = opt_update(a, p.x, g.x * a.gscale, s1.x, s2.x, bc1, bc2s);
   p.y = opt_update(a, p.y, g.y * a.gscale, s1.y, s2.y, bc1, bc2s);
   p.z = opt_update(a, p.z, g.z * a.gscale, s1.z, s2.z, bc1, bc2s);
@@ -186,9 +249,15 @@ __device__ __forceinline__ void apply4(const OptArgs& a, int64_t i, float4 g, fl
 // above, from the step number of the bias corrections), put in a.lr's place once at the head.  One kernel template and not a
 // body shared by two kernels: inlined from a device function the same statements compiled to other code (blockDim.x is
 // lowered there without the kernel's uniform-work-group-size attribute, and the sources form came out scheduled differently).
+// The pack's second optional element, behind SchedArgs where there is one, is a DecayArgs: every quad this launch updates
+// whose global position lies in a range of D.table is multiplied by f = decay_factor(lr_s, wd) before its update (kind-3
+// ranges are skipped before that, as before any other work).  Without it: the functions above, instruction for instruction.
 template <bool SRC, bool EMA, typename... Sched>
 __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int main_blocks, Sched... sc) {
-  static_assert(sizeof...(Sched) <= 1, "at most one SchedArgs");
+  static_assert(std::is_same<void(Sched...), void()>::value || std::is_same<void(Sched...), void(SchedArgs)>::value ||
+                std::is_same<void(Sched...), void(DecayArgs)>::value ||
+                std::is_same<void(Sched...), void(SchedArgs, DecayArgs)>::value, "(), (SchedArgs), (DecayArgs) or both in this order");
+  constexpr bool SCHED = pack_has<SchedArgs, Sched...>, DECAY = pack_has<DecayArgs, Sched...>;
   // self-counting mode (ticket != NULL): *step_dev holds the number of COMPLETED steps; every block reads it on
   // entry, and the block that draws the last exit ticket publishes step and resets the ticket -- it exits after
   // every other block has entered (and therefore read the old value), so no block can see the new count.
@@ -196,7 +265,10 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int
   // the buffer (a layer's range, issued as soon as its gradient is complete) takes part in a self-counting step whose
   // last launch publishes.
   const int step = a.step_dev ? *(volatile int32_t*)a.step_dev + (a.ticket ? 1 : a.step) : a.step;
-  if constexpr (sizeof...(Sched) == 1) a.lr = lr_scheduled(a.lr, sc..., step);
+  if constexpr (SCHED) a.lr = lr_scheduled(a.lr, pack_get<SchedArgs>(sc...), step);
+  DecayArgs D{};
+  float f = 1.f;                                 // the decay's factor, from the rate this launch uses
+  if constexpr (DECAY) { D = pack_get<DecayArgs>(sc...); f = decay_factor(a.lr, D.wd); }
   // bias corrections in double (torch computes them as Python floats) -- Adam / Adamax only: two double-precision pow()
   // are several hundred instructions at the head of every thread, ahead of its first load
   float bc1 = 1.f, bc2s = 1.f;
@@ -249,7 +321,11 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int
 #pragma unroll
         for (int k = 1; k < 16; ++k) { const float4 w = red[k][c4]; t.x += w.x; t.y += w.y; t.z += w.z; t.w += w.w; }
         t.x *= r.scale; t.y *= r.scale; t.z *= r.scale; t.w *= r.scale;
-        apply4<EMA>(a, (r.start + o) >> 2, t, bc1, bc2s, d, (int)min((int64_t)4, r.len - o));
+        if constexpr (DECAY)
+          apply4<EMA, true>(a, (r.start + o) >> 2, t, bc1, bc2s, d, (int)min((int64_t)4, r.len - o),
+                            decayed4(D, r.start + o), f);
+        else
+          apply4<EMA>(a, (r.start + o) >> 2, t, bc1, bc2s, d, (int)min((int64_t)4, r.len - o));
       }
     }
   } else {
@@ -264,6 +340,7 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int
     }
     float4 s1 = has1 ? reinterpret_cast<float4*>(a.s1)[i] : make_float4(0, 0, 0, 0);
     float4 s2 = has2 ? reinterpret_cast<float4*>(a.s2)[i] : make_float4(0, 0, 0, 0);
+    if constexpr (DECAY) p = decay4(p, decayed4(D, i * 4), f);
     p.x = opt_update(a, p.x, g.x * a.gscale, s1.x, s2.x, bc1, bc2s);
     p.y = opt_update(a, p.y, g.y * a.gscale, s1.y, s2.y, bc1, bc2s);
     p.z = opt_update(a, p.z, g.z * a.gscale, s1.z, s2.z, bc1, bc2s);
@@ -282,7 +359,12 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int
   const int64_t t0 = n4 * 4;
   for (int64_t i = t0 + (int64_t)lb * blockDim.x + threadIdx.x; i < a.n; i += gstride) {
     float s1 = has1 ? a.s1[i] : 0.f, s2 = has2 ? a.s2[i] : 0.f;
-    const float p = opt_update(a, a.p[i], a.g[i] * a.gscale, s1, s2, bc1, bc2s);
+    float pi = a.p[i];
+    if constexpr (DECAY) {
+      if (decayed4(D, t0)) pi = decay_mul(pi, f);              // the tail belongs to quad n / 4
+      asm("" : "+v"(pi));
+    }
+    const float p = opt_update(a, pi, a.g[i] * a.gscale, s1, s2, bc1, bc2s);
     a.p[i] = p;
     if (has1) a.s1[i] = s1;
     if (has2) a.s2[i] = s2;
@@ -337,11 +419,25 @@ __global__ __launch_bounds__(256) void lr_schedule_eval_kernel(float lr, SchedAr
     out[i] = lr_scheduled(lr, sc, steps[i]);
 }
 
+// the decayed launches (the *_decay entries): optim_kernel<SRC, EMA, DecayArgs> or <SRC, EMA, SchedArgs, DecayArgs>
+template <bool SRC>
+void optim_launch_decay(dim3 grid, ib_stream_t stream, const OptArgs& a, const OptSources& S, int main_blocks,
+                        const SchedArgs* sc, const DecayArgs& dk) {
+  if (sc && a.ema)
+    hipLaunchKernelGGL((optim_kernel<SRC, true, SchedArgs, DecayArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, *sc, dk);
+  else if (sc)
+    hipLaunchKernelGGL((optim_kernel<SRC, false, SchedArgs, DecayArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, *sc, dk);
+  else if (a.ema)
+    hipLaunchKernelGGL((optim_kernel<SRC, true, DecayArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, dk);
+  else
+    hipLaunchKernelGGL((optim_kernel<SRC, false, DecayArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, dk);
+}
+
 // the two launchers behind the C entries: ema == NULL launches optim_kernel<SRC, false>, the kernel without the EMA;
-// sc != NULL launches optim_kernel<SRC, EMA, SchedArgs> in their place (the *_sched entries)
+// sc != NULL launches optim_kernel<SRC, EMA, SchedArgs> in their place (the *_sched entries); dk != NULL the decayed ones
 int optim_plain(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr, float grad_scale, int32_t step,
                 int32_t* step_dev, int32_t* ticket, void* shadow_bf16, float* ema, float ema_decay, int ema_warmup,
-                const SchedArgs* sc, ib_stream_t stream) {
+                const SchedArgs* sc, ib_stream_t stream, const DecayArgs* dk = nullptr) {
   if (!p || !g || n <= 0 || opt < IB_OPT_SGD || opt > IB_OPT_ADAMAX) return IB_E_ARG;
   if (ticket && !step_dev) return IB_E_ARG;
   const bool need1 = opt != IB_OPT_SGD;
@@ -351,7 +447,9 @@ int optim_plain(int opt, float* p, const float* g, float* s1, float* s2, int64_t
   OptArgs a{p, g, need1 ? s1 : nullptr, need2 ? s2 : nullptr, reinterpret_cast<bf16_t*>(shadow_bf16),
             n, lr, grad_scale, step, step_dev, ticket, opt, ema, ema_decay, ema_warmup};
   const dim3 grid(ib_grid_1d(n / 4 + 1, 256));
-  if (sc && ema)
+  if (dk)
+    optim_launch_decay<false>(grid, stream, a, OptSources{}, 0, sc, *dk);
+  else if (sc && ema)
     hipLaunchKernelGGL((optim_kernel<false, true, SchedArgs>), grid, dim3(256), 0, ib_s(stream), a, OptSources{}, 0, *sc);
   else if (sc)
     hipLaunchKernelGGL((optim_kernel<false, false, SchedArgs>), grid, dim3(256), 0, ib_s(stream), a, OptSources{}, 0, *sc);
@@ -368,7 +466,7 @@ int optim_sources(int opt, float* p, const float* g, float* s1, float* s2, int64
                   const int64_t* len, const int32_t* kind, const void* const* base, const int64_t* stride,
                   const int32_t* count, const float* scale, const float* loss_col, int64_t loss_ld, int64_t loss_rows,
                   float loss_scale, float* loss_out, float* ema, float ema_decay, int ema_warmup, const SchedArgs* sc,
-                  ib_stream_t stream) {
+                  ib_stream_t stream, const DecayArgs* dk = nullptr) {
   if (!p || !g || n <= 0 || opt < IB_OPT_SGD || opt > IB_OPT_ADAMAX) return IB_E_ARG;
   if (ticket && !step_dev) return IB_E_ARG;
   if (nsrc < 0 || nsrc > OPT_MAXSRC || (nsrc > 0 && (!start || !len || !kind || !base || !stride || !count))) return IB_E_ARG;
@@ -406,7 +504,9 @@ int optim_sources(int opt, float* p, const float* g, float* s1, float* s2, int64
   for (int j = 0; j < nsrc; ++j)
     if (kind[j] == 2) cs_blocks += (int)((len[j] + 63) / 64);
   const dim3 grid(main_blocks + cs_blocks);
-  if (sc && ema)
+  if (dk)
+    optim_launch_decay<true>(grid, stream, a, S, main_blocks, sc, *dk);
+  else if (sc && ema)
     hipLaunchKernelGGL((optim_kernel<true, true, SchedArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, *sc);
   else if (sc)
     hipLaunchKernelGGL((optim_kernel<true, false, SchedArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, *sc);
@@ -429,6 +529,22 @@ bool sched_args_ok(int kind, int32_t warmup, int32_t total, float min_ratio) {
   if (kind != IB_SCHED_CONSTANT && total <= warmup) return false;
   return min_ratio >= 0.f && min_ratio <= 1.f;
 }
+
+// the *_decay entries: weight_decay >= 0 (NaN fails the comparison), a table of table_n >= 0 ranges (8-byte aligned int64
+// pairs; may be null only when empty), the launch's origin a quad boundary of the flat buffer
+bool decay_args_ok(float wd, const void* table, int table_n, int64_t origin) {
+  if (!(wd >= 0.f) || table_n < 0 || (table_n > 0 && !table) || !ib_aligned(table, 8)) return false;
+  return origin >= 0 && origin % 4 == 0;
+}
+
+// what the *_decay entries launch with: no SchedArgs for a constant schedule without warmup (the rate is the host's lr, as in
+// the entries without a schedule), no DecayArgs where nothing can be decayed (the kernels without decay, bit for bit)
+struct DecayLaunch {
+  SchedArgs sc; DecayArgs dk; bool has_sc, has_dk;
+  DecayLaunch(int kind, int32_t warmup, int32_t total, float min_ratio, float wd, const void* table, int table_n, int64_t origin)
+      : sc{kind, warmup, total, min_ratio}, dk{wd, table_n, reinterpret_cast<const int64_t*>(table), origin},
+        has_sc(!(kind == IB_SCHED_CONSTANT && warmup == 0)), has_dk(wd > 0.f && table_n > 0) {}
+};
 
 }  // namespace
 
@@ -508,4 +624,57 @@ extern "C" int ib_lr_schedule_eval(float lr, int kind, int32_t warmup, int32_t t
   hipLaunchKernelGGL(lr_schedule_eval_kernel, dim3(ib_grid_1d(n, 256)), dim3(256), 0, ib_s(stream), lr, sc, steps, out, n);
   IB_CHECK_LAUNCH();
   return IB_OK;
+}
+
+extern "C" size_t ib_decay_table_bytes(int n) { return n < 0 ? 0 : (size_t)(n > 0 ? n : 1) * 2 * sizeof(int64_t); }
+
+extern "C" int ib_decay_table_build(const int64_t* start, const int64_t* len, int n, void* table_dev, ib_stream_t stream) {
+  if (n < 0 || !table_dev || !ib_aligned(table_dev, 16) || (n > 0 && (!start || !len))) return IB_E_ARG;
+  std::vector<int64_t> t(2 * (size_t)n);
+  int64_t prev_end = 0;
+  for (int j = 0; j < n; ++j) {
+    if (start[j] < 0 || start[j] % 4 != 0 || len[j] <= 0 || len[j] > INT64_MAX - 3 - start[j]) return IB_E_ARG;
+    if (start[j] < prev_end) return IB_E_ARG;                 // unsorted, or inside the range before it
+    prev_end = start[j] + (len[j] + 3) / 4 * 4;               // a range covers whole quads
+    t[2 * j] = start[j];
+    t[2 * j + 1] = prev_end;
+  }
+  if (n == 0) return IB_OK;
+  // the host arrays may go on return: the copy out of this vector is complete before it is destroyed
+  if (hipMemcpyAsync(table_dev, t.data(), t.size() * sizeof(int64_t), hipMemcpyHostToDevice, ib_s(stream)) != hipSuccess)
+    return IB_E_LAUNCH;
+  if (hipStreamSynchronize(ib_s(stream)) != hipSuccess) return IB_E_LAUNCH;
+  return IB_OK;
+}
+
+extern "C" int ib_optim_step_decay(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
+                                   float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16,
+                                   float* ema, float ema_decay, int ema_warmup, int sched_kind, int32_t sched_warmup,
+                                   int32_t sched_total, float sched_min_ratio, float weight_decay, const void* table_dev,
+                                   int table_n, int64_t origin, ib_stream_t stream) {
+  if (!sched_args_ok(sched_kind, sched_warmup, sched_total, sched_min_ratio)) return IB_E_ARG;
+  if (ema && !ema_args_ok(ema, ema_decay)) return IB_E_ARG;
+  if (!decay_args_ok(weight_decay, table_dev, table_n, origin)) return IB_E_ARG;
+  const DecayLaunch L(sched_kind, sched_warmup, sched_total, sched_min_ratio, weight_decay, table_dev, table_n, origin);
+  return optim_plain(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup,
+                     L.has_sc ? &L.sc : nullptr, stream, L.has_dk ? &L.dk : nullptr);
+}
+
+extern "C" int ib_optim_step_sources_decay(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
+                                           float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket,
+                                           void* shadow_bf16, int nsrc, const int64_t* start, const int64_t* len,
+                                           const int32_t* kind, const void* const* base, const int64_t* stride,
+                                           const int32_t* count, const float* scale, const float* loss_col,
+                                           int64_t loss_ld, int64_t loss_rows, float loss_scale, float* loss_out,
+                                           float* ema, float ema_decay, int ema_warmup, int sched_kind,
+                                           int32_t sched_warmup, int32_t sched_total, float sched_min_ratio,
+                                           float weight_decay, const void* table_dev, int table_n, int64_t origin,
+                                           ib_stream_t stream) {
+  if (!sched_args_ok(sched_kind, sched_warmup, sched_total, sched_min_ratio)) return IB_E_ARG;
+  if (ema && !ema_args_ok(ema, ema_decay)) return IB_E_ARG;
+  if (!decay_args_ok(weight_decay, table_dev, table_n, origin)) return IB_E_ARG;
+  const DecayLaunch L(sched_kind, sched_warmup, sched_total, sched_min_ratio, weight_decay, table_dev, table_n, origin);
+  return optim_sources(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nsrc, start, len, kind,
+                       base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out, ema, ema_decay,
+                       ema_warmup, L.has_sc ? &L.sc : nullptr, stream, L.has_dk ? &L.dk : nullptr);
 }

@@ -36,6 +36,7 @@ from .loss.RegressionLossEvaluator import component_weights
 from .lr_schedule import LrSchedule, active as active_schedule
 from .module import HipModule, flat_layout
 from .plans import ParamSource
+from .weight_decay import check_weight_decay, decay_ranges, decayed_names
 
 
 TORCH_OPTIM_CLASS = {"sgd": "SGD", "adam": "Adam", "rmsprop": "RMSprop", "adagrad": "Adagrad", "adadelta": "Adadelta",
@@ -272,7 +273,7 @@ class HipTrainer:
     def __init__(self, model: HipModule, task: str, opt_type: str = "rmsprop", lr: float = 1e-4, args=None,
                  group=None, bucket_mb: float = 13.0, use_graph: bool = True, overlap_comm: Optional[bool] = None,
                  ema_decay: float = 0.0, ema_warmup: bool = True, cond_cols: int = 0, cond_drop: float = 0.0,
-                 lr_schedule=None):
+                 lr_schedule=None, weight_decay: float = 0.0, decay_filter=None):
         if task not in ("diffusion", "regression"):
             raise ValueError(task)
         if int(cond_cols) < 0 or (cond_cols and task != "diffusion"):
@@ -288,6 +289,9 @@ class HipTrainer:
             raise ValueError("Invalid optimizer type: " + opt_type)          # train.py:195-197
         if lr_schedule is not None and not isinstance(lr_schedule, LrSchedule):
             raise ValueError(f"lr_schedule must be None or an LrSchedule, got {type(lr_schedule).__name__}")
+        if decay_filter is not None and not callable(decay_filter):
+            raise ValueError(f"decay_filter must be None or a callable (name, shape) -> bool, got {type(decay_filter).__name__}")
+        self.weight_decay = check_weight_decay(weight_decay)
         self.model, self.task, self.opt_type, self.lr = model, task, opt_type, lr
         # diffusion: the first cond_cols columns of every frame row are conditioning -- they reach the denoiser clean at every
         # noise level and are not scored (csrc/diffusion.hip q_sample_cond_kernel, csrc/loss.hip mse_partial_cond_kernel).
@@ -359,6 +363,13 @@ class HipTrainer:
         # its own step from the device step counter (csrc/optim.hip, lr_scheduled), so a replayed graph follows it.  None, or a
         # constant schedule without warmup: the launches without a schedule, as ever.
         self.lr_schedule = lr_schedule
+        # decoupled weight decay (weight_decay.py, include/ib_hip_decay.h): every optimizer launch multiplies the quads of its
+        # slice that lie in a decayed range by 1 - lr_s * weight_decay before their update.  The ranges -- by default the
+        # parameters with ndim >= 2, each with its alignment padding, neighbours merged -- go to device memory once; the
+        # launches pass that one pointer and their slice's offset.  0: the launches without decay, as ever, and no table.
+        self.decayed = decayed_names(shapes, decay_filter)
+        self.decay_ranges = decay_ranges(self.layout, self.decayed)
+        self.decay_table = hip.DecayTable(self.decay_ranges, dev) if self.weight_decay > 0 else None
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)      # completed steps (device-resident)
         self.ticket = torch.zeros(hip.optim_ticket_words(), dtype=torch.int32, device=dev)   # optimizer exit tickets
         self.steps_done = 0
@@ -608,7 +619,7 @@ class HipTrainer:
         hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr, step=0,
                        step_dev=self.step_dev, ticket=self.ticket, grad_scale=1.0 / self.world,
                        shadow=sl(m._shadow) if dt == torch.bfloat16 else None, sources=src, **self._ema_args(sl),
-                       **self._sched_args())
+                       **self._sched_args(), **self._decay_args(lo))
 
     def _ema_args(self, sl) -> Dict:
         """optim_step's EMA arguments for a launch over the slice `sl` selects (none with the EMA off: the entries without it)"""
@@ -622,6 +633,14 @@ class HipTrainer:
         if active_schedule(self.lr_schedule) is None:
             return {}
         return {"lr_schedule": self.lr_schedule}
+
+    def _decay_args(self, lo: int) -> Dict:
+        """optim_step's weight-decay arguments for a launch over a slice that starts at element `lo` of the flat buffers: the
+        one table and the slice's origin (none with weight_decay = 0: the entries without it).  The launch that only counts
+        the step names its whole slice as done, so it decays nothing."""
+        if self.decay_table is None:
+            return {}
+        return {"weight_decay": self.weight_decay, "decay_table": self.decay_table, "decay_origin": int(lo)}
 
     def current_lr(self) -> float:
         """the rate the NEXT step's optimizer launches use (host arithmetic, no device read): lr_at(lr, steps_done + 1) of the
@@ -675,7 +694,7 @@ class HipTrainer:
             hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr, step=1,
                            step_dev=self.step_dev, grad_scale=1.0 / self.world,
                            shadow=sl(m._shadow) if dt == torch.bfloat16 else None, **self._ema_args(sl),
-                           **self._sched_args())
+                           **self._sched_args(), **self._decay_args(lo))
         self._br_opt.run(fn)
 
     def _prefix_range(self, prefix: str) -> Tuple[int, int]:
@@ -702,7 +721,7 @@ class HipTrainer:
         hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr, step=1,
                        step_dev=self.step_dev, grad_scale=1.0 / self.world,
                        shadow=sl(m._shadow) if dt == torch.bfloat16 else None, sources=sources, **self._ema_args(sl),
-                       **self._sched_args())
+                       **self._sched_args(), **self._decay_args(lo))
         self._early_done.append((lo, hi))
 
     def _stage(self, batch) -> Dict[str, torch.Tensor]:
@@ -1041,10 +1060,11 @@ class HipTrainer:
 
     def optimizer_state_dict(self) -> Dict:
         """"lr" is the BASE rate; "lr_schedule" the schedule's four fields, or None without one (a constant schedule
-        without warmup counts as none)"""
+        without warmup counts as none); "weight_decay" the fp32 decay and "decayed" the names it applies to (none at 0)"""
         sched = active_schedule(self.lr_schedule)
         return {"opt_type": self.opt_type, "lr": self.lr, "step": self.steps_done,
                 "lr_schedule": None if sched is None else sched.fields(),
+                "weight_decay": self.weight_decay, "decayed": list(self.decayed) if self.weight_decay > 0 else [],
                 "layout": {k: list(v) for k, v in self.layout.items()},
                 "s1": None if self.s1 is None else self.s1.detach().cpu(),
                 "s2": None if self.s2 is None else self.s2.detach().cpu()}
@@ -1053,7 +1073,9 @@ class HipTrainer:
         """the same state in torch.optim's own grammar ({'state': {i: {...}}, 'param_groups': [...]}, parameters numbered
         in model.parameters() order as `optim.X(model.parameters(), lr=...)` numbers them, train.py:183-194): what a
         reference-style (`--eager` / torch.optim) run or the reference itself can load.  param_groups carry the BASE rate:
-        torch.optim has no place for this trainer's schedule, so a scheduled run's rate at the checkpoint is not in here"""
+        torch.optim has no place for this trainer's schedule, so a scheduled run's rate at the checkpoint is not in here.
+        Nor has it one for the decoupled weight decay with its per-parameter rule: like the schedule, the decay is not in
+        here (param_groups carry no weight_decay of this trainer's)"""
         names = [k for k, _ in self.model.named_parameters()]
         state = torch_state_from_flat(self.opt_type, self.steps_done, names, lambda k: self._params[k].shape, self.layout,
                                       self.s1, self.s2)
@@ -1072,6 +1094,13 @@ class HipTrainer:
             if mine != theirs:
                 raise hip.HipError(f"the checkpoint's learning-rate schedule ({theirs if theirs else 'none'}) differs from "
                                    f"this trainer's ({mine if mine else 'none'})")
+        theirs_wd = float(sd.get("weight_decay", 0.0))     # a payload without the key is an older checkpoint: no decay
+        theirs_names = list(sd.get("decayed", [])) if theirs_wd > 0 else []
+        mine_names = list(self.decayed) if self.weight_decay > 0 else []
+        if theirs_wd != self.weight_decay or theirs_names != mine_names:
+            what = "" if theirs_wd != self.weight_decay else " over other parameters"
+            raise hip.HipError(f"the checkpoint's weight decay ({theirs_wd:g}{what}) differs from this trainer's "
+                               f"({self.weight_decay:g})")
         if self.s1 is not None:
             self.s1.copy_(sd["s1"])
         if self.s2 is not None:

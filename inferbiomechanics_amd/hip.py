@@ -16,7 +16,8 @@ of a posterior ensemble (csrc/ensemble.hip) in a seventh, ``include/ib_hip_ensem
 sampling step and the per-column range of a window table (csrc/clip.hip) in an eighth, ``include/ib_hip_clip.h``
 (``_CLIP_SIGS``), the per-column standardisation of the diffusion windows (csrc/standardize.hip) in a ninth,
 ``include/ib_hip_standardize.h`` (``_STANDARDIZE_SIGS``), the learning-rate schedule of the fused optimizer (csrc/optim.hip)
-in a tenth, ``include/ib_hip_sched.h`` (``_SCHED_SIGS``); a name may be declared once in the ten.
+in a tenth, ``include/ib_hip_sched.h`` (``_SCHED_SIGS``), its decoupled weight decay in an eleventh,
+``include/ib_hip_decay.h`` (``_DECAY_SIGS``); a name may be declared once in the eleven.
 """
 from __future__ import annotations
 
@@ -43,6 +44,7 @@ ENSEMBLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_e
 CLIP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_clip.h")
 STANDARDIZE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_standardize.h")
 SCHED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sched.h")
+DECAY_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_decay.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -125,6 +127,11 @@ _SCHED_SIGS = _parse_header(_read_header(SCHED_HEADER_PATH))                    
 _BOUND = {**_ALL_SIGS, **_SCHED_SIGS}
 if len(_BOUND) != len(_ALL_SIGS) + len(_SCHED_SIGS):
     raise HipError(f"declared in two headers: {sorted(n for n in _SCHED_SIGS if n in _ALL_SIGS)}")
+# the eleventh header likewise: _BOUND stays the ten headers' as their tests pin it; _sig() and lib() go through _LOADED
+_DECAY_SIGS = _parse_header(_read_header(DECAY_HEADER_PATH))                        # the optimizer's weight decay, off by default
+_LOADED = {**_BOUND, **_DECAY_SIGS}
+if len(_LOADED) != len(_BOUND) + len(_DECAY_SIGS):
+    raise HipError(f"declared in two headers: {sorted(n for n in _DECAY_SIGS if n in _BOUND)}")
 _kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_STITCH_KMAX[ \t]+(\d+)[ \t]*$", _read_header(STITCH_HEADER_PATH), flags=re.M)
 if _kmax is None:
     raise HipError(f"{STITCH_HEADER_PATH} does not define IB_STITCH_KMAX")
@@ -183,14 +190,19 @@ def sched_decls() -> List[str]:
     return sorted(_SCHED_SIGS)
 
 
+def decay_decls() -> List[str]:
+    """Every function include/ib_hip_decay.h declares"""
+    return sorted(_DECAY_SIGS)
+
+
 def _sig(name: str):
     """(restype, argtypes) of an entry point of any header"""
-    return _BOUND[name]
+    return _LOADED[name]
 
 
 # pure host queries: no launch, no stream
 _HOST_ONLY = ("_workspace", "_supported", "_workgroups", "_packed_elems", "_partial_width", "_last_path", "_slab_count",
-              "_ticket_words", "_mask_bytes")
+              "_ticket_words", "_mask_bytes", "_table_bytes")
 _HOST_NAMES = ("ib_version", "ib_error_string")
 
 
@@ -234,9 +246,9 @@ class _DryRunLib:
                 rd = lambda p, ct: ctypes.cast(p, ctypes.POINTER(ct))
                 st, ln, kd = rd(a[13], ctypes.c_int64), rd(a[14], ctypes.c_int64), rd(a[15], ctypes.c_int32)
                 self.ema_ranges.append((a[25], int(a[5]), [(st[j], ln[j]) for j in range(m) if kd[j] == 3]))
-            elif name == "ib_optim_step_sched" and a[12] is not None:
+            elif name in ("ib_optim_step_sched", "ib_optim_step_decay") and a[12] is not None:
                 self.ema_ranges.append((a[12], int(a[5]), []))
-            elif name == "ib_optim_step_sources_sched" and a[25] is not None:
+            elif name in ("ib_optim_step_sources_sched", "ib_optim_step_sources_decay") and a[25] is not None:
                 m = int(a[12])
                 rd = lambda p, ct: ctypes.cast(p, ctypes.POINTER(ct))
                 st, ln, kd = rd(a[13], ctypes.c_int64), rd(a[14], ctypes.c_int64), rd(a[15], ctypes.c_int32)
@@ -467,7 +479,7 @@ def lib():
             raise HipError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C inferbiomechanics_amd/csrc` (hipcc --offload-arch=gfx950). There is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _BOUND.items():
+        for name, (res, args) in _LOADED.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -1395,7 +1407,8 @@ def optim_ticket_words() -> int:
 
 
 def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=1.0, shadow=None, ticket=None,
-               sources=None, ema=None, ema_decay=0.0, ema_warmup=True, lr_schedule=None):
+               sources=None, ema=None, ema_decay=0.0, ema_warmup=True, lr_schedule=None, weight_decay=0.0, decay_table=None,
+               decay_origin=0):
     """step: the step number of the bias corrections; with `step_dev` the kernel uses `*step_dev + step`, so the default is
     0 there (the device counter alone) and 1 without a device counter.
     sources = (items, part, rows, segs): the gradient of some ranges of g is still partial sums -- items =
@@ -1408,7 +1421,22 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
     without it.
     lr_schedule: None or an lr_schedule.LrSchedule.  None or a constant schedule without warmup: the four entries above, as
     ever.  Anything else: the *_sched entries (include/ib_hip_sched.h) -- `lr` is then the BASE rate and the kernel computes
-    the rate of its own step number from it, LrSchedule.lr_at(lr, step), so a replayed graph follows the device counter."""
+    the rate of its own step number from it, LrSchedule.lr_at(lr, step), so a replayed graph follows the device counter.
+    weight_decay: 0 takes the entries above, as ever.  > 0: the *_decay entries (include/ib_hip_decay.h) -- every quad of p
+    whose global position decay_origin + 4 q lies in a range of decay_table (a DecayTable, built once over the whole flat
+    buffer; decay_origin is the offset of p[0] in it) is multiplied by weight_decay.decay_factor(rate of this step,
+    weight_decay) before its update; ranges named as done (kind 3) are left alone."""
+    decay = ()
+    if float(weight_decay) != 0.0:
+        if not float(weight_decay) > 0.0:                      # negative or NaN
+            raise HipError(f"weight_decay must be >= 0, got {weight_decay}")
+        if not isinstance(decay_table, DecayTable):
+            raise HipError(f"weight_decay needs a DecayTable, got {type(decay_table).__name__}")
+        if int(decay_origin) < 0 or int(decay_origin) % 4:
+            raise HipError(f"decay_origin must be a non-negative multiple of 4, got {decay_origin}")
+        if decay_table.buf.device != p.device:
+            raise HipError("decay_table lives on another device than p")
+        decay = (float(weight_decay), _ptr(decay_table.buf), decay_table.n, int(decay_origin))
     sched = ()
     if lr_schedule is not None:
         from .lr_schedule import LrSchedule
@@ -1488,7 +1516,10 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
                 _ptr(ticket), _ptr(shadow), m, cv(start), cv(ln), cv(kind), cv(base), cv(stride), cv(count), cv(scale),
                 ctypes.c_void_p(loss[0]) if loss else None, ld, int(rows), loss[1] if loss else 0.0,
                 _ptr(loss[2]) if loss else None)
-        if sched:
+        if decay:
+            _check(lib().ib_optim_step_sources_decay(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)),
+                                                     *(sched or _NO_SCHED), *decay, stream_ptr()), "ib_optim_step_sources_decay")
+        elif sched:
             _check(lib().ib_optim_step_sources_sched(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), *sched,
                                                      stream_ptr()), "ib_optim_step_sources_sched")
         elif ema is None:
@@ -1499,7 +1530,10 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
         return
     args = (OPT[opt], _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), n, float(lr), float(grad_scale), int(step), _ptr(step_dev),
             _ptr(ticket), _ptr(shadow))
-    if sched:
+    if decay:
+        _check(lib().ib_optim_step_decay(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), *(sched or _NO_SCHED),
+                                         *decay, stream_ptr()), "ib_optim_step_decay")
+    elif sched:
         _check(lib().ib_optim_step_sched(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), *sched, stream_ptr()),
                "ib_optim_step_sched")
     elif ema is None:
@@ -1507,6 +1541,27 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
     else:
         _check(lib().ib_optim_step_ema(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), stream_ptr()),
                "ib_optim_step_ema")
+
+
+_NO_SCHED = (0, 0, 0, 0.0)      # IB_SCHED_CONSTANT without warmup: the *_decay entries then run at the host's lr
+
+
+class DecayTable:
+    """the decayed ranges of a flat parameter buffer in device memory (ib_decay_table_build): ranges = [(start, len)] in
+    flat-buffer coordinates, sorted and disjoint, every start a multiple of 4; a length counts as rounded up to a multiple
+    of 4.  Built once; every optimizer launch passes the same pointer plus the offset of its slice."""
+
+    def __init__(self, ranges, device):
+        self.ranges = [(int(a), int(b)) for a, b in ranges]
+        self.n = len(self.ranges)
+        nbytes = int(lib().ib_decay_table_bytes(self.n))
+        self.buf = torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
+        if not (self.buf.is_cuda or _dry_run):
+            raise HipError("DecayTable: a device (HBM) table required")
+        arr = lambda k: (ctypes.c_int64 * max(self.n, 1))(*[r[k] for r in self.ranges])
+        start, ln = arr(0), arr(1)
+        cv = lambda a: ctypes.cast(a, ctypes.c_void_p)
+        _check(lib().ib_decay_table_build(cv(start), cv(ln), self.n, _ptr(self.buf), stream_ptr()), "ib_decay_table_build")
 
 
 def lr_schedule_eval(lr: float, lr_schedule, steps, out=None):
