@@ -3,6 +3,7 @@
 // (ROCm 7.2) dies in its inliner's call-graph update.
 #pragma once
 #include "wave_prims.h"
+#include "image_sweep.h"
 #include <utility>
 
 #ifdef IB_AB
@@ -158,6 +159,71 @@ __device__ __forceinline__ ff_karg_t<P>& ff_kargs() {
   return *(ff_karg_t<P>*)__builtin_amdgcn_kernarg_segment_ptr();
 }
 
+// ---- the image sweep (image_sweep.h): the workgroup's slice of every weight part its form will stream, requested before the
+// first row load.  A thread issues up to IB_SWEEP_LOADS 16-byte loads into registers that are dead at the head; on gfx9 loads
+// retire in order, so the wait of the first row pass already covers them and ff_sweep_drop (an empty asm that only names the
+// registers, placed behind that pass) ends their life without a wait of its own.  ptr[k] may be null where part[k] == 0.
+constexpr int FF_WBYTES = (int)(FF_WELEMS * sizeof(bf16_t));      // one packed [512 x 512] weight image
+// bytes of the parts a form streams, in the order it consumes them (forward: wop, w1p, w2p, wqkvp; backward: wqkvtp, w2tp,
+// w1tp, wotp, wqkvtp_own); the kernels and the probe entry (ib_image_sweep_slices) both take their lists from here
+__host__ __device__ inline void ff_sweep_parts_fwd(bool out, bool qkv, int nchunk, int (&part)[IB_SWEEP_PARTS]) {
+  part[0] = out ? FF_WBYTES : 0;
+  part[1] = part[2] = nchunk * FF_WBYTES;
+  part[3] = qkv ? 3 * FF_WBYTES : 0;
+  part[4] = 0;
+}
+__host__ __device__ inline void ff_sweep_parts_bwd(bool out, bool qkvh, bool att, int nchunk, int (&part)[IB_SWEEP_PARTS]) {
+  part[0] = qkvh ? 3 * FF_WBYTES : 0;
+  part[1] = part[2] = nchunk * FF_WBYTES;
+  part[3] = out ? FF_WBYTES : 0;
+  part[4] = att ? 3 * FF_WBYTES : 0;
+}
+// FF_SWEEP_ON: in the measurement build one more template parameter of the two kernels (their IB_NO_IMAGE_SWEEP arm is the
+// instantiation with it false); in the shipping library a constant, and the kernels keep their parameter lists and names
+#ifdef IB_AB
+#define FF_SWEEP_TPARAM , bool FF_SWEEP_ON = true
+#else
+#define FF_SWEEP_TPARAM
+constexpr bool FF_SWEEP_ON = true;
+#endif
+struct FfSweep { u32x4_t v[IB_SWEEP_LOADS]; };
+__device__ __forceinline__ void ff_sweep_issue(const bf16_t* const (&ptr)[IB_SWEEP_PARTS], const int (&part)[IB_SWEEP_PARTS],
+                                               int tid, FfSweep& s) {
+  int off[IB_SWEEP_PARTS], len[IB_SWEEP_PARTS];
+  const int bytes = ib_sweep_slices(part, (int)gridDim.x, (int)blockIdx.x, off, len);
+  tid = ff_fresh(tid);                                     // nothing computed here is kept for a later phase (ff_fresh)
+#pragma unroll
+  for (int j = 0; j < IB_SWEEP_LOADS; ++j) {
+    const int u = (j * FF_THREADS + tid) * 16;            // this thread's piece of the workgroup's bytes, parts end to end
+    s.v[j] = u32x4_t{0u, 0u, 0u, 0u};
+    if (u < bytes) {
+      const unsigned char* a = nullptr;
+      int start = 0;
+#pragma unroll
+      for (int k = 0; k < IB_SWEEP_PARTS; ++k) {
+        if (u >= start && u < start + len[k]) a = reinterpret_cast<const unsigned char*>(ptr[k]) + off[k] + (u - start);
+        start += len[k];
+      }
+      s.v[j] = *reinterpret_cast<const u32x4_t*>(a);
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);                       // nothing of the kernel moves ahead of the sweep's requests
+}
+__device__ __forceinline__ void ff_sweep_drop(const FfSweep& s) {
+  static_assert(IB_SWEEP_LOADS == 3, "one operand per load");
+  asm volatile("" ::"v"(s.v[0]), "v"(s.v[1]), "v"(s.v[2]));
+}
+
+// The same view through a pointer the optimiser cannot trace back to the kernarg segment: a field read through it is not
+// merged with a later read of the same field, so the image sweep's reads of the part pointers at the head do not keep them in
+// SGPRs until the phases that stream them (these kernels' register plans sit at their budget: SGPRs spill into VGPR lanes).
+template <class P>
+__device__ __forceinline__ ff_karg_t<P>& ff_kargs_fresh() {
+  ff_karg_t<P>* q = (ff_karg_t<P>*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(q));
+  return *q;
+}
+
 // ---- row-wise passes: wave w owns rows w, w + 8, ... of the panel, a lane 8 consecutive columns of the row (one row per
 // wave-instruction); the row sums are DPP-only (ff_row_sum).  Two rows at a time, stage by stage.
 
@@ -214,11 +280,12 @@ __device__ __forceinline__ void ff_ln_rows_fwd(unsigned char* img, bool back, in
 // LayerNorm backward of the panel's rows: dy rows from HBM (`dyg`) or, if `dyimg`, from an LDS image; the saved LayerNorm
 // input rows and statistics from HBM; dz rows -> image `zimg` (rows beyond the panel: exact zeros) and -> HBM (`dzg`);
 // this lane's dgamma | dbeta sums over the wave's rows come back in dgam / dbet (ff_colsum_put / ff_colsum_out add them up).
-template <bool FROM_IMG>
+// `requested()` runs behind the row requests, before the first row is used (the image sweep's registers end their life there).
+template <bool FROM_IMG, class Requested>
 __device__ __forceinline__ void ff_ln_rows_bwd(const bf16_t* dyg, const unsigned char* dyimg, const bf16_t* sg,
                                                const float* mean_g, const float* rstd_g, const float* gamma, int nrows,
                                                int wave_s, int lane, unsigned char* zimg, bf16_t* dzg, float (&dgam)[8],
-                                               float (&dbet)[8]) {
+                                               float (&dbet)[8], Requested&& requested) {
   constexpr int NJ = FF_ROWS / FF_WAVES;
   const float invH = 1.f / (float)FF_D;
   const int c8 = lane * 8;
@@ -234,6 +301,7 @@ __device__ __forceinline__ void ff_ln_rows_bwd(const bf16_t* dyg, const unsigned
   }
   float gm[8];
   ff_load8f(gamma + c8, gm);
+  requested();
 #pragma unroll
   for (int k = 0; k < 8; ++k) { dgam[k] = 0.f; dbet[k] = 0.f; }
   constexpr int G = 2;
@@ -272,6 +340,13 @@ __device__ __forceinline__ void ff_ln_rows_bwd(const bf16_t* dyg, const unsigned
       if (r < nrows) *reinterpret_cast<uint4*>(dzg + (int64_t)r * FF_D + c8) = zq;
     }
   }
+}
+template <bool FROM_IMG>
+__device__ __forceinline__ void ff_ln_rows_bwd(const bf16_t* dyg, const unsigned char* dyimg, const bf16_t* sg,
+                                               const float* mean_g, const float* rstd_g, const float* gamma, int nrows,
+                                               int wave_s, int lane, unsigned char* zimg, bf16_t* dzg, float (&dgam)[8],
+                                               float (&dbet)[8]) {
+  ff_ln_rows_bwd<FROM_IMG>(dyg, dyimg, sg, mean_g, rstd_g, gamma, nrows, wave_s, lane, zimg, dzg, dgam, dbet, [] {});
 }
 // a wave's per-lane dgamma | dbeta sums -> its rows of the exchange area `cr` ([2][8 waves][512] floats of LDS)
 __device__ __forceinline__ void ff_colsum_put(float* cr, int wave, int lane, const float (&dgam)[8], const float (&dbet)[8]) {

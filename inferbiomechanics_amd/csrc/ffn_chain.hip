@@ -25,6 +25,7 @@
 // L2 -> CU weight stream (4 MB per workgroup and direction).
 #include "ffn_chain.h"
 #include "../../include/ib_hip_head.h"
+#include "../../include/ib_hip_sweep.h"
 #include "head_jobs.h"
 
 #ifdef IB_AB
@@ -58,9 +59,13 @@ struct FfnFwdParams {
 
 // INFER: the frozen-weight forward (DDIM sampler at batches beyond the row-panel kernels of linln_panel.hip): nothing is saved
 // for a backward -- no f1 / s1 / s2 / x1 rows, no statistics, no ReLU bits leave the workgroup
-template <bool OUT, bool QKV, bool ATT, bool INFER = false>
+// The image sweep at the head (ffn_chain.h): every training form has it, the frozen-weight forms do not.  The measurement
+// build gives the kernel one more template parameter, so that it also holds the training forms without the sweep (its
+// IB_NO_IMAGE_SWEEP arm); in the shipping library the kernels keep their four parameters and their names.
+template <bool OUT, bool QKV, bool ATT, bool INFER = false FF_SWEEP_TPARAM>
 __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams) {
   ff_karg_t<FfnFwdParams>& p = ff_kargs<FfnFwdParams>();
+  constexpr bool SWEEP = FF_SWEEP_ON && !INFER;
   static_assert(!ATT || QKV, "the attention rides behind the QKV tail");
   static_assert(!INFER || (OUT && !ATT), "the frozen-weight form: attention epilogue, no attention tail");
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * FF_BUF];
@@ -74,8 +79,17 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams)
   const int colb = wave * 16 * FF_NT + 4 * g;             // this lane's first column inside a 512-wide GEMM output
   const int c8 = lane * 8;                                // row-wise passes: 8 consecutive columns of the wave's row
   IB_STAMP(p.prof, 64, 0, tid == 0);
+  [[maybe_unused]] FfSweep sweep;
+  if constexpr (SWEEP) {
+    int part[IB_SWEEP_PARTS];
+    ff_karg_t<FfnFwdParams>& ps = ff_kargs_fresh<FfnFwdParams>();
+    ff_sweep_parts_fwd(OUT, QKV, ps.nchunk, part);
+    const bf16_t* const parts[IB_SWEEP_PARTS] = {OUT ? ps.wop : nullptr, ps.w1p, ps.w2p, QKV ? ps.wqkvp : nullptr, nullptr};
+    ff_sweep_issue(parts, part, tid, sweep);
+  }
   // ---- the panel's input rows -> image X (16-byte pieces, rows beyond the panel = copies of the last row: finite)
   ff_panel_in(p.x1 + (int64_t)r0 * FF_D, imgX, nrows, tid);
+  if constexpr (SWEEP) ff_sweep_drop(sweep);
   if constexpr (OUT) {
     // attention output rows -> image H; o = attn . Wo^T (GEMM); s1 = x + o + bo written over x in image X (each position is
     // read and written by the same lane); row-wise LayerNorm1 turns image X into x1, the feed-forward input
@@ -308,6 +322,19 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_fwd_kernel(FfnFwdParams)
   }
 }
 
+// one training form's launch: with the sweep, or -- measurement build, IB_NO_IMAGE_SWEEP set -- without
+template <bool OUT, bool QKV, bool ATT>
+void ffn_chain_fwd_go(int nwg, ib_stream_t stream, const FfnFwdParams& p) {
+#ifdef IB_AB
+  static const bool no_sweep = ib_ab_set("IB_NO_IMAGE_SWEEP");
+  if (no_sweep) {
+    hipLaunchKernelGGL((ffn_chain_fwd_kernel<OUT, QKV, ATT, false, false>), dim3(nwg), dim3(FF_THREADS), 0, ib_s(stream), p);
+    return;
+  }
+#endif
+  hipLaunchKernelGGL((ffn_chain_fwd_kernel<OUT, QKV, ATT>), dim3(nwg), dim3(FF_THREADS), 0, ib_s(stream), p);
+}
+
 
 // ---- weight packing: [512 x 512] sub-matrices of the row-major bf16 weights -> fragment-major 1-KiB blocks
 // (block (nt, kb) at (kb * 32 + nt) * 1 KiB; W_eff[n][k] = src[n * ld + k], or src[k * ld + n] when transposed)
@@ -394,6 +421,22 @@ extern "C" int ib_debug_set_ffn_prof(void*) { return IB_E_UNSUPPORTED; }       /
 
 extern "C" int ib_ffn_chain_supported(int64_t d, int64_t ffn) {
   return (d == FF_D && ffn > 0 && ffn % FF_CHUNK == 0 && ffn / FF_CHUNK <= FF_MAXCHUNK) ? 1 : 0;
+}
+// The image sweep's slice rule as the kernels apply it (include/ib_hip_sweep.h): a pure host query, nothing is launched.
+extern "C" int ib_image_sweep_slices(int backward, int out, int qkv, int att, int64_t d, int64_t ffn, int grid, int wg,
+                                     int64_t* part_bytes, int64_t* off, int64_t* len) {
+  if (!ib_ffn_chain_supported(d, ffn)) return IB_E_UNSUPPORTED;
+  if (!part_bytes || !off || !len || grid < 1 || wg < 0 || wg >= grid) return IB_E_ARG;
+  // the forms that exist: forward <OUT, QKV, ATT> with ATT -> QKV -> OUT; backward <OUT, QKVH, ATT> with QKVH | ATT -> OUT, not both
+  const bool o = out != 0, q = qkv != 0, a = att != 0;
+  if (backward ? ((q || a) && !o) || (q && a) : (a && !q) || (q && !o)) return IB_E_ARG;
+  int part[IB_SWEEP_PARTS], po[IB_SWEEP_PARTS], pl[IB_SWEEP_PARTS];
+  const int nc = (int)(ffn / FF_CHUNK);
+  if (backward) ff_sweep_parts_bwd(o, q, a, nc, part);
+  else ff_sweep_parts_fwd(o, q, nc, part);
+  const int bytes = ib_sweep_slices(part, grid, wg, po, pl);
+  for (int k = 0; k < IB_SWEEP_PARTS; ++k) { part_bytes[k] = part[k]; off[k] = po[k]; len[k] = pl[k]; }
+  return bytes;
 }
 // elements of ONE layer's packed image: {W1 chunks | W2 chunks | W2^T chunks | W1^T chunks | Wo | Wo^T | Wqkv x 3 | Wqkv^T x 3},
 // each 512 x 512
@@ -557,10 +600,10 @@ int ffn_chain_fwd_launch(const void* x1, const void* packed, const float* b1, co
   p.M = (int)M; p.P = P; p.FF = (int)ffn; p.nchunk = nc; p.ln_eps = ln_eps;
   p.prof = IB_AB_PROF(g_ffn_prof);
   IB_PATH(IB_PATH_FFN_CHAIN);
-  if (att) hipLaunchKernelGGL((ffn_chain_fwd_kernel<true, true, true>), dim3(nwg), dim3(FF_THREADS), 0, ib_s(stream), p);
-  else if (tail) hipLaunchKernelGGL((ffn_chain_fwd_kernel<true, true, false>), dim3(nwg), dim3(FF_THREADS), 0, ib_s(stream), p);
-  else if (out) hipLaunchKernelGGL((ffn_chain_fwd_kernel<true, false, false>), dim3(nwg), dim3(FF_THREADS), 0, ib_s(stream), p);
-  else hipLaunchKernelGGL((ffn_chain_fwd_kernel<false, false, false>), dim3(nwg), dim3(FF_THREADS), 0, ib_s(stream), p);
+  if (att) ffn_chain_fwd_go<true, true, true>(nwg, stream, p);
+  else if (tail) ffn_chain_fwd_go<true, true, false>(nwg, stream, p);
+  else if (out) ffn_chain_fwd_go<true, false, false>(nwg, stream, p);
+  else ffn_chain_fwd_go<false, false, false>(nwg, stream, p);
   IB_CHECK_LAUNCH();
   return IB_OK;
 }

@@ -32,9 +32,13 @@ struct FfnBwdParams {
 // dst rows (image Z) = dqkv . Wqkv + addend: the addend rows wait in image Z, dqkv comes through image D one 512-column
 // chunk at a time (the next chunk's rows are requested during this chunk's GEMM and land after the barrier).  Leaves image Z
 // complete behind a barrier.
+// `landed()` runs behind the first row pass (the image sweep's registers end their life there).
+template <class Landed>
 __device__ __forceinline__ void ff_qkv_dgrad(const bf16_t* addend, const bf16_t* dq, const bf16_t* wqkvtp, unsigned char* imgZ,
-                                             unsigned char* imgD, int nrows, int tid, int wave_s, int l16, int colb) {
+                                             unsigned char* imgD, int nrows, int tid, int wave_s, int l16, int colb,
+                                             Landed&& landed) {
   ff_panel_in(addend, imgZ, nrows, tid);
+  landed();
   ff_panel_in(dq, imgD, nrows, tid, 3 * FF_D);
   __syncthreads();
   f32x4_t accd[4][FF_NT];
@@ -86,9 +90,12 @@ __device__ __forceinline__ void ff_qkv_dgrad(const bf16_t* addend, const bf16_t*
   __syncthreads();                     // image Z = dqkv . Wqkv + addend
 }
 
-template <bool OUT, bool QKVH, bool ATT>
+// The image sweep at the head (ffn_chain.h).  The measurement build gives the kernel one more template parameter, so that it
+// also holds the forms without the sweep (its IB_NO_IMAGE_SWEEP arm); in the shipping library the kernels keep their names.
+template <bool OUT, bool QKVH, bool ATT FF_SWEEP_TPARAM>
 __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams) {
   ff_karg_t<FfnBwdParams>& p = ff_kargs<FfnBwdParams>();
+  constexpr bool SWEEP = FF_SWEEP_ON;
   static_assert(!ATT || OUT, "the attention backward rides behind the out-projection's dgrad");
   __shared__ float attL[ATT ? FF_WAVES : 1][64], attD[ATT ? FF_WAVES : 1][64];   // per head: the rows' lse, D = sum_key P dP
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * FF_BUF];
@@ -101,16 +108,26 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
   const int r0 = blockIdx.x * p.P;
   const int nrows = min(p.P, p.M - r0);
   IB_STAMP(p.prof, 64, 0, tid == 0);
+  [[maybe_unused]] FfSweep sweep;
+  if constexpr (SWEEP) {
+    int part[IB_SWEEP_PARTS];
+    ff_karg_t<FfnBwdParams>& ps = ff_kargs_fresh<FfnBwdParams>();
+    ff_sweep_parts_bwd(OUT, QKVH, ATT, ps.nchunk, part);
+    const bf16_t* const parts[IB_SWEEP_PARTS] = {QKVH ? ps.wqkvtp : nullptr, ps.w2tp, ps.w1tp, OUT ? ps.wotp : nullptr,
+                                                 ATT ? ps.wqkvtp_own : nullptr};
+    ff_sweep_issue(parts, part, tid, sweep);
+  }
   if constexpr (QKVH) {
     // ---- dy = dqkv_next . Wqkv_next + ds1_next (the NEXT layer's in-projection dgrad + its residual addend) -> image Z
     ff_qkv_dgrad(p.ds1_next + (int64_t)r0 * FF_D, p.dqkv_next + (int64_t)r0 * (3 * FF_D), p.wqkvtp, imgZ, imgD, nrows, tid,
-                 wave_s, l16, ff_colb());
+                 wave_s, l16, ff_colb(), [&] { if constexpr (SWEEP) ff_sweep_drop(sweep); });
   }
   // ---- LayerNorm2 backward, row-wise: dz2 rows -> image Z (+ HBM); its dgamma | dbeta through image D's storage
   {
     float dgam[8], dbet[8];
     ff_ln_rows_bwd<QKVH>(p.dy + (int64_t)r0 * FF_D, imgZ, p.s2 + (int64_t)r0 * FF_D, p.mean + r0, p.rstd + r0, p.gamma, nrows,
-                         wave_s, lane, imgZ, p.ds2 + (int64_t)r0 * FF_D, dgam, dbet);
+                         wave_s, lane, imgZ, p.ds2 + (int64_t)r0 * FF_D, dgam, dbet,
+                         [&] { if constexpr (SWEEP && !QKVH) ff_sweep_drop(sweep); });
     ff_colsum_put(reinterpret_cast<float*>(imgD), wave, lane, dgam, dbet);
   }
   __syncthreads();                       // image Z = dz2 complete; the exchange rows are written
@@ -415,6 +432,19 @@ __global__ __launch_bounds__(FF_THREADS) void ffn_chain_bwd_kernel(FfnBwdParams)
   }
 }
 
+// one form's launch: with the sweep, or -- measurement build, IB_NO_IMAGE_SWEEP set -- without
+template <bool OUT, bool QKVH, bool ATT>
+void ffn_chain_bwd_go(int nwg, ib_stream_t stream, const FfnBwdParams& p) {
+#ifdef IB_AB
+  static const bool no_sweep = ib_ab_set("IB_NO_IMAGE_SWEEP");
+  if (no_sweep) {
+    hipLaunchKernelGGL((ffn_chain_bwd_kernel<OUT, QKVH, ATT, false>), dim3(nwg), dim3(FF_THREADS), 0, ib_s(stream), p);
+    return;
+  }
+#endif
+  hipLaunchKernelGGL((ffn_chain_bwd_kernel<OUT, QKVH, ATT>), dim3(nwg), dim3(FF_THREADS), 0, ib_s(stream), p);
+}
+
 }  // namespace
 
 namespace {
@@ -451,10 +481,10 @@ int ffn_chain_bwd_launch(const void* dy, const void* s2, const float* mean, cons
   p.M = (int)M; p.P = P; p.FF = (int)ffn; p.nchunk = nc;
   p.prof = IB_AB_PROF(g_ffn_prof);
   IB_PATH(IB_PATH_FFN_CHAIN);
-  if (att) hipLaunchKernelGGL((ffn_chain_bwd_kernel<true, false, true>), dim3(nwg), dim3(FF_THREADS), 0, ib_s(stream), p);
-  else if (head) hipLaunchKernelGGL((ffn_chain_bwd_kernel<true, true, false>), dim3(nwg), dim3(FF_THREADS), 0, ib_s(stream), p);
-  else if (out) hipLaunchKernelGGL((ffn_chain_bwd_kernel<true, false, false>), dim3(nwg), dim3(FF_THREADS), 0, ib_s(stream), p);
-  else hipLaunchKernelGGL((ffn_chain_bwd_kernel<false, false, false>), dim3(nwg), dim3(FF_THREADS), 0, ib_s(stream), p);
+  if (att) ffn_chain_bwd_go<true, false, true>(nwg, stream, p);
+  else if (head) ffn_chain_bwd_go<true, true, false>(nwg, stream, p);
+  else if (out) ffn_chain_bwd_go<true, false, false>(nwg, stream, p);
+  else ffn_chain_bwd_go<false, false, false>(nwg, stream, p);
   IB_CHECK_LAUNCH();
   return IB_OK;
 }

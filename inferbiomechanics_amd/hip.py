@@ -17,7 +17,8 @@ sampling step and the per-column range of a window table (csrc/clip.hip) in an e
 (``_CLIP_SIGS``), the per-column standardisation of the diffusion windows (csrc/standardize.hip) in a ninth,
 ``include/ib_hip_standardize.h`` (``_STANDARDIZE_SIGS``), the learning-rate schedule of the fused optimizer (csrc/optim.hip)
 in a tenth, ``include/ib_hip_sched.h`` (``_SCHED_SIGS``), its decoupled weight decay in an eleventh,
-``include/ib_hip_decay.h`` (``_DECAY_SIGS``); a name may be declared once in the eleven.
+``include/ib_hip_decay.h`` (``_DECAY_SIGS``), the slice rule of the whole-layer kernels' image sweep (csrc/image_sweep.h) in a
+twelfth, ``include/ib_hip_sweep.h`` (``_SWEEP_SIGS``); a name may be declared once in the twelve.
 """
 from __future__ import annotations
 
@@ -45,6 +46,7 @@ CLIP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_clip.
 STANDARDIZE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_standardize.h")
 SCHED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sched.h")
 DECAY_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_decay.h")
+SWEEP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sweep.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -132,6 +134,11 @@ _DECAY_SIGS = _parse_header(_read_header(DECAY_HEADER_PATH))                    
 _LOADED = {**_BOUND, **_DECAY_SIGS}
 if len(_LOADED) != len(_BOUND) + len(_DECAY_SIGS):
     raise HipError(f"declared in two headers: {sorted(n for n in _DECAY_SIGS if n in _BOUND)}")
+# the twelfth header likewise: _LOADED stays the eleven headers' as their tests pin it; _sig() and lib() go through _ENTRIES
+_SWEEP_SIGS = _parse_header(_read_header(SWEEP_HEADER_PATH))                        # a host query: the image sweep's slices
+_ENTRIES = {**_LOADED, **_SWEEP_SIGS}
+if len(_ENTRIES) != len(_LOADED) + len(_SWEEP_SIGS):
+    raise HipError(f"declared in two headers: {sorted(n for n in _SWEEP_SIGS if n in _LOADED)}")
 _kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_STITCH_KMAX[ \t]+(\d+)[ \t]*$", _read_header(STITCH_HEADER_PATH), flags=re.M)
 if _kmax is None:
     raise HipError(f"{STITCH_HEADER_PATH} does not define IB_STITCH_KMAX")
@@ -195,14 +202,19 @@ def decay_decls() -> List[str]:
     return sorted(_DECAY_SIGS)
 
 
+def sweep_decls() -> List[str]:
+    """Every function include/ib_hip_sweep.h declares"""
+    return sorted(_SWEEP_SIGS)
+
+
 def _sig(name: str):
     """(restype, argtypes) of an entry point of any header"""
-    return _LOADED[name]
+    return _ENTRIES[name]
 
 
 # pure host queries: no launch, no stream
 _HOST_ONLY = ("_workspace", "_supported", "_workgroups", "_packed_elems", "_partial_width", "_last_path", "_slab_count",
-              "_ticket_words", "_mask_bytes", "_table_bytes")
+              "_ticket_words", "_mask_bytes", "_table_bytes", "_sweep_slices")
 _HOST_NAMES = ("ib_version", "ib_error_string")
 
 
@@ -479,7 +491,7 @@ def lib():
             raise HipError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C inferbiomechanics_amd/csrc` (hipcc --offload-arch=gfx950). There is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _LOADED.items():
+        for name, (res, args) in _ENTRIES.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -1615,6 +1627,16 @@ def ffn_chain_workgroups(M: int, d: int, ffn: int, T: int = 0) -> int:
     if T:
         return int(lib().ib_ffn_chain_attn_workgroups(int(M), int(d), int(ffn), int(T)))
     return int(lib().ib_ffn_chain_workgroups(int(M), int(d), int(ffn), None))
+
+
+def image_sweep_slices(backward: bool, out: bool, qkv: bool, att: bool, d: int, ffn: int, grid: int, wg: int):
+    """The image sweep's slices of workgroup `wg` of `grid` for one form of the whole-layer kernels (include/ib_hip_sweep.h):
+    (bytes, [(part_bytes, off, len)] x 5, parts in the order the form consumes them).  A host query: nothing is launched."""
+    arr = [(ctypes.c_int64 * 5)() for _ in range(3)]
+    rc = int(lib().ib_image_sweep_slices(int(backward), int(out), int(qkv), int(att), int(d), int(ffn), int(grid), int(wg), *arr))
+    if rc < 0:
+        _check(rc, "ib_image_sweep_slices")
+    return rc, list(zip(*(list(a) for a in arr)))
 
 
 def ffn_chain_mask_bytes(M: int, d: int, ffn: int, T: int = 0) -> int:
