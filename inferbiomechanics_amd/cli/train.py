@@ -136,6 +136,12 @@ class TrainCommand(AbstractCommand):
                             'normalisation gains / offsets) by 1 - rate x W before the update, inside the fused optimizer '
                             'launches, at the rate of that step. Saved in the checkpoints; a resumed run must give the same '
                             'value. Not with --eager. Default: 0 (off).')
+        p.add_argument('--max-grad-norm', type=float, default=0.0,
+                       help='Clip the gradient to this global L2 norm (torch.nn.utils.clip_grad_norm_): the norm is taken on '
+                            'the device and the coefficient applied inside the fused optimizer launch, with no host read per '
+                            'step. The step then updates all parameters in one launch behind the last gradient instead of '
+                            'per layer. "inf" measures the norm without clipping. Saved in the checkpoints; a resumed run must '
+                            'give the same value. Not with --eager. Default: 0 (off).')
 
     # ------------------------------------------------------------------------------------------
     def run(self, args: argparse.Namespace):
@@ -150,6 +156,7 @@ class TrainCommand(AbstractCommand):
         check_ema_args(args)
         check_lr_schedule(args)
         check_weight_decay_args(args)
+        check_max_grad_norm_args(args)
         check_cond_cols(model_type, getattr(args, 'cond_cols', 0))
         check_cond_drop(args)
         check_record_range(args)
@@ -242,7 +249,11 @@ class TrainCommand(AbstractCommand):
                                  ema_decay=getattr(args, 'ema_decay', 0.0),
                                  ema_warmup=not getattr(args, 'no_ema_warmup', False), cond_cols=cond_cols,
                                  cond_drop=cond_drop, lr_schedule=lr_schedule,
-                                 weight_decay=getattr(args, 'weight_decay', 0.0))
+                                 weight_decay=getattr(args, 'weight_decay', 0.0),
+                                 max_grad_norm=getattr(args, 'max_grad_norm', 0.0))
+            if trainer.clip:
+                print(f"Gradient clipping: global L2 norm at most {trainer.max_grad_norm:g}, taken and applied on the device "
+                      f"(one optimizer launch over the whole buffer per step)")
             if trainer.weight_decay > 0:
                 print(f"Weight decay {trainer.weight_decay:g} (decoupled) on {len(trainer.decayed)} of "
                       f"{len(trainer.layout)} parameter tensors")
@@ -257,6 +268,9 @@ class TrainCommand(AbstractCommand):
             epoch_checkpoint, _ = self.load_latest_checkpoint(model, optimizer=trainer if trainer is not None else optimizer,
                                                               checkpoint_dir=checkpoint_dir)
         except HipError as exc:
+            if "gradient-norm clip" in str(exc):
+                raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --max-grad-norm or use another "
+                                 f"--checkpoint-dir") from None
             if "weight decay" in str(exc):
                 raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --weight-decay or use another "
                                  f"--checkpoint-dir") from None
@@ -438,6 +452,8 @@ class TrainCommand(AbstractCommand):
                     train_eval.print_report(args, reset=False) if not diffusion else train_eval.print_report(reset=False)
                     if trainer is not None and trainer._sched_args():
                         print(f"[rank={rank}] learning rate {trainer.current_lr():.6g} at step {trainer.steps_done + 1}")
+                    if trainer is not None and trainer.clip:
+                        print(f"[rank={rank}] gradient norm {trainer.grad_norm():.6g}, clip coefficient {trainer.clip_coef():.6g}")
                     if rank == 0:
                         save_checkpoint(checkpoint_dir, epoch, i, model, trainer if trainer is not None else optimizer)
                 if last:
@@ -498,6 +514,16 @@ def check_weight_decay_args(args: argparse.Namespace):
         raise SystemExit(f"--weight-decay must be finite and >= 0, got {wd}")
     if wd > 0 and getattr(args, 'eager', False):
         raise SystemExit("--weight-decay needs the fused trainer: --eager runs torch.optim with only the rate set")
+
+
+def check_max_grad_norm_args(args: argparse.Namespace):
+    """--max-grad-norm X: >= 0 and not NaN (0: off, inf: measure only); the norm is taken and applied inside the fused step, so
+    --eager (torch.optim with only the rate set) has none"""
+    x = getattr(args, 'max_grad_norm', 0.0)
+    if not x >= 0.0:                                    # NaN fails the comparison
+        raise SystemExit(f"--max-grad-norm must be >= 0 and not NaN, got {x}")
+    if x > 0 and getattr(args, 'eager', False):
+        raise SystemExit("--max-grad-norm needs the fused trainer: --eager runs torch.optim with only the rate set")
 
 
 def check_lr_schedule(args: argparse.Namespace):

@@ -8,7 +8,7 @@
 // Decoupled weight decay (the *_decay entries, include/ib_hip_decay.h; AdamW with Adam) multiplies the quads a range table
 // covers by 1 - lr_s * wd in the same pass, before the update: optim_kernel<SRC, EMA, ..., DecayArgs>.
 #include "ib_common.h"
-#include "../../include/ib_hip_decay.h"
+#include "../../include/ib_hip_gradnorm.h"
 #include <type_traits>
 #include <vector>
 
@@ -546,7 +546,225 @@ struct DecayLaunch {
         has_sc(!(kind == IB_SCHED_CONSTANT && warmup == 0)), has_dk(wd > 0.f && table_n > 0) {}
 };
 
+// ---- clipping to a global gradient norm (include/ib_hip_gradnorm.h states the arithmetic and the order of every sum) --------
+// The slot layout is a function of n alone: G slots of L elements, L a multiple of 1024 (every slot starts 16-byte aligned).
+constexpr int64_t GN_SLOT_ELEMS = 16384, GN_SLOT_ALIGN = 1024;
+constexpr int GN_MAX_SLOTS = 1024;
+inline int gn_slots(int64_t n) {
+  const int64_t G = n / GN_SLOT_ELEMS + (n % GN_SLOT_ELEMS != 0);
+  return (int)(G < 1 ? 1 : G > GN_MAX_SLOTS ? GN_MAX_SLOTS : G);
+}
+inline int64_t gn_slot_len(int64_t n, int G) {
+  const int64_t per = n / G + (n % G != 0);
+  return (per / GN_SLOT_ALIGN + (per % GN_SLOT_ALIGN != 0)) * GN_SLOT_ALIGN;
+}
+
+// the product of two fp32 values is exact in double, so a0 += gn_sq(x) rounds once whether or not it becomes an fma
+__device__ __forceinline__ double gn_sq(float x) { const double d = (double)x; return d * d; }
+
+// the workgroup's 256 thread sums: v[t] += v[t + h], h = 128, 64, ..., 1; every thread returns v[0]
+__device__ __forceinline__ double gn_tree256(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+#pragma unroll
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// one workgroup per slot, one pass: 16-byte loads, eight in flight per lane, four accumulators per thread (one per position in
+// the quad), the slot's ragged end (only the last slot has one) element by element on threads 0..2
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n, int64_t L,
+                                                         double* __restrict__ slots) {
+  __shared__ double red[256];
+  const int64_t b = (int64_t)blockIdx.x * L;
+  const int64_t len = b < n ? (n - b < L ? n - b : L) : 0;
+  const int64_t nq = len >> 2;
+  const float4* q = reinterpret_cast<const float4*>(g + b);
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  for (int64_t k = threadIdx.x; k < nq; k += 256 * 8) {
+    float4 v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (k + e * 256 < nq) v[e] = q[k + e * 256];
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (k + e * 256 < nq) { a0 += gn_sq(v[e].x); a1 += gn_sq(v[e].y); a2 += gn_sq(v[e].z); a3 += gn_sq(v[e].w); }
+  }
+  if ((int64_t)threadIdx.x < (len & 3)) {
+    const double s = gn_sq(g[b + 4 * nq + threadIdx.x]);
+    if (threadIdx.x == 0) a0 += s; else if (threadIdx.x == 1) a1 += s; else a2 += s;
+  }
+  const double t = gn_tree256((a0 + a1) + (a2 + a3), red);
+  if (threadIdx.x == 0) slots[blockIdx.x] = t;
+}
+
+// total of the G <= 1024 slots, by every workgroup that needs it: thread t adds slots t, t + 256, ... in order, then the tree
+__device__ __forceinline__ double gn_total(const double* slots, int G, double* red) {
+  double v = 0.0;
+  for (int s = threadIdx.x; s < G; s += 256) v += slots[s];
+  return gn_tree256(v, red);
+}
+
+// the header's arithmetic, every double operation rounded on its own; a NaN or infinite coef_d fails the comparison: coef = 1
+struct ClipOut { float norm, coef, gs; };
+__device__ __forceinline__ ClipOut grad_clip(double total, float gscale, float max_norm) {
+#pragma clang fp contract(off)
+  const double norm_d = sqrt(total) * fabs((double)gscale);
+  const double coef_d = (double)max_norm / (norm_d + 1e-6);
+  const float coef = coef_d < 1.0 ? (float)coef_d : 1.0f;
+  return ClipOut{(float)norm_d, coef, gscale * coef};
+}
+
+// the probe: total and {norm, coef, gs} as the clipped launch below gets them
+__global__ __launch_bounds__(256) void grad_norm_eval_kernel(const double* slots, int G, float gscale, float max_norm,
+                                                             double* __restrict__ total_out, float* __restrict__ stats) {
+  __shared__ double red[256];
+  const double total = gn_total(slots, G, red);
+  const ClipOut k = grad_clip(total, gscale, max_norm);
+  if (threadIdx.x == 0) { *total_out = total; stats[0] = k.norm; stats[1] = k.coef; stats[2] = k.gs; }
+}
+
+// The plain form of optim_kernel<false, EMA, SchedArgs, DecayArgs> (no gradient sources, no column-sum blocks, no loss scalar)
+// behind a head that puts gs = grad_scale * coef in grad_scale's place: every workgroup adds the slots itself (8 KB of L2 hits
+// at most) and evaluates grad_clip, so the coefficient needs no launch and no host read of its own.  gs is handed on as a
+// wave-uniform value (readfirstlane), as the kernel argument it replaces is.  A kernel of its own and not one more pack element of
+// optim_kernel: those instantiations stay the code they are.  The loop, the n % 4 tail and the exit tickets are optim_kernel's.
+struct ClipArgs { const double* slots; int G; float max_norm; float* stats; };
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void clipped_optim_kernel(OptArgs a, SchedArgs sc, DecayArgs D, ClipArgs c) {
+  __shared__ double red[256];
+  const ClipOut k = grad_clip(gn_total(c.slots, c.G, red), a.gscale, c.max_norm);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { c.stats[0] = k.norm; c.stats[1] = k.coef; c.stats[2] = k.gs; }
+  a.gscale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, k.gs)));
+  const int step = a.step_dev ? *(volatile int32_t*)a.step_dev + (a.ticket ? 1 : a.step) : a.step;
+  if (!(sc.kind == IB_SCHED_CONSTANT && sc.warmup == 0)) a.lr = lr_scheduled(a.lr, sc, step);   // else the host's lr, as there
+  const float f = decay_factor(a.lr, D.wd);
+  float bc1 = 1.f, bc2s = 1.f;
+  if (a.opt == IB_OPT_ADAM || a.opt == IB_OPT_ADAMAX) {
+    bc1 = (float)(1.0 - pow(0.9, (double)step));
+    bc2s = (float)sqrt(1.0 - pow(0.999, (double)step));
+  }
+  float d = 0.f;
+  if constexpr (EMA)
+    d = (float)(a.ema_warmup ? fmin((double)a.ema_decay, (1.0 + step) / (10.0 + step)) : (double)a.ema_decay);
+  const int64_t n4 = a.n / 4;
+  const bool has1 = a.s1 != nullptr, has2 = a.s2 != nullptr;
+  const int64_t gstride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gstride) {
+    float4 p = reinterpret_cast<float4*>(a.p)[i];
+    const float4 g = reinterpret_cast<const float4*>(a.g)[i];
+    float4 s1 = has1 ? reinterpret_cast<float4*>(a.s1)[i] : make_float4(0, 0, 0, 0);
+    float4 s2 = has2 ? reinterpret_cast<float4*>(a.s2)[i] : make_float4(0, 0, 0, 0);
+    p = decay4(p, decayed4(D, i * 4), f);
+    p.x = opt_update(a, p.x, g.x * a.gscale, s1.x, s2.x, bc1, bc2s);
+    p.y = opt_update(a, p.y, g.y * a.gscale, s1.y, s2.y, bc1, bc2s);
+    p.z = opt_update(a, p.z, g.z * a.gscale, s1.z, s2.z, bc1, bc2s);
+    p.w = opt_update(a, p.w, g.w * a.gscale, s1.w, s2.w, bc1, bc2s);
+    reinterpret_cast<float4*>(a.p)[i] = p;
+    if (has1) reinterpret_cast<float4*>(a.s1)[i] = s1;
+    if (has2) reinterpret_cast<float4*>(a.s2)[i] = s2;
+    if (a.shadow) {
+      bf16x4_t o;
+      o[0] = (bf16_t)p.x; o[1] = (bf16_t)p.y; o[2] = (bf16_t)p.z; o[3] = (bf16_t)p.w;
+      reinterpret_cast<bf16x4_t*>(a.shadow)[i] = o;
+    }
+    if constexpr (EMA) ema4(a, d, i, 4);
+  }
+  // tail (n % 4): it belongs to quad n / 4
+  const int64_t t0 = n4 * 4;
+  for (int64_t i = t0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gstride) {
+    float s1 = has1 ? a.s1[i] : 0.f, s2 = has2 ? a.s2[i] : 0.f;
+    float pi = a.p[i];
+    if (decayed4(D, t0)) pi = decay_mul(pi, f);
+    asm("" : "+v"(pi));
+    const float p = opt_update(a, pi, a.g[i] * a.gscale, s1, s2, bc1, bc2s);
+    a.p[i] = p;
+    if (has1) a.s1[i] = s1;
+    if (has2) a.s2[i] = s2;
+    if (a.shadow) a.shadow[i] = (bf16_t)p;
+    if constexpr (EMA) a.ema[i] = ema_update(d, a.ema[i], *(const volatile float*)(a.p + i));
+  }
+  if (a.ticket) {                        // exit tickets, two levels: as in optim_kernel
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int G = (int)gridDim.x;
+      const int nsub = G < OPT_TICKET_SUBS ? G : OPT_TICKET_SUBS;
+      const int sub = (int)blockIdx.x % OPT_TICKET_SUBS;
+      const int quota = (G - sub + OPT_TICKET_SUBS - 1) / OPT_TICKET_SUBS;
+      int32_t* tc = a.ticket + OPT_TICKET_LINE * (1 + sub);
+      if (atomicAdd(tc, 1) == quota - 1) {
+        *tc = 0;
+        if (atomicAdd(a.ticket, 1) == nsub - 1) {
+          *a.step_dev = step;
+          *a.ticket = 0;
+        }
+      }
+    }
+  }
+}
+
+// the entries of ib_hip_gradnorm.h: every pointer present and 16-byte aligned, max_norm > 0 (NaN fails the comparison)
+bool gradnorm_args_ok(std::initializer_list<const void*> ptrs, int64_t n, float max_norm) {
+  for (const void* q : ptrs)
+    if (!q) return false;
+  return ib_al16(ptrs) && n > 0 && max_norm > 0.f;
+}
+
 }  // namespace
+
+extern "C" size_t ib_grad_sumsq_workspace(int64_t n) { return n <= 0 ? 0 : (size_t)gn_slots(n) * sizeof(double); }
+
+extern "C" int ib_grad_sumsq(const float* g, int64_t n, double* slots, ib_stream_t stream) {
+  if (!gradnorm_args_ok({g, slots}, n, 1.f)) return IB_E_ARG;
+  const int G = gn_slots(n);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(G), dim3(256), 0, ib_s(stream), g, n, gn_slot_len(n, G), slots);
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+extern "C" int ib_grad_norm_eval(const double* slots, int64_t n, float grad_scale, float max_norm, double* total_out,
+                                 float* stats3, ib_stream_t stream) {
+  if (!gradnorm_args_ok({slots, total_out, stats3}, n, max_norm)) return IB_E_ARG;
+  hipLaunchKernelGGL(grad_norm_eval_kernel, dim3(1), dim3(256), 0, ib_s(stream), slots, gn_slots(n), grad_scale, max_norm,
+                     total_out, stats3);
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
+
+extern "C" int ib_optim_step_gradnorm(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
+                                      float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16,
+                                      float* ema, float ema_decay, int ema_warmup, int sched_kind, int32_t sched_warmup,
+                                      int32_t sched_total, float sched_min_ratio, float weight_decay, const void* table_dev,
+                                      int table_n, int64_t origin, const double* slots, int64_t sumsq_n, float max_norm,
+                                      float* stats3, ib_stream_t stream) {
+  if (!sched_args_ok(sched_kind, sched_warmup, sched_total, sched_min_ratio)) return IB_E_ARG;
+  if (ema && !ema_args_ok(ema, ema_decay)) return IB_E_ARG;
+  if (!decay_args_ok(weight_decay, table_dev, table_n, origin)) return IB_E_ARG;
+  if (!gradnorm_args_ok({slots, stats3}, sumsq_n, max_norm)) return IB_E_ARG;
+  if (!p || !g || n <= 0 || opt < IB_OPT_SGD || opt > IB_OPT_ADAMAX) return IB_E_ARG;       // as optim_plain
+  if (ticket && !step_dev) return IB_E_ARG;
+  const bool need1 = opt != IB_OPT_SGD;
+  const bool need2 = (opt == IB_OPT_ADAM || opt == IB_OPT_ADADELTA || opt == IB_OPT_ADAMAX);
+  if ((need1 && !s1) || (need2 && !s2)) return IB_E_ARG;
+  if (!ib_al16({p, g, s1, s2, ema}) || !ib_aligned(shadow_bf16, 8)) return IB_E_ARG;
+  OptArgs a{p, g, need1 ? s1 : nullptr, need2 ? s2 : nullptr, reinterpret_cast<bf16_t*>(shadow_bf16),
+            n, lr, grad_scale, step, step_dev, ticket, opt, ema, ema_decay, ema_warmup};
+  const SchedArgs sc{sched_kind, sched_warmup, sched_total, sched_min_ratio};
+  // weight_decay = 0 decays nothing through an empty table: decay_factor(lr, 0) = 1 would be a multiply by one all the same
+  const DecayArgs dk{weight_decay, weight_decay > 0.f ? table_n : 0, reinterpret_cast<const int64_t*>(table_dev), origin};
+  const ClipArgs c{slots, gn_slots(sumsq_n), max_norm, stats3};
+  const dim3 grid(ib_grid_1d(n / 4 + 1, 256));
+  if (ema)
+    hipLaunchKernelGGL((clipped_optim_kernel<true>), grid, dim3(256), 0, ib_s(stream), a, sc, dk, c);
+  else
+    hipLaunchKernelGGL((clipped_optim_kernel<false>), grid, dim3(256), 0, ib_s(stream), a, sc, dk, c);
+  IB_CHECK_LAUNCH();
+  return IB_OK;
+}
 
 extern "C" int ib_optim_ticket_words(void) { return OPT_TICKET_LINE * (1 + OPT_TICKET_SUBS); }
 

@@ -36,6 +36,7 @@ from .loss.RegressionLossEvaluator import component_weights
 from .lr_schedule import LrSchedule, active as active_schedule
 from .module import HipModule, flat_layout
 from .plans import ParamSource
+from .grad_norm import check_max_grad_norm
 from .weight_decay import check_weight_decay, decay_ranges, decayed_names
 
 
@@ -273,7 +274,7 @@ class HipTrainer:
     def __init__(self, model: HipModule, task: str, opt_type: str = "rmsprop", lr: float = 1e-4, args=None,
                  group=None, bucket_mb: float = 13.0, use_graph: bool = True, overlap_comm: Optional[bool] = None,
                  ema_decay: float = 0.0, ema_warmup: bool = True, cond_cols: int = 0, cond_drop: float = 0.0,
-                 lr_schedule=None, weight_decay: float = 0.0, decay_filter=None):
+                 lr_schedule=None, weight_decay: float = 0.0, decay_filter=None, max_grad_norm: float = 0.0):
         if task not in ("diffusion", "regression"):
             raise ValueError(task)
         if int(cond_cols) < 0 or (cond_cols and task != "diffusion"):
@@ -292,6 +293,7 @@ class HipTrainer:
         if decay_filter is not None and not callable(decay_filter):
             raise ValueError(f"decay_filter must be None or a callable (name, shape) -> bool, got {type(decay_filter).__name__}")
         self.weight_decay = check_weight_decay(weight_decay)
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
         self.model, self.task, self.opt_type, self.lr = model, task, opt_type, lr
         # diffusion: the first cond_cols columns of every frame row are conditioning -- they reach the denoiser clean at every
         # noise level and are not scored (csrc/diffusion.hip q_sample_cond_kernel, csrc/loss.hip mse_partial_cond_kernel).
@@ -400,7 +402,15 @@ class HipTrainer:
         # head of the step).  A plan that launches a bucket the moment its last gradient is reported may still have the
         # dgrad through those very weights ahead of it: updating them there is a race (caught by
         # tests/test_ddp_numerics_gpu.py on the MLP denoiser with forced overlap).
-        self.bucket_opt = bool(self.ddp and self.overlap_comm and self._flush_mode and not TU.no_bucket_opt)
+        # Clipping to a global gradient norm (grad_norm.py, include/ib_hip_gradnorm.h): the coefficient is a function of the WHOLE
+        # gradient, so no parameter may be updated before the last gradient (under data parallelism: the last all-reduce) is in
+        # self.grad.  The step then takes the materialised form -- no gradient sources, no per-layer and no per-bucket
+        # optimizer launches -- and ends in ib_grad_sumsq + ONE clipped launch over the whole flat buffer.  0: off, no buffer,
+        # no launch, the step as ever.  inf: the same two launches, coefficient 1 (measure only).
+        self.clip = self.max_grad_norm > 0
+        self.norm_slots = torch.zeros(hip.grad_sumsq_slots(flat.numel()), dtype=torch.float64, device=dev) if self.clip else None
+        self.norm_stats = torch.zeros(4, dtype=torch.float32, device=dev) if self.clip else None    # {norm, coef, gs, -}
+        self.bucket_opt = bool(self.ddp and self.overlap_comm and self._flush_mode and not TU.no_bucket_opt and not self.clip)
         self._br_opt = Branch(dev, enabled=self.bucket_opt, name="bucket_opt")
         self._early_done: List[Tuple[int, int]] = []
         # device-side batch draw (step_drawn): Philox key = torch's seed (torch.manual_seed(s) selects the noise as it would
@@ -478,6 +488,11 @@ class HipTrainer:
         m = self.model
         return m.output_frames_for(frames) if hasattr(m, "output_frames_for") else m.num_output_frames
 
+    def _fuse_reduce(self) -> bool:
+        """may the optimizer sum a gradient's partial sums itself (plan.fuse_reduce_into_optimizer)?  Not where the reduced
+        gradient is needed in memory first: for an all-reduce, or for the norm the clip coefficient comes from."""
+        return not self.ddp and not TU.no_opt_fuse and not self.clip
+
     # ---- the launch sequence ---------------------------------------------------------------------
     def _launches(self, st: Dict[str, torch.Tensor], cut=None):
         m, plan, dt = self.model, self.plan, self.model.compute_dtype
@@ -502,7 +517,7 @@ class HipTrainer:
                                    num_train_steps=m.num_train_steps, table=None if mc is None else mc.table,
                                    idx=st.get("widx"), x0=x0 if mc is not None else None)
             if hasattr(plan, "chain_ok") and plan.chain_ok(D, C):
-                plan.fuse_reduce_into_optimizer = not self.ddp and not TU.no_opt_fuse
+                plan.fuse_reduce_into_optimizer = self._fuse_reduce()
                 # MLP denoiser, bf16: q_sample + forward + loss + the dgrad chain are ONE launch (csrc/chain.hip)
                 if self._slots is None:
                     self._slots = torch.zeros(4, dtype=torch.int64, device=self.device)
@@ -513,7 +528,7 @@ class HipTrainer:
             # activations that are D (= 300) wide live in buffers with a 16-byte-aligned row pitch (304): the GEMM
             # operand pieces are then aligned 16-byte loads (the unpadded rows were 8-byte aligned: +11 us per wgrad)
             if hasattr(plan, "fuse_reduce_into_optimizer"):
-                plan.fuse_reduce_into_optimizer = not self.ddp and not TU.no_opt_fuse
+                plan.fuse_reduce_into_optimizer = self._fuse_reduce()
             if hasattr(plan, "early_optimizer"):
                 # one GPU: a layer's parameters are updated as soon as its gradient is complete, on the layer's side stream
                 # beside the backward of the layers below, instead of in one launch at the end of the step
@@ -567,7 +582,7 @@ class HipTrainer:
             else:
                 hip.concat_keys([st[f"in{i}"] for i in range(len(INPUT_KEY_ORDER))], x)
             if hasattr(plan, "fuse_reduce_into_optimizer"):
-                plan.fuse_reduce_into_optimizer = not self.ddp and not TU.no_opt_fuse
+                plan.fuse_reduce_into_optimizer = self._fuse_reduce()
             if hasattr(m, "output_frames_for"):
                 # Groundlink: [B, F', 30] with the four outputs interleaved per frame; the dropout masks are keyed on
                 # the device-resident step counter, so a replayed graph draws fresh masks every step
@@ -601,6 +616,19 @@ class HipTrainer:
             else:
                 self._br_opt.join()                  # the per-bucket optimizer launches (each waited for its own all-reduce)
                 self.buckets.finish()
+        if self.clip:
+            # the whole (all-reduced) gradient is in self.grad: its sum of squares, then the one self-counting launch over the
+            # whole flat buffer, which adds the slots, clips and updates (captured with the rest of the step: no host read)
+            if getattr(self.plan, "pending_sources", None) is not None or self._early_done:
+                raise hip.HipError("max_grad_norm: the plan left gradient sources or early optimizer launches behind")
+            hip.grad_sumsq(self.grad, self.norm_slots)
+            sl = lambda t: t
+            hip.optim_step(self.opt_type, self.flat, self.grad, self.s1, self.s2, self.lr, step=0, step_dev=self.step_dev,
+                           ticket=self.ticket, grad_scale=1.0 / self.world,
+                           shadow=m._shadow if dt == torch.bfloat16 else None, max_grad_norm=self.max_grad_norm,
+                           norm_slots=self.norm_slots, norm_stats=self.norm_stats, **self._ema_args(sl),
+                           **self._sched_args(), **self._decay_args(0))
+            return
         # self-counting optimizer launch: uses *step_dev + 1 and publishes it itself (no separate counter launch)
         src = getattr(self.plan, "pending_sources", None)
         done, self._early_done = list(self._early_done), []
@@ -1053,6 +1081,19 @@ class HipTrainer:
         """host readback of the last step's loss (synchronises)"""
         return float(self.result[0].cpu())
 
+    def _norm_stat(self, k: int) -> float:
+        if not self.clip:
+            raise hip.HipError("no gradient norm is taken: this trainer was built with max_grad_norm = 0")
+        return float(self.norm_stats[k].cpu())
+
+    def grad_norm(self) -> float:
+        """host readback of the last step's global gradient norm, 1 / world folded in, before clipping (synchronises)"""
+        return self._norm_stat(0)
+
+    def clip_coef(self) -> float:
+        """host readback of the coefficient the last step's gradient was multiplied by, 1 = not clipped (synchronises)"""
+        return self._norm_stat(1)
+
     # ---- checkpoint payload (grammar of train.py:272-278) ------------------------------------------
     # torch.optim state names behind the flat (s1, s2) buffers (csrc/optim.hip: the order of its update formulas)
     TORCH_STATE_KEYS = {"sgd": (), "adam": ("exp_avg", "exp_avg_sq"), "rmsprop": ("square_avg",), "adagrad": ("sum",),
@@ -1060,11 +1101,13 @@ class HipTrainer:
 
     def optimizer_state_dict(self) -> Dict:
         """"lr" is the BASE rate; "lr_schedule" the schedule's four fields, or None without one (a constant schedule
-        without warmup counts as none); "weight_decay" the fp32 decay and "decayed" the names it applies to (none at 0)"""
+        without warmup counts as none); "weight_decay" the fp32 decay and "decayed" the names it applies to (none at 0);
+        "max_grad_norm" the fp32 clipping norm (0: off, inf: measured only)"""
         sched = active_schedule(self.lr_schedule)
         return {"opt_type": self.opt_type, "lr": self.lr, "step": self.steps_done,
                 "lr_schedule": None if sched is None else sched.fields(),
                 "weight_decay": self.weight_decay, "decayed": list(self.decayed) if self.weight_decay > 0 else [],
+                "max_grad_norm": self.max_grad_norm,
                 "layout": {k: list(v) for k, v in self.layout.items()},
                 "s1": None if self.s1 is None else self.s1.detach().cpu(),
                 "s2": None if self.s2 is None else self.s2.detach().cpu()}
@@ -1101,6 +1144,10 @@ class HipTrainer:
             what = "" if theirs_wd != self.weight_decay else " over other parameters"
             raise hip.HipError(f"the checkpoint's weight decay ({theirs_wd:g}{what}) differs from this trainer's "
                                f"({self.weight_decay:g})")
+        theirs_mgn = float(sd.get("max_grad_norm", 0.0))   # a payload without the key is an older checkpoint: no clipping
+        if theirs_mgn != self.max_grad_norm:
+            raise hip.HipError(f"the checkpoint's gradient-norm clip ({theirs_mgn:g}) differs from this trainer's "
+                               f"({self.max_grad_norm:g})")
         if self.s1 is not None:
             self.s1.copy_(sd["s1"])
         if self.s2 is not None:

@@ -18,7 +18,8 @@ sampling step and the per-column range of a window table (csrc/clip.hip) in an e
 ``include/ib_hip_standardize.h`` (``_STANDARDIZE_SIGS``), the learning-rate schedule of the fused optimizer (csrc/optim.hip)
 in a tenth, ``include/ib_hip_sched.h`` (``_SCHED_SIGS``), its decoupled weight decay in an eleventh,
 ``include/ib_hip_decay.h`` (``_DECAY_SIGS``), the slice rule of the whole-layer kernels' image sweep (csrc/image_sweep.h) in a
-twelfth, ``include/ib_hip_sweep.h`` (``_SWEEP_SIGS``); a name may be declared once in the twelve.
+twelfth, ``include/ib_hip_sweep.h`` (``_SWEEP_SIGS``), the optimizer's clipping to a global gradient norm in a thirteenth,
+``include/ib_hip_gradnorm.h`` (``_GRADNORM_SIGS``); a name may be declared once in the thirteen.
 """
 from __future__ import annotations
 
@@ -47,6 +48,7 @@ STANDARDIZE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hi
 SCHED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sched.h")
 DECAY_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_decay.h")
 SWEEP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sweep.h")
+GRADNORM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_gradnorm.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -139,6 +141,11 @@ _SWEEP_SIGS = _parse_header(_read_header(SWEEP_HEADER_PATH))                    
 _ENTRIES = {**_LOADED, **_SWEEP_SIGS}
 if len(_ENTRIES) != len(_LOADED) + len(_SWEEP_SIGS):
     raise HipError(f"declared in two headers: {sorted(n for n in _SWEEP_SIGS if n in _LOADED)}")
+# the thirteenth header likewise: _ENTRIES stays the twelve headers' as their tests pin it; _sig() and lib() go through _EXPORTS
+_GRADNORM_SIGS = _parse_header(_read_header(GRADNORM_HEADER_PATH))                  # the optimizer's gradient clip, off by default
+_EXPORTS = {**_ENTRIES, **_GRADNORM_SIGS}
+if len(_EXPORTS) != len(_ENTRIES) + len(_GRADNORM_SIGS):
+    raise HipError(f"declared in two headers: {sorted(n for n in _GRADNORM_SIGS if n in _ENTRIES)}")
 _kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_STITCH_KMAX[ \t]+(\d+)[ \t]*$", _read_header(STITCH_HEADER_PATH), flags=re.M)
 if _kmax is None:
     raise HipError(f"{STITCH_HEADER_PATH} does not define IB_STITCH_KMAX")
@@ -207,9 +214,14 @@ def sweep_decls() -> List[str]:
     return sorted(_SWEEP_SIGS)
 
 
+def gradnorm_decls() -> List[str]:
+    """Every function include/ib_hip_gradnorm.h declares"""
+    return sorted(_GRADNORM_SIGS)
+
+
 def _sig(name: str):
     """(restype, argtypes) of an entry point of any header"""
-    return _ENTRIES[name]
+    return _EXPORTS[name]
 
 
 # pure host queries: no launch, no stream
@@ -258,7 +270,7 @@ class _DryRunLib:
                 rd = lambda p, ct: ctypes.cast(p, ctypes.POINTER(ct))
                 st, ln, kd = rd(a[13], ctypes.c_int64), rd(a[14], ctypes.c_int64), rd(a[15], ctypes.c_int32)
                 self.ema_ranges.append((a[25], int(a[5]), [(st[j], ln[j]) for j in range(m) if kd[j] == 3]))
-            elif name in ("ib_optim_step_sched", "ib_optim_step_decay") and a[12] is not None:
+            elif name in ("ib_optim_step_sched", "ib_optim_step_decay", "ib_optim_step_gradnorm") and a[12] is not None:
                 self.ema_ranges.append((a[12], int(a[5]), []))
             elif name in ("ib_optim_step_sources_sched", "ib_optim_step_sources_decay") and a[25] is not None:
                 m = int(a[12])
@@ -491,7 +503,7 @@ def lib():
             raise HipError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C inferbiomechanics_amd/csrc` (hipcc --offload-arch=gfx950). There is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _ENTRIES.items():
+        for name, (res, args) in _EXPORTS.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -1420,7 +1432,7 @@ def optim_ticket_words() -> int:
 
 def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=1.0, shadow=None, ticket=None,
                sources=None, ema=None, ema_decay=0.0, ema_warmup=True, lr_schedule=None, weight_decay=0.0, decay_table=None,
-               decay_origin=0):
+               decay_origin=0, max_grad_norm=0.0, norm_slots=None, norm_stats=None):
     """step: the step number of the bias corrections; with `step_dev` the kernel uses `*step_dev + step`, so the default is
     0 there (the device counter alone) and 1 without a device counter.
     sources = (items, part, rows, segs): the gradient of some ranges of g is still partial sums -- items =
@@ -1437,7 +1449,26 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
     weight_decay: 0 takes the entries above, as ever.  > 0: the *_decay entries (include/ib_hip_decay.h) -- every quad of p
     whose global position decay_origin + 4 q lies in a range of decay_table (a DecayTable, built once over the whole flat
     buffer; decay_origin is the offset of p[0] in it) is multiplied by weight_decay.decay_factor(rate of this step,
-    weight_decay) before its update; ranges named as done (kind 3) are left alone."""
+    weight_decay) before its update; ranges named as done (kind 3) are left alone.
+    max_grad_norm: 0 takes the entries above, as ever.  > 0 (inf: measure only): ib_optim_step_gradnorm
+    (include/ib_hip_gradnorm.h) -- norm_slots holds what grad_sumsq(whole gradient, norm_slots) left, the kernel adds the
+    slots, puts grad_norm.clip_coef(total, grad_scale, max_grad_norm)'s gs in grad_scale's place and writes {norm, coef, gs}
+    to norm_stats (3 fp32).  The plain form only: refused together with sources."""
+    clip = ()
+    if float(max_grad_norm) != 0.0:
+        if not float(max_grad_norm) > 0.0:                     # negative or NaN
+            raise HipError(f"max_grad_norm must be >= 0, got {max_grad_norm}")
+        if sources is not None:
+            raise HipError("max_grad_norm needs the materialised gradient: it cannot be combined with sources")
+        if norm_slots is None or norm_stats is None:
+            raise HipError("max_grad_norm needs norm_slots (as grad_sumsq filled them) and norm_stats (3 fp32)")
+        _req(norm_slots, "norm_slots", torch.float64, 1)
+        _req(norm_stats, "norm_stats", torch.float32, 1)
+        if not norm_slots.is_contiguous() or not norm_stats.is_contiguous() or norm_stats.numel() < 3:
+            raise HipError("norm_slots and norm_stats must be contiguous, norm_stats of 3 elements or more")
+        if norm_slots.device != p.device or norm_stats.device != p.device:
+            raise HipError("norm_slots / norm_stats live on another device than p")
+        clip = (_ptr(norm_slots), _sumsq_n(norm_slots), float(max_grad_norm), _ptr(norm_stats))
     decay = ()
     if float(weight_decay) != 0.0:
         if not float(weight_decay) > 0.0:                      # negative or NaN
@@ -1542,7 +1573,10 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
         return
     args = (OPT[opt], _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), n, float(lr), float(grad_scale), int(step), _ptr(step_dev),
             _ptr(ticket), _ptr(shadow))
-    if decay:
+    if clip:
+        _check(lib().ib_optim_step_gradnorm(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), *(sched or _NO_SCHED),
+                                            *(decay or _NO_DECAY), *clip, stream_ptr()), "ib_optim_step_gradnorm")
+    elif decay:
         _check(lib().ib_optim_step_decay(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), *(sched or _NO_SCHED),
                                          *decay, stream_ptr()), "ib_optim_step_decay")
     elif sched:
@@ -1556,6 +1590,52 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
 
 
 _NO_SCHED = (0, 0, 0, 0.0)      # IB_SCHED_CONSTANT without warmup: the *_decay entries then run at the host's lr
+_NO_DECAY = (0.0, None, 0, 0)   # ib_optim_step_gradnorm without weight decay: an empty table
+
+
+def grad_sumsq_slots(n: int) -> int:
+    """G(n): how many float64 slots ib_grad_sumsq fills for a gradient of n elements (ib_grad_sumsq_workspace / 8)"""
+    return int(lib().ib_grad_sumsq_workspace(int(n))) // 8
+
+
+_SUMSQ_SLOT_ELEMS = 16384       # include/ib_hip_gradnorm.h: G(n) = clamp(ceil(n / 16384), 1, 1024)
+
+
+def _sumsq_n(slots) -> int:
+    """the `sumsq_n` a consumer of a slot buffer passes: the entries use it for the slot count alone, and G(16384 G) = G"""
+    return slots.numel() * _SUMSQ_SLOT_ELEMS
+
+
+def grad_sumsq(g, slots=None):
+    """slots[s] = the sum of squares of slot s of the flat fp32 gradient g, in float64 (ib_grad_sumsq: one streaming launch,
+    the order of include/ib_hip_gradnorm.h).  slots: a float64 vector of grad_sumsq_slots(g.numel()) elements, made when None.
+    Returns slots."""
+    _req(g, "g", torch.float32, 1)
+    if g.numel() == 0 or not g.is_contiguous():
+        raise HipError("grad_sumsq: a non-empty contiguous fp32 vector required")
+    G = grad_sumsq_slots(g.numel())
+    if slots is None:
+        slots = torch.zeros(G, dtype=torch.float64, device=g.device)
+    _req(slots, "slots", torch.float64, 1)
+    if slots.numel() != G or not slots.is_contiguous() or slots.device != g.device:
+        raise HipError(f"grad_sumsq: slots must be a contiguous float64 vector of {G} elements on the device of g")
+    _check(lib().ib_grad_sumsq(_ptr(g), g.numel(), _ptr(slots), stream_ptr()), "ib_grad_sumsq")
+    return slots
+
+
+def grad_norm_eval(slots, grad_scale: float = 1.0, max_norm: float = float("inf")):
+    """the probe (ib_grad_norm_eval): adds the slots as the clipped optimizer launch does and evaluates its clip arithmetic.
+    Returns (total, stats): a float64 and an fp32 vector {norm, coef, gs} on the device of slots."""
+    _req(slots, "slots", torch.float64, 1)
+    if slots.numel() == 0 or not slots.is_contiguous():
+        raise HipError("grad_norm_eval: a non-empty contiguous float64 vector of slots required")
+    if not float(max_norm) > 0.0:
+        raise HipError(f"max_norm must be > 0, got {max_norm}")
+    total = torch.zeros(2, dtype=torch.float64, device=slots.device)      # 16 bytes: the entry wants aligned pointers
+    stats = torch.zeros(4, dtype=torch.float32, device=slots.device)
+    _check(lib().ib_grad_norm_eval(_ptr(slots), _sumsq_n(slots), float(grad_scale), float(max_norm), _ptr(total), _ptr(stats),
+                                   stream_ptr()), "ib_grad_norm_eval")
+    return total[:1], stats[:3]
 
 
 class DecayTable:
