@@ -112,6 +112,90 @@ __device__ __forceinline__ bool decayed4(const DecayArgs& D, int64_t idx) {
   return false;
 }
 
+// ---- clipping to a global gradient norm (include/ib_hip_gradnorm.h states the arithmetic and the order of every sum) --------
+// The slot layout is a function of n alone: G slots of L elements, L a multiple of 1024 (every slot starts 16-byte aligned).
+constexpr int64_t GN_SLOT_ELEMS = 16384, GN_SLOT_ALIGN = 1024;
+constexpr int GN_MAX_SLOTS = 1024;
+inline int gn_slots(int64_t n) {
+  const int64_t G = n / GN_SLOT_ELEMS + (n % GN_SLOT_ELEMS != 0);
+  return (int)(G < 1 ? 1 : G > GN_MAX_SLOTS ? GN_MAX_SLOTS : G);
+}
+inline int64_t gn_slot_len(int64_t n, int G) {
+  const int64_t per = n / G + (n % G != 0);
+  return (per / GN_SLOT_ALIGN + (per % GN_SLOT_ALIGN != 0)) * GN_SLOT_ALIGN;
+}
+
+// the product of two fp32 values is exact in double, so a0 += gn_sq(x) rounds once whether or not it becomes an fma
+__device__ __forceinline__ double gn_sq(float x) { const double d = (double)x; return d * d; }
+
+// the workgroup's 256 thread sums: v[t] += v[t + h], h = 128, 64, ..., 1; every thread returns v[0]
+__device__ __forceinline__ double gn_tree256(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+#pragma unroll
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// one workgroup per slot, one pass: 16-byte loads, eight in flight per lane, four accumulators per thread (one per position in
+// the quad), the slot's ragged end (only the last slot has one) element by element on threads 0..2
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n, int64_t L,
+                                                         double* __restrict__ slots) {
+  __shared__ double red[256];
+  const int64_t b = (int64_t)blockIdx.x * L;
+  const int64_t len = b < n ? (n - b < L ? n - b : L) : 0;
+  const int64_t nq = len >> 2;
+  const float4* q = reinterpret_cast<const float4*>(g + b);
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  for (int64_t k = threadIdx.x; k < nq; k += 256 * 8) {
+    float4 v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (k + e * 256 < nq) v[e] = q[k + e * 256];
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (k + e * 256 < nq) { a0 += gn_sq(v[e].x); a1 += gn_sq(v[e].y); a2 += gn_sq(v[e].z); a3 += gn_sq(v[e].w); }
+  }
+  if ((int64_t)threadIdx.x < (len & 3)) {
+    const double s = gn_sq(g[b + 4 * nq + threadIdx.x]);
+    if (threadIdx.x == 0) a0 += s; else if (threadIdx.x == 1) a1 += s; else a2 += s;
+  }
+  const double t = gn_tree256((a0 + a1) + (a2 + a3), red);
+  if (threadIdx.x == 0) slots[blockIdx.x] = t;
+}
+
+// total of the G <= 1024 slots, by every workgroup that needs it: thread t adds slots t, t + 256, ... in order, then the tree
+__device__ __forceinline__ double gn_total(const double* slots, int G, double* red) {
+  double v = 0.0;
+  for (int s = threadIdx.x; s < G; s += 256) v += slots[s];
+  return gn_tree256(v, red);
+}
+
+// the header's arithmetic, every double operation rounded on its own; a NaN or infinite coef_d fails the comparison: coef = 1
+struct ClipOut { float norm, coef, gs; };
+__device__ __forceinline__ ClipOut grad_clip(double total, float gscale, float max_norm) {
+#pragma clang fp contract(off)
+  const double norm_d = sqrt(total) * fabs((double)gscale);
+  const double coef_d = (double)max_norm / (norm_d + 1e-6);
+  const float coef = coef_d < 1.0 ? (float)coef_d : 1.0f;
+  return ClipOut{(float)norm_d, coef, gscale * coef};
+}
+
+// the probe: total and {norm, coef, gs} as the clipped launch below gets them
+__global__ __launch_bounds__(256) void grad_norm_eval_kernel(const double* slots, int G, float gscale, float max_norm,
+                                                             double* __restrict__ total_out, float* __restrict__ stats) {
+  __shared__ double red[256];
+  const double total = gn_total(slots, G, red);
+  const ClipOut k = grad_clip(total, gscale, max_norm);
+  if (threadIdx.x == 0) { *total_out = total; stats[0] = k.norm; stats[1] = k.coef; stats[2] = k.gs; }
+}
+
+// the clipped launch's own arguments: the slots ib_grad_sumsq left, their count, the bound, where {norm, coef, gs} go
+struct ClipArgs { const double* slots; int G; float max_norm; float* stats; };
+
 // the optional trailing arguments of optim_kernel: is T among them, and which one is it
 template <typename T, typename... P> constexpr bool pack_has = (std::is_same<T, P>::value || ...);
 template <typename T, typename F, typename... R>
@@ -252,12 +336,28 @@ __device__ __forceinline__ void apply4(const OptArgs& a, int64_t i, float4 g, fl
 // The pack's second optional element, behind SchedArgs where there is one, is a DecayArgs: every quad this launch updates
 // whose global position lies in a range of D.table is multiplied by f = decay_factor(lr_s, wd) before its update (kind-3
 // ranges are skipped before that, as before any other work).  Without it: the functions above, instruction for instruction.
+// The pack's third optional element, only behind both others and only with SRC = false (the clip needs the materialised
+// gradient), is a ClipArgs: a head in front of everything else puts gs = grad_scale * coef in grad_scale's place.  Every
+// workgroup adds the slots itself (8 KB of L2 hits at most) and evaluates grad_clip, so the coefficient needs no launch and
+// no host read of its own; block 0 writes {norm, coef, gs}; gs is handed on as a wave-uniform value (readfirstlane), as the
+// kernel argument it replaces is.  This form always carries a SchedArgs, so it tests at run time for the constant schedule
+// without warmup, where the rate is the host's lr as in the forms without a SchedArgs; an empty table decays nothing.
 template <bool SRC, bool EMA, typename... Sched>
 __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int main_blocks, Sched... sc) {
   static_assert(std::is_same<void(Sched...), void()>::value || std::is_same<void(Sched...), void(SchedArgs)>::value ||
                 std::is_same<void(Sched...), void(DecayArgs)>::value ||
-                std::is_same<void(Sched...), void(SchedArgs, DecayArgs)>::value, "(), (SchedArgs), (DecayArgs) or both in this order");
+                std::is_same<void(Sched...), void(SchedArgs, DecayArgs)>::value ||
+                (!SRC && std::is_same<void(Sched...), void(SchedArgs, DecayArgs, ClipArgs)>::value),
+                "(), (SchedArgs), (DecayArgs), both in this order, or both and a ClipArgs without sources");
   constexpr bool SCHED = pack_has<SchedArgs, Sched...>, DECAY = pack_has<DecayArgs, Sched...>;
+  constexpr bool CLIP = pack_has<ClipArgs, Sched...>;
+  if constexpr (CLIP) {
+    __shared__ double red[256];
+    const ClipArgs& c = pack_get<ClipArgs>(sc...);
+    const ClipOut k = grad_clip(gn_total(c.slots, c.G, red), a.gscale, c.max_norm);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { c.stats[0] = k.norm; c.stats[1] = k.coef; c.stats[2] = k.gs; }
+    a.gscale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, k.gs)));
+  }
   // self-counting mode (ticket != NULL): *step_dev holds the number of COMPLETED steps; every block reads it on
   // entry, and the block that draws the last exit ticket publishes step and resets the ticket -- it exits after
   // every other block has entered (and therefore read the old value), so no block can see the new count.
@@ -265,7 +365,10 @@ __global__ __launch_bounds__(256) void optim_kernel(OptArgs a, OptSources S, int
   // the buffer (a layer's range, issued as soon as its gradient is complete) takes part in a self-counting step whose
   // last launch publishes.
   const int step = a.step_dev ? *(volatile int32_t*)a.step_dev + (a.ticket ? 1 : a.step) : a.step;
-  if constexpr (SCHED) a.lr = lr_scheduled(a.lr, pack_get<SchedArgs>(sc...), step);
+  if constexpr (SCHED) {
+    const SchedArgs& q = pack_get<SchedArgs>(sc...);
+    if (!CLIP || !(q.kind == IB_SCHED_CONSTANT && q.warmup == 0)) a.lr = lr_scheduled(a.lr, q, step);
+  }
   DecayArgs D{};
   float f = 1.f;                                 // the decay's factor, from the rate this launch uses
   if constexpr (DECAY) { D = pack_get<DecayArgs>(sc...); f = decay_factor(a.lr, D.wd); }
@@ -419,62 +522,107 @@ __global__ __launch_bounds__(256) void lr_schedule_eval_kernel(float lr, SchedAr
     out[i] = lr_scheduled(lr, sc, steps[i]);
 }
 
-// the decayed launches (the *_decay entries): optim_kernel<SRC, EMA, DecayArgs> or <SRC, EMA, SchedArgs, DecayArgs>
-template <bool SRC>
-void optim_launch_decay(dim3 grid, ib_stream_t stream, const OptArgs& a, const OptSources& S, int main_blocks,
-                        const SchedArgs* sc, const DecayArgs& dk) {
-  if (sc && a.ema)
-    hipLaunchKernelGGL((optim_kernel<SRC, true, SchedArgs, DecayArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, *sc, dk);
-  else if (sc)
-    hipLaunchKernelGGL((optim_kernel<SRC, false, SchedArgs, DecayArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, *sc, dk);
-  else if (a.ema)
-    hipLaunchKernelGGL((optim_kernel<SRC, true, DecayArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, dk);
-  else
-    hipLaunchKernelGGL((optim_kernel<SRC, false, DecayArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, dk);
+// the *_ema entries: a 16-byte aligned EMA buffer (like p) and a decay in [0, 1] (NaN fails the comparisons too)
+bool ema_args_ok(const float* ema, float ema_decay) {
+  return ema && ib_aligned(ema, 16) && ema_decay >= 0.f && ema_decay <= 1.f;
 }
 
-// the two launchers behind the C entries: ema == NULL launches optim_kernel<SRC, false>, the kernel without the EMA;
-// sc != NULL launches optim_kernel<SRC, EMA, SchedArgs> in their place (the *_sched entries); dk != NULL the decayed ones
-int optim_plain(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr, float grad_scale, int32_t step,
-                int32_t* step_dev, int32_t* ticket, void* shadow_bf16, float* ema, float ema_decay, int ema_warmup,
-                const SchedArgs* sc, ib_stream_t stream, const DecayArgs* dk = nullptr) {
-  if (!p || !g || n <= 0 || opt < IB_OPT_SGD || opt > IB_OPT_ADAMAX) return IB_E_ARG;
-  if (ticket && !step_dev) return IB_E_ARG;
-  const bool need1 = opt != IB_OPT_SGD;
-  const bool need2 = (opt == IB_OPT_ADAM || opt == IB_OPT_ADADELTA || opt == IB_OPT_ADAMAX);
-  if ((need1 && !s1) || (need2 && !s2)) return IB_E_ARG;
-  if (!ib_al16({p, g, s1, s2, ema}) || !ib_aligned(shadow_bf16, 8)) return IB_E_ARG;
-  OptArgs a{p, g, need1 ? s1 : nullptr, need2 ? s2 : nullptr, reinterpret_cast<bf16_t*>(shadow_bf16),
-            n, lr, grad_scale, step, step_dev, ticket, opt, ema, ema_decay, ema_warmup};
-  const dim3 grid(ib_grid_1d(n / 4 + 1, 256));
-  if (dk)
-    optim_launch_decay<false>(grid, stream, a, OptSources{}, 0, sc, *dk);
-  else if (sc && ema)
-    hipLaunchKernelGGL((optim_kernel<false, true, SchedArgs>), grid, dim3(256), 0, ib_s(stream), a, OptSources{}, 0, *sc);
-  else if (sc)
-    hipLaunchKernelGGL((optim_kernel<false, false, SchedArgs>), grid, dim3(256), 0, ib_s(stream), a, OptSources{}, 0, *sc);
-  else if (ema)
-    hipLaunchKernelGGL((optim_kernel<false, true>), grid, dim3(256), 0, ib_s(stream), a, OptSources{}, 0);
+// the *_sched entries and the probe: kind 0..2, warmup >= 0, a decay needs total > warmup, min_ratio in [0, 1] (NaN fails too)
+bool sched_args_ok(int kind, int32_t warmup, int32_t total, float min_ratio) {
+  if (kind < IB_SCHED_CONSTANT || kind > IB_SCHED_COSINE || warmup < 0) return false;
+  if (kind != IB_SCHED_CONSTANT && total <= warmup) return false;
+  return min_ratio >= 0.f && min_ratio <= 1.f;
+}
+
+// the *_decay entries: weight_decay >= 0 (NaN fails the comparison), a table of table_n >= 0 ranges (8-byte aligned int64
+// pairs; may be null only when empty), the launch's origin a quad boundary of the flat buffer
+bool decay_args_ok(float wd, const void* table, int table_n, int64_t origin) {
+  if (!(wd >= 0.f) || table_n < 0 || (table_n > 0 && !table) || !ib_aligned(table, 8)) return false;
+  return origin >= 0 && origin % 4 == 0;
+}
+
+// The optional features of one launch, checked: what the entries hand to optim_launch.  The *_sched entries always pass their
+// SchedArgs.  The *_decay entries drop what does nothing: no SchedArgs for a constant schedule without warmup (the rate is the
+// host's lr, as in the entries without a schedule), no DecayArgs where nothing can be decayed (the kernels without decay, bit
+// for bit).  The gradnorm entry passes both, with an empty table at weight_decay = 0 (decay_factor(lr, 0) = 1 would be a
+// multiply by one all the same).  ok: the arguments passed their checks (an EMA buffer may be absent here).
+enum class OptEntry { sched, decay, gradnorm };
+struct OptFeatures {
+  SchedArgs sc; DecayArgs dk;
+  bool ok, has_sc, has_dk;
+  OptFeatures(OptEntry e, const float* ema, float ema_decay, int kind, int32_t warmup, int32_t total, float min_ratio,
+              float wd = 0.f, const void* table = nullptr, int table_n = 0, int64_t origin = 0)
+      : sc{kind, warmup, total, min_ratio},
+        dk{wd, e == OptEntry::gradnorm && !(wd > 0.f) ? 0 : table_n, reinterpret_cast<const int64_t*>(table), origin},
+        ok(sched_args_ok(kind, warmup, total, min_ratio) && (!ema || ema_args_ok(ema, ema_decay)) &&
+           decay_args_ok(wd, table, table_n, origin)),
+        has_sc(e != OptEntry::decay || !(kind == IB_SCHED_CONSTANT && warmup == 0)),
+        has_dk(e == OptEntry::gradnorm || (e == OptEntry::decay && wd > 0.f && table_n > 0)) {}
+  const SchedArgs* sched() const { return has_sc ? &sc : nullptr; }
+  const DecayArgs* decay() const { return has_dk ? &dk : nullptr; }
+};
+
+// The one place that names kernel instantiations: optim_kernel<SRC, EMA> with the pack (sc, dk, clip) that is present, the EMA
+// form where a.ema is.  A clip comes with both others and without sources.
+template <bool SRC, typename... F>
+void optim_launch_pack(dim3 grid, ib_stream_t stream, const OptArgs& a, const OptSources& S, int main_blocks, const F&... f) {
+  if (a.ema)
+    hipLaunchKernelGGL((optim_kernel<SRC, true, F...>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, f...);
   else
-    hipLaunchKernelGGL((optim_kernel<false, false>), grid, dim3(256), 0, ib_s(stream), a, OptSources{}, 0);
+    hipLaunchKernelGGL((optim_kernel<SRC, false, F...>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, f...);
+}
+
+template <bool SRC>
+void optim_launch(dim3 grid, ib_stream_t stream, const OptArgs& a, const OptSources& S, int main_blocks, const SchedArgs* sc,
+                  const DecayArgs* dk, const ClipArgs* clip) {
+  if constexpr (!SRC)
+    if (clip) return optim_launch_pack<SRC>(grid, stream, a, S, main_blocks, *sc, *dk, *clip);
+  if (sc && dk) optim_launch_pack<SRC>(grid, stream, a, S, main_blocks, *sc, *dk);
+  else if (sc) optim_launch_pack<SRC>(grid, stream, a, S, main_blocks, *sc);
+  else if (dk) optim_launch_pack<SRC>(grid, stream, a, S, main_blocks, *dk);
+  else optim_launch_pack<SRC>(grid, stream, a, S, main_blocks);
+}
+
+// the arguments every entry starts with, in the entries' order, as the kernel's OptArgs (unchecked: optim_check)
+OptArgs opt_args(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr, float grad_scale, int32_t step,
+                 int32_t* step_dev, int32_t* ticket, void* shadow_bf16, float* ema = nullptr, float ema_decay = 0.f,
+                 int ema_warmup = 0) {
+  return OptArgs{p, g, s1, s2, reinterpret_cast<bf16_t*>(shadow_bf16), n, lr, grad_scale, step, step_dev, ticket, opt,
+                 ema, ema_decay, ema_warmup};
+}
+
+// The checks every optimizer entry shares, on the arguments as the entry got them; s1 / s2 the optimizer does not use are
+// dropped.  quads_only (the sources form): n % 4 != 0 is IB_E_UNSUPPORTED, behind the checks on p, g, n, opt and the ticket
+// and in front of those on the states and the alignment.
+int optim_check(OptArgs& a, bool quads_only) {
+  if (!a.p || !a.g || a.n <= 0 || a.opt < IB_OPT_SGD || a.opt > IB_OPT_ADAMAX) return IB_E_ARG;
+  if (a.ticket && !a.step_dev) return IB_E_ARG;
+  if (quads_only && a.n % 4 != 0) return IB_E_UNSUPPORTED;
+  const bool need1 = a.opt != IB_OPT_SGD;
+  const bool need2 = (a.opt == IB_OPT_ADAM || a.opt == IB_OPT_ADADELTA || a.opt == IB_OPT_ADAMAX);
+  if ((need1 && !a.s1) || (need2 && !a.s2)) return IB_E_ARG;
+  if (!ib_al16({a.p, a.g, a.s1, a.s2, a.ema}) || !ib_aligned(a.shadow, 8)) return IB_E_ARG;
+  if (!need1) a.s1 = nullptr;
+  if (!need2) a.s2 = nullptr;
+  return IB_OK;
+}
+
+// the two launchers behind the C entries: ema == NULL launches optim_kernel<SRC, false>, the kernel without the EMA
+int optim_plain(OptArgs a, const SchedArgs* sc, const DecayArgs* dk, const ClipArgs* clip, ib_stream_t stream) {
+  if (const int rc = optim_check(a, false)) return rc;
+  optim_launch<false>(dim3(ib_grid_1d(a.n / 4 + 1, 256)), stream, a, OptSources{}, 0, sc, dk, clip);
   IB_CHECK_LAUNCH();
   return IB_OK;
 }
 
-int optim_sources(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr, float grad_scale,
-                  int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16, int nsrc, const int64_t* start,
-                  const int64_t* len, const int32_t* kind, const void* const* base, const int64_t* stride,
-                  const int32_t* count, const float* scale, const float* loss_col, int64_t loss_ld, int64_t loss_rows,
-                  float loss_scale, float* loss_out, float* ema, float ema_decay, int ema_warmup, const SchedArgs* sc,
-                  ib_stream_t stream, const DecayArgs* dk = nullptr) {
-  if (!p || !g || n <= 0 || opt < IB_OPT_SGD || opt > IB_OPT_ADAMAX) return IB_E_ARG;
-  if (ticket && !step_dev) return IB_E_ARG;
+int optim_sources(OptArgs a, int nsrc, const int64_t* start, const int64_t* len, const int32_t* kind, const void* const* base,
+                  const int64_t* stride, const int32_t* count, const float* scale, const float* loss_col, int64_t loss_ld,
+                  int64_t loss_rows, float loss_scale, float* loss_out, const SchedArgs* sc, const DecayArgs* dk,
+                  ib_stream_t stream) {
+  // a bad source list is IB_E_ARG whatever n % 4 is: in front of optim_check's IB_E_UNSUPPORTED
   if (nsrc < 0 || nsrc > OPT_MAXSRC || (nsrc > 0 && (!start || !len || !kind || !base || !stride || !count))) return IB_E_ARG;
-  if (n % 4 != 0) return IB_E_UNSUPPORTED;
-  const bool need1 = opt != IB_OPT_SGD;
-  const bool need2 = (opt == IB_OPT_ADAM || opt == IB_OPT_ADADELTA || opt == IB_OPT_ADAMAX);
-  if ((need1 && !s1) || (need2 && !s2)) return IB_E_ARG;
-  if (!ib_al16({p, g, s1, s2, ema}) || !ib_aligned(shadow_bf16, 8)) return IB_E_ARG;
+  if (const int rc = optim_check(a, true)) return rc;
+  const int64_t n = a.n;
   OptSources S{};
   S.n = nsrc;
   for (int j = 0; j < nsrc; ++j) {
@@ -497,214 +645,13 @@ int optim_sources(int opt, float* p, const float* g, float* s1, float* s2, int64
     if (!loss_col || loss_rows <= 0) return IB_E_ARG;
     S.loss_col = loss_col; S.loss_ld = loss_ld; S.loss_rows = (int)loss_rows; S.loss_scale = loss_scale; S.loss_out = loss_out;
   }
-  OptArgs a{p, g, need1 ? s1 : nullptr, need2 ? s2 : nullptr, reinterpret_cast<bf16_t*>(shadow_bf16),
-            n, lr, grad_scale, step, step_dev, ticket, opt, ema, ema_decay, ema_warmup};
   const int main_blocks = ib_grid_1d(n / 4 + 1, 256);
   int cs_blocks = 0;
   for (int j = 0; j < nsrc; ++j)
     if (kind[j] == 2) cs_blocks += (int)((len[j] + 63) / 64);
-  const dim3 grid(main_blocks + cs_blocks);
-  if (dk)
-    optim_launch_decay<true>(grid, stream, a, S, main_blocks, sc, *dk);
-  else if (sc && ema)
-    hipLaunchKernelGGL((optim_kernel<true, true, SchedArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, *sc);
-  else if (sc)
-    hipLaunchKernelGGL((optim_kernel<true, false, SchedArgs>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks, *sc);
-  else if (ema)
-    hipLaunchKernelGGL((optim_kernel<true, true>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks);
-  else
-    hipLaunchKernelGGL((optim_kernel<true, false>), grid, dim3(256), 0, ib_s(stream), a, S, main_blocks);
+  optim_launch<true>(dim3(main_blocks + cs_blocks), stream, a, S, main_blocks, sc, dk, nullptr);
   IB_CHECK_LAUNCH();
   return IB_OK;
-}
-
-// the *_ema entries: a 16-byte aligned EMA buffer (like p) and a decay in [0, 1] (NaN fails the comparisons too)
-bool ema_args_ok(const float* ema, float ema_decay) {
-  return ema && ib_aligned(ema, 16) && ema_decay >= 0.f && ema_decay <= 1.f;
-}
-
-// the *_sched entries and the probe: kind 0..2, warmup >= 0, a decay needs total > warmup, min_ratio in [0, 1] (NaN fails too)
-bool sched_args_ok(int kind, int32_t warmup, int32_t total, float min_ratio) {
-  if (kind < IB_SCHED_CONSTANT || kind > IB_SCHED_COSINE || warmup < 0) return false;
-  if (kind != IB_SCHED_CONSTANT && total <= warmup) return false;
-  return min_ratio >= 0.f && min_ratio <= 1.f;
-}
-
-// the *_decay entries: weight_decay >= 0 (NaN fails the comparison), a table of table_n >= 0 ranges (8-byte aligned int64
-// pairs; may be null only when empty), the launch's origin a quad boundary of the flat buffer
-bool decay_args_ok(float wd, const void* table, int table_n, int64_t origin) {
-  if (!(wd >= 0.f) || table_n < 0 || (table_n > 0 && !table) || !ib_aligned(table, 8)) return false;
-  return origin >= 0 && origin % 4 == 0;
-}
-
-// what the *_decay entries launch with: no SchedArgs for a constant schedule without warmup (the rate is the host's lr, as in
-// the entries without a schedule), no DecayArgs where nothing can be decayed (the kernels without decay, bit for bit)
-struct DecayLaunch {
-  SchedArgs sc; DecayArgs dk; bool has_sc, has_dk;
-  DecayLaunch(int kind, int32_t warmup, int32_t total, float min_ratio, float wd, const void* table, int table_n, int64_t origin)
-      : sc{kind, warmup, total, min_ratio}, dk{wd, table_n, reinterpret_cast<const int64_t*>(table), origin},
-        has_sc(!(kind == IB_SCHED_CONSTANT && warmup == 0)), has_dk(wd > 0.f && table_n > 0) {}
-};
-
-// ---- clipping to a global gradient norm (include/ib_hip_gradnorm.h states the arithmetic and the order of every sum) --------
-// The slot layout is a function of n alone: G slots of L elements, L a multiple of 1024 (every slot starts 16-byte aligned).
-constexpr int64_t GN_SLOT_ELEMS = 16384, GN_SLOT_ALIGN = 1024;
-constexpr int GN_MAX_SLOTS = 1024;
-inline int gn_slots(int64_t n) {
-  const int64_t G = n / GN_SLOT_ELEMS + (n % GN_SLOT_ELEMS != 0);
-  return (int)(G < 1 ? 1 : G > GN_MAX_SLOTS ? GN_MAX_SLOTS : G);
-}
-inline int64_t gn_slot_len(int64_t n, int G) {
-  const int64_t per = n / G + (n % G != 0);
-  return (per / GN_SLOT_ALIGN + (per % GN_SLOT_ALIGN != 0)) * GN_SLOT_ALIGN;
-}
-
-// the product of two fp32 values is exact in double, so a0 += gn_sq(x) rounds once whether or not it becomes an fma
-__device__ __forceinline__ double gn_sq(float x) { const double d = (double)x; return d * d; }
-
-// the workgroup's 256 thread sums: v[t] += v[t + h], h = 128, 64, ..., 1; every thread returns v[0]
-__device__ __forceinline__ double gn_tree256(double v, double* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-// one workgroup per slot, one pass: 16-byte loads, eight in flight per lane, four accumulators per thread (one per position in
-// the quad), the slot's ragged end (only the last slot has one) element by element on threads 0..2
-__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n, int64_t L,
-                                                         double* __restrict__ slots) {
-  __shared__ double red[256];
-  const int64_t b = (int64_t)blockIdx.x * L;
-  const int64_t len = b < n ? (n - b < L ? n - b : L) : 0;
-  const int64_t nq = len >> 2;
-  const float4* q = reinterpret_cast<const float4*>(g + b);
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  for (int64_t k = threadIdx.x; k < nq; k += 256 * 8) {
-    float4 v[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (k + e * 256 < nq) v[e] = q[k + e * 256];
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (k + e * 256 < nq) { a0 += gn_sq(v[e].x); a1 += gn_sq(v[e].y); a2 += gn_sq(v[e].z); a3 += gn_sq(v[e].w); }
-  }
-  if ((int64_t)threadIdx.x < (len & 3)) {
-    const double s = gn_sq(g[b + 4 * nq + threadIdx.x]);
-    if (threadIdx.x == 0) a0 += s; else if (threadIdx.x == 1) a1 += s; else a2 += s;
-  }
-  const double t = gn_tree256((a0 + a1) + (a2 + a3), red);
-  if (threadIdx.x == 0) slots[blockIdx.x] = t;
-}
-
-// total of the G <= 1024 slots, by every workgroup that needs it: thread t adds slots t, t + 256, ... in order, then the tree
-__device__ __forceinline__ double gn_total(const double* slots, int G, double* red) {
-  double v = 0.0;
-  for (int s = threadIdx.x; s < G; s += 256) v += slots[s];
-  return gn_tree256(v, red);
-}
-
-// the header's arithmetic, every double operation rounded on its own; a NaN or infinite coef_d fails the comparison: coef = 1
-struct ClipOut { float norm, coef, gs; };
-__device__ __forceinline__ ClipOut grad_clip(double total, float gscale, float max_norm) {
-#pragma clang fp contract(off)
-  const double norm_d = sqrt(total) * fabs((double)gscale);
-  const double coef_d = (double)max_norm / (norm_d + 1e-6);
-  const float coef = coef_d < 1.0 ? (float)coef_d : 1.0f;
-  return ClipOut{(float)norm_d, coef, gscale * coef};
-}
-
-// the probe: total and {norm, coef, gs} as the clipped launch below gets them
-__global__ __launch_bounds__(256) void grad_norm_eval_kernel(const double* slots, int G, float gscale, float max_norm,
-                                                             double* __restrict__ total_out, float* __restrict__ stats) {
-  __shared__ double red[256];
-  const double total = gn_total(slots, G, red);
-  const ClipOut k = grad_clip(total, gscale, max_norm);
-  if (threadIdx.x == 0) { *total_out = total; stats[0] = k.norm; stats[1] = k.coef; stats[2] = k.gs; }
-}
-
-// The plain form of optim_kernel<false, EMA, SchedArgs, DecayArgs> (no gradient sources, no column-sum blocks, no loss scalar)
-// behind a head that puts gs = grad_scale * coef in grad_scale's place: every workgroup adds the slots itself (8 KB of L2 hits
-// at most) and evaluates grad_clip, so the coefficient needs no launch and no host read of its own.  gs is handed on as a
-// wave-uniform value (readfirstlane), as the kernel argument it replaces is.  A kernel of its own and not one more pack element of
-// optim_kernel: those instantiations stay the code they are.  The loop, the n % 4 tail and the exit tickets are optim_kernel's.
-struct ClipArgs { const double* slots; int G; float max_norm; float* stats; };
-
-template <bool EMA>
-__global__ __launch_bounds__(256) void clipped_optim_kernel(OptArgs a, SchedArgs sc, DecayArgs D, ClipArgs c) {
-  __shared__ double red[256];
-  const ClipOut k = grad_clip(gn_total(c.slots, c.G, red), a.gscale, c.max_norm);
-  if (blockIdx.x == 0 && threadIdx.x == 0) { c.stats[0] = k.norm; c.stats[1] = k.coef; c.stats[2] = k.gs; }
-  a.gscale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, k.gs)));
-  const int step = a.step_dev ? *(volatile int32_t*)a.step_dev + (a.ticket ? 1 : a.step) : a.step;
-  if (!(sc.kind == IB_SCHED_CONSTANT && sc.warmup == 0)) a.lr = lr_scheduled(a.lr, sc, step);   // else the host's lr, as there
-  const float f = decay_factor(a.lr, D.wd);
-  float bc1 = 1.f, bc2s = 1.f;
-  if (a.opt == IB_OPT_ADAM || a.opt == IB_OPT_ADAMAX) {
-    bc1 = (float)(1.0 - pow(0.9, (double)step));
-    bc2s = (float)sqrt(1.0 - pow(0.999, (double)step));
-  }
-  float d = 0.f;
-  if constexpr (EMA)
-    d = (float)(a.ema_warmup ? fmin((double)a.ema_decay, (1.0 + step) / (10.0 + step)) : (double)a.ema_decay);
-  const int64_t n4 = a.n / 4;
-  const bool has1 = a.s1 != nullptr, has2 = a.s2 != nullptr;
-  const int64_t gstride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gstride) {
-    float4 p = reinterpret_cast<float4*>(a.p)[i];
-    const float4 g = reinterpret_cast<const float4*>(a.g)[i];
-    float4 s1 = has1 ? reinterpret_cast<float4*>(a.s1)[i] : make_float4(0, 0, 0, 0);
-    float4 s2 = has2 ? reinterpret_cast<float4*>(a.s2)[i] : make_float4(0, 0, 0, 0);
-    p = decay4(p, decayed4(D, i * 4), f);
-    p.x = opt_update(a, p.x, g.x * a.gscale, s1.x, s2.x, bc1, bc2s);
-    p.y = opt_update(a, p.y, g.y * a.gscale, s1.y, s2.y, bc1, bc2s);
-    p.z = opt_update(a, p.z, g.z * a.gscale, s1.z, s2.z, bc1, bc2s);
-    p.w = opt_update(a, p.w, g.w * a.gscale, s1.w, s2.w, bc1, bc2s);
-    reinterpret_cast<float4*>(a.p)[i] = p;
-    if (has1) reinterpret_cast<float4*>(a.s1)[i] = s1;
-    if (has2) reinterpret_cast<float4*>(a.s2)[i] = s2;
-    if (a.shadow) {
-      bf16x4_t o;
-      o[0] = (bf16_t)p.x; o[1] = (bf16_t)p.y; o[2] = (bf16_t)p.z; o[3] = (bf16_t)p.w;
-      reinterpret_cast<bf16x4_t*>(a.shadow)[i] = o;
-    }
-    if constexpr (EMA) ema4(a, d, i, 4);
-  }
-  // tail (n % 4): it belongs to quad n / 4
-  const int64_t t0 = n4 * 4;
-  for (int64_t i = t0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += gstride) {
-    float s1 = has1 ? a.s1[i] : 0.f, s2 = has2 ? a.s2[i] : 0.f;
-    float pi = a.p[i];
-    if (decayed4(D, t0)) pi = decay_mul(pi, f);
-    asm("" : "+v"(pi));
-    const float p = opt_update(a, pi, a.g[i] * a.gscale, s1, s2, bc1, bc2s);
-    a.p[i] = p;
-    if (has1) a.s1[i] = s1;
-    if (has2) a.s2[i] = s2;
-    if (a.shadow) a.shadow[i] = (bf16_t)p;
-    if constexpr (EMA) a.ema[i] = ema_update(d, a.ema[i], *(const volatile float*)(a.p + i));
-  }
-  if (a.ticket) {                        // exit tickets, two levels: as in optim_kernel
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int G = (int)gridDim.x;
-      const int nsub = G < OPT_TICKET_SUBS ? G : OPT_TICKET_SUBS;
-      const int sub = (int)blockIdx.x % OPT_TICKET_SUBS;
-      const int quota = (G - sub + OPT_TICKET_SUBS - 1) / OPT_TICKET_SUBS;
-      int32_t* tc = a.ticket + OPT_TICKET_LINE * (1 + sub);
-      if (atomicAdd(tc, 1) == quota - 1) {
-        *tc = 0;
-        if (atomicAdd(a.ticket, 1) == nsub - 1) {
-          *a.step_dev = step;
-          *a.ticket = 0;
-        }
-      }
-    }
-  }
 }
 
 // the entries of ib_hip_gradnorm.h: every pointer present and 16-byte aligned, max_norm > 0 (NaN fails the comparison)
@@ -741,29 +688,12 @@ extern "C" int ib_optim_step_gradnorm(int opt, float* p, const float* g, float* 
                                       int32_t sched_total, float sched_min_ratio, float weight_decay, const void* table_dev,
                                       int table_n, int64_t origin, const double* slots, int64_t sumsq_n, float max_norm,
                                       float* stats3, ib_stream_t stream) {
-  if (!sched_args_ok(sched_kind, sched_warmup, sched_total, sched_min_ratio)) return IB_E_ARG;
-  if (ema && !ema_args_ok(ema, ema_decay)) return IB_E_ARG;
-  if (!decay_args_ok(weight_decay, table_dev, table_n, origin)) return IB_E_ARG;
-  if (!gradnorm_args_ok({slots, stats3}, sumsq_n, max_norm)) return IB_E_ARG;
-  if (!p || !g || n <= 0 || opt < IB_OPT_SGD || opt > IB_OPT_ADAMAX) return IB_E_ARG;       // as optim_plain
-  if (ticket && !step_dev) return IB_E_ARG;
-  const bool need1 = opt != IB_OPT_SGD;
-  const bool need2 = (opt == IB_OPT_ADAM || opt == IB_OPT_ADADELTA || opt == IB_OPT_ADAMAX);
-  if ((need1 && !s1) || (need2 && !s2)) return IB_E_ARG;
-  if (!ib_al16({p, g, s1, s2, ema}) || !ib_aligned(shadow_bf16, 8)) return IB_E_ARG;
-  OptArgs a{p, g, need1 ? s1 : nullptr, need2 ? s2 : nullptr, reinterpret_cast<bf16_t*>(shadow_bf16),
-            n, lr, grad_scale, step, step_dev, ticket, opt, ema, ema_decay, ema_warmup};
-  const SchedArgs sc{sched_kind, sched_warmup, sched_total, sched_min_ratio};
-  // weight_decay = 0 decays nothing through an empty table: decay_factor(lr, 0) = 1 would be a multiply by one all the same
-  const DecayArgs dk{weight_decay, weight_decay > 0.f ? table_n : 0, reinterpret_cast<const int64_t*>(table_dev), origin};
+  const OptFeatures F(OptEntry::gradnorm, ema, ema_decay, sched_kind, sched_warmup, sched_total, sched_min_ratio, weight_decay,
+                      table_dev, table_n, origin);
+  if (!F.ok || !gradnorm_args_ok({slots, stats3}, sumsq_n, max_norm)) return IB_E_ARG;
   const ClipArgs c{slots, gn_slots(sumsq_n), max_norm, stats3};
-  const dim3 grid(ib_grid_1d(n / 4 + 1, 256));
-  if (ema)
-    hipLaunchKernelGGL((clipped_optim_kernel<true>), grid, dim3(256), 0, ib_s(stream), a, sc, dk, c);
-  else
-    hipLaunchKernelGGL((clipped_optim_kernel<false>), grid, dim3(256), 0, ib_s(stream), a, sc, dk, c);
-  IB_CHECK_LAUNCH();
-  return IB_OK;
+  return optim_plain(opt_args(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup),
+                     F.sched(), F.decay(), &c, stream);
 }
 
 extern "C" int ib_optim_ticket_words(void) { return OPT_TICKET_LINE * (1 + OPT_TICKET_SUBS); }
@@ -771,16 +701,16 @@ extern "C" int ib_optim_ticket_words(void) { return OPT_TICKET_LINE * (1 + OPT_T
 extern "C" int ib_optim_step(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
                              float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16,
                              ib_stream_t stream) {
-  return optim_plain(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nullptr, 0.f, 0, nullptr,
-                     stream);
+  return optim_plain(opt_args(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16), nullptr, nullptr,
+                     nullptr, stream);
 }
 
 extern "C" int ib_optim_step_ema(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
                                  float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16,
                                  float* ema, float ema_decay, int ema_warmup, ib_stream_t stream) {
   if (!ema_args_ok(ema, ema_decay)) return IB_E_ARG;
-  return optim_plain(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup,
-                     nullptr, stream);
+  return optim_plain(opt_args(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup),
+                     nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int ib_optim_step_sources(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
@@ -789,9 +719,8 @@ extern "C" int ib_optim_step_sources(int opt, float* p, const float* g, float* s
                                      const int32_t* kind, const void* const* base, const int64_t* stride,
                                      const int32_t* count, const float* scale, const float* loss_col, int64_t loss_ld,
                                      int64_t loss_rows, float loss_scale, float* loss_out, ib_stream_t stream) {
-  return optim_sources(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nsrc, start, len, kind,
-                       base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out, nullptr, 0.f, 0,
-                       nullptr, stream);
+  return optim_sources(opt_args(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16), nsrc, start, len, kind,
+                       base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out, nullptr, nullptr, stream);
 }
 
 extern "C" int ib_optim_step_sources_ema(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
@@ -802,20 +731,19 @@ extern "C" int ib_optim_step_sources_ema(int opt, float* p, const float* g, floa
                                          int64_t loss_ld, int64_t loss_rows, float loss_scale, float* loss_out,
                                          float* ema, float ema_decay, int ema_warmup, ib_stream_t stream) {
   if (!ema_args_ok(ema, ema_decay)) return IB_E_ARG;
-  return optim_sources(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nsrc, start, len, kind,
-                       base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out, ema, ema_decay,
-                       ema_warmup, nullptr, stream);
+  return optim_sources(opt_args(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup),
+                       nsrc, start, len, kind, base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out,
+                       nullptr, nullptr, stream);
 }
 
 extern "C" int ib_optim_step_sched(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
                                    float grad_scale, int32_t step, int32_t* step_dev, int32_t* ticket, void* shadow_bf16,
                                    float* ema, float ema_decay, int ema_warmup, int sched_kind, int32_t sched_warmup,
                                    int32_t sched_total, float sched_min_ratio, ib_stream_t stream) {
-  if (!sched_args_ok(sched_kind, sched_warmup, sched_total, sched_min_ratio)) return IB_E_ARG;
-  if (ema && !ema_args_ok(ema, ema_decay)) return IB_E_ARG;
-  const SchedArgs sc{sched_kind, sched_warmup, sched_total, sched_min_ratio};
-  return optim_plain(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup,
-                     &sc, stream);
+  const OptFeatures F(OptEntry::sched, ema, ema_decay, sched_kind, sched_warmup, sched_total, sched_min_ratio);
+  if (!F.ok) return IB_E_ARG;
+  return optim_plain(opt_args(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup),
+                     F.sched(), F.decay(), nullptr, stream);
 }
 
 extern "C" int ib_optim_step_sources_sched(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
@@ -827,12 +755,11 @@ extern "C" int ib_optim_step_sources_sched(int opt, float* p, const float* g, fl
                                            float* ema, float ema_decay, int ema_warmup, int sched_kind,
                                            int32_t sched_warmup, int32_t sched_total, float sched_min_ratio,
                                            ib_stream_t stream) {
-  if (!sched_args_ok(sched_kind, sched_warmup, sched_total, sched_min_ratio)) return IB_E_ARG;
-  if (ema && !ema_args_ok(ema, ema_decay)) return IB_E_ARG;
-  const SchedArgs sc{sched_kind, sched_warmup, sched_total, sched_min_ratio};
-  return optim_sources(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nsrc, start, len, kind,
-                       base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out, ema, ema_decay,
-                       ema_warmup, &sc, stream);
+  const OptFeatures F(OptEntry::sched, ema, ema_decay, sched_kind, sched_warmup, sched_total, sched_min_ratio);
+  if (!F.ok) return IB_E_ARG;
+  return optim_sources(opt_args(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup),
+                       nsrc, start, len, kind, base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out,
+                       F.sched(), F.decay(), stream);
 }
 
 extern "C" int ib_lr_schedule_eval(float lr, int kind, int32_t warmup, int32_t total, float min_ratio, const int32_t* steps,
@@ -870,12 +797,11 @@ extern "C" int ib_optim_step_decay(int opt, float* p, const float* g, float* s1,
                                    float* ema, float ema_decay, int ema_warmup, int sched_kind, int32_t sched_warmup,
                                    int32_t sched_total, float sched_min_ratio, float weight_decay, const void* table_dev,
                                    int table_n, int64_t origin, ib_stream_t stream) {
-  if (!sched_args_ok(sched_kind, sched_warmup, sched_total, sched_min_ratio)) return IB_E_ARG;
-  if (ema && !ema_args_ok(ema, ema_decay)) return IB_E_ARG;
-  if (!decay_args_ok(weight_decay, table_dev, table_n, origin)) return IB_E_ARG;
-  const DecayLaunch L(sched_kind, sched_warmup, sched_total, sched_min_ratio, weight_decay, table_dev, table_n, origin);
-  return optim_plain(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup,
-                     L.has_sc ? &L.sc : nullptr, stream, L.has_dk ? &L.dk : nullptr);
+  const OptFeatures F(OptEntry::decay, ema, ema_decay, sched_kind, sched_warmup, sched_total, sched_min_ratio, weight_decay,
+                      table_dev, table_n, origin);
+  if (!F.ok) return IB_E_ARG;
+  return optim_plain(opt_args(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup),
+                     F.sched(), F.decay(), nullptr, stream);
 }
 
 extern "C" int ib_optim_step_sources_decay(int opt, float* p, const float* g, float* s1, float* s2, int64_t n, float lr,
@@ -888,11 +814,10 @@ extern "C" int ib_optim_step_sources_decay(int opt, float* p, const float* g, fl
                                            int32_t sched_warmup, int32_t sched_total, float sched_min_ratio,
                                            float weight_decay, const void* table_dev, int table_n, int64_t origin,
                                            ib_stream_t stream) {
-  if (!sched_args_ok(sched_kind, sched_warmup, sched_total, sched_min_ratio)) return IB_E_ARG;
-  if (ema && !ema_args_ok(ema, ema_decay)) return IB_E_ARG;
-  if (!decay_args_ok(weight_decay, table_dev, table_n, origin)) return IB_E_ARG;
-  const DecayLaunch L(sched_kind, sched_warmup, sched_total, sched_min_ratio, weight_decay, table_dev, table_n, origin);
-  return optim_sources(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, nsrc, start, len, kind,
-                       base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out, ema, ema_decay,
-                       ema_warmup, L.has_sc ? &L.sc : nullptr, stream, L.has_dk ? &L.dk : nullptr);
+  const OptFeatures F(OptEntry::decay, ema, ema_decay, sched_kind, sched_warmup, sched_total, sched_min_ratio, weight_decay,
+                      table_dev, table_n, origin);
+  if (!F.ok) return IB_E_ARG;
+  return optim_sources(opt_args(opt, p, g, s1, s2, n, lr, grad_scale, step, step_dev, ticket, shadow_bf16, ema, ema_decay, ema_warmup),
+                       nsrc, start, len, kind, base, stride, count, scale, loss_col, loss_ld, loss_rows, loss_scale, loss_out,
+                       F.sched(), F.decay(), stream);
 }

@@ -607,7 +607,6 @@ class HipTrainer:
         self._finish_step(cut)
 
     def _finish_step(self, cut):
-        m, dt = self.model, self.model.compute_dtype
         if self.ddp:
             if cut is not None:
                 cut(-1 if self.overlap_comm else -2)
@@ -622,12 +621,7 @@ class HipTrainer:
             if getattr(self.plan, "pending_sources", None) is not None or self._early_done:
                 raise hip.HipError("max_grad_norm: the plan left gradient sources or early optimizer launches behind")
             hip.grad_sumsq(self.grad, self.norm_slots)
-            sl = lambda t: t
-            hip.optim_step(self.opt_type, self.flat, self.grad, self.s1, self.s2, self.lr, step=0, step_dev=self.step_dev,
-                           ticket=self.ticket, grad_scale=1.0 / self.world,
-                           shadow=m._shadow if dt == torch.bfloat16 else None, max_grad_norm=self.max_grad_norm,
-                           norm_slots=self.norm_slots, norm_stats=self.norm_stats, **self._ema_args(sl),
-                           **self._sched_args(), **self._decay_args(0))
+            self._optimizer_launch(0, self.flat.numel(), last=True, clip=True)
             return
         # self-counting optimizer launch: uses *step_dev + 1 and publishes it itself (no separate counter launch)
         src = getattr(self.plan, "pending_sources", None)
@@ -643,11 +637,20 @@ class HipTrainer:
         lo, hi, inner = self._last_launch_range(done, src)
         if src is not None and (inner or len(src) > 4):
             src = tuple(src[:4]) + ([self.grad[a:b] for a, b in inner],)
+        self._optimizer_launch(lo, hi, last=True, sources=src)
+
+    def _optimizer_launch(self, lo: int, hi: int, last: bool, sources=None, clip: bool = False):
+        """the optimizer over [lo, hi) of the flat buffers (states, bf16 shadow and EMA sliced alike, grad_scale = 1 / world).
+        last: the step's self-counting launch -- step = 0 with the ticket, it uses *step_dev + 1 and publishes it; otherwise an
+        early launch of the same step -- step = 1 without a ticket, the same step number, nothing published.  sources: the
+        gradient sources this launch sums itself.  clip: the clipped launch, behind grad_sumsq over the whole gradient."""
         sl = lambda t: None if t is None else t[lo:hi]
-        hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr, step=0,
-                       step_dev=self.step_dev, ticket=self.ticket, grad_scale=1.0 / self.world,
-                       shadow=sl(m._shadow) if dt == torch.bfloat16 else None, sources=src, **self._ema_args(sl),
-                       **self._sched_args(), **self._decay_args(lo))
+        kw = {"max_grad_norm": self.max_grad_norm, "norm_slots": self.norm_slots, "norm_stats": self.norm_stats} if clip else {}
+        hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr,
+                       step=0 if last else 1, step_dev=self.step_dev, ticket=self.ticket if last else None,
+                       grad_scale=1.0 / self.world,
+                       shadow=sl(self.model._shadow) if self.model.compute_dtype == torch.bfloat16 else None, sources=sources,
+                       **kw, **self._ema_args(sl), **self._sched_args(), **self._decay_args(lo))
 
     def _ema_args(self, sl) -> Dict:
         """optim_step's EMA arguments for a launch over the slice `sl` selects (none with the EMA off: the entries without it)"""
@@ -712,17 +715,12 @@ class HipTrainer:
             self._early_done.append((lo, hi))
         if not issue:
             return
-        m, dt = self.model, self.model.compute_dtype
-        sl = lambda t: None if t is None else t[lo:hi]
         w = self.buckets.take_work(b)
 
         def fn():
             if w is not None:
                 w.wait()                             # stream-level on the GPU path: the SIDE stream waits, not the backward
-            hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr, step=1,
-                           step_dev=self.step_dev, grad_scale=1.0 / self.world,
-                           shadow=sl(m._shadow) if dt == torch.bfloat16 else None, **self._ema_args(sl),
-                           **self._sched_args(), **self._decay_args(lo))
+            self._optimizer_launch(lo, hi, last=False)
         self._br_opt.run(fn)
 
     def _prefix_range(self, prefix: str) -> Tuple[int, int]:
@@ -744,12 +742,7 @@ class HipTrainer:
         """the optimizer over ONE layer's range (issued by the plan on that layer's side stream once its gradient sources
         are complete): same step number as the step's last, self-counting launch (*step_dev + 1), which skips the range"""
         lo, hi = self._prefix_range(prefix)
-        m, dt = self.model, self.model.compute_dtype
-        sl = lambda t: None if t is None else t[lo:hi]
-        hip.optim_step(self.opt_type, self.flat[lo:hi], self.grad[lo:hi], sl(self.s1), sl(self.s2), self.lr, step=1,
-                       step_dev=self.step_dev, grad_scale=1.0 / self.world,
-                       shadow=sl(m._shadow) if dt == torch.bfloat16 else None, sources=sources, **self._ema_args(sl),
-                       **self._sched_args(), **self._decay_args(lo))
+        self._optimizer_launch(lo, hi, last=False, sources=sources)
         self._early_done.append((lo, hi))
 
     def _stage(self, batch) -> Dict[str, torch.Tensor]:

@@ -263,20 +263,14 @@ class _DryRunLib:
                     t.from_param(v) if hasattr(t, "from_param") else None
             self.calls.append(name)
             self.args.append((name, a))
-            if name == "ib_optim_step_ema":
-                self.ema_ranges.append((a[12], int(a[5]), []))
-            elif name == "ib_optim_step_sources_ema":
-                m = int(a[12])
-                rd = lambda p, ct: ctypes.cast(p, ctypes.POINTER(ct))
-                st, ln, kd = rd(a[13], ctypes.c_int64), rd(a[14], ctypes.c_int64), rd(a[15], ctypes.c_int32)
-                self.ema_ranges.append((a[25], int(a[5]), [(st[j], ln[j]) for j in range(m) if kd[j] == 3]))
-            elif name in ("ib_optim_step_sched", "ib_optim_step_decay", "ib_optim_step_gradnorm") and a[12] is not None:
-                self.ema_ranges.append((a[12], int(a[5]), []))
-            elif name in ("ib_optim_step_sources_sched", "ib_optim_step_sources_decay") and a[25] is not None:
-                m = int(a[12])
-                rd = lambda p, ct: ctypes.cast(p, ctypes.POINTER(ct))
-                st, ln, kd = rd(a[13], ctypes.c_int64), rd(a[14], ctypes.c_int64), rd(a[15], ctypes.c_int32)
-                self.ema_ranges.append((a[25], int(a[5]), [(st[j], ln[j]) for j in range(m) if kd[j] == 3]))
+            at, has_sources = _OPTIM_EMA_AT.get(name, (None, False))
+            if at is not None and a[at] is not None:     # an optimizer launch that advances an EMA
+                done = []
+                if has_sources:
+                    rd = lambda p, ct: ctypes.cast(p, ctypes.POINTER(ct))
+                    st, ln, kd = rd(a[13], ctypes.c_int64), rd(a[14], ctypes.c_int64), rd(a[15], ctypes.c_int32)
+                    done = [(st[j], ln[j]) for j in range(int(a[12])) if kd[j] == 3]
+                self.ema_ranges.append((a[at], int(a[5]), done))
             return 0
         return call
 
@@ -1515,82 +1509,81 @@ def optim_step(opt: str, p, g, s1, s2, lr, step=None, step_dev=None, grad_scale=
         _req(ticket, "ticket", torch.int32)
         if ticket.numel() < optim_ticket_words() or not ticket.is_contiguous():
             raise HipError(f"ticket: {optim_ticket_words()} contiguous zeroed int32 words required (ib_optim_ticket_words)")
-    if sources is not None:
-        items, part, rows, segs = sources[:4]
-        done = sources[4] if len(sources) > 4 else ()       # views into g whose parameters an earlier launch updated
-        ld = 0
-        if part is not None:
-            pr, pc, ld = _mat(part, "part", torch.float32)
-        g0, g1 = g.data_ptr(), g.data_ptr() + 4 * n
-        ent, loss = [], None                      # (start, len, kind, base, stride, count, scale)
+    src = _optim_sources_args(g, n, sources) if sources is not None else ()
+    args = (OPT[opt], _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), n, float(lr), float(grad_scale), int(step), _ptr(step_dev),
+            _ptr(ticket), _ptr(shadow)) + src
+    on = "clip" if clip else "decay" if decay else "sched" if sched else "ema" if ema is not None else None
+    name, tails = _OPTIM_CALLS[sources is not None, on]
+    tail = {"sched": sched or _NO_SCHED, "decay": decay or _NO_DECAY, "clip": clip}
+    if "ema" in tails:
+        tail["ema"] = (_ptr(ema), float(ema_decay), int(bool(ema_warmup)))
+    for k in tails:
+        args += tail[k]
+    _check(getattr(lib(), name)(*args, stream_ptr()), name)
 
-        def flat_off(t, what):
-            a = t.data_ptr()
-            if not (g0 <= a < g1) or (a - g0) % 16 or not t.is_contiguous():
-                raise HipError(f"optim_step sources: {what} must be a contiguous, 16-byte aligned view into g")
-            return (a - g0) // 4
-        for ws, ns, dw in items:
-            ent.append((flat_off(dw, "dw"), dw.numel(), 1, ws.data_ptr(), dw.numel(), int(ns), 1.0))
-        for seg in segs:
-            c0, nc, d, d2, sc = seg[:5]
-            if len(seg) > 5:                      # a segment with its own partial matrix: (.., part_i, rows_i)
-                _, _, ld_i = _mat(seg[5], "part_i", torch.float32)
-                for dd in (d, d2):
-                    if dd is not None:
-                        ent.append((flat_off(dd, "dst"), nc, 2, seg[5].data_ptr() + 4 * c0, ld_i, int(seg[6]), float(sc)))
-                continue
-            if not (g0 <= d.data_ptr() < g1):     # the loss scalar lives outside the flat buffer
-                if nc != 1 or loss is not None:
-                    raise HipError("optim_step sources: at most one scalar destination outside g")
-                loss = (part.data_ptr() + 4 * c0, float(sc), d)
-                continue
+
+def _optim_sources_args(g, n, sources):
+    """optim_step's `sources` as the *_sources entries take them: the count, the seven arrays (start, len, kind, base, stride,
+    count, scale; sorted by start) and the loss scalar's (column, ld, rows, scale, destination)"""
+    items, part, rows, segs = sources[:4]
+    done = sources[4] if len(sources) > 4 else ()       # views into g whose parameters an earlier launch updated
+    ld = 0
+    if part is not None:
+        pr, pc, ld = _mat(part, "part", torch.float32)
+    g0, g1 = g.data_ptr(), g.data_ptr() + 4 * n
+    ent, loss = [], None                      # (start, len, kind, base, stride, count, scale)
+
+    def flat_off(t, what):
+        a = t.data_ptr()
+        if not (g0 <= a < g1) or (a - g0) % 16 or not t.is_contiguous():
+            raise HipError(f"optim_step sources: {what} must be a contiguous, 16-byte aligned view into g")
+        return (a - g0) // 4
+    for ws, ns, dw in items:
+        ent.append((flat_off(dw, "dw"), dw.numel(), 1, ws.data_ptr(), dw.numel(), int(ns), 1.0))
+    for seg in segs:
+        c0, nc, d, d2, sc = seg[:5]
+        if len(seg) > 5:                      # a segment with its own partial matrix: (.., part_i, rows_i)
+            _, _, ld_i = _mat(seg[5], "part_i", torch.float32)
             for dd in (d, d2):
                 if dd is not None:
-                    ent.append((flat_off(dd, "dst"), nc, 2, part.data_ptr() + 4 * c0, ld, int(rows), float(sc)))
-        for dv in done:
-            ent.append((flat_off(dv, "done range"), dv.numel(), 3, 0, 0, 0, 1.0))
-        ent.sort(key=lambda e: e[0])              # the kernel's range scan stops at the first source beyond the element
-        m = len(ent)
-        cv = lambda a: ctypes.cast(a, ctypes.c_void_p)
-        A = lambda ct, k: (ct * m)(*[e[k] for e in ent])
-        start, ln, kind = A(ctypes.c_int64, 0), A(ctypes.c_int64, 1), A(ctypes.c_int32, 2)
-        base, stride, count, scale = A(ctypes.c_void_p, 3), A(ctypes.c_int64, 4), A(ctypes.c_int32, 5), A(ctypes.c_float, 6)
-        args = (OPT[opt], _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), n, float(lr), float(grad_scale), int(step), _ptr(step_dev),
-                _ptr(ticket), _ptr(shadow), m, cv(start), cv(ln), cv(kind), cv(base), cv(stride), cv(count), cv(scale),
-                ctypes.c_void_p(loss[0]) if loss else None, ld, int(rows), loss[1] if loss else 0.0,
-                _ptr(loss[2]) if loss else None)
-        if decay:
-            _check(lib().ib_optim_step_sources_decay(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)),
-                                                     *(sched or _NO_SCHED), *decay, stream_ptr()), "ib_optim_step_sources_decay")
-        elif sched:
-            _check(lib().ib_optim_step_sources_sched(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), *sched,
-                                                     stream_ptr()), "ib_optim_step_sources_sched")
-        elif ema is None:
-            _check(lib().ib_optim_step_sources(*args, stream_ptr()), "ib_optim_step_sources")
-        else:
-            _check(lib().ib_optim_step_sources_ema(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), stream_ptr()),
-                   "ib_optim_step_sources_ema")
-        return
-    args = (OPT[opt], _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), n, float(lr), float(grad_scale), int(step), _ptr(step_dev),
-            _ptr(ticket), _ptr(shadow))
-    if clip:
-        _check(lib().ib_optim_step_gradnorm(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), *(sched or _NO_SCHED),
-                                            *(decay or _NO_DECAY), *clip, stream_ptr()), "ib_optim_step_gradnorm")
-    elif decay:
-        _check(lib().ib_optim_step_decay(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), *(sched or _NO_SCHED),
-                                         *decay, stream_ptr()), "ib_optim_step_decay")
-    elif sched:
-        _check(lib().ib_optim_step_sched(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), *sched, stream_ptr()),
-               "ib_optim_step_sched")
-    elif ema is None:
-        _check(lib().ib_optim_step(*args, stream_ptr()), "ib_optim_step")
-    else:
-        _check(lib().ib_optim_step_ema(*args, _ptr(ema), float(ema_decay), int(bool(ema_warmup)), stream_ptr()),
-               "ib_optim_step_ema")
+                    ent.append((flat_off(dd, "dst"), nc, 2, seg[5].data_ptr() + 4 * c0, ld_i, int(seg[6]), float(sc)))
+            continue
+        if not (g0 <= d.data_ptr() < g1):     # the loss scalar lives outside the flat buffer
+            if nc != 1 or loss is not None:
+                raise HipError("optim_step sources: at most one scalar destination outside g")
+            loss = (part.data_ptr() + 4 * c0, float(sc), d)
+            continue
+        for dd in (d, d2):
+            if dd is not None:
+                ent.append((flat_off(dd, "dst"), nc, 2, part.data_ptr() + 4 * c0, ld, int(rows), float(sc)))
+    for dv in done:
+        ent.append((flat_off(dv, "done range"), dv.numel(), 3, 0, 0, 0, 1.0))
+    ent.sort(key=lambda e: e[0])              # the kernel's range scan stops at the first source beyond the element
+    m = len(ent)
+    A = lambda ct, k: ctypes.cast((ct * m)(*[e[k] for e in ent]), ctypes.c_void_p)     # the cast keeps the array alive
+    return (m, A(ctypes.c_int64, 0), A(ctypes.c_int64, 1), A(ctypes.c_int32, 2), A(ctypes.c_void_p, 3), A(ctypes.c_int64, 4),
+            A(ctypes.c_int32, 5), A(ctypes.c_float, 6), ctypes.c_void_p(loss[0]) if loss else None, ld, int(rows),
+            loss[1] if loss else 0.0, _ptr(loss[2]) if loss else None)
 
 
 _NO_SCHED = (0, 0, 0, 0.0)      # IB_SCHED_CONSTANT without warmup: the *_decay entries then run at the host's lr
 _NO_DECAY = (0.0, None, 0, 0)   # ib_optim_step_gradnorm without weight decay: an empty table
+
+# optim_step's call: (sources given, the last feature that is on of ema < sched < decay < clip) -> the entry and the tails it
+# takes behind the common head and the sources, in its argument order; a tail that is off goes as None / _NO_SCHED / _NO_DECAY
+_OPTIM_CALLS = {
+    (False, None): ("ib_optim_step", ()),
+    (False, "ema"): ("ib_optim_step_ema", ("ema",)),
+    (False, "sched"): ("ib_optim_step_sched", ("ema", "sched")),
+    (False, "decay"): ("ib_optim_step_decay", ("ema", "sched", "decay")),
+    (False, "clip"): ("ib_optim_step_gradnorm", ("ema", "sched", "decay", "clip")),
+    (True, None): ("ib_optim_step_sources", ()),
+    (True, "ema"): ("ib_optim_step_sources_ema", ("ema",)),
+    (True, "sched"): ("ib_optim_step_sources_sched", ("ema", "sched")),
+    (True, "decay"): ("ib_optim_step_sources_decay", ("ema", "sched", "decay")),
+}
+# _DryRunLib's ema_ranges: entry -> (index of its ema argument, behind the 12 common arguments and the sources' 13; has sources)
+_OPTIM_EMA_AT = {name: (25 if src else 12, src) for (src, _), (name, tails) in _OPTIM_CALLS.items() if "ema" in tails}
 
 
 def grad_sumsq_slots(n: int) -> int:

@@ -7,7 +7,7 @@ csrc/optim.hip) on the GPU.
      n 2^-53 (< 2e-9 at the largest n), the square root halves it, so the one rounding to fp32 is what is left.  coef and gs
      within 1 fp32 ulp of grad_norm.clip_coef(the device's total): the host's restatement of the same double arithmetic,
      one ulp for the libraries' sqrt.  Two runs bitwise equal.  g = 0: norm 0, coef 1; one inf: coef 0; one NaN: coef 1.
-  2. decomposition, BITWISE: six optimizers, n = 8195, the step number from the host, from step_dev + step and from the ticket
+  2. decomposition, BITWISE: six optimizers, n = 3 (the tail alone), 256 (quads alone) and 8195, the step number from the host, from step_dev + step and from the ticket
      launch, with and without EMA + cosine schedule + decay table, grad_scale 1 and 0.5, max_norm below and above the norm:
      p, s1, s2, shadow, ema equal the entries older than the clip called with grad_scale = gs, gs read from the probe.
   3. AdamW with torch.nn.utils.clip_grad_norm_ on the CPU over ten steps, at the bound of the Adam trajectory test (2e-5).
@@ -129,13 +129,14 @@ def test_zero_inf_and_nan_gradients():
 # 2. decomposition
 # ---------------------------------------------------------------------------------------------------------------------
 RANGES = [(0, 1000), (1200, 30), (2048, 2052), (8192, 3)]        # the decay kernel test's: one at 0, the n % 4 tail
+# the decomposition's sizes and their decay ranges (each covers the first quad and ends inside the buffer): 3 = no quad, the
+# tail alone, one workgroup; 256 = quads alone, no tail; 8195 = eight workgroups of quads and a tail
+SIZED_RANGES = {3: [(0, 3)], 256: [(0, 100), (120, 30), (200, 40)], 8195: RANGES}
 
 
-@pytest.fixture(scope="module")
-def inputs():
+def make_inputs(n, ranges):
     from inferbiomechanics_amd import hip
     from inferbiomechanics_amd.lr_schedule import LrSchedule
-    n = 8195
     gen = torch.Generator().manual_seed(11)
     p0 = torch.randn(n, generator=gen).to(DEV)
     g = (torch.randn(n, generator=gen) * 1e-2).to(DEV)
@@ -144,7 +145,17 @@ def inputs():
     e0 = (p0 + torch.randn(n, generator=gen).to(DEV) * 1e-2).contiguous()
     slots = hip.grad_sumsq(g)
     torch.cuda.synchronize()
-    return n, p0, g, s10, s20, e0, slots, hip.DecayTable(RANGES, DEV), LrSchedule("cosine", 5, 15, 0.1), host_norm(g.cpu())
+    return n, p0, g, s10, s20, e0, slots, hip.DecayTable(ranges, DEV), LrSchedule("cosine", 5, 15, 0.1), host_norm(g.cpu())
+
+
+@pytest.fixture(scope="module")
+def sized_inputs():
+    return {n: make_inputs(n, ranges) for n, ranges in SIZED_RANGES.items()}
+
+
+@pytest.fixture(scope="module")
+def inputs(sized_inputs):
+    return sized_inputs[8195]
 
 
 def launch(opt, bufs, mode, s, full, grad_scale, clip=None):
@@ -175,7 +186,12 @@ def launch(opt, bufs, mode, s, full, grad_scale, clip=None):
 
 @pytest.mark.parametrize("opt", OPTS)
 @pytest.mark.parametrize("mode", ["host", "step_dev", "ticket"])
-def test_clipped_update_is_the_old_entry_with_the_probes_scale(opt, mode, inputs):
+def test_clipped_update_is_the_old_entry_with_the_probes_scale(opt, mode, sized_inputs):
+    for n in sorted(sized_inputs):
+        clipped_update_is_the_old_entry(opt, mode, sized_inputs[n])
+
+
+def clipped_update_is_the_old_entry(opt, mode, inputs):
     from inferbiomechanics_amd import hip
     slots, norm = inputs[6], inputs[9]
     for full, steps in ((True, [1, 6, 16]), (False, [6])):
@@ -187,7 +203,7 @@ def test_clipped_update_is_the_old_entry_with_the_probes_scale(opt, mode, inputs
                 coef, gs = float(probe[1]), float(probe[2])
                 assert (coef < 1.0 and gs < grad_scale) if frac < 1 else (coef == 1.0 and gs == grad_scale), (frac, coef, gs)
                 for s in steps:
-                    what = (opt, mode, full, grad_scale, frac, s)
+                    what = (inputs[0], opt, mode, full, grad_scale, frac, s)
                     ref, untouched = launch(opt, inputs, mode, s, full, gs)
                     got, stats = launch(opt, inputs, mode, s, full, grad_scale, clip=mx)
                     for a, b, nm in zip(ref, got, NAMES):

@@ -98,7 +98,8 @@ def test_thirteenth_header_has_its_own_table_and_is_built():
     assert re.search(r"^build/optim\.o build_ab/optim\.o: \.\./\.\./include/ib_hip_gradnorm\.h$", mk, flags=re.M)
     assert mk.index("\nall:") < mk.index("ib_hip_gradnorm.h"), "the default goal stays `all`"
     src = open(os.path.join(os.path.dirname(hip.__file__), "csrc", "optim.hip")).read()
-    assert "ib_hip_gradnorm.h" in src and "template <bool EMA>\n__global__ __launch_bounds__(256) void clipped_optim_kernel(" in src
+    assert "ib_hip_gradnorm.h" in src and "clipped_optim_kernel" not in src
+    assert "std::is_same<void(Sched...), void(SchedArgs, DecayArgs, ClipArgs)>::value" in src, "the clip is optim_kernel's third pack element"
     for path in (hip.LIB_PATH, hip.AB_LIB_PATH):
         if not os.path.exists(path):
             pytest.fail(f"{path} is not built")
@@ -153,13 +154,16 @@ def test_argument_errors_come_before_any_launch():
 
 
 def test_clipped_kernels_do_not_spill_to_scratch():
-    """both clipped_optim_kernel instantiations and the norm kernels compile without spills or scratch (compile only)"""
+    """both clip forms of optim_kernel (the two of its eighteen instantiations whose mangled name carries a ClipArgs) and the
+    norm kernels compile without spills or scratch (compile only)"""
     from tools import kernel_resources as kr
     if kr.hipcc() is None:
         pytest.skip("hipcc not installed")
     rows = kr.resources("optim.hip")
-    clipped = [k for k in rows if k["kernel"].startswith("clipped_optim_kernel<")]
-    assert len(clipped) == 2 and len([k for k in rows if k["kernel"].startswith("optim_kernel<")]) == 16
+    optim = [k for k in rows if k["kernel"].startswith("optim_kernel<")]
+    clipped = [k for k in optim if "8ClipArgs" in k["mangled"]]
+    assert len(clipped) == 2 and len(optim) == 18 and not any(k["kernel"].startswith("optim_kernel<1") for k in clipped)
+    assert sorted(k["kernel"] for k in clipped) == ["optim_kernel<0,0>", "optim_kernel<0,1>"], "with and without the EMA"
     norm = [k for k in rows if k["kernel"] in ("grad_sumsq_kernel", "grad_norm_eval_kernel")]
     assert len(norm) == 2
     for k in clipped + norm:
