@@ -142,6 +142,16 @@ class TrainCommand(AbstractCommand):
                             'step. The step then updates all parameters in one launch behind the last gradient instead of '
                             'per layer. "inf" measures the norm without clipping. Saved in the checkpoints; a resumed run must '
                             'give the same value. Not with --eager. Default: 0 (off).')
+        p.add_argument('--loss-weight', type=str, default='off', choices=['off', 'uniform', 'min-snr'],
+                       help='Diffusion models: weight each window\'s eps-MSE by its noise level inside the loss launch of the '
+                            'fused step. "min-snr" is Min-SNR-gamma (Hang et al. 2023), w_t = min(1, gamma / SNR_t) for '
+                            'eps-prediction; "uniform" optimises the unweighted loss through the same launches and exists '
+                            'for its report: the periodic report lines then show the unweighted eps-MSE beside the optimised '
+                            'loss and its mean per band of noise level. The bf16 MLP denoiser then leaves its one-launch chain '
+                            'kernel for the per-op step. Saved in the checkpoints; a resumed run must give the same value. '
+                            'Not with --eager. Default: off.')
+        p.add_argument('--min-snr-gamma', type=float, default=5.0,
+                       help='gamma of --loss-weight min-snr, > 0. Default: 5.')
 
     # ------------------------------------------------------------------------------------------
     def run(self, args: argparse.Namespace):
@@ -157,6 +167,7 @@ class TrainCommand(AbstractCommand):
         check_lr_schedule(args)
         check_weight_decay_args(args)
         check_max_grad_norm_args(args)
+        loss_weight = resolve_loss_weight(args)
         check_cond_cols(model_type, getattr(args, 'cond_cols', 0))
         check_cond_drop(args)
         check_record_range(args)
@@ -250,7 +261,10 @@ class TrainCommand(AbstractCommand):
                                  ema_warmup=not getattr(args, 'no_ema_warmup', False), cond_cols=cond_cols,
                                  cond_drop=cond_drop, lr_schedule=lr_schedule,
                                  weight_decay=getattr(args, 'weight_decay', 0.0),
-                                 max_grad_norm=getattr(args, 'max_grad_norm', 0.0))
+                                 max_grad_norm=getattr(args, 'max_grad_norm', 0.0), loss_weight=loss_weight)
+            if trainer.loss_weight is not None:
+                print(f"Loss weighting by noise level: {trainer.loss_weight}; the reports show the unweighted eps-MSE beside "
+                      f"the optimised loss, and its mean per band of noise level")
             if trainer.clip:
                 print(f"Gradient clipping: global L2 norm at most {trainer.max_grad_norm:g}, taken and applied on the device "
                       f"(one optimizer launch over the whole buffer per step)")
@@ -268,6 +282,9 @@ class TrainCommand(AbstractCommand):
             epoch_checkpoint, _ = self.load_latest_checkpoint(model, optimizer=trainer if trainer is not None else optimizer,
                                                               checkpoint_dir=checkpoint_dir)
         except HipError as exc:
+            if "loss weighting" in str(exc):
+                raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --loss-weight / --min-snr-gamma or use "
+                                 f"another --checkpoint-dir") from None
             if "gradient-norm clip" in str(exc):
                 raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --max-grad-norm or use another "
                                  f"--checkpoint-dir") from None
@@ -452,6 +469,12 @@ class TrainCommand(AbstractCommand):
                     train_eval.print_report(args, reset=False) if not diffusion else train_eval.print_report(reset=False)
                     if trainer is not None and trainer._sched_args():
                         print(f"[rank={rank}] learning rate {trainer.current_lr():.6g} at step {trainer.steps_done + 1}")
+                    if trainer is not None and trainer.loss_weight is not None:
+                        rep = trainer.level_loss(reset=True)        # since the last report line
+                        if rep["steps"]:
+                            print(f"[rank={rank}] optimised loss {rep['weighted']:.6g} ({trainer.loss_weight}), unweighted "
+                                  f"eps-MSE {rep['unweighted']:.6g} over {rep['steps']} steps")
+                            print(f"[rank={rank}] eps-MSE per noise-level band: {format_level_report(rep)}")
                     if trainer is not None and trainer.clip:
                         print(f"[rank={rank}] gradient norm {trainer.grad_norm():.6g}, clip coefficient {trainer.clip_coef():.6g}")
                     if rank == 0:
@@ -524,6 +547,32 @@ def check_max_grad_norm_args(args: argparse.Namespace):
         raise SystemExit(f"--max-grad-norm must be >= 0 and not NaN, got {x}")
     if x > 0 and getattr(args, 'eager', False):
         raise SystemExit("--max-grad-norm needs the fused trainer: --eager runs torch.optim with only the rate set")
+
+
+def resolve_loss_weight(args: argparse.Namespace):
+    """--loss-weight {off,uniform,min-snr} / --min-snr-gamma G -> a loss_weight.LossWeight, or None for off.  A diffusion model
+    type; the weight is applied inside the fused step's loss launch, so --eager (the evaluator's plain eps-MSE) has none"""
+    from ..loss_weight import LossWeight, check_gamma
+    kind = getattr(args, 'loss_weight', 'off') or 'off'
+    if kind == 'off':
+        return None
+    if not is_diffusion(args.model_type):
+        raise SystemExit(f"--loss-weight weights the diffusion loss by noise level: it needs a diffusion model type, got "
+                         f"{args.model_type}")
+    if getattr(args, 'eager', False):
+        raise SystemExit("--loss-weight needs the fused trainer: the weight is applied inside its loss launch, --eager has none")
+    if kind == 'uniform':
+        return LossWeight('uniform')
+    try:
+        return LossWeight('min_snr', gamma=check_gamma(getattr(args, 'min_snr_gamma', 5.0)))
+    except ValueError as exc:
+        raise SystemExit(f"--min-snr-gamma: {exc}") from None
+
+
+def format_level_report(rep: dict) -> str:
+    """one line of the band means of trainer.level_loss(): `t lo-hi mean` per band, `-` where no window fell in it"""
+    return "  ".join(f"t {lo}-{hi - 1} {'-' if mean is None else format(mean, '.6g')}" for lo, hi, mean in rep["bands"]
+                     if hi > lo)
 
 
 def check_lr_schedule(args: argparse.Namespace):

@@ -21,6 +21,7 @@ at construction (DDP ctor), optimizer arithmetic = torch.optim defaults with onl
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import weakref
 from collections import OrderedDict
@@ -37,6 +38,7 @@ from .lr_schedule import LrSchedule, active as active_schedule
 from .module import HipModule, flat_layout
 from .plans import ParamSource
 from .grad_norm import check_max_grad_norm
+from .loss_weight import LossWeight, band_edges
 from .weight_decay import check_weight_decay, decay_ranges, decayed_names
 
 
@@ -274,9 +276,14 @@ class HipTrainer:
     def __init__(self, model: HipModule, task: str, opt_type: str = "rmsprop", lr: float = 1e-4, args=None,
                  group=None, bucket_mb: float = 13.0, use_graph: bool = True, overlap_comm: Optional[bool] = None,
                  ema_decay: float = 0.0, ema_warmup: bool = True, cond_cols: int = 0, cond_drop: float = 0.0,
-                 lr_schedule=None, weight_decay: float = 0.0, decay_filter=None, max_grad_norm: float = 0.0):
+                 lr_schedule=None, weight_decay: float = 0.0, decay_filter=None, max_grad_norm: float = 0.0,
+                 loss_weight: Optional[LossWeight] = None):
         if task not in ("diffusion", "regression"):
             raise ValueError(task)
+        if loss_weight is not None and not isinstance(loss_weight, LossWeight):
+            raise ValueError(f"loss_weight must be None or a LossWeight, got {type(loss_weight).__name__}")
+        if loss_weight is not None and task != "diffusion":
+            raise ValueError(f"loss_weight weights the diffusion loss by noise level, got task '{task}'")
         if int(cond_cols) < 0 or (cond_cols and task != "diffusion"):
             raise ValueError(f"cond_cols must be >= 0 and is a diffusion-task setting, got {cond_cols} for task '{task}'")
         if not 0.0 <= float(cond_drop) <= 1.0:
@@ -410,6 +417,18 @@ class HipTrainer:
         self.clip = self.max_grad_norm > 0
         self.norm_slots = torch.zeros(hip.grad_sumsq_slots(flat.numel()), dtype=torch.float64, device=dev) if self.clip else None
         self.norm_stats = torch.zeros(4, dtype=torch.float32, device=dev) if self.clip else None    # {norm, coef, gs, -}
+        # The loss weighted by noise level (loss_weight.py, include/ib_hip_lossweight.h): the per-level table goes to the device
+        # once, the step's loss seam becomes the weighted pair of launches -- result[0], the loss the step reports, is then the
+        # weighted mean, result[1] the unweighted one -- and every finalize advances a float64 running total of the report
+        # (level_loss()) on the device.  None: nothing is allocated and the step launches what it always did.
+        self.loss_weight = loss_weight
+        self.level_table = self.level_accum = None
+        self._level_steps = 0
+        if loss_weight is not None:
+            loss_weight.check_levels(model.num_train_steps)
+            from .diffusion.schedule import alphas_cumprod
+            self.level_table = torch.from_numpy(loss_weight.weights(alphas_cumprod(model.num_train_steps))).to(dev)
+            self.level_accum = torch.zeros(2 + 2 * hip.LOSS_LEVEL_BUCKETS, dtype=torch.float64, device=dev)
         self.bucket_opt = bool(self.ddp and self.overlap_comm and self._flush_mode and not TU.no_bucket_opt and not self.clip)
         self._br_opt = Branch(dev, enabled=self.bucket_opt, name="bucket_opt")
         self._early_done: List[Tuple[int, int]] = []
@@ -516,7 +535,8 @@ class HipTrainer:
                 hip.diffusion_draw(self.noise_seed, step_dev=self.step_dev, stream_id=self.noise_stream, eps=eps, t=t,
                                    num_train_steps=m.num_train_steps, table=None if mc is None else mc.table,
                                    idx=st.get("widx"), x0=x0 if mc is not None else None)
-            if hasattr(plan, "chain_ok") and plan.chain_ok(D, C):
+            LW = self.loss_weight
+            if hasattr(plan, "chain_ok") and plan.chain_ok(D, C, weighted=LW is not None):
                 plan.fuse_reduce_into_optimizer = self._fuse_reduce()
                 # MLP denoiser, bf16: q_sample + forward + loss + the dgrad chain are ONE launch (csrc/chain.hip)
                 if self._slots is None:
@@ -560,13 +580,20 @@ class HipTrainer:
             else:
                 hip.q_sample(x0, eps, t, tabs.sqrt_ab, tabs.sqrt_1mab, xt)
             plan.forward(xt, t, tabs.temb, P, out=pred, BT=(B, T))
-            ws = plan.buf.bytes("tr.mse", hip.mse_loss_workspace_bytes(M * D))
             n = M * D
-            if C:
+            if LW is not None:
+                # weighted by each window's noise level, any C; the finalize also counts t per band and advances the report
+                ws = plan.buf.bytes("tr.mse_w", hip.mse_loss_weighted_workspace_bytes(n))
+                hip.mse_loss_weighted_partial(pred, eps.view(M, D), ws, t, self.level_table, T, cond_cols=C, dpred=dpred)
+                self._br_loss.run(lambda: hip.mse_loss_weighted_finalize(ws, self.result, t, self.level_table.numel(), n,
+                                                                         M * (D - C), accum=self.level_accum))
+            elif C:
                 # free columns only; dpred = 0 on the conditioning columns, rewritten every step
+                ws = plan.buf.bytes("tr.mse", hip.mse_loss_workspace_bytes(M * D))
                 hip.mse_loss_partial_cond(pred, eps.view(M, D), ws, C, dpred=dpred)
                 self._br_loss.run(lambda: hip.mse_loss_finalize_cond(ws, self.result, n, M * (D - C)))
             else:
+                ws = plan.buf.bytes("tr.mse", hip.mse_loss_workspace_bytes(M * D))
                 hip.mse_loss_partial(pred, eps, ws, dpred=dpred)          # dL/dpred + per-block partial sums
                 self._br_loss.run(lambda: hip.mse_loss_finalize(ws, self.result, n))   # the scalar: off the chain
             plan.backward(dpred, P, accumulate=False)
@@ -1034,6 +1061,8 @@ class HipTrainer:
             self._rec = self._capture(st)
             self._rec.replay()                  # the capture itself executed nothing
         self.steps_done += 1
+        if self.loss_weight is not None:
+            self._level_steps += 1              # counted once the step is issued: the steps in the device's running total
         return self.result[0]
 
     def pin_batches(self, batches) -> int:
@@ -1074,6 +1103,39 @@ class HipTrainer:
         """host readback of the last step's loss (synchronises)"""
         return float(self.result[0].cpu())
 
+    def level_loss(self, reset: bool = True) -> Dict:
+        """The report over the steps since the last reset, from the device's float64 running total (synchronises):
+        "weighted" the mean of the optimised loss, "unweighted" the mean of the plain eps-MSE over the same steps, "bands" a
+        list of (t_lo, t_hi, mean or None) per band of noise level -- mean = the band's sum of squared error / (its windows *
+        T * (D - C)), None where no window fell in it -- "windows" the window counts, "steps" the steps covered.  Under data
+        parallelism each rank reports its own windows.  reset: zero the total with a fill on the trainer's stream, between
+        two replays of the step's graph."""
+        if self.loss_weight is None:
+            raise hip.HipError("no level report is kept: this trainer was built without a loss_weight")
+        NB = hip.LOSS_LEVEL_BUCKETS
+        with (torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()):
+            tot = self.level_accum.cpu().tolist()        # stream-ordered behind the last step's finalize
+            if reset:
+                self.level_accum.zero_()
+        steps = self._level_steps
+        if reset:
+            self._level_steps = 0
+        x0 = self._static_shape("x0")
+        per_window = None if x0 is None else x0[1] * (x0[2] - self.cond_cols)
+        counts = [int(round(c)) for c in tot[2 + NB:2 + 2 * NB]]
+        bands = []
+        for (lo, hi), ssq, cnt in zip(band_edges(self.level_table.numel(), NB), tot[2:2 + NB], counts):
+            bands.append((lo, hi, ssq / (cnt * per_window) if cnt and per_window else None))
+        return {"weighted": tot[0] / steps if steps else None, "unweighted": tot[1] / steps if steps else None,
+                "bands": bands, "windows": counts, "steps": steps}
+
+    def _static_shape(self, name: str):
+        """shape of the trainer's static batch buffer `name` of the current step signature, None before the first step"""
+        for n, shape in (self._sig or ()):
+            if n == name:
+                return shape
+        return None
+
     def _norm_stat(self, k: int) -> float:
         if not self.clip:
             raise hip.HipError("no gradient norm is taken: this trainer was built with max_grad_norm = 0")
@@ -1095,12 +1157,14 @@ class HipTrainer:
     def optimizer_state_dict(self) -> Dict:
         """"lr" is the BASE rate; "lr_schedule" the schedule's four fields, or None without one (a constant schedule
         without warmup counts as none); "weight_decay" the fp32 decay and "decayed" the names it applies to (none at 0);
-        "max_grad_norm" the fp32 clipping norm (0: off, inf: measured only)"""
+        "max_grad_norm" the fp32 clipping norm (0: off, inf: measured only); "loss_weight" the kind, gamma and -- kind
+        'table' -- the table of the loss's weighting by noise level, or None without one"""
         sched = active_schedule(self.lr_schedule)
         return {"opt_type": self.opt_type, "lr": self.lr, "step": self.steps_done,
                 "lr_schedule": None if sched is None else sched.fields(),
                 "weight_decay": self.weight_decay, "decayed": list(self.decayed) if self.weight_decay > 0 else [],
                 "max_grad_norm": self.max_grad_norm,
+                "loss_weight": None if self.loss_weight is None else self.loss_weight.fields(),
                 "layout": {k: list(v) for k, v in self.layout.items()},
                 "s1": None if self.s1 is None else self.s1.detach().cpu(),
                 "s2": None if self.s2 is None else self.s2.detach().cpu()}
@@ -1141,6 +1205,10 @@ class HipTrainer:
         if theirs_mgn != self.max_grad_norm:
             raise hip.HipError(f"the checkpoint's gradient-norm clip ({theirs_mgn:g}) differs from this trainer's "
                                f"({self.max_grad_norm:g})")
+        theirs_lw = LossWeight.from_fields(sd.get("loss_weight"))    # a payload without the key is an older checkpoint: none
+        if theirs_lw != self.loss_weight:
+            raise hip.HipError(f"the checkpoint's loss weighting ({theirs_lw if theirs_lw else 'none'}) differs from this "
+                               f"trainer's ({self.loss_weight if self.loss_weight else 'none'})")
         if self.s1 is not None:
             self.s1.copy_(sd["s1"])
         if self.s2 is not None:

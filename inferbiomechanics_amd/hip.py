@@ -19,7 +19,8 @@ sampling step and the per-column range of a window table (csrc/clip.hip) in an e
 in a tenth, ``include/ib_hip_sched.h`` (``_SCHED_SIGS``), its decoupled weight decay in an eleventh,
 ``include/ib_hip_decay.h`` (``_DECAY_SIGS``), the slice rule of the whole-layer kernels' image sweep (csrc/image_sweep.h) in a
 twelfth, ``include/ib_hip_sweep.h`` (``_SWEEP_SIGS``), the optimizer's clipping to a global gradient norm in a thirteenth,
-``include/ib_hip_gradnorm.h`` (``_GRADNORM_SIGS``); a name may be declared once in the thirteen.
+``include/ib_hip_gradnorm.h`` (``_GRADNORM_SIGS``), the diffusion loss weighted by noise level (csrc/loss_weight.hip) in a
+fourteenth, ``include/ib_hip_lossweight.h`` (``_LOSSWEIGHT_SIGS``); a name may be declared once in the fourteen.
 """
 from __future__ import annotations
 
@@ -49,6 +50,7 @@ SCHED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sche
 DECAY_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_decay.h")
 SWEEP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sweep.h")
 GRADNORM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_gradnorm.h")
+LOSSWEIGHT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_lossweight.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -146,6 +148,15 @@ _GRADNORM_SIGS = _parse_header(_read_header(GRADNORM_HEADER_PATH))              
 _EXPORTS = {**_ENTRIES, **_GRADNORM_SIGS}
 if len(_EXPORTS) != len(_ENTRIES) + len(_GRADNORM_SIGS):
     raise HipError(f"declared in two headers: {sorted(n for n in _GRADNORM_SIGS if n in _ENTRIES)}")
+# the fourteenth header likewise: _EXPORTS stays the thirteen headers' as their tests pin it; _sig() and lib() go through _SYMBOLS
+_LOSSWEIGHT_SIGS = _parse_header(_read_header(LOSSWEIGHT_HEADER_PATH))              # the loss weighted by noise level, off by default
+_SYMBOLS = {**_EXPORTS, **_LOSSWEIGHT_SIGS}
+if len(_SYMBOLS) != len(_EXPORTS) + len(_LOSSWEIGHT_SIGS):
+    raise HipError(f"declared in two headers: {sorted(n for n in _LOSSWEIGHT_SIGS if n in _EXPORTS)}")
+_nb = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_LOSS_LEVEL_BUCKETS[ \t]+(\d+)[ \t]*$", _read_header(LOSSWEIGHT_HEADER_PATH), flags=re.M)
+if _nb is None:
+    raise HipError(f"{LOSSWEIGHT_HEADER_PATH} does not define IB_LOSS_LEVEL_BUCKETS")
+LOSS_LEVEL_BUCKETS = int(_nb.group(1))      # the header's value; loss_level_buckets() asks the library it was compiled into
 _kmax = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_STITCH_KMAX[ \t]+(\d+)[ \t]*$", _read_header(STITCH_HEADER_PATH), flags=re.M)
 if _kmax is None:
     raise HipError(f"{STITCH_HEADER_PATH} does not define IB_STITCH_KMAX")
@@ -219,14 +230,19 @@ def gradnorm_decls() -> List[str]:
     return sorted(_GRADNORM_SIGS)
 
 
+def lossweight_decls() -> List[str]:
+    """Every function include/ib_hip_lossweight.h declares"""
+    return sorted(_LOSSWEIGHT_SIGS)
+
+
 def _sig(name: str):
     """(restype, argtypes) of an entry point of any header"""
-    return _EXPORTS[name]
+    return _SYMBOLS[name]
 
 
 # pure host queries: no launch, no stream
 _HOST_ONLY = ("_workspace", "_supported", "_workgroups", "_packed_elems", "_partial_width", "_last_path", "_slab_count",
-              "_ticket_words", "_mask_bytes", "_table_bytes", "_sweep_slices")
+              "_ticket_words", "_mask_bytes", "_table_bytes", "_sweep_slices", "_level_buckets")
 _HOST_NAMES = ("ib_version", "ib_error_string")
 
 
@@ -497,7 +513,7 @@ def lib():
             raise HipError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C inferbiomechanics_amd/csrc` (hipcc --offload-arch=gfx950). There is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _EXPORTS.items():
+        for name, (res, args) in _SYMBOLS.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -1414,6 +1430,74 @@ def mse_loss_finalize_cond(workspace, result, n_launch: int, n_mean: int):
     wsb = workspace.numel() * workspace.element_size()
     _check(lib().ib_mse_loss_finalize_cond(_ptr(workspace), wsb, _ptr(result), n_launch, n_mean, stream_ptr()),
            "ib_mse_loss_finalize_cond")
+
+
+# ---- the loss weighted by noise level (include/ib_hip_lossweight.h, csrc/loss_weight.hip) ----
+def loss_level_buckets() -> int:
+    """the number of noise-level bands the library reports (IB_LOSS_LEVEL_BUCKETS as it was compiled)"""
+    return int(lib().ib_loss_level_buckets())
+
+
+def mse_loss_weighted_workspace_bytes(n) -> int:
+    return int(lib().ib_mse_loss_weighted_workspace(int(n)))
+
+
+def mse_loss_weighted_partial(pred, target, workspace, t, wtab, rows_per_window: int, cond_cols: int = 0, dpred=None):
+    """mse_loss_partial_cond with every row's squared error and gradient multiplied by wtab[t[row // rows_per_window]]: pred /
+    dpred are 2-D [rows, cols] (contiguous or row-padded), target contiguous, t int64 [rows / rows_per_window], wtab fp32
+    [n_levels].  The workspace (mse_loss_weighted_workspace_bytes(rows * cols)) receives per workgroup the weighted sum, the
+    unweighted sum and the unweighted sum per band of noise level; cond_cols = 0 runs the same kernel."""
+    dt = pred.dtype
+    rows, cols, ldp = _mat(pred, "pred", dt)
+    _req(target, "target", dt)
+    if not target.is_contiguous() or target.numel() != rows * cols:
+        raise HipError("mse_loss_weighted: target must be contiguous with rows * cols elements")
+    ldd = 0
+    if dpred is not None:
+        r2, c2, ldd = _mat(dpred, "dpred", dt)
+        if (r2, c2) != (rows, cols):
+            raise HipError("mse_loss_weighted: dpred shape mismatch")
+    rows_per_window, cond_cols = int(rows_per_window), int(cond_cols)
+    if rows_per_window < 1 or rows % rows_per_window:
+        raise HipError(f"mse_loss_weighted_partial: rows ({rows}) must be a multiple of rows_per_window ({rows_per_window})")
+    if not 0 <= cond_cols < cols:
+        raise HipError(f"mse_loss_weighted_partial: cond_cols must lie in [0, {cols}), got {cond_cols}")
+    _req(t, "t", torch.int64, 1)
+    _req(wtab, "wtab", torch.float32, 1)
+    if not t.is_contiguous() or t.numel() != rows // rows_per_window:
+        raise HipError(f"mse_loss_weighted_partial: t must be a contiguous int64 vector of {rows // rows_per_window} windows")
+    if not wtab.is_contiguous() or wtab.numel() < 1:
+        raise HipError("mse_loss_weighted_partial: wtab must be a non-empty contiguous fp32 vector")
+    wsb = workspace.numel() * workspace.element_size()
+    if wsb < mse_loss_weighted_workspace_bytes(rows * cols):
+        raise HipError("mse_loss_weighted: workspace too small")
+    _check(lib().ib_mse_loss_weighted_partial(_ptr(pred), ldp, _ptr(target), _ptr(dpred), ldd, _ptr(t), _ptr(wtab),
+                                              wtab.numel(), rows_per_window, _ptr(workspace), wsb, rows, cols, cond_cols,
+                                              dtype_code(dt), stream_ptr()), "ib_mse_loss_weighted_partial")
+
+
+def mse_loss_weighted_finalize(workspace, result, t, n_levels: int, n_launch: int, n_mean: int, accum=None):
+    """result, fp32 [2 + 2 NB]: {weighted mean, unweighted mean, NB band sums of squared error, NB window counts of t};
+    accum (float64 [2 + 2 NB], optional) += the same.  n_launch = rows * cols of the partial launch, n_mean = rows * (cols -
+    cond_cols)"""
+    nres = 2 + 2 * LOSS_LEVEL_BUCKETS
+    _req(result, "result", torch.float32)
+    if result.numel() < nres or not result.is_contiguous():
+        raise HipError(f"mse_loss_weighted_finalize: result must hold {nres} contiguous fp32 values")
+    _req(t, "t", torch.int64, 1)
+    if not t.is_contiguous() or t.numel() < 1:
+        raise HipError("mse_loss_weighted_finalize: t must be a non-empty contiguous int64 vector")
+    if accum is not None:
+        _req(accum, "accum", torch.float64)
+        if accum.numel() < nres or not accum.is_contiguous():
+            raise HipError(f"mse_loss_weighted_finalize: accum must hold {nres} contiguous float64 values")
+    n_levels, n_launch, n_mean = int(n_levels), int(n_launch), int(n_mean)
+    if n_levels < 1 or not 0 < n_mean <= n_launch:
+        raise HipError(f"mse_loss_weighted_finalize: n_levels >= 1 and 0 < n_mean <= n_launch required, got {n_levels}, "
+                       f"{n_mean}, {n_launch}")
+    wsb = workspace.numel() * workspace.element_size()
+    _check(lib().ib_mse_loss_weighted_finalize(_ptr(workspace), wsb, _ptr(t), t.numel(), n_levels, _ptr(result), _ptr(accum),
+                                               n_launch, n_mean, stream_ptr()), "ib_mse_loss_weighted_finalize")
 
 
 # --------------------------------------------------------------------------------------------

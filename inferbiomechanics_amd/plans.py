@@ -1256,10 +1256,11 @@ class DenoiserMLPPlan:
 
 
     # ---- fused chain: q_sample + forward + loss + dgrad chain in ONE launch (csrc/chain.hip) ------------------
-    def chain_ok(self, D: int, cond_cols: int = 0) -> bool:
+    def chain_ok(self, D: int, cond_cols: int = 0, weighted: bool = False) -> bool:
         # cond_cols > 0 (a denoiser conditioned on its first columns): the chain kernel noises and scores every column, so
-        # the conditional step takes the per-op path
-        if TU.no_chain or cond_cols or self.dtype != torch.bfloat16 or not self.hidden:
+        # the conditional step takes the per-op path.  weighted (a loss weighted by noise level): the chain kernel scores
+        # every row alike, so that step takes the per-op path too
+        if TU.no_chain or cond_cols or weighted or self.dtype != torch.bfloat16 or not self.hidden:
             return False
         H = self.hidden[0]
         return all(h == H for h in self.hidden) and hip.mlp_chain_supported(D, H, len(self.hidden))
