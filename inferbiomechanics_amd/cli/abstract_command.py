@@ -153,6 +153,8 @@ class AbstractCommand:
             target.cond_cols = int(checkpoint.get('cond_cols', 0))
         if hasattr(target, 'cond_drop'):                     # denoisers: `train --cond-drop`
             target.cond_drop = float(checkpoint.get('cond_drop', 0.0))
+        if hasattr(target, 'prediction'):                    # denoisers: `train --prediction`; no key: an eps model
+            target.prediction = str(checkpoint.get('prediction', 'eps'))
         if hasattr(target, 'column_range'):                  # denoisers: `train --record-range`
             r = checkpoint.get('column_range')
             target.column_range = None if r is None else torch.as_tensor(r, dtype=torch.float32).cpu()

@@ -152,6 +152,14 @@ class TrainCommand(AbstractCommand):
                             'Not with --eager. Default: off.')
         p.add_argument('--min-snr-gamma', type=float, default=5.0,
                        help='gamma of --loss-weight min-snr, > 0. Default: 5.')
+        p.add_argument('--prediction', type=str, default='eps', choices=['eps', 'x0', 'v'],
+                       help='Diffusion models: what the denoiser predicts. "eps" is the noise; "x0" the clean window; "v" is '
+                            'sqrt(ab) eps - sqrt(1 - ab) x0 (Salimans & Ho 2022). With x0 or v the target is formed inside the '
+                            'loss launch of the fused step, the samplers convert the output into a noise prediction with one '
+                            'more launch per step, --loss-weight min-snr takes the form of that prediction, and the reports keep '
+                            'showing the eps-MSE, overall and per band of noise level. The bf16 MLP denoiser then leaves its '
+                            'one-launch chain kernel for the per-op step. Saved in the checkpoints; a resumed run must give the '
+                            'same value. Not with --eager. Default: eps.')
 
     # ------------------------------------------------------------------------------------------
     def run(self, args: argparse.Namespace):
@@ -168,6 +176,7 @@ class TrainCommand(AbstractCommand):
         check_weight_decay_args(args)
         check_max_grad_norm_args(args)
         loss_weight = resolve_loss_weight(args)
+        prediction = resolve_prediction(args)
         check_cond_cols(model_type, getattr(args, 'cond_cols', 0))
         check_cond_drop(args)
         check_record_range(args)
@@ -234,6 +243,7 @@ class TrainCommand(AbstractCommand):
             check_cond_cols(model_type, cond_cols, feat_dim=model.feat_dim)
             model.cond_cols = cond_cols
             model.cond_drop = cond_drop
+            model.prediction = prediction
             train_eval, dev_eval = DiffusionLossEvaluator('train', cond_cols), DiffusionLossEvaluator(DEV, cond_cols)
         else:
             train_eval = RegressionLossEvaluator(dataset=train_dataset, split='train', device=device)
@@ -261,7 +271,11 @@ class TrainCommand(AbstractCommand):
                                  ema_warmup=not getattr(args, 'no_ema_warmup', False), cond_cols=cond_cols,
                                  cond_drop=cond_drop, lr_schedule=lr_schedule,
                                  weight_decay=getattr(args, 'weight_decay', 0.0),
-                                 max_grad_norm=getattr(args, 'max_grad_norm', 0.0), loss_weight=loss_weight)
+                                 max_grad_norm=getattr(args, 'max_grad_norm', 0.0), loss_weight=loss_weight,
+                                 prediction=prediction)
+            if trainer.prediction != 'eps':
+                print(f"The denoiser predicts {trainer.prediction}; the reports show the eps-MSE its output implies beside the "
+                      f"optimised loss, and its mean per band of noise level")
             if trainer.loss_weight is not None:
                 print(f"Loss weighting by noise level: {trainer.loss_weight}; the reports show the unweighted eps-MSE beside "
                       f"the optimised loss, and its mean per band of noise level")
@@ -285,6 +299,9 @@ class TrainCommand(AbstractCommand):
             if "loss weighting" in str(exc):
                 raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --loss-weight / --min-snr-gamma or use "
                                  f"another --checkpoint-dir") from None
+            if "checkpoint's prediction" in str(exc):
+                raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --prediction or use another "
+                                 f"--checkpoint-dir") from None
             if "gradient-norm clip" in str(exc):
                 raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --max-grad-norm or use another "
                                  f"--checkpoint-dir") from None
@@ -299,6 +316,9 @@ class TrainCommand(AbstractCommand):
         if diffusion and model.cond_cols != cond_cols:       # the checkpoint's value: a resumed run keeps training that model
             raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained with --cond-cols {model.cond_cols}, this run "
                              f"asks for {cond_cols}: resume with the same value or use another --checkpoint-dir")
+        if diffusion and model.prediction != prediction:
+            raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained with --prediction {model.prediction}, this run "
+                             f"asks for {prediction}: resume with the same value or use another --checkpoint-dir")
         if diffusion and model.cond_drop != cond_drop:
             raise SystemExit(f"the checkpoint in {checkpoint_dir} was trained with --cond-drop {model.cond_drop}, this run "
                              f"asks for {cond_drop}: resume with the same value or use another --checkpoint-dir")
@@ -406,7 +426,10 @@ class TrainCommand(AbstractCommand):
                         tabs = model.tables(device)
                         xt = torch.empty_like(xd)
                         noise_batch(xd, ed, td, tabs, xt)
-                        dev_eval(model(xt, td), ed)
+                        out = model(xt, td)
+                        if prediction != 'eps':      # the report stays the eps-MSE: the noise prediction the output implies
+                            hip.pred_to_eps(xt, out, td, tabs.sqrt_ab, tabs.sqrt_1mab, tabs.inv_sqrt_1mab, prediction)
+                        dev_eval(out, ed)
                     else:
                         inputs, labels, subj, trial = batch
                         dev_eval(inputs, model(inputs), labels, subj, trial, args, compute_report=args.compute_report)
@@ -469,10 +492,12 @@ class TrainCommand(AbstractCommand):
                     train_eval.print_report(args, reset=False) if not diffusion else train_eval.print_report(reset=False)
                     if trainer is not None and trainer._sched_args():
                         print(f"[rank={rank}] learning rate {trainer.current_lr():.6g} at step {trainer.steps_done + 1}")
-                    if trainer is not None and trainer.loss_weight is not None:
+                    if trainer is not None and trainer.level_accum is not None:
                         rep = trainer.level_loss(reset=True)        # since the last report line
                         if rep["steps"]:
-                            print(f"[rank={rank}] optimised loss {rep['weighted']:.6g} ({trainer.loss_weight}), unweighted "
+                            how = trainer.loss_weight if trainer.loss_weight is not None else "unweighted"
+                            how = how if trainer.prediction == "eps" else f"{trainer.prediction}-prediction, {how}"
+                            print(f"[rank={rank}] optimised loss {rep['weighted']:.6g} ({how}), unweighted "
                                   f"eps-MSE {rep['unweighted']:.6g} over {rep['steps']} steps")
                             print(f"[rank={rank}] eps-MSE per noise-level band: {format_level_report(rep)}")
                     if trainer is not None and trainer.clip:
@@ -567,6 +592,20 @@ def resolve_loss_weight(args: argparse.Namespace):
         return LossWeight('min_snr', gamma=check_gamma(getattr(args, 'min_snr_gamma', 5.0)))
     except ValueError as exc:
         raise SystemExit(f"--min-snr-gamma: {exc}") from None
+
+
+def resolve_prediction(args: argparse.Namespace) -> str:
+    """--prediction {eps,x0,v}.  x0 / v need a diffusion model type and the fused trainer: the target is formed inside its loss
+    launch, --eager (the evaluator's plain eps-MSE) has none"""
+    kind = getattr(args, 'prediction', 'eps') or 'eps'
+    if kind == 'eps':
+        return kind
+    if not is_diffusion(args.model_type):
+        raise SystemExit(f"--prediction sets what a diffusion denoiser predicts: it needs a diffusion model type, got "
+                         f"{args.model_type}")
+    if getattr(args, 'eager', False):
+        raise SystemExit("--prediction needs the fused trainer: the target is formed inside its loss launch, --eager has none")
+    return kind
 
 
 def format_level_report(rep: dict) -> str:
@@ -667,9 +706,10 @@ def save_checkpoint(checkpoint_dir: str, epoch: int, batch: int, model, opt):
     """file grammar of train.py:271-278; keys are saved WITHOUT DDP's `module.` prefix.  A trainer with an EMA adds
     'ema_state_dict' (the model's state dict over the EMA weights) and 'ema' ({'decay', 'warmup'}); without one the file
     holds the three reference keys only.  A denoiser trained with --cond-cols N > 0 adds 'cond_cols': N, one trained with
-    --cond-drop P > 0 'cond_drop': P, one trained with --record-range 'column_range': fp32 [feat_dim, 2], one trained with
-    --standardize 'column_stats': fp32 [feat_dim, 2] = per column (mean, scale).  With both, column_range is taken over the
-    standardised table: it is in the units the sampler works in, the units of the x0 clip's bounds."""
+    --cond-drop P > 0 'cond_drop': P, one trained with --prediction x0 / v 'prediction': the kind, one trained with
+    --record-range 'column_range': fp32 [feat_dim, 2], one trained with --standardize 'column_stats': fp32 [feat_dim, 2] =
+    per column (mean, scale).  With both, column_range is taken over the standardised table: it is in the units the sampler
+    works in, the units of the x0 clip's bounds."""
     os.makedirs(checkpoint_dir, exist_ok=True)
     path = f"{checkpoint_dir}/epoch_{epoch}_batch_{batch}.pt"
     osd = opt.optimizer_state_dict() if hasattr(opt, 'optimizer_state_dict') else opt.state_dict()
@@ -680,6 +720,8 @@ def save_checkpoint(checkpoint_dir: str, epoch: int, batch: int, model, opt):
         ckpt['cond_cols'] = int(model.cond_cols)
     if getattr(model, 'cond_drop', 0.0) > 0:
         ckpt['cond_drop'] = float(model.cond_drop)
+    if getattr(model, 'prediction', 'eps') != 'eps':
+        ckpt['prediction'] = str(model.prediction)
     if getattr(model, 'column_range', None) is not None:
         ckpt['column_range'] = torch.as_tensor(model.column_range, dtype=torch.float32).detach().cpu().clone()
     if getattr(model, 'column_stats', None) is not None:

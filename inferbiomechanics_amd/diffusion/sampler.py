@@ -65,7 +65,16 @@ layouts, resampling and the second-order solvers' history follow by themselves. 
 overlapping window on its own, before the update kernel blends the predictions.  Observed elements (the mask), columns
 without finite bounds hi > lo and pad columns are never counted and never changed.  With None no buffer, launch or
 signature entry exists: the loop is the unclipped one bit for bit and launch for launch.  What the clip does to label
-accuracy on trained checkpoints is unmeasured."""
+accuracy on trained checkpoints is unmeasured.
+
+What the model predicts (model.prediction: 'eps', 'x0' or 'v'; prediction.py, `train --prediction`; all four classes) is one
+more seam of the same kind: every row above takes a noise prediction, so for an x0 / v model one launch (ib_pred_to_eps,
+csrc/predict.hip) directly after the forward -- in the guided step after ib_cfg_combine, over the first half: the conversion
+is affine in the output with the same x_t on the free columns and the guidance weights sum to 1, so the two commute up to
+rounding -- rewrites the output into the noise prediction it implies at the windows' levels t_vec, before the clip and the
+update.  Solvers, eta, stitching, resampling, the clip and standardisation follow unchanged.  The kind is part of the
+signature.  For 'eps' no launch, table or signature entry exists.  What x0 / v prediction does to label accuracy on trained
+checkpoints is unmeasured."""
 from dataclasses import dataclass
 from typing import Optional, Sequence, Union
 
@@ -73,6 +82,7 @@ import torch
 
 from .. import hip
 from ..plans import ParamSource
+from ..prediction import check_kind
 from .schedule import (CLIP_MODES, OBSERVATIONS, check_resample, check_sampler_settings, clip_rank, clip_tables,
                        resample_walk, stitch_layout)
 
@@ -324,6 +334,8 @@ class DDIMSampler:
         if clip is not None:
             # the launch bakes in the mode, the rank (a function of the call's mask and the bounds) and the tables' addresses
             sig += ("x0_clip", self.x0_clip.mode, clip["k"]) + tuple(ptr(clip[n]) for n in ("coef", "lo", "hi", "m", "h", "ih"))
+        if self._prediction() != "eps":
+            sig += ("prediction", self._prediction(), ptr(tabs.inv_sqrt_1mab))   # one more launch per step, by kind
         guided = self._guided(c)
         if guided:
             # the seam's launches bake in the strength, the conditioning width and xin's address.  xin belongs to the
@@ -396,6 +408,19 @@ class DDIMSampler:
         else:
             hip.x0_clip_dynamic(x3, e3, mask, clip["lo"], clip["hi"], clip["coef"], clip["m"], clip["h"], clip["ih"], clip["k"],
                                 step_dev=ctr, D=c.D)
+
+    def _prediction(self) -> str:
+        """what the model's output approximates (prediction.py): 'eps' unless the model says otherwise"""
+        return check_kind(getattr(self.model, "prediction", "eps"))
+
+    def _launch_convert(self, c: SampleCall, x, out, t_vec, tabs):
+        """an x0 / v model's output becomes the noise prediction every launch after it expects (ib_pred_to_eps), over the B
+        windows of x / out as [B, T, ld] at the levels t_vec; nothing for an eps model"""
+        kind = self._prediction()
+        if kind == "eps":
+            return
+        hip.pred_to_eps(x.view(c.B, c.T, -1), out.view(c.B, c.T, -1), t_vec, tabs.sqrt_ab, tabs.sqrt_1mab, tabs.inv_sqrt_1mab,
+                        kind, D=c.D)
 
     def _start_masked(self, c: SampleCall, x, tabs):
         """the masked loop's start state, once x holds the start draw: the observation, the mask and the draw z go into
@@ -524,6 +549,7 @@ class DDIMSampler:
             plan.forward(xin.view(B2 * T, Dp)[:, :c.D], t_vec, tabs.temb, P, out=eps_buf.view(B2 * T, Dp)[:, :c.D],
                          BT=(B2, T))
             hip.cfg_combine(eps_buf, self.guidance)
+            self._launch_convert(c, x, eps_buf[:c.B], t_vec[:c.B], tabs)
             self._launch_clip(c, x, eps_buf[:c.B], ctr, tabs)
             self._launch_update(c, x, eps_buf[:c.B], ctr, t_vec[:c.B], tabs)
             hip.cfg_mirror(xin, t_vec, int(self.model.cond_cols), D=c.D)
@@ -532,10 +558,12 @@ class DDIMSampler:
             # 2-D views; the DDIM update runs over the whole pitched buffers (0 stays 0 in the pad columns)
             B, T, Dp = x.shape
             plan.forward(x.view(B * T, Dp)[:, :c.D], t_vec, tabs.temb, P, out=eps_buf.view(B * T, Dp)[:, :c.D], BT=(B, T))
+            self._launch_convert(c, x, eps_buf, t_vec, tabs)
             self._launch_clip(c, x, eps_buf, ctr, tabs)
             self._launch_update(c, x, eps_buf, ctr, t_vec, tabs)
         else:
             eps = plan.forward(x, t_vec, tabs.temb, P)
+            self._launch_convert(c, x, eps, t_vec, tabs)
             self._launch_clip(c, x, eps, ctr, tabs)
             self._launch_update(c, x, eps, ctr, t_vec, tabs)
         hip.counter_add(ctr, 1)

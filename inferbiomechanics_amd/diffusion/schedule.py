@@ -449,10 +449,19 @@ class DiffusionTables:
         self.alphas_cumprod64 = ab
         self.sqrt_ab = torch.sqrt(ab).to(torch.float32).to(device)
         self.sqrt_1mab = torch.sqrt(1.0 - ab).to(torch.float32).to(device)
+        self._inv_sqrt_1mab = None
         self.temb = timestep_embedding_table(num_train_steps, temb_dim).to(torch.float32).to(device).contiguous()
         self.observations = "noised"
         self.set_sampler(num_sample_steps)
         self.device = device
+
+    @property
+    def inv_sqrt_1mab(self):
+        """1 / sqrt(1 - ab) in float64, cast once: what hip.pred_to_eps multiplies by under x0-prediction.  Made when first
+        asked for, so an eps model allocates nothing"""
+        if self._inv_sqrt_1mab is None:
+            self._inv_sqrt_1mab = (1.0 / torch.sqrt(1.0 - self.alphas_cumprod64)).to(torch.float32).to(self.sqrt_ab.device)
+        return self._inv_sqrt_1mab
 
     def set_sampler(self, num_sample_steps: int, eta: float = 0.0, solver: str = "ddim", spacing: str = "time",
                     observations: str = "noised"):

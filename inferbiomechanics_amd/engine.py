@@ -39,6 +39,7 @@ from .module import HipModule, flat_layout
 from .plans import ParamSource
 from .grad_norm import check_max_grad_norm
 from .loss_weight import LossWeight, band_edges
+from .prediction import check_kind, eps_units
 from .weight_decay import check_weight_decay, decay_ranges, decayed_names
 
 
@@ -277,9 +278,12 @@ class HipTrainer:
                  group=None, bucket_mb: float = 13.0, use_graph: bool = True, overlap_comm: Optional[bool] = None,
                  ema_decay: float = 0.0, ema_warmup: bool = True, cond_cols: int = 0, cond_drop: float = 0.0,
                  lr_schedule=None, weight_decay: float = 0.0, decay_filter=None, max_grad_norm: float = 0.0,
-                 loss_weight: Optional[LossWeight] = None):
+                 loss_weight: Optional[LossWeight] = None, prediction: str = "eps"):
         if task not in ("diffusion", "regression"):
             raise ValueError(task)
+        check_kind(prediction)
+        if prediction != "eps" and task != "diffusion":
+            raise ValueError(f"prediction '{prediction}' is what a diffusion denoiser predicts, got task '{task}'")
         if loss_weight is not None and not isinstance(loss_weight, LossWeight):
             raise ValueError(f"loss_weight must be None or a LossWeight, got {type(loss_weight).__name__}")
         if loss_weight is not None and task != "diffusion":
@@ -424,10 +428,27 @@ class HipTrainer:
         self.loss_weight = loss_weight
         self.level_table = self.level_accum = None
         self._level_steps = 0
-        if loss_weight is not None:
-            loss_weight.check_levels(model.num_train_steps)
+        # What the denoiser predicts (prediction.py, include/ib_hip_predict.h).  'x0' / 'v': the loss seam is
+        # ib_mse_loss_pred_partial, which forms the target in registers, with the weighted finalize -- the weight table is ones
+        # without a loss_weight, units_table keeps result[1] and the band sums the eps-MSE, and the report is always kept.  The
+        # bf16 MLP denoiser then takes the per-op step, as under a loss_weight: the chain kernel scores eps alone.  'eps':
+        # nothing is allocated and the step launches what it always did.
+        self.prediction = prediction
+        if getattr(model, "prediction", "eps") not in ("eps", prediction):
+            raise ValueError(f"the model predicts '{model.prediction}', this trainer was asked for '{prediction}'")
+        if prediction != "eps":
+            model.prediction = prediction            # the samplers convert the model's output by it
+        self.units_table = None
+        if loss_weight is not None or prediction != "eps":
             from .diffusion.schedule import alphas_cumprod
-            self.level_table = torch.from_numpy(loss_weight.weights(alphas_cumprod(model.num_train_steps))).to(dev)
+            ab = alphas_cumprod(model.num_train_steps)
+            if loss_weight is not None:
+                loss_weight.check_levels(model.num_train_steps)
+                self.level_table = torch.from_numpy(loss_weight.weights(ab, prediction)).to(dev)
+            else:
+                self.level_table = torch.ones(model.num_train_steps, dtype=torch.float32, device=dev)
+            if prediction != "eps":
+                self.units_table = torch.from_numpy(eps_units(ab, prediction)).to(dev)
             self.level_accum = torch.zeros(2 + 2 * hip.LOSS_LEVEL_BUCKETS, dtype=torch.float64, device=dev)
         self.bucket_opt = bool(self.ddp and self.overlap_comm and self._flush_mode and not TU.no_bucket_opt and not self.clip)
         self._br_opt = Branch(dev, enabled=self.bucket_opt, name="bucket_opt")
@@ -535,8 +556,8 @@ class HipTrainer:
                 hip.diffusion_draw(self.noise_seed, step_dev=self.step_dev, stream_id=self.noise_stream, eps=eps, t=t,
                                    num_train_steps=m.num_train_steps, table=None if mc is None else mc.table,
                                    idx=st.get("widx"), x0=x0 if mc is not None else None)
-            LW = self.loss_weight
-            if hasattr(plan, "chain_ok") and plan.chain_ok(D, C, weighted=LW is not None):
+            LW, kind = self.loss_weight, self.prediction
+            if hasattr(plan, "chain_ok") and plan.chain_ok(D, C, weighted=LW is not None or kind != "eps"):
                 plan.fuse_reduce_into_optimizer = self._fuse_reduce()
                 # MLP denoiser, bf16: q_sample + forward + loss + the dgrad chain are ONE launch (csrc/chain.hip)
                 if self._slots is None:
@@ -581,7 +602,14 @@ class HipTrainer:
                 hip.q_sample(x0, eps, t, tabs.sqrt_ab, tabs.sqrt_1mab, xt)
             plan.forward(xt, t, tabs.temb, P, out=pred, BT=(B, T))
             n = M * D
-            if LW is not None:
+            if kind != "eps":
+                # the target ('x0': x0, 'v': sqrt_ab eps - sqrt_1mab x0) is formed inside the launch; the weighted finalize
+                ws = plan.buf.bytes("tr.mse_w", hip.mse_loss_weighted_workspace_bytes(n))
+                hip.mse_loss_pred_partial(pred, x0.view(M, D), eps.view(M, D), ws, t, self.level_table, self.units_table,
+                                          tabs.sqrt_ab, tabs.sqrt_1mab, T, kind, cond_cols=C, dpred=dpred)
+                self._br_loss.run(lambda: hip.mse_loss_weighted_finalize(ws, self.result, t, self.level_table.numel(), n,
+                                                                         M * (D - C), accum=self.level_accum))
+            elif LW is not None:
                 # weighted by each window's noise level, any C; the finalize also counts t per band and advances the report
                 ws = plan.buf.bytes("tr.mse_w", hip.mse_loss_weighted_workspace_bytes(n))
                 hip.mse_loss_weighted_partial(pred, eps.view(M, D), ws, t, self.level_table, T, cond_cols=C, dpred=dpred)
@@ -1025,6 +1053,8 @@ class HipTrainer:
             sig += (("cond_cols", self.cond_cols),)     # chooses the step's launches: part of what a captured graph is
         if self.cond_drop > 0.0:
             sig += (("cond_drop", self.cond_drop),)     # the drop threshold is an argument the captured launch bakes in
+        if self.prediction != "eps":
+            sig += (("prediction", self.prediction),)   # chooses the loss launch and its target
         if sig != self._sig:
             self._sig, self._rec, self._warm = sig, None, 0
             self._pinned, self._seen = {}, {}
@@ -1061,7 +1091,7 @@ class HipTrainer:
             self._rec = self._capture(st)
             self._rec.replay()                  # the capture itself executed nothing
         self.steps_done += 1
-        if self.loss_weight is not None:
+        if self.level_accum is not None:
             self._level_steps += 1              # counted once the step is issued: the steps in the device's running total
         return self.result[0]
 
@@ -1110,8 +1140,8 @@ class HipTrainer:
         T * (D - C)), None where no window fell in it -- "windows" the window counts, "steps" the steps covered.  Under data
         parallelism each rank reports its own windows.  reset: zero the total with a fill on the trainer's stream, between
         two replays of the step's graph."""
-        if self.loss_weight is None:
-            raise hip.HipError("no level report is kept: this trainer was built without a loss_weight")
+        if self.level_accum is None:
+            raise hip.HipError("no level report is kept: this trainer was built without a loss_weight, for eps-prediction")
         NB = hip.LOSS_LEVEL_BUCKETS
         with (torch.cuda.stream(self.stream) if self.stream is not None else contextlib.nullcontext()):
             tot = self.level_accum.cpu().tolist()        # stream-ordered behind the last step's finalize
@@ -1158,16 +1188,20 @@ class HipTrainer:
         """"lr" is the BASE rate; "lr_schedule" the schedule's four fields, or None without one (a constant schedule
         without warmup counts as none); "weight_decay" the fp32 decay and "decayed" the names it applies to (none at 0);
         "max_grad_norm" the fp32 clipping norm (0: off, inf: measured only); "loss_weight" the kind, gamma and -- kind
-        'table' -- the table of the loss's weighting by noise level, or None without one"""
+        'table' -- the table of the loss's weighting by noise level, or None without one; "prediction" what the denoiser
+        predicts, present only when it is not 'eps'"""
         sched = active_schedule(self.lr_schedule)
-        return {"opt_type": self.opt_type, "lr": self.lr, "step": self.steps_done,
-                "lr_schedule": None if sched is None else sched.fields(),
-                "weight_decay": self.weight_decay, "decayed": list(self.decayed) if self.weight_decay > 0 else [],
-                "max_grad_norm": self.max_grad_norm,
-                "loss_weight": None if self.loss_weight is None else self.loss_weight.fields(),
-                "layout": {k: list(v) for k, v in self.layout.items()},
-                "s1": None if self.s1 is None else self.s1.detach().cpu(),
-                "s2": None if self.s2 is None else self.s2.detach().cpu()}
+        sd = {"opt_type": self.opt_type, "lr": self.lr, "step": self.steps_done,
+              "lr_schedule": None if sched is None else sched.fields(),
+              "weight_decay": self.weight_decay, "decayed": list(self.decayed) if self.weight_decay > 0 else [],
+              "max_grad_norm": self.max_grad_norm,
+              "loss_weight": None if self.loss_weight is None else self.loss_weight.fields(),
+              "layout": {k: list(v) for k, v in self.layout.items()},
+              "s1": None if self.s1 is None else self.s1.detach().cpu(),
+              "s2": None if self.s2 is None else self.s2.detach().cpu()}
+        if self.prediction != "eps":
+            sd["prediction"] = self.prediction
+        return sd
 
     def torch_optimizer_state_dict(self) -> Dict:
         """the same state in torch.optim's own grammar ({'state': {i: {...}}, 'param_groups': [...]}, parameters numbered
@@ -1209,6 +1243,9 @@ class HipTrainer:
         if theirs_lw != self.loss_weight:
             raise hip.HipError(f"the checkpoint's loss weighting ({theirs_lw if theirs_lw else 'none'}) differs from this "
                                f"trainer's ({self.loss_weight if self.loss_weight else 'none'})")
+        theirs_kind = sd.get("prediction", "eps")                    # a payload without the key: an eps model's
+        if theirs_kind != self.prediction:
+            raise hip.HipError(f"the checkpoint's prediction ({theirs_kind}) differs from this trainer's ({self.prediction})")
         if self.s1 is not None:
             self.s1.copy_(sd["s1"])
         if self.s2 is not None:

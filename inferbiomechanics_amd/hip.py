@@ -20,7 +20,9 @@ in a tenth, ``include/ib_hip_sched.h`` (``_SCHED_SIGS``), its decoupled weight d
 ``include/ib_hip_decay.h`` (``_DECAY_SIGS``), the slice rule of the whole-layer kernels' image sweep (csrc/image_sweep.h) in a
 twelfth, ``include/ib_hip_sweep.h`` (``_SWEEP_SIGS``), the optimizer's clipping to a global gradient norm in a thirteenth,
 ``include/ib_hip_gradnorm.h`` (``_GRADNORM_SIGS``), the diffusion loss weighted by noise level (csrc/loss_weight.hip) in a
-fourteenth, ``include/ib_hip_lossweight.h`` (``_LOSSWEIGHT_SIGS``); a name may be declared once in the fourteen.
+fourteenth, ``include/ib_hip_lossweight.h`` (``_LOSSWEIGHT_SIGS``), what the denoiser predicts -- eps, x0 or v
+(csrc/predict.hip) -- in a fifteenth, ``include/ib_hip_predict.h`` (``_PREDICT_SIGS``); a name may be declared once in the
+fifteen.
 """
 from __future__ import annotations
 
@@ -51,6 +53,7 @@ DECAY_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_deca
 SWEEP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_sweep.h")
 GRADNORM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_gradnorm.h")
 LOSSWEIGHT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_lossweight.h")
+PREDICT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_predict.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -153,6 +156,11 @@ _LOSSWEIGHT_SIGS = _parse_header(_read_header(LOSSWEIGHT_HEADER_PATH))          
 _SYMBOLS = {**_EXPORTS, **_LOSSWEIGHT_SIGS}
 if len(_SYMBOLS) != len(_EXPORTS) + len(_LOSSWEIGHT_SIGS):
     raise HipError(f"declared in two headers: {sorted(n for n in _LOSSWEIGHT_SIGS if n in _EXPORTS)}")
+# the fifteenth header likewise: _SYMBOLS stays the fourteen headers' as their tests pin it; _sig() and lib() go through _DECLARED
+_PREDICT_SIGS = _parse_header(_read_header(PREDICT_HEADER_PATH))                    # x0 / v prediction, eps by default
+_DECLARED = {**_SYMBOLS, **_PREDICT_SIGS}
+if len(_DECLARED) != len(_SYMBOLS) + len(_PREDICT_SIGS):
+    raise HipError(f"declared in two headers: {sorted(n for n in _PREDICT_SIGS if n in _SYMBOLS)}")
 _nb = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_LOSS_LEVEL_BUCKETS[ \t]+(\d+)[ \t]*$", _read_header(LOSSWEIGHT_HEADER_PATH), flags=re.M)
 if _nb is None:
     raise HipError(f"{LOSSWEIGHT_HEADER_PATH} does not define IB_LOSS_LEVEL_BUCKETS")
@@ -235,9 +243,14 @@ def lossweight_decls() -> List[str]:
     return sorted(_LOSSWEIGHT_SIGS)
 
 
+def predict_decls() -> List[str]:
+    """Every function include/ib_hip_predict.h declares"""
+    return sorted(_PREDICT_SIGS)
+
+
 def _sig(name: str):
     """(restype, argtypes) of an entry point of any header"""
-    return _SYMBOLS[name]
+    return _DECLARED[name]
 
 
 # pure host queries: no launch, no stream
@@ -513,7 +526,7 @@ def lib():
             raise HipError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C inferbiomechanics_amd/csrc` (hipcc --offload-arch=gfx950). There is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SYMBOLS.items():
+        for name, (res, args) in _DECLARED.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -1498,6 +1511,76 @@ def mse_loss_weighted_finalize(workspace, result, t, n_levels: int, n_launch: in
     wsb = workspace.numel() * workspace.element_size()
     _check(lib().ib_mse_loss_weighted_finalize(_ptr(workspace), wsb, _ptr(t), t.numel(), n_levels, _ptr(result), _ptr(accum),
                                                n_launch, n_mean, stream_ptr()), "ib_mse_loss_weighted_finalize")
+
+
+# ---- what the denoiser predicts: eps, x0 or v (include/ib_hip_predict.h, csrc/predict.hip) ----
+PRED_KINDS = {"eps": 0, "x0": 1, "v": 2}
+
+
+def _level_table(tab, name: str, n_levels: Optional[int] = None):
+    _req(tab, name, torch.float32, 1)
+    if not tab.is_contiguous() or tab.numel() < 1 or (n_levels is not None and tab.numel() != n_levels):
+        raise HipError(f"{name} must be a contiguous fp32 vector of {'n_levels' if n_levels is None else n_levels} entries")
+
+
+def mse_loss_pred_partial(pred, x0, eps, workspace, t, wtab, utab, sqrt_ab, sqrt_1mab, rows_per_window: int, kind: str,
+                          cond_cols: int = 0, dpred=None):
+    """mse_loss_weighted_partial with the target formed per element from x0, eps and the row's noise level -- kind 'eps': eps,
+    'x0': x0, 'v': sqrt_ab eps - sqrt_1mab x0 -- and the reported sums multiplied by utab[t] (prediction.eps_units64: they
+    stay the eps-MSE).  x0 / eps contiguous with rows * cols elements, the four tables fp32 [n_levels].  The workspace and the
+    finalize are the weighted entry's (mse_loss_weighted_workspace_bytes, mse_loss_weighted_finalize)."""
+    if kind not in PRED_KINDS:
+        raise HipError(f"mse_loss_pred_partial: kind must be one of {tuple(PRED_KINDS)}, got {kind!r}")
+    dt = pred.dtype
+    rows, cols, ldp = _mat(pred, "pred", dt)
+    for ten, name in ((x0, "x0"), (eps, "eps")):
+        _req(ten, name, dt)
+        if not ten.is_contiguous() or ten.numel() != rows * cols:
+            raise HipError(f"mse_loss_pred_partial: {name} must be contiguous with rows * cols elements")
+    ldd = 0
+    if dpred is not None:
+        r2, c2, ldd = _mat(dpred, "dpred", dt)
+        if (r2, c2) != (rows, cols):
+            raise HipError("mse_loss_pred_partial: dpred shape mismatch")
+    rows_per_window, cond_cols = int(rows_per_window), int(cond_cols)
+    if rows_per_window < 1 or rows % rows_per_window:
+        raise HipError(f"mse_loss_pred_partial: rows ({rows}) must be a multiple of rows_per_window ({rows_per_window})")
+    if not 0 <= cond_cols < cols:
+        raise HipError(f"mse_loss_pred_partial: cond_cols must lie in [0, {cols}), got {cond_cols}")
+    _req(t, "t", torch.int64, 1)
+    if not t.is_contiguous() or t.numel() != rows // rows_per_window:
+        raise HipError(f"mse_loss_pred_partial: t must be a contiguous int64 vector of {rows // rows_per_window} windows")
+    _level_table(wtab, "wtab")
+    for tab, name in ((utab, "utab"), (sqrt_ab, "sqrt_ab"), (sqrt_1mab, "sqrt_1mab")):
+        _level_table(tab, name, wtab.numel())
+    wsb = workspace.numel() * workspace.element_size()
+    if wsb < mse_loss_weighted_workspace_bytes(rows * cols):
+        raise HipError("mse_loss_pred_partial: workspace too small")
+    _check(lib().ib_mse_loss_pred_partial(_ptr(pred), ldp, _ptr(x0), _ptr(eps), _ptr(dpred), ldd, _ptr(t), _ptr(wtab),
+                                          _ptr(utab), _ptr(sqrt_ab), _ptr(sqrt_1mab), wtab.numel(), rows_per_window,
+                                          _ptr(workspace), wsb, rows, cols, cond_cols, PRED_KINDS[kind], dtype_code(dt),
+                                          stream_ptr()), "ib_mse_loss_pred_partial")
+
+
+def pred_to_eps(x, out, t, sqrt_ab, sqrt_1mab, inv_sqrt_1mab, kind: str, D=None):
+    """Rewrite `out`, the network's outputs of kind 'x0' or 'v' at the state `x`, into noise predictions, in place.  x (read)
+    and out: contiguous [B, T, ld] of one dtype; the first D columns (default ld) are features, the rest padding that is never
+    written.  t: int64 [B], the level of each window; the tables fp32 [n_levels] (DiffusionTables).  'eps' is refused: there
+    is nothing to launch."""
+    if kind not in ("x0", "v"):
+        raise HipError(f"pred_to_eps: kind must be 'x0' or 'v', got {kind!r} (an eps model launches nothing)")
+    B, T, D, ld = _pitched_state("pred_to_eps", x, D)
+    _like_x("pred_to_eps", "out", out, x)
+    _req(t, "t", torch.int64, 1)
+    if not t.is_contiguous() or t.numel() != B:
+        raise HipError(f"pred_to_eps: t must be a contiguous int64 vector of {B} windows")
+    _level_table(sqrt_ab, "sqrt_ab")
+    for tab, name in ((sqrt_1mab, "sqrt_1mab"), (inv_sqrt_1mab, "inv_sqrt_1mab")):
+        _level_table(tab, name, sqrt_ab.numel())
+    _check(lib().ib_pred_to_eps(_ptr(x), _ptr(out), _ptr(t), _ptr(sqrt_ab), _ptr(sqrt_1mab), _ptr(inv_sqrt_1mab),
+                                sqrt_ab.numel(), PRED_KINDS[kind], B, T, D, ld, dtype_code(x.dtype), stream_ptr()),
+           "ib_pred_to_eps")
+    return out
 
 
 # --------------------------------------------------------------------------------------------

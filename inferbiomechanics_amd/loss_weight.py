@@ -7,6 +7,10 @@ table on the host, in float64, cast to fp32 once.
     'min_snr'   w_t = min(1, gamma / snr_t)          Min-SNR-gamma (Hang et al. 2023) for eps-prediction: min(snr, gamma) / snr
     'table'     w_t = the caller's [n_levels] values, finite and >= 0
 
+A weight multiplies the squared error of what the network predicts (prediction.py).  'uniform' and 'table' mean the same under
+every prediction kind; Min-SNR-gamma is min(snr, gamma) divided by the SNR-weight the kind's own squared error already carries
+relative to the x0 error: min(snr, gamma) / snr for eps, min(snr, gamma) for x0, min(snr, gamma) / (snr + 1) for v.
+
 The optimised loss is mean(w_t (eps_hat - eps)^2), a plain mean: it is not divided by the sum of the weights.  Beside it the
 kernels report the unweighted error, overall and per band of noise level: level t of n_levels falls in band
 t * LEVEL_BUCKETS // n_levels (level_band)."""
@@ -74,7 +78,9 @@ class LossWeight:
         if self.table is not None and self.table.size != int(n_levels):
             raise ValueError(f"the weight table has {self.table.size} entries, the model {int(n_levels)} noise levels")
 
-    def weights64(self, alpha_bar) -> np.ndarray:
+    def weights64(self, alpha_bar, prediction: str = "eps") -> np.ndarray:
+        if prediction not in ("eps", "x0", "v"):
+            raise ValueError(f"prediction must be one of ('eps', 'x0', 'v'), got {prediction!r}")
         ab = np.asarray(alpha_bar.detach().cpu().numpy() if hasattr(alpha_bar, "detach") else alpha_bar, dtype=np.float64)
         if ab.ndim != 1 or ab.size < 1:
             raise ValueError(f"alpha_bar must be a non-empty vector, got shape {ab.shape}")
@@ -86,11 +92,15 @@ class LossWeight:
         if not np.all((ab > 0) & (ab < 1)):
             raise ValueError("alpha_bar must lie in (0, 1) for an SNR")
         snr = ab / (1.0 - ab)
+        if prediction == "x0":
+            return np.minimum(snr, self.gamma)
+        if prediction == "v":
+            return np.minimum(snr, self.gamma) / (snr + 1.0)
         return np.minimum(1.0, self.gamma / snr)
 
-    def weights(self, alpha_bar) -> np.ndarray:
+    def weights(self, alpha_bar, prediction: str = "eps") -> np.ndarray:
         """fp32 [n_levels]: what goes to the device"""
-        return self.weights64(alpha_bar).astype(np.float32)
+        return self.weights64(alpha_bar, prediction).astype(np.float32)
 
     # ---- checkpoint payload
     def fields(self) -> dict:

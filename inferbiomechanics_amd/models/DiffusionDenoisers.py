@@ -27,6 +27,10 @@ class _DenoiserBase(HipModule):
         # the share of training windows whose conditioning columns were all zero, the null condition of classifier-free
         # guidance (`train --cond-drop`; saved in the checkpoint).  0: the model never saw it and cannot be guided.
         self.cond_drop = 0.0
+        # what the network's output approximates: 'eps' (the noise), 'x0' (the clean window) or 'v' (prediction.py; `train
+        # --prediction`; saved in the checkpoint when not 'eps').  Not a parameter of the network either: the trainer forms its
+        # target by it and the samplers convert the output into a noise prediction by it (hip.pred_to_eps).
+        self.prediction = 'eps'
         # fp32 [feat_dim, 2]: the (minimum, maximum) every column takes in the training windows (`train --record-range`; saved
         # in the checkpoint), what `analyze --x0-clip` / `visualize --x0-clip` take their bounds from.  None: not recorded.
         self.column_range = None
