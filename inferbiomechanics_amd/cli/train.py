@@ -160,6 +160,16 @@ class TrainCommand(AbstractCommand):
                             'showing the eps-MSE, overall and per band of noise level. The bf16 MLP denoiser then leaves its '
                             'one-launch chain kernel for the per-op step. Saved in the checkpoints; a resumed run must give the '
                             'same value. Not with --eager. Default: eps.')
+        p.add_argument('--velocity-loss', type=float, default=0.0,
+                       help='Diffusion models: weight LAMBDA > 0 of a velocity term in the loss, the squared error of the '
+                            'frame-to-frame difference of the predicted clean window (the geometric loss of MDM, Tevet et al. '
+                            '2023), weighted per noise level by min(SNR_t, gamma). It is computed inside the loss launch of '
+                            'the fused step under every --prediction; the report lines show the term and the velocity error in '
+                            'x0 units beside the other numbers. The bf16 MLP denoiser then leaves its one-launch chain kernel '
+                            'for the per-op step. Saved in the checkpoints; a resumed run must give the same value. Not with '
+                            '--eager. Default: 0 (off).')
+        p.add_argument('--velocity-gamma', type=float, default=5.0,
+                       help='gamma of --velocity-loss, > 0; inf weights by the plain SNR. Default: 5.')
 
     # ------------------------------------------------------------------------------------------
     def run(self, args: argparse.Namespace):
@@ -177,6 +187,7 @@ class TrainCommand(AbstractCommand):
         check_max_grad_norm_args(args)
         loss_weight = resolve_loss_weight(args)
         prediction = resolve_prediction(args)
+        velocity_loss = resolve_velocity_loss(args)
         check_cond_cols(model_type, getattr(args, 'cond_cols', 0))
         check_cond_drop(args)
         check_record_range(args)
@@ -272,7 +283,10 @@ class TrainCommand(AbstractCommand):
                                  cond_drop=cond_drop, lr_schedule=lr_schedule,
                                  weight_decay=getattr(args, 'weight_decay', 0.0),
                                  max_grad_norm=getattr(args, 'max_grad_norm', 0.0), loss_weight=loss_weight,
-                                 prediction=prediction)
+                                 prediction=prediction, velocity_loss=velocity_loss)
+            if trainer.velocity_loss is not None:
+                print(f"Velocity loss on the predicted x0: {trainer.velocity_loss}; the reports show the term and the velocity "
+                      f"error in x0 units beside the optimised loss")
             if trainer.prediction != 'eps':
                 print(f"The denoiser predicts {trainer.prediction}; the reports show the eps-MSE its output implies beside the "
                       f"optimised loss, and its mean per band of noise level")
@@ -302,6 +316,9 @@ class TrainCommand(AbstractCommand):
             if "checkpoint's prediction" in str(exc):
                 raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --prediction or use another "
                                  f"--checkpoint-dir") from None
+            if "checkpoint's velocity loss" in str(exc):
+                raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --velocity-loss / --velocity-gamma or use "
+                                 f"another --checkpoint-dir") from None
             if "gradient-norm clip" in str(exc):
                 raise SystemExit(f"{checkpoint_dir}: {exc}. Resume with the same --max-grad-norm or use another "
                                  f"--checkpoint-dir") from None
@@ -500,6 +517,11 @@ class TrainCommand(AbstractCommand):
                             print(f"[rank={rank}] optimised loss {rep['weighted']:.6g} ({how}), unweighted "
                                   f"eps-MSE {rep['unweighted']:.6g} over {rep['steps']} steps")
                             print(f"[rank={rank}] eps-MSE per noise-level band: {format_level_report(rep)}")
+                            if trainer.velocity_loss is not None:
+                                print(f"[rank={rank}] weighted MSE term {rep['mse']:.6g}, velocity term {rep['velocity']:.6g} "
+                                      f"({trainer.velocity_loss}), x0 velocity error {rep['x0_velocity']:.6g}")
+                                print(f"[rank={rank}] x0 velocity error per noise-level band: "
+                                      f"{format_level_report({'bands': rep['x0_velocity_bands']})}")
                     if trainer is not None and trainer.clip:
                         print(f"[rank={rank}] gradient norm {trainer.grad_norm():.6g}, clip coefficient {trainer.clip_coef():.6g}")
                     if rank == 0:
@@ -606,6 +628,24 @@ def resolve_prediction(args: argparse.Namespace) -> str:
     if getattr(args, 'eager', False):
         raise SystemExit("--prediction needs the fused trainer: the target is formed inside its loss launch, --eager has none")
     return kind
+
+
+def resolve_velocity_loss(args: argparse.Namespace):
+    """--velocity-loss LAMBDA / --velocity-gamma G -> a velocity_loss.VelocityLoss, or None for 0 (off).  A diffusion model
+    type; the term is computed inside the fused step's loss launch, so --eager (the evaluator's plain eps-MSE) has none"""
+    lam = getattr(args, 'velocity_loss', 0.0) or 0.0
+    if lam == 0.0:
+        return None
+    if not is_diffusion(args.model_type):
+        raise SystemExit(f"--velocity-loss scores the frame differences of a diffusion denoiser's predicted x0: it needs a "
+                         f"diffusion model type, got {args.model_type}")
+    if getattr(args, 'eager', False):
+        raise SystemExit("--velocity-loss needs the fused trainer: the term is computed inside its loss launch, --eager has none")
+    from ..velocity_loss import VelocityLoss
+    try:
+        return VelocityLoss(lam, gamma=getattr(args, 'velocity_gamma', 5.0))
+    except ValueError as exc:
+        raise SystemExit(f"--velocity-loss / --velocity-gamma: {exc}") from None
 
 
 def format_level_report(rep: dict) -> str:

@@ -40,6 +40,7 @@ from .plans import ParamSource
 from .grad_norm import check_max_grad_norm
 from .loss_weight import LossWeight, band_edges
 from .prediction import check_kind, eps_units
+from .velocity_loss import VelocityLoss
 from .weight_decay import check_weight_decay, decay_ranges, decayed_names
 
 
@@ -278,7 +279,8 @@ class HipTrainer:
                  group=None, bucket_mb: float = 13.0, use_graph: bool = True, overlap_comm: Optional[bool] = None,
                  ema_decay: float = 0.0, ema_warmup: bool = True, cond_cols: int = 0, cond_drop: float = 0.0,
                  lr_schedule=None, weight_decay: float = 0.0, decay_filter=None, max_grad_norm: float = 0.0,
-                 loss_weight: Optional[LossWeight] = None, prediction: str = "eps"):
+                 loss_weight: Optional[LossWeight] = None, prediction: str = "eps",
+                 velocity_loss: Optional[VelocityLoss] = None):
         if task not in ("diffusion", "regression"):
             raise ValueError(task)
         check_kind(prediction)
@@ -288,6 +290,13 @@ class HipTrainer:
             raise ValueError(f"loss_weight must be None or a LossWeight, got {type(loss_weight).__name__}")
         if loss_weight is not None and task != "diffusion":
             raise ValueError(f"loss_weight weights the diffusion loss by noise level, got task '{task}'")
+        if velocity_loss is not None and not isinstance(velocity_loss, VelocityLoss):
+            raise ValueError(f"velocity_loss must be None or a VelocityLoss, got {type(velocity_loss).__name__}")
+        if velocity_loss is not None and task != "diffusion":
+            raise ValueError(f"velocity_loss scores the frame differences of a diffusion denoiser's predicted x0, got task "
+                             f"'{task}'")
+        if velocity_loss is not None and getattr(model, "window", 2) < 2:
+            raise ValueError(f"velocity_loss needs windows of at least 2 frames, the model's have {model.window}")
         if int(cond_cols) < 0 or (cond_cols and task != "diffusion"):
             raise ValueError(f"cond_cols must be >= 0 and is a diffusion-task setting, got {cond_cols} for task '{task}'")
         if not 0.0 <= float(cond_drop) <= 1.0:
@@ -438,8 +447,15 @@ class HipTrainer:
             raise ValueError(f"the model predicts '{model.prediction}', this trainer was asked for '{prediction}'")
         if prediction != "eps":
             model.prediction = prediction            # the samplers convert the model's output by it
+        # A velocity term on the predicted x0 (velocity_loss.py, include/ib_hip_velocity.h): the loss seam is
+        # ib_vel_loss_partial with its own finalize, under every prediction kind and with or without a loss_weight -- result[0]
+        # is the optimised total, and the report gains the two terms and the velocity error in x0 units (level_loss()).  The
+        # bf16 MLP denoiser takes the per-op step, as under every other loss option.  None: nothing is allocated and the step
+        # launches what it always did.
+        self.velocity_loss = velocity_loss
+        self.vel_table = self.vel_units_table = None
         self.units_table = None
-        if loss_weight is not None or prediction != "eps":
+        if loss_weight is not None or prediction != "eps" or velocity_loss is not None:
             from .diffusion.schedule import alphas_cumprod
             ab = alphas_cumprod(model.num_train_steps)
             if loss_weight is not None:
@@ -447,9 +463,15 @@ class HipTrainer:
                 self.level_table = torch.from_numpy(loss_weight.weights(ab, prediction)).to(dev)
             else:
                 self.level_table = torch.ones(model.num_train_steps, dtype=torch.float32, device=dev)
-            if prediction != "eps":
+            if prediction != "eps" or velocity_loss is not None:
                 self.units_table = torch.from_numpy(eps_units(ab, prediction)).to(dev)
-            self.level_accum = torch.zeros(2 + 2 * hip.LOSS_LEVEL_BUCKETS, dtype=torch.float64, device=dev)
+            n_report = 2 + 2 * hip.LOSS_LEVEL_BUCKETS
+            if velocity_loss is not None:
+                velocity_loss.check_levels(model.num_train_steps)
+                vtab, xtab = velocity_loss.tables(ab, prediction)
+                self.vel_table, self.vel_units_table = torch.from_numpy(vtab).to(dev), torch.from_numpy(xtab).to(dev)
+                n_report = hip.VEL_RESULT_LEN        # the same places first, then the two terms and the x0-unit error
+            self.level_accum = torch.zeros(n_report, dtype=torch.float64, device=dev)
         self.bucket_opt = bool(self.ddp and self.overlap_comm and self._flush_mode and not TU.no_bucket_opt and not self.clip)
         self._br_opt = Branch(dev, enabled=self.bucket_opt, name="bucket_opt")
         self._early_done: List[Tuple[int, int]] = []
@@ -556,8 +578,10 @@ class HipTrainer:
                 hip.diffusion_draw(self.noise_seed, step_dev=self.step_dev, stream_id=self.noise_stream, eps=eps, t=t,
                                    num_train_steps=m.num_train_steps, table=None if mc is None else mc.table,
                                    idx=st.get("widx"), x0=x0 if mc is not None else None)
-            LW, kind = self.loss_weight, self.prediction
-            if hasattr(plan, "chain_ok") and plan.chain_ok(D, C, weighted=LW is not None or kind != "eps"):
+            LW, kind, VL = self.loss_weight, self.prediction, self.velocity_loss
+            if VL is not None and T < 2:
+                raise ValueError(f"velocity_loss needs windows of at least 2 frames, got {T}")
+            if hasattr(plan, "chain_ok") and plan.chain_ok(D, C, weighted=LW is not None or kind != "eps" or VL is not None):
                 plan.fuse_reduce_into_optimizer = self._fuse_reduce()
                 # MLP denoiser, bf16: q_sample + forward + loss + the dgrad chain are ONE launch (csrc/chain.hip)
                 if self._slots is None:
@@ -602,7 +626,16 @@ class HipTrainer:
                 hip.q_sample(x0, eps, t, tabs.sqrt_ab, tabs.sqrt_1mab, xt)
             plan.forward(xt, t, tabs.temb, P, out=pred, BT=(B, T))
             n = M * D
-            if kind != "eps":
+            if VL is not None:
+                # every kind, with or without a weight: the target is formed inside the launch, which walks each window's
+                # frames for the velocity term; its own finalize reports the total, the two terms and the x0-unit error
+                ws = plan.buf.bytes("tr.vel", hip.vel_loss_workspace_bytes(M, D, T))
+                hip.vel_loss_partial(pred, x0.view(M, D), eps.view(M, D), ws, t, self.level_table, self.units_table,
+                                     self.vel_table, self.vel_units_table, tabs.sqrt_ab, tabs.sqrt_1mab, T, kind, cond_cols=C,
+                                     dpred=dpred)
+                self._br_loss.run(lambda: hip.vel_loss_finalize(ws, self.result, t, self.level_table.numel(), M, D, C, T,
+                                                                accum=self.level_accum))
+            elif kind != "eps":
                 # the target ('x0': x0, 'v': sqrt_ab eps - sqrt_1mab x0) is formed inside the launch; the weighted finalize
                 ws = plan.buf.bytes("tr.mse_w", hip.mse_loss_weighted_workspace_bytes(n))
                 hip.mse_loss_pred_partial(pred, x0.view(M, D), eps.view(M, D), ws, t, self.level_table, self.units_table,
@@ -1055,6 +1088,8 @@ class HipTrainer:
             sig += (("cond_drop", self.cond_drop),)     # the drop threshold is an argument the captured launch bakes in
         if self.prediction != "eps":
             sig += (("prediction", self.prediction),)   # chooses the loss launch and its target
+        if self.velocity_loss is not None:
+            sig += (("velocity_loss", self.velocity_loss.weight),)     # chooses the loss launch
         if sig != self._sig:
             self._sig, self._rec, self._warm = sig, None, 0
             self._pinned, self._seen = {}, {}
@@ -1156,8 +1191,20 @@ class HipTrainer:
         bands = []
         for (lo, hi), ssq, cnt in zip(band_edges(self.level_table.numel(), NB), tot[2:2 + NB], counts):
             bands.append((lo, hi, ssq / (cnt * per_window) if cnt and per_window else None))
-        return {"weighted": tot[0] / steps if steps else None, "unweighted": tot[1] / steps if steps else None,
-                "bands": bands, "windows": counts, "steps": steps}
+        rep = {"weighted": tot[0] / steps if steps else None, "unweighted": tot[1] / steps if steps else None,
+               "bands": bands, "windows": counts, "steps": steps}
+        if self.velocity_loss is not None:
+            # "weighted" is then the optimised total; "mse" the weighted MSE term of it, "velocity" the velocity term,
+            # "x0_velocity" the squared error of the predicted x0's frame difference and "x0_velocity_bands" the same per band
+            # of noise level: (t_lo, t_hi, the band's sum / (its windows * (T - 1) * (D - C)) or None)
+            per_window_v = None if x0 is None else (x0[1] - 1) * (x0[2] - self.cond_cols)
+            mean = lambda k: tot[k] / steps if steps else None
+            rep.update({"mse": mean(hip.VEL_R_MSE), "velocity": mean(hip.VEL_R_VEL), "x0_velocity": mean(hip.VEL_R_X0),
+                        "x0_velocity_bands": [(lo, hi, ssq / (cnt * per_window_v) if cnt and per_window_v else None)
+                                              for (lo, hi), ssq, cnt in zip(band_edges(self.level_table.numel(), NB),
+                                                                            tot[hip.VEL_R_X0_BANDS:hip.VEL_R_X0_BANDS + NB],
+                                                                            counts)]})
+        return rep
 
     def _static_shape(self, name: str):
         """shape of the trainer's static batch buffer `name` of the current step signature, None before the first step"""
@@ -1189,7 +1236,8 @@ class HipTrainer:
         without warmup counts as none); "weight_decay" the fp32 decay and "decayed" the names it applies to (none at 0);
         "max_grad_norm" the fp32 clipping norm (0: off, inf: measured only); "loss_weight" the kind, gamma and -- kind
         'table' -- the table of the loss's weighting by noise level, or None without one; "prediction" what the denoiser
-        predicts, present only when it is not 'eps'"""
+        predicts, present only when it is not 'eps'; "velocity_loss" the weight, gamma and table of the velocity term, present
+        only with one"""
         sched = active_schedule(self.lr_schedule)
         sd = {"opt_type": self.opt_type, "lr": self.lr, "step": self.steps_done,
               "lr_schedule": None if sched is None else sched.fields(),
@@ -1201,6 +1249,8 @@ class HipTrainer:
               "s2": None if self.s2 is None else self.s2.detach().cpu()}
         if self.prediction != "eps":
             sd["prediction"] = self.prediction
+        if self.velocity_loss is not None:
+            sd["velocity_loss"] = self.velocity_loss.fields()
         return sd
 
     def torch_optimizer_state_dict(self) -> Dict:
@@ -1246,6 +1296,10 @@ class HipTrainer:
         theirs_kind = sd.get("prediction", "eps")                    # a payload without the key: an eps model's
         if theirs_kind != self.prediction:
             raise hip.HipError(f"the checkpoint's prediction ({theirs_kind}) differs from this trainer's ({self.prediction})")
+        theirs_vl = VelocityLoss.from_fields(sd.get("velocity_loss"))    # a payload without the key: no velocity term
+        if theirs_vl != self.velocity_loss:
+            raise hip.HipError(f"the checkpoint's velocity loss ({theirs_vl if theirs_vl else 'none'}) differs from this "
+                               f"trainer's ({self.velocity_loss if self.velocity_loss else 'none'})")
         if self.s1 is not None:
             self.s1.copy_(sd["s1"])
         if self.s2 is not None:

@@ -21,8 +21,9 @@ in a tenth, ``include/ib_hip_sched.h`` (``_SCHED_SIGS``), its decoupled weight d
 twelfth, ``include/ib_hip_sweep.h`` (``_SWEEP_SIGS``), the optimizer's clipping to a global gradient norm in a thirteenth,
 ``include/ib_hip_gradnorm.h`` (``_GRADNORM_SIGS``), the diffusion loss weighted by noise level (csrc/loss_weight.hip) in a
 fourteenth, ``include/ib_hip_lossweight.h`` (``_LOSSWEIGHT_SIGS``), what the denoiser predicts -- eps, x0 or v
-(csrc/predict.hip) -- in a fifteenth, ``include/ib_hip_predict.h`` (``_PREDICT_SIGS``); a name may be declared once in the
-fifteen.
+(csrc/predict.hip) -- in a fifteenth, ``include/ib_hip_predict.h`` (``_PREDICT_SIGS``), the velocity term of the diffusion
+loss (csrc/velocity.hip) in a sixteenth, ``include/ib_hip_velocity.h`` (``_VELOCITY_SIGS``); a name may be declared once in
+the sixteen.
 """
 from __future__ import annotations
 
@@ -54,6 +55,7 @@ SWEEP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_swee
 GRADNORM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_gradnorm.h")
 LOSSWEIGHT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_lossweight.h")
 PREDICT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_predict.h")
+VELOCITY_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "ib_hip_velocity.h")
 
 F32, BF16 = 0, 1
 ACT = {"none": 0, "identity": 0, None: 0, "relu": 1, "tanh": 2, "sigmoid": 3, "silu": 4, "elu": 5}
@@ -161,6 +163,11 @@ _PREDICT_SIGS = _parse_header(_read_header(PREDICT_HEADER_PATH))                
 _DECLARED = {**_SYMBOLS, **_PREDICT_SIGS}
 if len(_DECLARED) != len(_SYMBOLS) + len(_PREDICT_SIGS):
     raise HipError(f"declared in two headers: {sorted(n for n in _PREDICT_SIGS if n in _SYMBOLS)}")
+# the sixteenth header likewise: _DECLARED stays the fifteen headers' as their tests pin it; _sig() and lib() go through _BINDINGS
+_VELOCITY_SIGS = _parse_header(_read_header(VELOCITY_HEADER_PATH))                  # the loss's velocity term, off by default
+_BINDINGS = {**_DECLARED, **_VELOCITY_SIGS}
+if len(_BINDINGS) != len(_DECLARED) + len(_VELOCITY_SIGS):
+    raise HipError(f"declared in two headers: {sorted(n for n in _VELOCITY_SIGS if n in _DECLARED)}")
 _nb = re.search(r"^[ \t]*#[ \t]*define[ \t]+IB_LOSS_LEVEL_BUCKETS[ \t]+(\d+)[ \t]*$", _read_header(LOSSWEIGHT_HEADER_PATH), flags=re.M)
 if _nb is None:
     raise HipError(f"{LOSSWEIGHT_HEADER_PATH} does not define IB_LOSS_LEVEL_BUCKETS")
@@ -248,14 +255,19 @@ def predict_decls() -> List[str]:
     return sorted(_PREDICT_SIGS)
 
 
+def velocity_decls() -> List[str]:
+    """Every function include/ib_hip_velocity.h declares"""
+    return sorted(_VELOCITY_SIGS)
+
+
 def _sig(name: str):
     """(restype, argtypes) of an entry point of any header"""
-    return _DECLARED[name]
+    return _BINDINGS[name]
 
 
 # pure host queries: no launch, no stream
 _HOST_ONLY = ("_workspace", "_supported", "_workgroups", "_packed_elems", "_partial_width", "_last_path", "_slab_count",
-              "_ticket_words", "_mask_bytes", "_table_bytes", "_sweep_slices", "_level_buckets")
+              "_ticket_words", "_mask_bytes", "_table_bytes", "_sweep_slices", "_level_buckets", "_frame_chunk")
 _HOST_NAMES = ("ib_version", "ib_error_string")
 
 
@@ -526,7 +538,7 @@ def lib():
             raise HipError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C inferbiomechanics_amd/csrc` (hipcc --offload-arch=gfx950). There is no fallback path.")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _DECLARED.items():
+        for name, (res, args) in _BINDINGS.items():
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -1581,6 +1593,99 @@ def pred_to_eps(x, out, t, sqrt_ab, sqrt_1mab, inv_sqrt_1mab, kind: str, D=None)
                                 sqrt_ab.numel(), PRED_KINDS[kind], B, T, D, ld, dtype_code(x.dtype), stream_ptr()),
            "ib_pred_to_eps")
     return out
+
+
+# ---- the velocity term of the diffusion loss (include/ib_hip_velocity.h, csrc/velocity.hip) ----
+def _vel_define(name: str) -> int:
+    m = re.search(rf"^[ \t]*#[ \t]*define[ \t]+{name}[ \t]+(\d+)[ \t]*$", _read_header(VELOCITY_HEADER_PATH), flags=re.M)
+    if m is None:
+        raise HipError(f"{VELOCITY_HEADER_PATH} does not define {name}")
+    return int(m.group(1))
+
+
+VEL_FRAME_CHUNK = _vel_define("IB_VEL_FRAME_CHUNK")     # the header's value; vel_loss_frame_chunk() asks the library
+# the places of ib_vel_loss_finalize's result, as the header's IB_VEL_R_* spell them
+VEL_R_TOTAL, VEL_R_EPS, VEL_R_BANDS, VEL_R_COUNTS = 0, 1, 2, 2 + LOSS_LEVEL_BUCKETS
+VEL_R_MSE, VEL_R_VEL, VEL_R_X0 = 2 + 2 * LOSS_LEVEL_BUCKETS, 3 + 2 * LOSS_LEVEL_BUCKETS, 4 + 2 * LOSS_LEVEL_BUCKETS
+VEL_R_X0_BANDS = 5 + 2 * LOSS_LEVEL_BUCKETS
+VEL_RESULT_LEN = 5 + 3 * LOSS_LEVEL_BUCKETS
+
+
+def vel_loss_frame_chunk() -> int:
+    """frames per chunk of ib_vel_loss_partial (IB_VEL_FRAME_CHUNK as the library was compiled)"""
+    return int(lib().ib_vel_loss_frame_chunk())
+
+
+def vel_loss_workspace_bytes(rows, cols, rows_per_window) -> int:
+    return int(lib().ib_vel_loss_workspace(int(rows), int(cols), int(rows_per_window)))
+
+
+def vel_loss_partial(pred, x0, eps, workspace, t, wtab, utab, vtab, xtab, sqrt_ab, sqrt_1mab, rows_per_window: int, kind: str,
+                     cond_cols: int = 0, dpred=None):
+    """mse_loss_pred_partial plus the velocity term: the squared error of the frame difference of q = pred - target inside
+    each window of rows_per_window >= 2 rows, weighted by vtab[t] in the loss and the gradient and by xtab[t] in the report
+    (velocity_loss.VelocityLoss.tables).  Operands as mse_loss_pred_partial's; the workspace holds
+    vel_loss_workspace_bytes(rows, cols, rows_per_window) bytes and vel_loss_finalize finishes the launch."""
+    if kind not in PRED_KINDS:
+        raise HipError(f"vel_loss_partial: kind must be one of {tuple(PRED_KINDS)}, got {kind!r}")
+    dt = pred.dtype
+    rows, cols, ldp = _mat(pred, "pred", dt)
+    for ten, name in ((x0, "x0"), (eps, "eps")):
+        _req(ten, name, dt)
+        if not ten.is_contiguous() or ten.numel() != rows * cols:
+            raise HipError(f"vel_loss_partial: {name} must be contiguous with rows * cols elements")
+    ldd = 0
+    if dpred is not None:
+        r2, c2, ldd = _mat(dpred, "dpred", dt)
+        if (r2, c2) != (rows, cols):
+            raise HipError("vel_loss_partial: dpred shape mismatch")
+    rows_per_window, cond_cols = int(rows_per_window), int(cond_cols)
+    if rows_per_window < 2:
+        raise HipError(f"vel_loss_partial: a frame difference needs windows of at least 2 rows, got {rows_per_window}")
+    if rows % rows_per_window:
+        raise HipError(f"vel_loss_partial: rows ({rows}) must be a multiple of rows_per_window ({rows_per_window})")
+    if not 0 <= cond_cols < cols:
+        raise HipError(f"vel_loss_partial: cond_cols must lie in [0, {cols}), got {cond_cols}")
+    _req(t, "t", torch.int64, 1)
+    if not t.is_contiguous() or t.numel() != rows // rows_per_window:
+        raise HipError(f"vel_loss_partial: t must be a contiguous int64 vector of {rows // rows_per_window} windows")
+    _level_table(wtab, "wtab")
+    for tab, name in ((utab, "utab"), (vtab, "vtab"), (xtab, "xtab"), (sqrt_ab, "sqrt_ab"), (sqrt_1mab, "sqrt_1mab")):
+        _level_table(tab, name, wtab.numel())
+    wsb = workspace.numel() * workspace.element_size()
+    if wsb < vel_loss_workspace_bytes(rows, cols, rows_per_window):
+        raise HipError("vel_loss_partial: workspace too small")
+    _check(lib().ib_vel_loss_partial(_ptr(pred), ldp, _ptr(x0), _ptr(eps), _ptr(dpred), ldd, _ptr(t), _ptr(wtab), _ptr(utab),
+                                     _ptr(vtab), _ptr(xtab), _ptr(sqrt_ab), _ptr(sqrt_1mab), wtab.numel(), rows_per_window,
+                                     _ptr(workspace), wsb, rows, cols, cond_cols, PRED_KINDS[kind], dtype_code(dt),
+                                     stream_ptr()), "ib_vel_loss_partial")
+
+
+def vel_loss_finalize(workspace, result, t, n_levels: int, rows: int, cols: int, cond_cols: int, rows_per_window: int,
+                      accum=None):
+    """result, fp32 [VEL_RESULT_LEN], by the VEL_R_* places: the optimised loss, the unweighted eps-MSE with its band sums and
+    window counts (laid out as mse_loss_weighted_finalize's result), the weighted MSE term, the velocity term, the velocity
+    error in x0 units and its band sums; accum (float64 [VEL_RESULT_LEN], optional) += the same.  rows, cols, cond_cols and
+    rows_per_window are the partial launch's."""
+    _req(result, "result", torch.float32)
+    if result.numel() < VEL_RESULT_LEN or not result.is_contiguous():
+        raise HipError(f"vel_loss_finalize: result must hold {VEL_RESULT_LEN} contiguous fp32 values")
+    rows, cols, cond_cols, rows_per_window, n_levels = int(rows), int(cols), int(cond_cols), int(rows_per_window), int(n_levels)
+    if rows_per_window < 2 or rows < 1 or rows % rows_per_window or not 0 <= cond_cols < cols or n_levels < 1:
+        raise HipError(f"vel_loss_finalize: n_levels >= 1, windows of >= 2 rows, rows a multiple of them and 0 <= cond_cols < "
+                       f"cols required, got {n_levels}, {rows_per_window}, {rows}, {cond_cols}, {cols}")
+    _req(t, "t", torch.int64, 1)
+    if not t.is_contiguous() or t.numel() != rows // rows_per_window:
+        raise HipError(f"vel_loss_finalize: t must be a contiguous int64 vector of {rows // rows_per_window} windows")
+    if accum is not None:
+        _req(accum, "accum", torch.float64)
+        if accum.numel() < VEL_RESULT_LEN or not accum.is_contiguous():
+            raise HipError(f"vel_loss_finalize: accum must hold {VEL_RESULT_LEN} contiguous float64 values")
+    wsb = workspace.numel() * workspace.element_size()
+    if wsb < vel_loss_workspace_bytes(rows, cols, rows_per_window):
+        raise HipError("vel_loss_finalize: workspace too small")
+    _check(lib().ib_vel_loss_finalize(_ptr(workspace), wsb, _ptr(t), n_levels, _ptr(result), _ptr(accum), rows, cols, cond_cols,
+                                      rows_per_window, stream_ptr()), "ib_vel_loss_finalize")
 
 
 # --------------------------------------------------------------------------------------------
